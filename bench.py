@@ -8,12 +8,19 @@ One "step" = forward + L1 + backward + Adam (+ StepLR tick) over one synthetic b
 Workload (default --config c2) = BASELINE.json configs[1]: GF-2-shaped 4-band 32x32 MS / 128x128 PAN, K=4 stages, 32 pairs per
 GPU, executed in FAITHFUL mode (all K LGTs run forward like the reference; backward over the live graph).  Weak scaling: per-GPU
 batch fixed.  --config c3 / c5 run BASELINE configs[2] / [4] (8 bands; parity-test cases that a driver run can also record).
-Prints ONE JSON line on rank 0 (contract in the task description), including
-  roofline     -- the dominant kernel timed live with HIP events on its launch stream (lg_prof_*), against its roof; `traffic`
-                  is read from the committed PMC summary of the same command (profiles/r02_bench_bs32_pmc_hbm.csv)
+Prints ONE JSON line on rank 0: metric, value (pairs/s), unit, higher_is_better, dtype, ms_per_step (one timed step) and the run's
+shape.  A plain run does only that: set-up, --warmup steps, --steps timed steps, the outputs (--dump-outputs), the line.
+--full adds every other measurement, all of them after the timed steps except the first:
+  roofline     -- the dominant kernel timed live with HIP events on its launch stream (lg_prof_*) inside the timed region, against
+                  its roof; `traffic` is read from the committed PMC summary of the same command (profiles/rNN_bench_*_pmc_hbm.csv)
+  live_mode, overlap_dead_mode, bf16_mode, roofline_by_kernel, c3_mode / c5_mode -- side measurements, NOT `value`
   eval_forward -- eval-mode forward pairs/s on the same batch (faithful and live), SURVEY 8d
   cpu_baseline -- the oracle's CPU train step at the same batch size and its B=1 eval forward (kind "port") on this host's cores,
                   bounded sample (rank 0, N=1 only), with the CPU model string
+--dump-outputs DIR writes what the last timed step left to its caller (rank 0): DIR/loss.npy (float64) and DIR/weights.npy (every
+parameter after its Adam update, float32, flattened in state_dict order).  Inputs and initial weights are seeded: the same arguments
+give the same inputs in every run, so two builds compare output for output.  The weights repeat bitwise from run to run; the loss
+is summed with float atomics across workgroups and repeats to fp32 rounding (a few 1e-7 relative).
 """
 import argparse
 import ctypes
@@ -262,6 +269,16 @@ def cpu_baseline(cores, config):
                                      sample='3 timed eval forwards (faithful), configs[0]: C=4, 128x128 PAN, K=4, batch 1'))
 
 
+def dump_outputs(path, eng, net):
+    """what the last timed step returned to its caller: the loss and every parameter after the Adam update (state_dict order)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    np.save(os.path.join(path, 'loss.npy'), np.array([eng._loss.item()], dtype=np.float64))
+    weights = torch.cat([v.detach().reshape(-1).float().cpu() for v in net.state_dict().values()])
+    np.save(os.path.join(path, 'weights.npy'), weights.numpy())
+
+
 def main():
     global C, K, H, B_PER_GPU, E, P0
     ap = argparse.ArgumentParser()
@@ -269,14 +286,19 @@ def main():
     ap.add_argument('--steps', type=int, default=50)   # 0.3 s timed region at configs[1] (20 steps were 0.14 s)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--config', default='c2', choices=sorted(CONFIGS), help='c2 = BASELINE configs[1] (the metric; default); c3 / c5 = the 8-band configs')
-    ap.add_argument('--prof-kernel', default='ffn', help='kernel timed live for the roofline object (default: the dominant one)')
+    ap.add_argument('--prof-kernel', default=None,
+                    help='kernel timed live for the roofline object (default: the dominant one, ffn, with --full; none otherwise)')
     ap.add_argument('--mode', default='faithful', choices=['faithful', 'live', 'chained'],
                     help="'faithful' = the reference's graph (headline); 'live' / 'chained' are labelled non-headline variants")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-live', action='store_true', help='skip the side measurements (profiling runs)')
+    ap.add_argument('--full', action='store_true', help='also the roofline and every side measurement (default: the headline only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the last timed step\'s loss and updated weights as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-live', action='store_true', help='with --full: skip the side measurements (profiling runs)')
     ap.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'],
                     help="fp32: parity mode (default).  bf16: saved/hidden FFN activations of the backward stored as bf16")
     args = ap.parse_args()
+    if args.prof_kernel is None:
+        args.prof_kernel = 'ffn' if args.full else 'none'
     C, K, H, B_PER_GPU, label = CONFIGS[args.config]
     E, P0 = 4 * C, H * H
 
@@ -389,7 +411,9 @@ def main():
         _lib.check(L.lg_prof_read(ctypes.byref(tot_ms), ctypes.byref(n_l)), 'lg_prof_read')
         L.lg_prof_disable()
     loss = float(eng._loss.item()) * world if world == 1 else None
-    side = world == 1 and not args.no_live
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, net)
+    side = world == 1 and args.full and not args.no_live
     n_side = max(5, args.steps // 2)
     # side measurement (NOT `value`): the same train step with the K-1 dead LGT forwards skipped -- bit-identical outputs,
     # gradients and weights (tests/test_gpu_fullsize.py), i.e. what a user of this framework can run instead
@@ -532,8 +556,9 @@ def main():
                    dtype='f32 (GEMMs and the local mixer: split 16-bit MFMA -- f16 pairs in the forward FFN, the W2 products of its backward and P V, bf16 triples elsewhere -- fp32 accumulate; fp32-equivalent)' if args.precision == 'fp32'
                          else 'bf16 / f16 MFMA (FFN, local mixer) + bf16 saved activations, f32 elsewhere', data='synthetic',
                    config=dict(workload=label + ', train step = fwd + L1 + bwd + Adam + StepLR tick', mode=args.mode,
-                               global_batch=B_PER_GPU * world, parallelism=f'dp{world}', dropout=True),
-                   roofline=roof)
+                               global_batch=B_PER_GPU * world, parallelism=f'dp{world}', dropout=True))
+        if args.full or kid:
+            out['roofline'] = roof
         out['watchdog_s'] = wd
         if world > 1 or forced_pg:
             bk = eng.buckets[False] if eng.buckets else None
@@ -559,7 +584,7 @@ def main():
         if others is not None:
             out['c3_mode'] = others['c3']
             out['c5_mode'] = others['c5']
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(host_cores(), args.config)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -25,7 +25,7 @@ env = dict(os.environ, LGTEUN_DDP_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0'
 for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'LG_DDP_OVERLAP'):
     env.pop(k, None)
 cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1', '--master-port', str(port),
-       os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-live']
+       os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-live']
 with open(os.path.join(outdir, 'bench2.out'), 'w') as fo, open(os.path.join(outdir, 'bench2.err'), 'w') as fe:
     try:
         rc = subprocess.run(cmd, stdout=fo, stderr=fe, env=env, cwd=ROOT, timeout=600).returncode

@@ -147,37 +147,37 @@ def test_metrics_reproduce_reference_golden_values(manifest):
         assert np.allclose(got, g['metrics'], rtol=1e-12, atol=0), (name, got, g['metrics'])
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference'), reason='needs the reference tree (build container only)')
 def test_reference_checkpoint_converter(tmp_path):
-    """a checkpoint written the reference's way (pickled module objects, base_model.py:354-369) converts to a plain
-    state_dict that the product module loads bit-exactly"""
+    """a checkpoint written the reference's way (pickled module objects, base_model.py:354-369; tests/golden/ref_checkpoint_c4_k2_iter7.pth,
+    written by the reference through tools/gen_goldens.py) converts to a plain state_dict that the product module loads bit-exactly"""
     import subprocess
     import sys
     import lgteun_amd
     from lgteun_amd.compat import Config
-    src, dst = tmp_path / 'model_iter_7.pth', tmp_path / 'model_iter_7.state.pth'
-    gen = (
-        "import sys, torch; sys.path.insert(0, r'%s/tools'); from _ref_import import import_reference; R = import_reference();"
-        "torch.manual_seed(3); net = R.Pansharpening(R.Config(ms_chans=4), None, stage=2);"
-        "torch.save({'core_module': net, 'iter_num': 7}, r'%s')" % (ROOT, src))
-    subprocess.run([sys.executable, '-W', 'ignore', '-c', gen], check=True)
-    subprocess.run([sys.executable, '-W', 'ignore', os.path.join(ROOT, 'tools', 'convert_checkpoint.py'), str(src), str(dst)], check=True)
+    src, dst = os.path.join(ROOT, 'tests', 'golden', 'ref_checkpoint_c4_k2_iter7.pth'), tmp_path / 'model_iter_7.state.pth'
+    subprocess.run([sys.executable, '-W', 'ignore', os.path.join(ROOT, 'tools', 'convert_checkpoint.py'), src, str(dst)], check=True, cwd=tmp_path)
     ck = torch.load(dst, weights_only=True)              # reference-free: plain tensors only
     assert ck['iter_num'] == 7
+    assert list(ck['core_module']) == lgteun_amd.canonical_names(4, 2)
     net = lgteun_amd.Pansharpening(Config(ms_chans=4), None, stage=2)
     net.load_state_dict(ck['core_module'])
     for k, v in net.state_dict().items():
         assert torch.equal(v, ck['core_module'][k]), k
 
 
-@pytest.mark.skipif(not os.path.isfile('/root/reference/configs/unlg_former.py'), reason='needs the reference tree (build container only)')
-def test_reference_config_file_builds_the_model(tmp_path):
-    """the reference's own entry config (configs/unlg_former.py:23 model_type, :92-94 model_cfg, :82-86 optimiser / schedule)
-    loads through Config.fromfile -> build_model exactly as main.py:90 does, and yields the canonical parameter surface"""
+def test_reference_config_file_builds_the_model(tmp_path, manifest):
+    """the reference's own entry config (configs/unlg_former.py:23 model_type, :92-94 model_cfg, :82-86 optimiser / schedule; its
+    values are tests/golden/ref_config_unlg_former.json, one Python literal per name) loads through Config.fromfile -> build_model
+    exactly as main.py:90 does, and yields the canonical parameter surface"""
+    import json
     import logging
     import lgteun_amd
     from lgteun_amd.compat import Config
-    cfg = Config.fromfile('/root/reference/configs/unlg_former.py')
+    with open(os.path.join(ROOT, 'tests', 'golden', 'ref_config_unlg_former.json')) as f:
+        values = json.load(f)
+    cfg_file = tmp_path / 'unlg_former.py'
+    cfg_file.write_text(''.join(f'{k} = {v}\n' for k, v in values.items()))
+    cfg = Config.fromfile(str(cfg_file))
     assert cfg.model_type == 'UnlgFormer' and cfg.ms_chans == 8 and cfg.model_cfg['core_module']['stage'] == 2
     cfg.work_dir = str(tmp_path)                       # the file's own work_dir is relative to the author's checkout
     runner = lgteun_amd.build_model(cfg.model_type, cfg, logging.getLogger('cfgtest'), None, None, None)

@@ -76,7 +76,7 @@ def test_fused_train_step_gradients_match_autograd_path(manifest):
     assert float(eng.gflat[a:b].abs().max()) == 0.0
 
 
-def test_three_train_iterations_vs_reference_runner(manifest):
+def test_three_train_iterations_vs_reference_runner(manifest, tmp_path):
     """UnlgFormer.train_iter x3 with fused Adam + StepLR-per-iteration vs the reference runner's losses / weights."""
     import logging
     import lgteun_amd
@@ -84,7 +84,7 @@ def test_three_train_iterations_vs_reference_runner(manifest):
     from helpers import state_shapes
     m = manifest['train3_c4_k2_p32']
     g = load_gold('train3_c4_k2_p32')
-    cfg = Config(dict(ms_chans=4, work_dir='/tmp/lgteun_test', datas='GF-2', cuda=True, max_iter=3, bit_depth=11,
+    cfg = Config(dict(ms_chans=4, work_dir=str(tmp_path), datas='GF-2', cuda=True, max_iter=3, bit_depth=11,
                       loss_cfg={'rec_loss': dict(type='l1', w=1.)},
                       optim_cfg={'core_module': dict(type='Adam', betas=(0.9, 0.999), lr=m['lr'])},
                       sched_cfg=dict(step_size=m['step_size'], gamma=m['gamma']),

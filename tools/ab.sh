@@ -7,7 +7,7 @@ PK=ffn
 if [ "$1" = "--prof-kernel" ]; then PK=$2; shift 2; fi
 for round in $(seq 1 ${AB_ROUNDS:-3}); do
   for lib in "$@"; do
-    LGTEUN_HIP_LIB=$ROOT/$lib python $ROOT/bench.py --no-cpu-baseline --no-live --steps 30 --warmup 5 --prof-kernel $PK $AB_ARGS 2>/dev/null | tail -1 | \
+    LGTEUN_HIP_LIB=$ROOT/$lib python $ROOT/bench.py --full --no-cpu-baseline --no-live --steps 30 --warmup 5 --prof-kernel $PK $AB_ARGS 2>/dev/null | tail -1 | \
       python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$lib', 'ms/step', d['ms_per_step'], 'kernel_us', d['roofline']['avg_launch_us'])"
   done
 done

@@ -1,25 +1,43 @@
 """Convert a reference-era checkpoint to a plain state_dict file.
 
 The reference saves whole pickled module objects: `torch.save({'core_module': <models.unlg_former.Pansharpening>,
-'iter_num': n})` (models/base/base_model.py:354-369), so its checkpoints can only be unpickled where the reference's
-classes are importable -- i.e. in the build container with /root/reference (this tool uses tools/_ref_import.py).
-The output is a reference-free file: {'core_module': OrderedDict(name -> tensor), 'iter_num': n} that
+'iter_num': n})` (models/base/base_model.py:354-369), so its checkpoints name the reference's classes.  This tool does not need
+them: every class the unpickler cannot import is replaced by an empty torch.nn.Module subclass of the same name, which takes the
+pickled module state (parameters, buffers, submodules) as it is, so its state_dict() lists the names and tensors the reference's
+module would.  The output is a reference-free file: {'core_module': OrderedDict(name -> tensor), 'iter_num': n} that
 `lgteun_amd` loads anywhere:  runner.load_checkpoint(path)  /  module.load_state_dict(ckpt['core_module']).
 
     python tools/convert_checkpoint.py model_iter_255000.pth model_iter_255000.state.pth
 """
-import os
+import pickle
 import sys
+import types
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+_STAND_INS = {}
+
+
+def _stand_in(module, name):
+    """an empty nn.Module class named like the missing one: unpickling fills its __dict__ (nn.Module.__setstate__)"""
+    if (module, name) not in _STAND_INS:
+        _STAND_INS[module, name] = type(name, (torch.nn.Module,), {'__module__': module})
+    return _STAND_INS[module, name]
+
+
+class _Unpickler(pickle.Unpickler):
+    def find_class(self, module, name):
+        try:
+            return super().find_class(module, name)
+        except (ImportError, AttributeError):
+            return _stand_in(module, name)
+
+
+_PICKLE = types.SimpleNamespace(__name__='convert_checkpoint_pickle', Unpickler=_Unpickler, load=lambda f, **kw: _Unpickler(f, **kw).load())
 
 
 def convert(src, dst):
-    from _ref_import import import_reference
-    import_reference()                      # makes models.unlg_former.* resolvable for the unpickler
-    ckpt = torch.load(src, map_location='cpu', weights_only=False)
+    ckpt = torch.load(src, map_location='cpu', weights_only=False, pickle_module=_PICKLE)
     out = {}
     for k, v in ckpt.items():
         if hasattr(v, 'state_dict'):

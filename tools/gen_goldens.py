@@ -202,8 +202,28 @@ def round5():
     print('dataset_utils.npz:', len(out), 'arrays')
 
 
+def round7(R):
+    """inputs of the two boundary checks that once read the reference tree itself (tests/test_boundary_cpu.py): a checkpoint written
+    the reference's way (whole pickled module objects, base_model.py:354-369; C=4, K=2, torch seed 3, iteration 7) and the values its
+    entry config (configs/unlg_former.py) evaluates to, one Python literal per name"""
+    import ast
+    import runpy
+    import types
+    from _ref_import import REF
+    torch.manual_seed(3)
+    net = R.Pansharpening(R.Config(ms_chans=4), None, stage=2)
+    torch.save({'core_module': net, 'iter_num': 7}, os.path.join(GOLD, 'ref_checkpoint_c4_k2_iter7.pth'))
+    cfg = runpy.run_path(os.path.join(REF, 'configs', 'unlg_former.py'))
+    vals = {k: repr(v) for k, v in cfg.items() if not k.startswith('__') and not callable(v) and not isinstance(v, types.ModuleType)}
+    assert all(ast.literal_eval(r) == cfg[k] for k, r in vals.items())
+    with open(os.path.join(GOLD, 'ref_config_unlg_former.json'), 'w') as f:
+        json.dump(vals, f, indent=1, sort_keys=True)
+    print('ref_checkpoint_c4_k2_iter7.pth, ref_config_unlg_former.json:', len(vals), 'config names')
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--only-r7', action='store_true', help='write only the round-7 fixtures (a reference checkpoint, its config\'s values)')
     ap.add_argument('--only-r5', action='store_true', help='write only the round-5 fixture (the reference\'s dataset/utils.py functions)')
     ap.add_argument('--check', action='store_true')
     ap.add_argument('--only-r3', action='store_true', help='write only the round-3 fixtures (fp64 gradients of the cancelling-sum kinds)')
@@ -219,6 +239,9 @@ def main():
     torch.set_num_threads(8)
     R = import_reference()
     manifest = {}
+    if args.only_r7:
+        round7(R)
+        return
     if args.only_r4:
         with open(os.path.join(GOLD, 'manifest.json')) as f:
             manifest = json.load(f)
@@ -365,6 +388,7 @@ def main():
     round3(R, manifest)
     round4(R, manifest)
     round5()
+    round7(R)
     print('wrote', GOLD)
 
 
