@@ -202,6 +202,31 @@ int lg_op_data_step_bwd(const lg_plan* plan, const float* params, float* grads, 
 int lg_op_lgt_bwd(const lg_plan* plan, const float* params, float* grads, int32_t stage, const float* z, const float* dout, float* dz,
                   void* workspace, size_t workspace_bytes, int32_t B, int32_t flags, uint64_t seed, void* stream);
 
+/* ---- evaluation indices of lgteun_amd/metrics.py (reference models/base/metrics.py:22-182, 271-333, 409-425) in fp64 on the device ----
+ * Same definitions as the host functions; only the order of summation differs.  Every input element is first multiplied by `scale` in
+ * fp32 (2^bit_depth - 0.5 for normalised inputs, as data_denormalize does; 1 for digital numbers), then widened to fp64.  Reductions
+ * are per-workgroup partials in the workspace plus a fixed-order pass (no atomics): repeated calls give the same bits, and row b of a
+ * batch equals the row of image b scored alone.  Shapes: 2 <= C <= LG_IQA_MAX_BANDS; H, W >= LG_IQA_SSIM_TAPS (one SSIM window); the
+ * no-reference indices also need H, W >= LG_IQA_QNR_BLOCK and multiples of LG_IQA_RATIO. */
+#define LG_IQA_PEAK 2047.5     /* dynamic range of PSNR / SSIM (11-bit data)          metrics.PEAK */
+#define LG_IQA_SSIM_TAPS 11    /* SSIM: Gaussian window taps                          metrics.SSIM_TAPS */
+#define LG_IQA_SSIM_SIGMA 1.5  /*       and its sigma                                 metrics.SSIM_SIGMA */
+#define LG_IQA_Q_BLOCK 8       /* Q: box window of the reduced-resolution pass        metrics.Q_BLOCK */
+#define LG_IQA_RATIO 4         /* ERGAS ratio = PAN / MS resolution                   metrics.ERGAS_RATIO */
+#define LG_IQA_QNR_BLOCK 32    /* Q window of D_lambda / D_s                          metrics.QNR_BLOCK */
+#define LG_IQA_MTF_TAPS 41     /* PAN low-pass (MTF-matched Gaussian) taps            metrics.MTF_TAPS */
+#define LG_IQA_MTF_GAIN 0.15   /*   and its gain at the MS Nyquist frequency          metrics.MTF_GAIN_PAN */
+#define LG_IQA_MAX_BANDS 16
+/* bytes of workspace a call on [B, C, H, W] images needs (no_ref = 0: lg_iqa_ref, 1: lg_iqa_no_ref); 0 for a shape the indices
+ * are not defined for */
+size_t lg_iqa_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t no_ref);
+/* metrics.ref_evaluate of every image: pred, gt [B,C,H,W] fp32 -> out [B,5] fp64 = PSNR, SSIM, Q, SAM, ERGAS */
+int lg_iqa_ref(const float* pred, const float* gt, double* out, int32_t B, int32_t C, int32_t H, int32_t W, float scale,
+               void* workspace, size_t workspace_bytes, void* stream);
+/* metrics.no_ref_evaluate of every image: pred [B,C,H,W], pan [B,1,H,W], ms [B,C,H/4,W/4] fp32 -> out [B,3] fp64 = D_lambda, D_s, QNR */
+int lg_iqa_no_ref(const float* pred, const float* pan, const float* ms, double* out, int32_t B, int32_t C, int32_t H, int32_t W,
+                  float scale, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

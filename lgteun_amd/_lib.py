@@ -120,6 +120,10 @@ SIGNATURES = {
                                 c_uint64, c_void_p]),
     'lg_op_block_bwd': (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_size_t, c_int32, c_void_p]),
+    'lg_iqa_workspace_bytes': (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    'lg_iqa_ref': (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_size_t, c_void_p]),
+    'lg_iqa_no_ref': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_size_t,
+                                c_void_p]),
 }
 
 

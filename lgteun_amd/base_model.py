@@ -10,6 +10,7 @@ import torch
 import torch.nn as nn
 from torch.optim import SGD, Adam, AdamW, RMSprop, lr_scheduler
 
+from . import device_metrics as dmt
 from . import metrics as mtc
 from .compat import Timer, mkdir_or_exist
 from .losses import get_loss_module
@@ -208,8 +209,14 @@ class Base_model:
         """evaluation (base_model.py:267-352).  ref=True: reduced-resolution set, PSNR / SSIM / Q / SAM / ERGAS against the target,
         `<metric>_mean` / `<metric>_std` lists in self.eval_results like the reference.  ref=False: the full-resolution set, no target:
         D_lambda / D_s / QNR from the fused image, the PAN and the MS input (lgteun_amd/metrics.py: parity-unpinned).  Inputs are always normalised; arrays are brought back
-        to digital numbers before the metrics / the TIFF writer only with cfg.norm_input (base_model.py:296,311-316)."""
+        to digital numbers before the metrics / the TIFF writer only with cfg.norm_input (base_model.py:296,311-316).
+        cfg.eval_metrics: 'host' (default) scores every image with the float64 numpy functions of metrics.py; 'device' scores every batch
+        on the GPU (device_metrics.py: the same definitions in fp64 HIP kernels), keeps the rows there and copies them to the host once,
+        at the end -- the fused images leave the device only for the TIFF writer (save=True)."""
         from .dataset import save_image
+        metrics_on = self.cfg.get('eval_metrics', 'host')
+        if metrics_on not in ('host', 'device'):
+            raise ValueError(f"cfg.eval_metrics must be 'host' or 'device' (got {metrics_on!r})")
         loader = self.test_data_loader1 if ref else self.test_data_loader0
         for module in self.module_dict.values():
             module.eval()
@@ -237,19 +244,30 @@ class Base_model:
         smp = getattr(inner, 'sampler', None)
         own_idx = [int(i) for i in smp] if (sharded and isinstance(smp, ShardedSampler)) else None
         res, ids, seen_here = [], [], 0
+        dev_rows = []                     # eval_metrics = 'device': one [nb, k] float64 device tensor per batch
+        scale = float(2 ** self.cfg.bit_depth - .5) if denorm else 1.0
         for bi, input_batch in enumerate(loader or []):
             if self.world > 1 and not sharded and bi % self.world != self.rank:
                 continue
             input_batch = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in input_batch.items()}
             input_batch = data_normalize(input_batch, self.cfg.bit_depth)
-            out = to_np(self.get_model_output(input_batch))
-            if ref:
-                gt = to_np(input_batch['target'])
-                res.extend(mtc.ref_evaluate(out[i], gt[i]) for i in range(out.shape[0]))
-            else:                                                # full-resolution set: no target (base_model.py:330-334)
-                pan_np, lr_np = to_np(input_batch['input_pan']), to_np(input_batch['input_lr'])
-                res.extend(mtc.no_ref_evaluate(out[i], pan_np[i], lr_np[i]) for i in range(out.shape[0]))
-            nb = out.shape[0]
+            fused = self.get_model_output(input_batch)
+            nb = fused.shape[0]
+            if metrics_on == 'device':
+                if ref:
+                    dev_rows.append(dmt.ref_evaluate_batch(fused.contiguous(), input_batch['target'].contiguous(), scale))
+                else:
+                    dev_rows.append(dmt.no_ref_evaluate_batch(fused.contiguous(), input_batch['input_pan'].contiguous(),
+                                                              input_batch['input_lr'].contiguous(), scale))
+                out = to_np(fused) if save else None
+            else:
+                out = to_np(fused)
+                if ref:
+                    gt = to_np(input_batch['target'])
+                    res.extend(mtc.ref_evaluate(out[i], gt[i]) for i in range(nb))
+                else:                                            # full-resolution set: no target (base_model.py:330-334)
+                    pan_np, lr_np = to_np(input_batch['input_pan']), to_np(input_batch['input_lr'])
+                    res.extend(mtc.no_ref_evaluate(out[i], pan_np[i], lr_np[i]) for i in range(nb))
             if own_idx is not None:
                 ids.extend(('idx', own_idx[seen_here + i]) for i in range(nb))
             elif not sharded:
@@ -262,6 +280,8 @@ class Base_model:
                     # [C, H, W] for the writer (the reference hands its HWC array to a CHW writer, base_model.py:336: a
                     # transposed file; not reproduced)
                     save_image(osp.join(out_dir, f'{image_id}_mul_hat.tif'), np.moveaxis(out[i], -1, 0))
+        if dev_rows:
+            res = torch.cat(dev_rows).cpu().tolist()          # the one device-to-host copy of the pass
         latest = {}
         if self.world > 1:
             import torch.distributed as dist

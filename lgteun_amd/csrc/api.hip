@@ -643,6 +643,21 @@ extern "C" int lg_l1_loss(const float* out, const float* gt, float* dout, float*
 }
 
 // ------------------------------------------------------------------------------------------------
+// evaluation indices (k_iqa.hip)
+// ------------------------------------------------------------------------------------------------
+extern "C" size_t lg_iqa_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t no_ref) {
+    return iqa_workspace_bytes(B, C, H, W, no_ref);
+}
+extern "C" int lg_iqa_ref(const float* pred, const float* gt, double* out, int32_t B, int32_t C, int32_t H, int32_t W, float scale,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    return launch_iqa_ref(pred, gt, out, B, C, H, W, scale, workspace, workspace_bytes, (hipStream_t)stream);
+}
+extern "C" int lg_iqa_no_ref(const float* pred, const float* pan, const float* ms, double* out, int32_t B, int32_t C, int32_t H, int32_t W,
+                             float scale, void* workspace, size_t workspace_bytes, void* stream) {
+    return launch_iqa_no_ref(pred, pan, ms, out, B, C, H, W, scale, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Adam (torch.optim.Adam single-tensor semantics) over ranges of the flat buffers
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,

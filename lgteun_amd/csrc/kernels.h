@@ -2,6 +2,13 @@
 #pragma once
 #include "common.h"
 
+// ---------------- evaluation indices of lgteun_amd/metrics.py (k_iqa.hip; arguments validated before any HIP call) ----------------
+size_t iqa_workspace_bytes(int B, int C, int H, int W, int no_ref);
+int launch_iqa_ref(const float* pred, const float* gt, double* out, int B, int C, int H, int W, float scale, void* workspace,
+                   size_t workspace_bytes, hipStream_t s);
+int launch_iqa_no_ref(const float* pred, const float* pan, const float* ms, double* out, int B, int C, int H, int W, float scale,
+                      void* workspace, size_t workspace_bytes, hipStream_t s);
+
 // ---------------- data module (reference models/unlg_former.py:29-37,58-61) ----------------
 struct DwArgs {
     const float* in;    // [planes, hi, wi]

@@ -21,6 +21,7 @@ published definitions as well: Q on 32 x 32 windows, the PAN image brought to MS
 Nyquist frequency is the sensor's MTF value, then decimation.  The reference builds that filter with a 2-D window method on top of cv2 /
 scipy.ndimage and a per-satellite table; this is the separable Gaussian of the same MTF gain, so the family is PARITY-UNPINNED like SSIM / Q
 and is checked against brute-force evaluations of its definitions only.
+Device versions for whole batches (fp64 HIP kernels, tested against these functions): lgteun_amd/device_metrics.py.
 """
 import numpy as np
 from numpy.lib.stride_tricks import sliding_window_view
