@@ -147,6 +147,36 @@ int lg_adam_step(float* params, const float* grads, float* exp_avg, float* exp_a
                  int32_t n_ranges, int64_t max_range, int32_t step, float lr, float beta1, float beta2, float eps,
                  float grad_scale, void* stream);
 
+/* nn.MSELoss(mean) forward+backward (losses.py:19-40 with type 'l2'; unlg_former.py:99-104): the contract of lg_l1_loss with
+ * loss_accum[0] += sum (out-gt)^2 / N and dout = 2 (out-gt) * scale / N.   N = number of elements of the GLOBAL batch (DDP: pass
+ * n_global).  The sum is carried in fp64; loss_accum takes one float add per call.  dout is rounded as torch's MSE backward rounds it:
+ * (fl(2 / N) * (out-gt)) * scale. */
+int lg_l2_loss(const float* out, const float* gt, float* dout, float* loss_accum, int64_t n_local, int64_t n_global,
+               float scale, void* stream);
+
+/* One step of torch.optim's single-tensor Adam / AdamW / SGD / RMSprop (base_model.py:116-135 hands torch's keyword arguments
+ * through) over [begin,end) float ranges of the flat buffers, one launch.  ranges: DEVICE int64 pairs as for lg_adam_step; step is
+ * 1-based (bias corrections; the SGD momentum buffer of step 1 is the gradient itself).  Hyper-parameters per algorithm:
+ *   LG_OPT_ADAM, LG_OPT_ADAMW  h0 = beta1, h1 = beta2; flag LG_OPT_AMSGRAD; weight_decay is L2 (Adam) or decoupled (AdamW)
+ *                              state0 = exp_avg, state1 = exp_avg_sq, state2 = max_exp_avg_sq (amsgrad only)
+ *   LG_OPT_SGD                 h0 = momentum, h1 = dampening; flag LG_OPT_NESTEROV; state0 = momentum buffer (momentum != 0 only)
+ *   LG_OPT_RMSPROP             h0 = alpha, h1 = momentum; flag LG_OPT_CENTERED; eps is added after the square root
+ *                              state0 = square_avg, state1 = momentum buffer (momentum > 0 only), state2 = grad_avg (centered only)
+ * State buffers are caller-owned fp32 buffers laid out like params; those an option set does not use may be NULL.
+ * Gradients are read as grads * grad_scale.  The scalars are fp64, as torch holds them: 1 - beta, lr / bias_correction1 and 1 - lr *
+ * weight_decay are taken in fp64 and rounded to fp32 once.  Every op of torch's multi-tensor form is one rounding step of the kernel, so a
+ * step fed the same gradients gives the bits torch's device kernels give. */
+#define LG_OPT_ADAM 0
+#define LG_OPT_ADAMW 1
+#define LG_OPT_SGD 2
+#define LG_OPT_RMSPROP 3
+#define LG_OPT_AMSGRAD 1
+#define LG_OPT_NESTEROV 2
+#define LG_OPT_CENTERED 4
+int lg_optim_step(float* params, const float* grads, float* state0, float* state1, float* state2, const int64_t* ranges,
+                  int32_t n_ranges, int64_t max_range, int32_t step, int32_t algo, int32_t flags, double lr, double h0, double h1,
+                  double eps, double weight_decay, double grad_scale, void* stream);
+
 /* Live per-kernel timing: when enabled for `kernel_id`, every launch of that kernel is bracketed by hipEvents recorded on
  * the stream it is launched on.  lg_prof_read synchronises on the recorded events and returns the summed device time (ms)
  * and the number of launches since lg_prof_enable / lg_prof_reset.  Host-side event objects are the only thing the library

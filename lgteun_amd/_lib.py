@@ -6,7 +6,7 @@ product path raises -- the CPU restatement in oracle/ is test infrastructure onl
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('LGTEUN_HIP_LIB') or os.path.join(_HERE, '_lgteun_hip.so')   # override: diagnostic builds (tools/build_stamps.sh)
@@ -40,6 +40,8 @@ LG_VAR_FFN_XS = 1 << 13
 LG_VAR_ATTN_BF16X3 = 1 << 14
 LG_VAR_FFN_H3_RECOMPUTE = 1 << 15
 LG_VAR_ATTN_BWD_RESTATS = 1 << 16
+LG_OPT_ADAM, LG_OPT_ADAMW, LG_OPT_SGD, LG_OPT_RMSPROP = 0, 1, 2, 3      # lg_optim_step: algo
+LG_OPT_AMSGRAD, LG_OPT_NESTEROV, LG_OPT_CENTERED = 1, 2, 4             # lg_optim_step: flags
 LG_ABI_VERSION = 2   # include/lgteun_hip.h: checked against lg_abi_version() when the library is loaded
 
 
@@ -100,6 +102,9 @@ SIGNATURES = {
     'lg_l1_loss': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_float, c_void_p]),
     'lg_adam_step': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_float, c_float,
                                c_float, c_float, c_float, c_void_p]),
+    'lg_l2_loss': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_float, c_void_p]),
+    'lg_optim_step': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32,
+                                c_double, c_double, c_double, c_double, c_double, c_double, c_void_p]),
     'lg_op_resample': (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     'lg_op_data_step': (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                   c_void_p]),

@@ -1,6 +1,6 @@
 """Runner counterpart of reference models/base/base_model.py restricted to the hot path's callers:
 add_module :56, set_cuda :91 (one process per GPU + RCCL instead of nn.DataParallel), load_checkpoint :102,
-set_optim :116 (Adam -> fused HIP Adam), set_sched :137 (StepLR stepped EVERY iteration :197-199),
+set_optim :116 (Adam / AdamW / SGD / RMSprop -> their fused HIP steps), set_sched :137 (StepLR stepped EVERY iteration :197-199),
 train :164, test :267 (reference-based indices PSNR / SSIM / Q / SAM / ERGAS on the reduced-resolution set, the no-reference
 D_lambda / D_s / QNR on the full-resolution set), save :354 (same `train_out/` location; optimizer state added)."""
 import os.path as osp
@@ -123,27 +123,22 @@ class Base_model:
         self._load_modules(self._read_checkpoint(path, allow_pickle))
 
     def set_optim(self):
-        from .engine import FusedAdam
+        from .engine import FUSED_OPTIMIZERS
         optim_cfg = self.cfg.get('optim_cfg', {})
         for module_name, module in self.module_dict.items():
             if module_name in optim_cfg:
                 cfg = dict(optim_cfg[module_name])
                 typ = cfg.pop('type')
                 fused = cfg.pop('fused', True)
-                if typ == 'Adam':
-                    self.optim_dict[module_name] = (FusedAdam if fused else Adam)(module.parameters(), **cfg)
-                elif typ == 'RMSprop':
-                    self.optim_dict[module_name] = RMSprop(module.parameters(), **cfg)
-                elif typ == 'SGD':
-                    self.optim_dict[module_name] = SGD(module.parameters(), **cfg)
-                elif typ == 'AdamW':
-                    self.optim_dict[module_name] = AdamW(module.parameters(), **cfg)
-                else:
+                # every type the reference accepts has a fused class with torch's arithmetic; `fused=False` in the entry selects torch's own
+                torch_cls = {'Adam': Adam, 'RMSprop': RMSprop, 'SGD': SGD, 'AdamW': AdamW}
+                if typ not in torch_cls:
                     raise SystemExit(f'No such type optim:{typ}')
+                self.optim_dict[module_name] = (FUSED_OPTIMIZERS[typ] if fused else torch_cls[typ])(module.parameters(), **cfg)
             else:
                 self.optim_dict[module_name] = Adam(module.parameters(), betas=(0.9, 0.999), lr=1e-4)
             resume = getattr(self, '_resume_optim', None) or {}
-            if module_name in resume:                     # load_checkpoint ran first (main.py order): continue the Adam moments
+            if module_name in resume:                     # load_checkpoint ran first (main.py order): continue the optimizer state
                 self.optim_dict[module_name].load_state_dict(resume[module_name])
 
     def set_sched(self):

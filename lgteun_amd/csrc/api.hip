@@ -643,6 +643,71 @@ extern "C" int lg_l1_loss(const float* out, const float* gt, float* dout, float*
 }
 
 // ------------------------------------------------------------------------------------------------
+// L2 loss (nn.MSELoss, mean) forward + backward -- models/base/losses.py:19-40 with type 'l2'
+// ------------------------------------------------------------------------------------------------
+// k_l1's access pattern and reduction shape.  The squares are summed in fp64 and the workgroups meet in an fp64 slot of the library
+// (one per launch in flight, handed out round-robin), so loss_accum takes ONE float add per launch, by the workgroup that arrives
+// last: up to 256 float atomics on the scalar would each round at the loss's magnitude, in an order that changes from run to run.
+// dout = (fl(2 / n) d) scale, rounded after each product: the bits of torch's own MSE backward (norm * (input - target) * grad_output).
+#define LG_L2_SLOTS 64
+struct l2_slot { double acc; unsigned int arrived; unsigned int pad; };
+__device__ l2_slot g_l2_slots[LG_L2_SLOTS];
+
+__global__ __launch_bounds__(256) void k_l2(const float* __restrict__ out, const float* __restrict__ gt, float* __restrict__ dout,
+                                            float* loss_accum, long n, double inv_n, float norm, float scale, int slot_id) {
+    l2_slot* slot = &g_l2_slots[slot_id];
+    double part = 0.0;
+    const long n4 = n >> 2, stride = (long)gridDim.x * 256L;
+    const float4* __restrict__ o4 = reinterpret_cast<const float4*>(out);
+    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(gt);
+    float4* __restrict__ d4 = reinterpret_cast<float4*>(dout);
+    auto one = [&](float d) { part += (double)d * (double)d; return (norm * d) * scale; };
+    long i = blockIdx.x * 256L + threadIdx.x;
+    for (; i + 3 * stride < n4; i += 4 * stride) {
+        float4 a[4], b[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { a[u] = o4[i + u * stride]; b[u] = g4[i + u * stride]; }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            d4[i + u * stride] = make_float4(one(a[u].x - b[u].x), one(a[u].y - b[u].y), one(a[u].z - b[u].z), one(a[u].w - b[u].w));
+    }
+    for (; i < n4; i += stride) {
+        const float4 a = o4[i], b = g4[i];
+        d4[i] = make_float4(one(a.x - b.x), one(a.y - b.y), one(a.z - b.z), one(a.w - b.w));
+    }
+    for (long j = 4 * n4 + blockIdx.x * 256L + threadIdx.x; j < n; j += stride) dout[j] = one(out[j] - gt[j]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
+    __shared__ double sm[4];
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = part;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(&slot->acc, sm[0] + sm[1] + sm[2] + sm[3]);
+        __threadfence();
+        if (atomicAdd(&slot->arrived, 1u) == gridDim.x - 1) {       // every workgroup's sum is in: hand the slot back empty
+            __threadfence();
+            const double total = __longlong_as_double((long long)atomicExch((unsigned long long*)&slot->acc, 0ull));
+            atomicExch(&slot->arrived, 0u);
+            atomicAdd(loss_accum, (float)(total * inv_n));
+        }
+    }
+}
+
+extern "C" int lg_l2_loss(const float* out, const float* gt, float* dout, float* loss_accum, int64_t n_local, int64_t n_global,
+                          float scale, void* stream) {
+    if (!out || !gt || !dout || !loss_accum || n_local <= 0 || n_global <= 0) { lg_set_error("l2_loss: invalid argument"); return -1; }
+    if (((uintptr_t)out | (uintptr_t)gt | (uintptr_t)dout) & 15) { lg_set_error("l2_loss: tensors must be 16-byte aligned"); return -1; }
+    int grid = (int)((n_local / 4 + 255) / 256);
+    if (grid > 256) grid = 256;
+    if (grid < 1) grid = 1;
+    static std::atomic<unsigned> next_slot{0};
+    k_l2<<<grid, 256, 0, (hipStream_t)stream>>>(out, gt, dout, loss_accum, n_local, 1.0 / (double)n_global, (float)(2.0 / (double)n_global), scale,
+                                                (int)(next_slot.fetch_add(1) % LG_L2_SLOTS));
+    LG_CHECK_LAUNCH();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // evaluation indices (k_iqa.hip)
 // ------------------------------------------------------------------------------------------------
 extern "C" size_t lg_iqa_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t no_ref) {
@@ -687,6 +752,140 @@ extern "C" int lg_adam_step(float* params, const float* grads, float* exp_avg, f
     dim3 grid(gx, n_ranges);
     k_adam<<<grid, 256, 0, (hipStream_t)stream>>>(params, grads, exp_avg, exp_avg_sq, ranges, (float)(lr / bc1), beta1, beta2,
                                                    (float)(1.0 / sqrt(bc2)), eps, grad_scale);
+    LG_CHECK_LAUNCH();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// torch.optim single-tensor steps (Adam / AdamW / SGD / RMSprop with their options) over ranges of the flat buffers
+// (base_model.py:116-135 passes torch's keyword arguments through).  One instance per option set: ALGO and the bits of OPT are
+// compile-time, so no element branches on an option.  The operation order is torch's (_single_tensor_adam / _sgd / _rmsprop).
+// ------------------------------------------------------------------------------------------------
+enum { OPT_WD = 1, OPT_ALT = 2, OPT_MOM = 4, OPT_FIRST = 8 };   // ALT: amsgrad (Adam, AdamW) / nesterov (SGD) / centered (RMSprop)
+struct optim_args {
+    float lr;          // Adam, AdamW: lr / (1 - beta1^step)
+    float h0, h1;      // Adam, AdamW: beta1, beta2; SGD: momentum, dampening; RMSprop: alpha, momentum
+    float c0, c1;      // 1 - h0, 1 - h1: taken in fp64 and rounded once, like torch's Python-side `1 - beta`
+    float eps, wd, gscale;
+    float bc2_sqrt;    // Adam, AdamW: sqrt(1 - beta2^step)
+    float decay;       // AdamW: 1 - lr * weight_decay
+};
+
+// Rounding: every torch op of the multi-tensor (foreach) form the device route runs is one rounding step here -- `a * s`, `b * c`,
+// `b / c`, sqrt are rounded on their own, `a + s * x` (add with alpha, addcmul, addcdiv, lerp) is one fused multiply-add as the
+// compiler contracts it in torch's kernels -- so that a run fed the same gradients lands on the same bits as `fused=False`.
+// Contraction is switched off for the kernel and every fma is written out.
+#ifndef LG_OPT_FMA
+#define LG_OPT_FMA(a, b, c) __builtin_fmaf(a, b, c)
+#endif
+template <int ALGO, int OPT>
+__global__ __launch_bounds__(256) void k_optim(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0,
+                                               float* __restrict__ s1, float* __restrict__ s2, const int64_t* __restrict__ ranges,
+                                               optim_args a) {
+#pragma clang fp contract(off)
+    const int64_t lo = ranges[2 * blockIdx.y], hi = ranges[2 * blockIdx.y + 1];
+    for (int64_t i = lo + blockIdx.x * 256L + threadIdx.x; i < hi; i += (int64_t)gridDim.x * 256L) {
+        float pi = p[i];
+        float gi = g[i] * a.gscale;
+        if constexpr (ALGO == LG_OPT_ADAMW) pi = pi * a.decay;                       // _foreach_mul_(params, 1 - lr * weight_decay)
+        else if constexpr ((OPT & OPT_WD) != 0) gi = LG_OPT_FMA(a.wd, pi, gi);       // _foreach_add(grads, params, alpha=weight_decay)
+        if constexpr (ALGO == LG_OPT_ADAM || ALGO == LG_OPT_ADAMW) {
+            float mi = s0[i];
+            mi = LG_OPT_FMA(a.c0, gi - mi, mi);                                      // _foreach_lerp_(exp_avgs, grads, 1 - beta1)
+            const float vb = s1[i] * a.h1;                                           // _foreach_mul_(exp_avg_sqs, beta2)
+            float vi = LG_OPT_FMA(a.c1, gi * gi, vb);                                // _foreach_addcmul_(exp_avg_sqs, grads, grads, 1 - beta2)
+            s0[i] = mi;
+            s1[i] = vi;
+            if constexpr ((OPT & OPT_ALT) != 0) { vi = fmaxf(s2[i], vi); s2[i] = vi; }
+            float denom = sqrtf(vi) / a.bc2_sqrt;
+            denom = denom + a.eps;
+            pi = LG_OPT_FMA(-a.lr, mi / denom, pi);                                  // _foreach_addcdiv_(params, exp_avgs, denom, -step_size)
+        } else if constexpr (ALGO == LG_OPT_SGD) {
+            if constexpr ((OPT & OPT_MOM) != 0) {
+                float bi;
+                if constexpr ((OPT & OPT_FIRST) != 0) bi = gi;                       // torch: the first buffer is a clone of the gradient
+                else bi = LG_OPT_FMA(a.c1, gi, s0[i] * a.h0);                        // _foreach_mul_(bufs, momentum); _foreach_add_(bufs, grads, alpha=1 - dampening)
+                s0[i] = bi;
+                if constexpr ((OPT & OPT_ALT) != 0) gi = LG_OPT_FMA(a.h0, bi, gi);   // _foreach_add_(grads, bufs, alpha=momentum)
+                else gi = bi;
+            }
+            pi = LG_OPT_FMA(-a.lr, gi, pi);                                          // _foreach_add_(params, grads, alpha=-lr)
+        } else {
+            const float vb = s0[i] * a.h0;                                           // _foreach_mul_(square_avgs, alpha)
+            const float vi = LG_OPT_FMA(a.c0, gi * gi, vb);                          // _foreach_addcmul_(square_avgs, grads, grads, value=1 - alpha)
+            s0[i] = vi;
+            float avg;
+            if constexpr ((OPT & OPT_ALT) != 0) {
+                float ci = s2[i];
+                ci = LG_OPT_FMA(a.c0, gi - ci, ci);                                  // _foreach_lerp_(grad_avgs, grads, 1 - alpha)
+                s2[i] = ci;
+                avg = sqrtf(LG_OPT_FMA(-1.0f, ci * ci, vi));                         // _foreach_addcmul(square_avgs, grad_avgs, grad_avgs, value=-1), sqrt
+            } else {
+                avg = sqrtf(vi);
+            }
+            avg = avg + a.eps;
+            if constexpr ((OPT & OPT_MOM) != 0) {
+                const float bi = LG_OPT_FMA(1.0f, gi / avg, s1[i] * a.h1);           // _foreach_mul_(bufs, momentum); _foreach_addcdiv_(bufs, grads, avg)
+                s1[i] = bi;
+                pi = LG_OPT_FMA(-a.lr, bi, pi);                                      // _foreach_add_(params, bufs, alpha=-lr)
+            } else {
+                pi = LG_OPT_FMA(-a.lr, gi / avg, pi);                                // _foreach_addcdiv_(params, grads, avg, value=-lr)
+            }
+        }
+        p[i] = pi;
+    }
+}
+
+template <int ALGO, int OPT>
+static void launch_optim(dim3 grid, hipStream_t st, float* p, const float* g, float* s0, float* s1, float* s2, const int64_t* ranges,
+                         const optim_args& a) {
+    k_optim<ALGO, OPT><<<grid, 256, 0, st>>>(p, g, s0, s1, s2, ranges, a);
+}
+
+extern "C" int lg_optim_step(float* params, const float* grads, float* state0, float* state1, float* state2, const int64_t* ranges,
+                             int32_t n_ranges, int64_t max_range, int32_t step, int32_t algo, int32_t flags, double lr, double h0, double h1,
+                             double eps, double weight_decay, double grad_scale, void* stream) {
+    if (!params || !grads || !ranges || n_ranges <= 0 || step < 1 || algo < LG_OPT_ADAM || algo > LG_OPT_RMSPROP ||
+        (flags & ~(LG_OPT_AMSGRAD | LG_OPT_NESTEROV | LG_OPT_CENTERED))) { lg_set_error("optim_step: invalid argument"); return -1; }
+    const bool adam = algo == LG_OPT_ADAM || algo == LG_OPT_ADAMW;
+    const int own = adam ? LG_OPT_AMSGRAD : (algo == LG_OPT_SGD ? LG_OPT_NESTEROV : LG_OPT_CENTERED);
+    if (flags & ~own) { lg_set_error("optim_step: the flag belongs to another algorithm"); return -1; }
+    int opt = (weight_decay != 0.0 && algo != LG_OPT_ADAMW ? OPT_WD : 0) | (flags ? OPT_ALT : 0);
+    if (algo == LG_OPT_SGD && h0 != 0.0) opt |= OPT_MOM | (step == 1 ? OPT_FIRST : 0);
+    if (algo == LG_OPT_RMSPROP && h1 > 0.0) opt |= OPT_MOM;
+    if (algo == LG_OPT_SGD && (opt & OPT_ALT) && !(opt & OPT_MOM)) { lg_set_error("optim_step: nesterov needs a momentum"); return -1; }
+    // the state buffers this option set reads and writes
+    const bool need0 = algo != LG_OPT_SGD || (opt & OPT_MOM), need1 = adam || (algo == LG_OPT_RMSPROP && (opt & OPT_MOM));
+    const bool need2 = algo != LG_OPT_SGD && (opt & OPT_ALT);
+    if ((need0 && !state0) || (need1 && !state1) || (need2 && !state2)) { lg_set_error("optim_step: a state buffer of this option set is missing"); return -1; }
+    // the scalars are torch's Python floats: every derived one is taken in fp64 and rounded to fp32 once, where torch hands it to a tensor op
+    optim_args a = {(float)lr, (float)h0, (float)h1, (float)(1.0 - h0), (float)(1.0 - h1), (float)eps, (float)weight_decay, (float)grad_scale,
+                    1.f, 1.f};
+    if (adam) {
+        a.lr = (float)(lr / (1.0 - pow(h0, (double)step)));
+        a.bc2_sqrt = (float)sqrt(1.0 - pow(h1, (double)step));
+        a.decay = (float)(1.0 - lr * weight_decay);
+    }
+    int gx = (int)((max_range + 255) / 256);
+    if (gx < 1) gx = 1;
+    if (gx > 512) gx = 512;
+    const dim3 grid(gx, n_ranges);
+    const hipStream_t st = (hipStream_t)stream;
+#define LG_OPT_CASE(A, O) case (A) * 16 + (O): launch_optim<A, O>(grid, st, params, grads, state0, state1, state2, ranges, a); break;
+    switch (algo * 16 + opt) {
+        LG_OPT_CASE(LG_OPT_ADAM, 0) LG_OPT_CASE(LG_OPT_ADAM, OPT_WD) LG_OPT_CASE(LG_OPT_ADAM, OPT_ALT) LG_OPT_CASE(LG_OPT_ADAM, OPT_WD | OPT_ALT)
+        LG_OPT_CASE(LG_OPT_ADAMW, 0) LG_OPT_CASE(LG_OPT_ADAMW, OPT_ALT)
+        LG_OPT_CASE(LG_OPT_SGD, 0) LG_OPT_CASE(LG_OPT_SGD, OPT_WD)
+        LG_OPT_CASE(LG_OPT_SGD, OPT_MOM) LG_OPT_CASE(LG_OPT_SGD, OPT_MOM | OPT_WD)
+        LG_OPT_CASE(LG_OPT_SGD, OPT_MOM | OPT_FIRST) LG_OPT_CASE(LG_OPT_SGD, OPT_MOM | OPT_FIRST | OPT_WD)
+        LG_OPT_CASE(LG_OPT_SGD, OPT_MOM | OPT_ALT) LG_OPT_CASE(LG_OPT_SGD, OPT_MOM | OPT_ALT | OPT_WD)
+        LG_OPT_CASE(LG_OPT_SGD, OPT_MOM | OPT_ALT | OPT_FIRST) LG_OPT_CASE(LG_OPT_SGD, OPT_MOM | OPT_ALT | OPT_FIRST | OPT_WD)
+        LG_OPT_CASE(LG_OPT_RMSPROP, 0) LG_OPT_CASE(LG_OPT_RMSPROP, OPT_WD) LG_OPT_CASE(LG_OPT_RMSPROP, OPT_ALT) LG_OPT_CASE(LG_OPT_RMSPROP, OPT_ALT | OPT_WD)
+        LG_OPT_CASE(LG_OPT_RMSPROP, OPT_MOM) LG_OPT_CASE(LG_OPT_RMSPROP, OPT_MOM | OPT_WD)
+        LG_OPT_CASE(LG_OPT_RMSPROP, OPT_MOM | OPT_ALT) LG_OPT_CASE(LG_OPT_RMSPROP, OPT_MOM | OPT_ALT | OPT_WD)
+        default: lg_set_error("optim_step: no kernel for this option set"); return -1;
+    }
+#undef LG_OPT_CASE
     LG_CHECK_LAUNCH();
     return 0;
 }

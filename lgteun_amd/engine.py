@@ -306,8 +306,11 @@ class Engine:
         return _LgteunFn.apply(self, ms, pan, flags, *live)
 
     # ------------------------------------------------------------------------------------------
-    def train_step(self, ms, pan, gt, optim, loss_weight=1.0):
-        """forward + L1(mean) + backward + Adam as library calls; returns the device loss scalar (this rank's share)."""
+    def train_step(self, ms, pan, gt, optim, loss_weight=1.0, loss_type='l1'):
+        """forward + L1 / L2 (mean) + backward + the fused optimizer's step as library calls; returns the device loss scalar (this
+        rank's share)."""
+        if loss_type not in ('l1', 'l2'):
+            raise ValueError(f"loss_type must be 'l1' or 'l2' (got {loss_type!r})")
         self._check_attached()
         flags = self.base_flags(True) | LG_FLAG_SAVE
         if not getattr(optim, 'dropout', True):
@@ -321,8 +324,9 @@ class Engine:
         gt = gt.contiguous()
         dout = torch.empty_like(out)
         n_local = out.numel()
-        check(self.lib.lg_l1_loss(_ptr(out), _ptr(gt), _ptr(dout), _ptr(self._loss), n_local, n_local * self.world,
-                                  float(loss_weight), _stream_ptr()), 'lg_l1_loss')
+        loss_fn = self.lib.lg_l1_loss if loss_type == 'l1' else self.lib.lg_l2_loss
+        check(loss_fn(_ptr(out), _ptr(gt), _ptr(dout), _ptr(self._loss), n_local, n_local * self.world, float(loss_weight),
+                      _stream_ptr()), f'lg_{loss_type}_loss')
         bk = self.buckets[bool(flags & LG_FLAG_CHAINED)] if (self.world > 1 or self.force_collectives) else None
         overlap = bool(bk is not None and bk.overlap and not (flags & LG_FLAG_CHAINED))
         if defer or overlap:
@@ -365,6 +369,13 @@ class Engine:
                                     _ptr(self.ranges_dev), len(self.live_ranges), self.max_range, step, float(lr),
                                     float(betas[0]), float(betas[1]), float(eps), float(grad_scale), _stream_ptr()),
               'lg_adam_step')
+
+    def optim_step(self, states, step, algo, flags, lr, h0, h1, eps, weight_decay, grad_scale=1.0):
+        """lg_optim_step over the live ranges.  states: the three state slots of include/lgteun_hip.h (None: not used by the option set)"""
+        s0, s1, s2 = (None if t is None else _ptr(t) for t in states)
+        check(self.lib.lg_optim_step(_ptr(self.flat), _ptr(self.gflat), s0, s1, s2, _ptr(self.ranges_dev), len(self.live_ranges),
+                                     self.max_range, step, int(algo), int(flags), float(lr), float(h0), float(h1), float(eps),
+                                     float(weight_decay), float(grad_scale), _stream_ptr()), 'lg_optim_step')
 
 
 class _WsLease:
@@ -410,29 +421,46 @@ class _LgteunFn(torch.autograd.Function):
         return (None, None, None, None, *grads)
 
 
-class FusedAdam(torch.optim.Optimizer):
-    """torch.optim.Adam semantics (reference models/base/base_model.py:123-124) as one HIP launch over the flat
-    live ranges.  Subclasses Optimizer so lr_scheduler.StepLR (base_model.py:137-147) drives `param_groups[0]['lr']`."""
+class _FusedOptimizer(torch.optim.Optimizer):
+    """what the fused optimizers share: a torch.optim.Optimizer (so lr_scheduler.StepLR, base_model.py:137-147, drives
+    `param_groups[0]['lr']`, and the options sit in `param_groups[0]` under torch's names) whose step is ONE HIP launch over the flat
+    live ranges.  Dead-stage parameters have no gradient in the reference, and torch skips those: no weight decay, no state -- the
+    launch covers `engine.live_ranges` only.  State: flat fp32 buffers of `engine.total` floats, only those the option set needs."""
     is_fused_lgteun = True
+    TORCH_NAME = None                  # the torch.optim class whose arithmetic this is, and which `fused=False` selects
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
-        super().__init__(list(params), dict(lr=lr, betas=betas, eps=eps))
+    def __init__(self, params, defaults, unknown):
+        if unknown:
+            raise TypeError(f'{type(self).__name__} got unexpected keyword argument(s) {sorted(unknown)}: the fused step takes '
+                            f'{sorted(defaults)} only; put fused=False into the optim_cfg entry to use torch.optim.{self.TORCH_NAME}, '
+                            'which takes them')
+        super().__init__(list(params), defaults)
         self._step = 0
         self._state = None
         self.dropout = True
 
+    def state_names(self):
+        """the state buffers of this option set, in the order of lg_optim_step's state0 / state1 / state2 slots (None: unused)"""
+        raise NotImplementedError
+
+    def _launch(self, engine, group, state):
+        raise NotImplementedError
+
     def step_flat(self, engine):
-        if self._state is None or self._state['exp_avg'].numel() != engine.total:
-            self._state = dict(exp_avg=torch.zeros_like(engine.flat), exp_avg_sq=torch.zeros_like(engine.flat))
-        elif self._state['exp_avg'].device != engine.flat.device or not self._state['exp_avg'].is_contiguous():
-            # moments restored from a checkpoint (loaded to the host): the kernel takes device pointers
-            self._state = {k: v.to(engine.flat.device).contiguous() for k, v in self._state.items()}
+        names = [n for n in self.state_names() if n is not None]
+        st = self._state
+        if st is None or set(st) != set(names) or any(v.numel() != engine.total for v in st.values()):
+            st = {n: torch.zeros_like(engine.flat) for n in names}
+        elif any(v.device != engine.flat.device or not v.is_contiguous() for v in st.values()):
+            # state restored from a checkpoint (loaded to the host): the kernel takes device pointers
+            st = {k: v.to(engine.flat.device).contiguous() for k, v in st.items()}
+        self._state = st
         self._step += 1
-        g = self.param_groups[0]
-        engine.adam(self._state, self._step, g['lr'], g['betas'], g['eps'])
+        self._launch(engine, self.param_groups[0], st)
 
     def step(self, closure=None):   # pragma: no cover - the fused path goes through Engine.train_step
-        raise RuntimeError('FusedAdam is stepped by Engine.train_step(); use torch.optim.Adam for the autograd path')
+        raise RuntimeError(f'{type(self).__name__} is stepped by Engine.train_step(); use torch.optim.{self.TORCH_NAME} '
+                           '(fused=False in the optim_cfg entry) for the autograd path')
 
     def state_dict(self):
         sd = super().state_dict()
@@ -443,5 +471,113 @@ class FusedAdam(torch.optim.Optimizer):
         sd = dict(sd)                   # the caller's dict stays as it was
         extra = sd.pop('lgteun', None)
         super().load_state_dict(sd)
+        for group in self.param_groups:     # a checkpoint written before an option existed (torch's classes do this in __setstate__)
+            for k, v in self.defaults.items():
+                group.setdefault(k, v)
         if extra is not None:
             self._step, self._state = extra['step'], extra['state']
+
+    def _optim_step(self, engine, state, algo, flags, lr, h0, h1, eps, weight_decay):
+        engine.optim_step([state.get(n) if n is not None else None for n in self.state_names()], self._step, algo, flags, lr, h0, h1,
+                          eps, weight_decay)
+
+
+def _check_adam_args(lr, betas, eps, weight_decay):
+    """torch/optim/adam.py's argument checks"""
+    if not 0.0 <= lr:
+        raise ValueError(f'Invalid learning rate: {lr}')
+    if not 0.0 <= eps:
+        raise ValueError(f'Invalid epsilon value: {eps}')
+    if not 0.0 <= betas[0] < 1.0:
+        raise ValueError(f'Invalid beta parameter at index 0: {betas[0]}')
+    if not 0.0 <= betas[1] < 1.0:
+        raise ValueError(f'Invalid beta parameter at index 1: {betas[1]}')
+    if not 0.0 <= weight_decay:
+        raise ValueError(f'Invalid weight_decay value: {weight_decay}')
+
+
+class FusedAdam(_FusedOptimizer):
+    """torch.optim.Adam semantics (reference models/base/base_model.py:123-124) as one HIP launch over the flat live ranges;
+    `weight_decay` is torch's L2 term (added to the gradient), `amsgrad` keeps the running maximum of exp_avg_sq in a third buffer.
+    The plain option set (no weight decay, no amsgrad) is `lg_adam_step`, every other one an instance of `lg_optim_step`."""
+    TORCH_NAME = 'Adam'
+    ALGO = _lib.LG_OPT_ADAM
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, **unknown):
+        _check_adam_args(lr, betas, eps, weight_decay)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad), unknown)
+
+    def state_names(self):
+        return ['exp_avg', 'exp_avg_sq', 'max_exp_avg_sq' if self.param_groups[0]['amsgrad'] else None]
+
+    def _launch(self, engine, g, state):
+        if self.ALGO == _lib.LG_OPT_ADAM and not g['weight_decay'] and not g['amsgrad']:
+            engine.adam(state, self._step, g['lr'], g['betas'], g['eps'])
+        else:
+            self._optim_step(engine, state, self.ALGO, _lib.LG_OPT_AMSGRAD if g['amsgrad'] else 0, g['lr'], g['betas'][0], g['betas'][1],
+                             g['eps'], g['weight_decay'])
+
+
+class FusedAdamW(FusedAdam):
+    """torch.optim.AdamW (base_model.py:129-130): the decay is decoupled, p <- p (1 - lr weight_decay) ahead of the Adam update"""
+    TORCH_NAME = 'AdamW'
+    ALGO = _lib.LG_OPT_ADAMW
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, **unknown):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, **unknown)
+
+
+class FusedSGD(_FusedOptimizer):
+    """torch.optim.SGD (base_model.py:127-128) with momentum, dampening, nesterov and weight_decay (L2).  Like torch's, the momentum
+    buffer of the first step is the gradient itself."""
+    TORCH_NAME = 'SGD'
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, **unknown):
+        if lr < 0.0:
+            raise ValueError(f'Invalid learning rate: {lr}')
+        if momentum < 0.0:
+            raise ValueError(f'Invalid momentum value: {momentum}')
+        if weight_decay < 0.0:
+            raise ValueError(f'Invalid weight_decay value: {weight_decay}')
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError('Nesterov momentum requires a momentum and zero dampening')
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov),
+                         unknown)
+
+    def state_names(self):
+        return ['momentum_buffer' if self.param_groups[0]['momentum'] != 0 else None, None, None]
+
+    def _launch(self, engine, g, state):
+        self._optim_step(engine, state, _lib.LG_OPT_SGD, _lib.LG_OPT_NESTEROV if g['nesterov'] else 0, g['lr'], g['momentum'],
+                         g['dampening'], 0.0, g['weight_decay'])
+
+
+class FusedRMSprop(_FusedOptimizer):
+    """torch.optim.RMSprop (base_model.py:125-126) with alpha, eps (added after the square root), weight_decay (L2), momentum and
+    centered"""
+    TORCH_NAME = 'RMSprop'
+
+    def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0, momentum=0, centered=False, **unknown):
+        if not 0.0 <= lr:
+            raise ValueError(f'Invalid learning rate: {lr}')
+        if not 0.0 <= eps:
+            raise ValueError(f'Invalid epsilon value: {eps}')
+        if not 0.0 <= momentum:
+            raise ValueError(f'Invalid momentum value: {momentum}')
+        if not 0.0 <= weight_decay:
+            raise ValueError(f'Invalid weight_decay value: {weight_decay}')
+        if not 0.0 <= alpha:
+            raise ValueError(f'Invalid alpha value: {alpha}')
+        super().__init__(params, dict(lr=lr, alpha=alpha, eps=eps, weight_decay=weight_decay, momentum=momentum, centered=centered),
+                         unknown)
+
+    def state_names(self):
+        g = self.param_groups[0]
+        return ['square_avg', 'momentum_buffer' if g['momentum'] > 0 else None, 'grad_avg' if g['centered'] else None]
+
+    def _launch(self, engine, g, state):
+        self._optim_step(engine, state, _lib.LG_OPT_RMSPROP, _lib.LG_OPT_CENTERED if g['centered'] else 0, g['lr'], g['alpha'],
+                         g['momentum'], g['eps'], g['weight_decay'])
+
+
+FUSED_OPTIMIZERS = {'Adam': FusedAdam, 'AdamW': FusedAdamW, 'SGD': FusedSGD, 'RMSprop': FusedRMSprop}

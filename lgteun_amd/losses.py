@@ -1,7 +1,7 @@
 """The loss surface the LGTEUN runner needs (reference models/base/losses.py: `ReconstructionLoss` :19-40 and the
 `get_loss_module` factory :222-249, as used by configs/unlg_former.py:88-90 -- one `rec_loss` entry of type l1 / l2 with weight w).
 The adversarial / QNR / mutual-information losses of the comparison methods are outside this build.
-The fused train step does not call this module: it computes L1 + its gradient in `lg_l1_loss`; this is the autograd-path /
+The fused train step does not call this module: it computes the loss + its gradient in `lg_l1_loss` / `lg_l2_loss`; this is the autograd-path /
 torch-optimizer route and what `get_type()` callers see."""
 import torch.nn as nn
 

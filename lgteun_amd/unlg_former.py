@@ -162,18 +162,18 @@ class UnlgFormer(Base_model):
         return self.module_dict['core_module'](input_lr, input_pan)
 
     def train_iter(self, iter_id, input_batch, log_freq=10):
-        """Same contract as the reference train_iter.  With the fused optimizer (`set_optim` default on this
-        build) forward + L1 + backward + Adam run as four library calls with no per-iteration host sync
-        (the reference's two `.item()` syncs, unlg_former.py:105,107, happen only every `log_freq`)."""
+        """Same contract as the reference train_iter.  With a fused optimizer (`set_optim` default on this
+        build) and a rec_loss of type l1 or l2, forward + loss + backward + optimizer step run as four library calls with no
+        per-iteration host sync (the reference's two `.item()` syncs, unlg_former.py:105,107, happen only every `log_freq`)."""
         G = self.module_dict['core_module']
         G_optim = self.optim_dict['core_module']
         loss_cfg = self.cfg.get('loss_cfg', {})
         w = float(loss_cfg['rec_loss'].w) if 'rec_loss' in self.loss_module else 0.0
         core = G.module if hasattr(G, 'module') else G
         if getattr(G_optim, 'is_fused_lgteun', False) and 'rec_loss' in self.loss_module and \
-                self.loss_module['rec_loss'].get_type() == 'l1':
+                self.loss_module['rec_loss'].get_type() in ('l1', 'l2'):
             loss_t = core.engine().train_step(input_batch['input_lr'], input_batch['input_pan'], input_batch['target'],
-                                              G_optim, loss_weight=w)
+                                              G_optim, loss_weight=w, loss_type=self.loss_module['rec_loss'].get_type())
             if iter_id % log_freq == 0:
                 v = core.engine().global_loss()        # all ranks: under DDP `loss_t` is this rank's share of the global mean
                 self.print_train_log(iter_id, dict(rec_loss=v / w if w else 0.0, full_loss=v), log_freq)

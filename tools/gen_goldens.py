@@ -221,8 +221,46 @@ def round7(R):
     print('ref_checkpoint_c4_k2_iter7.pth, ref_config_unlg_former.json:', len(vals), 'config names')
 
 
+def train3_l2_adamw(R):
+    """runner-level: 3 train_iter of the reference with loss type l2 and AdamW (UnlgFormer.train_iter, StepLR per iteration, modules
+    kept in eval() -> dropout off).  Same content as train3_c4_k2_p32.npz; the case describes itself (`meta`: a JSON string inside the
+    file), so the manifest is not involved."""
+    import logging
+    meta = dict(C=4, K=2, B=2, h=8, seed=11, kind='smooth', salt=0, step_size=2, gamma=0.85, lr=1.5e-3, loss='l2', optim='AdamW',
+                betas=[0.9, 0.999], weight_decay=1e-2)
+    cfg = R.Config(ms_chans=meta['C'], work_dir='/tmp/lgteun_gold', datas='GF-2', cuda=False, max_iter=3,
+                   loss_cfg={'rec_loss': dict(type=meta['loss'], w=1.)},
+                   optim_cfg={'core_module': dict(type=meta['optim'], betas=tuple(meta['betas']), lr=meta['lr'],
+                                                  weight_decay=meta['weight_decay'])},
+                   sched_cfg=dict(step_size=meta['step_size'], gamma=meta['gamma']),
+                   model_cfg={'core_module': dict(stage=meta['K'])})
+    runner = R.UnlgFormer(cfg, logging.getLogger('gold'), None, None, None)
+    core = runner.module_dict['core_module']
+    shapes = {k: tuple(v.shape) for k, v in core.state_dict().items()}
+    sd = dw.fill_state_dict(shapes, salt=meta['salt'])
+    core.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    core.eval()
+    runner.set_optim()
+    runner.set_sched()
+    import mmcv
+    runner.timer = mmcv.Timer()
+    ms, pan, gt = dw.make_inputs(meta['B'], meta['C'], meta['h'], meta['h'], seed=meta['seed'], kind=meta['kind'])
+    lrs, logged = [], []
+    runner.print_train_log = lambda it, res, freq=10: logged.append(res['full_loss'])
+    for it in range(1, 4):
+        lrs.append(runner.optim_dict['core_module'].param_groups[0]['lr'])
+        runner.train_iter(it, dict(input_lr=t(ms), input_pan=t(pan), target=t(gt), image_id=['a', 'b']))
+        runner.sched_dict['core_module'].step()
+    final = {k.replace('.', '/'): v.detach().numpy() for k, v in core.state_dict().items() if not k.startswith('prior_module.0.')}
+    np.savez_compressed(os.path.join(GOLD, 'train3_l2_adamw_c4_k2_p32.npz'), losses=np.array(logged), lrs=np.array(lrs),
+                        meta=np.array(json.dumps(meta, sort_keys=True)), **final)
+    print('train3 l2 + AdamW losses', logged, 'lrs', lrs)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--only-train3-l2-adamw', action='store_true', help='write only train3_l2_adamw_c4_k2_p32.npz (three reference '
+                                                                        'iterations with loss type l2 and AdamW); no manifest entry')
     ap.add_argument('--only-r7', action='store_true', help='write only the round-7 fixtures (a reference checkpoint, its config\'s values)')
     ap.add_argument('--only-r5', action='store_true', help='write only the round-5 fixture (the reference\'s dataset/utils.py functions)')
     ap.add_argument('--check', action='store_true')
@@ -241,6 +279,9 @@ def main():
     manifest = {}
     if args.only_r7:
         round7(R)
+        return
+    if args.only_train3_l2_adamw:
+        train3_l2_adamw(R)
         return
     if args.only_r4:
         with open(os.path.join(GOLD, 'manifest.json')) as f:
@@ -389,6 +430,7 @@ def main():
     round4(R, manifest)
     round5()
     round7(R)
+    train3_l2_adamw(R)
     print('wrote', GOLD)
 
 
