@@ -40,6 +40,7 @@ LG_VAR_FFN_XS = 1 << 13
 LG_VAR_ATTN_BF16X3 = 1 << 14
 LG_VAR_FFN_H3_RECOMPUTE = 1 << 15
 LG_VAR_ATTN_BWD_RESTATS = 1 << 16
+LG_VAR_REDUCE_PER_BLOCK = 1 << 17
 LG_OPT_ADAM, LG_OPT_ADAMW, LG_OPT_SGD, LG_OPT_RMSPROP = 0, 1, 2, 3      # lg_optim_step: algo
 LG_OPT_AMSGRAD, LG_OPT_NESTEROV, LG_OPT_CENTERED = 1, 2, 4             # lg_optim_step: flags
 LG_ABI_VERSION = 2   # include/lgteun_hip.h: checked against lg_abi_version() when the library is loaded
@@ -77,6 +78,8 @@ def variant_from_env(env=None):
         v |= LG_VAR_FFN_H3_RECOMPUTE
     if env.get('LG_ATTN_BWD_STATS', '') == 'recompute':
         v |= LG_VAR_ATTN_BWD_RESTATS
+    if env.get('LG_REDUCE', '') == 'per_block':
+        v |= LG_VAR_REDUCE_PER_BLOCK
     return v
 
 

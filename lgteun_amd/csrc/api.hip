@@ -150,6 +150,7 @@ extern "C" int lg_plan_create(const lg_config* cfg, const int64_t* offsets, int3
         p->attn_bf16x3 = (v & LG_VAR_ATTN_BF16X3) ? 1 : 0;
         p->ffn_h3_re = (v & LG_VAR_FFN_H3_RECOMPUTE) ? 1 : 0;
         p->attn_restats = (v & LG_VAR_ATTN_BWD_RESTATS) ? 1 : 0;
+        p->reduce_per_block = (v & LG_VAR_REDUCE_PER_BLOCK) ? 1 : 0;
     }
     p->off = (int64_t*)malloc(sizeof(int64_t) * n_offsets);
     memcpy(p->off, offsets, sizeof(int64_t) * n_offsets);

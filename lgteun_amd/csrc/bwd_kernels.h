@@ -33,31 +33,61 @@ int launch_reduce_chan(const float* part, const ChanReduce& m, hipStream_t s);
 int launch_reduce_slab_pair(const float* slab_a, const float* slab_b, long nslices, int n, float* dst_a, float* dst_b, hipStream_t s);
 
 // Deferred reductions: while a ReduceQueue is active on the calling thread (reduce_queue_begin), launch_reduce_slab* /
-// launch_reduce_chan only RECORD their job; flush() sums all recorded slabs in ONE launch (blockIdx.y = job).  A backward
-// pass has ~60 of these tiny reductions (5 us of pure latency each).  Slabs must then stay untouched until the flush, so
-// producers take them from the queue's arena (take() flushes by itself when the arena or the job table is full).
+// launch_reduce_chan only RECORD their job; flush() sums all recorded slabs in ONE launch.  A backward pass has a few hundred of these
+// tiny reductions (about 21 per LGT block and 44 per data step, 5 us of pure latency each; tests/test_gpu_reduce_merge.py prints the counts of
+// the bench shapes).  Slabs must then stay untouched until the flush, so producers take them from the queue's arena (take() flushes by itself when the arena or the job table is full).
+//
+// Two forms of the launch:
+//  * merged (default): the whole queue in one flat grid.  The table lives in DEVICE memory (k_wgrad.hip: a small cache of
+//    uploaded tables keyed by their content -- the job list of a (plan, B, flags, workspace, gradient buffer) repeats from step
+//    to step, so a training loop uploads twice and never again).  Every workgroup finds its job in the prefix sums of the
+//    per-job workgroup counts.  Jobs that add into the SAME destination (the K data steps' shared parameters) are CHAINED in
+//    the order they were pushed: one set of workgroups walks the chain, each link's total formed and added exactly as its own
+//    launch would have -- bit for bit what one launch per link gives.  Two unchained jobs of a table never share a destination
+//    element (checked on the host when a table is first seen; an error instead of a launch).
+//  * per_block (lg_config.variant LG_VAR_REDUCE_PER_BLOCK): the launch points of rounds 2 - 6 -- one launch per LGT block and
+//    per data step, table as a kernel argument, blockIdx.y = job.
 struct ReduceJob {
     const float* slab;   // element (slice s, row r, col c) at slab[s * slice_stride + r * row_stride + c]
     float* dst;          // dst[r * ld + c] += sum_s ...   for r < rows_valid, c < cols_valid
     float* dst2;         // optional second destination
     long nslices, slice_stride;
     int rows, cols, row_stride, ld, rows_valid, cols_valid;
+    int next = -1;       // merged form: table index of the next link of this destination's chain, -1 = last (filled by flush())
+    int v4 = -1;         // merged form: 1 = four outputs per thread (filled by flush(); -1: the kernel decides, as the per_block form does)
 };
-#define LG_MAX_REDUCE_JOBS 56
+#define LG_MAX_REDUCE_JOBS 56    // per_block form: 56 x 72 bytes + the count fit the 4 KB of kernel arguments
+#define LG_RQ_MAX_JOBS 512       // merged form: jobs of one launch
 struct ReduceJobTable {
     ReduceJob j[LG_MAX_REDUCE_JOBS];
     int n;
+};
+// device image of a merged launch: chain heads first (one entry of wg_start each), then the other links
+struct ReduceImage {
+    int nheads, njobs, total_wgs, pad;
+    int wg_start[LG_RQ_MAX_JOBS];   // first workgroup of head k (ascending)
+    ReduceJob j[LG_RQ_MAX_JOBS];
 };
 struct ReduceQueue {
     float* arena;
     size_t cap, off;   // floats
     hipStream_t stream;
-    ReduceJobTable tab;
-    void init(float* base, size_t cap_floats, hipStream_t s) { arena = base; cap = cap_floats; off = 0; stream = s; tab.n = 0; }
+    bool per_block;    // the launch form (above)
+    int n;
+    ReduceJob jobs[LG_RQ_MAX_JOBS];
+    void init(float* base, size_t cap_floats, hipStream_t s, bool per_block_form) {
+        arena = base; cap = cap_floats; off = 0; stream = s; per_block = per_block_form; n = 0;
+    }
     float* take(size_t nfloats);   // nullptr (error set) when nfloats > cap
     int push(const ReduceJob& j);
     int flush();
+    int block_end() { return per_block ? flush() : 0; }   // a launch point of the per_block form only
 };
+// process-wide counters of the reduce queues' launches (tests, diagnosis; all host threads together): [0] launches (both forms), [1] flushes that
+// take() or push() triggered because the arena or the table was full, [2] tables uploaded to the device (each one a miss of the table cache: a
+// drained device + a blocking copy), [3] jobs and [5] chains of the largest merged launch, [4] host nanoseconds spent in merged flush()es
+#define LG_RQ_NSTATS 6
+void reduce_queue_stats(long long out[LG_RQ_NSTATS], int reset);
 int launch_reduce_slab_wb(const float* wslab, const float* bslab, long nslices, int rows, int cols, float* dW, int ld, float* db, hipStream_t s);
 // one job: recorded when a queue is active on this thread, otherwise summed right away on `s`
 int launch_reduce_job(const ReduceJob& j, hipStream_t s);

@@ -60,6 +60,8 @@ struct lg_plan {
     bool attn_saves_stats(int e) const { return cfg.precision == 0 && !attn_fwd_valu && !attn_restats && !(e == 32 && attn_bwd_core_m); }
     bool attn_f16x2() const { return cfg.precision == 0 && !attn_bf16x3 && !attn_fwd_valu && ffn_tile == 0 && !ffn_bf16x3; }   // (the scales ride in the FFN prep launch: the f16-pair FFN arithmetic must be on)
     int attn_fwd_valu; // A/B switch (lg_config.variant LG_VAR_ATTN_FWD_VALU; Python side: LG_ATTN_FWD=valu): round 2's vector-pipe k_attn instead of the matrix-pipe k_attn_m
+    int reduce_per_block; // A/B switch (lg_config.variant LG_VAR_REDUCE_PER_BLOCK; Python side: LG_REDUCE=per_block): the parameter-gradient reduce launches of rounds 2 - 6 (one per
+                          // LGT block and per data step, table as a kernel argument) instead of one launch for the LGT and one for the K data steps (bwd_kernels.h: ReduceQueue)
     int dstep_tiles; // A/B switch (lg_config.variant LG_VAR_DSTEP_TILES; Python side: LG_DSTEP=tiles): the tile kernels of the data step also where the one-launch
                      // plane-in-LDS form (k_dstep.hip) exists
     bool dstep_fused(int h, int w) const;   // k_dstep.hip: square planes of 128 or 64

@@ -9,7 +9,7 @@
 struct BwdBufs {
     float *dzA, *dzB, *gu3, *gs1, *gu1, *gr, *gd3, *gt1, *gd1;
     float *dx[3];
-    float *dh2, *dh1, *y2, *do2, *dg, *dym, *cat, *y1, *dqkv, *dpos_slab;
+    float *dh2, *dh1, *y2, *do2, *dg, *dym, *cat, *y1, *dqkv;
     float *w3t[5], *w2t[5], *w1t[5], *wsp, *dt, *dskip, *v, *du, *fft_scratch;   // transposed FFN weights, one set per block of the LGT
     float* slab_arena;    // scratch of the deferred parameter-gradient reductions (ReduceQueue, bwd_kernels.h)
     float* attn_stats;    // [P0][2][4]: row statistics between the two launches of k_attn_bwd_core_m (LG_ATTN_BWD_CORE=m)
@@ -19,6 +19,11 @@ struct BwdBufs {
     size_t bytes;
 };
 
+// the local mixer's pos_emb partial rows of one block: k_attn_bwd_f's rows (every parameter gradient of the half-block) or the three-kernel form's
+static size_t dpos_slab_floats() {
+    const size_t f = (size_t)ATTN_BWD_F_WGS * ATTN_BWD_F_ROW, r3 = (size_t)512 * 2 * 64 * 64;
+    return f > r3 ? f : r3;
+}
 static void carve_bwd(const lg_plan* plan, int B, void* base, BwdBufs& bb) {
     const lg_config& c = plan->cfg;
     Carver cv{reinterpret_cast<char*>(base), 0};
@@ -32,7 +37,6 @@ static void carve_bwd(const lg_plan* plan, int B, void* base, BwdBufs& bb) {
     bb.dym = cv.take(P0 * E); bb.cat = cv.take(P0 * E); bb.y1 = cv.take(P0 * 16 > P0 * E / 2 ? P0 * 16 : P0 * E / 2);
     bb.dqkv = cv.take(P0 * 2 * E);
     bb.attn_stats = cv.take(P0 * 8);
-    bb.dpos_slab = cv.take((size_t)ATTN_BWD_F_WGS * ATTN_BWD_F_ROW > (size_t)512 * 2 * 64 * 64 ? (size_t)ATTN_BWD_F_WGS * ATTN_BWD_F_ROW : (size_t)512 * 2 * 64 * 64);
     for (int j = 0; j < 5; ++j) { bb.w3t[j] = cv.take(8 * E * 2 * E); bb.w2t[j] = cv.take(8 * E * 8 * E); bb.w1t[j] = cv.take(8 * E * 2 * E); }
     bb.wsp = cv.take(ffn_wsplit_bytes(32) / sizeof(float));   // pre-split W2^T / W1^T fragments of k_ffn1_bwd_x32 (e = 32 blocks)
     size_t sl = wgrad_slab_floats((int)(8 * E), (int)(8 * E), (long)P0);
@@ -44,8 +48,9 @@ static void carve_bwd(const lg_plan* plan, int B, void* base, BwdBufs& bb) {
     const size_t sl5 = (size_t)PIXEL_PART_WGS * (2 * 8 * c.C + 2 * c.C);
     if (sl5 > sl4) sl4 = sl5;
     if (sl4 > sl) sl = sl4;
-    // arena: one block's worth of slabs (dw-conv partials + the three FFN weight gradients + the small ones) between flushes;
-    // take() flushes by itself if a configuration needs more
+    // arena: a whole LGT backward between flushes -- five blocks' worth of slabs (each: dw-conv partials + the three FFN weight gradients + the
+    // small ones, and the local mixer's pos_emb partial rows); the weight-gradient slabs of the down / up / fusion convs ride in the blocks'
+    // slack.  take() flushes by itself if a configuration needs more
     if (sl3 > sl) sl = sl3;
     for (size_t e = E; e <= 2 * E; e *= 2)   // slab rows of the fused FFN backward kernels (k_ffn_bwd_x.hip, k_ffn_dwbwd_x.hip): only of the paths this plan runs
         if ((e == 16 && plan->ffn_bwd_x(16)) || (e == 32 && plan->ffn1_bwd_x32(32))) {
@@ -54,7 +59,7 @@ static void carve_bwd(const lg_plan* plan, int B, void* base, BwdBufs& bb) {
     if (ffn_dw_bwd_x_slab_floats(16) > sl) sl = ffn_dw_bwd_x_slab_floats(16);
     if (ffn_dw_bwd_x_slab_floats(32) > sl) sl = ffn_dw_bwd_x_slab_floats(32);
     if (ffn_dw_bwd_h_slab_floats() > sl) sl = ffn_dw_bwd_h_slab_floats();
-    bb.slab_cap = 4 * sl;
+    bb.slab_cap = 5 * (4 * sl + dpos_slab_floats());
     bb.slab_arena = cv.take(bb.slab_cap);
     bb.ffn_scales = nullptr;
     bb.dt = cv.take(P0 * E); bb.dskip = cv.take(P0 * E); bb.v = cv.take(P1 * E); bb.du = cv.take(P1 * E);
@@ -71,8 +76,8 @@ size_t bwd_workspace_bytes(const lg_plan* plan, int B) {
 
 // deactivates the calling thread's reduce queue on every exit path (error returns included)
 struct ReduceQueueScope {
-    explicit ReduceQueueScope(BwdBufs& bb, hipStream_t s) {
-        bb.rq.init(bb.slab_arena, bb.slab_cap, s);
+    explicit ReduceQueueScope(BwdBufs& bb, hipStream_t s, bool per_block) {
+        bb.rq.init(bb.slab_arena, bb.slab_cap, s, per_block);
         reduce_queue_begin(&bb.rq);
     }
     ~ReduceQueueScope() { (void)reduce_queue_end(); }
@@ -245,7 +250,8 @@ static int mixer_half_bwd(const lg_plan* pl, const float* P, float* G, int st, i
         af.pos = P + pl->blk(st, j, B_POS);
         af.ln1g = P + pl->blk(st, j, B_LN1G); af.ln1b = P + pl->blk(st, j, B_LN1B);
         af.qkvw = P + pl->blk(st, j, B_QKVW); af.qkvb = P + pl->blk(st, j, B_QKVB); af.projw = P + pl->blk(st, j, B_PROJW);
-        af.slab = bb.dpos_slab;   // ATTN_BWD_F_WGS rows: untouched until the block's flush
+        af.slab = bb.rq.take((size_t)ATTN_BWD_F_WGS * ATTN_BWD_F_ROW);   // a slab of its own per block: untouched until the pass's reduce launch
+        if (!af.slab) return -3;
         af.d_pos = G + pl->blk(st, j, B_POS); af.d_qkvw = G + pl->blk(st, j, B_QKVW); af.d_qkvb = G + pl->blk(st, j, B_QKVB);
         af.d_projw = G + pl->blk(st, j, B_PROJW); af.d_ln1g = G + pl->blk(st, j, B_LN1G); af.d_ln1b = G + pl->blk(st, j, B_LN1B);
         af.B = B; af.h = fb.h; af.w = fb.w;
@@ -263,7 +269,8 @@ static int mixer_half_bwd(const lg_plan* pl, const float* P, float* G, int st, i
     AttnBwdArgs at;
     at.x = fb.xin; at.dy = tmp; at.dym = dym; at.o2 = fb.o2; at.dg = bb.dg; at.dx = dx_out;
     at.cat = bb.cat; at.y1 = bb.y1; at.dqkv = bb.dqkv;
-    at.pos = P + pl->blk(st, j, B_POS); at.posT = posT; at.dpos_slab = bb.dpos_slab;
+    at.pos = P + pl->blk(st, j, B_POS); at.posT = posT; at.dpos_slab = bb.rq.take((size_t)512 * 2 * 64 * 64);
+    if (!at.dpos_slab) return -3;
     at.ln1g = P + pl->blk(st, j, B_LN1G); at.ln1b = P + pl->blk(st, j, B_LN1B);
     at.qkvw = P + pl->blk(st, j, B_QKVW); at.qkvb = P + pl->blk(st, j, B_QKVB); at.projw = P + pl->blk(st, j, B_PROJW);
     at.d_ln1g = G + pl->blk(st, j, B_LN1G); at.d_ln1b = G + pl->blk(st, j, B_LN1B); at.part = bb.rq.take(attn_bwd_part_floats(e));
@@ -274,7 +281,7 @@ static int mixer_half_bwd(const lg_plan* pl, const float* P, float* G, int st, i
     if (pl->attn_saves_stats(e) && !(e == 32 && pl->attn_bwd_core_m)) { at.so = fb.att_o; at.sl = fb.att_l; }   // left by the forward's saving launch (block_mixer_fwd)
     RC(launch_attn_bwd(e, at, s));
     const int grid = attn_bwd_grid(e, B, fb.h, fb.w);
-    RC(launch_reduce_slab(bb.dpos_slab, grid, 1, 2 * 64 * 64, G + pl->blk(st, j, B_POS), 2 * 64 * 64, 1, 2 * 64 * 64, s));
+    RC(launch_reduce_slab(at.dpos_slab, grid, 1, 2 * 64 * 64, G + pl->blk(st, j, B_POS), 2 * 64 * 64, 1, 2 * 64 * 64, s));
     RC(wgrad(dym, e, bb.cat, e, G + pl->blk(st, j, B_PROJW), e, G + pl->blk(st, j, B_PROJB), Pn, e, e, e, e, 0, 0, bb, s));
     if (!attn_bwd_fuses_qkv(e)) {
         const int y1ld = (hc + 15) / 16 * 16, dqld = (3 * hc + 15) / 16 * 16;
@@ -288,7 +295,7 @@ static int block_bwd(const lg_plan* pl, const float* P, float* G, int st, int j,
                      const float* dy, float* tmp, float* dx_out, int B, int flags, uint64_t seed, hipStream_t s) {
     RC(ffn_half_bwd(pl, P, G, st, j, fb, bb, dy, tmp, B, s));
     RC(mixer_half_bwd(pl, P, G, st, j, fb, bb, posT, tmp, dx_out, B, flags, seed, s));
-    return bb.rq.flush();   // dpos_slab and the arena are reused by the next block
+    return bb.rq.block_end();   // (per_block form: one reduce launch per block; merged form: the pass's launch takes these jobs)
 }
 
 // per-op backward entry (tests): which 0: global mixer (dy, dx planar), 1: mixer half-block, 2: ffn half-block
@@ -300,7 +307,7 @@ int op_block_bwd(const lg_plan* pl, const float* P, float* G, int st, int j, int
     bb.ffn_scales = nb.ffn_scales;
     const BlockBufs& fb = nb.blk[j];
     if (which == 0) return fft_bwd_call(pl, P, G, st, j, fb, dy, dx, B, s, nb.fft_scratch, bb.slab_arena);   // no queue: summed at once
-    ReduceQueueScope rqs(bb, s);
+    ReduceQueueScope rqs(bb, s, pl->reduce_per_block != 0);
     int rc = which == 1 ? 0 : ffn_transposes(pl, P, st, j, j + 1, nb, bb, s);
     if (!rc) rc = which == 1 ? mixer_half_bwd(pl, P, G, st, j, fb, bb, nb.posT, dy, dx, B, 0, 0, s)
                              : ffn_half_bwd(pl, P, G, st, j, fb, bb, dy, dx, B, s);
@@ -332,7 +339,7 @@ static int data_step_bwd(const lg_plan* pl, const float* P, float* G, int st, co
         gg.rw = G + pl->shared(S_RW); gg.rb = G + pl->shared(S_RB); gg.rtw = G + pl->shared(S_RTW); gg.rtb = G + pl->shared(S_RTB);
         gg.eta = G + pl->eta(st);
         RC(launch_dstep_bwd(a, gg, s));
-        return bb.rq.flush();   // the K stages share these parameters: two stages' jobs must not meet in one reduce launch
+        return bb.rq.block_end();   // the K stages share these parameters: per_block form, one launch per stage; merged form, one chain per parameter
     }
     DstepTopArgs t;
     t.g = g; t.s1 = nb.s1[st]; t.z = zin; t.pan = pan; t.gu = bb.gu3; t.dz = dz;
@@ -372,7 +379,7 @@ static int data_step_bwd(const lg_plan* pl, const float* P, float* G, int st, co
     if (!d.part) return -3;
     RC(launch_dw_bwd(0, d, s));
     RC(launch_resample_adj(0, bb.gd1, dz, planes, H, W, 1, s));
-    return bb.rq.flush();   // the K stages share these parameters: two stages' jobs must not meet in one reduce launch
+    return bb.rq.block_end();   // the K stages share these parameters: per_block form, one launch per stage; merged form, one chain per parameter
 }
 
 // backward of stage st's LGT (LGT.py:314-344, reversed) from the activation set `nb` holds: dout = gradient wrt the LGT's
@@ -435,7 +442,7 @@ int op_data_step_bwd(const lg_plan* pl, const float* P, float* G, int st, NetBuf
                      const float* g, float* dz, int B, hipStream_t s) {
     BwdBufs bb;
     carve_bwd(pl, B, bwd_ws, bb);
-    ReduceQueueScope rqs(bb, s);
+    ReduceQueueScope rqs(bb, s, pl->reduce_per_block != 0);
     const int rc = data_step_bwd(pl, P, G, st, nb, bb, z_in, pan, g, dz, B, s);
     const int rc2 = reduce_queue_end();
     return rc ? rc : rc2;
@@ -448,7 +455,7 @@ int op_lgt_bwd(const lg_plan* pl, const float* P, float* G, int st, NetBufs& nb,
     bb.fft_scratch = nb.fft_scratch;
     bb.ffn_scales = nb.ffn_scales;
     bb.dzA = dz;                       // lgt_bwd leaves the gradient wrt the LGT's input here
-    ReduceQueueScope rqs(bb, s);
+    ReduceQueueScope rqs(bb, s, pl->reduce_per_block != 0);
     const int rc = lgt_bwd(pl, P, G, st, nb, bb, dout, z, B, flags, seed, s);
     const int rc2 = reduce_queue_end();
     return rc ? rc : rc2;
@@ -462,14 +469,16 @@ int net_backward(const lg_plan* pl, const float* P, float* G, const float* ms, c
     carve_bwd(pl, B, bwd_ws, bb);
     bb.fft_scratch = nb.fft_scratch;
     bb.ffn_scales = nb.ffn_scales;
-    ReduceQueueScope rqs(bb, s);
+    ReduceQueueScope rqs(bb, s, pl->reduce_per_block != 0);
     if (flags & LG_FLAG_CHAINED) {
         // intended unfolding (every stage live): LGT_i then data step i, last stage first; each LGT reads its own activation set
         const float* g = dout;
         for (int i = c.K - 1; i >= 0; --i) {
             const NetBufs sv = stage_view(nb, i);
             RC(lgt_bwd(pl, P, G, i, sv, bb, g, nb.Z[i + 1], B, flags, seed, s));
+            if (!bb.rq.per_block) RC(bb.rq.flush());   // merged form: one launch per LGT and per data step here (the arena holds one LGT pass)
             RC(data_step_bwd(pl, P, G, i, nb, bb, nb.X[i], pan, bb.dzA, bb.dzB, B, s));
+            RC(bb.rq.flush());
             g = bb.dzB;
         }
         return reduce_queue_end();
@@ -479,6 +488,8 @@ int net_backward(const lg_plan* pl, const float* P, float* G, const float* ms, c
     // ---------------- LGT of the last stage: the only live one
     if (do_lgt) RC(lgt_bwd(pl, P, G, c.K - 1, nb, bb, dout, nb.Z[c.K], B, flags, seed, s));
     if (!do_data) return reduce_queue_end();
+    // merged form: the LGT's gradients are complete here (LG_FLAG_BWD_LGT / _DATA, the two-bucket all-reduce), the K data steps follow in ONE launch
+    if (do_lgt && !bb.rq.per_block) RC(bb.rq.flush());
     // ---------------- K shared data steps, last to first (unlg_former.py:56-61); input gradient: bb.dzA
     float* g = bb.dzA;
     float* dz = bb.dzB;

@@ -8,6 +8,11 @@
 #include "kernels.h"
 #include "bwd_kernels.h"
 #include "hstore.h"
+#include <string.h>
+#include <algorithm>
+#include <chrono>
+#include <mutex>
+#include <vector>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -210,38 +215,54 @@ __global__ __launch_bounds__(256) void k_reduce_slab(const float* __restrict__ s
     }
 }
 
-// all queued jobs in one launch: blockIdx.y = job, same 16 outputs x 16 slice phases shape as k_reduce_slab
-__global__ __launch_bounds__(256) void k_reduce_jobs(ReduceJobTable t) {
-    __shared__ float4 part[16][17];
-    const ReduceJob& jb = t.j[blockIdx.y];
+// round 6: jobs whose rows are whole, 16-byte aligned quads (every large one: pos_emb, the FFN weight slabs) move FOUR outputs per thread -- a
+// 16-lane group reads 256 contiguous bytes of a slice instead of 64, a quarter of the workgroups.  Same order of additions per output.
+__host__ __device__ inline bool reduce_job_v4(const ReduceJob& jb) {
+    return ((jb.cols | jb.row_stride | jb.ld) & 3) == 0 && (jb.slice_stride & 3) == 0 && jb.rows_valid == jb.rows && jb.cols_valid == jb.cols &&
+           ((reinterpret_cast<uintptr_t>(jb.slab) | reinterpret_cast<uintptr_t>(jb.dst) | reinterpret_cast<uintptr_t>(jb.dst2)) & 15) == 0;
+}
+__host__ __device__ inline long reduce_job_wgs(const ReduceJob& jb, bool v4) {
+    const long n = (long)jb.rows * jb.cols;
+    return v4 ? ((n >> 2) + 15) / 16 : (n + 15) / 16;
+}
+// one job, the outputs of workgroup `wg` of it (wg < reduce_job_wgs): 16 outputs (V4: 16 quads of outputs) x 16 slice phases, the shape of
+// k_reduce_slab.  The order of additions of an output is the same in both forms.
+// (slabs and destinations are global memory; said explicitly, because an entry rebuilt from scalar registers has lost that and would read through flat loads)
+typedef __attribute__((address_space(1))) const float* rq_gsrc;
+typedef __attribute__((address_space(1))) float* rq_gdst;
+typedef __attribute__((address_space(1))) const f32x4* rq_gsrc4;
+typedef __attribute__((address_space(1))) f32x4* rq_gdst4;
+__device__ __forceinline__ float4 rq_ld4(rq_gsrc p) { const f32x4 v = *(rq_gsrc4)p; return make_float4(v.x, v.y, v.z, v.w); }
+__device__ __forceinline__ void rq_add4(rq_gdst p, const float4& t) {   // *p += t
+    const rq_gdst4 d = (rq_gdst4)p;
+    const f32x4 v = *d;
+    *d = (f32x4){v.x + t.x, v.y + t.y, v.z + t.z, v.w + t.w};
+}
+template <bool V4>
+__device__ __forceinline__ void reduce_job_wg(const ReduceJob& jb, long wg, float4 (*part)[17]) {
     const long n = (long)jb.rows * jb.cols;
     const int o = threadIdx.x & 15, ph = threadIdx.x >> 4;
-    // round 6: jobs whose rows are whole, 16-byte aligned quads (every large one: pos_emb, the FFN weight slabs) move FOUR outputs per thread -- a
-    // 16-lane group reads 256 contiguous bytes of a slice instead of 64, a quarter of the workgroups.  Same order of additions per output.
-    const bool v4 = ((jb.cols | jb.row_stride | jb.ld) & 3) == 0 && (jb.slice_stride & 3) == 0 && jb.rows_valid == jb.rows && jb.cols_valid == jb.cols &&
-                    ((reinterpret_cast<uintptr_t>(jb.slab) | reinterpret_cast<uintptr_t>(jb.dst) | reinterpret_cast<uintptr_t>(jb.dst2)) & 15) == 0;
-    if (v4) {
+    if (V4) {
         const long n4 = n >> 2;
-        if (blockIdx.x * 16L >= n4) return;
-        const long i4 = blockIdx.x * 16L + o;
+        const long i4 = wg * 16L + o;
         const long i = i4 << 2;
         const int row = (int)(i / jb.cols), col = (int)(i - (long)row * jb.cols);
         float4 sv[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) sv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (i4 < n4) {
-            const float* __restrict__ src = jb.slab + (long)row * jb.row_stride + col;
+            const rq_gsrc src = (rq_gsrc)jb.slab + (long)row * jb.row_stride + col;
             const long ss = jb.slice_stride, ns = jb.nslices;
             long k = ph;
             for (; k + 16 * 7 < ns; k += 16 * 8) {
                 float4 ld[8];
 #pragma unroll
-                for (int u = 0; u < 8; ++u) ld[u] = *reinterpret_cast<const float4*>(src + (k + 16 * u) * ss);
+                for (int u = 0; u < 8; ++u) ld[u] = rq_ld4(src + (k + 16 * u) * ss);
 #pragma unroll
                 for (int u = 0; u < 8; ++u) { sv[u].x += ld[u].x; sv[u].y += ld[u].y; sv[u].z += ld[u].z; sv[u].w += ld[u].w; }
             }
             for (; k < ns; k += 16) {
-                const float4 l = *reinterpret_cast<const float4*>(src + k * ss);
+                const float4 l = rq_ld4(src + k * ss);
                 sv[0].x += l.x; sv[0].y += l.y; sv[0].z += l.z; sv[0].w += l.w;
             }
         }
@@ -252,23 +273,18 @@ __global__ __launch_bounds__(256) void k_reduce_jobs(ReduceJobTable t) {
             float4 ts = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
             for (int q = 0; q < 16; ++q) ts = add4(ts, part[q][o]);
-            float4* d = reinterpret_cast<float4*>(jb.dst + (long)row * jb.ld + col);
-            *d = add4(*d, ts);
-            if (jb.dst2) {
-                float4* d2 = reinterpret_cast<float4*>(jb.dst2 + (long)row * jb.ld + col);
-                *d2 = add4(*d2, ts);
-            }
+            rq_add4((rq_gdst)jb.dst + (long)row * jb.ld + col, ts);
+            if (jb.dst2) rq_add4((rq_gdst)jb.dst2 + (long)row * jb.ld + col, ts);
         }
         return;
     }
-    if (blockIdx.x * 16L >= n) return;
-    const long i = blockIdx.x * 16L + o;
+    const long i = wg * 16L + o;
     const int row = (int)(i / jb.cols), col = (int)(i - (long)row * jb.cols);
     float sv[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) sv[u] = 0.f;
     if (i < n) {
-        const float* __restrict__ src = jb.slab + (long)row * jb.row_stride + col;
+        const rq_gsrc src = (rq_gsrc)jb.slab + (long)row * jb.row_stride + col;
         const long ss = jb.slice_stride, ns = jb.nslices;
         long k = ph;
         for (; k + 16 * 7 < ns; k += 16 * 8) {
@@ -284,52 +300,297 @@ __global__ __launch_bounds__(256) void k_reduce_jobs(ReduceJobTable t) {
         float tsum = 0.f;
 #pragma unroll
         for (int q = 0; q < 16; ++q) tsum += parts[q * 17 + o];
-        jb.dst[(long)row * jb.ld + col] += tsum;
-        if (jb.dst2) jb.dst2[(long)row * jb.ld + col] += tsum;
+        ((rq_gdst)jb.dst)[(long)row * jb.ld + col] += tsum;
+        if (jb.dst2) ((rq_gdst)jb.dst2)[(long)row * jb.ld + col] += tsum;
     }
 }
 
+// one chain of jobs (the same destination: bwd_kernels.h), link after link in the SAME threads -- an output's value goes through the additions
+// dst += total(link 0), dst += total(link 1), ... exactly as one launch per link would have done them
+// (a table entry is the same for every lane: read once and kept in scalar registers, so the slab / destination addresses are scalar base + lane
+// offset as they are when the table is a kernel argument -- loads behind a barrier are not turned into scalar loads by the compiler itself)
+__device__ __forceinline__ ReduceJob reduce_job_uniform(const ReduceJob* p) {
+    constexpr int NW = sizeof(ReduceJob) / 4;
+    const int* q = reinterpret_cast<const int*>(p);
+    int w[NW];
+#pragma unroll
+    for (int k = 0; k < NW; ++k) w[k] = __builtin_amdgcn_readfirstlane(q[k]);
+    ReduceJob j;
+    __builtin_memcpy(&j, w, sizeof(ReduceJob));
+    return j;
+}
+__device__ __forceinline__ void reduce_chain_wg(const ReduceJob* jb, const ReduceJob* tab, long wg, float4 (*part)[17]) {
+    ReduceJob j = reduce_job_uniform(jb);
+    const bool v4 = j.v4 == 1;   // (the head's: flush() clears it when a link of the chain cannot run in that form)
+    for (;;) {
+        if (v4) reduce_job_wg<true>(j, wg, part);
+        else reduce_job_wg<false>(j, wg, part);
+        if (j.next < 0) break;
+        j = reduce_job_uniform(tab + j.next);
+        __syncthreads();   // `part` is read by the phase-0 threads of the link just done
+    }
+}
+// per_block form and the direct single-job launches: table as a kernel argument, blockIdx.y = job
+__global__ __launch_bounds__(256) void k_reduce_jobs_tab(ReduceJobTable t) {
+    __shared__ float4 part[16][17];
+    const ReduceJob& jb = t.j[blockIdx.y];
+    const bool v4 = reduce_job_v4(jb);
+    if ((long)blockIdx.x >= reduce_job_wgs(jb, v4)) return;
+    if (v4) reduce_job_wg<true>(jb, blockIdx.x, part);
+    else reduce_job_wg<false>(jb, blockIdx.x, part);
+}
+// merged form: every job of a backward pass in one flat grid; workgroup -> job through the prefix sums of the per-job workgroup counts
+// (<= 512 entries: two loads per thread and a count, no search chain)
+__global__ __launch_bounds__(256) void k_reduce_jobs(const ReduceImage* __restrict__ img) {
+    __shared__ float4 part[16][17];
+    __shared__ int s_cnt;
+    const int nh = img->nheads;
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    int c = 0;
+    for (int k = threadIdx.x; k < nh; k += 256) c += img->wg_start[k] <= (int)blockIdx.x ? 1 : 0;
+    if (c) atomicAdd(&s_cnt, c);
+    __syncthreads();
+    const int job = __builtin_amdgcn_readfirstlane(s_cnt) - 1;   // wg_start[0] = 0: job >= 0
+    const int wg0 = __builtin_amdgcn_readfirstlane(img->wg_start[job]);
+    reduce_chain_wg(img->j + job, img->j, (long)((int)blockIdx.x - wg0), part);
+}
+
 static thread_local ReduceQueue* tl_rq = nullptr;
+static std::atomic<long long> g_rq_stats[LG_RQ_NSTATS];   // process-wide (bwd_kernels.h: reduce_queue_stats)
+void reduce_queue_stats(long long out[LG_RQ_NSTATS], int reset) {
+    for (int k = 0; k < LG_RQ_NSTATS; ++k) out[k] = reset ? g_rq_stats[k].exchange(0) : g_rq_stats[k].load();
+}
+// debug export (tests/test_gpu_reduce_merge.py): the LG_RQ_NSTATS = 6 counters since the last reset
+extern "C" __attribute__((visibility("default"))) int lg_debug_reduce_stats(long long* out6, int reset) {
+    if (!out6) return -1;
+    reduce_queue_stats(out6, reset);
+    return 0;
+}
 void reduce_queue_begin(ReduceQueue* q) { tl_rq = q; }
 int reduce_queue_end() {
     ReduceQueue* q = tl_rq;
     tl_rq = nullptr;
     return q ? q->flush() : 0;
 }
-int ReduceQueue::flush() {
-    off = 0;
-    if (tab.n == 0) return 0;
-    long nmax = 0;
-    for (int k = 0; k < tab.n; ++k) {
-        const long n = (long)tab.j[k].rows * tab.j[k].cols;
-        if (n > nmax) nmax = n;
+
+// ---- merged form: the device-side tables ----
+// The image of a launch depends on the plan, the batch size, the flags and the workspace / gradient pointers only, so a training loop builds
+// the same two images (LGT part, data part) every step.  Uploaded images are kept per device and found again by content: a hit costs one
+// memcmp on the host and nothing on the stream.  A miss takes the least recently filled slot; the device is drained first (a launch that
+// still reads the slot, on whatever stream, has finished; the slot's host copy is no longer the source of a pending transfer).
+// The content includes the workspace and gradient-buffer POINTERS: a caller whose gradient buffer moves from step to step misses twice per
+// backward (counter [2] of reduce_queue_stats).  The 16 images of a device (630 KB) are allocated at the first launch there and live as long
+// as the library.
+namespace {
+constexpr int RQ_SLOTS = 16;
+struct RqSlot { std::vector<char> host; uint64_t hash = 0; };
+struct RqCache {
+    ReduceImage* dev = nullptr;   // RQ_SLOTS images
+    RqSlot slot[RQ_SLOTS];
+    int next_victim = 0;
+};
+std::mutex g_rq_mu;
+RqCache* g_rq_cache[64];
+size_t image_bytes(const ReduceImage& im) { return offsetof(ReduceImage, j) + (size_t)im.njobs * sizeof(ReduceJob); }
+uint64_t fnv1a(const char* p, size_t n) {
+    uint64_t h = 1469598103934665603ull;
+    const uint64_t* q = reinterpret_cast<const uint64_t*>(p);
+    for (size_t k = 0; k < n / 8; ++k) { h ^= q[k]; h *= 1099511628211ull; }
+    return h;   // (image_bytes is a multiple of 8)
+}
+// No two heads of one launch may touch the same destination element: their workgroups run concurrently.  Extents are sorted; where two
+// overlap as intervals they may still interleave (the 3 x 3 taps of a depthwise weight are nine jobs of stride 9, the two halves of the
+// fusion conv's weight two jobs of row pitch 2E): same pitch and disjoint column windows.  Anything else is an error.
+struct RqExtent { uintptr_t lo, hi; long ld; long cols; int job; };
+bool extents_clash(const RqExtent& a, const RqExtent& b) {
+    const long ld = a.ld ? a.ld : b.ld;
+    if (!ld) return true;                              // two single rows whose intervals overlap
+    if ((a.ld && a.ld != ld) || (b.ld && b.ld != ld)) return true;
+    if (a.cols > ld || b.cols > ld) return true;
+    const long d = (long)(((b.lo - a.lo) / sizeof(float)) % (uintptr_t)ld);   // b's first column in a's rows (b.lo >= a.lo)
+    return !(d >= a.cols && d + b.cols <= ld);
+}
+int check_disjoint(const ReduceImage& im) {
+    std::vector<RqExtent> ex;
+    ex.reserve(2 * (size_t)im.nheads);
+    for (int k = 0; k < im.nheads; ++k) {
+        const ReduceJob& j = im.j[k];
+        if (j.rows_valid <= 0 || j.cols_valid <= 0) continue;
+        float* dsts[2] = {j.dst, j.dst2};
+        for (float* d : dsts) {
+            if (!d) continue;
+            RqExtent e;
+            e.lo = reinterpret_cast<uintptr_t>(d);
+            e.hi = reinterpret_cast<uintptr_t>(d + (long)(j.rows_valid - 1) * j.ld + j.cols_valid);
+            e.ld = j.rows_valid > 1 ? j.ld : 0;   // a single row fits any pitch
+            e.cols = j.cols_valid;
+            e.job = k;
+            ex.push_back(e);
+        }
     }
-    dim3 grid((unsigned)((nmax + 15) / 16), (unsigned)tab.n);
-#ifdef LG_RQ_DEBUG
-    fprintf(stderr, "[rq] flush: %d jobs, grid.x %u:", tab.n, grid.x);
-    for (int k = 0; k < tab.n; ++k) fprintf(stderr, " (%ld sl x %d x %d)", tab.j[k].nslices, tab.j[k].rows, tab.j[k].cols);
-    fprintf(stderr, "\n");
-#endif
-    k_reduce_jobs<<<grid, 256, 0, stream>>>(tab);
-    tab.n = 0;
+    std::sort(ex.begin(), ex.end(), [](const RqExtent& a, const RqExtent& b) { return a.lo < b.lo; });
+    for (size_t a = 0; a < ex.size(); ++a)
+        for (size_t b = a + 1; b < ex.size() && ex[b].lo < ex[a].hi; ++b)
+            if (extents_clash(ex[a], ex[b])) {
+                lg_set_error("reduce queue: jobs %d and %d of one launch add into the same gradient elements", ex[a].job, ex[b].job);
+                return -4;
+            }
+    return 0;
+}
+// launches k_reduce_jobs on the device copy of `im` (uploaded on `s` first if it is not there yet).  The launch is queued UNDER the lock: a miss of
+// another host thread may then take any slot -- it drains the device first, and the launch that reads the slot is already in its stream
+int launch_image(const ReduceImage& im, hipStream_t s) {
+    const size_t bytes = image_bytes(im);
+    const char* src = reinterpret_cast<const char*>(&im);
+    const uint64_t h = fnv1a(src, bytes);
+    std::lock_guard<std::mutex> lock(g_rq_mu);
+    RqCache*& c = g_rq_cache[DeviceOnce::dev()];
+    if (!c) {
+        RqCache* nc = new RqCache;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&nc->dev), sizeof(ReduceImage) * RQ_SLOTS);
+        if (e != hipSuccess) { delete nc; lg_set_error("reduce queue: hipMalloc(job tables): %s", hipGetErrorString(e)); return (int)e; }
+        c = nc;
+    }
+    for (int k = 0; k < RQ_SLOTS; ++k) {
+        const RqSlot& sl = c->slot[k];
+        if (sl.hash == h && sl.host.size() == bytes && memcmp(sl.host.data(), src, bytes) == 0) {
+            k_reduce_jobs<<<(unsigned)im.total_wgs, 256, 0, s>>>(c->dev + k);
+            LG_CHECK_LAUNCH();
+            return 0;
+        }
+    }
+    int rc = check_disjoint(im);
+    if (rc) return rc;
+    const int k = c->next_victim;
+    c->next_victim = (k + 1) % RQ_SLOTS;
+    RqSlot& sl = c->slot[k];
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) { lg_set_error("reduce queue: hipDeviceSynchronize: %s", hipGetErrorString(e)); return (int)e; }
+    sl.host.clear();   // (invalid until the transfer is queued)
+    sl.hash = 0;
+    e = hipMemcpyAsync(c->dev + k, src, bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);   // `im` is the caller's staging buffer
+    if (e != hipSuccess) { lg_set_error("reduce queue: upload of a job table: %s", hipGetErrorString(e)); return (int)e; }
+    sl.host.assign(src, src + bytes);
+    sl.hash = h;
+    g_rq_stats[2]++;
+    k_reduce_jobs<<<(unsigned)im.total_wgs, 256, 0, s>>>(c->dev + k);
     LG_CHECK_LAUNCH();
     return 0;
 }
+}  // namespace
+
+// debug export (tests/test_reduce_variant_cpu.py; host only): the destination check of a merged launch on n made-up jobs -- job k adds into
+// rows_valid[k] x cols_valid[k] elements of row pitch ld[k] that start dst_off[k] floats into one buffer (dst2_off[k] >= 0: a second destination).
+// 0 = no two jobs share an element, -4 (error set) otherwise
+extern "C" __attribute__((visibility("default"))) int lg_debug_reduce_disjoint(int n, const long long* dst_off, const long long* dst2_off,
+                                                                                const int* rows_valid, const int* cols_valid, const int* ld) {
+    if (n < 0 || n > LG_RQ_MAX_JOBS || !dst_off || !dst2_off || !rows_valid || !cols_valid || !ld) return -1;
+    static thread_local ReduceImage im;
+    float* const base = reinterpret_cast<float*>((uintptr_t)1 << 32);   // never dereferenced
+    for (int k = 0; k < n; ++k) {
+        ReduceJob& j = im.j[k];
+        j = ReduceJob();
+        j.slab = nullptr; j.dst = base + dst_off[k]; j.dst2 = dst2_off[k] >= 0 ? base + dst2_off[k] : nullptr;
+        j.rows = j.rows_valid = rows_valid[k]; j.cols = j.cols_valid = cols_valid[k]; j.ld = ld[k];
+    }
+    im.nheads = im.njobs = n;
+    return check_disjoint(im);
+}
+
+int ReduceQueue::flush() {
+    off = 0;
+    if (n == 0) return 0;
+    const int nj = n;
+    n = 0;
+    g_rq_stats[0]++;
+    if (per_block) {
+        static thread_local ReduceJobTable tab;   // (nj <= LG_MAX_REDUCE_JOBS: push() drains the queue there)
+        long nmax = 0;
+        for (int k = 0; k < nj; ++k) {
+            tab.j[k] = jobs[k];
+            const long m = (long)jobs[k].rows * jobs[k].cols;
+            if (m > nmax) nmax = m;
+        }
+        tab.n = nj;
+        dim3 grid((unsigned)((nmax + 15) / 16), (unsigned)nj);
+        k_reduce_jobs_tab<<<grid, 256, 0, stream>>>(tab);
+        LG_CHECK_LAUNCH();
+        return 0;
+    }
+    // chains: a job whose destination an earlier job of the table already has joins that job's chain (same output shape; anything else is
+    // left to check_disjoint).  Heads keep their order and come first in the image, then the other links.
+    static thread_local ReduceImage im;
+    static thread_local int head_of[LG_RQ_MAX_JOBS], tail_of[LG_RQ_MAX_JOBS], slot_of[LG_RQ_MAX_JOBS], heads[LG_RQ_MAX_JOBS], prev_of[LG_RQ_MAX_JOBS];
+    static thread_local int by_dst[4 * LG_RQ_MAX_JOBS];   // open-addressing table of the heads, keyed by destination: the search is linear in the jobs
+    const auto t0 = std::chrono::steady_clock::now();
+    memset(by_dst, 0xff, sizeof(by_dst));
+    int nheads = 0;
+    for (int i = 0; i < nj; ++i) {
+        const ReduceJob& a = jobs[i];
+        int h = -1;
+        unsigned p = (unsigned)((reinterpret_cast<uintptr_t>(a.dst) >> 2) * 0x9E3779B97F4A7C15ull >> 40) % (4 * LG_RQ_MAX_JOBS);
+        for (; by_dst[p] >= 0; p = (p + 1) % (4 * LG_RQ_MAX_JOBS)) {
+            const ReduceJob& b = jobs[by_dst[p]];
+            if (b.dst == a.dst && b.dst2 == a.dst2 && b.rows == a.rows && b.cols == a.cols && b.ld == a.ld && b.rows_valid == a.rows_valid &&
+                b.cols_valid == a.cols_valid) {
+                h = by_dst[p];
+                break;
+            }
+        }
+        if (h < 0) { by_dst[p] = i; heads[nheads++] = i; head_of[i] = i; tail_of[i] = i; prev_of[i] = -1; }
+        else { head_of[i] = h; prev_of[i] = tail_of[h]; tail_of[h] = i; }
+    }
+    int pos = 0;
+    for (int k = 0; k < nheads; ++k) slot_of[heads[k]] = pos++;
+    for (int i = 0; i < nj; ++i) if (head_of[i] != i) slot_of[i] = pos++;
+    memset(&im, 0, offsetof(ReduceImage, j));
+    for (int i = 0; i < nj; ++i) {
+        ReduceJob& d = im.j[slot_of[i]];
+        d = jobs[i];
+        d.next = -1;
+        d.v4 = reduce_job_v4(jobs[i]) ? 1 : 0;
+    }
+    for (int i = 0; i < nj; ++i) {
+        if (prev_of[i] >= 0) im.j[slot_of[prev_of[i]]].next = slot_of[i];
+        if (!im.j[slot_of[i]].v4) im.j[slot_of[head_of[i]]].v4 = 0;   // a chain runs in the form all of its links can
+    }
+    long total = 0;
+    for (int k = 0; k < nheads; ++k) {
+        im.wg_start[k] = (int)total;
+        total += reduce_job_wgs(im.j[k], im.j[k].v4 == 1);
+    }
+    if (total <= 0 || total > 0x3fffffffL) { lg_set_error("reduce queue: %ld workgroups in one launch", total); return -4; }
+    im.nheads = nheads; im.njobs = nj; im.total_wgs = (int)total;
+#ifdef LG_RQ_DEBUG
+    fprintf(stderr, "[rq] flush: %d jobs, %d chains, %ld workgroups\n", nj, nheads, total);
+#endif
+    const int rc = launch_image(im, stream);
+    if (g_rq_stats[3].load() < nj) g_rq_stats[3] = nj;
+    if (g_rq_stats[5].load() < nheads) g_rq_stats[5] = nheads;
+    g_rq_stats[4] += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
+}
 int ReduceQueue::push(const ReduceJob& j) {
-    if (tab.n == LG_MAX_REDUCE_JOBS) {
+    if (n == (per_block ? LG_MAX_REDUCE_JOBS : LG_RQ_MAX_JOBS)) {
         // the slabs already handed out stay valid: only the table is drained (off is restored)
         const size_t keep = off;
+        g_rq_stats[1]++;
         int rc = flush();
         off = keep;
         if (rc) return rc;
     }
-    tab.j[tab.n++] = j;
+    jobs[n++] = j;
     return 0;
 }
 float* ReduceQueue::take(size_t nfloats) {
     nfloats = (nfloats + 63) & ~(size_t)63;
     if (nfloats > cap) { lg_set_error("reduce queue: slab of %zu floats exceeds the arena (%zu)", nfloats, cap); return nullptr; }
-    if (off + nfloats > cap && flush()) return nullptr;
+    if (off + nfloats > cap) {
+        g_rq_stats[1]++;
+        if (flush()) return nullptr;
+    }
     float* p = arena + off;
     off += nfloats;
     return p;
@@ -355,11 +616,11 @@ static int launch_reduce_slab2(const float* slab, long nslices, int rows, int co
 }
 int launch_reduce_job(const ReduceJob& j, hipStream_t s) {
     if (tl_rq) return tl_rq->push(j);
-    ReduceJobTable t;
+    static thread_local ReduceJobTable t;
     t.j[0] = j;
     t.n = 1;
     const long n = (long)j.rows * j.cols;
-    k_reduce_jobs<<<dim3((unsigned)((n + 15) / 16), 1), 256, 0, s>>>(t);
+    k_reduce_jobs_tab<<<dim3((unsigned)((n + 15) / 16), 1), 256, 0, s>>>(t);
     LG_CHECK_LAUNCH();
     return 0;
 }
