@@ -62,7 +62,7 @@ extern "C" {
 /* kernel ids for the live HIP-event timing facility (lg_prof_*) */
 enum lg_kernel_id {
     LG_K_NONE = 0, LG_K_FFN1, LG_K_FFN2, LG_K_FFT, LG_K_ATTN, LG_K_UPFUSE, LG_K_DOWN, LG_K_EMBED, LG_K_TAIL, LG_K_DATASTEP,
-    LG_K_FFN1_BWD, LG_K_FFN2_BWD, LG_K_FFT_BWD, LG_K_ATTN_BWD, LG_K_WGRAD, LG_K_COUNT
+    LG_K_FFN1_BWD, LG_K_FFN2_BWD, LG_K_FFT_BWD, LG_K_ATTN_BWD, LG_K_WGRAD, LG_K_BATCH, LG_K_COUNT
 };
 
 typedef struct lg_config {
@@ -257,6 +257,25 @@ int lg_iqa_ref(const float* pred, const float* gt, double* out, int32_t B, int32
 /* metrics.no_ref_evaluate of every image: pred [B,C,H,W], pan [B,1,H,W], ms [B,C,H/4,W/4] fp32 -> out [B,3] fp64 = D_lambda, D_s, QNR */
 int lg_iqa_no_ref(const float* pred, const float* pan, const float* ms, double* out, int32_t B, int32_t C, int32_t H, int32_t W,
                   float scale, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- device-resident dataset (lgteun_amd/resident.py; kernels in lgteun_amd/csrc/k_batch.hip) ----
+ * The store holds a whole data set on the device in the files' sample type: pan [N,1,H,W], lr [N,C,h,w], mul [N,C,H,W] (optional) and the
+ * fp32 pan_l [N,1,h,w], with H = 4 h and W = 4 w.  Arguments are validated before any HIP call. */
+#define LG_DT_U8 0
+#define LG_DT_U16 1
+#define LG_DT_F32 2
+/* input_pan_l of `planes` PAN planes [H, W] of sample type `dtype`: two levels of the 5 x 5 binomial pyramid ([1 4 6 4 1] / 16 per axis,
+ * BORDER_REFLECT_101, even rows and columns) -> pan_l [planes, H/4, W/4] fp32.  Integer planes are computed in integer arithmetic (exact; one
+ * rounding, to fp32), float planes in fp64.  H, W: multiples of 4, at least 8. */
+int lg_pyr_down2(const void* pan, float* pan_l, int64_t planes, int32_t H, int32_t W, int32_t dtype, void* stream);
+/* One training / evaluation batch in one launch: item b of the outputs is store item idx[idx_offset + b] (a DEVICE int32 list; values are
+ * clamped into 0 .. N-1), converted to fp32, flipped as the device word *flips says (bit 0: up-down, bit 1: left-right; flips == NULL: no
+ * flip) and scaled: n_div (0, 1 or 2) correctly rounded fp32 divisions by `divisor`, then one fp32 multiplication by post_scale unless it
+ * is 1.  Outputs are contiguous fp32 NCHW: o_pan [B,1,H,W], o_lr [B,C,h,w], o_mul [B,C,H,W] (NULL together with mul), o_pan_l [B,1,h,w].
+ * All arrays 16-byte aligned.  1 <= B <= 65535, 1 <= C <= 16. */
+int lg_batch_assemble(const void* pan, const void* lr, const void* mul, const float* pan_l, int64_t N, const int32_t* idx, int64_t idx_offset,
+                      const uint32_t* flips, float* o_pan, float* o_lr, float* o_mul, float* o_pan_l, int32_t B, int32_t C, int32_t H, int32_t W,
+                      int32_t h, int32_t w, int32_t dtype, float divisor, int32_t n_div, float post_scale, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,3 +6,4 @@ from .unlg_former import Pansharpening, UnlgFormer  # noqa: F401
 from .engine import Engine, FusedAdam, FusedAdamW, FusedRMSprop, FusedSGD, canonical_names  # noqa: F401
 from .dataset import DATASETS, PSDataset, PrefetchLoader, ShardedSampler, build_dataset, build_loader  # noqa: F401
 from .device_metrics import no_ref_evaluate_batch, ref_evaluate_batch  # noqa: F401
+from .resident import ResidentLoader, ResidentStore  # noqa: F401

@@ -19,7 +19,7 @@ LG_FLAG_BWD_DATA = 16
 LG_FLAG_CHAINED = 32
 LG_FLAG_DEFER_DEAD = 64
 KERNEL_IDS = {n: i for i, n in enumerate(['none', 'ffn1', 'ffn', 'fft', 'attn', 'upfuse', 'down', 'embed', 'tail', 'datastep', 'ffn1_bwd',
-                                           'ffn2_bwd', 'fft_bwd', 'attn_bwd', 'wgrad'])}
+                                           'ffn2_bwd', 'fft_bwd', 'attn_bwd', 'wgrad', 'batch'])}
 
 
 class LgConfig(ctypes.Structure):
@@ -43,6 +43,7 @@ LG_VAR_ATTN_BWD_RESTATS = 1 << 16
 LG_VAR_REDUCE_PER_BLOCK = 1 << 17
 LG_OPT_ADAM, LG_OPT_ADAMW, LG_OPT_SGD, LG_OPT_RMSPROP = 0, 1, 2, 3      # lg_optim_step: algo
 LG_OPT_AMSGRAD, LG_OPT_NESTEROV, LG_OPT_CENTERED = 1, 2, 4             # lg_optim_step: flags
+LG_DT_U8, LG_DT_U16, LG_DT_F32 = 0, 1, 2                                # lg_pyr_down2 / lg_batch_assemble: sample type of the store
 LG_ABI_VERSION = 2   # include/lgteun_hip.h: checked against lg_abi_version() when the library is loaded
 
 
@@ -132,6 +133,9 @@ SIGNATURES = {
     'lg_iqa_ref': (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_size_t, c_void_p]),
     'lg_iqa_no_ref': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_size_t,
                                 c_void_p]),
+    'lg_pyr_down2': (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
+    'lg_batch_assemble': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, c_float, c_void_p]),
 }
 
 

@@ -101,7 +101,7 @@ extern "C" int lg_prof_read(double* total_ms, int64_t* launches) {
 }
 extern "C" const char* lg_kernel_name(int32_t k) {
     static const char* names[LG_K_COUNT] = {"none", "k_ffn1", "fused FFN forward (k_ffn_xr e=16 / k_ffn_x32 e=32 / k_ffn1_x64+k_ffn2_x64 e=64)", "k_fftmix", "k_attn", "k_upfuse", "k_down", "k_embed", "k_tail",
-                                            "k_resample_dw", "k_ffn1_bwd", "k_ffn2_bwd", "k_fftmix_bwd", "k_attn_bwd", "k_wgrad"};
+                                            "k_resample_dw", "k_ffn1_bwd", "k_ffn2_bwd", "k_fftmix_bwd", "k_attn_bwd", "k_wgrad", "k_batch_assemble"};
     return (k >= 0 && k < LG_K_COUNT) ? names[k] : "?";
 }
 
@@ -706,6 +706,19 @@ extern "C" int lg_l2_loss(const float* out, const float* gt, float* dout, float*
                                                 (int)(next_slot.fetch_add(1) % LG_L2_SLOTS));
     LG_CHECK_LAUNCH();
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// device-resident dataset (k_batch.hip)
+// ------------------------------------------------------------------------------------------------
+extern "C" int lg_pyr_down2(const void* pan, float* pan_l, int64_t planes, int32_t H, int32_t W, int32_t dtype, void* stream) {
+    return launch_pyr_down2(pan, pan_l, planes, H, W, dtype, (hipStream_t)stream);
+}
+extern "C" int lg_batch_assemble(const void* pan, const void* lr, const void* mul, const float* pan_l, int64_t N, const int32_t* idx, int64_t idx_offset,
+                                 const uint32_t* flips, float* o_pan, float* o_lr, float* o_mul, float* o_pan_l, int32_t B, int32_t C, int32_t H, int32_t W,
+                                 int32_t h, int32_t w, int32_t dtype, float divisor, int32_t n_div, float post_scale, void* stream) {
+    return launch_batch_assemble(pan, lr, mul, pan_l, N, idx, idx_offset, flips, o_pan, o_lr, o_mul, o_pan_l, B, C, H, W, h, w, dtype, divisor, n_div,
+                                 post_scale, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,0 +1,239 @@
+// Device-resident dataset (lgteun_amd/resident.py): the one-time PAN pyramid of the whole set and the per-batch gather.
+//
+//   k_pyr_down2<T>       input_pan_l of every stored PAN plane: two levels of cv2.pyrDown (5 x 5 binomial, BORDER_REFLECT_101, even rows and
+//                        columns), dataset.pyr_down(pyr_down(.)).  Integer planes in integer arithmetic -- level 1 times 2^8 is below 2^24, level 2
+//                        times 2^16 below 2^32 -- so every sum is exact and the one rounding is the conversion to fp32, like the host's
+//                        float64 -> float32; float planes in fp64.
+//   k_batch_assemble<T>  one launch per batch: gathers B stored items by a device index list into fresh fp32 NCHW tensors, with the batch's
+//                        up-down / left-right flip, 0 - 2 correctly rounded fp32 divisions (dataset normalisation) and an optional fp32 multiply.
+//                        A streaming kernel: one 16-byte load per lane (16 uint8 / 8 uint16 / 4 float), float4 stores; a row whose width is not
+//                        a multiple of the vector ends in a scalar chunk, and a chunk whose addresses are not 16-byte aligned (rows of such
+//                        widths alternate) goes the scalar way too.
+#include "common.h"
+#include "kernels.h"
+
+// ------------------------------------------------------------------------------------------------
+// pyramid
+// ------------------------------------------------------------------------------------------------
+#define PYR_T 8                       // level-2 outputs per tile edge
+#define PYR_L1 (2 * PYR_T + 3)        // level-1 values per tile edge
+#define PYR_NT 256
+
+template <typename T> struct PyrAcc { typedef uint32_t type; };
+template <> struct PyrAcc<float> { typedef double type; };
+
+__device__ __forceinline__ int reflect101(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
+
+template <typename T>
+__global__ __launch_bounds__(PYR_NT) void k_pyr_down2(const T* __restrict__ in, float* __restrict__ out, int H, int W, int tiles_x, int tiles) {
+    typedef typename PyrAcc<T>::type A;
+    constexpr bool INT = !__is_same(T, float);
+    __shared__ A l1[PYR_L1][PYR_L1 + 1];
+    const int h1 = H >> 1, w1 = W >> 1, h2 = H >> 2, w2 = W >> 2;
+    const int plane = blockIdx.x / tiles, tile = blockIdx.x - plane * tiles;
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const int oy0 = ty * PYR_T, ox0 = tx * PYR_T;
+    const T* __restrict__ p = in + (size_t)plane * H * W;
+    const A kw[5] = {(A)1, (A)4, (A)6, (A)4, (A)1};
+    // level 1 at the (reflected) positions the tile's level-2 taps touch
+    for (int t = threadIdx.x; t < PYR_L1 * PYR_L1; t += PYR_NT) {
+        const int ry = t / PYR_L1, rx = t - ry * PYR_L1;
+        const int py = reflect101(2 * oy0 - 2 + ry, h1), px = reflect101(2 * ox0 - 2 + rx, w1);
+        A acc = 0;
+        if ((unsigned)py < (unsigned)h1 && (unsigned)px < (unsigned)w1) {   // positions past a partial tile's own taps reflect out of the plane: never read below
+#pragma unroll
+            for (int a = 0; a < 5; ++a) {
+                const T* __restrict__ row = p + (size_t)reflect101(2 * py + a - 2, H) * W;
+                A r = 0;
+#pragma unroll
+                for (int b = 0; b < 5; ++b) r += kw[b] * (A)row[reflect101(2 * px + b - 2, W)];
+                acc += kw[a] * (INT ? r : r * (A)0.0625);
+            }
+            if (!INT) acc = acc * (A)0.0625;
+        }
+        l1[ry][rx] = acc;
+    }
+    __syncthreads();
+    if (threadIdx.x < PYR_T * PYR_T) {
+        const int ly = threadIdx.x / PYR_T, lx = threadIdx.x % PYR_T;
+        const int oy = oy0 + ly, ox = ox0 + lx;
+        if (oy < h2 && ox < w2) {
+            A acc = 0;
+#pragma unroll
+            for (int a = 0; a < 5; ++a) {
+                A r = 0;
+#pragma unroll
+                for (int b = 0; b < 5; ++b) r += kw[b] * l1[2 * ly + a][2 * lx + b];
+                acc += kw[a] * (INT ? r : r * (A)0.0625);
+            }
+            float v;
+            if (INT) v = (float)acc * (1.0f / 65536.0f);          // round-to-nearest-even conversion, then an exact power of two
+            else v = (float)(acc * (A)0.0625);
+            out[(size_t)plane * h2 * w2 + (size_t)oy * w2 + ox] = v;
+        }
+    }
+}
+
+static const char* pyr_check(const void* pan, const float* pan_l, int64_t planes, int H, int W, int dtype) {
+    if (!pan || !pan_l) return "null pointer";
+    if (dtype < LG_DT_U8 || dtype > LG_DT_F32) return "unknown sample type (LG_DT_U8 / LG_DT_U16 / LG_DT_F32)";
+    if (H < 8 || W < 8 || (H & 3) || (W & 3) || H > 32768 || W > 32768) return "H and W must be multiples of 4 in 8 .. 32768";
+    const int64_t tiles = (int64_t)((H / 4 + PYR_T - 1) / PYR_T) * ((W / 4 + PYR_T - 1) / PYR_T);
+    if (planes <= 0 || planes * tiles > 0x7fffffffll) return "planes must be positive and planes x tiles below 2^31";
+    return nullptr;
+}
+
+int launch_pyr_down2(const void* pan, float* pan_l, int64_t planes, int H, int W, int dtype, hipStream_t s) {
+    if (const char* why = pyr_check(pan, pan_l, planes, H, W, dtype)) { lg_set_error("pyr_down2: %s", why); return -1; }
+    const int tiles_x = (W / 4 + PYR_T - 1) / PYR_T, tiles = tiles_x * ((H / 4 + PYR_T - 1) / PYR_T);
+    const unsigned grid = (unsigned)(planes * tiles);
+    if (dtype == LG_DT_U8) k_pyr_down2<uint8_t><<<grid, PYR_NT, 0, s>>>((const uint8_t*)pan, pan_l, H, W, tiles_x, tiles);
+    else if (dtype == LG_DT_U16) k_pyr_down2<uint16_t><<<grid, PYR_NT, 0, s>>>((const uint16_t*)pan, pan_l, H, W, tiles_x, tiles);
+    else k_pyr_down2<float><<<grid, PYR_NT, 0, s>>>((const float*)pan, pan_l, H, W, tiles_x, tiles);
+    LG_CHECK_LAUNCH();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// batch assembly
+// ------------------------------------------------------------------------------------------------
+#define BA_NT 256
+#define BA_FLIP_UD 1u
+#define BA_FLIP_LR 2u
+
+struct BatchArgs {
+    const void *pan, *lr, *mul;       // store: [N,1,H,W], [N,C,h,w], [N,C,H,W] or null
+    const float* pan_l;               // store: [N,1,h,w]
+    float *o_pan, *o_lr, *o_mul, *o_pan_l;
+    const int32_t* idx;               // B store indices of this batch
+    const uint32_t* flips;            // the batch's flip word (bit 0 up-down, bit 1 left-right) or null
+    int N, C, H, W, h, w;
+    float divisor, post_scale;
+    int n_div, has_scale;
+};
+
+template <typename T> struct Vec16 { static constexpr int N = 16 / (int)sizeof(T); };
+
+// the 16 bytes of one load as Vec16<T>::N floats
+__device__ __forceinline__ void unpack16(const uint4& r, float (&f)[16], const uint8_t*) {
+    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+    for (int i = 0; i < 16; ++i) f[i] = (float)((w[i >> 2] >> (8 * (i & 3))) & 0xffu);
+}
+__device__ __forceinline__ void unpack16(const uint4& r, float (&f)[8], const uint16_t*) {
+    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+    for (int i = 0; i < 8; ++i) f[i] = (float)((w[i >> 1] >> (16 * (i & 1))) & 0xffffu);
+}
+__device__ __forceinline__ void unpack16(const uint4& r, float (&f)[4], const float*) {
+    f[0] = __uint_as_float(r.x); f[1] = __uint_as_float(r.y); f[2] = __uint_as_float(r.z); f[3] = __uint_as_float(r.w);
+}
+
+__device__ __forceinline__ float ba_scale(float x, float divisor, int n_div, float post_scale, int has_scale) {
+    if (n_div > 0) x = __fdiv_rn(x, divisor);
+    if (n_div > 1) x = __fdiv_rn(x, divisor);
+    if (has_scale) x = __fmul_rn(x, post_scale);
+    return x;
+}
+
+// chunk q of a [planes, rows, width] block of one item: VEC consecutive output elements of one row
+template <typename T>
+__device__ __forceinline__ void ba_chunk(const T* __restrict__ src, float* __restrict__ dst, int rows, int width, int cpr, int q,
+                                         uint32_t flips, const BatchArgs& a) {
+    constexpr int V = Vec16<T>::N;
+    const int row = q / cpr, c = q - row * cpr;
+    const int plane = row / rows, y = row - plane * rows;
+    const int ys = (flips & BA_FLIP_UD) ? rows - 1 - y : y;
+    const bool lrf = (flips & BA_FLIP_LR) != 0;
+    const T* __restrict__ srow = src + ((size_t)plane * rows + ys) * width;
+    float* __restrict__ drow = dst + ((size_t)plane * rows + y) * width;
+    const int e0 = c * V;
+    if (e0 + V <= width) {
+        const T* sp = srow + (lrf ? width - e0 - V : e0);      // the mirrored chunk, reversed in registers below
+        float* dp = drow + e0;
+        if ((((uintptr_t)sp | (uintptr_t)dp) & 15) == 0) {
+            const uint4 raw = *reinterpret_cast<const uint4*>(sp);
+            float f[V];
+            unpack16(raw, f, (const T*)nullptr);
+#pragma unroll
+            for (int i = 0; i < V; ++i) f[i] = ba_scale(f[i], a.divisor, a.n_div, a.post_scale, a.has_scale);
+#pragma unroll
+            for (int i = 0; i < V; i += 4) {
+                const float4 o = lrf ? make_float4(f[V - 1 - i], f[V - 2 - i], f[V - 3 - i], f[V - 4 - i]) : make_float4(f[i], f[i + 1], f[i + 2], f[i + 3]);
+                *reinterpret_cast<float4*>(dp + i) = o;
+            }
+            return;
+        }
+    }
+    const int e1 = e0 + V < width ? e0 + V : width;
+    for (int e = e0; e < e1; ++e)
+        drow[e] = ba_scale((float)srow[lrf ? width - 1 - e : e], a.divisor, a.n_div, a.post_scale, a.has_scale);
+}
+
+template <typename T>
+__global__ __launch_bounds__(BA_NT) void k_batch_assemble(const BatchArgs a, int cprW, int cprw, int cprp, int n_pan, int n_mul, int n_lr, int n_pl) {
+    constexpr int V = Vec16<T>::N;
+    (void)V;
+    const int b = blockIdx.y;
+    int q = blockIdx.x * BA_NT + threadIdx.x;
+    int n = a.idx[b];
+    n = n < 0 ? 0 : (n >= a.N ? a.N - 1 : n);              // an index outside the store never becomes an address
+    const uint32_t flips = a.flips ? *a.flips : 0u;
+    const size_t HW = (size_t)a.H * a.W, hw = (size_t)a.h * a.w;
+    if (q < n_pan) {
+        ba_chunk<T>((const T*)a.pan + (size_t)n * HW, a.o_pan + (size_t)b * HW, a.H, a.W, cprW, q, flips, a);
+        return;
+    }
+    q -= n_pan;
+    if (q < n_mul) {
+        ba_chunk<T>((const T*)a.mul + (size_t)n * a.C * HW, a.o_mul + (size_t)b * a.C * HW, a.H, a.W, cprW, q, flips, a);
+        return;
+    }
+    q -= n_mul;
+    if (q < n_lr) {
+        ba_chunk<T>((const T*)a.lr + (size_t)n * a.C * hw, a.o_lr + (size_t)b * a.C * hw, a.h, a.w, cprw, q, flips, a);
+        return;
+    }
+    q -= n_lr;
+    if (q < n_pl) ba_chunk<float>(a.pan_l + (size_t)n * hw, a.o_pan_l + (size_t)b * hw, a.h, a.w, cprp, q, flips, a);
+}
+
+template <typename T>
+static void ba_launch(const BatchArgs& a, int B, hipStream_t s) {
+    constexpr int V = Vec16<T>::N;
+    const int cprW = (a.W + V - 1) / V, cprw = (a.w + V - 1) / V, cprp = (a.w + 3) / 4;
+    const int n_pan = a.H * cprW, n_mul = a.mul ? a.C * a.H * cprW : 0, n_lr = a.C * a.h * cprw, n_pl = a.h * cprp;
+    const int total = n_pan + n_mul + n_lr + n_pl;
+    k_batch_assemble<T><<<dim3((total + BA_NT - 1) / BA_NT, B), BA_NT, 0, s>>>(a, cprW, cprw, cprp, n_pan, n_mul, n_lr, n_pl);
+}
+
+int launch_batch_assemble(const void* pan, const void* lr, const void* mul, const float* pan_l, int64_t N, const int32_t* idx, int64_t idx_offset,
+                          const uint32_t* flips, float* o_pan, float* o_lr, float* o_mul, float* o_pan_l, int B, int C, int H, int W, int h, int w,
+                          int dtype, float divisor, int n_div, float post_scale, hipStream_t s) {
+    const char* why = nullptr;
+    if (!pan || !lr || !pan_l || !idx || !o_pan || !o_lr || !o_pan_l || ((mul == nullptr) != (o_mul == nullptr))) why = "null pointer (mul and its output go together)";
+    else if (B <= 0 || B > 65535) why = "B must be in 1 .. 65535";
+    else if (C < 1 || C > 16) why = "C must be in 1 .. 16";
+    else if (h <= 0 || w <= 0 || h > 8192 || w > 8192 || H != 4 * h || W != 4 * w) why = "H and W must be 4 x the MS size (MS up to 8192)";
+    else if (dtype < LG_DT_U8 || dtype > LG_DT_F32) why = "unknown sample type (LG_DT_U8 / LG_DT_U16 / LG_DT_F32)";
+    else if (n_div < 0 || n_div > 2) why = "the divide count must be 0, 1 or 2";
+    else if (n_div > 0 && !(divisor > 0.0f && divisor < INFINITY)) why = "the divisor must be positive and finite";
+    else if (!(post_scale == post_scale) || post_scale == INFINITY || post_scale == -INFINITY) why = "the scale must be finite";
+    else if (N <= 0 || N > 0x7fffffffll || idx_offset < 0) why = "N must be in 1 .. 2^31 - 1 and the index offset non-negative";
+    else if ((int64_t)(C + 1) * H * ((W + 3) / 4) + (int64_t)(C + 1) * h * w > 0x7fffffffll) why = "item too large";
+    else if (((uintptr_t)pan | (uintptr_t)lr | (uintptr_t)mul | (uintptr_t)pan_l | (uintptr_t)o_pan | (uintptr_t)o_lr | (uintptr_t)o_mul | (uintptr_t)o_pan_l) & 15)
+        why = "store and output arrays must be 16-byte aligned";
+    if (why) { lg_set_error("batch_assemble: %s", why); return -1; }
+    BatchArgs a;
+    a.pan = pan; a.lr = lr; a.mul = mul; a.pan_l = pan_l;
+    a.o_pan = o_pan; a.o_lr = o_lr; a.o_mul = o_mul; a.o_pan_l = o_pan_l;
+    a.idx = idx + idx_offset; a.flips = flips;
+    a.N = (int)N; a.C = C; a.H = H; a.W = W; a.h = h; a.w = w;
+    a.divisor = divisor; a.post_scale = post_scale; a.n_div = n_div; a.has_scale = post_scale != 1.0f;
+    ProfScope prof(LG_K_BATCH, s);
+    if (dtype == LG_DT_U8) ba_launch<uint8_t>(a, B, s);
+    else if (dtype == LG_DT_U16) ba_launch<uint16_t>(a, B, s);
+    else ba_launch<float>(a, B, s);
+    LG_CHECK_LAUNCH();
+    return 0;
+}

@@ -2,6 +2,11 @@
 #pragma once
 #include "common.h"
 
+// ---------------- device-resident dataset (k_batch.hip; arguments validated before any HIP call) ----------------
+int launch_pyr_down2(const void* pan, float* pan_l, int64_t planes, int H, int W, int dtype, hipStream_t s);
+int launch_batch_assemble(const void* pan, const void* lr, const void* mul, const float* pan_l, int64_t N, const int32_t* idx, int64_t idx_offset,
+                          const uint32_t* flips, float* o_pan, float* o_lr, float* o_mul, float* o_pan_l, int B, int C, int H, int W, int h, int w,
+                          int dtype, float divisor, int n_div, float post_scale, hipStream_t s);
 // ---------------- evaluation indices of lgteun_amd/metrics.py (k_iqa.hip; arguments validated before any HIP call) ----------------
 size_t iqa_workspace_bytes(int B, int C, int H, int W, int no_ref);
 int launch_iqa_ref(const float* pred, const float* gt, double* out, int B, int C, int H, int W, float scale, void* workspace,

@@ -391,12 +391,28 @@ class PrefetchLoader:
             yield moved
 
 
-def build_loader(set_cfg, rank=0, world=1, device=None, seed=0, prefetch_depth=2, evaluation=False):
+def build_loader(set_cfg, rank=0, world=1, device=None, seed=0, prefetch_depth=2, evaluation=False, resident=False, fold_normalize=False,
+                 aug_dict=None):
     """main.py:71-86: `set_cfg` = dict(dataset=dict(type='PSDataset', ...), batch_size=, num_workers=, shuffle=) -> loader.
     With world > 1 the shuffle flag moves into a ShardedSampler (batch_size is per rank); with `device` the loader is wrapped
-    in a PrefetchLoader.  evaluation=True: the sampler does not pad (each image on exactly one rank).  Returns (loader, sampler-or-None)."""
+    in a PrefetchLoader.  evaluation=True: the sampler does not pad (each image on exactly one rank).  Returns (loader, sampler-or-None).
+    resident=True (or `resident=True` inside set_cfg): the set is decoded once and kept on `device`, and the loader is a
+    resident.ResidentLoader -- returns (loader, None); num_workers / pin_memory do not apply, `fold_normalize` and `aug_dict` (arguments
+    or set_cfg keys) are the ResidentLoader's.  Without the flag nothing changes."""
     cfg = dict(set_cfg)
+    resident = bool(cfg.pop('resident', False)) or bool(resident)
+    fold_normalize = bool(cfg.pop('fold_normalize', fold_normalize))
+    aug_dict = cfg.pop('aug_dict', aug_dict)
     cfg['dataset'] = build_dataset(cfg['dataset'])
+    if resident:
+        from .resident import ResidentLoader, ResidentStore
+        if device is None:
+            raise ValueError('build_loader(resident=True) needs the device the set is to live on')
+        ds = cfg['dataset']
+        store = ResidentStore.from_dataset(ds, device)
+        return ResidentLoader(store, cfg.get('batch_size', 1), shuffle=bool(cfg.get('shuffle', False)), rank=rank, world=world, seed=seed,
+                              drop_last=bool(cfg.get('drop_last', False)), evaluation=evaluation, aug_dict=aug_dict,
+                              fold_normalize=fold_normalize, bit_depth=ds.bit_depth, norm_input=ds.norm_input), None
     sampler = None
     if world > 1:
         sampler = ShardedSampler(len(cfg['dataset']), rank, world, shuffle=bool(cfg.pop('shuffle', False)), seed=seed,
