@@ -209,31 +209,45 @@ def feed_forward(P, pre, x):
     return t.permute(0, 2, 3, 1)
 
 
-def lgb(P, pre, x, nblocks):
+def lgb(P, pre, x, nblocks, drop_masks=None, stage=0, blk0=0):
     """LGT.py:222-248.  x [B,H,W,E] -> [B,H,W,E] (the reference's trailing NCHW permute is
-    left to the caller)."""
+    left to the caller).  drop_masks: None (eval) or a callable (stage, blk, B, h, w, e) -> [B,e,h,w]
+    factors of the LGMixer dropout (LGT.py:197-198,215); this LGB's blocks are numbered blk0 .. blk0 + nblocks - 1
+    of stage `stage`, the numbering of lg_op_block (include/lgteun_hip.h)."""
     for j in range(nblocks):
         bp = f'{pre}blocks.{j}.'
         y = layer_norm(x, P[bp + '0.fn.norm.weight'], P[bp + '0.fn.norm.bias'])
-        x = x + lg_mixer(P, bp + '0.fn.fn.', y)
+        mask = None
+        if drop_masks is not None:
+            B, h, w, e = x.shape
+            mask = drop_masks(stage, blk0 + j, B, h, w, e)
+        x = x + lg_mixer(P, bp + '0.fn.fn.', y, mask)
         y = layer_norm(x, P[bp + '1.fn.norm.weight'], P[bp + '1.fn.norm.bias'])
         x = x + feed_forward(P, bp + '1.fn.fn.', y)
     return x
 
 
-def lgt(P, pre, x, num_block=(2, 1)):
-    """LGT.forward, LGT.py:314-344, scales=2.  x [B,C,H,W] -> [B,C,H,W]."""
+def lgt(P, pre, x, num_block=(2, 1), drop_masks=None, stage=None):
+    """LGT.forward, LGT.py:314-344, scales=2.  x [B,C,H,W] -> [B,C,H,W].
+    drop_masks: None, or the callable of lgb() with `stage` = this LGT's stage index, or (stage=None) a callable
+    already bound to its stage: (blk, B, h, w, e) -> [B,e,h,w].  Blocks: 0, 1 encoder; 2 bottleneck; 3, 4 decoder."""
+    dm = drop_masks
+    if drop_masks is not None and stage is None:
+        def dm(_stage, *a):
+            return drop_masks(*a)
+    st = 0 if stage is None else stage
+    n_enc = num_block[0]
     fea = patch_embed(P, pre + 'patch_embed.', x)
-    fea = lgb(P, pre + 'encoder_layers.0.0.', fea, num_block[0])
+    fea = lgb(P, pre + 'encoder_layers.0.0.', fea, num_block[0], dm, st, 0)
     skip = fea.permute(0, 3, 1, 2)
     t = resample(skip, 0.5)
     t = point_conv(t, P[pre + 'encoder_layers.0.1.1.weight'], P[pre + 'encoder_layers.0.1.1.bias'])
-    fea = lgb(P, pre + 'bottleneck.', t.permute(0, 2, 3, 1), num_block[1])
+    fea = lgb(P, pre + 'bottleneck.', t.permute(0, 2, 3, 1), num_block[1], dm, st, n_enc)
     t = resample(fea.permute(0, 3, 1, 2), 2)
     t = point_conv(t, P[pre + 'decoder_layers.0.0.1.weight'], P[pre + 'decoder_layers.0.0.1.bias'])
     t = point_conv(torch.cat([t, skip], dim=1), P[pre + 'decoder_layers.0.1.weight'],
                    P[pre + 'decoder_layers.0.1.bias'])
-    fea = lgb(P, pre + 'decoder_layers.0.2.', t.permute(0, 2, 3, 1), num_block[0])
+    fea = lgb(P, pre + 'decoder_layers.0.2.', t.permute(0, 2, 3, 1), num_block[0], dm, st, n_enc + num_block[1])
     out = point_conv(fea.permute(0, 3, 1, 2), P[pre + 'tail.1.weight'], P[pre + 'tail.1.bias'])
     return out + x
 
@@ -241,12 +255,13 @@ def lgt(P, pre, x, num_block=(2, 1)):
 # --------------------------------------------------------------------------------------
 # whole net  -- models/unlg_former.py:50-67
 # --------------------------------------------------------------------------------------
-def forward(P, ms, pan, stage, mode='live'):
+def forward(P, ms, pan, stage, mode='live', drop_masks=None):
     """Pansharpening.forward.  mode='faithful' executes every stage's LGT like the reference
     (results of stages 0..K-2 are discarded: unlg_former.py:63 never feeds Z_ back, SURVEY D3);
     mode='live' skips them.  Outputs are identical.
     mode='chained' is NOT the reference: the intended unfolding, where the next stage's data step consumes the
-    LGT's output -- the same two functions composed the other way, so it is pinned only through them."""
+    LGT's output -- the same two functions composed the other way, so it is pinned only through them.
+    drop_masks: None (eval), or the callable of lgb(): stage i's LGT draws its five masks as drop_masks(i, blk, B, h, w, e)."""
     if mode not in ('faithful', 'live', 'chained'):
         raise ValueError(mode)
     z = resample(ms, 4)
@@ -254,7 +269,7 @@ def forward(P, ms, pan, stage, mode='live'):
     for i in range(stage):
         z = data_step(P, z, ms, pan, P[f'eta.{i}'])
         if mode != 'live' or i == stage - 1:
-            out = lgt(P, f'prior_module.{i}.', z)
+            out = lgt(P, f'prior_module.{i}.', z, drop_masks=drop_masks, stage=i)
         if mode == 'chained':
             z = out
     return out

@@ -11,7 +11,7 @@ from lgteun_amd.compat import Config
 from lgteun_amd.engine import _ptr, _stream_ptr
 from oracle import detweights as dw
 
-from helpers import state_shapes
+from helpers import mask_tensor, state_shapes
 
 
 def make_module(C, K, salt=0, device='cuda'):
@@ -21,6 +21,17 @@ def make_module(C, K, salt=0, device='cuda'):
     net = net.to(device)
     net.eval()
     return net
+
+
+def device_drop_masks(seed, dtype=torch.float64):
+    """the `drop_masks` callable of oracle.lgb / lgt / forward, drawn from the LIBRARY's export lg_dropout_mask (host tensors)"""
+    lib = _lib.lib()
+
+    def masks(stage, blk, B, h, w, e):
+        out = torch.empty(B * h * w * e, device='cuda')
+        _lib.check(lib.lg_dropout_mask(seed, stage, blk, 0, out.numel(), _ptr(out), _stream_ptr()), 'lg_dropout_mask')
+        return mask_tensor(out.cpu(), B, h, w, e, dtype)
+    return masks
 
 
 class Ops:
@@ -50,11 +61,14 @@ class Ops:
                                             _ptr(tmp), B, _stream_ptr()), 'lg_op_data_step')
         return out
 
-    def lgt(self, stage, z):
+    def dropout_masks(self, seed, dtype=torch.float64):
+        return device_drop_masks(seed, dtype)
+
+    def lgt(self, stage, z, flags=0, seed=0):
         B = z.shape[0]
         out = torch.empty_like(z)
         ws = self.ws(B)
-        _lib.check(self.lib.lg_op_lgt(self.plan, _ptr(self.eng.flat), stage, _ptr(z), _ptr(out), _ptr(ws), ws.numel(), B, 0, 0,
+        _lib.check(self.lib.lg_op_lgt(self.plan, _ptr(self.eng.flat), stage, _ptr(z), _ptr(out), _ptr(ws), ws.numel(), B, flags, seed,
                                       _stream_ptr()), 'lg_op_lgt')
         return out
 
@@ -87,14 +101,14 @@ class Ops:
                                                 _ptr(dz_out), _ptr(dz), _ptr(ws), ws.numel(), B, _stream_ptr()), 'lg_op_data_step_bwd')
         return dz, grads
 
-    def lgt_bwd(self, stage, z, dout):
-        """returns (dz, flat_param_grads) of one LGT (dropout off)"""
+    def lgt_bwd(self, stage, z, dout, flags=0, seed=0):
+        """returns (dz, flat_param_grads) of one LGT; flags: 0 or LG_FLAG_DROPOUT (with seed)"""
         B = z.shape[0]
         dz = torch.empty_like(z)
         grads = torch.zeros_like(self.eng.flat)
         ws = self.ws(B, train=True)
         _lib.check(self.lib.lg_op_lgt_bwd(self.plan, _ptr(self.eng.flat), _ptr(grads), stage, _ptr(z), _ptr(dout), _ptr(dz), _ptr(ws),
-                                          ws.numel(), B, 0, 0, _stream_ptr()), 'lg_op_lgt_bwd')
+                                          ws.numel(), B, flags, seed, _stream_ptr()), 'lg_op_lgt_bwd')
         return dz, grads
 
     def grad_of(self, flat_grads, name):

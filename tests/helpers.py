@@ -82,3 +82,34 @@ def rel_l2(a, b):
     a = np.asarray(a, dtype=np.float64)
     b = np.asarray(b, dtype=np.float64)
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
+
+
+def _dropout_mask_numpy(seed, stage, blk, first, n):
+    """numpy restatement of csrc/common.h mix_seed + dropout_scale (test infrastructure only)"""
+    M = (1 << 64) - 1
+    z = (seed + 0x9E3779B97F4A7C15 * (stage * 8 + blk + 1)) & M
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M
+    z ^= z >> 31
+    idx = np.arange(first, first + n, dtype=np.uint64)
+    pair = idx >> np.uint64(1)                 # round 5: one hash per PAIR of elements, 16 bits of it per element
+    x = (pair + np.uint64(z & 0xffffffff)).astype(np.uint32)
+    x ^= x >> np.uint32(16); x *= np.uint32(0x7feb352d)
+    x ^= np.uint32(z >> 32) ^ (pair >> np.uint64(32)).astype(np.uint32)
+    x ^= x >> np.uint32(15); x *= np.uint32(0x846ca68b)
+    x ^= x >> np.uint32(16)
+    h = np.where((idx & np.uint64(1)) == 1, x >> np.uint32(16), x & np.uint32(0xffff))
+    return np.where(h < np.uint32(6554), np.float32(0), np.float32(1.0 / 0.9))
+
+
+def mask_tensor(flat, B, h, w, e, dtype):
+    """the B * h * w * e flat factors of one block, in the header's order (include/lgteun_hip.h lg_dropout_mask: element
+    i = pixel * e + channel, pixel running over the whole batch in NHWC order), as the [B, e, h, w] tensor oracle.lg_mixer takes"""
+    return flat.reshape(B, h, w, e).permute(0, 3, 1, 2).contiguous().to(dtype)
+
+
+def numpy_drop_masks(seed, dtype=torch.float64):
+    """the `drop_masks` callable of oracle.lgb / lgt / forward, drawn from the numpy restatement"""
+    def masks(stage, blk, B, h, w, e):
+        return mask_tensor(torch.from_numpy(_dropout_mask_numpy(seed, stage, blk, 0, B * h * w * e)), B, h, w, e, dtype)
+    return masks

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import _dropout_mask_numpy
 from oracle import detweights as dw
 
 pytestmark = pytest.mark.gpu
@@ -187,24 +188,6 @@ def test_deferred_dead_stage_forwards_change_nothing(drop):
     assert np.allclose(res[0][0], res[1][0], rtol=1e-6, atol=0)   # the logged loss scalar is summed with float atomics (order varies)
     assert torch.equal(res[0][1], res[1][1]) and torch.equal(res[0][2], res[1][2])
     assert float(res[1][1].abs().max()) > 0
-
-
-def _dropout_mask_numpy(seed, stage, blk, first, n):
-    """numpy restatement of csrc/common.h mix_seed + dropout_scale (test infrastructure only)"""
-    M = (1 << 64) - 1
-    z = (seed + 0x9E3779B97F4A7C15 * (stage * 8 + blk + 1)) & M
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M
-    z ^= z >> 31
-    idx = np.arange(first, first + n, dtype=np.uint64)
-    pair = idx >> np.uint64(1)                 # round 5: one hash per PAIR of elements, 16 bits of it per element
-    x = (pair + np.uint64(z & 0xffffffff)).astype(np.uint32)
-    x ^= x >> np.uint32(16); x *= np.uint32(0x7feb352d)
-    x ^= np.uint32(z >> 32) ^ (pair >> np.uint64(32)).astype(np.uint32)
-    x ^= x >> np.uint32(15); x *= np.uint32(0x846ca68b)
-    x ^= x >> np.uint32(16)
-    h = np.where((idx & np.uint64(1)) == 1, x >> np.uint32(16), x & np.uint32(0xffff))
-    return np.where(h < np.uint32(6554), np.float32(0), np.float32(1.0 / 0.9))
 
 
 def test_dropout_mask_rate_independence_and_restatement():
