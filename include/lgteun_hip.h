@@ -62,7 +62,7 @@ extern "C" {
 /* kernel ids for the live HIP-event timing facility (lg_prof_*) */
 enum lg_kernel_id {
     LG_K_NONE = 0, LG_K_FFN1, LG_K_FFN2, LG_K_FFT, LG_K_ATTN, LG_K_UPFUSE, LG_K_DOWN, LG_K_EMBED, LG_K_TAIL, LG_K_DATASTEP,
-    LG_K_FFN1_BWD, LG_K_FFN2_BWD, LG_K_FFT_BWD, LG_K_ATTN_BWD, LG_K_WGRAD, LG_K_BATCH, LG_K_COUNT
+    LG_K_FFN1_BWD, LG_K_FFN2_BWD, LG_K_FFT_BWD, LG_K_ATTN_BWD, LG_K_WGRAD, LG_K_BATCH, LG_K_SCENE_GATHER, LG_K_SCENE_BLEND, LG_K_COUNT
 };
 
 typedef struct lg_config {
@@ -276,6 +276,38 @@ int lg_pyr_down2(const void* pan, float* pan_l, int64_t planes, int32_t H, int32
 int lg_batch_assemble(const void* pan, const void* lr, const void* mul, const float* pan_l, int64_t N, const int32_t* idx, int64_t idx_offset,
                       const uint32_t* flips, float* o_pan, float* o_lr, float* o_mul, float* o_pan_l, int32_t B, int32_t C, int32_t H, int32_t W,
                       int32_t h, int32_t w, int32_t dtype, float divisor, int32_t n_div, float post_scale, void* stream);
+
+/* ---- tiled scene fusion (lgteun_amd/scene.py; kernels in lgteun_amd/csrc/k_scene.hip) ----
+ * A scene larger than one plan (or off the 16-pixel grid) is cut into overlapping tiles, the tiles go through lgteun_forward in batches and
+ * the outputs are blended back.  The scene is device-resident in the files' sample type: pan [1,H,W], ms [C,H/4,W/4]; H, W multiples of 4
+ * in 16 .. 65536.  Tiles are th x tw PAN pixels, multiples of 16 in 16 .. 1024, not larger than the scene.  The grid of scene.tile_grid: per
+ * axis of length L with tile t and stride s = t - overlap, n = 1 if L == t else ceil((L - t) / s) + 1 tiles at origins min(i * s, L - t);
+ * tiles are numbered row-major (index = iy * nx + ix).  Arguments are validated before any HIP call; the calls allocate nothing and
+ * synchronise nothing. */
+/* Tile batch `first .. first + B - 1` of the origin list (a DEVICE int32 list of n_tiles pairs (oy, ox) in PAN pixels, multiples of 4; values
+ * are clamped into the scene and rounded down to the 4-pixel grid, so no value becomes an address outside it) -> o_pan [B,1,th,tw],
+ * o_ms [B,C,th/4,tw/4], contiguous fp32, scaled like lg_batch_assemble scales: n_div (0, 1 or 2) correctly rounded fp32 divisions by
+ * `divisor`, then one fp32 multiplication by post_scale unless it is 1 (the same device function).  Scene and tile arrays 16-byte aligned.
+ * 1 <= B <= 65535, 1 <= C <= 16. */
+int lg_scene_gather(const void* pan, const void* ms, const int32_t* origins, int64_t n_tiles, int64_t first, float* o_pan, float* o_ms,
+                    int32_t B, int32_t C, int32_t H, int32_t W, int32_t th, int32_t tw, int32_t dtype, float divisor, int32_t n_div,
+                    float post_scale, void* stream);
+/* Adds the outputs `tiles` [B,C,th,tw] of grid tiles first .. first + B - 1 into scene [C,H,W] (fp32).  Call it for consecutive batches in
+ * ascending order on one stream, every tile of the grid exactly once.  overlap: a multiple of 4 in 0 .. min(th, tw) / 2.  The weight of local
+ * coordinate u on an axis of tile side t is (float)min(min(u, t - 1 - u) + 1, overlap + 1) / (float)(overlap + 1), a tile's weight the fp32
+ * product w(y) * w(x).  After the last batch
+ *   (a) a pixel holds (sum_k w_k v_k) / (sum_k w_k) over its covering tiles k in ascending index: the numerator is w_0 v_0 continued by
+ *       fmaf(w_k, v_k, .) in that order, the denominator (sum_y w(y)) * (sum_x w(x)) with both sums in ascending order, and the one
+ *       division is correctly rounded;
+ *   (b) a pixel that one tile alone covers holds that tile's value, bit for bit;
+ *   (c) the bits do not depend on how the tile list was cut into batches (between launches the scene holds the running numerator);
+ *   (d) the scene needs no initialisation: a pixel's lowest-index cover writes it without reading it.
+ * No atomics: within a launch exactly one lane writes a pixel.  tiles and scene 16-byte aligned. */
+int lg_scene_blend(const float* tiles, float* scene, int64_t first, int32_t B, int32_t C, int32_t H, int32_t W, int32_t th, int32_t tw,
+                   int32_t overlap, void* stream);
+/* dst[i] = clip(rint(src[i] * scale), 0, 65535) with one fp32 multiplication and round-half-even (NaN -> 0): data_denormalize followed by the
+ * TIFF writer's conversion.  n: a multiple of 4; src 16-byte, dst 8-byte aligned. */
+int lg_scene_to_u16(const float* src, uint16_t* dst, int64_t n, float scale, void* stream);
 
 #ifdef __cplusplus
 }

@@ -7,3 +7,4 @@ from .engine import Engine, FusedAdam, FusedAdamW, FusedRMSprop, FusedSGD, canon
 from .dataset import DATASETS, PSDataset, PrefetchLoader, ShardedSampler, build_dataset, build_loader  # noqa: F401
 from .device_metrics import no_ref_evaluate_batch, ref_evaluate_batch  # noqa: F401
 from .resident import ResidentLoader, ResidentStore  # noqa: F401
+from .scene import fuse_scene, tile_grid  # noqa: F401

@@ -19,7 +19,7 @@ LG_FLAG_BWD_DATA = 16
 LG_FLAG_CHAINED = 32
 LG_FLAG_DEFER_DEAD = 64
 KERNEL_IDS = {n: i for i, n in enumerate(['none', 'ffn1', 'ffn', 'fft', 'attn', 'upfuse', 'down', 'embed', 'tail', 'datastep', 'ffn1_bwd',
-                                           'ffn2_bwd', 'fft_bwd', 'attn_bwd', 'wgrad', 'batch'])}
+                                           'ffn2_bwd', 'fft_bwd', 'attn_bwd', 'wgrad', 'batch', 'scene_gather', 'scene_blend'])}
 
 
 class LgConfig(ctypes.Structure):
@@ -136,6 +136,10 @@ SIGNATURES = {
     'lg_pyr_down2': (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
     'lg_batch_assemble': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, c_float, c_void_p]),
+    'lg_scene_gather': (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                  c_int32, c_int32, c_float, c_int32, c_float, c_void_p]),
+    'lg_scene_blend': (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    'lg_scene_to_u16': (c_int32, [c_void_p, c_void_p, c_int64, c_float, c_void_p]),
 }
 
 

@@ -101,7 +101,7 @@ extern "C" int lg_prof_read(double* total_ms, int64_t* launches) {
 }
 extern "C" const char* lg_kernel_name(int32_t k) {
     static const char* names[LG_K_COUNT] = {"none", "k_ffn1", "fused FFN forward (k_ffn_xr e=16 / k_ffn_x32 e=32 / k_ffn1_x64+k_ffn2_x64 e=64)", "k_fftmix", "k_attn", "k_upfuse", "k_down", "k_embed", "k_tail",
-                                            "k_resample_dw", "k_ffn1_bwd", "k_ffn2_bwd", "k_fftmix_bwd", "k_attn_bwd", "k_wgrad", "k_batch_assemble"};
+                                            "k_resample_dw", "k_ffn1_bwd", "k_ffn2_bwd", "k_fftmix_bwd", "k_attn_bwd", "k_wgrad", "k_batch_assemble", "k_scene_gather", "k_scene_blend"};
     return (k >= 0 && k < LG_K_COUNT) ? names[k] : "?";
 }
 
@@ -719,6 +719,18 @@ extern "C" int lg_batch_assemble(const void* pan, const void* lr, const void* mu
                                  int32_t h, int32_t w, int32_t dtype, float divisor, int32_t n_div, float post_scale, void* stream) {
     return launch_batch_assemble(pan, lr, mul, pan_l, N, idx, idx_offset, flips, o_pan, o_lr, o_mul, o_pan_l, B, C, H, W, h, w, dtype, divisor, n_div,
                                  post_scale, (hipStream_t)stream);
+}
+extern "C" int lg_scene_gather(const void* pan, const void* ms, const int32_t* origins, int64_t n_tiles, int64_t first, float* o_pan, float* o_ms,
+                               int32_t B, int32_t C, int32_t H, int32_t W, int32_t th, int32_t tw, int32_t dtype, float divisor, int32_t n_div,
+                               float post_scale, void* stream) {
+    return launch_scene_gather(pan, ms, origins, n_tiles, first, o_pan, o_ms, B, C, H, W, th, tw, dtype, divisor, n_div, post_scale, (hipStream_t)stream);
+}
+extern "C" int lg_scene_blend(const float* tiles, float* scene, int64_t first, int32_t B, int32_t C, int32_t H, int32_t W, int32_t th, int32_t tw,
+                              int32_t overlap, void* stream) {
+    return launch_scene_blend(tiles, scene, first, B, C, H, W, th, tw, overlap, (hipStream_t)stream);
+}
+extern "C" int lg_scene_to_u16(const float* src, uint16_t* dst, int64_t n, float scale, void* stream) {
+    return launch_scene_to_u16(src, dst, n, scale, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@
 //                        widths alternate) goes the scalar way too.
 #include "common.h"
 #include "kernels.h"
+#include "sample_io.h"
 
 // ------------------------------------------------------------------------------------------------
 // pyramid
@@ -111,30 +112,6 @@ struct BatchArgs {
     float divisor, post_scale;
     int n_div, has_scale;
 };
-
-template <typename T> struct Vec16 { static constexpr int N = 16 / (int)sizeof(T); };
-
-// the 16 bytes of one load as Vec16<T>::N floats
-__device__ __forceinline__ void unpack16(const uint4& r, float (&f)[16], const uint8_t*) {
-    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-    for (int i = 0; i < 16; ++i) f[i] = (float)((w[i >> 2] >> (8 * (i & 3))) & 0xffu);
-}
-__device__ __forceinline__ void unpack16(const uint4& r, float (&f)[8], const uint16_t*) {
-    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-    for (int i = 0; i < 8; ++i) f[i] = (float)((w[i >> 1] >> (16 * (i & 1))) & 0xffffu);
-}
-__device__ __forceinline__ void unpack16(const uint4& r, float (&f)[4], const float*) {
-    f[0] = __uint_as_float(r.x); f[1] = __uint_as_float(r.y); f[2] = __uint_as_float(r.z); f[3] = __uint_as_float(r.w);
-}
-
-__device__ __forceinline__ float ba_scale(float x, float divisor, int n_div, float post_scale, int has_scale) {
-    if (n_div > 0) x = __fdiv_rn(x, divisor);
-    if (n_div > 1) x = __fdiv_rn(x, divisor);
-    if (has_scale) x = __fmul_rn(x, post_scale);
-    return x;
-}
 
 // chunk q of a [planes, rows, width] block of one item: VEC consecutive output elements of one row
 template <typename T>

@@ -7,6 +7,11 @@ int launch_pyr_down2(const void* pan, float* pan_l, int64_t planes, int H, int W
 int launch_batch_assemble(const void* pan, const void* lr, const void* mul, const float* pan_l, int64_t N, const int32_t* idx, int64_t idx_offset,
                           const uint32_t* flips, float* o_pan, float* o_lr, float* o_mul, float* o_pan_l, int B, int C, int H, int W, int h, int w,
                           int dtype, float divisor, int n_div, float post_scale, hipStream_t s);
+// ---------------- tiled scene fusion (k_scene.hip; arguments validated before any HIP call) ----------------
+int launch_scene_gather(const void* pan, const void* ms, const int32_t* origins, int64_t n_tiles, int64_t first, float* o_pan, float* o_ms,
+                        int B, int C, int H, int W, int th, int tw, int dtype, float divisor, int n_div, float post_scale, hipStream_t s);
+int launch_scene_blend(const float* tiles, float* scene, int64_t first, int B, int C, int H, int W, int th, int tw, int overlap, hipStream_t s);
+int launch_scene_to_u16(const float* src, uint16_t* dst, int64_t n, float scale, hipStream_t s);
 // ---------------- evaluation indices of lgteun_amd/metrics.py (k_iqa.hip; arguments validated before any HIP call) ----------------
 size_t iqa_workspace_bytes(int B, int C, int H, int W, int no_ref);
 int launch_iqa_ref(const float* pred, const float* gt, double* out, int B, int C, int H, int W, float scale, void* workspace,

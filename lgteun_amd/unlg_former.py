@@ -145,6 +145,11 @@ class Pansharpening(nn.Module):
                                'Move the module and inputs to cuda.')
         return self.engine().forward_autograd(ms, pan, training=self.training)
 
+    def fuse_scene(self, ms, pan, **kw):
+        """one scene of any size, MS [C,h,w] / PAN [1,4h,4w], through overlapping tiles of the training size (lgteun_amd/scene.py)"""
+        from .scene import fuse_scene
+        return fuse_scene(self, ms, pan, **kw)
+
 
 @MODELS.register_module()
 class UnlgFormer(Base_model):
@@ -159,6 +164,17 @@ class UnlgFormer(Base_model):
     def get_model_output(self, input_batch):
         input_pan = input_batch['input_pan']
         input_lr = input_batch['input_lr']
+        tile = self.cfg.get('scene_tile', None)
+        if tile is not None:
+            # opt-in: every item as a tiled scene (eval mode, no_grad) -- how a full-resolution set above 1024 or off the 16-pixel grid is
+            # evaluated.  The batch is already normalised: the tiles take the samples as they are.
+            from .scene import default_overlap, fuse_scene
+            G = self.module_dict['core_module']
+            core = G.module if hasattr(G, 'module') else G
+            overlap = self.cfg.get('scene_overlap', None)
+            if overlap is None:
+                overlap = default_overlap(input_pan.shape[2], input_pan.shape[3], tile)
+            return torch.stack([fuse_scene(core, input_lr[i], input_pan[i], tile=tile, overlap=overlap) for i in range(input_pan.shape[0])])
         return self.module_dict['core_module'](input_lr, input_pan)
 
     def train_iter(self, iter_id, input_batch, log_freq=10):

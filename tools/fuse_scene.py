@@ -1,0 +1,63 @@
+"""Pan-sharpen one scene of any size with a trained network: reads PREFIX_lr.tif (MS, [h,w,C]) and PREFIX_pan.tif ([4h,4w]) with
+dataset.read_tiff, fuses them tile by tile on the GPU (lgteun_amd/scene.py) and writes PREFIX_mul_hat.tif.
+
+    python tools/fuse_scene.py PREFIX --checkpoint model.state.pth [--tile 128] [--overlap 32] [--bit-depth 11] [--norm-input]
+                               [--batch B] [--float] [--out FILE]
+
+The checkpoint is a plain-tensor file ({'core_module': state_dict}, what Base_model.save writes and tools/convert_checkpoint.py makes of a
+reference-era file); the band count and the stage count are read from it.  The output holds uint16 digital numbers
+(rint(x * (2**bit_depth - 0.5)), clipped) unless --float asks for the normalised float32 image."""
+import argparse
+import os
+import sys
+
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, R)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import lgteun_amd  # noqa: E402
+from lgteun_amd.compat import Config  # noqa: E402
+from lgteun_amd.dataset import read_tiff, write_tiff  # noqa: E402
+
+
+def load_module(path, device='cuda:0'):
+    ckpt = torch.load(path, map_location='cpu', weights_only=True)
+    sd = ckpt['core_module'] if 'core_module' in ckpt else ckpt
+    C = int(sd['R.weight'].shape[1])
+    K = sum(1 for k in sd if k.startswith('eta.'))
+    net = lgteun_amd.Pansharpening(Config(ms_chans=C), None, stage=K)
+    net.load_state_dict(sd)
+    return net.to(device).eval()
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('prefix')
+    ap.add_argument('--checkpoint', required=True)
+    ap.add_argument('--tile', type=int, nargs='+', default=[128], help='one side, or height and width')
+    ap.add_argument('--overlap', type=int, default=32)
+    ap.add_argument('--batch', type=int, default=None)
+    ap.add_argument('--bit-depth', type=int, default=11)
+    ap.add_argument('--norm-input', action='store_true', help="the dataset's extra division (cfg.norm_input of the training run)")
+    ap.add_argument('--float', action='store_true', help='write the normalised float32 image instead of uint16 digital numbers')
+    ap.add_argument('--out', default=None)
+    a = ap.parse_args()
+    if len(a.tile) > 2:
+        ap.error('--tile takes one or two values')
+    tile = a.tile[0] if len(a.tile) == 1 else tuple(a.tile)
+    ms, pan = read_tiff(f'{a.prefix}_lr.tif'), read_tiff(f'{a.prefix}_pan.tif')
+    if ms.ndim != 3 or pan.ndim != 2:
+        sys.exit(f'{a.prefix}: expected MS [h,w,C] and PAN [4h,4w], got {ms.shape} / {pan.shape}')
+    if ms.dtype != pan.dtype or ms.dtype.name not in ('uint8', 'uint16'):
+        ms, pan = ms.astype(np.float64).astype(np.float32), pan.astype(np.float64).astype(np.float32)      # like PSDataset
+    net = load_module(a.checkpoint)
+    fused = net.fuse_scene(np.ascontiguousarray(ms.transpose(2, 0, 1)), pan[np.newaxis], tile=tile, overlap=a.overlap, batch=a.batch,
+                           bit_depth=a.bit_depth, norm_input=a.norm_input, out_dtype='float32' if a.float else 'uint16')
+    out = a.out or f'{a.prefix}_mul_hat.tif'
+    write_tiff(out, fused.permute(1, 2, 0).contiguous().cpu().numpy())
+    print(f'{out}: {tuple(fused.shape)} {fused.dtype}')
+
+
+if __name__ == '__main__':
+    main()
