@@ -76,7 +76,9 @@ typedef struct lg_config {
                         * the default; the library itself reads no environment variable).  Bits this build does not carry are rejected. */
 } lg_config;
 
-/* lg_config.variant: A/B switches (all default off) */
+/* lg_config.variant: A/B switches (all default off).  lg_plan_create resolves them, with precision, C and the plane sizes, into the plan's
+ * kernel routes in ONE function (lgteun_amd/csrc/route.hip: lg_resolve_route; the table of bit -> LG_* environment name -> effect is
+ * there); lg_plan_describe shows the result. */
 #define LG_VAR_FFN_IMPL_MASK 3u   /* fused FFN forward: 0 = split-bf16 kernels; 1 = the exact f32-MFMA strip kernel (v_mfma_f32_16x16x4_f32: bit
                                    * for bit an fp32 fma chain -- the yardstick of the arithmetic-criterion test); 2 = round 1's per-tile
                                    * f32-MFMA kernel, 3 = the software-pipelined split kernel (both only in `make AB=1` builds) */
@@ -115,6 +117,10 @@ const char* lg_last_error(void); /* thread-local, host string */
 /* offsets: host array of n_offsets = 12 + K + 119*K int64 (float offsets into the flat parameter buffer). */
 int lg_plan_create(const lg_config* cfg, const int64_t* offsets, int32_t n_offsets, lg_plan** out);
 void lg_plan_destroy(lg_plan* plan);
+/* The kernel routes the plan resolved from its configuration, as a short stable text in the HOST buffer buf[n]: one "net" line, then per level
+ * (L0: e = 4C at H x W, L1: e = 8C at H/2 x W/2) a line for the plain forward, the LG_FLAG_SAVE forward (with the save slots it writes) and
+ * the backward (with the slots it reads).  -3 when n is too small (1 KiB is enough). */
+int lg_plan_describe(const lg_plan* plan, char* buf, size_t n);
 /* bytes of workspace lgteun_forward/backward need for batch B: train = 0 forward only, 1 = forward with LG_FLAG_SAVE + backward,
  * 2 = the same with LG_FLAG_CHAINED (K saved activation sets). */
 size_t lg_workspace_bytes(const lg_plan* plan, int32_t B, int32_t train);

@@ -97,6 +97,7 @@ SIGNATURES = {
     'lg_last_error': (c_char_p, []),
     'lg_plan_create': (c_int32, [POINTER(LgConfig), POINTER(c_int64), c_int32, POINTER(c_void_p)]),
     'lg_plan_destroy': (None, [c_void_p]),
+    'lg_plan_describe': (c_int32, [c_void_p, c_char_p, c_size_t]),
     'lg_workspace_bytes': (c_size_t, [c_void_p, c_int32, c_int32]),
     'lgteun_forward': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_int32,
                                  c_uint64, c_void_p]),

@@ -123,35 +123,12 @@ extern "C" int lg_plan_create(const lg_config* cfg, const int64_t* offsets, int3
     if (n_offsets != expect) { lg_set_error("plan_create: expected %d offsets, got %d", expect, n_offsets); return -2; }
     for (int i = 0; i < n_offsets; ++i)
         if (offsets[i] < 0 || (offsets[i] & 3)) { lg_set_error("plan_create: offset %d (=%lld) must be a non-negative multiple of 4 floats", i, (long long)offsets[i]); return -2; }
-    if (cfg->variant & ~LG_VAR_ALL) { lg_set_error("plan_create: unknown variant bits 0x%x", cfg->variant & ~LG_VAR_ALL); return -2; }
-    if ((cfg->variant & LG_VAR_FFN_SAVE_MASK) == LG_VAR_FFN_SAVE_MASK) { lg_set_error("plan_create: invalid FFN save variant"); return -2; }
-#ifndef LG_BUILD_AB
-    if ((cfg->variant & LG_VAR_FFN_IMPL_MASK) >= LG_VAR_FFN_TILE) { lg_set_error("plan_create: FFN variants 2 / 3 exist in `make AB=1` builds only"); return -2; }
-    if (cfg->precision == 1 && (cfg->variant & LG_VAR_FFN_IMPL_MASK)) { lg_set_error("plan_create: precision = 1 with an FFN variant exists in `make AB=1` builds only"); return -2; }
-#endif
+    LgRoute route;   // A/B switches come in through lg_config.variant (the library reads no environment variable)
+    if (int rc = lg_resolve_route(*cfg, &route)) return rc;
     lg_plan* p = new lg_plan;
     p->cfg = *cfg;
     p->n_offsets = n_offsets;
-    {   // A/B switches come in through lg_config.variant (the library reads no environment variable)
-        const uint32_t v = cfg->variant;
-        p->ffn_tile = (int)(v & LG_VAR_FFN_IMPL_MASK);
-        const uint32_t sv = v & LG_VAR_FFN_SAVE_MASK;
-        p->save_mode = sv == LG_VAR_FFN_SAVE5 ? 5 : (sv == LG_VAR_FFN_SAVE3 ? 3 : 2);   // common.h: lg_plan::save_mode
-        p->bwd32_old = (v & LG_VAR_FFN_BWD32_PAIR) ? 1 : 0;   // default (round 5): k_ffn1_bwd_xs<32> behind the strip-walking spatial half -- 14.36 -> 14.20 ms per c3 step, and the forward no longer saves gelu(h1) / gelu'(h1)
-        p->dwbwd_tile = (v & LG_VAR_FFN_DWBWD_TILE) ? 1 : 0;
-        p->attn_bwd_old = (v & LG_VAR_ATTN_BWD_R3) ? 1 : 0;
-        p->dstep_tiles = (v & LG_VAR_DSTEP_TILES) ? 1 : 0;
-        p->attn_fwd_valu = (v & LG_VAR_ATTN_FWD_VALU) ? 1 : 0;
-        p->ffn_bf16x3 = (v & LG_VAR_FFN_BF16X3) ? 1 : 0;
-        p->fft_full = (v & LG_VAR_FFT_FULL) ? 1 : 0;
-        p->attn_bwd_core_m = (v & LG_VAR_ATTN_BWD_CORE_M) ? 1 : 0;
-        p->ffn_bwd_bf16x3 = (v & LG_VAR_FFN_BWD_BF16X3) ? 1 : 0;
-        p->ffn_xs = (v & LG_VAR_FFN_XS) ? 1 : 0;
-        p->attn_bf16x3 = (v & LG_VAR_ATTN_BF16X3) ? 1 : 0;
-        p->ffn_h3_re = (v & LG_VAR_FFN_H3_RECOMPUTE) ? 1 : 0;
-        p->attn_restats = (v & LG_VAR_ATTN_BWD_RESTATS) ? 1 : 0;
-        p->reduce_per_block = (v & LG_VAR_REDUCE_PER_BLOCK) ? 1 : 0;
-    }
+    p->route = route;
     p->off = (int64_t*)malloc(sizeof(int64_t) * n_offsets);
     memcpy(p->off, offsets, sizeof(int64_t) * n_offsets);
     *out = p;
@@ -162,6 +139,11 @@ extern "C" void lg_plan_destroy(lg_plan* plan) {
     if (!plan) return;
     free(plan->off);
     delete plan;
+}
+
+extern "C" int lg_plan_describe(const lg_plan* plan, char* buf, size_t n) {
+    if (!plan) { lg_set_error("plan_describe: null argument"); return -1; }
+    return lg_describe_route(plan->cfg, plan->route, buf, n);
 }
 
 extern "C" size_t lg_workspace_bytes(const lg_plan* plan, int32_t B, int32_t train) {
@@ -180,7 +162,7 @@ static int data_step_fwd(const lg_plan* pl, const float* P, int stage, const flo
                          float* z_out, float* t1, float* r, float* s1, float* pr, int B, hipStream_t s) {
     const lg_config& c = pl->cfg;
     const int planes = B * c.C, H = c.H, W = c.W;
-    if (pl->dstep_fused(H, W)) {
+    if (pl->route.dstep_fused) {
         DstepFwdArgs f;
         f.z = z_in; f.ms = ms; f.pan = pan; f.zout = z_out; f.t1 = t1; f.r = r; f.s1 = s1; f.pr = pr;
         f.d1w = P + pl->shared(S_D1W); f.d1b = P + pl->shared(S_D1B); f.d3w = P + pl->shared(S_D3W); f.d3b = P + pl->shared(S_D3B);
@@ -216,6 +198,7 @@ static int data_step_fwd(const lg_plan* pl, const float* P, int stage, const flo
 static int block_mixer_fwd(const lg_plan* pl, const float* P, int stage, int j, const BlockBufs& bb, const float* posT, int B,
                            int flags, uint64_t seed, hipStream_t s, float* fft_scratch = nullptr, const float* attn_scales = nullptr) {
     int rc;
+    const MixerRoute& mr = pl->mixer(bb.e);
     FftArgs f;
     f.g = bb.g; f.o = bb.o2;
     f.amp = (flags & LG_FLAG_SAVE) ? bb.amp : nullptr;
@@ -224,53 +207,54 @@ static int block_mixer_fwd(const lg_plan* pl, const float* P, int stage, int j, 
     f.scratch = fft_scratch;
     f.ampw = P + pl->blk(stage, j, B_AMPW); f.ampb = P + pl->blk(stage, j, B_AMPB);
     f.phaw = P + pl->blk(stage, j, B_PHAW); f.phab = P + pl->blk(stage, j, B_PHAB);
-    f.ch = bb.e / 2; f.planes = B * f.ch; f.n = bb.h; f.h = bb.h; f.w = bb.w; f.full = pl->fft_full;
+    f.ch = bb.e / 2; f.planes = B * f.ch; f.n = bb.h; f.h = bb.h; f.w = bb.w; f.full = pl->route.fft_full;
     if ((rc = launch_fftmix(f, s))) return rc;
     AttnArgs t;
     t.x = bb.xin; t.o2 = bb.o2; t.y = bb.xmid; t.posT = posT; t.pos = P + pl->blk(stage, j, B_POS);
-    t.bf16 = pl->cfg.precision == 1 ? 1 : 0;
+    t.bf16 = mr.bf16 ? 1 : 0;
     t.ln1g = P + pl->blk(stage, j, B_LN1G); t.ln1b = P + pl->blk(stage, j, B_LN1B);
     t.qkvw = P + pl->blk(stage, j, B_QKVW); t.qkvb = P + pl->blk(stage, j, B_QKVB);
     t.projw = P + pl->blk(stage, j, B_PROJW); t.projb = P + pl->blk(stage, j, B_PROJB);
     t.B = B; t.h = bb.h; t.w = bb.w;
     t.dropout = (flags & LG_FLAG_DROPOUT) ? 1 : 0;
     t.seed = mix_seed(seed, stage, j);
-    t.scales = (attn_scales && pl->attn_f16x2()) ? attn_scales + ((size_t)stage * 5 + j) * 4 : nullptr;   // written by prep_stages for the stages of this call
-    if ((flags & LG_FLAG_SAVE) && pl->attn_saves_stats(bb.e)) { t.save_o = bb.att_o; t.save_l = bb.att_l; }
-    return pl->attn_fwd_valu ? launch_attn(bb.e, t, s) : launch_attn_m(bb.e, t, s);
+    t.scales = (attn_scales && mr.f16x2) ? attn_scales + ((size_t)stage * 5 + j) * 4 : nullptr;   // written by prep_stages for the stages of this call
+    if ((flags & LG_FLAG_SAVE) && mr.stats) { t.save_o = bb.att_o; t.save_l = bb.att_l; }
+    return mr.fwd == ATTN_FWD_VALU ? launch_attn(bb.e, t, s) : launch_attn_m(bb.e, t, s);
 }
 
 static int block_ffn_fwd(const lg_plan* pl, const float* P, int stage, int j, const BlockBufs& bb, float* g_next, int next_blk,
                          int B, int flags, hipStream_t s, float* wsplit, const float* ffn_scales) {
     int rc;
+    const FfnRoute& fr = pl->ffn(bb.e);
+    const unsigned saves = (flags & LG_FLAG_SAVE) ? fr.saves : 0;   // the slots the backward's route reads (route.h)
     Ffn1Args a1;
-    const bool pre = pl->ffn_saves_preact(bb.e);   // h1 / h3 go to the a1 / a3 slots, nothing to g1 / g3
-    const bool noh1 = pl->ffn_bwd_x(bb.e) || pl->ffn1_bwd_x32(bb.e);   // the backward re-computes h1 from x: nothing of it is saved
-    a1.x = bb.xmid; a1.a1s = ((flags & LG_FLAG_SAVE) && !noh1) ? bb.a1 : nullptr; a1.g1s = ((flags & LG_FLAG_SAVE) && !pre && !noh1) ? bb.g1 : nullptr; a1.h2 = bb.h2;
+    a1.x = bb.xmid; a1.a1s = (saves & FFN_SLOT_A1) ? bb.a1 : nullptr; a1.g1s = (saves & FFN_SLOT_G1) ? bb.g1 : nullptr;
     a1.ln2g = P + pl->blk(stage, j, B_LN2G); a1.ln2b = P + pl->blk(stage, j, B_LN2B);
     a1.w1 = P + pl->blk(stage, j, B_W1); a1.b1 = P + pl->blk(stage, j, B_B1);
     a1.w2 = P + pl->blk(stage, j, B_W2); a1.b2 = P + pl->blk(stage, j, B_B2);
     a1.P = (long)B * bb.h * bb.w;
-    a1.hbf = pl->hidden_bf16(bb.e) ? 1 : 0;
-    a1.tile16 = pl->ffn_tile ? pl->ffn_tile : ((pl->ffn_xs && bb.e == 16) ? 4 : 0);
+    a1.hbf = fr.hbf ? 1 : 0;
+    a1.kernel = fr.fwd[(flags & LG_FLAG_SAVE) ? 1 : 0];
     a1.wsplit = wsplit ? wsplit + ((size_t)stage * 5 + j) * (ffn_wsplit_bytes(8 * pl->cfg.C) / sizeof(float)) : nullptr;   // this block's slot, filled by prep_stages
     a1.wsplit_ready = (wsplit && bb.e >= 32) ? 1 : 0;
-    a1.scales = pl->ffn_f16x2(bb.e) ? ffn_scales + ((size_t)stage * 5 + j) * 8 : nullptr;   // written by prep_stages for the stages of this call
+    a1.scales = fr.scales ? ffn_scales + ((size_t)stage * 5 + j) * 8 : nullptr;   // written by prep_stages for the stages of this call
     Ffn2Args a2;
-    a2.h2 = bb.h2; a2.x = bb.xmid; a2.a3s = ((flags & LG_FLAG_SAVE) && !pl->ffn_h3_recompute(bb.e)) ? bb.a3 : nullptr; a2.g3s = ((flags & LG_FLAG_SAVE) && !pre && !pl->ffn_dw_x32(bb.e, bb.h, bb.w)) ? bb.g3 : nullptr; a2.y = bb.xout;   // g3s null with a3s set: a3 receives the PRE-activation h3
+    a2.h2 = bb.h2; a2.x = bb.xmid; a2.a3s = (saves & FFN_SLOT_A3) ? bb.a3 : nullptr; a2.g3s = (saves & FFN_SLOT_G3) ? bb.g3 : nullptr; a2.y = bb.xout;   // g3s null with a3s set: a3 receives the PRE-activation h3
     a2.g = g_next;
     a2.dww = P + pl->blk(stage, j, B_DWW); a2.dwb = P + pl->blk(stage, j, B_DWB);
     a2.w3 = P + pl->blk(stage, j, B_W3); a2.b3 = P + pl->blk(stage, j, B_B3);
     a2.n1g = g_next ? P + pl->blk(stage, next_blk, B_LN1G) : nullptr;
     a2.n1b = g_next ? P + pl->blk(stage, next_blk, B_LN1B) : nullptr;
     a2.B = B; a2.h = bb.h; a2.w = bb.w; a2.hbf = a1.hbf;
-    // fused path (e <= 32): h2 only leaves the chip when the backward needs it; e = 64 passes it through HBM between its two kernels
-    a1.h2 = ((flags & LG_FLAG_SAVE) || bb.e == 64) ? bb.h2 : nullptr;
-    rc = launch_ffn_fused(bb.e, a1, a2, s);
-    if (rc != LG_FFN_NOT_FUSED) return rc;
     a1.h2 = bb.h2;
-    if ((rc = launch_ffn1(bb.e, a1, s))) return rc;
-    return launch_ffn2(bb.e, a2, s);
+    if (a1.kernel == FFN_FWD_UNFUSED) {
+        if ((rc = launch_ffn1(bb.e, a1, s))) return rc;
+        return launch_ffn2(bb.e, a2, s);
+    }
+    // fused kernels (e <= 32): h2 only leaves the chip when the backward needs it; e = 64 passes it through HBM between its two kernels
+    if (!saves && bb.e != 64) a1.h2 = nullptr;
+    return launch_ffn_fused(bb.e, a1, a2, s);
 }
 
 // pos_emb^T of stages [st0, st1) into nb.posT, all tables in ONE launch (a launch per stage was 5 us + a launch gap each)
@@ -286,10 +270,10 @@ static int pos_transpose_stages(const lg_plan* pl, const float* P, int st0, int 
 // what the LGTs of stages [st0, st1) need in front of their first kernel: the transposed pos_emb tables (round 2's vector-pipe mixer alone reads
 // them) and the operand scales of the f16-pair FFN arithmetic -- one launch each for all stages of the call
 static int prep_stages(const lg_plan* pl, const float* P, int st0, int st1, NetBufs& nb, hipStream_t s) {
-    int rc = pl->attn_fwd_valu ? pos_transpose_stages(pl, P, st0, st1, nb.posT, s) : 0;   // only round 2's vector-pipe forward (LG_ATTN_FWD=valu) reads the transposed tables
+    int rc = pl->route.mix[0].fwd == ATTN_FWD_VALU ? pos_transpose_stages(pl, P, st0, st1, nb.posT, s) : 0;   // only round 2's vector-pipe forward (LG_ATTN_FWD=valu) reads the transposed tables
     if (rc || st1 <= st0) return rc;
     const int E = 4 * pl->cfg.C;
-    if (pl->ffn_f16x2(E) || pl->ffn_f16x2(2 * E)) {
+    if (pl->route.ffn[0].scales) {   // (the same at both levels)
         FfnPrepJob jobs[5 * LG_MAX_K];
         int n = 0;
         for (int st = st0; st < st1; ++st)
@@ -301,7 +285,7 @@ static int prep_stages(const lg_plan* pl, const float* P, int st0, int st1, NetB
                 q.e = j == 2 ? 2 * E : E;
                 q.ln1g = P + pl->blk(st, j, B_LN1G); q.ln1b = P + pl->blk(st, j, B_LN1B); q.qkvw = P + pl->blk(st, j, B_QKVW); q.qkvb = P + pl->blk(st, j, B_QKVB);
             }
-        if ((rc = launch_ffn_scales(n, jobs, nb.ffn_scales + (size_t)st0 * 5 * 8, s, pl->attn_f16x2() ? nb.attn_scales + (size_t)st0 * 5 * 4 : nullptr))) return rc;
+        if ((rc = launch_ffn_scales(n, jobs, nb.ffn_scales + (size_t)st0 * 5 * 8, s, pl->route.mix[0].f16x2 ? nb.attn_scales + (size_t)st0 * 5 * 4 : nullptr))) return rc;
     }
     // the pre-split weight fragments of every e >= 32 block of these stages, behind the scales they are multiplied by (round 5: one launch per
     // forward call instead of one in front of every FFN launch)
@@ -314,7 +298,7 @@ static int prep_stages(const lg_plan* pl, const float* P, int st0, int st1, NetB
             if (e < 32 || e % 32) continue;
             SplitWJob& q = sj[ns++];
             q.w1 = P + pl->blk(st, j, B_W1); q.w2 = P + pl->blk(st, j, B_W2); q.w3 = P + pl->blk(st, j, B_W3);
-            q.e = e; q.np = pl->hidden_bf16(e) ? 1 : (pl->ffn_f16x2(e) ? 2 : 3);
+            q.e = e; q.np = pl->ffn(e).wsplit_np;
             q.scales = q.np == 2 ? nb.ffn_scales + ((size_t)st * 5 + j) * 8 : nullptr;
             q.out = nb.wsplit + ((size_t)st * 5 + j) * slot;
         }
@@ -502,7 +486,7 @@ extern "C" int lg_op_block(const lg_plan* plan, const float* params, int32_t sta
         f.g = bb.g; f.o = y; f.amp = nullptr; f.pha = nullptr; f.sgn = nullptr; f.scratch = nb.fft_scratch;
         f.ampw = params + plan->blk(stage, blk, B_AMPW); f.ampb = params + plan->blk(stage, blk, B_AMPB);
         f.phaw = params + plan->blk(stage, blk, B_PHAW); f.phab = params + plan->blk(stage, blk, B_PHAB);
-        f.ch = bb.e / 2; f.planes = B * f.ch; f.n = bb.h; f.h = bb.h; f.w = bb.w; f.full = plan->fft_full;
+        f.ch = bb.e / 2; f.planes = B * f.ch; f.n = bb.h; f.h = bb.h; f.w = bb.w; f.full = plan->route.fft_full;
         return launch_fftmix(f, s);
     }
     if (which == 1) {

@@ -235,8 +235,8 @@ struct Ffn1BwdArgs {
     long P;
     int hbf;           // hidden storage: 0 fp32, 1 bf16
     int pre;           // 1: g1 holds the PRE-ACTIVATION h1; gelu'(h1) is evaluated in the kernel
-    // e = 32: the split-bf16 kernel k_ffn1_bwd_x32 runs when both are set (w1 = the forward W1 [4e][e], wsplit = ffn_wsplit_bytes(32)
-    // bytes of scratch for the pre-split W2^T / W1^T fragments); null -> the f32-MFMA kernel k_ffn1_bwd<32>
+    // e = 32, the split-bf16 kernel k_ffn1_bwd_x32 (FFN1_BWD_X32): w1 = the forward W1 [4e][e], wsplit = ffn_wsplit_bytes(32) bytes of scratch
+    // for the pre-split W2^T / W1^T fragments; null for the f32-MFMA kernel k_ffn1_bwd
     const float* w1;
     void* wsplit;
 };
@@ -246,7 +246,7 @@ inline bool ffn1_bwd_fuses_w1(int e) { return e <= 32; }
 #define LG_FW2 0   // 1: k_ffn1_bwd accumulates dW2 itself in the pre-activation mode (64 extra f32 MFMAs per chunk: 7.51 ms against 7.43 with dW2 from k_wgrad_t, gelu evaluated on its X operand)
 #endif
 inline bool ffn1_bwd_fuses_w2(int e, int pre) { return LG_FW2 && pre && e == 16; }
-int launch_ffn1_bwd(int e, const Ffn1BwdArgs& a, hipStream_t s);
+int launch_ffn1_bwd(int e, Ffn1BwdKernel k, const Ffn1BwdArgs& a, hipStream_t s);   // k: FFN1_BWD_TILE | FFN1_BWD_X32 (route.h)
 int launch_ffn1_bwd_x32(const Ffn1BwdArgs& a, const float* w1, void* wsplit, hipStream_t s);   // k_ffn1_bwd_x32.hip
 // e = 16 | 32 (k_ffn_bwd_x.hip): everything that hangs off dh2 in ONE pass on the bf16 matrix pipe (split arithmetic) --
 // h1 re-computed from x, dx, LayerNorm gradients, dW1 / db1 AND dW2 / db2; replaces k_ffn1_bwd<16> / k_ffn1_bwd_x32 + the 4e x 4e k_wgrad_t launches
@@ -268,7 +268,6 @@ struct Ffn1BwdXArgs {
 };
 inline int ffn1_bwd_x_wgs(int e) { return e == 16 ? 512 : 256; }   // persistent grid: two workgroups per CU at e = 16 (55 KB of LDS), one at e = 32 (139 KB)
 size_t ffn1_bwd_x_slab_floats(int e);                               // floats of Ffn1BwdXArgs::slab
-bool ffn1_bwd_x32_built();                                          // the e = 32 instance is compiled (make AB=1)
 int launch_ffn1_bwd_xs(int e, const Ffn1BwdXArgs& a, hipStream_t s);   // e = 16 | 32
 // e = 16 | 32 (k_ffn_dwbwd_x.hip): the strip-walking spatial half -- dh3 in an LDS ring, dh2 out, depthwise gradients AND
 // dW3 / db3 in the same pass; replaces k_ffn_dw_bwd<16> + the 16 x 64 k_wgrad_t launch

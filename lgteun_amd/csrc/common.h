@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <atomic>
 #include "../../include/lgteun_hip.h"
+#include "route.h"
 
 // ----------------------------------------------------------------------------------------------
 // parameter slots, in Pansharpening.state_dict() order (reference models/unlg_former.py:22-48,
@@ -31,49 +32,9 @@ static inline int block_base(int blk) {
 struct lg_plan {
     lg_config cfg;
     int n_offsets;
-    int ffn_tile;  // A/B switch (lg_config.variant & LG_VAR_FFN_IMPL_MASK; Python side: LG_FFN_IMPL = strip | tile | xp): the f32-MFMA fused FFN kernels instead of the split-bf16 ones
-    int save_mode; // A/B switch (lg_config.variant LG_VAR_FFN_SAVE3 | _SAVE5; Python side: LG_FFN_SAVE = 5 | 3 | 2, default 2): what the live stage's e = 16 FFN half-blocks
-    // keep for the backward.  2 (default): the pre-activations h2, h3 -- h1 is re-computed from x by k_ffn1_bwd_xs (k_ffn_bwd_x.hip), which
-    // also forms dW1 / dW2 on the bf16 matrix pipe; 3: h1, h2, h3 (round 2's default: k_ffn1_bwd<16> + k_wgrad_t re-evaluate gelu / gelu');
-    // 5: gelu(h1), gelu'(h1), h2, gelu(h3), gelu'(h3) (GELU-free backward; the only form of the other widths and of precision = 'bf16').
-    // In modes 2 / 3 the tensors sit in the a1 / h2 / a3 slots (workspace.h) and the g1 / g3 slots stay unused.
-    int dwbwd_tile; // A/B switch (lg_config.variant LG_VAR_FFN_DWBWD_TILE; Python side: LG_FFN_DWBWD=tile): round 2's tile kernel k_ffn_dw_bwd<16> + k_wgrad_t for dW3
-                    // instead of the strip-walking k_ffn_dw_bwd_xs
-    // precision = 'bf16' applies where a plain-bf16 kernel exists: e = 16 and e = 32.  The e = 64 half-blocks (level 1 of the 8-band net) have
-    // only the round-1 f32-MFMA pair in that form (436 + 372 us against 123 + 95 us for the split-bf16 k_ffn_x64 pair), so they run the
-    // default kernels with fp32 storage in both modes -- 'bf16' is never slower than the default (c3 / c5)
-    bool hidden_bf16(int e) const { return cfg.precision == 1 && e != 64; }
-    // precision = 'bf16' (plain bf16 MFMA, bf16 storage of the saved tensors) knows modes 2 and 5 only (3 falls back to 5)
-    int attn_bwd_old; // A/B switch (lg_config.variant LG_VAR_ATTN_BWD_R3; Python side: LG_ATTN_BWD=r3): 1 = round 3's k_attn_bwd_core + k_attn_bwd_epi + k_wgrad_t at e = 16 instead of k_attn_bwd_f
-    int ffn_bwd_bf16x3; // A/B switch (lg_config.variant LG_VAR_FFN_BWD_BF16X3; Python side: LG_FFN_BWD_SPLIT=bf16x3): the pixelwise half of the FFN backward on three bf16 pieces / six products (rounds 3 - 4) instead of f16 pairs
-    int attn_bwd_core_m; // A/B switch (lg_config.variant LG_VAR_ATTN_BWD_CORE_M; Python side: LG_ATTN_BWD_CORE=m): the matrix-pipe k_attn_bwd_core_m at e = 32 instead of the vector-pipe k_attn_bwd_core
-    int fft_full;      // A/B switch (lg_config.variant LG_VAR_FFT_FULL; Python side: LG_FFT=full): complex-row in-LDS FFT mixer kernels instead of the real-input ones
-    int ffn_bf16x3;    // A/B switch (lg_config.variant LG_VAR_FFN_BF16X3; Python side: LG_FFN_SPLIT=bf16x3): the fused FFN forward's GEMMs as three bf16 pieces / six
-                       // products (round 2) instead of two f16 pieces / three products with proven power-of-two operand scales (round 5, k_ffn_prep.hip)
-    bool ffn_f16x2(int e) const { return cfg.precision == 0 && ffn_tile == 0 && !ffn_bf16x3 && (e == 16 || e == 32 || e == 64); }
-    int attn_restats;  // A/B switch (lg_config.variant LG_VAR_ATTN_BWD_RESTATS; Python side: LG_ATTN_BWD_STATS=recompute): k_attn_bwd_f re-derives the softmax row statistics instead of reading the forward's (round 6)
-    int ffn_h3_re;     // A/B switch (lg_config.variant LG_VAR_FFN_H3_RECOMPUTE; Python side: LG_FFN_H3=recompute): the live stage's e = 16 FFN saves h2 only and its backward re-computes h3 (k_ffn_dw_bwd_h, round 6) instead of saving h2 and h3 (k_ffn_dw_bwd_xs, the default)
-    bool ffn_h3_recompute(int e) const { return e == 16 && ffn_bwd_x(e) && cfg.precision == 0 && !dwbwd_tile && ffn_h3_re && !ffn_xs && ffn_f16x2(e); }
-    int ffn_xs;        // A/B switch (lg_config.variant LG_VAR_FFN_XS; Python side: LG_FFN_FWD=xs): rounds 2 - 5's channel-split k_ffn_xs at e = 16 instead of the register-chain k_ffn_xr
-    int attn_bf16x3;   // A/B switch (lg_config.variant LG_VAR_ATTN_BF16X3; Python side: LG_ATTN_SPLIT=bf16x3): to_qkv and Q K^T of k_attn_m on three bf16 pieces / six products (round 5) instead of f16 pairs with static scales (round 6)
-    // the live stage's local mixers leave their row log-sum-exp and attention output for k_attn_bwd_f / k_attn_bwd_core (fp32-equivalent mode, matrix-pipe forward)
-    bool attn_saves_stats(int e) const { return cfg.precision == 0 && !attn_fwd_valu && !attn_restats && !(e == 32 && attn_bwd_core_m); }
-    bool attn_f16x2() const { return cfg.precision == 0 && !attn_bf16x3 && !attn_fwd_valu && ffn_tile == 0 && !ffn_bf16x3; }   // (the scales ride in the FFN prep launch: the f16-pair FFN arithmetic must be on)
-    int attn_fwd_valu; // A/B switch (lg_config.variant LG_VAR_ATTN_FWD_VALU; Python side: LG_ATTN_FWD=valu): round 2's vector-pipe k_attn instead of the matrix-pipe k_attn_m
-    int reduce_per_block; // A/B switch (lg_config.variant LG_VAR_REDUCE_PER_BLOCK; Python side: LG_REDUCE=per_block): the parameter-gradient reduce launches of rounds 2 - 6 (one per
-                          // LGT block and per data step, table as a kernel argument) instead of one launch for the LGT and one for the K data steps (bwd_kernels.h: ReduceQueue)
-    int dstep_tiles; // A/B switch (lg_config.variant LG_VAR_DSTEP_TILES; Python side: LG_DSTEP=tiles): the tile kernels of the data step also where the one-launch
-                     // plane-in-LDS form (k_dstep.hip) exists
-    bool dstep_fused(int h, int w) const;   // k_dstep.hip: square planes of 128 or 64
-    int bwd32_old; // A/B switch (lg_config.variant LG_VAR_FFN_BWD32_PAIR turns it on; Python side: LG_FFN_BWD32=pair): 1 = k_ffn1_bwd_x32 + two k_wgrad_t launches at e = 32 (round 2 .. 4's default);
-                   // 0 = k_ffn1_bwd_xs<32>, the e = 16 kernel's template at 8 waves / one workgroup per CU -- correct, but slower there
-    bool ffn1_bwd_x32(int e) const { return e == 32 && ffn_tile == 0 && !bwd32_old; }
-    // e = 32 (round 4): the spatial half through the strip-walking k_ffn_dw_bwd_xs<32> (dW3 / db3 included): the forward saves the PRE-activation h3
-    // in the a3 slot and nothing in g3; the pixelwise half stays k_ffn1_bwd_x32 + the 128 x 128 weight-gradient launch on the saved gelu(h1) / gelu'(h1)
-    // (a strip is 16 columns wide and every output pixel of a step must be inside the plane: level-1 planes whose width is 8 mod 16 keep round 2's kernels)
-    bool ffn_dw_x32(int e, int h, int w) const { return e == 32 && ffn_tile == 0 && !dwbwd_tile && (h & 7) == 0 && (w & 15) == 0; }
-    bool ffn_bwd_x(int e) const { return e == 16 && ffn_tile == 0 && save_mode == 2; }   // h1 not saved; backward through k_ffn_dw_bwd_xs + k_ffn1_bwd_xs
-    bool ffn_saves_preact(int e) const { return e == 16 && ffn_tile == 0 && (save_mode == 2 || (save_mode == 3 && cfg.precision == 0)); }
+    LgRoute route;   // which kernels run, what they save and read: resolved once by lg_resolve_route (route.hip), read everywhere else
+    const FfnRoute& ffn(int e) const { return route.ffn[e != 4 * cfg.C]; }
+    const MixerRoute& mixer(int e) const { return route.mix[e != 4 * cfg.C]; }
     int64_t* off;  // host copy of offsets
     int64_t shared(int s) const { return off[s]; }
     int64_t eta(int i) const { return off[S_NSHARED + i]; }

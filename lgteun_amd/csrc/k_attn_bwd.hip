@@ -676,6 +676,7 @@ static int launch_attn_bwd_t(const AttnBwdArgs& a, hipStream_t s) {
 
 int launch_attn_bwd(int e, const AttnBwdArgs& a, hipStream_t s) {
     if ((a.h & 7) || (a.w & 7)) { lg_set_error("attn_bwd: h,w must be multiples of 8"); return -2; }
+    if (a.core_m && e != 32) { lg_set_error("attn_bwd: k_attn_bwd_core_m runs e = 32 only (e=%d)", e); return -2; }   // (route.h: ATTN_BWD_R3_CORE_M)
     if (e == 16) return launch_attn_bwd_t<8, 8>(a, s);
     if (e == 32) return launch_attn_bwd_t<16, 4>(a, s);
     if (e == 64) return launch_attn_bwd_t<32, 4>(a, s);

@@ -52,10 +52,8 @@ static void carve_bwd(const lg_plan* plan, int B, void* base, BwdBufs& bb) {
     // small ones, and the local mixer's pos_emb partial rows); the weight-gradient slabs of the down / up / fusion convs ride in the blocks'
     // slack.  take() flushes by itself if a configuration needs more
     if (sl3 > sl) sl = sl3;
-    for (size_t e = E; e <= 2 * E; e *= 2)   // slab rows of the fused FFN backward kernels (k_ffn_bwd_x.hip, k_ffn_dwbwd_x.hip): only of the paths this plan runs
-        if ((e == 16 && plan->ffn_bwd_x(16)) || (e == 32 && plan->ffn1_bwd_x32(32))) {
-            if (ffn1_bwd_x_slab_floats((int)e) > sl) sl = ffn1_bwd_x_slab_floats((int)e);
-        }
+    for (const FfnRoute& fr : plan->route.ffn)   // slab rows of the fused FFN backward kernels (k_ffn_bwd_x.hip, k_ffn_dwbwd_x.hip): only of the paths this plan runs
+        if (fr.px == FFN1_BWD_XS && ffn1_bwd_x_slab_floats(fr.e) > sl) sl = ffn1_bwd_x_slab_floats(fr.e);
     if (ffn_dw_bwd_x_slab_floats(16) > sl) sl = ffn_dw_bwd_x_slab_floats(16);
     if (ffn_dw_bwd_x_slab_floats(32) > sl) sl = ffn_dw_bwd_x_slab_floats(32);
     if (ffn_dw_bwd_h_slab_floats() > sl) sl = ffn_dw_bwd_h_slab_floats();
@@ -107,27 +105,42 @@ static int ffn_transposes(const lg_plan* pl, const float* P, int st, int j0, int
     return launch_transpose3(tsrc, tdst, trows, tcols, n, s);
 }
 
-// feed_forward half-block backward: dy (grad wrt block output) -> tmp (grad wrt the mid activation); bb.w?t[j] hold the transposed weights
+// feed_forward half-block backward: dy (grad wrt block output) -> tmp (grad wrt the mid activation); bb.w?t[j] hold the transposed weights.
+// The spatial kernel of the block's route (dh2; the depthwise gradients; dW3 / db3 unless it is the tile kernel), then the pixelwise kernel
+// (dx, the LayerNorm gradients; dW1 / dW2 when it is k_ffn1_bwd_xs), then the weight-gradient launches the route lists; dh2 is the only tensor
+// between the halves
 static int ffn_half_bwd(const lg_plan* pl, const float* P, float* G, int st, int j, const BlockBufs& fb, BwdBufs& bb, const float* dy,
                         float* tmp, int B, hipStream_t s) {
+    const FfnRoute& fr = pl->ffn(fb.e);
     const int e = fb.e, n1 = 4 * e;
-    const int hbf = pl->hidden_bf16(e) ? 1 : 0;       // bf16 storage of the hidden / saved FFN tensors
-    const int pre = pl->ffn_saves_preact(e) ? 1 : 0;  // fb.a1 / fb.a3 hold h1 / h3 (fb.g1 / fb.g3 unused): GELU re-evaluated where needed
+    const int hbf = fr.hbf ? 1 : 0;   // bf16 storage of the hidden / saved FFN tensors
+    const int pre = fr.pre ? 1 : 0;   // fb.a1 / fb.a3 hold h1 / h3 (fb.g1 / fb.g3 unused): GELU re-evaluated where needed
     const long Pn = (long)B * fb.h * fb.w;
-    if (pl->ffn_bwd_x(e) && (!pl->dwbwd_tile || hbf)) {
-        // two launches per half-block: the strip-walking spatial half (dh3 in LDS -> dh2, depthwise gradients, dW3 / db3) and the pixelwise
-        // half (h1 re-computed, dx, LayerNorm gradients, dW1 / db1, dW2 / db2); dh2 is the only tensor between them
+    // f16-pair products in k_ffn1_bwd_xs (round 5): the forward's operand scales of this block + max |dh2|, which the spatial half leaves in word 6
+    float* fsc = (bb.ffn_scales && fr.bwd_scales) ? bb.ffn_scales + ((size_t)st * 5 + j) * 8 : nullptr;
+    if (fr.dw == FFN_DWBWD_TILE) {
+        FfnDwBwdArgs fd;
+        fd.dy = dy; fd.g3 = pre ? fb.a3 : fb.g3; fd.h2 = fb.h2; fd.dh2 = bb.dh2; fd.w3t = bb.w3t[j]; fd.dww = P + pl->blk(st, j, B_DWW);
+        fd.slab_w = bb.rq.take(ffn_dw_bwd_slab_floats(e, B, fb.h, fb.w));
+        if (!fd.slab_w) return -3;
+        fd.slab_b = fd.slab_w + ffn_dw_bwd_slab_floats(e, B, fb.h, fb.w) / 10 * 9;
+        fd.d_dww = G + pl->blk(st, j, B_DWW); fd.d_dwb = G + pl->blk(st, j, B_DWB);
+        fd.B = B; fd.h = fb.h; fd.w = fb.w; fd.hbf = hbf; fd.pre = pre;
+        RC(launch_ffn_dw_bwd(e, fd, s));
+    } else {
+        // the strip walk: dh3 in an LDS ring on the saved pre-activation h3, or (FFN_DWBWD_H, round 6) on h3 re-computed from h2 and the depthwise bias
+        const bool h3re = fr.dw == FFN_DWBWD_H;
         FfnDwBwdXArgs fk;
-        const bool h3re = pl->ffn_h3_recompute(e) && (fb.h & 7) == 0 && (fb.w & 15) == 0;   // round 6: the forward saved h2 only; h3 is re-computed in the kernel
         fk.dy = dy; fk.h3 = h3re ? nullptr : fb.a3; fk.h2 = fb.h2; fk.dh2 = bb.dh2; fk.w3t = bb.w3t[j]; fk.dww = P + pl->blk(st, j, B_DWW); fk.dwb = P + pl->blk(st, j, B_DWB);
         fk.slab = bb.rq.take(h3re ? ffn_dw_bwd_h_slab_floats() : ffn_dw_bwd_x_slab_floats(e));
         if (!fk.slab) return -3;
         fk.d_dww = G + pl->blk(st, j, B_DWW); fk.d_dwb = G + pl->blk(st, j, B_DWB); fk.d_w3 = G + pl->blk(st, j, B_W3); fk.d_b3 = G + pl->blk(st, j, B_B3);
         fk.B = B; fk.h = fb.h; fk.w = fb.w; fk.hbf = hbf;
-        // f16-pair products in the pixelwise half (round 5): the forward's operand scales of this block + max |dh2|, which the spatial half leaves in word 6
-        float* fsc = (bb.ffn_scales && pl->ffn_f16x2(e) && !pl->ffn_bwd_bf16x3 && !hbf) ? bb.ffn_scales + ((size_t)st * 5 + j) * 8 : nullptr;
         fk.dh2_max = fsc ? fsc + 6 : nullptr;
         RC(h3re ? launch_ffn_dw_bwd_h(fk, s) : launch_ffn_dw_bwd_xs(e, fk, s));
+    }
+    if (fr.px == FFN1_BWD_XS) {
+        // one pass over dh2 re-computes h1 and yields dx, the LayerNorm gradients, dW1 / db1 and dW2 / db2
         Ffn1BwdXArgs fx;
         fx.scales = fsc;
         fx.dh2 = bb.dh2; fx.x = fb.xmid; fx.dy = dy; fx.dx = tmp;
@@ -138,78 +151,35 @@ static int ffn_half_bwd(const lg_plan* pl, const float* P, float* G, int st, int
         fx.d_w1 = G + pl->blk(st, j, B_W1); fx.d_b1 = G + pl->blk(st, j, B_B1); fx.d_w2 = G + pl->blk(st, j, B_W2); fx.d_b2 = G + pl->blk(st, j, B_B2);
         fx.d_ln2g = G + pl->blk(st, j, B_LN2G); fx.d_ln2b = G + pl->blk(st, j, B_LN2B);
         fx.P = Pn; fx.hbf = hbf;
-        return launch_ffn1_bwd_xs(e, fx, s);
-    }
-    const bool dwx32 = pl->ffn_dw_x32(e, fb.h, fb.w);
-    float* fsc2 = nullptr;
-    if (dwx32) {
-        // e = 32: the strip-walking spatial half (dh3 in an LDS ring -> dh2; depthwise gradients, dW3 / db3 in the same pass) on the saved
-        // pre-activation h3; the pixelwise half below is round 2's k_ffn1_bwd_x32 + the 128 x 128 weight-gradient launch
-        FfnDwBwdXArgs fk;
-        fk.dy = dy; fk.h3 = fb.a3; fk.h2 = fb.h2; fk.dh2 = bb.dh2; fk.w3t = bb.w3t[j]; fk.dww = P + pl->blk(st, j, B_DWW);
-        fk.slab = bb.rq.take(ffn_dw_bwd_x_slab_floats(e));
-        if (!fk.slab) return -3;
-        fk.d_dww = G + pl->blk(st, j, B_DWW); fk.d_dwb = G + pl->blk(st, j, B_DWB); fk.d_w3 = G + pl->blk(st, j, B_W3); fk.d_b3 = G + pl->blk(st, j, B_B3);
-        fk.B = B; fk.h = fb.h; fk.w = fb.w; fk.hbf = hbf;
-        fsc2 = (bb.ffn_scales && pl->ffn_f16x2(e) && !pl->ffn_bwd_bf16x3 && !hbf && pl->ffn1_bwd_x32(e)) ? bb.ffn_scales + ((size_t)st * 5 + j) * 8 : nullptr;
-        fk.dh2_max = fsc2 ? fsc2 + 6 : nullptr;
-        RC(launch_ffn_dw_bwd_xs(e, fk, s));
-    }
-    if (!dwx32) {
-        FfnDwBwdArgs fd;
-        fd.dy = dy; fd.g3 = pre ? fb.a3 : fb.g3; fd.h2 = fb.h2; fd.dh2 = bb.dh2; fd.w3t = bb.w3t[j]; fd.dww = P + pl->blk(st, j, B_DWW);
-        fd.slab_w = bb.rq.take(ffn_dw_bwd_slab_floats(e, B, fb.h, fb.w));
-        if (!fd.slab_w) return -3;
-        fd.slab_b = fd.slab_w + ffn_dw_bwd_slab_floats(e, B, fb.h, fb.w) / 10 * 9;
-        fd.d_dww = G + pl->blk(st, j, B_DWW); fd.d_dwb = G + pl->blk(st, j, B_DWB);
-        fd.B = B; fd.h = fb.h; fd.w = fb.w; fd.hbf = hbf; fd.pre = pre;
-        RC(launch_ffn_dw_bwd(e, fd, s));
-    }
-    if (pl->ffn_bwd_x(e) || pl->ffn1_bwd_x32(e)) {
-        // one pass over dh2 re-computes h1 and yields dx, the LayerNorm gradients, dW1 / db1 and dW2 / db2 (e = 16: h1 was not saved; e = 32:
-        // the saved gelu(h1) / gelu'(h1) are simply not read)
-        Ffn1BwdXArgs fx;
-        fx.scales = fsc2;      // (set only when dh2 came from k_ffn_dw_bwd_xs, which leaves max |dh2| behind)
-        fx.dh2 = bb.dh2; fx.x = fb.xmid; fx.dy = dy; fx.dx = tmp;
-        fx.w1 = P + pl->blk(st, j, B_W1); fx.b1 = P + pl->blk(st, j, B_B1); fx.w2t = bb.w2t[j]; fx.w1t = bb.w1t[j];
-        fx.ln2g = P + pl->blk(st, j, B_LN2G); fx.ln2b = P + pl->blk(st, j, B_LN2B);
-        fx.slab = bb.rq.take(ffn1_bwd_x_slab_floats(e));
-        if (!fx.slab) return -3;
-        fx.d_w1 = G + pl->blk(st, j, B_W1); fx.d_b1 = G + pl->blk(st, j, B_B1); fx.d_w2 = G + pl->blk(st, j, B_W2); fx.d_b2 = G + pl->blk(st, j, B_B2);
-        fx.d_ln2g = G + pl->blk(st, j, B_LN2G); fx.d_ln2b = G + pl->blk(st, j, B_LN2B);
-        fx.P = Pn; fx.hbf = hbf;
         RC(launch_ffn1_bwd_xs(e, fx, s));
-        if (dwx32) return 0;   // dW3 / db3 came out of k_ffn_dw_bwd_xs<32>
-        return wgrad(dy, e, fb.a3, n1, G + pl->blk(st, j, B_W3), n1, G + pl->blk(st, j, B_B3), Pn, e, n1, e, n1, 0, hbf, bb, s, pre);
+    } else {
+        Ffn1BwdArgs f1;
+        f1.dh2 = bb.dh2; f1.g1 = pre ? fb.a1 : fb.g1; f1.x = fb.xmid; f1.dy = dy; f1.dh1 = bb.dh1; f1.y2 = bb.y2; f1.dx = tmp;
+        f1.w2t = bb.w2t[j]; f1.w1t = bb.w1t[j];
+        f1.ln2g = P + pl->blk(st, j, B_LN2G); f1.ln2b = P + pl->blk(st, j, B_LN2B);
+        f1.d_ln2g = G + pl->blk(st, j, B_LN2G); f1.d_ln2b = G + pl->blk(st, j, B_LN2B); f1.part = bb.rq.take((size_t)PIXEL_PART_WGS * 2 * e);
+        if (!f1.part) return -3;
+        f1.P = Pn; f1.hbf = hbf; f1.pre = pre;
+        f1.w1 = nullptr; f1.wsplit = nullptr;
+        if (fr.px == FFN1_BWD_X32) { f1.w1 = P + pl->blk(st, j, B_W1); f1.wsplit = bb.wsp; }
+        f1.w1slab = nullptr; f1.d_w1 = nullptr; f1.d_b1 = nullptr;
+        if (!fr.wgrad_w1) {   // dW1 / db1 come out of k_ffn1_bwd itself
+            f1.w1slab = bb.rq.take((size_t)FFN1_BWD_WGS * ((size_t)n1 * e + n1));
+            if (!f1.w1slab) return -3;
+            f1.d_w1 = G + pl->blk(st, j, B_W1); f1.d_b1 = G + pl->blk(st, j, B_B1);
+        }
+        f1.w2slab = nullptr; f1.d_w2 = nullptr; f1.d_b2 = nullptr;
+        if (!fr.wgrad_w2) {   // dW2 / db2 too
+            f1.w2slab = bb.rq.take((size_t)FFN1_BWD_WGS * ((size_t)n1 * n1 + n1));
+            if (!f1.w2slab) return -3;
+            f1.d_w2 = G + pl->blk(st, j, B_W2); f1.d_b2 = G + pl->blk(st, j, B_B2);
+        }
+        RC(launch_ffn1_bwd(e, fr.px, f1, s));
     }
-    Ffn1BwdArgs f1;
-    f1.dh2 = bb.dh2; f1.g1 = pre ? fb.a1 : fb.g1; f1.x = fb.xmid; f1.dy = dy; f1.dh1 = bb.dh1; f1.y2 = bb.y2; f1.dx = tmp;
-    f1.w2t = bb.w2t[j]; f1.w1t = bb.w1t[j];
-    f1.ln2g = P + pl->blk(st, j, B_LN2G); f1.ln2b = P + pl->blk(st, j, B_LN2B);
-    f1.d_ln2g = G + pl->blk(st, j, B_LN2G); f1.d_ln2b = G + pl->blk(st, j, B_LN2B); f1.part = bb.rq.take((size_t)PIXEL_PART_WGS * 2 * e);
-    if (!f1.part) return -3;
-    f1.P = Pn; f1.hbf = hbf; f1.pre = pre;
-    f1.w1 = nullptr; f1.wsplit = nullptr;
-    if (e == 32 && pl->ffn_tile == 0) { f1.w1 = P + pl->blk(st, j, B_W1); f1.wsplit = bb.wsp; }   // LG_FFN_IMPL=strip|tile: the f32-MFMA kernel (A/B)
-    f1.w1slab = nullptr; f1.d_w1 = nullptr; f1.d_b1 = nullptr;
-    if (ffn1_bwd_fuses_w1(e)) {   // dW1 / db1 come out of k_ffn1_bwd itself
-        f1.w1slab = bb.rq.take((size_t)FFN1_BWD_WGS * ((size_t)n1 * e + n1));
-        if (!f1.w1slab) return -3;
-        f1.d_w1 = G + pl->blk(st, j, B_W1); f1.d_b1 = G + pl->blk(st, j, B_B1);
-    }
-    f1.w2slab = nullptr; f1.d_w2 = nullptr; f1.d_b2 = nullptr;
-    if (ffn1_bwd_fuses_w2(e, pre)) {   // dW2 / db2 too
-        f1.w2slab = bb.rq.take((size_t)FFN1_BWD_WGS * ((size_t)n1 * n1 + n1));
-        if (!f1.w2slab) return -3;
-        f1.d_w2 = G + pl->blk(st, j, B_W2); f1.d_b2 = G + pl->blk(st, j, B_B2);
-    }
-    RC(launch_ffn1_bwd(e, f1, s));
-    if (!ffn1_bwd_fuses_w2(e, pre))
-        RC(wgrad(bb.dh2, n1, fb.a1, n1, G + pl->blk(st, j, B_W2), n1, G + pl->blk(st, j, B_B2), Pn, n1, n1, n1, n1, hbf, hbf, bb, s, pre));
-    if (!ffn1_bwd_fuses_w1(e))
-        RC(wgrad(bb.dh1, n1, bb.y2, e, G + pl->blk(st, j, B_W1), e, G + pl->blk(st, j, B_B1), Pn, n1, e, n1, e, hbf, 0, bb, s));
-    // last: dh2's two readers run right behind its producer (Infinity Cache), this one only needs the saved gelu(h3) and dy
-    if (!dwx32) RC(wgrad(dy, e, fb.a3, n1, G + pl->blk(st, j, B_W3), n1, G + pl->blk(st, j, B_B3), Pn, e, n1, e, n1, 0, hbf, bb, s, pre));
+    if (fr.wgrad_w2) RC(wgrad(bb.dh2, n1, fb.a1, n1, G + pl->blk(st, j, B_W2), n1, G + pl->blk(st, j, B_B2), Pn, n1, n1, n1, n1, hbf, hbf, bb, s, pre));
+    if (fr.wgrad_w1) RC(wgrad(bb.dh1, n1, bb.y2, e, G + pl->blk(st, j, B_W1), e, G + pl->blk(st, j, B_B1), Pn, n1, e, n1, e, hbf, 0, bb, s));
+    // last: dh2's two readers run right behind its producer (Infinity Cache), this one only needs the saved h3 / gelu(h3) and dy
+    if (fr.wgrad_w3) RC(wgrad(dy, e, fb.a3, n1, G + pl->blk(st, j, B_W3), n1, G + pl->blk(st, j, B_B3), Pn, e, n1, e, n1, 0, hbf, bb, s, pre));
     return 0;
 }
 
@@ -222,7 +192,7 @@ static int fft_bwd_call(const lg_plan* pl, const float* P, float* G, int st, int
     fa.phaw = P + pl->blk(st, j, B_PHAW); fa.phab = P + pl->blk(st, j, B_PHAB);
     fa.d_ampw = G + pl->blk(st, j, B_AMPW); fa.d_ampb = G + pl->blk(st, j, B_AMPB);
     fa.d_phaw = G + pl->blk(st, j, B_PHAW); fa.d_phab = G + pl->blk(st, j, B_PHAB);
-    fa.ch = hc; fa.planes = B * hc; fa.n = fb.h; fa.h = fb.h; fa.w = fb.w; fa.part = part; fa.full = pl->fft_full;
+    fa.ch = hc; fa.planes = B * hc; fa.n = fb.h; fa.h = fb.h; fa.w = fb.w; fa.part = part; fa.full = pl->route.fft_full;
     return launch_fftmix_bwd(fa, s);
 }
 
@@ -232,7 +202,8 @@ static int mixer_half_bwd(const lg_plan* pl, const float* P, float* G, int st, i
     const int e = fb.e, hc = e / 2;
     const long Pn = (long)B * fb.h * fb.w;
     const int drop = (flags & LG_FLAG_DROPOUT) ? 1 : 0;
-    if (attn_bwd_fused(e) && !pl->attn_bwd_old) {
+    const MixerRoute& mr = pl->mixer(e);
+    if (mr.bwd == ATTN_BWD_F) {
         // round 4: three launches per half-block -- proj^T towards the global mixer (+ dropout keep bits, proj bias gradient), the FFT-mixer
         // backward, and ONE kernel for everything else (flash passes, to_qkv^T, LayerNorm backward, dx, every parameter gradient)
         uint32_t* keep = drop ? reinterpret_cast<uint32_t*>(bb.dym) : nullptr;
@@ -255,7 +226,7 @@ static int mixer_half_bwd(const lg_plan* pl, const float* P, float* G, int st, i
         af.d_pos = G + pl->blk(st, j, B_POS); af.d_qkvw = G + pl->blk(st, j, B_QKVW); af.d_qkvb = G + pl->blk(st, j, B_QKVB);
         af.d_projw = G + pl->blk(st, j, B_PROJW); af.d_ln1g = G + pl->blk(st, j, B_LN1G); af.d_ln1b = G + pl->blk(st, j, B_LN1B);
         af.B = B; af.h = fb.h; af.w = fb.w;
-        if (pl->attn_saves_stats(e)) { af.so = fb.att_o; af.sl = fb.att_l; }   // left by the forward's saving launch (block_mixer_fwd)
+        if (mr.stats) { af.so = fb.att_o; af.sl = fb.att_l; }   // left by the forward's saving launch (block_mixer_fwd)
         return launch_attn_bwd_f(e, af, s);
     }
     ProjO2BwdArgs po;
@@ -277,8 +248,8 @@ static int mixer_half_bwd(const lg_plan* pl, const float* P, float* G, int st, i
     at.d_qkvw = G + pl->blk(st, j, B_QKVW); at.d_qkvb = G + pl->blk(st, j, B_QKVB);
     if (attn_bwd_fuses_qkv(e)) at.y1 = nullptr;   // the epilogue kernel forms y1 itself and accumulates the to_qkv weight gradient
     if (!at.part) return -3;
-    at.B = B; at.h = fb.h; at.w = fb.w; at.core_m = pl->attn_bwd_core_m; at.stats = bb.attn_stats;
-    if (pl->attn_saves_stats(e) && !(e == 32 && pl->attn_bwd_core_m)) { at.so = fb.att_o; at.sl = fb.att_l; }   // left by the forward's saving launch (block_mixer_fwd)
+    at.B = B; at.h = fb.h; at.w = fb.w; at.core_m = mr.bwd == ATTN_BWD_R3_CORE_M ? 1 : 0; at.stats = bb.attn_stats;
+    if (mr.stats) { at.so = fb.att_o; at.sl = fb.att_l; }   // left by the forward's saving launch (block_mixer_fwd)
     RC(launch_attn_bwd(e, at, s));
     const int grid = attn_bwd_grid(e, B, fb.h, fb.w);
     RC(launch_reduce_slab(at.dpos_slab, grid, 1, 2 * 64 * 64, G + pl->blk(st, j, B_POS), 2 * 64 * 64, 1, 2 * 64 * 64, s));
@@ -307,7 +278,7 @@ int op_block_bwd(const lg_plan* pl, const float* P, float* G, int st, int j, int
     bb.ffn_scales = nb.ffn_scales;
     const BlockBufs& fb = nb.blk[j];
     if (which == 0) return fft_bwd_call(pl, P, G, st, j, fb, dy, dx, B, s, nb.fft_scratch, bb.slab_arena);   // no queue: summed at once
-    ReduceQueueScope rqs(bb, s, pl->reduce_per_block != 0);
+    ReduceQueueScope rqs(bb, s, pl->route.reduce_per_block);
     int rc = which == 1 ? 0 : ffn_transposes(pl, P, st, j, j + 1, nb, bb, s);
     if (!rc) rc = which == 1 ? mixer_half_bwd(pl, P, G, st, j, fb, bb, nb.posT, dy, dx, B, 0, 0, s)
                              : ffn_half_bwd(pl, P, G, st, j, fb, bb, dy, dx, B, s);
@@ -320,7 +291,7 @@ static int data_step_bwd(const lg_plan* pl, const float* P, float* G, int st, co
                          const float* pan, const float* g, float* dz, int B, hipStream_t s) {
     const lg_config& c = pl->cfg;
     const int planes = B * c.C, H = c.H, W = c.W;
-    if (pl->dstep_fused(H, W)) {
+    if (pl->route.dstep_fused) {
         // one pixelwise + one plane-in-LDS launch (k_dstep.hip) instead of the nine tile launches below
         DstepBwdArgs a;
         a.g = g; a.z = zin; a.pan = pan; a.t1 = nb.t1[st]; a.r = nb.r[st]; a.s1 = nb.s1[st]; a.dz = dz;
@@ -442,7 +413,7 @@ int op_data_step_bwd(const lg_plan* pl, const float* P, float* G, int st, NetBuf
                      const float* g, float* dz, int B, hipStream_t s) {
     BwdBufs bb;
     carve_bwd(pl, B, bwd_ws, bb);
-    ReduceQueueScope rqs(bb, s, pl->reduce_per_block != 0);
+    ReduceQueueScope rqs(bb, s, pl->route.reduce_per_block);
     const int rc = data_step_bwd(pl, P, G, st, nb, bb, z_in, pan, g, dz, B, s);
     const int rc2 = reduce_queue_end();
     return rc ? rc : rc2;
@@ -455,7 +426,7 @@ int op_lgt_bwd(const lg_plan* pl, const float* P, float* G, int st, NetBufs& nb,
     bb.fft_scratch = nb.fft_scratch;
     bb.ffn_scales = nb.ffn_scales;
     bb.dzA = dz;                       // lgt_bwd leaves the gradient wrt the LGT's input here
-    ReduceQueueScope rqs(bb, s, pl->reduce_per_block != 0);
+    ReduceQueueScope rqs(bb, s, pl->route.reduce_per_block);
     const int rc = lgt_bwd(pl, P, G, st, nb, bb, dout, z, B, flags, seed, s);
     const int rc2 = reduce_queue_end();
     return rc ? rc : rc2;
@@ -469,7 +440,7 @@ int net_backward(const lg_plan* pl, const float* P, float* G, const float* ms, c
     carve_bwd(pl, B, bwd_ws, bb);
     bb.fft_scratch = nb.fft_scratch;
     bb.ffn_scales = nb.ffn_scales;
-    ReduceQueueScope rqs(bb, s, pl->reduce_per_block != 0);
+    ReduceQueueScope rqs(bb, s, pl->route.reduce_per_block);
     if (flags & LG_FLAG_CHAINED) {
         // intended unfolding (every stage live): LGT_i then data step i, last stage first; each LGT reads its own activation set
         const float* g = dout;

@@ -863,7 +863,6 @@ int launch_bwd_t(const DstepBwdArgs& a, hipStream_t s) {
 }
 }  // namespace
 
-bool lg_plan::dstep_fused(int h, int w) const { return !dstep_tiles && dstep_fused_ok(cfg.C, h, w); }
 bool dstep_fused_ok(int C, int H, int W) { return H == W && (H == 128 || H == 64) && (C == 4 || C == 8); }
 
 int launch_dstep_fwd(const DstepFwdArgs& a, hipStream_t s) {

@@ -1189,43 +1189,46 @@ static int launch_ffn_fused_bf_t(const Ffn1Args& a1, const Ffn2Args& a2, hipStre
     return 0;
 }
 
-// returns LG_FFN_NOT_FUSED if the fused kernels do not cover this size (caller falls back to k_ffn1 + k_ffn2)
+// runs the kernel the block's route names (a1.kernel: FfnFwdKernel, route.h).  The save pointers do not select the kernel: they must be
+// the ones it writes (round 1's kernels: all five slots or none; k_ffn_xr: h2 / h3 at most; the others check their own)
 int launch_ffn_fused(int e, const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s) {
-    if (a1.hbf) {   // throughput mode: bf16 matrix cores for the three GEMMs
-#ifdef LG_BUILD_AB   // round 1's bf16 tile kernels: A/B builds only (lg_plan_create rejects precision = 1 with an FFN variant otherwise)
-        if (e == 16 && a1.tile16 != 0) return launch_ffn_fused_bf_t<16>(a1, a2, s);
-        if (e == 32 && (a1.tile16 != 0 || !a1.wsplit)) return launch_ffn_fused_bf_t<32>(a1, a2, s);
+    const bool five = a1.a1s && a1.g1s && a1.h2 && a2.a3s && a2.g3s, none = !a1.a1s && !a1.g1s && !a2.a3s && !a2.g3s;
+    switch (a1.kernel) {
+#ifdef LG_BUILD_AB   // round 1's bf16 tile kernels, its f32 tile kernel at e = 16 and k_ffn_xp: A/B builds only (lg_plan_create rejects their variants otherwise)
+    case FFN_FWD_TILE_BF16:
+        if (!a1.hbf || !(five || none)) break;
+        if (e == 16) return launch_ffn_fused_bf_t<16>(a1, a2, s);
+        if (e == 32) return launch_ffn_fused_bf_t<32>(a1, a2, s);
+        break;
+    case FFN_FWD_XP:
+        if (e != 16 || a1.hbf || !(five || none)) break;
+        return launch_ffn_xp(a1, a2, s);
 #endif
-        if (e == 16 && (a1.tile16 == 0 || a1.tile16 == 4)) {                            // k_ffn_xr<., NP = 1> (round 6) / k_ffn_xs<., NP = 1> (the other save modes, LG_VAR_FFN_XS)
-            const bool save = a1.h2 != nullptr, h2h3 = save && !a1.a1s && !a1.g1s && a2.a3s && !a2.g3s;
-            if (a1.tile16 == 0 && (!save || h2h3)) return launch_ffn_xr(a1, a2, s);
-            return launch_ffn_xs(a1, a2, s);
-        }
-        if (e == 32 && a1.tile16 == 0 && a1.wsplit) return launch_ffn_x32(a1, a2, s);   // k_ffn_x32<., NP = 1>
-        if (e == 64) return LG_FFN_NOT_FUSED;
-        lg_set_error("ffn: precision = 1 with an FFN variant needs a `make AB=1` build");
-        return -2;
-    }
-    // e = 16: the strip kernel on the bf16 matrix pipe in fp32-equivalent split arithmetic (k_ffn_x.hip); for A/B runs the plan's
-    // switch (lg_config.variant & LG_VAR_FFN_IMPL_MASK) selects the f32-MFMA strip kernel (1), the per-tile kernel (2: `make AB=1` builds)
-    // it replaced, or the software-pipelined variant k_ffn_xp (3: same results bit for bit, measured 2.5 % slower)
-#ifdef LG_BUILD_AB
-    if (e == 16 && a1.tile16 == 3) return launch_ffn_xp(a1, a2, s);
-#else
-    if (e == 16 && a1.tile16 == 3) { lg_set_error("LG_FFN_IMPL=xp: k_ffn_xp is an A/B kernel, build the library with `make AB=1`"); return -2; }
-#endif
-#ifdef LG_BUILD_AB
-    if (e == 16 && a1.tile16 == 2) return launch_ffn_fused_t<16>(a1, a2, s);   // round 1's per-tile kernel at e = 16: A/B builds only
-#endif
-    if (e == 16 && a1.tile16 == 1) return launch_ffn_strip(a1, a2, s);
-    if (e == 16) {
-        // round 6: the register chain k_ffn_xr where it exists (f16 pairs, nothing or h2 / h3 saved); k_ffn_xs for the bf16 x 3 arithmetic, the
-        // other save modes and as the A/B variant LG_VAR_FFN_XS
-        const bool save = a1.h2 != nullptr, h2h3 = save && !a1.a1s && !a1.g1s && !a2.g3s;   // (a3s null: h2 alone, the backward re-computes h3)
-        if (a1.tile16 == 0 && a1.scales && (!save || h2h3)) return launch_ffn_xr(a1, a2, s);
+    case FFN_FWD_XR:
+        if (e != 16 || a1.a1s || a1.g1s || a2.g3s || (a2.a3s && !a1.h2)) break;
+        return launch_ffn_xr(a1, a2, s);
+    case FFN_FWD_XS:
+        if (e != 16) break;
         return launch_ffn_xs(a1, a2, s);
+    case FFN_FWD_X32:
+        if (e != 32) break;
+        return launch_ffn_x32(a1, a2, s);
+    case FFN_FWD_X64:
+        if (e != 64 || a1.hbf) break;
+        return launch_ffn_x64(a1, a2, s);   // two kernels, split-bf16 GEMMs
+    case FFN_FWD_STRIP:
+        if (e != 16 || a1.hbf || !(five || none)) break;
+        return launch_ffn_strip(a1, a2, s);
+    case FFN_FWD_TILE:
+        if (a1.hbf || !(five || none)) break;
+#ifdef LG_BUILD_AB
+        if (e == 16) return launch_ffn_fused_t<16>(a1, a2, s);
+#endif
+        if (e == 32) return launch_ffn_fused_t<32>(a1, a2, s);
+        break;
+    default: break;
     }
-    if (e == 32) return (a1.tile16 == 0 && a1.wsplit) ? launch_ffn_x32(a1, a2, s) : launch_ffn_fused_t<32>(a1, a2, s);
-    if (e == 64 && a1.tile16 == 0 && a1.wsplit && a1.h2) return launch_ffn_x64(a1, a2, s);   // two kernels, split-bf16 GEMMs
-    return LG_FFN_NOT_FUSED;
+    lg_set_error("ffn: forward kernel %d does not run e=%d, hbf=%d with these save slots (a1 %d, g1 %d, h2 %d, a3 %d, g3 %d)", a1.kernel, e, a1.hbf,
+                 a1.a1s != nullptr, a1.g1s != nullptr, a1.h2 != nullptr, a2.a3s != nullptr, a2.g3s != nullptr);
+    return -2;
 }

@@ -700,9 +700,14 @@ static int launch_ffn1_bwd_t(const Ffn1BwdArgs& a, hipStream_t s) {
     if (rc || !ffn1_bwd_fuses_w2(E, a.pre)) return rc;
     return launch_reduce_slab_wb(a.w2slab, a.w2slab + (size_t)grid * N1 * N1, grid, N1, N1, a.d_w2, N1, a.d_b2, s);
 }
-int launch_ffn1_bwd(int e, const Ffn1BwdArgs& a, hipStream_t s) {
+int launch_ffn1_bwd(int e, Ffn1BwdKernel k, const Ffn1BwdArgs& a, hipStream_t s) {
+    if (k == FFN1_BWD_X32) {   // (e = 32 only: the split-bf16 kernel needs the forward W1 and the fragment scratch, the f32-MFMA kernel takes neither)
+        if (e != 32 || !a.w1 || !a.wsplit) { lg_set_error("ffn1_bwd: k_ffn1_bwd_x32 runs e = 32 with w1 and the weight-fragment scratch (e=%d)", e); return -2; }
+        return launch_ffn1_bwd_x32(a, a.w1, a.wsplit, s);
+    }
+    if (k != FFN1_BWD_TILE || a.w1 || a.wsplit) { lg_set_error("ffn1_bwd: k_ffn1_bwd takes no w1 / wsplit (pixelwise kernel %d of the route)", (int)k); return -2; }
     if (e == 16) return launch_ffn1_bwd_t<16, 1>(a, s);
-    if (e == 32) return (a.w1 && a.wsplit) ? launch_ffn1_bwd_x32(a, a.w1, a.wsplit, s) : launch_ffn1_bwd_t<32, 2>(a, s);
+    if (e == 32) return launch_ffn1_bwd_t<32, 2>(a, s);
     if (e == 64) return launch_ffn1_bwd_t<64, 1>(a, s);
     lg_set_error("ffn1_bwd: e=%d unsupported", e);
     return -1;

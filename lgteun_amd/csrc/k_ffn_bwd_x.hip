@@ -500,7 +500,6 @@ int launch_t(const Ffn1BwdXArgs& a, hipStream_t s) {
 }   // namespace
 
 size_t ffn1_bwd_x_slab_floats(int e) { return (size_t)ffn1_bwd_x_wgs(e) * (e == 16 ? KB<16>::ROW : KB<32>::ROW); }
-bool ffn1_bwd_x32_built() { return true; }
 
 int launch_ffn1_bwd_xs(int e, const Ffn1BwdXArgs& a, hipStream_t s) {
     ProfScope prof__(LG_K_FFN1_BWD, s);

@@ -142,7 +142,7 @@ struct Ffn1Args {
     void* g1s;       // optional save [P,4e]: gelu'(h1)       (backward never re-evaluates GELU)
     void* h2;        // [P,4e] = W2 gelu(W1 LN(x) + b1) + b2
     int hbf;         // hidden storage: 0 fp32, 1 bf16 (hstore.h)
-    int tile16;      // A/B switch (lg_plan::ffn_tile / ffn_xs): 0 = split-arithmetic kernels (default), 1 = f32-MFMA strip kernel, 2 = f32-MFMA per-tile kernel, 3 = software-pipelined split kernel k_ffn_xp (e = 16), 4 = the channel-split k_ffn_xs where the register-chain k_ffn_xr is the default (e = 16)
+    int kernel;      // host only: the FfnFwdKernel of the block's route (route.h); launch_ffn_fused switches on it
     const float *ln2g, *ln2b, *w1, *b1, *w2, *b2;
     long P;
     void* wsplit;    // workspace scratch for pre-split weight fragments (ffn_wsplit_bytes; k_ffn_x32.hip), or nullptr
@@ -172,9 +172,7 @@ struct Ffn2Args {
     int B, h, w;
 };
 int launch_ffn2(int e, const Ffn2Args& a, hipStream_t s);
-// fused feed_forward half-block (h2 stays in LDS); returns LG_FFN_NOT_FUSED when e is not covered -> use launch_ffn1 + launch_ffn2
-// (a code of its own: 1 is hipErrorInvalidValue)
-#define LG_FFN_NOT_FUSED (-1000)
+// fused feed_forward half-block (h2 stays in LDS): runs a1.kernel; -2 when the save pointers are not the ones that kernel writes
 int launch_ffn_fused(int e, const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s);
 int launch_ffn_xs(const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s);   // e = 16, fp32 storage (k_ffn_x.hip)
 int launch_ffn_xr(const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s);   // e = 16, f16 pairs, fp32 storage: the register chain (k_ffn_xr.hip, round 6)

@@ -219,6 +219,12 @@ class Engine:
             self._plans[key] = out
         return self._plans[key]
 
+    def describe(self, H, W):
+        """which kernels the plan of an H x W PAN runs, what its saving forward keeps and its backward reads (lg_plan_describe)"""
+        buf = ctypes.create_string_buffer(2048)
+        check(self.lib.lg_plan_describe(self.plan(H, W), buf, len(buf)), 'lg_plan_describe')
+        return buf.value.decode()
+
     def workspace(self, plan, B, train):
         """train: 0 inference, 1 training, 2 chained training (K saved activation sets)"""
         need = self.lib.lg_workspace_bytes(plan, B, int(train))

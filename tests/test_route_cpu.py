@@ -1,0 +1,197 @@
+"""CPU (no GPU) checks of the kernel routes a plan resolves at creation (csrc/route.hip): lg_plan_create and lg_plan_describe are host code."""
+import ctypes
+import itertools
+import json
+import os
+
+import pytest
+
+from lgteun_amd import _lib
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+
+K = 2
+N_OFF = 12 + K + 119 * K
+OFFS = (ctypes.c_int64 * N_OFF)(*[4 * i for i in range(N_OFF)])
+
+# The resolver fills the FFN route, the mixer route and the net-level switches in three functions that read disjoint bit groups, except for the
+# FFN implementation field and LG_VAR_FFN_BF16X3 (the local mixer's operand scales ride in the FFN's prep launch): both groups carry those two.
+# test_bit_groups_are_independent checks the claim on the text; the sweeps below then iterate each group on its own instead of 4 * 3 * 2^14 words.
+FFN_BITS = [_lib.LG_VAR_FFN_BWD32_PAIR, _lib.LG_VAR_FFN_DWBWD_TILE, _lib.LG_VAR_FFN_BF16X3, _lib.LG_VAR_FFN_BWD_BF16X3, _lib.LG_VAR_FFN_XS,
+            _lib.LG_VAR_FFN_H3_RECOMPUTE]
+MIXER_BITS = [_lib.LG_VAR_ATTN_BWD_R3, _lib.LG_VAR_ATTN_FWD_VALU, _lib.LG_VAR_FFN_BF16X3, _lib.LG_VAR_ATTN_BWD_CORE_M, _lib.LG_VAR_ATTN_BF16X3,
+              _lib.LG_VAR_ATTN_BWD_RESTATS]
+NET_BITS = [_lib.LG_VAR_DSTEP_TILES, _lib.LG_VAR_FFT_FULL, _lib.LG_VAR_REDUCE_PER_BLOCK]
+SINGLE = [1, 2, 3, _lib.LG_VAR_FFN_SAVE3, _lib.LG_VAR_FFN_SAVE5] + [1 << b for b in range(4, 18)]
+
+
+def subsets(bits):
+    for r in range(len(bits) + 1):
+        for c in itertools.combinations(bits, r):
+            yield sum(c)
+
+
+class Plan:
+    """a plan of the library under test, or the message it was refused with"""
+
+    def __init__(self, C, prec, H, W, variant):
+        self.lib = _lib.lib()
+        self.handle = ctypes.c_void_p()
+        cfg = _lib.LgConfig(C, K, H, W, prec, variant)
+        rc = self.lib.lg_plan_create(ctypes.byref(cfg), OFFS, N_OFF, ctypes.byref(self.handle))
+        self.error = None if rc == 0 else self.lib.lg_last_error().decode()
+        if rc:
+            assert rc < 0 and self.error, (rc, self.error)
+            self.handle = None
+
+    def describe(self):
+        buf = ctypes.create_string_buffer(2048)
+        assert self.lib.lg_plan_describe(self.handle, buf, len(buf)) == 0, self.lib.lg_last_error()
+        return buf.value.decode()
+
+    def workspace_bytes(self):
+        return [int(self.lib.lg_workspace_bytes(self.handle, B, t)) for B in (1, 2) for t in (0, 1, 2)]
+
+    def __del__(self):
+        if self.handle:
+            self.lib.lg_plan_destroy(self.handle)
+
+
+def parse(text):
+    """{(level, mode): (ffn fields, mixer fields)} of the per-level lines, and the net line"""
+    lines = text.splitlines()
+    assert lines[0].startswith('net ') and len(lines) == 7, text
+    out = {}
+    for line in lines[1:]:
+        head, rest = line.split(': ', 1)
+        ffn, mixer = rest.split(' | ')
+        out[(int(head[1]), head.split()[-1])] = (dict(kv.split('=', 1) for kv in ffn.split()), dict(kv.split('=', 1) for kv in mixer.split()))
+    assert sorted(out) == [(lvl, mode) for lvl in (0, 1) for mode in ('bwd', 'fwd', 'save')], text
+    return lines[0], out
+
+
+def check_reads_are_written(text):
+    _, r = parse(text)
+    for lvl in (0, 1):
+        (fs, ms), (fb, mb) = r[(lvl, 'save')], r[(lvl, 'bwd')]
+        # a slot is named with what it holds ('a3' gelu(h3), 'a3:h3' the pre-activation): the backward has to read the form that was written
+        written, read = set(fs['writes'].split(',')), set(fb['reads'].split(','))
+        assert read <= written, (lvl, text)
+        assert (mb['stats'] == 'saved') <= (ms['writes'] == 'o,l'), (lvl, text)
+        assert r[(lvl, 'fwd')][0]['ffn'] and fs['ffn'] and fb['ffn'] and mb['mixer'], text
+
+
+CONFIGS = [(C, prec, n) for C in (4, 8) for prec in (0, 1) for n in (32, 48, 128)]   # 48: the level-1 width is 8 mod 16 (no 16-wide strips)
+
+
+@pytest.mark.parametrize('C,prec,n', CONFIGS)
+def test_every_backward_read_is_a_forward_write(C, prec, n):
+    words = {impl | save | rest for impl in range(4) for save in (0, _lib.LG_VAR_FFN_SAVE3, _lib.LG_VAR_FFN_SAVE5) for rest in subsets(FFN_BITS)}
+    words |= {impl | rest for impl in range(4) for rest in subsets(MIXER_BITS)}
+    words |= set(subsets(NET_BITS)) | set(SINGLE)
+    accepted = 0
+    for v in sorted(words):
+        p = Plan(C, prec, n, n, v)
+        if p.error is not None:
+            assert 'AB=1' in p.error, (hex(v), p.error)   # every word of the product is a valid one: only the build can refuse it
+            continue
+        accepted += 1
+        check_reads_are_written(p.describe())
+    assert accepted >= len(words) // 4
+
+
+def test_bit_groups_are_independent():
+    """a bit outside a group leaves that group's part of the text alone, on the default and on every single switch"""
+    def parts(text):
+        net, r = parse(text)
+        return net.split(': ')[1], [r[k][0] for k in sorted(r)], [r[k][1] for k in sorted(r)]
+    for C, prec in ((4, 0), (8, 0), (4, 1)):
+        for base in [0] + SINGLE:
+            p0 = Plan(C, prec, 128, 128, base)
+            if p0.error is not None:
+                continue
+            net0, ffn0, mix0 = parts(p0.describe())
+            for bit in set(FFN_BITS + MIXER_BITS + NET_BITS) - {base}:
+                p1 = Plan(C, prec, 128, 128, base | bit)
+                assert p1.error is None
+                net1, ffn1, mix1 = parts(p1.describe())
+                assert net1 == net0 or bit in NET_BITS
+                assert ffn1 == ffn0 or bit in FFN_BITS
+                assert mix1 == mix0 or bit in MIXER_BITS
+
+
+def test_invalid_variant_words_are_rejected():
+    for v in (1 << 18, 1 << 20, 1 << 31, _lib.LG_VAR_REDUCE_PER_BLOCK | 1 << 19):
+        p = Plan(4, 0, 32, 32, v)
+        assert p.error is not None and 'unknown variant bits' in p.error
+    p = Plan(4, 0, 32, 32, _lib.LG_VAR_FFN_SAVE3 | _lib.LG_VAR_FFN_SAVE5)
+    assert p.error is not None and 'invalid FFN save variant' in p.error
+
+
+# the default plans at 128 x 128; the kernel names are the ones a kernel trace of the library before the route table shows for these configurations
+DEFAULT_ROUTES = {
+    (4, 0): """\
+net C=4 128x128 precision=0 variant=0x0: dstep=fused fft=k_fftmix_r reduce=merged
+L0 e=16 128x128 fwd: ffn=k_ffn_xr arith=f16x2 hidden=fp32 | mixer=k_attn_m arith=f16x2
+L0 e=16 128x128 save: ffn=k_ffn_xr writes=h2,a3:h3 | mixer=k_attn_m writes=o,l
+L0 e=16 128x128 bwd: ffn=k_ffn_dw_bwd_xs+k_ffn1_bwd_xs arith=f16x2 reads=h2,a3:h3 | mixer=k_attn_bwd_f stats=saved
+L1 e=32 64x64 fwd: ffn=k_ffn_x32 arith=f16x2 hidden=fp32 | mixer=k_attn_m arith=f16x2
+L1 e=32 64x64 save: ffn=k_ffn_x32 writes=h2,a3:h3 | mixer=k_attn_m writes=o,l
+L1 e=32 64x64 bwd: ffn=k_ffn_dw_bwd_xs+k_ffn1_bwd_xs arith=f16x2 reads=h2,a3:h3 | mixer=k_attn_bwd_core+k_attn_bwd_epi stats=saved
+""",
+    (4, 1): """\
+net C=4 128x128 precision=1 variant=0x0: dstep=fused fft=k_fftmix_r reduce=merged
+L0 e=16 128x128 fwd: ffn=k_ffn_xr arith=bf16 hidden=bf16 | mixer=k_attn_m arith=bf16
+L0 e=16 128x128 save: ffn=k_ffn_xr writes=h2,a3:h3 | mixer=k_attn_m writes=-
+L0 e=16 128x128 bwd: ffn=k_ffn_dw_bwd_xs+k_ffn1_bwd_xs arith=bf16 reads=h2,a3:h3 | mixer=k_attn_bwd_f stats=recomputed
+L1 e=32 64x64 fwd: ffn=k_ffn_x32 arith=bf16 hidden=bf16 | mixer=k_attn_m arith=bf16
+L1 e=32 64x64 save: ffn=k_ffn_x32 writes=h2,a3:h3 | mixer=k_attn_m writes=-
+L1 e=32 64x64 bwd: ffn=k_ffn_dw_bwd_xs+k_ffn1_bwd_xs arith=bf16 reads=h2,a3:h3 | mixer=k_attn_bwd_core+k_attn_bwd_epi stats=recomputed
+""",
+    (8, 0): """\
+net C=8 128x128 precision=0 variant=0x0: dstep=fused fft=k_fftmix_r reduce=merged
+L0 e=32 128x128 fwd: ffn=k_ffn_x32 arith=f16x2 hidden=fp32 | mixer=k_attn_m arith=f16x2
+L0 e=32 128x128 save: ffn=k_ffn_x32 writes=h2,a3:h3 | mixer=k_attn_m writes=o,l
+L0 e=32 128x128 bwd: ffn=k_ffn_dw_bwd_xs+k_ffn1_bwd_xs arith=f16x2 reads=h2,a3:h3 | mixer=k_attn_bwd_core+k_attn_bwd_epi stats=saved
+L1 e=64 64x64 fwd: ffn=k_ffn1_x64+k_ffn2_x64 arith=f16x2 hidden=fp32 | mixer=k_attn_m arith=f16x2
+L1 e=64 64x64 save: ffn=k_ffn1_x64+k_ffn2_x64 writes=a1,g1,h2,a3,g3 | mixer=k_attn_m writes=o,l
+L1 e=64 64x64 bwd: ffn=k_ffn_dw_bwd+k_ffn1_bwd+k_wgrad(W2)+k_wgrad(W1)+k_wgrad(W3) arith=f32 reads=a1,g1,h2,a3,g3 | mixer=k_attn_bwd_core+k_attn_bwd_epi stats=saved
+""",
+    (8, 1): """\
+net C=8 128x128 precision=1 variant=0x0: dstep=fused fft=k_fftmix_r reduce=merged
+L0 e=32 128x128 fwd: ffn=k_ffn_x32 arith=bf16 hidden=bf16 | mixer=k_attn_m arith=bf16
+L0 e=32 128x128 save: ffn=k_ffn_x32 writes=h2,a3:h3 | mixer=k_attn_m writes=-
+L0 e=32 128x128 bwd: ffn=k_ffn_dw_bwd_xs+k_ffn1_bwd_xs arith=bf16 reads=h2,a3:h3 | mixer=k_attn_bwd_core+k_attn_bwd_epi stats=recomputed
+L1 e=64 64x64 fwd: ffn=k_ffn1_x64+k_ffn2_x64 arith=bf16x3 hidden=fp32 | mixer=k_attn_m arith=bf16
+L1 e=64 64x64 save: ffn=k_ffn1_x64+k_ffn2_x64 writes=a1,g1,h2,a3,g3 | mixer=k_attn_m writes=-
+L1 e=64 64x64 bwd: ffn=k_ffn_dw_bwd+k_ffn1_bwd+k_wgrad(W2)+k_wgrad(W1)+k_wgrad(W3) arith=f32 reads=a1,g1,h2,a3,g3 | mixer=k_attn_bwd_core+k_attn_bwd_epi stats=recomputed
+""",
+}
+
+
+@pytest.mark.parametrize('C,prec', sorted(DEFAULT_ROUTES))
+def test_default_routes_are_pinned(C, prec):
+    p = Plan(C, prec, 128, 128, 0)
+    assert p.error is None
+    assert p.describe() == DEFAULT_ROUTES[(C, prec)]
+
+
+def test_describe_reports_a_short_buffer():
+    p = Plan(4, 0, 128, 128, 0)
+    buf = ctypes.create_string_buffer(64)
+    assert p.lib.lg_plan_describe(p.handle, buf, len(buf)) == -3 and b'too small' in p.lib.lg_last_error()
+
+
+def test_workspace_bytes_are_those_of_the_library_before_the_route_table():
+    with open(os.path.join(GOLD, 'workspace_bytes.json')) as f:
+        gold = json.load(f)
+    assert gold['K'] == K
+    seen = set()
+    for c in gold['cases']:
+        p = Plan(c['C'], c['precision'], c['H'], c['W'], c['variant'])
+        if p.error is not None:
+            assert 'AB=1' in p.error   # (recorded from a `make AB=1` build; the product build carries fewer variants, with the same sizes)
+            continue
+        assert p.workspace_bytes() == c['bytes'], c
+        seen.add(c['variant'])
+    assert {0, 1, _lib.LG_VAR_FFN_SAVE3, _lib.LG_VAR_FFN_SAVE5} | {1 << b for b in range(4, 18)} <= seen
