@@ -283,6 +283,29 @@ int lg_batch_assemble(const void* pan, const void* lr, const void* mul, const fl
                       const uint32_t* flips, float* o_pan, float* o_lr, float* o_mul, float* o_pan_l, int32_t B, int32_t C, int32_t H, int32_t W,
                       int32_t h, int32_t w, int32_t dtype, float divisor, int32_t n_div, float post_scale, void* stream);
 
+/* ---- training from a raw scene (lgteun_amd/wald.py; kernels in lgteun_amd/csrc/k_wald.hip and k_batch.hip) ----
+ * Arguments are validated before any HIP call; the calls allocate nothing and synchronise nothing. */
+/* Wald's degradation: a separable FIR low-pass and decimation by 4 of `planes` planes [H, W] of sample type `dtype`.  taps: a DEVICE array
+ * [planes, n_taps] of fp64, one row per plane, used on both axes; n_taps odd, in 1 .. 63.  Output (i, j) of a plane is the filtered plane at
+ * (4 i + phase, 4 j + phase), phase in 0 .. 3; indices past the border are clamped into the plane (replicate).  H, W: multiples of 4 in
+ * 8 .. 65536.  fp64 arithmetic: the row pass, then the column pass, each sum_k taps[k] * x[. + k - n_taps / 2] with every product and every
+ * sum rounded on its own, in ascending k from 0.0.  out [planes, H/4, W/4]: fp32 (out_f32 = 1: the fp64 value rounded once) or the input's
+ * integer type (out_f32 = 0, integer planes only: round half to even, saturated to the type's range, NaN -> 0).  An output's bits depend on
+ * its own samples and taps only, not on the launch geometry or on the other planes of the call. */
+int lg_fir_decimate4(const void* in, void* out, const double* taps, int64_t planes, int32_t H, int32_t W, int32_t n_taps, int32_t phase,
+                     int32_t dtype, int32_t out_f32, void* stream);
+/* One training / evaluation batch cut out of ONE device-resident scene in two launches (gather, window pyramid): pan [1,Hs,Ws],
+ * lr [C,Hs/4,Ws/4], mul [C,Hs,Ws] (NULL together with o_mul) in sample type `dtype`; Hs, Ws multiples of 4 in 8 .. 65536.  Item b is the
+ * P x Q window (multiples of 4 in 8 .. 4096, not larger than the scene) at origin first + b of `origins`, a DEVICE int32 list of n_windows
+ * pairs (oy, ox) in PAN pixels, multiples of 4; values are clamped into the scene and rounded down to the 4-pixel grid, so no value becomes
+ * an address outside it.  o_pan [B,1,P,Q], o_lr [B,C,P/4,Q/4], o_mul [B,C,P,Q], o_pan_l [B,1,P/4,Q/4]: contiguous fp32, every one bit for
+ * bit what lg_batch_assemble writes for a store whose item b is that window (pan_l by lg_pyr_down2 of the window: the pyramid reflects at
+ * the WINDOW's border), with the same flip word and (divisor, n_div, post_scale).  Scene and output arrays 16-byte aligned (window rows
+ * need not be).  No atomics.  1 <= B <= 65535, 1 <= C <= 16. */
+int lg_window_assemble(const void* pan, const void* lr, const void* mul, const int32_t* origins, int64_t n_windows, int64_t first,
+                       const uint32_t* flips, float* o_pan, float* o_lr, float* o_mul, float* o_pan_l, int32_t B, int32_t C, int32_t Hs, int32_t Ws,
+                       int32_t P, int32_t Q, int32_t dtype, float divisor, int32_t n_div, float post_scale, void* stream);
+
 /* ---- tiled scene fusion (lgteun_amd/scene.py; kernels in lgteun_amd/csrc/k_scene.hip) ----
  * A scene larger than one plan (or off the 16-pixel grid) is cut into overlapping tiles, the tiles go through lgteun_forward in batches and
  * the outputs are blended back.  The scene is device-resident in the files' sample type: pan [1,H,W], ms [C,H/4,W/4]; H, W multiples of 4

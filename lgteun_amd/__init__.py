@@ -4,7 +4,8 @@ reference's MODELS-registry / nn.Module surface.  Compute = hand-written HIP ker
 from .builder import MODELS, build_model  # noqa: F401
 from .unlg_former import Pansharpening, UnlgFormer  # noqa: F401
 from .engine import Engine, FusedAdam, FusedAdamW, FusedRMSprop, FusedSGD, canonical_names  # noqa: F401
-from .dataset import DATASETS, PSDataset, PrefetchLoader, ShardedSampler, build_dataset, build_loader  # noqa: F401
+from .dataset import DATASETS, PSDataset, PrefetchLoader, SceneDataset, ShardedSampler, build_dataset, build_loader  # noqa: F401
 from .device_metrics import no_ref_evaluate_batch, ref_evaluate_batch  # noqa: F401
 from .resident import ResidentLoader, ResidentStore  # noqa: F401
 from .scene import fuse_scene, tile_grid  # noqa: F401
+from .wald import SceneLoader, SceneStore, degrade_scene, export_triplets, mtf_taps, window_origins  # noqa: F401

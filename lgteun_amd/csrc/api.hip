@@ -693,7 +693,7 @@ extern "C" int lg_l2_loss(const float* out, const float* gt, float* dout, float*
 }
 
 // ------------------------------------------------------------------------------------------------
-// device-resident dataset (k_batch.hip)
+// device-resident dataset (k_batch.hip), Wald degradation (k_wald.hip)
 // ------------------------------------------------------------------------------------------------
 extern "C" int lg_pyr_down2(const void* pan, float* pan_l, int64_t planes, int32_t H, int32_t W, int32_t dtype, void* stream) {
     return launch_pyr_down2(pan, pan_l, planes, H, W, dtype, (hipStream_t)stream);
@@ -703,6 +703,16 @@ extern "C" int lg_batch_assemble(const void* pan, const void* lr, const void* mu
                                  int32_t h, int32_t w, int32_t dtype, float divisor, int32_t n_div, float post_scale, void* stream) {
     return launch_batch_assemble(pan, lr, mul, pan_l, N, idx, idx_offset, flips, o_pan, o_lr, o_mul, o_pan_l, B, C, H, W, h, w, dtype, divisor, n_div,
                                  post_scale, (hipStream_t)stream);
+}
+extern "C" int lg_fir_decimate4(const void* in, void* out, const double* taps, int64_t planes, int32_t H, int32_t W, int32_t n_taps, int32_t phase,
+                                int32_t dtype, int32_t out_f32, void* stream) {
+    return launch_fir_decimate4(in, out, taps, planes, H, W, n_taps, phase, dtype, out_f32, (hipStream_t)stream);
+}
+extern "C" int lg_window_assemble(const void* pan, const void* lr, const void* mul, const int32_t* origins, int64_t n_windows, int64_t first,
+                                  const uint32_t* flips, float* o_pan, float* o_lr, float* o_mul, float* o_pan_l, int32_t B, int32_t C, int32_t Hs,
+                                  int32_t Ws, int32_t P, int32_t Q, int32_t dtype, float divisor, int32_t n_div, float post_scale, void* stream) {
+    return launch_window_assemble(pan, lr, mul, origins, n_windows, first, flips, o_pan, o_lr, o_mul, o_pan_l, B, C, Hs, Ws, P, Q, dtype, divisor,
+                                  n_div, post_scale, (hipStream_t)stream);
 }
 extern "C" int lg_scene_gather(const void* pan, const void* ms, const int32_t* origins, int64_t n_tiles, int64_t first, float* o_pan, float* o_ms,
                                int32_t B, int32_t C, int32_t H, int32_t W, int32_t th, int32_t tw, int32_t dtype, float divisor, int32_t n_div,

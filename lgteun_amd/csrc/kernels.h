@@ -7,6 +7,12 @@ int launch_pyr_down2(const void* pan, float* pan_l, int64_t planes, int H, int W
 int launch_batch_assemble(const void* pan, const void* lr, const void* mul, const float* pan_l, int64_t N, const int32_t* idx, int64_t idx_offset,
                           const uint32_t* flips, float* o_pan, float* o_lr, float* o_mul, float* o_pan_l, int B, int C, int H, int W, int h, int w,
                           int dtype, float divisor, int n_div, float post_scale, hipStream_t s);
+int launch_window_assemble(const void* pan, const void* lr, const void* mul, const int32_t* origins, int64_t n_windows, int64_t first,
+                           const uint32_t* flips, float* o_pan, float* o_lr, float* o_mul, float* o_pan_l, int B, int C, int Hs, int Ws, int P, int Q,
+                           int dtype, float divisor, int n_div, float post_scale, hipStream_t s);
+// ---------------- Wald degradation of a raw scene (k_wald.hip; arguments validated before any HIP call) ----------------
+int launch_fir_decimate4(const void* in, void* out, const double* taps, int64_t planes, int H, int W, int n_taps, int phase, int dtype, int out_f32,
+                         hipStream_t s);
 // ---------------- tiled scene fusion (k_scene.hip; arguments validated before any HIP call) ----------------
 int launch_scene_gather(const void* pan, const void* ms, const int32_t* origins, int64_t n_tiles, int64_t first, float* o_pan, float* o_ms,
                         int B, int C, int H, int W, int th, int tw, int dtype, float divisor, int n_div, float post_scale, hipStream_t s);

@@ -14,6 +14,7 @@ and what the reference does not have but one process per GPU at thousands of pai
   PrefetchLoader                pinned-memory batches staged to the device on a side stream `depth` batches ahead, instead of the
                                 synchronous `set_batch_cuda` (dataset/utils.py:98-110); a pair is only 336 KB fp32
   build_loader                  main.py:71-86 (DataLoader from a *_set_cfg dict) + the two above
+  SceneDataset                  the configuration of a set cut out of one raw scene on the GPU (wald.py)
 """
 import os
 import struct
@@ -264,6 +265,24 @@ class PSDataset(data.Dataset):
         return len(self.image_ids)
 
 
+@DATASETS.register_module()
+class SceneDataset:
+    """The configuration of a data set cut out of ONE raw scene on the GPU (lgteun_amd/wald.py): the paths of the MS and the PAN TIFF,
+    `bit_depth`, the window `patch`, and either `step` (the fixed grid) or `windows_per_epoch` (fresh random windows every epoch);
+    `region` = (y0, x0, y1, x1) keeps the windows to a part of the scene (PAN pixels of the grid the windows are cut on: the raw MS grid
+    with degrade=True).  gains_ms / gain_pan: the sensor's MTF gains at Nyquist (None: wald.DEFAULT_GAIN_MS / DEFAULT_GAIN_PAN, which are
+    no sensor's measured values).  degrade=False: the raw pair, no target.  It holds no samples: build_loader(device=...) reads the files and
+    returns a wald.SceneLoader."""
+
+    def __init__(self, ms_path, pan_path, bit_depth, patch, step=None, windows_per_epoch=None, region=None, gains_ms=None, gain_pan=None,
+                 phase=2, n_taps=41, degrade=True, norm_input=False):
+        if (step is None) == (windows_per_epoch is None):
+            raise ValueError('SceneDataset needs exactly one of step (a fixed grid of windows) and windows_per_epoch (random windows)')
+        self.ms_path, self.pan_path, self.bit_depth, self.patch, self.step = ms_path, pan_path, bit_depth, patch, step
+        self.windows_per_epoch, self.region, self.gains_ms, self.gain_pan = windows_per_epoch, region, gains_ms, gain_pan
+        self.phase, self.n_taps, self.degrade, self.norm_input = phase, n_taps, bool(degrade), bool(norm_input)
+
+
 def data_augmentation(img_dict, aug_dict=None, rng=None):
     """reference dataset/utils.py:155-229 on [N, C, H, W] tensors.  `aug_dict` maps 'ud_flip' / 'lr_flip' / 'r4_crop' /
     'r2_crop' to a probability and is overwritten with the drawn booleans, as there.  Every selected transform is applied to the
@@ -398,12 +417,21 @@ def build_loader(set_cfg, rank=0, world=1, device=None, seed=0, prefetch_depth=2
     in a PrefetchLoader.  evaluation=True: the sampler does not pad (each image on exactly one rank).  Returns (loader, sampler-or-None).
     resident=True (or `resident=True` inside set_cfg): the set is decoded once and kept on `device`, and the loader is a
     resident.ResidentLoader -- returns (loader, None); num_workers / pin_memory do not apply, `fold_normalize` and `aug_dict` (arguments
-    or set_cfg keys) are the ResidentLoader's.  Without the flag nothing changes."""
+    or set_cfg keys) are the ResidentLoader's.  Without the flag nothing changes.
+    dataset=dict(type='SceneDataset', ...): the set is cut out of one raw scene on `device` (wald.py) -- returns (SceneLoader, None), with
+    the same arguments as the resident form."""
     cfg = dict(set_cfg)
     resident = bool(cfg.pop('resident', False)) or bool(resident)
     fold_normalize = bool(cfg.pop('fold_normalize', fold_normalize))
     aug_dict = cfg.pop('aug_dict', aug_dict)
     cfg['dataset'] = build_dataset(cfg['dataset'])
+    if isinstance(cfg['dataset'], SceneDataset):
+        from .wald import loader_from_config
+        if device is None:
+            raise ValueError('a SceneDataset needs the device the scene is to live on: build_loader(..., device=)')
+        return loader_from_config(cfg['dataset'], cfg.get('batch_size', 1), device, shuffle=bool(cfg.get('shuffle', False)), rank=rank, world=world,
+                                  seed=seed, drop_last=bool(cfg.get('drop_last', False)), evaluation=evaluation, aug_dict=aug_dict,
+                                  fold_normalize=fold_normalize), None
     if resident:
         from .resident import ResidentLoader, ResidentStore
         if device is None:
