@@ -34,6 +34,22 @@ def device_drop_masks(seed, dtype=torch.float64):
     return masks
 
 
+GUARD = 1024        # floats of NaN band on each side of a guarded output (4 KiB: the output keeps its 16-byte alignment)
+
+
+def guarded_empty(shape, device):
+    """(buffer, out): `out` is a view of `shape` into a larger buffer filled with NaN -- `out` itself and GUARD floats on each side"""
+    n = int(np.prod(shape))
+    buf = torch.full((n + 2 * GUARD,), float('nan'), device=device)
+    return buf, buf[GUARD:GUARD + n].view(shape)
+
+
+def assert_guards_intact(buf, what):
+    """both bands of a guarded_empty buffer are still all-NaN: nothing next to the output was written"""
+    lo, hi = torch.isnan(buf[:GUARD]), torch.isnan(buf[-GUARD:])
+    assert bool(lo.all()) and bool(hi.all()), (what, 'written outside the output', int((~lo).sum()), int((~hi).sum()))
+
+
 class Ops:
     def __init__(self, net, H, W):
         self.net = net
@@ -45,40 +61,56 @@ class Ops:
     def ws(self, B, train=False):
         return self.eng.workspace(self.plan, B, train)
 
-    def resample(self, x, mode):
+    @staticmethod
+    def _out(shape, device, guard):
+        """guard=True: the output is a view into a NaN-filled buffer (itself included) with GUARD floats of band on each side; the caller
+        hands the buffer to assert_guards_intact behind the launch"""
+        if guard:
+            return guarded_empty(tuple(shape), device)
+        return None, torch.empty(tuple(shape), device=device)
+
+    def resample(self, x, mode, guard=False):
         planes = x.shape[0] * x.shape[1]
         hi, wi = x.shape[2], x.shape[3]
         f = {0: 0.5, 1: 2, 2: 4}[mode]
-        y = torch.empty(x.shape[0], x.shape[1], int(hi * f), int(wi * f), device=x.device)
+        buf, y = self._out((x.shape[0], x.shape[1], int(hi * f), int(wi * f)), x.device, guard)
         _lib.check(self.lib.lg_op_resample(_ptr(x), _ptr(y), planes, hi, wi, mode, _stream_ptr()), 'lg_op_resample')
+        if guard:
+            assert_guards_intact(buf, 'lg_op_resample')
         return y
 
-    def data_step(self, stage, z, ms, pan):
+    def data_step(self, stage, z, ms, pan, guard=False):
         B = z.shape[0]
-        out = torch.empty_like(z)
+        buf, out = self._out(z.shape, z.device, guard)
         tmp = torch.empty(3 * z.numel() // 4 + z.numel() // z.shape[1], device=z.device)   # include/lgteun_hip.h: lg_op_data_step
         _lib.check(self.lib.lg_op_data_step(self.plan, _ptr(self.eng.flat), stage, _ptr(z), _ptr(ms), _ptr(pan), _ptr(out),
                                             _ptr(tmp), B, _stream_ptr()), 'lg_op_data_step')
+        if guard:
+            assert_guards_intact(buf, 'lg_op_data_step')
         return out
 
     def dropout_masks(self, seed, dtype=torch.float64):
         return device_drop_masks(seed, dtype)
 
-    def lgt(self, stage, z, flags=0, seed=0):
+    def lgt(self, stage, z, flags=0, seed=0, guard=False):
         B = z.shape[0]
-        out = torch.empty_like(z)
-        ws = self.ws(B)
+        buf, out = self._out(z.shape, z.device, guard)
+        ws = self.ws(B, train=bool(flags & _lib.LG_FLAG_SAVE))                 # LG_FLAG_SAVE writes the training workspace's save slots
         _lib.check(self.lib.lg_op_lgt(self.plan, _ptr(self.eng.flat), stage, _ptr(z), _ptr(out), _ptr(ws), ws.numel(), B, flags, seed,
                                       _stream_ptr()), 'lg_op_lgt')
+        if guard:
+            assert_guards_intact(buf, 'lg_op_lgt')
         return out
 
-    def block(self, stage, blk, which, x):
+    def block(self, stage, blk, which, x, guard=False):
         """x NHWC [B,h,w,e]; which 0: global mixer (planar out), 1: mixer half-block, 2: ffn half-block"""
         B, h, w, e = x.shape
-        y = torch.empty(B, e // 2, h, w, device=x.device) if which == 0 else torch.empty_like(x)
+        buf, y = self._out((B, e // 2, h, w) if which == 0 else x.shape, x.device, guard)
         ws = self.ws(B)
         _lib.check(self.lib.lg_op_block(self.plan, _ptr(self.eng.flat), stage, blk, which, _ptr(x), _ptr(y), _ptr(ws),
                                         ws.numel(), B, _stream_ptr()), 'lg_op_block')
+        if guard:
+            assert_guards_intact(buf, 'lg_op_block')
         return y
 
     def block_bwd(self, stage, blk, which, x, dy):
