@@ -184,6 +184,34 @@ int lg_optim_step(float* params, const float* grads, float* state0, float* state
                   int32_t n_ranges, int64_t max_range, int32_t step, int32_t algo, int32_t flags, double lr, double h0, double h1,
                   double eps, double weight_decay, double grad_scale, void* stream);
 
+/* L2 norm of `grads` over [begin,end) float ranges (DEVICE int64 pairs, as for lg_optim_step) and the clip coefficient of
+ * torch.nn.utils.clip_grad_norm_(error_if_nonfinite=False), both left in device memory:
+ *   out[0] = (float)sqrt(sum of squares), squares and sum carried in fp64;
+ *   out[1] = min(1, (float)max_norm / (out[0] + 1e-6f)) in fp32, with torch.clamp's handling of a NaN (it stays a NaN).
+ * Non-finite gradients propagate as torch's do: an infinite norm gives the coefficient 0, a NaN gives NaN.  Two launches: one fp64 partial
+ * per workgroup into `workspace`, then a fixed-order finishing pass -- no floating-point atomics, so the same call gives the same bits.
+ * Nothing outside the ranges is read; a range may begin and end at any float offset and be of any length.  workspace: 8-byte aligned,
+ * lg_grad_norm_workspace_bytes(n_ranges, max_range) bytes (0 for arguments lg_grad_norm rejects); its content need not survive the call. */
+size_t lg_grad_norm_workspace_bytes(int32_t n_ranges, int64_t max_range);
+int lg_grad_norm(const float* grads, const int64_t* ranges, int32_t n_ranges, int64_t max_range, double max_norm, float* out,
+                 void* workspace, size_t workspace_bytes, void* stream);
+
+/* lg_optim_step with the controls of a train step, still ONE launch.  With clip_coef == NULL, ema == NULL and plain_adam == 0 it is
+ * lg_optim_step, bit for bit.
+ *   clip_coef   DEVICE pointer or NULL (out + 1 of lg_grad_norm): gradients are read as fl(fl(grads * grad_scale) * *clip_coef), the
+ *               rounding `g.mul_(clip_coef)` in front of torch's optimizer gives.  No host synchronisation: the kernel loads it.
+ *   ema         NULL, or an fp32 buffer laid out like params: behind the parameter update, every element of the ranges takes
+ *               ema = fma(1 - ema_decay, p_new - ema, ema) with 1 - ema_decay taken in fp64 and rounded once -- torch._foreach_lerp_(ema,
+ *               params, 1 - ema_decay), which has this form for a weight below 0.5: ema_decay must lie in (0.5, 1).  Elements outside the
+ *               ranges are neither read nor written.
+ *   plain_adam  1: the arithmetic of lg_adam_step (algo LG_OPT_ADAM, weight_decay 0, no flag; state0 = exp_avg, state1 = exp_avg_sq;
+ *               lr, h0, h1, eps and grad_scale rounded to fp32 first, as that entry point takes them) extended the same way, so that
+ *               switching a control on does not move a plain-Adam run onto lg_optim_step's bits.  0: lg_optim_step's. */
+int lg_optim_step_ex(float* params, const float* grads, float* state0, float* state1, float* state2, const int64_t* ranges,
+                     int32_t n_ranges, int64_t max_range, int32_t step, int32_t algo, int32_t flags, double lr, double h0, double h1,
+                     double eps, double weight_decay, double grad_scale, const float* clip_coef, float* ema, double ema_decay,
+                     int32_t plain_adam, void* stream);
+
 /* Live per-kernel timing: when enabled for `kernel_id`, every launch of that kernel is bracketed by hipEvents recorded on
  * the stream it is launched on.  lg_prof_read synchronises on the recorded events and returns the summed device time (ms)
  * and the number of launches since lg_prof_enable / lg_prof_reset.  Host-side event objects are the only thing the library

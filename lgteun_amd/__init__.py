@@ -3,7 +3,7 @@ reference's MODELS-registry / nn.Module surface.  Compute = hand-written HIP ker
 (include/lgteun_hip.h); this package is the host-side mirror of the reference interface."""
 from .builder import MODELS, build_model  # noqa: F401
 from .unlg_former import Pansharpening, UnlgFormer  # noqa: F401
-from .engine import Engine, FusedAdam, FusedAdamW, FusedRMSprop, FusedSGD, canonical_names  # noqa: F401
+from .engine import Engine, FusedAdam, FusedAdamW, FusedRMSprop, FusedSGD, TrainControls, canonical_names  # noqa: F401
 from .dataset import DATASETS, PSDataset, PrefetchLoader, SceneDataset, ShardedSampler, build_dataset, build_loader  # noqa: F401
 from .device_metrics import no_ref_evaluate_batch, ref_evaluate_batch  # noqa: F401
 from .resident import ResidentLoader, ResidentStore  # noqa: F401

@@ -110,6 +110,11 @@ SIGNATURES = {
     'lg_l2_loss': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_float, c_void_p]),
     'lg_optim_step': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32,
                                 c_double, c_double, c_double, c_double, c_double, c_double, c_void_p]),
+    'lg_grad_norm_workspace_bytes': (c_size_t, [c_int32, c_int64]),
+    'lg_grad_norm': (c_int32, [c_void_p, c_void_p, c_int32, c_int64, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'lg_optim_step_ex': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32,
+                                   c_double, c_double, c_double, c_double, c_double, c_double, c_void_p, c_void_p, c_double, c_int32,
+                                   c_void_p]),
     'lg_op_resample': (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     'lg_op_data_step': (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                   c_void_p]),

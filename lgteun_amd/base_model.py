@@ -3,6 +3,7 @@ add_module :56, set_cuda :91 (one process per GPU + RCCL instead of nn.DataParal
 set_optim :116 (Adam / AdamW / SGD / RMSprop -> their fused HIP steps), set_sched :137 (StepLR stepped EVERY iteration :197-199),
 train :164, test :267 (reference-based indices PSNR / SSIM / Q / SAM / ERGAS on the reduced-resolution set, the no-reference
 D_lambda / D_s / QNR on the full-resolution set), save :354 (same `train_out/` location; optimizer state added)."""
+import contextlib
 import os.path as osp
 
 import numpy as np
@@ -128,9 +129,22 @@ class Base_model:
     def load_pretrained(self, path, allow_pickle=None):
         self._load_modules(self._read_checkpoint(path, allow_pickle))
 
+    def _train_controls(self):
+        """cfg.train_cfg = dict(accumulate=, max_grad_norm=, ema_decay=, eval_ema=) as a TrainControls; None when the key is absent"""
+        from .engine import TrainControls
+        train_cfg = self.cfg.get('train_cfg', None)
+        if train_cfg is None:
+            return None
+        known = ('accumulate', 'max_grad_norm', 'ema_decay', 'eval_ema')
+        unknown = sorted(set(train_cfg) - set(known))
+        if unknown:
+            raise ValueError(f'cfg.train_cfg has unknown key(s) {unknown}: it takes {list(known)}')
+        return TrainControls(**dict(train_cfg))
+
     def set_optim(self):
         from .engine import FUSED_OPTIMIZERS
         optim_cfg = self.cfg.get('optim_cfg', {})
+        controls = self._train_controls()
         for module_name, module in self.module_dict.items():
             if module_name in optim_cfg:
                 cfg = dict(optim_cfg[module_name])
@@ -143,6 +157,15 @@ class Base_model:
                 self.optim_dict[module_name] = (FUSED_OPTIMIZERS[typ] if fused else torch_cls[typ])(module.parameters(), **cfg)
             else:
                 self.optim_dict[module_name] = Adam(module.parameters(), betas=(0.9, 0.999), lr=1e-4)
+            if controls is not None:                      # before the state is restored: a checkpoint may sit inside an accumulation window
+                optim = self.optim_dict[module_name]
+                if getattr(optim, 'is_fused_lgteun', False):
+                    optim.set_controls(controls)
+                elif controls.ema_decay is not None:
+                    raise ValueError("cfg.train_cfg: ema_decay needs the fused optimizer (the average is updated inside its launch); take "
+                                     f"fused=False out of optim_cfg['{module_name}'] or ema_decay out of train_cfg")
+                else:                                     # torch's own optimizer: train_iter accumulates and clips with torch's functions
+                    optim.lgteun_controls, optim.lgteun_window_pos = controls, 0
             resume = getattr(self, '_resume_optim', None) or {}
             if module_name in resume:                     # load_checkpoint ran first (main.py order): continue the optimizer state
                 self.optim_dict[module_name].load_state_dict(resume[module_name])
@@ -206,8 +229,26 @@ class Base_model:
     def train_iter(self, iter_id, input_batch, log_freq=10):
         raise NotImplementedError
 
+    @contextlib.contextmanager
+    def _eval_weights(self):
+        """cfg.train_cfg with ema_decay and eval_ema: the averaged weights sit in every fused module for the length of the block"""
+        with contextlib.ExitStack() as stack:
+            for name, module in self.module_dict.items():
+                ctl = getattr(self.optim_dict.get(name), 'controls', None)
+                core = module.module if hasattr(module, 'module') else module
+                if ctl is not None and ctl.ema_decay is not None and ctl.eval_ema and hasattr(core, 'engine'):
+                    stack.enter_context(core.engine().ema_weights(self.optim_dict[name]))
+            yield
+
     @torch.no_grad()
     def test(self, iter_id, save=False, ref=True):
+        """`_test` below, with the weights `cfg.train_cfg` asks for: the exponential moving average when it has ema_decay and eval_ema
+        (the raw weights are back when the call returns or raises), the raw weights otherwise"""
+        with self._eval_weights():
+            return self._test(iter_id, save=save, ref=ref)
+
+    @torch.no_grad()
+    def _test(self, iter_id, save=False, ref=True):
         """evaluation (base_model.py:267-352).  ref=True: reduced-resolution set, PSNR / SSIM / Q / SAM / ERGAS against the target,
         `<metric>_mean` / `<metric>_std` lists in self.eval_results like the reference.  ref=False: the full-resolution set, no target:
         D_lambda / D_s / QNR from the fused image, the PAN and the MS input (lgteun_amd/metrics.py: parity-unpinned).  Inputs are always normalised; arrays are brought back
@@ -314,7 +355,8 @@ class Base_model:
     def save(self, iter_id):
         """`train_out/model_iter_N.pth` like the reference (base_model.py:354-369), written by rank 0 only, holding plain tensors:
         {module name: state_dict, 'iter_num', 'optim': optimizer state (absent in the reference)} -- loadable with
-        `weights_only=True`.  `cfg.pickle_modules = True` writes the reference's own format instead (whole pickled module
+        `weights_only=True`.  With cfg.train_cfg the modules' entries are still the RAW weights, so that a resumed run continues the same
+        trajectory; the averaged weights (ema_decay) and the position inside an accumulation window travel in 'optim'.  `cfg.pickle_modules = True` writes the reference's own format instead (whole pickled module
         objects), for tools that expect it; such a file needs `allow_pickle` to be read back."""
         path = osp.join(self.train_out, f'model_iter_{iter_id}.pth')
         if self.rank == 0:

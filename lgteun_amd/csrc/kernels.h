@@ -24,6 +24,10 @@ int launch_iqa_ref(const float* pred, const float* gt, double* out, int B, int C
                    size_t workspace_bytes, hipStream_t s);
 int launch_iqa_no_ref(const float* pred, const float* pan, const float* ms, double* out, int B, int C, int H, int W, float scale,
                       void* workspace, size_t workspace_bytes, hipStream_t s);
+// ---------------- gradient norm + clip coefficient of a train step (k_gradnorm.hip; arguments validated before any HIP call) ----------------
+size_t grad_norm_workspace_bytes(int n_ranges, int64_t max_range);
+int launch_grad_norm(const float* grads, const int64_t* ranges, int n_ranges, int64_t max_range, double max_norm, float* out, void* workspace,
+                     size_t workspace_bytes, hipStream_t s);
 
 // ---------------- data module (reference models/unlg_former.py:29-37,58-61) ----------------
 struct DwArgs {

@@ -9,7 +9,9 @@ Layout decisions (MI355X-first):
     are ever written -- dead-stage parameters keep `grad is None` exactly like the reference.
   * one workspace tensor per (B, train) holds every activation; the library allocates nothing.
 """
+import contextlib
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -78,6 +80,44 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+class TrainControls:
+    """What a training run asks for around the optimizer of the fused step; attached with `optimizer.set_controls(...)`, or by the runner
+    from `cfg.train_cfg`.  Everything is off by default, and an optimizer without controls steps exactly as it always did.
+      accumulate     A >= 1: a step is a WINDOW of A train_step calls.  Each call adds its gradients, at loss scale loss_weight / A; only
+                     the last one reduces across ranks, clips and steps the optimizer.  A scheduler keeps ticking per call, and the
+                     learning rate a window applies is the one at its LAST call.
+      max_grad_norm  clip the global L2 norm of the gradients to this value (torch.nn.utils.clip_grad_norm_): the norm and the coefficient
+                     are taken on the device, behind the all-reduce, and the optimizer launch reads the coefficient there
+      ema_decay      keep an exponential moving average of the weights, updated inside the optimizer launch: optimizer state 'ema'
+      eval_ema       the runner evaluates (Base_model.test) with the averaged weights"""
+
+    def __init__(self, accumulate=1, max_grad_norm=None, ema_decay=None, eval_ema=True):
+        if isinstance(accumulate, bool) or not isinstance(accumulate, (int, np.integer)) or accumulate < 1:
+            raise ValueError(f'accumulate must be an integer >= 1 (got {accumulate!r}): the number of train_step calls per optimizer step')
+        if max_grad_norm is not None:
+            if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float, np.integer, np.floating)) \
+                    or not math.isfinite(max_grad_norm) or max_grad_norm <= 0:
+                raise ValueError(f'max_grad_norm must be None (no clipping) or a finite number > 0 (got {max_grad_norm!r})')
+        if ema_decay is not None:
+            if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float, np.integer, np.floating)) or not 0.5 < ema_decay < 1:
+                raise ValueError(f'ema_decay must be None (no average) or lie in 0.5 < decay < 1 (got {ema_decay!r}): the average moves by '
+                                 '1 - decay per step, e.g. 0.999')
+        self.accumulate = int(accumulate)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.eval_ema = bool(eval_ema)
+
+    def is_window_end(self, call):
+        """call: 0-based count of train_step calls; True where that call ends a window, i.e. steps the optimizer"""
+        return (call + 1) % self.accumulate == 0
+
+    def as_dict(self):
+        return dict(accumulate=self.accumulate, max_grad_norm=self.max_grad_norm, ema_decay=self.ema_decay, eval_ema=self.eval_ema)
+
+    def __repr__(self):
+        return 'TrainControls(' + ', '.join(f'{k}={v!r}' for k, v in self.as_dict().items()) + ')'
+
+
 class Engine:
     def __init__(self, module):
         self.lib = _lib.lib()          # raises if the HIP library is not built -- no fallback
@@ -134,6 +174,10 @@ class Engine:
         self.buckets = None
         self.force_collectives = False   # attach_ddp(force=True): collectives also in a group of one rank
         self.local_only = False        # True: the caller runs independent replicas inside an initialised process group on purpose
+        self._clip = None              # TrainControls.max_grad_norm: [norm, clip coefficient] of the last optimizer step, on the device
+        self._norm_ws = None
+        self._window_seen = 1          # train_step calls of the current accumulation window so far (global_loss divides by it)
+        self._optim = None             # the fused optimizer of the last train_step: whose 'ema' state ema_weights() swaps in
 
     def chained(self):
         return self.module_mode() == 'chained'
@@ -175,8 +219,11 @@ class Engine:
 
     def global_loss(self):
         """the GLOBAL-mean loss of the last train_step as a Python float (host sync; under DDP one scalar all-reduce: `_loss`
-        holds this rank's share of the global mean).  For the logging cadence only."""
+        holds this rank's share of the global mean).  For the logging cadence only.  Inside an accumulation window
+        (TrainControls.accumulate) `_loss` is the sum over the window's calls so far: the mean over those micro-batches is returned."""
         t = self._loss.clone()
+        if self._window_seen > 1:
+            t /= self._window_seen
         if self.world > 1:
             import torch.distributed as dist
             dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.process_group)
@@ -314,15 +361,27 @@ class Engine:
     # ------------------------------------------------------------------------------------------
     def train_step(self, ms, pan, gt, optim, loss_weight=1.0, loss_type='l1'):
         """forward + L1 / L2 (mean) + backward + the fused optimizer's step as library calls; returns the device loss scalar (this
-        rank's share)."""
+        rank's share).  With `optim.controls` (TrainControls) a call is one micro-batch of a window of `accumulate` calls: the first
+        clears gradients and loss, every call adds its gradients at loss scale loss_weight / accumulate and its loss to the scalar, and
+        only the last issues the all-reduce, the norm (max_grad_norm) and the optimizer launch.  The learning rate applied is the one
+        `optim.param_groups[0]['lr']` holds at that last call."""
         if loss_type not in ('l1', 'l2'):
             raise ValueError(f"loss_type must be 'l1' or 'l2' (got {loss_type!r})")
         self._check_attached()
+        ctl = getattr(optim, 'controls', None)
+        acc = ctl.accumulate if ctl is not None else 1
+        pos = optim._window_pos if acc > 1 else 0
+        last = pos + 1 >= acc
         flags = self.base_flags(True) | LG_FLAG_SAVE
         if not getattr(optim, 'dropout', True):
             flags &= ~LG_FLAG_DROPOUT
         seed = self.next_seed()
-        self._gbuf.zero_()                 # gradients and the loss scalar
+        if pos == 0:
+            self._gbuf.zero_()             # gradients and the loss scalar
+        elif optim._window_gbuf is not None and optim._window_gbuf is not self._gbuf:
+            self._gbuf.copy_(optim._window_gbuf)     # a window cut by a checkpoint: what its earlier calls had accumulated
+        if acc > 1:
+            optim._window_gbuf = None
         defer = bool(self.overlap_dead and (flags & LG_FLAG_FAITHFUL) and not (flags & LG_FLAG_CHAINED) and self.K > 1)
         if defer:
             flags |= LG_FLAG_DEFER_DEAD
@@ -331,9 +390,10 @@ class Engine:
         dout = torch.empty_like(out)
         n_local = out.numel()
         loss_fn = self.lib.lg_l1_loss if loss_type == 'l1' else self.lib.lg_l2_loss
-        check(loss_fn(_ptr(out), _ptr(gt), _ptr(dout), _ptr(self._loss), n_local, n_local * self.world, float(loss_weight),
+        scale = float(loss_weight) if acc == 1 else float(loss_weight) / acc
+        check(loss_fn(_ptr(out), _ptr(gt), _ptr(dout), _ptr(self._loss), n_local, n_local * self.world, scale,
                       _stream_ptr()), f'lg_{loss_type}_loss')
-        bk = self.buckets[bool(flags & LG_FLAG_CHAINED)] if (self.world > 1 or self.force_collectives) else None
+        bk = self.buckets[bool(flags & LG_FLAG_CHAINED)] if (last and (self.world > 1 or self.force_collectives)) else None
         overlap = bool(bk is not None and bk.overlap and not (flags & LG_FLAG_CHAINED))
         if defer or overlap:
             # two backward calls: the dead-stage forwards (side stream) and / or the opt-in asynchronous bucket of the last stage's
@@ -353,10 +413,68 @@ class Engine:
             self.backward_raw(saved, dout, self.gflat, flags, seed)
         if bk is not None and not overlap:
             bk.all_reduce(self.gflat)      # default: ONE stream-ordered collective behind the whole backward (ddp.py)
-        optim.step_flat(self)
+        self._window_seen = pos + 1
+        self._optim = optim
+        if last:
+            if ctl is not None and ctl.max_grad_norm is not None:
+                self.grad_norm(ctl.max_grad_norm)      # behind the all-reduce: the global gradient, the same coefficient on every rank
+            optim.step_flat(self)
+            if acc > 1:
+                optim._window_pos = 0
+        else:
+            optim._window_pos = pos + 1
+            optim._window_gbuf = self._gbuf            # a checkpoint written inside the window carries the gradients so far
         if defer:
             torch.cuda.current_stream().wait_stream(self._side_stream)   # the step ends when its dead-stage work has ended
         return self._loss
+
+    def grad_norm(self, max_norm):
+        """lg_grad_norm over the live ranges of the gradient buffer into the engine's [norm, clip coefficient] pair on the device (no host
+        sync); returns that pair"""
+        if self._clip is None:
+            self._clip = torch.zeros(2, dtype=torch.float32, device=self.device)
+        n = len(self.live_ranges)
+        need = int(self.lib.lg_grad_norm_workspace_bytes(n, self.max_range))
+        if self._norm_ws is None or self._norm_ws.numel() * 8 < need:
+            self._norm_ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
+        check(self.lib.lg_grad_norm(_ptr(self.gflat), _ptr(self.ranges_dev), n, self.max_range, float(max_norm), _ptr(self._clip),
+                                    _ptr(self._norm_ws), self._norm_ws.numel() * 8, _stream_ptr()), 'lg_grad_norm')
+        return self._clip
+
+    def last_grad_norm(self):
+        """the global gradient norm the last clipped optimizer step saw, before clipping, as a Python float (host sync: for logging only)"""
+        if self._clip is None:
+            raise RuntimeError('no gradient norm yet: it is taken by train_step when the optimizer has controls with max_grad_norm '
+                               '(optimizer.set_controls(TrainControls(max_grad_norm=...)) or cfg.train_cfg)')
+        return float(self._clip[0].item())
+
+    def _ema_of(self, optim):
+        optim = self._optim if optim is None else optim
+        ctl = getattr(optim, 'controls', None)
+        if ctl is None or ctl.ema_decay is None:
+            raise RuntimeError('no averaged weights: the optimizer has no controls with ema_decay (optimizer.set_controls(TrainControls('
+                               'ema_decay=...)) or cfg.train_cfg); pass the optimizer if it has not stepped this engine yet')
+        ema = (optim._state or {}).get('ema')
+        if ema is None:
+            return None                    # no optimizer step yet: the average IS the weights
+        if ema.numel() != self.total:
+            raise RuntimeError(f"the optimizer's 'ema' state holds {ema.numel()} floats, this engine {self.total}")
+        return ema
+
+    @contextlib.contextmanager
+    def ema_weights(self, optim=None):
+        """inside the block the flat parameter storage (and so every nn.Parameter, state_dict() and forward) holds the averaged weights of
+        `optim` (default: the optimizer of the last train_step); the raw weights are put back on exit, also after an exception"""
+        ema = self._ema_of(optim)
+        if ema is None:
+            yield self
+            return
+        raw = self.flat.clone()
+        self.flat.copy_(ema)               # a restored (host) state is copied up here
+        try:
+            yield self
+        finally:
+            self.flat.copy_(raw)
 
     def _dead_forward(self, saved, flags, seed):
         """the dead-stage LGT forwards of a LG_FLAG_DEFER_DEAD forward, on the side stream: ordered behind everything enqueued so far
@@ -382,6 +500,17 @@ class Engine:
         check(self.lib.lg_optim_step(_ptr(self.flat), _ptr(self.gflat), s0, s1, s2, _ptr(self.ranges_dev), len(self.live_ranges),
                                      self.max_range, step, int(algo), int(flags), float(lr), float(h0), float(h1), float(eps),
                                      float(weight_decay), float(grad_scale), _stream_ptr()), 'lg_optim_step')
+
+    def optim_step_ex(self, states, step, algo, flags, lr, h0, h1, eps, weight_decay, clip=False, ema=None, ema_decay=0.0, plain_adam=False,
+                      grad_scale=1.0):
+        """lg_optim_step_ex over the live ranges.  clip: read the coefficient the last grad_norm() left on the device; ema: the average to
+        update in the same launch; plain_adam: lg_adam_step's arithmetic"""
+        s0, s1, s2 = (None if t is None else _ptr(t) for t in states)
+        check(self.lib.lg_optim_step_ex(_ptr(self.flat), _ptr(self.gflat), s0, s1, s2, _ptr(self.ranges_dev), len(self.live_ranges),
+                                        self.max_range, step, int(algo), int(flags), float(lr), float(h0), float(h1), float(eps),
+                                        float(weight_decay), float(grad_scale),
+                                        ctypes.c_void_p(self._clip.data_ptr() + 4) if clip else None, None if ema is None else _ptr(ema),
+                                        float(ema_decay), int(plain_adam), _stream_ptr()), 'lg_optim_step_ex')
 
 
 class _WsLease:
@@ -444,6 +573,25 @@ class _FusedOptimizer(torch.optim.Optimizer):
         self._step = 0
         self._state = None
         self.dropout = True
+        self.controls = None           # TrainControls (set_controls); None: the step every earlier build took
+        self._window_pos = 0           # train_step calls of the current accumulation window already made
+        self._window_gbuf = None       # ... and the engine's gradient + loss buffer they filled (what a checkpoint inside a window saves)
+
+    def set_controls(self, controls):
+        """attach a TrainControls (or None: none).  Not a constructor option: the constructors take torch's keywords only."""
+        if controls is not None and not isinstance(controls, TrainControls):
+            raise ValueError(f'set_controls takes a TrainControls or None (got {type(controls).__name__}); build one with '
+                             'TrainControls(**cfg.train_cfg)')
+        self.controls = controls
+        self._window_pos, self._window_gbuf = 0, None
+        return self
+
+    def _ema_on(self):
+        return self.controls is not None and self.controls.ema_decay is not None
+
+    def _ex_on(self):
+        """the step goes through lg_optim_step_ex: a control that the optimizer LAUNCH carries is on (accumulate alone is not one)"""
+        return self.controls is not None and (self.controls.max_grad_norm is not None or self.controls.ema_decay is not None)
 
     def state_names(self):
         """the state buffers of this option set, in the order of lg_optim_step's state0 / state1 / state2 slots (None: unused)"""
@@ -455,11 +603,21 @@ class _FusedOptimizer(torch.optim.Optimizer):
     def step_flat(self, engine):
         names = [n for n in self.state_names() if n is not None]
         st = self._state
+        ema = None
+        if st is not None and 'ema' in st:     # the average is kept beside the algorithm's buffers, not one of them
+            st = dict(st)
+            ema = st.pop('ema')
         if st is None or set(st) != set(names) or any(v.numel() != engine.total for v in st.values()):
             st = {n: torch.zeros_like(engine.flat) for n in names}
         elif any(v.device != engine.flat.device or not v.is_contiguous() for v in st.values()):
             # state restored from a checkpoint (loaded to the host): the kernel takes device pointers
             st = {k: v.to(engine.flat.device).contiguous() for k, v in st.items()}
+        if self._ema_on():
+            if ema is None or ema.numel() != engine.total:
+                ema = engine.flat.detach().clone()     # a full copy: dead-stage slots equal the weights, and stay so
+            elif ema.device != engine.flat.device or not ema.is_contiguous():
+                ema = ema.to(engine.flat.device).contiguous()
+            st['ema'] = ema
         self._state = st
         self._step += 1
         self._launch(engine, self.param_groups[0], st)
@@ -471,6 +629,9 @@ class _FusedOptimizer(torch.optim.Optimizer):
     def state_dict(self):
         sd = super().state_dict()
         sd['lgteun'] = dict(step=self._step, state=self._state)
+        if self.controls is not None:          # without controls: exactly the keys of every earlier checkpoint
+            sd['lgteun']['window'] = dict(pos=self._window_pos, accumulate=self.controls.accumulate,
+                                          gbuf=None if self._window_pos == 0 or self._window_gbuf is None else self._window_gbuf.detach().clone())
         return sd
 
     def load_state_dict(self, sd):
@@ -482,10 +643,23 @@ class _FusedOptimizer(torch.optim.Optimizer):
                 group.setdefault(k, v)
         if extra is not None:
             self._step, self._state = extra['step'], extra['state']
+            win = extra.get('window')          # absent: a checkpoint written without controls -- it ended on a window boundary
+            acc = self.controls.accumulate if self.controls is not None else 1
+            if win is not None and win['pos'] > 0 and (win['accumulate'] != acc or win['gbuf'] is None):
+                raise ValueError(f"the checkpoint was written {win['pos']} call(s) into an accumulation window of {win['accumulate']}; "
+                                 f'this optimizer accumulates {acc}: resume with train_cfg accumulate={win["accumulate"]}, or from a '
+                                 'checkpoint written at a window boundary')
+            self._window_pos = win['pos'] if win is not None else 0
+            self._window_gbuf = win['gbuf'] if self._window_pos else None
 
-    def _optim_step(self, engine, state, algo, flags, lr, h0, h1, eps, weight_decay):
-        engine.optim_step([state.get(n) if n is not None else None for n in self.state_names()], self._step, algo, flags, lr, h0, h1,
-                          eps, weight_decay)
+    def _optim_step(self, engine, state, algo, flags, lr, h0, h1, eps, weight_decay, plain_adam=False):
+        states = [state.get(n) if n is not None else None for n in self.state_names()]
+        if not self._ex_on():
+            engine.optim_step(states, self._step, algo, flags, lr, h0, h1, eps, weight_decay)
+            return
+        c = self.controls
+        engine.optim_step_ex(states, self._step, algo, flags, lr, h0, h1, eps, weight_decay, clip=c.max_grad_norm is not None,
+                             ema=state.get('ema'), ema_decay=c.ema_decay or 0.0, plain_adam=plain_adam)
 
 
 def _check_adam_args(lr, betas, eps, weight_decay):
@@ -518,7 +692,10 @@ class FusedAdam(_FusedOptimizer):
 
     def _launch(self, engine, g, state):
         if self.ALGO == _lib.LG_OPT_ADAM and not g['weight_decay'] and not g['amsgrad']:
-            engine.adam(state, self._step, g['lr'], g['betas'], g['eps'])
+            if self._ex_on():              # lg_adam_step's arithmetic with the controls in the launch: the run stays on its bits
+                self._optim_step(engine, state, self.ALGO, 0, g['lr'], g['betas'][0], g['betas'][1], g['eps'], 0.0, plain_adam=True)
+            else:
+                engine.adam(state, self._step, g['lr'], g['betas'], g['eps'])
         else:
             self._optim_step(engine, state, self.ALGO, _lib.LG_OPT_AMSGRAD if g['amsgrad'] else 0, g['lr'], g['betas'][0], g['betas'][1],
                              g['eps'], g['weight_decay'])

@@ -145,6 +145,13 @@ class Pansharpening(nn.Module):
                                'Move the module and inputs to cuda.')
         return self.engine().forward_autograd(ms, pan, training=self.training)
 
+    def ema_state_dict(self, optim=None):
+        """`state_dict()` with the exponentially averaged weights of `optim` (a fused optimizer whose controls have ema_decay; default: the
+        one that last stepped this module) in place of the raw ones: detached copies, for export.  Before the first optimizer step the
+        average is the weights themselves."""
+        with self.engine().ema_weights(optim):
+            return {k: v.detach().clone() for k, v in self.state_dict().items()}
+
     def fuse_scene(self, ms, pan, **kw):
         """one scene of any size, MS [C,h,w] / PAN [1,4h,4w], through overlapping tiles of the training size (lgteun_amd/scene.py)"""
         from .scene import fuse_scene
@@ -202,7 +209,27 @@ class UnlgFormer(Base_model):
             loss_g = loss_g + rec_loss * w
             loss_res['rec_loss'] = rec_loss.item()
         loss_res['full_loss'] = loss_g.item()
-        G_optim.zero_grad()
-        loss_g.backward()
-        G_optim.step()
+        ctl = getattr(G_optim, 'lgteun_controls', None)      # cfg.train_cfg on torch's own optimizer: the window with torch's functions
+        acc = ctl.accumulate if ctl is not None else 1
+        pos = G_optim.lgteun_window_pos if acc > 1 else 0
+        if pos == 0:
+            G_optim.zero_grad()
+        (loss_g / acc if acc > 1 else loss_g).backward()
+        if pos + 1 >= acc:
+            if ctl is not None and ctl.max_grad_norm is not None:
+                self._torch_grad_norm = torch.nn.utils.clip_grad_norm_([p for p in core.parameters() if p.grad is not None], ctl.max_grad_norm)
+            G_optim.step()
+            pos = -1
+        if acc > 1:
+            G_optim.lgteun_window_pos = pos + 1
         self.print_train_log(iter_id, loss_res, log_freq)
+
+    def last_grad_norm(self):
+        """the global gradient norm of the last clipped optimizer step, before clipping (cfg.train_cfg with max_grad_norm), as a Python
+        float: a host sync, for logging"""
+        G = self.module_dict['core_module']
+        if getattr(self.optim_dict['core_module'], 'is_fused_lgteun', False):
+            return (G.module if hasattr(G, 'module') else G).engine().last_grad_norm()
+        if getattr(self, '_torch_grad_norm', None) is None:
+            raise RuntimeError('no gradient norm yet: cfg.train_cfg needs max_grad_norm, and one optimizer step')
+        return float(self._torch_grad_norm)

@@ -3,7 +3,12 @@
 logging cadence (one host sync every 10 iterations on the fused route, two per iteration on the other).  The fused route is the four
 library calls of Engine.train_step; the other one is the autograd bridge + nn.L1Loss / nn.MSELoss + the torch.optim class.
 Both runners of a pair are warmed up, then their legs alternate; a leg is timed with device events around `--steps` iterations.
-Prints one JSON line.   python tools/time_train_configs.py [--steps N] [--reps R]"""
+Prints one JSON line.   python tools/time_train_configs.py [--steps N] [--reps R]
+
+With `--train-cfg JSON` (may be repeated) the tool times the train-step controls instead: the fused route of ONE configuration (`--config`,
+default l1+Adam) without `train_cfg` against the same route with each given `cfg.train_cfg`, legs alternating in the same process, e.g.
+    python tools/time_train_configs.py --train-cfg '{"max_grad_norm": 1.0}' --train-cfg '{"ema_decay": 0.999}' --train-cfg '{"accumulate": 2}'
+The unit stays ms per train_iter call: with accumulate = A that is the cost per micro-batch, averaged over the window."""
 import argparse
 import json
 import os
@@ -34,10 +39,11 @@ def synth_batch(device):
 
 
 class Leg:
-    def __init__(self, loss, entry, fused, work_dir):
+    def __init__(self, loss, entry, fused, work_dir, train_cfg=None):
+        extra = {} if train_cfg is None else dict(train_cfg=dict(train_cfg))
         cfg = Config(dict(ms_chans=C, work_dir=work_dir, datas='GF-2', cuda=True, max_iter=10 ** 9, bit_depth=11,
                           loss_cfg={'rec_loss': dict(type=loss, w=1.)}, optim_cfg={'core_module': dict(entry, fused=fused)},
-                          sched_cfg=dict(step_size=25900, gamma=0.85), model_cfg={'core_module': dict(stage=K)}))
+                          sched_cfg=dict(step_size=25900, gamma=0.85), model_cfg={'core_module': dict(stage=K)}, **extra))
         torch.manual_seed(19971118)
         self.runner = lgteun_amd.build_model('UnlgFormer', cfg, None, None, None, None)
         self.runner.set_cuda()
@@ -69,13 +75,27 @@ def main():
     ap.add_argument('--reps', type=int, default=3, help='timed legs per route; the two routes alternate')
     ap.add_argument('--warmup', type=int, default=15)
     ap.add_argument('--work-dir', default=None, help='where the runners create their output tree (default: a temporary directory)')
+    ap.add_argument('--train-cfg', action='append', default=None, metavar='JSON',
+                    help='a cfg.train_cfg as a JSON object, e.g. \'{"max_grad_norm": 1.0}\'; may be repeated.  Times the fused route of --config '
+                         'without train_cfg against the fused route with each of them')
+    ap.add_argument('--config', default='l1+Adam', help='LOSS+OPTIMIZER of the --train-cfg comparison (default l1+Adam)')
     a = ap.parse_args()
     if a.steps < 100:
         ap.error('--steps must be at least 100')
+    if a.train_cfg is not None:
+        try:
+            a.train_cfg = [json.loads(t) for t in a.train_cfg]
+        except ValueError as e:
+            ap.error(f'--train-cfg takes a JSON object: {e}')
+        loss, _, name = a.config.partition('+')
+        if loss not in ('l1', 'l2') or name not in OPTIMS or not all(isinstance(t, dict) for t in a.train_cfg):
+            ap.error(f"--config is l1+ or l2+ one of {list(OPTIMS)}; every --train-cfg a JSON object")
     warnings.filterwarnings('ignore', message='Detected call of')
     if a.work_dir is None:
         a.work_dir = tempfile.mkdtemp(prefix='lgteun_time_')
     batch = synth_batch(torch.device('cuda', 0))
+    if a.train_cfg is not None:
+        return time_controls(a, batch)
     rows = {}
     for loss in ('l1', 'l2'):
         for name, entry in OPTIMS.items():
@@ -97,6 +117,28 @@ def main():
     print(json.dumps({'tool': 'time_train_configs', 'unit': 'ms per train_iter (median of the legs; spread = max - min of the legs)',
                       'workload': f'C={C}, PAN {H}x{H}, K={K}, {B} pairs, faithful mode, dropout on', 'steps_per_leg': a.steps,
                       'legs_per_route': a.reps, 'device': torch.cuda.get_device_name(0), 'cases': rows}))
+
+
+def time_controls(a, batch):
+    """the fused route of one configuration: no train_cfg (every launch what it was before the controls existed) against each train_cfg"""
+    loss, _, name = a.config.partition('+')
+    legs = {'off': Leg(loss, OPTIMS[name], True, a.work_dir)}
+    for t in a.train_cfg:
+        legs[json.dumps(t, sort_keys=True)] = Leg(loss, OPTIMS[name], True, a.work_dir, train_cfg=t)
+    for leg in legs.values():
+        leg.run(batch, a.warmup)
+    ms = {k: [] for k in legs}
+    for _ in range(a.reps):
+        for k, leg in legs.items():
+            ms[k].append(leg.timed_ms(batch, a.steps))
+    rows = {}
+    for k, v in ms.items():
+        rows[k] = dict(ms=round(statistics.median(v), 4), spread_ms=round(max(v) - min(v), 4))
+    for k, row in rows.items():
+        row['over_off'] = round(row['ms'] / rows['off']['ms'], 4)
+    print(json.dumps({'tool': 'time_train_configs', 'unit': 'ms per train_iter call (median of the legs; spread = max - min of the legs)',
+                      'workload': f'{a.config}, fused route, C={C}, PAN {H}x{H}, K={K}, {B} pairs, faithful mode, dropout on',
+                      'steps_per_leg': a.steps, 'legs_per_case': a.reps, 'device': torch.cuda.get_device_name(0), 'train_cfg': rows}))
 
 
 if __name__ == '__main__':
