@@ -59,6 +59,13 @@ extern "C" {
  * a chain of ~40 small latency-bound launches that leaves most of the GPU idle.  Same kernels, same work, same results. */
 #define LG_FLAG_DEFER_DEAD 64
 
+/* forward / dead_forward, with LG_FLAG_FAITHFUL: run the K-1 dead-stage LGT forwards ONE BY ONE (in lgteun_forward each behind its data step),
+ * as the library did before it had the batched pass.  Default (bit clear), for a plan with two or more dead stages whose route's forward kernels can take the
+ * samples of several stages in one launch (C = 4, planes up to 128 x 128): the K data steps first, then the dead stages as ONE pass over
+ * (K-1) B samples -- every kernel launched once, each workgroup choosing its stage's weights by its sample -- then the live stage.  Same work,
+ * same arithmetic, bitwise the same results; other plans run one by one whatever the bit says. */
+#define LG_FLAG_STAGEWISE 128
+
 /* kernel ids for the live HIP-event timing facility (lg_prof_*) */
 enum lg_kernel_id {
     LG_K_NONE = 0, LG_K_FFN1, LG_K_FFN2, LG_K_FFT, LG_K_ATTN, LG_K_UPFUSE, LG_K_DOWN, LG_K_EMBED, LG_K_TAIL, LG_K_DATASTEP,
@@ -109,7 +116,8 @@ typedef struct lg_plan lg_plan; /* host-side, immutable after creation */
 
 const char* lg_version(void);
 /* Bumped whenever a struct layout, an argument meaning or a caller-provided buffer size changes (2: lg_config.variant, the data step's
- * tmp of 3*B*C*H*W/4 + B*H*W floats).  A binding checks it at load time -- lgteun_amd/_lib.py does -- instead of passing a stale struct. */
+ * tmp of 3*B*C*H*W/4 + B*H*W floats).  Additions keep it: lg_op_lgt_stages, lg_workspace_deadout and LG_FLAG_STAGEWISE came without a bump (no struct,
+ * argument or caller-sized buffer changed: workspaces are sized by lg_workspace_bytes, which grew for the plans that batch their dead stages).  A binding checks it at load time -- lgteun_amd/_lib.py does -- instead of passing a stale struct. */
 #define LG_ABI_VERSION 2
 int32_t lg_abi_version(void);
 const char* lg_last_error(void); /* thread-local, host string */
@@ -214,7 +222,8 @@ int lg_optim_step_ex(float* params, const float* grads, float* state0, float* st
 
 /* Live per-kernel timing: when enabled for `kernel_id`, every launch of that kernel is bracketed by hipEvents recorded on
  * the stream it is launched on.  lg_prof_read synchronises on the recorded events and returns the summed device time (ms)
- * and the number of launches since lg_prof_enable / lg_prof_reset.  Host-side event objects are the only thing the library
+ * and the number of launches since lg_prof_enable / lg_prof_reset -- counted in launches of ONE stage's samples: a launch over the samples
+ * of S dead stages (LG_FLAG_STAGEWISE clear) counts S, so time / launches stays the time per stage-sized launch.  Host-side event objects are the only thing the library
  * ever creates; lg_prof_disable destroys them. */
 int lg_prof_enable(int32_t kernel_id, int32_t max_launches);
 int lg_prof_reset(void);
@@ -238,6 +247,18 @@ int lg_op_data_step(const lg_plan* plan, const float* params, int32_t stage, con
 /* one LGT forward (LGT.py:314-344) with stage `stage`'s weights: z [B,C,H,W] -> out [B,C,H,W]. */
 int lg_op_lgt(const lg_plan* plan, const float* params, int32_t stage, const float* z, float* out, void* workspace,
               size_t workspace_bytes, int32_t B, int32_t flags, uint64_t seed, void* stream);
+/* n LGT forwards (LGT.py:314-344) with the weights of stages stage0 .. stage0 + n - 1, as the reference issues them for the stages whose
+ * result it discards (unlg_former.py:56-67): z [n,B,C,H,W] -> out [n,B,C,H,W], nothing saved, as ONE pass over n B samples -- every
+ * kernel launched once.  n > 1 needs a plan whose dead stages run that way (C = 4, K >= 3, planes up to 128 x 128; n <= K-1) and is an
+ * error otherwise.  flags: 0 or LG_FLAG_DROPOUT: stage s's masks are those of lg_op_lgt(stage s) with the same seed.  grid_cap > 0 bounds
+ * the grid of the persistent kernels (fused FFN, local mixer), so that a small shape gives a workgroup samples of two stages; 0: no bound.
+ * The workspace is that of lg_workspace_bytes(plan, B, 0). */
+int lg_op_lgt_stages(const lg_plan* plan, const float* params, int32_t stage0, int32_t n, const float* z, float* out, void* workspace,
+                     size_t workspace_bytes, int32_t B, int32_t flags, uint64_t seed, int32_t grid_cap, void* stream);
+/* Where a forward with LG_FLAG_FAITHFUL leaves the discarded LGT outputs inside its workspace (train as for lg_workspace_bytes): stage i's
+ * [B,C,H,W] at byte offset *offset + i * *stage_stride.  *stage_stride is 0 for a plan that keeps one slot (every dead stage overwrites the
+ * previous one's). */
+int lg_workspace_deadout(const lg_plan* plan, int32_t B, int32_t train, size_t* offset, size_t* stage_stride);
 /* pieces of one LGB block `blk` (0,1: encoder; 2: bottleneck; 3,4: decoder) of stage `stage`, on NHWC x:
  *  which = 0: global_mixer on LN(x)[..., e/2:]  -> y planar [B,e/2,h,w]        (LGT.py:149-180)
  *          1: x + LGMixer(LN(x))                -> y [B,h,w,e]                 (LGT.py:183-219,231-248)

@@ -18,6 +18,7 @@ LG_FLAG_BWD_LGT = 8
 LG_FLAG_BWD_DATA = 16
 LG_FLAG_CHAINED = 32
 LG_FLAG_DEFER_DEAD = 64
+LG_FLAG_STAGEWISE = 128
 KERNEL_IDS = {n: i for i, n in enumerate(['none', 'ffn1', 'ffn', 'fft', 'attn', 'upfuse', 'down', 'embed', 'tail', 'datastep', 'ffn1_bwd',
                                            'ffn2_bwd', 'fft_bwd', 'attn_bwd', 'wgrad', 'batch', 'scene_gather', 'scene_blend'])}
 
@@ -120,6 +121,9 @@ SIGNATURES = {
                                   c_void_p]),
     'lg_op_lgt': (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_int32, c_uint64,
                             c_void_p]),
+    'lg_op_lgt_stages': (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_int32, c_uint64,
+                                   c_int32, c_void_p]),
+    'lg_workspace_deadout': (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_size_t), POINTER(c_size_t)]),
     'lg_op_block': (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_int32,
                               c_void_p]),
     'lg_dropout_mask': (c_int32, [c_uint64, c_int32, c_int32, c_int64, c_int64, c_void_p, c_void_p]),

@@ -34,6 +34,7 @@ static struct {
     std::atomic<int> kid{0};
     std::atomic<int> paused{0};
     int cap = 0, n = 0;
+    int64_t units = 0;         // stage-sized launches the n timed launches stand for (ProfScope: a launch over S stages counts S)
     hipEvent_t* ev = nullptr;  // 2 per launch
     std::mutex mu;
 } g_prof;
@@ -44,18 +45,20 @@ void lg_prof_begin(int kid, hipStream_t s) {
     if (kid != g_prof.kid.load(std::memory_order_relaxed) || g_prof.n >= g_prof.cap) return;
     hipEventRecord(g_prof.ev[2 * g_prof.n], s);
 }
-void lg_prof_end(int kid, hipStream_t s) {
+void lg_prof_end(int kid, hipStream_t s, int units) {
     if (kid != g_prof.kid.load(std::memory_order_relaxed) || g_prof.paused.load(std::memory_order_relaxed)) return;
     std::lock_guard<std::mutex> lk(g_prof.mu);
     if (kid != g_prof.kid.load(std::memory_order_relaxed) || g_prof.n >= g_prof.cap) return;
     hipEventRecord(g_prof.ev[2 * g_prof.n + 1], s);
     g_prof.n++;
+    g_prof.units += units;
 }
 static void prof_disable_locked() {
     for (int i = 0; i < 2 * g_prof.cap; ++i) hipEventDestroy(g_prof.ev[i]);
     free(g_prof.ev);
     g_prof.ev = nullptr;
     g_prof.cap = g_prof.n = 0;
+    g_prof.units = 0;
     g_prof.kid.store(0);
     g_prof.paused.store(0);
 }
@@ -82,6 +85,7 @@ extern "C" void lg_prof_pause(int32_t paused) { g_prof.paused.store(paused ? 1 :
 extern "C" int lg_prof_reset(void) {
     std::lock_guard<std::mutex> lk(g_prof.mu);
     g_prof.n = 0;
+    g_prof.units = 0;
     return 0;
 }
 extern "C" int lg_prof_read(double* total_ms, int64_t* launches) {
@@ -96,7 +100,7 @@ extern "C" int lg_prof_read(double* total_ms, int64_t* launches) {
         tot += ms;
     }
     *total_ms = tot;
-    *launches = g_prof.n;
+    *launches = g_prof.units;
     return 0;
 }
 extern "C" const char* lg_kernel_name(int32_t k) {
@@ -109,6 +113,7 @@ extern "C" const char* lg_version(void) { return "lgteun_hip 0.2 (gfx950)"; }
 extern "C" int32_t lg_abi_version(void) { return LG_ABI_VERSION; }
 extern "C" const char* lg_last_error(void) { return g_err; }
 
+static void lg_plan_stage_batch(lg_plan* p);
 extern "C" int lg_plan_create(const lg_config* cfg, const int64_t* offsets, int32_t n_offsets, lg_plan** out) {
     if (!cfg || !offsets || !out) { lg_set_error("plan_create: null argument"); return -1; }
     if (cfg->C != 4 && cfg->C != 8) { lg_set_error("plan_create: C must be 4 or 8 (got %d)", cfg->C); return -2; }
@@ -131,8 +136,27 @@ extern "C" int lg_plan_create(const lg_config* cfg, const int64_t* offsets, int3
     p->route = route;
     p->off = (int64_t*)malloc(sizeof(int64_t) * n_offsets);
     memcpy(p->off, offsets, sizeof(int64_t) * n_offsets);
+    lg_plan_stage_batch(p);
     *out = p;
     return 0;
+}
+
+// Decided once per plan: can the forward kernels of its route take the samples of several stages in one launch (kernels.h: StageSel), and is there
+// anything to gain (two or more dead stages)?  The parameter offsets must be affine in the stage, the FFT mixer the real-input in-LDS kernel, the
+// FFN / mixer kernels the persistent ones of the C = 4 route, and no workgroup's tile may straddle two samples.  Otherwise the dead stages run one by one.
+static void lg_plan_stage_batch(lg_plan* p) {
+    const lg_config& c = p->cfg;
+    const LgRoute& r = p->route;
+    p->stage_stride = c.K > 1 ? p->lgt(1, 0) - p->lgt(0, 0) : 0;
+    bool ok = c.K - 1 >= 2 && c.C == 4 && p->stage_stride > 0;
+    for (int st = 1; ok && st < c.K; ++st)
+        for (int slot = 0; slot < L_NSLOT; ++slot)
+            if (p->lgt(st, slot) - p->lgt(0, slot) != st * p->stage_stride) { ok = false; break; }
+    ok = ok && r.ffn[0].fwd[0] == FFN_FWD_XR && r.ffn[1].fwd[0] == FFN_FWD_X32 && r.mix[0].fwd == ATTN_FWD_M && r.mix[1].fwd == ATTN_FWD_M && !r.fft_full;
+    ok = ok && (r.ffn[1].scales || r.ffn[1].hbf);                        // (k_ffn_x32's three-piece arithmetic has no multi-stage instance)
+    ok = ok && !fft_is_generic(c.H, c.W) && c.H <= 128;                 // both levels' planes in LDS
+    ok = ok && ((c.H / 16) * (c.W / 16)) % 4 == 0;                      // level 1: whole window quads per sample (k_attn_m); the pixel kernels' tiles follow
+    p->stage_batch = ok;
 }
 
 extern "C" void lg_plan_destroy(lg_plan* plan) {
@@ -153,6 +177,16 @@ extern "C" size_t lg_workspace_bytes(const lg_plan* plan, int32_t B, int32_t tra
     size_t fwd = nb.bytes;
     if (train) fwd += bwd_workspace_bytes(plan, B);
     return fwd;
+}
+
+extern "C" int lg_workspace_deadout(const lg_plan* plan, int32_t B, int32_t train, size_t* offset, size_t* stage_stride) {
+    if (!plan || B <= 0 || train < 0 || train > 2 || !offset || !stage_stride) { lg_set_error("workspace_deadout: invalid argument"); return -1; }
+    NetBufs nb;
+    char base[1];   // carve() only adds offsets to the base it is given
+    carve(plan, B, train, base, nb);
+    *offset = (size_t)(reinterpret_cast<char*>(nb.deadout) - base);
+    *stage_stride = (plan->stage_batch && train != 2) ? (size_t)B * plan->cfg.C * plan->cfg.H * plan->cfg.W * sizeof(float) : 0;
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -196,7 +230,8 @@ static int data_step_fwd(const lg_plan* pl, const float* P, int stage, const flo
 }
 
 static int block_mixer_fwd(const lg_plan* pl, const float* P, int stage, int j, const BlockBufs& bb, const float* posT, int B,
-                           int flags, uint64_t seed, hipStream_t s, float* fft_scratch = nullptr, const float* attn_scales = nullptr) {
+                           int flags, uint64_t seed, hipStream_t s, float* fft_scratch = nullptr, const float* attn_scales = nullptr,
+                           const StageSel& sg = StageSel()) {
     int rc;
     const MixerRoute& mr = pl->mixer(bb.e);
     FftArgs f;
@@ -208,6 +243,7 @@ static int block_mixer_fwd(const lg_plan* pl, const float* P, int stage, int j, 
     f.ampw = P + pl->blk(stage, j, B_AMPW); f.ampb = P + pl->blk(stage, j, B_AMPB);
     f.phaw = P + pl->blk(stage, j, B_PHAW); f.phab = P + pl->blk(stage, j, B_PHAB);
     f.ch = bb.e / 2; f.planes = B * f.ch; f.n = bb.h; f.h = bb.h; f.w = bb.w; f.full = pl->route.fft_full;
+    f.sg = sg;
     if ((rc = launch_fftmix(f, s))) return rc;
     AttnArgs t;
     t.x = bb.xin; t.o2 = bb.o2; t.y = bb.xmid; t.posT = posT; t.pos = P + pl->blk(stage, j, B_POS);
@@ -218,13 +254,15 @@ static int block_mixer_fwd(const lg_plan* pl, const float* P, int stage, int j, 
     t.B = B; t.h = bb.h; t.w = bb.w;
     t.dropout = (flags & LG_FLAG_DROPOUT) ? 1 : 0;
     t.seed = mix_seed(seed, stage, j);
+    t.sg = sg; t.sg.seed = seed; t.sg.stage0 = stage; t.sg.blk = j;   // several stages: the kernel keys each stage's mask itself
     t.scales = (attn_scales && mr.f16x2) ? attn_scales + ((size_t)stage * 5 + j) * 4 : nullptr;   // written by prep_stages for the stages of this call
     if ((flags & LG_FLAG_SAVE) && mr.stats) { t.save_o = bb.att_o; t.save_l = bb.att_l; }
+    if (sg.n > 1 && mr.fwd == ATTN_FWD_VALU) { lg_set_error("mixer: the vector-pipe kernel takes one stage per launch"); return -2; }
     return mr.fwd == ATTN_FWD_VALU ? launch_attn(bb.e, t, s) : launch_attn_m(bb.e, t, s);
 }
 
 static int block_ffn_fwd(const lg_plan* pl, const float* P, int stage, int j, const BlockBufs& bb, float* g_next, int next_blk,
-                         int B, int flags, hipStream_t s, float* wsplit, const float* ffn_scales) {
+                         int B, int flags, hipStream_t s, float* wsplit, const float* ffn_scales, const StageSel& sg = StageSel()) {
     int rc;
     const FfnRoute& fr = pl->ffn(bb.e);
     const unsigned saves = (flags & LG_FLAG_SAVE) ? fr.saves : 0;   // the slots the backward's route reads (route.h)
@@ -248,6 +286,8 @@ static int block_ffn_fwd(const lg_plan* pl, const float* P, int stage, int j, co
     a2.n1b = g_next ? P + pl->blk(stage, next_blk, B_LN1B) : nullptr;
     a2.B = B; a2.h = bb.h; a2.w = bb.w; a2.hbf = a1.hbf;
     a1.h2 = bb.h2;
+    a1.sg = sg;
+    if (sg.n > 1 && a1.kernel != FFN_FWD_XR && a1.kernel != FFN_FWD_X32) { lg_set_error("ffn: this route's kernel takes one stage per launch"); return -2; }
     if (a1.kernel == FFN_FWD_UNFUSED) {
         if ((rc = launch_ffn1(bb.e, a1, s))) return rc;
         return launch_ffn2(bb.e, a2, s);
@@ -307,11 +347,21 @@ static int prep_stages(const lg_plan* pl, const float* P, int st0, int st1, NetB
 
 // LGT.forward (LGT.py:314-344) on z -> out with the buffers of `nb`
 // pos_ready: nb.posT already holds this stage's transposed pos_emb tables (the net-level entries transpose all stages in one launch)
+// nst > 1: the LGTs of stages stage .. stage + nst - 1 in ONE pass, every kernel launched once over nst * B samples (kernels.h: StageSel) -- stage
+// stage + i reads z + i * zstride, writes out + i * B C H W and uses samples [i B, (i + 1) B) of every buffer of `nb` (workspace.h carves them
+// that large for a plan with stage_batch).  Never with LG_FLAG_SAVE: only dead stages run this way.
 static int lgt_fwd(const lg_plan* pl, const float* P, int stage, const float* z, float* out, NetBufs& nb, int B, int flags,
-                   uint64_t seed, hipStream_t s, bool pos_ready = false) {
+                   uint64_t seed, hipStream_t s, bool pos_ready = false, int nst = 1, long zstride = 0, int grid_cap = 0) {
     const lg_config& c = pl->cfg;
     const int E = 4 * c.C;
     int rc;
+    StageSel sg;
+    if (nst > 1) {
+        if (!pl->stage_batch || (flags & LG_FLAG_SAVE) || !pos_ready) { lg_set_error("lgt_fwd: this plan / call runs one stage per pass"); return -2; }
+        sg.n = nst; sg.Bs = B; sg.pstride = pl->stage_stride; sg.zstride = zstride; sg.grid_cap = grid_cap;
+        sg.fs_stride = 5 * 8; sg.as_stride = 5 * 4; sg.ws_stride = 5 * (long)ffn_wsplit_bytes(8 * c.C);   // the rows prep_stages writes per stage
+    }
+    B *= nst;   // what every kernel below sees: a plain batch
     float* posT = nb.posT + (size_t)stage * 5 * 2 * 64 * 64;
     if (!pos_ready && (rc = prep_stages(pl, P, stage, stage + 1, nb, s))) return rc;
     EmbedArgs ea;
@@ -320,24 +370,24 @@ static int lgt_fwd(const lg_plan* pl, const float* P, int stage, const float* z,
     ea.w = P + pl->lgt(stage, L_PE_W); ea.b = P + pl->lgt(stage, L_PE_B);
     ea.lng = P + pl->lgt(stage, L_PE_LNG); ea.lnb = P + pl->lgt(stage, L_PE_LNB);
     ea.n1g = P + pl->blk(stage, 0, B_LN1G); ea.n1b = P + pl->blk(stage, 0, B_LN1B);
-    ea.HW = c.H * c.W; ea.total = (long)B * c.H * c.W;
+    ea.HW = c.H * c.W; ea.total = (long)B * c.H * c.W; ea.sg = sg;
     if ((rc = launch_embed(c.C, ea, s))) return rc;
     // encoder LGB (2 blocks)
-    if ((rc = block_mixer_fwd(pl, P, stage, 0, nb.blk[0], posT + 0 * 8192, B, flags, seed, s, nb.fft_scratch, nb.attn_scales))) return rc;
-    if ((rc = block_ffn_fwd(pl, P, stage, 0, nb.blk[0], nb.blk[1].g, 1, B, flags, s, nb.wsplit, nb.ffn_scales))) return rc;
-    if ((rc = block_mixer_fwd(pl, P, stage, 1, nb.blk[1], posT + 1 * 8192, B, flags, seed, s, nb.fft_scratch, nb.attn_scales))) return rc;
-    if ((rc = block_ffn_fwd(pl, P, stage, 1, nb.blk[1], nullptr, 0, B, flags, s, nb.wsplit, nb.ffn_scales))) return rc;
+    if ((rc = block_mixer_fwd(pl, P, stage, 0, nb.blk[0], posT + 0 * 8192, B, flags, seed, s, nb.fft_scratch, nb.attn_scales, sg))) return rc;
+    if ((rc = block_ffn_fwd(pl, P, stage, 0, nb.blk[0], nb.blk[1].g, 1, B, flags, s, nb.wsplit, nb.ffn_scales, sg))) return rc;
+    if ((rc = block_mixer_fwd(pl, P, stage, 1, nb.blk[1], posT + 1 * 8192, B, flags, seed, s, nb.fft_scratch, nb.attn_scales, sg))) return rc;
+    if ((rc = block_ffn_fwd(pl, P, stage, 1, nb.blk[1], nullptr, 0, B, flags, s, nb.wsplit, nb.ffn_scales, sg))) return rc;
     // down
     DownArgs da;
     da.x = nb.blk[1].xout; da.y = nb.blk[2].xin; da.g = nb.blk[2].g;
     da.u_save = (flags & LG_FLAG_SAVE) ? nb.u_down : nullptr;
     da.w = P + pl->lgt(stage, L_DOWNW); da.b = P + pl->lgt(stage, L_DOWNB);
     da.n1g = P + pl->blk(stage, 2, B_LN1G); da.n1b = P + pl->blk(stage, 2, B_LN1B);
-    da.B = B; da.H = c.H; da.W = c.W;
+    da.B = B; da.H = c.H; da.W = c.W; da.sg = sg;
     if ((rc = launch_down(E, da, s))) return rc;
     // bottleneck
-    if ((rc = block_mixer_fwd(pl, P, stage, 2, nb.blk[2], posT + 2 * 8192, B, flags, seed, s, nb.fft_scratch, nb.attn_scales))) return rc;
-    if ((rc = block_ffn_fwd(pl, P, stage, 2, nb.blk[2], nullptr, 0, B, flags, s, nb.wsplit, nb.ffn_scales))) return rc;
+    if ((rc = block_mixer_fwd(pl, P, stage, 2, nb.blk[2], posT + 2 * 8192, B, flags, seed, s, nb.fft_scratch, nb.attn_scales, sg))) return rc;
+    if ((rc = block_ffn_fwd(pl, P, stage, 2, nb.blk[2], nullptr, 0, B, flags, s, nb.wsplit, nb.ffn_scales, sg))) return rc;
     // up + fusion
     UpFuseArgs ua;
     ua.xb = nb.blk[2].xout; ua.skip = nb.blk[1].xout; ua.y = nb.blk[3].xin; ua.g = nb.blk[3].g;
@@ -345,19 +395,28 @@ static int lgt_fwd(const lg_plan* pl, const float* P, int stage, const float* z,
     ua.upw = P + pl->lgt(stage, L_UPW); ua.upb = P + pl->lgt(stage, L_UPB);
     ua.fw = P + pl->lgt(stage, L_FUSEW); ua.fb = P + pl->lgt(stage, L_FUSEB);
     ua.n1g = P + pl->blk(stage, 3, B_LN1G); ua.n1b = P + pl->blk(stage, 3, B_LN1B);
-    ua.B = B; ua.H = c.H; ua.W = c.W;
+    ua.B = B; ua.H = c.H; ua.W = c.W; ua.sg = sg;
     if ((rc = launch_upfuse(E, ua, s))) return rc;
     // decoder LGB (2 blocks)
-    if ((rc = block_mixer_fwd(pl, P, stage, 3, nb.blk[3], posT + 3 * 8192, B, flags, seed, s, nb.fft_scratch, nb.attn_scales))) return rc;
-    if ((rc = block_ffn_fwd(pl, P, stage, 3, nb.blk[3], nb.blk[4].g, 4, B, flags, s, nb.wsplit, nb.ffn_scales))) return rc;
-    if ((rc = block_mixer_fwd(pl, P, stage, 4, nb.blk[4], posT + 4 * 8192, B, flags, seed, s, nb.fft_scratch, nb.attn_scales))) return rc;
-    if ((rc = block_ffn_fwd(pl, P, stage, 4, nb.blk[4], nullptr, 0, B, flags, s, nb.wsplit, nb.ffn_scales))) return rc;
+    if ((rc = block_mixer_fwd(pl, P, stage, 3, nb.blk[3], posT + 3 * 8192, B, flags, seed, s, nb.fft_scratch, nb.attn_scales, sg))) return rc;
+    if ((rc = block_ffn_fwd(pl, P, stage, 3, nb.blk[3], nb.blk[4].g, 4, B, flags, s, nb.wsplit, nb.ffn_scales, sg))) return rc;
+    if ((rc = block_mixer_fwd(pl, P, stage, 4, nb.blk[4], posT + 4 * 8192, B, flags, seed, s, nb.fft_scratch, nb.attn_scales, sg))) return rc;
+    if ((rc = block_ffn_fwd(pl, P, stage, 4, nb.blk[4], nullptr, 0, B, flags, s, nb.wsplit, nb.ffn_scales, sg))) return rc;
     // tail
     TailArgs ta;
     ta.x = nb.blk[4].xout; ta.z = z; ta.out = out;
     ta.w = P + pl->lgt(stage, L_TAILW); ta.b = P + pl->lgt(stage, L_TAILB);
-    ta.HW = c.H * c.W; ta.total = (long)B * c.H * c.W;
+    ta.HW = c.H * c.W; ta.total = (long)B * c.H * c.W; ta.sg = sg;
     return launch_tail(c.C, ta, s);
+}
+
+// where dead stage i's output goes: a plan with stage_batch has room for all K-1 of them (the batched pass writes them side by side), any other one slot
+static float* dead_out(const lg_plan* pl, const NetBufs& nb, int i, int B) {
+    return nb.deadout + (pl->stage_batch ? (size_t)i * B * pl->cfg.C * pl->cfg.H * pl->cfg.W : 0);
+}
+// the K-1 dead-stage LGT forwards as one pass (lgt_fwd with nst = K-1): non-saving, Z[1 ..] in, deadout[0 ..] out
+static int dead_pass(const lg_plan* pl, const float* P, NetBufs& nb, int B, int flags, uint64_t seed, hipStream_t s) {
+    return lgt_fwd(pl, P, 0, nb.Z[1], nb.deadout, nb, B, flags & ~LG_FLAG_SAVE, seed, s, true, pl->cfg.K - 1, (long)(nb.Z[2] - nb.Z[1]));
 }
 
 extern "C" int lgteun_forward(const lg_plan* plan, const float* params, const float* ms, const float* pan, float* out,
@@ -388,17 +447,18 @@ extern "C" int lgteun_forward(const lg_plan* plan, const float* params, const fl
         }
         return 0;
     }
+    // The reference executes the LGTs of stages 0 .. K-2 and discards their result (unlg_former.py:63-67).  They read Z[1] .. Z[K-1], which
+    // the data steps alone produce, so with two or more of them (and a route whose kernels can: lg_plan_stage_batch) the K data steps run first and the
+    // dead stages follow as ONE pass over (K-1) B samples; LG_FLAG_STAGEWISE keeps them one by one, each behind its data step.
+    const bool dead = (flags & LG_FLAG_FAITHFUL) && !(flags & LG_FLAG_DEFER_DEAD) && c.K > 1;
+    const bool dead_batched = dead && plan->stage_batch && !(flags & LG_FLAG_STAGEWISE);
     for (int i = 0; i < c.K; ++i) {
         if ((rc = data_step_fwd(plan, params, i, nb.Z[i], ms, pan, nb.Z[i + 1], nb.t1[i], nb.r[i], nb.s1[i], nb.pr, B, s))) return rc;
-        const bool last = (i == c.K - 1);
-        if (last) {
-            if ((rc = lgt_fwd(plan, params, i, nb.Z[i + 1], out, nb, B, flags, seed, s, true))) return rc;
-        } else if ((flags & LG_FLAG_FAITHFUL) && !(flags & LG_FLAG_DEFER_DEAD)) {
-            // the reference executes these LGTs and discards their result (unlg_former.py:63-67)
-            if ((rc = lgt_fwd(plan, params, i, nb.Z[i + 1], nb.deadout, nb, B, flags & ~LG_FLAG_SAVE, seed, s, true))) return rc;
-        }
+        if (i < c.K - 1 && dead && !dead_batched &&
+            (rc = lgt_fwd(plan, params, i, nb.Z[i + 1], dead_out(plan, nb, i, B), nb, B, flags & ~LG_FLAG_SAVE, seed, s, true))) return rc;
     }
-    return 0;
+    if (dead_batched && (rc = dead_pass(plan, params, nb, B, flags, seed, s))) return rc;
+    return lgt_fwd(plan, params, c.K - 1, nb.Z[c.K], out, nb, B, flags, seed, s, true);
 }
 
 extern "C" int lgteun_dead_forward(const lg_plan* plan, const float* params, void* workspace, size_t workspace_bytes, int32_t B,
@@ -413,8 +473,9 @@ extern "C" int lgteun_dead_forward(const lg_plan* plan, const float* params, voi
         const int rc = prep_stages(plan, params, 0, plan->cfg.K - 1, nb, (hipStream_t)stream);
         if (rc) return rc;
     }
+    if (plan->stage_batch && !(flags & LG_FLAG_STAGEWISE)) return dead_pass(plan, params, nb, B, flags, seed, (hipStream_t)stream);
     for (int i = 0; i + 1 < plan->cfg.K; ++i) {
-        const int rc = lgt_fwd(plan, params, i, nb.Z[i + 1], nb.deadout, nb, B, flags & ~LG_FLAG_SAVE, seed, (hipStream_t)stream, true);
+        const int rc = lgt_fwd(plan, params, i, nb.Z[i + 1], dead_out(plan, nb, i, B), nb, B, flags & ~LG_FLAG_SAVE, seed, (hipStream_t)stream, true);
         if (rc) return rc;
     }
     return 0;
@@ -460,6 +521,19 @@ extern "C" int lg_op_lgt(const lg_plan* plan, const float* params, int32_t stage
     NetBufs nb;
     carve(plan, B, train, workspace, nb);
     return lgt_fwd(plan, params, stage, z, out, nb, B, flags, seed, (hipStream_t)stream);
+}
+
+extern "C" int lg_op_lgt_stages(const lg_plan* plan, const float* params, int32_t stage0, int32_t n, const float* z, float* out, void* workspace,
+                                size_t workspace_bytes, int32_t B, int32_t flags, uint64_t seed, int32_t grid_cap, void* stream) {
+    if (!plan || !params || !z || !out || !workspace || B <= 0 || stage0 < 0 || n < 1 || stage0 + n > plan->cfg.K || grid_cap < 0) { lg_set_error("op_lgt_stages: invalid argument"); return -1; }
+    if (flags & ~LG_FLAG_DROPOUT) { lg_set_error("op_lgt_stages: only LG_FLAG_DROPOUT applies (nothing is saved)"); return -2; }
+    if (n > 1 && (!plan->stage_batch || n > plan->cfg.K - 1)) { lg_set_error("op_lgt_stages: this plan runs one stage per pass (lg_plan_stage_batch), or n > K-1"); return -2; }
+    if (workspace_bytes < lg_workspace_bytes(plan, B, 0)) { lg_set_error("op_lgt_stages: workspace too small"); return -3; }
+    NetBufs nb;
+    carve(plan, B, 0, workspace, nb);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = prep_stages(plan, params, stage0, stage0 + n, nb, s)) return rc;
+    return lgt_fwd(plan, params, stage0, z, out, nb, B, flags, seed, s, true, n, (long)B * plan->cfg.C * plan->cfg.H * plan->cfg.W, grid_cap);
 }
 
 extern "C" int lg_op_block(const lg_plan* plan, const float* params, int32_t stage, int32_t blk, int32_t which, const float* x,

@@ -36,6 +36,8 @@ struct lg_plan {
     const FfnRoute& ffn(int e) const { return route.ffn[e != 4 * cfg.C]; }
     const MixerRoute& mixer(int e) const { return route.mix[e != 4 * cfg.C]; }
     int64_t* off;  // host copy of offsets
+    int64_t stage_stride = 0;   // floats from a tensor of LGT s to the same tensor of LGT s + 1 (the K LGTs have identical shapes)
+    bool stage_batch = false;   // the K-1 dead-stage LGT forwards of a faithful step can run as ONE pass over (K-1) B samples (api.hip: lg_plan_stage_batch)
     int64_t shared(int s) const { return off[s]; }
     int64_t eta(int i) const { return off[S_NSHARED + i]; }
     int64_t lgt(int stage, int slot) const { return off[S_NSHARED + cfg.K + stage * L_NSLOT + slot]; }
@@ -54,6 +56,9 @@ struct DeviceOnce {
 };
 
 // per-(stage, block) dropout seed, shared by forward and backward
+#ifdef __HIPCC__
+__host__ __device__
+#endif
 static inline uint64_t mix_seed(uint64_t seed, int stage, int blk) {
     uint64_t z = seed + 0x9E3779B97F4A7C15ull * (uint64_t)(stage * 8 + blk + 1);
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -74,13 +79,15 @@ static inline uint64_t mix_seed(uint64_t seed, int stage, int blk) {
 #define LG_EPS 1e-5f
 
 // live per-kernel timing (api.hip): RAII scope used at the top of a launcher
+// units: how many stage-sized launches this one stands for (a launch over the samples of S stages records S: lg_prof_read's count, and with it the
+// time per launch a caller derives, stay those of one stage's launch)
 void lg_prof_begin(int kid, hipStream_t s);
-void lg_prof_end(int kid, hipStream_t s);
+void lg_prof_end(int kid, hipStream_t s, int units);
 struct ProfScope {
-    int kid;
+    int kid, units;
     hipStream_t s;
-    ProfScope(int k, hipStream_t st) : kid(k), s(st) { lg_prof_begin(kid, s); }
-    ~ProfScope() { lg_prof_end(kid, s); }
+    ProfScope(int k, hipStream_t st, int u = 1) : kid(k), units(u > 1 ? u : 1), s(st) { lg_prof_begin(kid, s); }
+    ~ProfScope() { lg_prof_end(kid, s, units); }
 };
 
 #ifdef __HIPCC__
@@ -216,6 +223,10 @@ __device__ __forceinline__ float gelu_grad_f(float x) {
     const float pdf = 0.39894228040143267794f * __expf(-0.5f * x * x);
     return cdf + x * pdf;
 }
+// a value every lane of the wave holds alike, moved to a scalar register.  A load from a uniform address inside a loop that also stores is issued as
+// a vector load (the compiler cannot prove that nothing clobbers it) and its value -- and every constant derived from it -- would occupy a vector
+// register per lane: the operand scales the persistent kernels read again at a stage boundary (kernels.h: StageSel)
+__device__ __forceinline__ float uniform_f(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // cubic-convolution weights, A = -0.75 (torch upsample_bicubic2d); taps at i0-1 .. i0+2.

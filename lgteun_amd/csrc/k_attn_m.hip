@@ -209,8 +209,9 @@ __device__ unsigned long long am_stamps[1024][4][8];
 #else
 #define AM_STAMP(i) do { } while (0)
 #endif
-template <int HC, int NP>
-__global__ __launch_bounds__(256, (HC <= 16 ? 2 : 1)) void k_attn_m(AttnArgs a, int nwin, int nquads, int uneven) {
+// MULTI: the launch covers the samples of several stages (kernels.h: StageSel); false: the segment loop below is one straight pass
+template <int HC, int NP, bool MULTI = false>
+__global__ __launch_bounds__(256, (HC <= 16 ? 2 : 1)) void k_attn_m(AttnArgs a_, int nwin, int nquads, int uneven) {
     using namespace am;
     using G = Geo<HC>;
     constexpr int E = G::E, D = G::D, DG = G::DG, NCH = G::NCH, NY = G::NY, MTQK = G::MTQK, NTV = G::NTV;
@@ -234,9 +235,35 @@ __global__ __launch_bounds__(256, (HC <= 16 ? 2 : 1)) void k_attn_m(AttnArgs a, 
 #ifdef LG_ATTN_STAMPS
     unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = __builtin_amdgcn_s_memtime();
 #endif
+    // The workgroup's window quads.  One stage in the launch: quads q0, + qstep, ... (the uneven split included) in ONE pass of the segment loop.
+    // Several stages (kernels.h: StageSel; quads ascend with the sample): a contiguous run of quads, one segment per stage -- at a stage boundary
+    // pos_emb, the weight fragments and the lane constants are staged again, behind a barrier, from that stage's block.
+    const StageSel sg = a_.sg;
+    constexpr bool multi = MULTI;
+    const int half = (int)gridDim.x >> 1, first = (int)blockIdx.x < half ? 1 : 0;
+    const int nmine = uneven ? (first ? uneven : 8 - uneven) : 0x7fffffff;
+    const int q0 = uneven ? (first ? (int)blockIdx.x : half * uneven + ((int)blockIdx.x - half)) : (int)blockIdx.x;
+    const int qstep = multi ? 1 : (uneven ? half : (int)gridDim.x);
+    const int per_stage = multi ? __builtin_amdgcn_readfirstlane(nquads / sg.n) : nquads;
+    const int run0 = multi ? __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (unsigned)nquads / gridDim.x)) : q0;              // (grid x quads < 2^32: the launcher checks it)
+    const int run1 = multi ? __builtin_amdgcn_readfirstlane((int)((blockIdx.x + 1) * (unsigned)nquads / gridDim.x)) : nquads;
+    int seg0 = run0;
+    do {
+    const int stg = multi ? __builtin_amdgcn_readfirstlane(seg0 / per_stage) : 0;   // (division runs on the vector pipe: kernels.h, stage_of)
+    const int seg1 = multi ? min(run1, (stg + 1) * per_stage) : run1;
+    AttnArgs a = a_;
+    {
+        const long po = stg * sg.pstride;
+        a.pos += po; a.ln1g += po; a.ln1b += po; a.qkvw += po; a.qkvb += po; a.projw += po; a.projb += po;
+        if (NP == 2) a.scales += stg * sg.as_stride;
+    }
+    // dropout of stage stg: its own key, its elements counted from the start of the stage's own tensor
+    const uint64_t dseed = multi ? mix_seed(sg.seed, sg.stage0 + stg, sg.blk) : a.seed;
+    const long dpix0 = (long)stg * sg.Bs * a.h * a.w;
+    if (seg0 != run0) __syncthreads();   // every wave is done with the previous stage's tables
     // static operand scales of the pairs (powers of two: exact; taken out again by constants that were multiplications already)
     float sy = 1.f, sw = 1.f, sq = 1.f, sk = 1.f;
-    if (NP == 2) { sy = a.scales[0]; sw = a.scales[1]; sq = a.scales[2]; sk = a.scales[3]; }
+    if (NP == 2) { sy = uniform_f(a.scales[0]); sw = uniform_f(a.scales[1]); sq = uniform_f(a.scales[2]); sk = uniform_f(a.scales[3]); }
     const float syw = sy * sw, inv_yw = 1.0f / syw, sqk = sq * sk, inv_qk = 1.0f / sqk;
     // ---- once per (persistent) workgroup: pos_emb in fragment order, the weight fragments, the lane constants.  Every request of the prologue goes out
     // before its first wait (as pos -> store -> table -> store -> table -> ... it was seven dependent round trips per launch at HC = 8)
@@ -299,11 +326,7 @@ __global__ __launch_bounds__(256, (HC <= 16 ? 2 : 1)) void k_attn_m(AttnArgs a, 
 
     // uneven (launcher: 512 resident workgroups, eight window quads per pair): the dispatcher places workgroups 0 .. 255 one per CU before the second 256 and the SIMD
     // arbiter issues the older wave first, so a CU's first workgroup runs faster than its second (k_ffn_xr.hip has the measurement): it takes 5 of the pair's 8 quads
-    const int half = (int)gridDim.x >> 1, first = (int)blockIdx.x < half ? 1 : 0;
-    const int nmine = uneven ? (first ? uneven : 8 - uneven) : 0x7fffffff;
-    const int q0 = uneven ? (first ? (int)blockIdx.x : half * uneven + ((int)blockIdx.x - half)) : (int)blockIdx.x;
-    const int qstep = uneven ? half : (int)gridDim.x;
-    for (int quad = q0, kq = 0; quad < nquads && kq < nmine; quad += qstep, ++kq) {
+    for (int quad = seg0, kq = 0; quad < seg1 && kq < nmine; quad += qstep, ++kq) {
         const int win = quad * 4 + __builtin_amdgcn_readfirstlane(wave);   // provably wave-uniform: window origins stay in scalar registers
         if (win >= nwin) continue;   // no barrier inside the loop
         const int wx = win % nwx, rr = win / nwx, wy = rr % nwy;
@@ -513,13 +536,13 @@ __global__ __launch_bounds__(256, (HC <= 16 ? 2 : 1)) void k_attn_m(AttnArgs a, 
 #pragma unroll
                 for (int k = 0; k < NKP; ++k) acc = mfma_bf(sWp[(mt * NKP + k) * 64 + lane], cf[k], acc);
                 float o[4];
-                const uint64_t di = (uint64_t)(pix * E + 16 * mt + 4 * g);   // a multiple of 4: | v below never carries
+                const uint64_t di = (uint64_t)((pix - dpix0) * E + 16 * mt + 4 * g);   // a multiple of 4: | v below never carries
 #pragma unroll
                 for (int v = 0; v < 4; ++v) o[v] = acc[v];
                 if (a.dropout) {   // two hashes for the lane's four consecutive channels
                     float s0, s1, s2, s3;
-                    dropout_scale2(a.seed, di, s0, s1);
-                    dropout_scale2(a.seed, di + 2, s2, s3);
+                    dropout_scale2(dseed, di, s0, s1);
+                    dropout_scale2(dseed, di + 2, s2, s3);
                     o[0] *= s0; o[1] *= s1; o[2] *= s2; o[3] *= s3;
                 }
                 const float4 xr = RELOADX ? *reinterpret_cast<const float4*>(xw + (qt * tstep * E + 16 * mt + lx)) : xv[qt][mt];
@@ -528,6 +551,8 @@ __global__ __launch_bounds__(256, (HC <= 16 ? 2 : 1)) void k_attn_m(AttnArgs a, 
         }
         AM_STAMP(5);   // proj, dropout, residual, stores issued
     }
+    seg0 = seg1;
+    } while (MULTI && seg0 < run1);   // segments (stages) of this workgroup
 #ifdef LG_ATTN_STAMPS
     if (lane == 0 && blockIdx.x < 1024) {
         for (int i = 0; i < 6; ++i) am_stamps[blockIdx.x][wave][i] = st[i];
@@ -536,7 +561,7 @@ __global__ __launch_bounds__(256, (HC <= 16 ? 2 : 1)) void k_attn_m(AttnArgs a, 
 #endif
 }
 
-template <int HC, int NP>
+template <int HC, int NP, bool MULTI = false>
 static int launch_attn_m_t(const AttnArgs& a, hipStream_t s) {
     using G = am::Geo<HC>;
     constexpr int NPQ = NP == 2 ? 2 : NP, NPP = NP == 2 ? 3 : NP;
@@ -546,7 +571,7 @@ static int launch_attn_m_t(const AttnArgs& a, hipStream_t s) {
     const size_t lds = (size_t)(2 * 4 * 4 * 64 + (G::MTQK + G::NTV) * NKQ * 64 + G::NCH * NKP * 64) * 16;
     static DeviceOnce attr_once;
     if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_attn_m<HC, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipError_t e = hipFuncSetAttribute((const void*)k_attn_m<HC, NP, MULTI>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) { lg_set_error("attn_m: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
         attr_once.done();
     }
@@ -557,7 +582,7 @@ static int launch_attn_m_t(const AttnArgs& a, hipStream_t s) {
     int per_cu = per_cu_cache[DeviceOnce::dev()].load(std::memory_order_acquire);
     if (per_cu <= 0) {
         int nb = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_attn_m<HC, NP>, 256, lds);
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_attn_m<HC, NP, MULTI>, 256, lds);
         if (e != hipSuccess || nb < 1) { lg_set_error("attn_m: occupancy query: %s (%d)", hipGetErrorString(e), nb); return e != hipSuccess ? (int)e : -3; }
         per_cu = nb;
         per_cu_cache[DeviceOnce::dev()].store(per_cu, std::memory_order_release);
@@ -565,19 +590,31 @@ static int launch_attn_m_t(const AttnArgs& a, hipStream_t s) {
     int ncu = 256;
     const int cap = ncu * per_cu;
     const int rounds = (nquads + cap - 1) / cap;
-    const int grid = nquads < cap ? nquads : (nquads + rounds - 1) / rounds;
+    int grid = nquads < cap ? nquads : (nquads + rounds - 1) / rounds;
+    constexpr bool multi = MULTI;
+    if (multi) {   // whole quads per stage (a quad = the four windows of a workgroup's waves), and with more quads than slots exactly the resident workgroups
+        if (a.save_o || a.save_l || a.sg.Bs <= 0 || a.B != a.sg.n * a.sg.Bs || (a.sg.Bs * (a.h / 8) * (a.w / 8)) % 4) { lg_set_error("attn_m: a window quad would straddle the stages of the launch"); return -2; }
+        if (nquads > cap) grid = cap;
+        if (a.sg.grid_cap > 0 && grid > a.sg.grid_cap) grid = a.sg.grid_cap;
+    }
 #ifndef LG_ATTN_UNEVEN
 #define LG_ATTN_UNEVEN 5
 #endif
-    const int uneven = (per_cu == 2 && grid == 512 && nquads == 4 * grid && nwin == 4 * nquads) ? LG_ATTN_UNEVEN : 0;   // the measured shape only
-    k_attn_m<HC, NP><<<grid, 256, lds, s>>>(a, nwin, nquads, uneven == 4 ? 0 : uneven);
+    const int uneven = (!multi && per_cu == 2 && grid == 512 && nquads == 4 * grid && nwin == 4 * nquads) ? LG_ATTN_UNEVEN : 0;   // the measured shape only
+    k_attn_m<HC, NP, MULTI><<<grid, 256, lds, s>>>(a, nwin, nquads, uneven == 4 ? 0 : uneven);
     LG_CHECK_LAUNCH();
     return 0;
 }
 
 int launch_attn_m(int e, const AttnArgs& a, hipStream_t s) {
-    ProfScope prof__(LG_K_ATTN, s);
+    ProfScope prof__(LG_K_ATTN, s, a.sg.n);
     if ((a.h & 7) || (a.w & 7)) { lg_set_error("attn: h,w must be multiples of 8"); return -2; }
+    if (a.sg.n > 1) {   // several stages in one launch: the C = 4 route's widths
+        if (e == 16) return a.bf16 ? launch_attn_m_t<8, 1, true>(a, s) : (a.scales ? launch_attn_m_t<8, 2, true>(a, s) : launch_attn_m_t<8, 3, true>(a, s));
+        if (e == 32) return a.bf16 ? launch_attn_m_t<16, 1, true>(a, s) : (a.scales ? launch_attn_m_t<16, 2, true>(a, s) : launch_attn_m_t<16, 3, true>(a, s));
+        lg_set_error("attn: e=%d takes one stage per launch", e);
+        return -2;
+    }
     if (a.bf16) {
         if (e == 16) return launch_attn_m_t<8, 1>(a, s);
         if (e == 32) return launch_attn_m_t<16, 1>(a, s);

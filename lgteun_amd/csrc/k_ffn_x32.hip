@@ -91,20 +91,44 @@ __global__ __launch_bounds__(256) void k_split_w_jobs(SplitWTable tab) {
 // SAVE: 0 nothing; 1 gelu(h1), gelu'(h1), h2 and gelu(h3) / gelu'(h3) or the pre-activation h3 (a2.g3s null); 2 h2 and h3 only (the backward
 // re-computes h1 from x: k_ffn1_bwd_xs<32>) -- a compile-time mode: as a run-time test of a1.a1s inside the unrolled stage the saving launch
 // spilled and ran 570 us instead of 341
-template <int SAVE, int NP>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_ffn_x32(Ffn1Args a1, Ffn2Args a2, const u32x4_t* __restrict__ wsp, int tiles_x, int strips_y, int nstrips, int SH) {
+// MULTI: the launch covers the samples of several stages (kernels.h: StageSel); false: the segment loop is one straight pass (k_ffn_xr.hip)
+template <int SAVE, int NP, bool MULTI = false>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_ffn_x32(Ffn1Args a1_, Ffn2Args a2_, const u32x4_t* __restrict__ wsp_, int tiles_x, int strips_y, int nstrips, int SH) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float* ring = reinterpret_cast<float*>(smem_raw);                                   // [RING*HX][LDR]
     uint16_t* A2 = reinterpret_cast<uint16_t*>(smem_raw + (size_t)RING * HX * LDR * 4);   // [NA2][3][CH][N1], chunk-swizzled
     uint16_t* XA = A2 + NA2 * A2_HALVES;                                                // [2][3][CH][E]
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
     uint16_t* G3 = A2 + wave * G3_WAVE;                                                 // [3][16][64], aliases A2 / XA
-    const int h = a2.h, w = a2.w;
+    const int h = a2_.h, w = a2_.w;
     __shared__ __attribute__((aligned(16))) float sPar[5 * E];
     __shared__ __attribute__((aligned(16))) float sMask[4][CH];   // halo-pixel masks of up to four chunks in flight (slot = chunk & 3; round 2's form uses two)
     float* sLn2g = sPar;            float* sLn2b = sPar + E;
     float* sN1g = sPar + 2 * E;     float* sN1b = sPar + 3 * E;
     float* sB3 = sPar + 4 * E;
+    // The workgroup's strips: one stage in the launch -- strips blockIdx.x, + gridDim.x, ... in ONE pass of the segment loop; several stages (kernels.h:
+    // StageSel) -- a contiguous run of strips in one segment per stage, the tables staged again behind a barrier at a stage boundary (k_ffn_xr.hip)
+    const StageSel sg = a1_.sg;
+    constexpr bool multi = MULTI;
+    const int per_stage = multi ? sg.Bs * tiles_x * strips_y : nstrips;
+    const int run0 = multi ? __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (unsigned)nstrips / gridDim.x)) : (int)blockIdx.x;          // (grid x strips < 2^31: both are
+    const int run1 = multi ? __builtin_amdgcn_readfirstlane((int)((blockIdx.x + 1) * (unsigned)nstrips / gridDim.x)) : nstrips;              //  below 2^15 x 2^16)
+    const int rstep = multi ? 1 : (int)gridDim.x;
+    int seg0 = run0;
+    do {
+    const int st = multi ? __builtin_amdgcn_readfirstlane(seg0 / per_stage) : 0;   // (division runs on the vector pipe: kernels.h, stage_of)
+    const int seg1 = multi ? min(run1, (st + 1) * per_stage) : run1;
+    Ffn1Args a1 = a1_;
+    Ffn2Args a2 = a2_;
+    const u32x4_t* __restrict__ wsp = wsp_ + st * (sg.ws_stride / (long)sizeof(u32x4_t));
+    {
+        const long po = st * sg.pstride;
+        a1.ln2g += po; a1.ln2b += po; a1.b1 += po; a1.b2 += po;
+        a2.dww += po; a2.dwb += po; a2.b3 += po;
+        if (a2.g) { a2.n1g += po; a2.n1b += po; }
+        if (NP == 2) a1.scales += st * sg.fs_stride;
+    }
+    if (seg0 != run0) __syncthreads();   // every wave is done with the previous stage's tables
     for (int i = threadIdx.x; i < E; i += 512) {
         sLn2g[i] = a1.ln2g[i]; sLn2b[i] = a1.ln2b[i]; sB3[i] = a2.b3[i];
         sN1g[i] = a2.g ? a2.n1g[i] : 0.f; sN1b[i] = a2.g ? a2.n1b[i] : 0.f;
@@ -112,7 +136,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     constexpr bool BF = (NP == 1);                    // plain-bf16 mode: saved activations stored as bf16 (hstore.h)
     // NP = 2 (f16 pairs): the operand scales of k_ffn_prep.hip and how they leave again -- k_ffn_x.hip has the scheme
     float sx = 1.f, sa1 = 1.f, sa3 = 1.f, sw1 = 1.f, sw2 = 1.f, sw3 = 1.f;
-    if (NP == 2) { sx = a1.scales[0]; sa1 = a1.scales[1]; sa3 = a1.scales[2]; sw1 = a1.scales[3]; sw2 = a1.scales[4]; sw3 = a1.scales[5]; }
+    if (NP == 2) { sx = uniform_f(a1.scales[0]); sa1 = uniform_f(a1.scales[1]); sa3 = uniform_f(a1.scales[2]); sw1 = uniform_f(a1.scales[3]); sw2 = uniform_f(a1.scales[4]); sw3 = uniform_f(a1.scales[5]); }
     const float S1 = sx * sw1, S2 = sa1 * sw2, S3 = sa3 * sw3;
     const float inv1 = 1.0f / S1, g1c = 0.70710678118654752440f / S1, g1h = 0.5f * sa1 / S1, g3h = 0.5f * sa3, inv2 = 1.0f / S2, inv3 = 1.0f / S3;   // (powers of two: exact)
     const int c0 = wave * 16 + 4 * g;                 // first of the four h1 / h2 channels this lane holds after GEMM1 / GEMM2
@@ -134,7 +158,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (NP == 2) { lng = make_float4(lng.x * sx, lng.y * sx, lng.z * sx, lng.w * sx); lnb = make_float4(lnb.x * sx, lnb.y * sx, lnb.z * sx, lnb.w * sx); }
 
 #pragma unroll 1
-    for (int strip = blockIdx.x; strip < nstrips; strip += gridDim.x) {
+    for (int strip = seg0; strip < seg1; strip += rstep) {
     int t = strip;
     const int tx_i = t % tiles_x;
     t /= tiles_x;
@@ -475,7 +499,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
     }
     }   // steps of the strip
-    }   // strips of this workgroup
+    }   // strips of this segment
+    seg0 = seg1;
+    } while (MULTI && seg0 < run1);   // segments (stages) of this workgroup
 }
 
 }   // namespace
@@ -515,7 +541,7 @@ int launch_split_w_jobs(int n, const SplitWJob* jobs, hipStream_t s) {
 }
 
 int launch_ffn_x32(const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s) {
-    ProfScope prof__(LG_K_FFN2, s);
+    ProfScope prof__(LG_K_FFN2, s, a1.sg.n);
     if (!a1.wsplit) { lg_set_error("ffn_x32: no weight-fragment scratch in the workspace"); return -3; }
     static DeviceOnce attr_once;
     if (attr_once.need()) {
@@ -528,29 +554,38 @@ int launch_ffn_x32(const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s) {
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_x32<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_x32<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_x32<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_x32<0, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_x32<0, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
         if (e != hipSuccess) { lg_set_error("ffn_x32: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
         attr_once.done();
     }
+    const bool multi = a1.sg.n > 1;
+    if (multi && (a1.h2 || (!a1.scales && !a1.hbf) || !a1.wsplit_ready || a1.sg.Bs <= 0 || a2.B != a1.sg.n * a1.sg.Bs)) { lg_set_error("ffn_x32: several stages need pre-split fragments and B = stages x samples"); return -2; }
     if (!a1.wsplit_ready) {
         const int rc = launch_split_w(a1.w1, a1.w2, a2.w3, a1.wsplit, E, a1.hbf ? 1 : (a1.scales ? 2 : 3), s, a1.scales);
         if (rc) return rc;
     }
     const int tiles_x = (a2.w + 15) / 16;
     // strip height: the tallest multiple of 8 rows that still yields >= 256 strips (one resident workgroup per CU), at least 16
+    // (several stages in the launch: the strip height of ONE stage's launch)
+    const int Bsh = multi ? a1.sg.Bs : a2.B;
     int SH = (a2.h + 7) / 8 * 8;
-    while (SH > 16 && (long)a2.B * tiles_x * ((a2.h + SH - 1) / SH) < 256) SH = (SH / 2 + 7) / 8 * 8;
+    while (SH > 16 && (long)Bsh * tiles_x * ((a2.h + SH - 1) / SH) < 256) SH = (SH / 2 + 7) / 8 * 8;
     const int strips_y = (a2.h + SH - 1) / SH;
     const int nstrips = a2.B * tiles_x * strips_y;
-    const int grid = nstrips < 256 ? nstrips : 256;
+    int grid = nstrips < 256 ? nstrips : 256;
+    if (multi && a1.sg.grid_cap > 0 && grid > a1.sg.grid_cap) grid = a1.sg.grid_cap;
     const u32x4_t* wsp = reinterpret_cast<const u32x4_t*>(a1.wsplit);
     const bool save = a1.h2 != nullptr;           // h2 leaves the chip only for the backward
     if (a1.hbf) {   // precision = 'bf16'
         if (save && !a1.a1s) k_ffn_x32<2, 1><<<grid, 512, LDS_BYTES, s>>>(a1, a2, wsp, tiles_x, strips_y, nstrips, SH);
         else if (save) k_ffn_x32<1, 1><<<grid, 512, LDS_BYTES, s>>>(a1, a2, wsp, tiles_x, strips_y, nstrips, SH);
+        else if (multi) k_ffn_x32<0, 1, true><<<grid, 512, LDS_BYTES, s>>>(a1, a2, wsp, tiles_x, strips_y, nstrips, SH);
         else k_ffn_x32<0, 1><<<grid, 512, LDS_BYTES, s>>>(a1, a2, wsp, tiles_x, strips_y, nstrips, SH);
     } else if (a1.scales) {   // f16 pairs (three products per block instead of six)
         if (save && !a1.a1s) k_ffn_x32<2, 2><<<grid, 512, LDS_BYTES, s>>>(a1, a2, wsp, tiles_x, strips_y, nstrips, SH);
         else if (save) k_ffn_x32<1, 2><<<grid, 512, LDS_BYTES, s>>>(a1, a2, wsp, tiles_x, strips_y, nstrips, SH);
+        else if (multi) k_ffn_x32<0, 2, true><<<grid, 512, LDS_BYTES, s>>>(a1, a2, wsp, tiles_x, strips_y, nstrips, SH);
         else k_ffn_x32<0, 2><<<grid, 512, LDS_BYTES, s>>>(a1, a2, wsp, tiles_x, strips_y, nstrips, SH);
     } else if (save && !a1.a1s) k_ffn_x32<2, 3><<<grid, 512, LDS_BYTES, s>>>(a1, a2, wsp, tiles_x, strips_y, nstrips, SH);
     else if (save) k_ffn_x32<1, 3><<<grid, 512, LDS_BYTES, s>>>(a1, a2, wsp, tiles_x, strips_y, nstrips, SH);

@@ -154,8 +154,10 @@ __device__ __forceinline__ lg_v2f geluN(lg_v2f x, const GK& k) {
 }  // namespace xr
 
 // SAVE: 0 nothing; 3 the pre-activations h2 and h3 (the backward re-computes h1 from x: k_ffn1_bwd_xs) -- the two modes of the default path
-template <int SAVE, int NP>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_ffn_xr(Ffn1Args a1, Ffn2Args a2, int tiles_x, int strips_y, int nstrips,
+// MULTI: the launch covers the samples of several stages (kernels.h: StageSel); false: the segment loop below is ONE straight pass and the kernel the
+// one-stage kernel it always was.
+template <int SAVE, int NP, bool MULTI = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_ffn_xr(Ffn1Args a1_, Ffn2Args a2_, int tiles_x, int strips_y, int nstrips,
                                                                                        int SH, int dS) {
     using namespace xr;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -174,11 +176,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
         if (lane == 0) old_ = atomicXor(&g_xr_turn[key & 8191u], 1u);
         slot_par = (unsigned)__builtin_amdgcn_readfirstlane((int)old_) & 1u;
     }
-    const int h = a2.h, w = a2.w;
+    const int h = a2_.h, w = a2_.w;
+    // The workgroup's strips.  One stage in the launch: strips blockIdx.x, + gridDim.x, ... and ONE pass of the segment loop below.  Several stages
+    // (kernels.h: StageSel; strips ascend with the sample, so a stage is a contiguous range of them): a contiguous run of strips, cut into one segment
+    // per stage -- at a stage boundary the tables are staged again, behind a barrier, from that stage's weights (at 3 x 32 pairs two workgroups of 512).
+    const StageSel sg = a1_.sg;
+    constexpr bool multi = MULTI;
+    const int per_stage = multi ? sg.Bs * tiles_x * strips_y : nstrips;
+    const int run0 = multi ? __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (unsigned)nstrips / gridDim.x)) : (int)blockIdx.x;          // (grid x strips < 2^31: both are
+    const int run1 = multi ? __builtin_amdgcn_readfirstlane((int)((blockIdx.x + 1) * (unsigned)nstrips / gridDim.x)) : nstrips;              //  below 2^15 x 2^16)
+    const int rstep = multi ? 1 : (int)gridDim.x;
+    int seg0 = run0;
+    do {
+    const int st = multi ? __builtin_amdgcn_readfirstlane(seg0 / per_stage) : 0;   // (division runs on the vector pipe: kernels.h, stage_of)
+    const int seg1 = multi ? min(run1, (st + 1) * per_stage) : run1;
+    Ffn1Args a1 = a1_;
+    Ffn2Args a2 = a2_;
+    {
+        const long po = st * sg.pstride;
+        a1.ln2g += po; a1.ln2b += po; a1.w1 += po; a1.b1 += po; a1.w2 += po; a1.b2 += po;
+        a2.dww += po; a2.dwb += po; a2.w3 += po; a2.b3 += po;
+        if (a2.g) { a2.n1g += po; a2.n1b += po; }
+        if (NP == 2) a1.scales += st * sg.fs_stride;
+    }
+    if (seg0 != run0) __syncthreads();   // every wave is done with the previous stage's tables
     // operand scales (k_ffn_prep.hip; k_ffn_x.hip has the derivation): S1 h1, S2 h2, S3 (...) in the accumulators
     constexpr bool BF = NP == 1;
     float sx = 1.f, sa1 = 1.f, sa3 = 1.f, sw1 = 1.f, sw2 = 1.f, sw3 = 1.f;
-    if (NP == 2) { sx = a1.scales[0]; sa1 = a1.scales[1]; sa3 = a1.scales[2]; sw1 = a1.scales[3]; sw2 = a1.scales[4]; sw3 = a1.scales[5]; }
+    if (NP == 2) { sx = uniform_f(a1.scales[0]); sa1 = uniform_f(a1.scales[1]); sa3 = uniform_f(a1.scales[2]); sw1 = uniform_f(a1.scales[3]); sw2 = uniform_f(a1.scales[4]); sw3 = uniform_f(a1.scales[5]); }
     const float S1 = sx * sw1, S2 = sa1 * sw2, S3 = sa3 * sw3;
     const float inv2 = 1.0f / S2, inv3 = 1.0f / S3;   // (powers of two: exact)
 #ifdef LG_XR_OLDGELU   // A/B build: rounds 2 - 5's GELU sequence (common.h gelu2_scaled)
@@ -218,7 +243,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     {
         int tx_i, Y0f, Yendf;
         long b;
-        strip_geo(blockIdx.x, tx_i, b, Y0f, Yendf);
+        strip_geo(seg0, tx_i, b, Y0f, Yendf);
         const int m = 16 * (wave < 3 ? wave : 0) + c, hy = m / HX, hx = m - hy * HX;
         const int y = clampi(Y0f - 1 + hy, 0, h - 1), x = clampi(tx_i * TX + hx - 1, 0, w - 1);
         xp_first = *reinterpret_cast<const float4*>(a1.x + ((b * h + y) * (long)w + x) * E + 4 * g);
@@ -226,7 +251,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     // ---- once per (persistent) workgroup: weight fragments, taps, biases
     float4 lng, lnb;
     {
-        const int t = threadIdx.x, ln = t >> 2, i = t & 3, lg = ln >> 4, lr = ln & 15;
+        int t = threadIdx.x;
+        if (MULTI) asm volatile("" : "+v"(t));   // (the staging addresses are formed again per segment: hoisted out of the segment loop they would hold ~30 registers for the whole kernel)
+        const int ln = t >> 2, i = t & 3, lg = ln >> 4, lr = ln & 15;
         // every value is requested before the first store
         // taps, biases, LayerNorm affines: requested with the weights, from clamped indices (as a `for (k = t; ...; k += 256)` loop and two `if (t < n)`
         // blocks this was five further dependent round trips: 5 k of a launch's ~ 160 k cycles went to the staging)
@@ -296,7 +323,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     XSTAMP_AT(9, 1);
 
 #pragma unroll 1
-    for (int strip = blockIdx.x; strip < nstrips; strip += gridDim.x) {
+    for (int strip = seg0; strip < seg1; strip += rstep) {
         int tx_i, Y0, Yend;
         long b;
         strip_geo(strip, tx_i, b, Y0, Yend);
@@ -575,7 +602,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
         // front of the table staging) and the first step's are in flight before anything is computed
         float4 xh[3];
         {
-            const float4 xp = strip == (int)blockIdx.x ? xp_first : xload(Y0 - 1, wave < 3 ? wave : 0);
+            const float4 xp = strip == seg0 ? xp_first : xload(Y0 - 1, wave < 3 ? wave : 0);
             xh[0] = xload(Y0 + 1, 2 * wave); xh[1] = xload(Y0 + 1, 2 * wave + 1); xh[2] = xload(Y0 + 1, 8);
             __syncthreads();     // the previous strip's spatial phase is done with the ring
             if (uwave < 3) halo(IC<1>{}, IC<0>{}, Y0 - 1, 2 * HX, wave, &xp, nullptr, nullptr);
@@ -736,18 +763,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
             XR_TAKE_TURNS();
             XSTAMP(5);
         }   // steps of the strip
-    }   // strips of this workgroup
+    }   // strips of this segment
+    seg0 = seg1;
+    } while (MULTI && seg0 < run1);   // segments (stages) of this workgroup
 }
 
 int launch_ffn_xr(const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s) {
     using namespace xr;
-    ProfScope prof__(LG_K_FFN2, s);
+    ProfScope prof__(LG_K_FFN2, s, a1.sg.n);
     static DeviceOnce attr_once;
     if (attr_once.need()) {
         hipError_t e = hipFuncSetAttribute((const void*)k_ffn_xr<0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_xr<3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_xr<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_xr<3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_xr<0, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_xr<0, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
         if (e != hipSuccess) { lg_set_error("ffn_xr: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
         attr_once.done();
     }
@@ -757,18 +788,25 @@ int launch_ffn_xr(const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s) {
     if ((long)a2.B * a2.h * a2.w * N1 >= (1ll << 32)) { lg_set_error("ffn_xr: hidden tensor of %ld elements exceeds the 32-bit save index", (long)a2.B * a2.h * a2.w * N1); return -2; }
     const int tiles_x = (a2.w + 15) / 16;
     // strip height: the tallest multiple of 8 rows that still yields >= 512 strips (two resident workgroups per CU), at least 16
+    // (several stages in the launch: the strip height of ONE stage's launch, so that a workgroup gets whole strips of that size -- three at 3 x 32 pairs)
+    const bool multi = a1.sg.n > 1;
+    const int Bsh = multi ? a1.sg.Bs : a2.B;
+    if (multi && (save || a1.sg.Bs <= 0 || a2.B != a1.sg.n * a1.sg.Bs)) { lg_set_error("ffn_xr: B = %d is not %d stages of %d samples", a2.B, a1.sg.n, a1.sg.Bs); return -2; }
     int SH = (a2.h + 7) / 8 * 8;
-    while (SH > 16 && (long)a2.B * tiles_x * ((a2.h + SH - 1) / SH) < LG_XR_GRID) SH = (SH / 2 + 7) / 8 * 8;
+    while (SH > 16 && (long)Bsh * tiles_x * ((a2.h + SH - 1) / SH) < LG_XR_GRID) SH = (SH / 2 + 7) / 8 * 8;
     const int strips_y = (a2.h + SH - 1) / SH;
     const int nstrips = a2.B * tiles_x * strips_y;
-    const int grid = nstrips < LG_XR_GRID ? nstrips : LG_XR_GRID;
+    int grid = nstrips < LG_XR_GRID ? nstrips : LG_XR_GRID;
+    if (multi && a1.sg.grid_cap > 0 && grid > a1.sg.grid_cap) grid = a1.sg.grid_cap;
     // uneven split of strip pairs (strip_geo in the kernel): only in the shape it was measured in -- one strip per workgroup, exactly two workgroups per CU
     int dS = 0;
-    if (LG_XR_UNEVEN && nstrips == LG_XR_GRID && LG_XR_GRID == 512 && (strips_y & 1) == 0 && SH >= 32 && a2.h % (2 * SH) == 0) dS = (SH * LG_XR_UNEVEN / 64 + 7) / 8 * 8;
+    if (!multi && LG_XR_UNEVEN && nstrips == LG_XR_GRID && LG_XR_GRID == 512 && (strips_y & 1) == 0 && SH >= 32 && a2.h % (2 * SH) == 0) dS = (SH * LG_XR_UNEVEN / 64 + 7) / 8 * 8;
     if (a1.hbf) {    // precision = 'bf16'
         if (save) k_ffn_xr<3, 1><<<grid, 256, LDS_BYTES, s>>>(a1, a2, tiles_x, strips_y, nstrips, SH, dS);
+        else if (multi) k_ffn_xr<0, 1, true><<<grid, 256, LDS_BYTES, s>>>(a1, a2, tiles_x, strips_y, nstrips, SH, dS);
         else k_ffn_xr<0, 1><<<grid, 256, LDS_BYTES, s>>>(a1, a2, tiles_x, strips_y, nstrips, SH, dS);
     } else if (save) k_ffn_xr<3, 2><<<grid, 256, LDS_BYTES, s>>>(a1, a2, tiles_x, strips_y, nstrips, SH, dS);
+    else if (multi) k_ffn_xr<0, 2, true><<<grid, 256, LDS_BYTES, s>>>(a1, a2, tiles_x, strips_y, nstrips, SH, dS);
     else k_ffn_xr<0, 2><<<grid, 256, LDS_BYTES, s>>>(a1, a2, tiles_x, strips_y, nstrips, SH, dS);
     LG_CHECK_LAUNCH();
     return 0;

@@ -511,7 +511,8 @@ __global__ void __launch_bounds__(NTH, (LG >= 7 && NTH == 512) ? 4 : 1) k_fftmix
     __syncthreads();
     FFT_STAMP(3);
     // ---- amplitude / phase edit (LGT.py:168-177)
-    const float aw = a.ampw[ch], ab = a.ampb[ch], pw = a.phaw[ch], pb = a.phab[ch];
+    const long po = stage_of_unit(a.sg, plane, a.ch) * a.sg.pstride + ch;   // several stages in one launch (kernels.h: StageSel): sample = plane / ch
+    const float aw = a.ampw[po], ab = a.ampb[po], pw = a.phaw[po], pb = a.phab[po];
     for (int it = threadIdx.x; it < n * (half + 1); it += NTH) {
         int q, c;
         fftr_bin(it, n, lg, q, c);
@@ -1079,8 +1080,9 @@ static int launch_fft_generic(const FftArgs* fa, const FftBwdArgs* ba, int h, in
 }
 
 int launch_fftmix(const FftArgs& a, hipStream_t s) {
-    ProfScope prof__(LG_K_FFT, s);
+    ProfScope prof__(LG_K_FFT, s, a.sg.n);
     const int ph = a.h ? a.h : a.n, pw = a.w ? a.w : a.n;
+    if (a.sg.n > 1 && (a.full || fft_is_generic(ph, pw) || ph > 128)) { lg_set_error("fftmix: only the real-input in-LDS kernel takes several stages in one launch"); return -2; }
     if (fft_is_generic(ph, pw)) return launch_fft_generic(&a, nullptr, ph, pw, s);
     int n = ph, lg = 0;
     while ((1 << lg) < n) ++lg;

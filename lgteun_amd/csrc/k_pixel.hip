@@ -162,6 +162,12 @@ __global__ __launch_bounds__(256) void k_embed(EmbedArgs a) {
     long p = blockIdx.x * 256L + threadIdx.x;
     if (p >= a.total) return;
     long b = p / a.HW, s = p - b * a.HW;
+    {   // several stages in one launch (kernels.h: StageSel): the workgroup's pixels belong to ONE sample (HW is a multiple of 256), so the shift is uniform
+        const int st = stage_of_unit(a.sg, (int)blockIdx.x, a.HW >> 8);
+        const long po = st * a.sg.pstride;
+        a.dww += po; a.dwb += po; a.w += po; a.b += po; a.lng += po; a.lnb += po; a.n1g += po; a.n1b += po;
+        a.z += st * (a.sg.zstride - (long)a.sg.Bs * C * a.HW);
+    }
     float t[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) t[c] = a.z[(b * C + c) * a.HW + s] * a.dww[c] + a.dwb[c];
@@ -208,7 +214,8 @@ __global__ __launch_bounds__(256) void k_embed(EmbedArgs a) {
 }
 
 int launch_embed(int C, const EmbedArgs& a, hipStream_t s) {
-    ProfScope prof__(LG_K_EMBED, s);
+    ProfScope prof__(LG_K_EMBED, s, a.sg.n);
+    if (a.sg.n > 1 && a.HW % 256) { lg_set_error("embed: a workgroup's pixels would straddle the stages of the launch"); return -2; }
     int grid = (int)((a.total + 255) / 256);
     if (C == 4) k_embed<4, 16><<<grid, 256, 0, s>>>(a);
     else if (C == 8) k_embed<8, 32><<<grid, 256, 0, s>>>(a);
@@ -231,6 +238,10 @@ __global__ __launch_bounds__(256) void k_down(DownArgs a) {
     __shared__ __attribute__((aligned(16))) float sW[2 * E * E];   // [k][n]
     __shared__ float sB[2 * E], sNg[2 * E], sNb[2 * E];
     __shared__ __attribute__((aligned(16))) float ux[PPW * LDU];
+    {   // several stages in one launch (kernels.h: StageSel): the workgroup's PPW pixels belong to one sample (the launcher checks it)
+        const long po = stage_of_unit(a.sg, (int)blockIdx.x, (a.H / 2) * (a.W / 2) / PPW) * a.sg.pstride;
+        a.w += po; a.b += po; a.n1g += po; a.n1b += po;
+    }
     {   // all four arrays requested before the first store (common.h: lds_stage_ld / _st); absent LayerNorm vectors: a valid dummy source
         float vw[(2 * E * E + 255) / 256], vb[1], vg[1], vn[1];
         lds_stage_ld<256, 2 * E * E>(vw, a.w);
@@ -325,9 +336,10 @@ __global__ __launch_bounds__(256) void k_down(DownArgs a) {
 }
 
 int launch_down(int E, const DownArgs& a, hipStream_t s) {
-    ProfScope prof__(LG_K_DOWN, s);
+    ProfScope prof__(LG_K_DOWN, s, a.sg.n);
     const long total = (long)a.B * (a.H / 2) * (a.W / 2);
     const int ppw = 256 / (E / 4);
+    if (a.sg.n > 1 && ((long)(a.H / 2) * (a.W / 2)) % ppw) { lg_set_error("down: a workgroup's pixels would straddle the stages of the launch"); return -2; }
     int grid = (int)((total + ppw - 1) / ppw);
     if (E == 16) k_down<16><<<grid, 256, 0, s>>>(a);
     else if (E == 32) k_down<32><<<grid, 256, 0, s>>>(a);
@@ -369,6 +381,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E == 16 ? 4
     t /= tiles_x;
     const int ty_i = t % tiles_y;
     const long b = t / tiles_y;
+    {   // several stages in one launch (kernels.h: StageSel)
+        const long po = stage_of_unit(a.sg, (int)blockIdx.x, tiles_x * tiles_y) * a.sg.pstride;
+        a.upw += po; a.upb += po; a.fw += po; a.fb += po; a.n1g += po; a.n1b += po;
+    }
     const int Y0 = ty_i * TY, X0 = tx_i * TX;
     const int sy0 = Y0 / 2 - 2, sx0 = X0 / 2 - 2;
     // The up-path 1x1 conv (2E -> E on the NS source pixels) runs on the matrix cores (round 6): out[px][n] = sum_k src[px][k] Wu[n][k] as
@@ -601,7 +617,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E == 16 ? 4
 }
 
 int launch_upfuse(int E, const UpFuseArgs& a, hipStream_t s) {
-    ProfScope prof__(LG_K_UPFUSE, s);
+    ProfScope prof__(LG_K_UPFUSE, s, a.sg.n);
     if ((a.H & 1) || (a.W & 1)) { lg_set_error("upfuse: H, W must be even"); return -2; }
     const int tiles_x = (a.W + 31) / 32, tiles_y = (a.H + 7) / 8;
     const int grid = a.B * tiles_x * tiles_y;
@@ -624,6 +640,12 @@ __global__ __launch_bounds__(256) void k_tail(TailArgs a) {
     const long pr = blockIdx.x * 256L + threadIdx.x;
     const long p = pr < a.total ? pr : a.total - 1;
     const long b = p / a.HW, s = p - b * a.HW;
+    {   // several stages in one launch (kernels.h: StageSel): HW is a multiple of 256, one sample per workgroup
+        const int st = stage_of_unit(a.sg, (int)blockIdx.x, a.HW >> 8);
+        const long po = st * a.sg.pstride;
+        a.w += po; a.b += po;
+        a.z += st * (a.sg.zstride - (long)a.sg.Bs * C * a.HW);
+    }
     float4 xv[E / 4];
     float zv[C];
     {
@@ -653,7 +675,8 @@ __global__ __launch_bounds__(256) void k_tail(TailArgs a) {
 }
 
 int launch_tail(int C, const TailArgs& a, hipStream_t s) {
-    ProfScope prof__(LG_K_TAIL, s);
+    ProfScope prof__(LG_K_TAIL, s, a.sg.n);
+    if (a.sg.n > 1 && a.HW % 256) { lg_set_error("tail: a workgroup's pixels would straddle the stages of the launch"); return -2; }
     int grid = (int)((a.total + 255) / 256);
     if (C == 4) k_tail<4, 16><<<grid, 256, 0, s>>>(a);
     else if (C == 8) k_tail<8, 32><<<grid, 256, 0, s>>>(a);

@@ -63,6 +63,31 @@ struct DstepFwdArgs {
 bool dstep_fused_ok(int C, int H, int W);
 int launch_dstep_fwd(const DstepFwdArgs& a, hipStream_t s);
 
+// ---------------- several stages in one launch (the dead-stage LGT forwards of a faithful step, api.hip: lgt_fwd) ----------------
+// A forward kernel of the LGT sees a plain batch of n * Bs samples; sample b belongs to stage b / Bs, and a workgroup moves its weight, scale and
+// table pointers by (b / Bs) x the stage strides before it stages anything.  The K LGTs have identical shapes, so every tensor of the flat
+// parameter buffer has the SAME stride from one stage to the next (lg_plan::stage_stride).  n <= 1: one stage, every shift is zero.
+struct StageSel {
+    int n = 1;           // stages in the launch
+    int Bs = 0;          // samples per stage
+    long pstride = 0;    // floats between a parameter tensor of stage s and the same tensor of stage s + 1
+    long zstride = 0;    // floats between the LGT inputs z of two consecutive stages
+    int fs_stride = 0;   // floats between the stages' rows of ffn_scales
+    int as_stride = 0;   // ... of attn_scales
+    long ws_stride = 0;  // bytes between the stages' rows of wsplit
+    int grid_cap = 0;    // test entry (lg_op_lgt_stages): upper bound of a persistent kernel's grid, 0 = none
+    // dropout: the mask of stage s is keyed by mix_seed(seed, stage0 + s, blk) and counts its elements from the start of the stage's own tensor
+    uint64_t seed = 0;
+    int stage0 = 0, blk = 0;
+};
+#ifdef __HIPCC__
+// stage of sample b (workgroup-uniform).  Integer division runs on the vector pipe, so its result is moved to a scalar register: left in a vector
+// register it would drag every shifted pointer, and every load through one, onto the vector side.
+__device__ __forceinline__ int stage_of(const StageSel& sg, int b) { return sg.n > 1 ? __builtin_amdgcn_readfirstlane(b / sg.Bs) : 0; }
+// ... of the workgroup, where a sample is `per_sample` consecutive workgroups (or other units) and `unit` this workgroup's
+__device__ __forceinline__ int stage_of_unit(const StageSel& sg, int unit, int per_sample) { return sg.n > 1 ? __builtin_amdgcn_readfirstlane(unit / (per_sample * sg.Bs)) : 0; }
+#endif
+
 // ---------------- LGT pixelwise pieces (reference models/common/LGT.py) ----------------
 struct EmbedArgs {
     const float* z;  // [B,C,H,W]
@@ -71,6 +96,7 @@ struct EmbedArgs {
     const float *dww, *dwb, *w, *b, *lng, *lnb, *n1g, *n1b;
     int HW;
     long total;  // B*H*W
+    StageSel sg;
 };
 int launch_embed(int C, const EmbedArgs& a, hipStream_t s);
 
@@ -81,6 +107,7 @@ struct DownArgs {
     float* u_save;   // optional [B,H/2,W/2,E]: the resampled conv input (for the weight gradient)
     const float *w, *b, *n1g, *n1b;
     int B, H, W;  // input size
+    StageSel sg;
 };
 int launch_down(int E, const DownArgs& a, hipStream_t s);
 
@@ -92,6 +119,7 @@ struct UpFuseArgs {
     float* t_save;      // optional [B,H,W,E]: up-path tensor after its 1x1 conv (for the weight gradient)
     const float *upw, *upb, *fw, *fb, *n1g, *n1b;
     int B, H, W;  // output size
+    StageSel sg;
 };
 int launch_upfuse(int E, const UpFuseArgs& a, hipStream_t s);
 
@@ -102,6 +130,7 @@ struct TailArgs {
     const float *w, *b;
     int HW;
     long total;
+    StageSel sg;
 };
 int launch_tail(int C, const TailArgs& a, hipStream_t s);
 
@@ -117,6 +146,7 @@ struct FftArgs {
     int planes, ch, n;   // n: side of a square plane (legacy callers); h, w (when non-zero) override it
     int h, w;
     int full = 0;      // 1: the complex-row in-LDS kernels (A/B variant LG_VAR_FFT_FULL); 0: the real-input kernels (k_fftmix_r / k_fftmix_bwd_r)
+    StageSel sg;       // k_fftmix_r only
 };
 int launch_fftmix(const FftArgs& a, hipStream_t s);
 size_t fft_scratch_floats(int planes, int n);
@@ -138,6 +168,7 @@ struct AttnArgs {
     float* save_o = nullptr;         // k_attn_m, e = 16, saving launch (round 6): [P,e/2] attention output before proj (head-major = the local half of cat) and
     float* save_l = nullptr;         // [P,2] log2-domain log-sum-exp of the score rows, for k_attn_bwd_f (which then skips its reduction pass); null: not written
     const float* scales = nullptr;   // k_attn_m: this block's static operand scales { s_y, s_w, s_q, s_k } (k_ffn_prep.hip, round 6): to_qkv and Q K^T on f16 pairs; nullptr: bf16 triples
+    StageSel sg;                     // k_attn_m only
 };
 int launch_attn(int e, const AttnArgs& a, hipStream_t s);     // round 2's kernel: lane = token, every product on the vector pipe (LG_VAR_ATTN_FWD_VALU)
 int launch_attn_m(int e, const AttnArgs& a, hipStream_t s);   // round 5: every product on the matrix pipe (k_attn_m.hip)
@@ -159,6 +190,7 @@ struct Ffn1Args {
     int wsplit_ready = 0;   // 1: the fragments are in `wsplit` already (prep launch of the forward call: launch_split_w_jobs); 0: the launcher splits in front of its kernel
     const float* scales;   // this block's operand scales { s_x, s_a1, s_a3, s_w1, s_w2, s_w3 } (k_ffn_prep.hip): the f16-pair arithmetic (NP = 2) of the
                            // fused forward kernels; nullptr = the three-piece bf16 arithmetic (NP = 3)
+    StageSel sg;           // k_ffn_xr / k_ffn_x32 only (covers the Ffn2Args of the same launch too)
 };
 // operand scales of the f16-pair FFN arithmetic: one job per block, all in one launch (k_ffn_prep.hip); out[job][8]
 struct FfnPrepJob { const float *ln2g, *ln2b, *w1, *b1, *w2, *b2, *dww, *dwb, *w3; int e; const float *ln1g, *ln1b, *qkvw, *qkvb; };   // ln1 / qkv: the local mixer's static scales (attn_out)

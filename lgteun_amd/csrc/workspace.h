@@ -65,6 +65,10 @@ static inline void carve(const lg_plan* plan, int B, int train, void* base, NetB
     const lg_config& c = plan->cfg;
     Carver cv{reinterpret_cast<char*>(base), 0};
     const size_t P0 = (size_t)c.H * c.W, P1 = P0 / 4, E = 4 * (size_t)c.C;
+    // A plan whose dead stages run as one pass (lg_plan::stage_batch: K-1 >= 2 of them) carves the TRANSIENT forward buffers -- what a non-saving
+    // LGT forward writes -- for S = K-1 stages of B samples: stage s's part follows stage s-1's, so a kernel sees a plain batch of S B samples.  The live
+    // stage uses the first B samples' worth.  Saved tensors, the data steps' buffers and every other plan (K = 2 among them) are unchanged.
+    const size_t BT = (size_t)B * ((plan->stage_batch && train != 2) ? c.K - 1 : 1);
     for (int i = 0; i <= c.K; ++i) nb.Z[i] = cv.take(B * c.C * P0);
     for (int i = 0; i < c.K; ++i) {
         nb.t1[i] = cv.take(B * c.C * P1);
@@ -76,7 +80,7 @@ static inline void carve(const lg_plan* plan, int B, int train, void* base, NetB
     nb.ffn_scales = cv.take((size_t)c.K * 5 * 8);
     nb.attn_scales = cv.take((size_t)c.K * 5 * 4);
     nb.wsplit = cv.take((size_t)c.K * 5 * (ffn_wsplit_bytes((int)(2 * E)) / sizeof(float)));   // [K][5] slots sized for the widest block (level 1: e = 8 C): written once per forward call (prep_stages)
-    nb.deadout = cv.take(B * c.C * P0);
+    nb.deadout = cv.take(BT * c.C * P0);
     nb.X[0] = nb.Z[0];
     for (int i = 1; i < c.K; ++i) nb.X[i] = (train == 2) ? cv.take(B * c.C * P0) : nb.deadout;
     float* shared_h2 = nullptr;
@@ -90,10 +94,10 @@ static inline void carve(const lg_plan* plan, int B, int train, void* base, NetB
         bb.w = l1 ? c.W / 2 : c.W;
         const size_t P = l1 ? P1 : P0, e = bb.e;
         bb.xin = nullptr;  // wired below
-        bb.xmid = cv.take(B * P * e);
-        bb.xout = cv.take(B * P * e);
-        bb.g = cv.take(B * P * e / 2);
-        bb.o2 = cv.take(B * P * e / 2);
+        bb.xmid = cv.take(BT * P * e);
+        bb.xout = cv.take(BT * P * e);
+        bb.g = cv.take(BT * P * e / 2);
+        bb.o2 = cv.take(BT * P * e / 2);
         if (train) {
             bb.amp = cv.take(B * (e / 2) * bb.h * (bb.w / 2 + 1));
             bb.pha = cv.take(B * (e / 2) * bb.h * (bb.w / 2 + 1));
@@ -111,11 +115,11 @@ static inline void carve(const lg_plan* plan, int B, int train, void* base, NetB
             bb.h2 = shared_h2;
         }
     }
-    nb.x0 = cv.take(B * P0 * E);
+    nb.x0 = cv.take(BT * P0 * E);
     nb.blk[0].xin = nb.x0;
     nb.blk[1].xin = nb.blk[0].xout;
-    nb.blk[2].xin = cv.take(B * P1 * 2 * E);  // down output
-    nb.blk[3].xin = cv.take(B * P0 * E);      // up+fusion output
+    nb.blk[2].xin = cv.take(BT * P1 * 2 * E);  // down output
+    nb.blk[3].xin = cv.take(BT * P0 * E);      // up+fusion output
     nb.blk[4].xin = nb.blk[3].xout;
     nb.u_down = train ? cv.take(B * P1 * E) : nullptr;
     nb.t_up = train ? cv.take(B * P0 * E) : nullptr;
@@ -123,7 +127,7 @@ static inline void carve(const lg_plan* plan, int B, int train, void* base, NetB
     if (train == 2) cv.off += (size_t)(c.K - 1) * nb.set_bytes;
     {
         // level 0: B * E/2 planes of H x W; level 1: B * E planes of H/2 x W/2 -- level 0's is the larger whenever both need one
-        const size_t f0 = fft_scratch_floats_hw((int)(B * (E / 2)), c.H, c.W), f1 = fft_scratch_floats_hw((int)(B * E), c.H / 2, c.W / 2);
+        const size_t f0 = fft_scratch_floats_hw((int)(BT * (E / 2)), c.H, c.W), f1 = fft_scratch_floats_hw((int)(BT * E), c.H / 2, c.W / 2);
         const size_t fl = f0 > f1 ? f0 : f1;
         nb.fft_scratch = fl ? cv.take(fl) : nullptr;
     }

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (LG_FLAG_BWD_DATA, LG_FLAG_BWD_LGT, LG_FLAG_CHAINED, LG_FLAG_DEFER_DEAD, LG_FLAG_DROPOUT, LG_FLAG_FAITHFUL, LG_FLAG_SAVE,
+from ._lib import (LG_FLAG_BWD_DATA, LG_FLAG_BWD_LGT, LG_FLAG_CHAINED, LG_FLAG_DEFER_DEAD, LG_FLAG_DROPOUT, LG_FLAG_FAITHFUL, LG_FLAG_SAVE, LG_FLAG_STAGEWISE,
                    LgConfig, check, variant_from_env)
 
 
@@ -166,6 +166,10 @@ class Engine:
         # small launches get in at kernel boundaries -- while the co-running launches stretch the fused FFN's measured duration by
         # 6 %, so the default keeps one stream and per-kernel numbers that mean what they say.
         self.overlap_dead = os.environ.get('LG_OVERLAP_DEAD', '0') == '1'
+        # 'faithful' mode with two or more dead stages: the library runs their LGT forwards as ONE pass over (K-1) B samples where the plan's
+        # kernels can (include/lgteun_hip.h: LG_FLAG_STAGEWISE).  dead_stagewise = True (LG_DEAD_STAGEWISE=1) sets the bit: one stage at a
+        # time, bitwise the same step -- the reference of the tests and the other leg of an A/B.
+        self.dead_stagewise = os.environ.get('LG_DEAD_STAGEWISE', '0') == '1'
         self.variant = None            # lg_config.variant of the plans: None = from the diagnostic LG_* environment variables (normally 0)
         self._side_stream = None
         self.world = 1
@@ -341,6 +345,8 @@ class Engine:
         if mode not in ('faithful', 'live', 'chained'):
             raise ValueError(f"mode must be 'faithful', 'live' or 'chained' (got {mode!r})")
         f = {'faithful': LG_FLAG_FAITHFUL, 'live': 0, 'chained': LG_FLAG_CHAINED}[mode]
+        if self.dead_stagewise:
+            f |= LG_FLAG_STAGEWISE
         if training:
             f |= LG_FLAG_DROPOUT
         return f
