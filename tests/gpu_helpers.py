@@ -34,6 +34,14 @@ def device_drop_masks(seed, dtype=torch.float64):
     return masks
 
 
+def make_ops(C, H, W, K=1, precision=None):
+    """Ops on a fresh module with the deterministic weights (a fresh module builds a fresh plan); precision: None or 'bf16'"""
+    net = make_module(C, K)
+    if precision is not None:
+        net.precision = precision
+    return Ops(net, H, W)
+
+
 GUARD = 1024        # floats of NaN band on each side of a guarded output (4 KiB: the output keeps its 16-byte alignment)
 
 
@@ -113,34 +121,71 @@ class Ops:
             assert_guards_intact(buf, 'lg_op_block')
         return y
 
-    def block_bwd(self, stage, blk, which, x, dy):
-        """returns (dx, flat_param_grads).  which 0: dy/dx planar [B,e/2,h,w]; 1,2: NHWC."""
+    def _grads(self, owned):
+        """the flat gradient buffer of a per-op backward.  owned=None: plain zeros.  owned=[names]: a guarded view whose owned tensors start at
+        zero and whose every other float (the 16-byte padding between tensors included) starts as a finite sentinel of tiny magnitude,
+        2^-100 x (1 + index mod 251): a stray store or a stray `+=` of anything non-zero changes its bits, where NaN would hide the `+=`"""
+        flat = self.eng.flat
+        if owned is None:
+            return None, torch.zeros_like(flat)
+        buf, grads = guarded_empty((flat.numel(),), flat.device)
+        sentinel = (torch.arange(flat.numel(), device=flat.device) % 251 + 1).float() * 2.0 ** -100
+        foreign = torch.ones(flat.numel(), dtype=torch.bool, device=flat.device)
+        for name in owned:
+            i = self.eng.names.index(name)
+            foreign[self.eng.offsets[i]:self.eng.offsets[i] + self.eng.params[i].numel()] = False
+        grads.copy_(torch.where(foreign, sentinel, torch.zeros_like(sentinel)))
+        return (buf, sentinel, foreign), grads
+
+    def _grads_intact(self, state, grads, what):
+        """behind the launch: every float that is not an owned tensor's is bitwise the sentinel, both bands of the buffer are NaN"""
+        if state is None:
+            return
+        buf, sentinel, foreign = state
+        assert_guards_intact(buf, what + ' (gradient buffer)')
+        moved = foreign & (grads.view(torch.int32) != sentinel.view(torch.int32))
+        if bool(moved.any()):
+            at = [int(i) for i in moved.nonzero().flatten()[:8]]
+            owners = sorted({self.eng.names[max(j for j, o in enumerate(self.eng.offsets) if o <= i)] for i in at})
+            assert False, (what, 'gradient floats that are not its own were written', int(moved.sum()), at, owners)
+
+    def block_bwd(self, stage, blk, which, x, dy, guard=False, owned=None):
+        """returns (dx, flat_param_grads).  which 0: dy/dx planar [B,e/2,h,w]; 1,2: NHWC.  guard / owned: see _out / _grads"""
         B = x.shape[0]
-        dx = torch.empty_like(dy)
-        grads = torch.zeros_like(self.eng.flat)
+        buf, dx = self._out(dy.shape, dy.device, guard)
+        state, grads = self._grads(owned)
         ws = self.ws(B, train=True)
         _lib.check(self.lib.lg_op_block_bwd(self.plan, _ptr(self.eng.flat), _ptr(grads), stage, blk, which, _ptr(x), _ptr(dy),
                                             _ptr(dx), _ptr(ws), ws.numel(), B, _stream_ptr()), 'lg_op_block_bwd')
+        if guard:
+            assert_guards_intact(buf, 'lg_op_block_bwd')
+        self._grads_intact(state, grads, 'lg_op_block_bwd')
         return dx, grads
 
-    def data_step_bwd(self, stage, z, ms, pan, dz_out):
+    def data_step_bwd(self, stage, z, ms, pan, dz_out, guard=False, owned=None):
         """returns (dz_in, flat_param_grads) of one data step"""
         B = z.shape[0]
-        dz = torch.empty_like(z)
-        grads = torch.zeros_like(self.eng.flat)
+        buf, dz = self._out(z.shape, z.device, guard)
+        state, grads = self._grads(owned)
         ws = self.ws(B, train=True)
         _lib.check(self.lib.lg_op_data_step_bwd(self.plan, _ptr(self.eng.flat), _ptr(grads), stage, _ptr(z), _ptr(ms), _ptr(pan),
                                                 _ptr(dz_out), _ptr(dz), _ptr(ws), ws.numel(), B, _stream_ptr()), 'lg_op_data_step_bwd')
+        if guard:
+            assert_guards_intact(buf, 'lg_op_data_step_bwd')
+        self._grads_intact(state, grads, 'lg_op_data_step_bwd')
         return dz, grads
 
-    def lgt_bwd(self, stage, z, dout, flags=0, seed=0):
+    def lgt_bwd(self, stage, z, dout, flags=0, seed=0, guard=False, owned=None):
         """returns (dz, flat_param_grads) of one LGT; flags: 0 or LG_FLAG_DROPOUT (with seed)"""
         B = z.shape[0]
-        dz = torch.empty_like(z)
-        grads = torch.zeros_like(self.eng.flat)
+        buf, dz = self._out(z.shape, z.device, guard)
+        state, grads = self._grads(owned)
         ws = self.ws(B, train=True)
         _lib.check(self.lib.lg_op_lgt_bwd(self.plan, _ptr(self.eng.flat), _ptr(grads), stage, _ptr(z), _ptr(dout), _ptr(dz), _ptr(ws),
                                           ws.numel(), B, flags, seed, _stream_ptr()), 'lg_op_lgt_bwd')
+        if guard:
+            assert_guards_intact(buf, 'lg_op_lgt_bwd')
+        self._grads_intact(state, grads, 'lg_op_lgt_bwd')
         return dz, grads
 
     def grad_of(self, flat_grads, name):

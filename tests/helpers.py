@@ -1,8 +1,11 @@
 """Shared test helpers: deterministic weights + shapes of the reference state_dict."""
+import functools
+
 import numpy as np
 import torch
 
 from oracle import detweights as dw
+from oracle import lgteun_oracle as orc
 
 
 def state_shapes(C, K):
@@ -113,3 +116,48 @@ def numpy_drop_masks(seed, dtype=torch.float64):
     def masks(stage, blk, B, h, w, e):
         return mask_tensor(torch.from_numpy(_dropout_mask_numpy(seed, stage, blk, 0, B * h * w * e)), B, h, w, e, dtype)
     return masks
+
+
+# ---- inputs and oracle restatements shared by the per-op shape files (test_gpu_forward_shapes.py, test_gpu_backward_shapes.py)
+BLOCKS = {0: 'encoder_layers.0.0.blocks.0.', 1: 'encoder_layers.0.0.blocks.1.', 2: 'bottleneck.blocks.0.',
+          3: 'decoder_layers.0.2.blocks.0.', 4: 'decoder_layers.0.2.blocks.1.'}
+
+
+def block_prefix(blk):
+    return 'prior_module.0.' + BLOCKS[blk]
+
+
+@functools.lru_cache(maxsize=None)
+def block_features(C, blk, B, H, W):
+    """standard-normal NHWC features of block `blk` of a B x H x W PAN batch; the last sample's global half has a negative mean"""
+    h, w, e = (H // 2, W // 2, 8 * C) if blk == 2 else (H, W, 4 * C)
+    rng = np.random.default_rng(1000 + H + W + 7 * blk + C)
+    x = torch.from_numpy(rng.standard_normal((B, h, w, e)).astype(np.float32))
+    x[-1, ..., e // 2:] -= 0.7
+    return x
+
+
+def ffn_half_block(P, blk, x):
+    p = block_prefix(blk)
+    return x + orc.feed_forward(P, p + '1.fn.fn.', orc.layer_norm(x, P[p + '1.fn.norm.weight'], P[p + '1.fn.norm.bias']))
+
+
+def mixer_half_block(P, blk, x):
+    p = block_prefix(blk)
+    return x + orc.lg_mixer(P, p + '0.fn.fn.', orc.layer_norm(x, P[p + '0.fn.norm.weight'], P[p + '0.fn.norm.bias']))
+
+
+def mixer_restated(P, blk, x, x1, o2):
+    """x + proj(cat(local_mixer(LN(x)[..., :e/2]), o2)): o2 planar [B, e/2, h, w], the build's own global-mixer output"""
+    p = block_prefix(blk) + '0.fn.fn.'
+    cat = torch.cat((x1, o2.permute(0, 2, 3, 1)), dim=-1).permute(0, 3, 1, 2)
+    return x + orc.point_conv(cat, P[p + 'proj.weight'], P[p + 'proj.bias']).permute(0, 2, 3, 1)
+
+
+@functools.lru_cache(maxsize=None)
+def lgt_input(C, B, H, W):
+    return torch.from_numpy(np.random.default_rng(H + W).uniform(0, 1, (B, C, H, W)).astype(np.float32))
+
+
+LGT_CASES = [(4, 1, 16, 16), (4, 2, 16, 48), (4, 3, 80, 48), (8, 1, 48, 208), (8, 2, 48, 48), (8, 3, 80, 48)]                 # (C, B, H, W)
+DSTEP_CASES = [(1, 4, 16, 16), (3, 4, 48, 16), (3, 8, 80, 48), (1, 4, 208, 176), (2, 8, 16, 48), (5, 4, 64, 64)]               # (B, C, H, W)

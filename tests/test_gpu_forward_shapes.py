@@ -59,15 +59,14 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import det_params, rel_l2
+from helpers import DSTEP_CASES, LGT_CASES, block_features as _features, block_prefix as _pre, det_params, ffn_half_block as _ffn, lgt_input as _lgt_input
+from helpers import mixer_half_block as _mixer, mixer_restated as _mixer_restated, rel_l2
 from oracle import lgteun_oracle as orc
 
 pytestmark = pytest.mark.gpu
 
 T = torch.from_numpy
 BAR = 8.0                   # element-wise error: at most this many times the fp32 oracle's own
-BLOCKS = {0: 'encoder_layers.0.0.blocks.0.', 1: 'encoder_layers.0.0.blocks.1.', 2: 'bottleneck.blocks.0.',
-          3: 'decoder_layers.0.2.blocks.0.', 4: 'decoder_layers.0.2.blocks.1.'}
 
 
 @pytest.fixture(autouse=True)
@@ -82,41 +81,10 @@ def _params(C, K, dtype):
     return det_params(C, K, dtype=dtype)
 
 
-def _pre(blk):
-    return 'prior_module.0.' + BLOCKS[blk]
-
-
-@functools.lru_cache(maxsize=None)
-def _features(C, blk, B, H, W):
-    """standard-normal NHWC features of block `blk` of a B x H x W PAN batch; the last sample's global half has a negative mean"""
-    h, w, e = (H // 2, W // 2, 8 * C) if blk == 2 else (H, W, 4 * C)
-    rng = np.random.default_rng(1000 + H + W + 7 * blk + C)
-    x = T(rng.standard_normal((B, h, w, e)).astype(np.float32))
-    x[-1, ..., e // 2:] -= 0.7
-    return x
-
-
-def _ffn(P, blk, x):
-    p = _pre(blk)
-    return x + orc.feed_forward(P, p + '1.fn.fn.', orc.layer_norm(x, P[p + '1.fn.norm.weight'], P[p + '1.fn.norm.bias']))
-
-
-def _mixer(P, blk, x):
-    p = _pre(blk)
-    return x + orc.lg_mixer(P, p + '0.fn.fn.', orc.layer_norm(x, P[p + '0.fn.norm.weight'], P[p + '0.fn.norm.bias']))
-
-
 def _local(P, blk, x):
     p = _pre(blk)
     y = orc.layer_norm(x, P[p + '0.fn.norm.weight'], P[p + '0.fn.norm.bias'])
     return orc.local_mixer(P, p + '0.fn.fn.local_mixer.', y[..., :x.shape[-1] // 2])
-
-
-def _mixer_restated(P, blk, x, x1, o2):
-    """x + proj(cat(local_mixer(LN(x)[..., :e/2]), o2)): o2 planar [B, e/2, h, w], the build's own global-mixer output"""
-    p = _pre(blk) + '0.fn.fn.'
-    cat = torch.cat((x1, o2.permute(0, 2, 3, 1)), dim=-1).permute(0, 3, 1, 2)
-    return x + orc.point_conv(cat, P[p + 'proj.weight'], P[p + 'proj.bias']).permute(0, 2, 3, 1)
 
 
 @functools.lru_cache(maxsize=None)
@@ -137,11 +105,8 @@ def _mixer_refs(C, blk, B, H, W):
 
 
 def _ops(C, H, W, K=1, precision=None):
-    from gpu_helpers import Ops, make_module
-    net = make_module(C, K)
-    if precision is not None:
-        net.precision = precision
-    return Ops(net, H, W)
+    from gpu_helpers import make_ops
+    return make_ops(C, H, W, K, precision)
 
 
 def _max_err(a, b, den):
@@ -228,14 +193,6 @@ def test_second_encoder_and_decoder_blocks(C, blk, which):
 
 
 # ---- 5. one LGT: k_embed / k_down / k_upfuse / k_tail around the blocks, at rectangles and half-tiles
-LGT_CASES = [(4, 1, 16, 16), (4, 2, 16, 48), (4, 3, 80, 48), (8, 1, 48, 208), (8, 2, 48, 48), (8, 3, 80, 48)]
-
-
-@functools.lru_cache(maxsize=None)
-def _lgt_input(C, B, H, W):
-    return T(np.random.default_rng(H + W).uniform(0, 1, (B, C, H, W)).astype(np.float32))
-
-
 @pytest.mark.parametrize('C,B,H,W', LGT_CASES)
 def test_one_lgt_at_awkward_shapes(C, B, H, W):
     z = _lgt_input(C, B, H, W)
@@ -269,9 +226,6 @@ def test_saving_forward_is_bitwise_the_plain_forward(C, B, H, W):
 
 
 # ---- 6. data step forward: stage 1 of K = 2
-DSTEP_CASES = [(1, 4, 16, 16), (3, 4, 48, 16), (3, 8, 80, 48), (1, 4, 208, 176), (2, 8, 16, 48), (5, 4, 64, 64)]
-
-
 @pytest.mark.parametrize('B,C,H,W', DSTEP_CASES)
 def test_data_step_at_awkward_shapes(B, C, H, W):
     """the 32 x 32 tile kernels on planes that are no multiple of 32, an MS plane of 4 x 4, the one-launch form (64 x 64) at an odd batch"""

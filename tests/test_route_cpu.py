@@ -100,6 +100,30 @@ def test_every_backward_read_is_a_forward_write(C, prec, n):
     assert accepted >= len(words) // 4
 
 
+# PAN sizes whose level-1 plane (8 x 8, 40 x 24, 24 x 104) is no whole number of 8-row steps of 16-column strips: resolve_ffn turns the strip walk off there
+FALLBACK_PLANES = [(16, 16), (80, 48), (48, 208)]
+
+
+@pytest.mark.parametrize('C', [4, 8])
+@pytest.mark.parametrize('prec', [0, 1])
+@pytest.mark.parametrize('H,W', FALLBACK_PLANES)
+def test_level_1_planes_without_whole_strips_fall_back_to_the_tile_kernel(C, prec, H, W):
+    """the default plan at rectangles: every backward read is a forward write, and the level-1 FFN backward is the tile kernel k_ffn_dw_bwd (with its
+    k_wgrad launch for dW3), not the strip walk k_ffn_dw_bwd_xs -- which level 0, whose planes are whole strips, keeps where it has one"""
+    p = Plan(C, prec, H, W, 0)
+    assert p.error is None
+    text = p.describe()
+    check_reads_are_written(text)
+    _, r = parse(text)
+    l1 = r[(1, 'bwd')][0]['ffn'].split('+')
+    assert l1[0] == 'k_ffn_dw_bwd' and 'k_ffn_dw_bwd_xs' not in l1 and l1[-1] == 'k_wgrad(W3)', text
+    assert l1[1] == ('k_ffn1_bwd_xs' if C == 4 else 'k_ffn1_bwd'), text
+    assert r[(0, 'bwd')][0]['ffn'] == 'k_ffn_dw_bwd_xs+k_ffn1_bwd_xs', text
+    # the same heights at a width of whole strips (level 1: 32 columns) keep the strip walk at e = 32 (C = 4); e = 64 has the tile kernel only
+    whole = parse(Plan(C, prec, H, 64, 0).describe())[1]
+    assert (whole[(1, 'bwd')][0]['ffn'].split('+')[0] == 'k_ffn_dw_bwd_xs') == (C == 4), (C, prec, H, W)
+
+
 def test_bit_groups_are_independent():
     """a bit outside a group leaves that group's part of the text alone, on the default and on every single switch"""
     def parts(text):
