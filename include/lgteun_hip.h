@@ -116,7 +116,7 @@ typedef struct lg_plan lg_plan; /* host-side, immutable after creation */
 
 const char* lg_version(void);
 /* Bumped whenever a struct layout, an argument meaning or a caller-provided buffer size changes (2: lg_config.variant, the data step's
- * tmp of 3*B*C*H*W/4 + B*H*W floats).  Additions keep it: lg_op_lgt_stages, lg_workspace_deadout and LG_FLAG_STAGEWISE came without a bump (no struct,
+ * tmp of 3*B*C*H*W/4 + B*H*W floats).  Additions keep it: lg_op_lgt_stages, lg_workspace_deadout, LG_FLAG_STAGEWISE and the lg_debug_stage_* entries came without a bump (no struct,
  * argument or caller-sized buffer changed: workspaces are sized by lg_workspace_bytes, which grew for the plans that batch their dead stages).  A binding checks it at load time -- lgteun_amd/_lib.py does -- instead of passing a stale struct. */
 #define LG_ABI_VERSION 2
 int32_t lg_abi_version(void);
@@ -259,6 +259,17 @@ int lg_op_lgt_stages(const lg_plan* plan, const float* params, int32_t stage0, i
  * [B,C,H,W] at byte offset *offset + i * *stage_stride.  *stage_stride is 0 for a plan that keeps one slot (every dead stage overwrites the
  * previous one's). */
 int lg_workspace_deadout(const lg_plan* plan, int32_t B, int32_t train, size_t* offset, size_t* stage_stride);
+/* Debug, host only (no device, no launch): the units the workgroups of a persistent multi-stage launch walk, from the functions the kernels call.
+ * kind 0: the fused FFN (k_ffn_xr) -- split 0: `units` strips in even runs; split != 0: `units` strip PAIRS, the two workgroups w and w + grid/2
+ * on the same run of pairs, the second at strip base `units`.  kind 1: the local mixer (k_attn_m) -- `units` window quads; split = eighths of a
+ * CU's chunk to its first workgroup, 4 = even runs.  per_stage: units of one stage.  out: rows of five int32 { workgroup, seg0, seg1, stage,
+ * strip base }, one per (workgroup, stage segment) in workgroup order; at most n_out rows are written.  Returns the number of rows, < 0 on error. */
+int lg_debug_stage_runs(int32_t kind, int32_t units, int32_t per_stage, int32_t grid, int32_t split, int32_t* out, int32_t n_out);
+/* ... and the launchers' decision for n stages of Bs samples on h x w planes under grid_cap (lg_op_lgt_stages).  kind 0: k_ffn_xr, out8 =
+ * { uneven, rows shifted dS, units, units per stage, grid, strip height, column tiles, strips per column }; kind 8 / 16: k_attn_m<8|16> with
+ * two resident workgroups per CU, out8 = { uneven, eighths, quads, quads per stage, grid, windows, 0, 0 }.  units / split are what
+ * lg_debug_stage_runs takes. */
+int lg_debug_stage_decision(int32_t kind, int32_t h, int32_t w, int32_t Bs, int32_t n, int32_t grid_cap, int32_t* out8);
 /* pieces of one LGB block `blk` (0,1: encoder; 2: bottleneck; 3,4: decoder) of stage `stage`, on NHWC x:
  *  which = 0: global_mixer on LN(x)[..., e/2:]  -> y planar [B,e/2,h,w]        (LGT.py:149-180)
  *          1: x + LGMixer(LN(x))                -> y [B,h,w,e]                 (LGT.py:183-219,231-248)

@@ -123,6 +123,8 @@ SIGNATURES = {
                             c_void_p]),
     'lg_op_lgt_stages': (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_int32, c_uint64,
                                    c_int32, c_void_p]),
+    'lg_debug_stage_runs': (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), c_int32]),
+    'lg_debug_stage_decision': (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32)]),
     'lg_workspace_deadout': (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_size_t), POINTER(c_size_t)]),
     'lg_op_block': (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_int32,
                               c_void_p]),

@@ -536,6 +536,47 @@ extern "C" int lg_op_lgt_stages(const lg_plan* plan, const float* params, int32_
     return lgt_fwd(plan, params, stage0, z, out, nb, B, flags, seed, s, true, n, (long)B * plan->cfg.C * plan->cfg.H * plan->cfg.W, grid_cap);
 }
 
+// debug exports (tests/test_stage_runs_cpu.py; host only, no device, no launch): the partition of a persistent multi-stage launch, from the functions
+// the kernels call (kernels.h: stage_run_*), and the launchers' decision for a shape
+extern "C" int lg_debug_stage_runs(int32_t kind, int32_t units, int32_t per_stage, int32_t grid, int32_t split, int32_t* out, int32_t n_out) {
+    if (kind < 0 || kind > 1 || units <= 0 || per_stage <= 0 || units % per_stage || grid <= 0 || !out || n_out < 0 || (int64_t)units * grid >= (1ll << 31)) {
+        lg_set_error("debug_stage_runs: invalid argument");
+        return -1;
+    }
+    const bool uneven = kind == 0 ? split != 0 : split != 4;
+    if (!uneven && grid > units) { lg_set_error("debug_stage_runs: more workgroups than units"); return -1; }
+    // (what the launchers guarantee: a pair of strips per pair of workgroups, two quads per CU)
+    if (uneven && ((grid & 1) || (kind == 0 ? 2 * units < grid : units < grid) || (kind == 1 && (split < 1 || split > 7)))) { lg_set_error("debug_stage_runs: an uneven split needs an even grid, a unit per workgroup and 1 <= eighths <= 7"); return -2; }
+    int rows = 0;
+    for (int wg = 0; wg < grid; ++wg) {
+        const StageRun r = !uneven ? stage_run_even(units, grid, wg) : (kind == 0 ? stage_run_pairs(units, grid, wg) : stage_run_chunk(units, grid, wg, split));
+        int seg0 = r.run0;
+        do {   // the kernels' segment loop
+            const int st = seg0 / per_stage, seg1 = stage_seg_end(st, r.run1, per_stage);
+            if (rows < n_out) { int32_t* o = out + 5 * (size_t)rows; o[0] = wg; o[1] = seg0; o[2] = seg1; o[3] = st; o[4] = r.base; }
+            ++rows;
+            seg0 = seg1;
+        } while (seg0 < r.run1);
+    }
+    return rows;
+}
+
+extern "C" int lg_debug_stage_decision(int32_t kind, int32_t h, int32_t w, int32_t Bs, int32_t n, int32_t grid_cap, int32_t* out8) {
+    if ((kind != 0 && kind != 8 && kind != 16) || h <= 0 || w <= 0 || Bs <= 0 || n < 1 || grid_cap < 0 || !out8 || (int64_t)Bs * n * h * w >= (1ll << 31)) { lg_set_error("debug_stage_decision: invalid argument"); return -1; }
+    if (kind == 0) {
+        const XrGeo q = ffn_xr_geometry(h, w, Bs * n, Bs, n, grid_cap);
+        const int sh = q.dS ? 1 : 0;
+        const int32_t o[8] = {q.dS != 0, q.dS, q.nstrips >> sh, (Bs * q.tiles_x * q.strips_y) >> sh, q.grid, q.SH, q.tiles_x, q.strips_y};
+        memcpy(out8, o, sizeof(o));
+    } else {
+        if ((h & 7) || (w & 7) || (Bs * (h / 8) * (w / 8)) % 4) { lg_set_error("debug_stage_decision: not whole window quads per stage"); return -2; }
+        const AttnMGeo q = attn_m_geometry(kind, h, w, Bs * n, n, grid_cap, 2);   // two resident workgroups per CU: what the runtime reports for HC <= 16
+        const int32_t o[8] = {q.uneven != 0, q.uneven ? q.uneven : 4, q.nquads, q.nquads / n, q.grid, q.nwin, 0, 0};
+        memcpy(out8, o, sizeof(o));
+    }
+    return 0;
+}
+
 extern "C" int lg_op_block(const lg_plan* plan, const float* params, int32_t stage, int32_t blk, int32_t which, const float* x,
                            float* y, void* workspace, size_t workspace_bytes, int32_t B, void* stream) {
     if (!plan || !params || !x || !y || !workspace || stage < 0 || stage >= plan->cfg.K || blk < 0 || blk > 4 || which < 0 || which > 2) {

@@ -209,6 +209,12 @@ __device__ unsigned long long am_stamps[1024][4][8];
 #else
 #define AM_STAMP(i) do { } while (0)
 #endif
+// Multi-stage instances of HC >= this form the lane constants again in every segment, behind a laundered thread index: hoisted out of the segment loop
+// they stay live through the kernel.  k_attn_m<16,2,true>: 9 spilled registers -> 4, its time unchanged.  At HC = 8 nothing was spilled (236 -> 230
+// registers) and the launch got slower, so 8 stays out.  The measured figures are in DESIGN section 4.
+#ifndef LG_ATTN_MULTI_REFORM_HC
+#define LG_ATTN_MULTI_REFORM_HC 16
+#endif
 // MULTI: the launch covers the samples of several stages (kernels.h: StageSel); false: the segment loop below is one straight pass
 template <int HC, int NP, bool MULTI = false>
 __global__ __launch_bounds__(256, (HC <= 16 ? 2 : 1)) void k_attn_m(AttnArgs a_, int nwin, int nquads, int uneven) {
@@ -230,7 +236,6 @@ __global__ __launch_bounds__(256, (HC <= 16 ? 2 : 1)) void k_attn_m(AttnArgs a_,
     u32x4_t* sWqk = smem4 + 2 * 4 * 4 * 64;                       // [MTQK][NKQ][64]
     u32x4_t* sWv = sWqk + MTQK * NKQ * 64;                        // [NTV][NKQ][64]
     u32x4_t* sWp = sWv + NTV * NKQ * 64;                          // [MTP][NKP][64]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, c = lane & 15;
 
 #ifdef LG_ATTN_STAMPS
     unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = __builtin_amdgcn_s_memtime();
@@ -241,16 +246,21 @@ __global__ __launch_bounds__(256, (HC <= 16 ? 2 : 1)) void k_attn_m(AttnArgs a_,
     const StageSel sg = a_.sg;
     constexpr bool multi = MULTI;
     const int half = (int)gridDim.x >> 1, first = (int)blockIdx.x < half ? 1 : 0;
-    const int nmine = uneven ? (first ? uneven : 8 - uneven) : 0x7fffffff;
+    const int nmine = (!multi && uneven) ? (first ? uneven : 8 - uneven) : 0x7fffffff;
     const int q0 = uneven ? (first ? (int)blockIdx.x : half * uneven + ((int)blockIdx.x - half)) : (int)blockIdx.x;
     const int qstep = multi ? 1 : (uneven ? half : (int)gridDim.x);
     const int per_stage = multi ? __builtin_amdgcn_readfirstlane(nquads / sg.n) : nquads;
-    const int run0 = multi ? __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (unsigned)nquads / gridDim.x)) : q0;              // (grid x quads < 2^32: the launcher checks it)
-    const int run1 = multi ? __builtin_amdgcn_readfirstlane((int)((blockIdx.x + 1) * (unsigned)nquads / gridDim.x)) : nquads;
+    // several stages and uneven (launcher: the resident workgroups, two per CU): the two workgroups of a CU share one contiguous chunk of quads, uneven : 8 - uneven
+    const StageRun rn = stage_run_chunk(nquads, (int)gridDim.x, (int)blockIdx.x, multi ? uneven : 0);   // (uneven = 0: stage_run_even)
+    const int run0 = multi ? __builtin_amdgcn_readfirstlane(rn.run0) : q0;              // (grid x quads < 2^32: the launcher checks it)
+    const int run1 = multi ? __builtin_amdgcn_readfirstlane(rn.run1) : nquads;
     int seg0 = run0;
     do {
     const int stg = multi ? __builtin_amdgcn_readfirstlane(seg0 / per_stage) : 0;   // (division runs on the vector pipe: kernels.h, stage_of)
-    const int seg1 = multi ? min(run1, (stg + 1) * per_stage) : run1;
+    const int seg1 = multi ? stage_seg_end(stg, run1, per_stage) : run1;
+    int tid_ = threadIdx.x;
+    if (MULTI && HC >= LG_ATTN_MULTI_REFORM_HC) asm volatile("" : "+v"(tid_));   // (the lane constants are formed again per segment: see LG_ATTN_MULTI_REFORM_HC)
+    const int lane = tid_ & 63, wave = tid_ >> 6, g = lane >> 4, c = lane & 15;
     AttnArgs a = a_;
     {
         const long po = stg * sg.pstride;
@@ -554,6 +564,7 @@ __global__ __launch_bounds__(256, (HC <= 16 ? 2 : 1)) void k_attn_m(AttnArgs a_,
     seg0 = seg1;
     } while (MULTI && seg0 < run1);   // segments (stages) of this workgroup
 #ifdef LG_ATTN_STAMPS
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0 && blockIdx.x < 1024) {
         for (int i = 0; i < 6; ++i) am_stamps[blockIdx.x][wave][i] = st[i];
         am_stamps[blockIdx.x][wave][7] = 1ull;
@@ -561,13 +572,43 @@ __global__ __launch_bounds__(256, (HC <= 16 ? 2 : 1)) void k_attn_m(AttnArgs a_,
 #endif
 }
 
+#ifndef LG_ATTN_UNEVEN
+#define LG_ATTN_UNEVEN 5
+#endif
+// the same split in the multi-stage instances (kernels.h: stage_run_chunk), in eighths of a CU's chunk of quads to its first workgroup; 4: even runs
+#ifndef LG_ATTN_MULTI_UNEVEN
+#define LG_ATTN_MULTI_UNEVEN 5     // HC = 8: k_attn_m<8,2,true> over 3 x 32 pairs (24 quads per CU), us per launch: even 106.2 - 107.8, 5 (15 : 9) 97.9, 6 (18 : 6) 121
+#endif
+#ifndef LG_ATTN_MULTI_UNEVEN16
+#define LG_ATTN_MULTI_UNEVEN16 4   // HC = 16 stays EVEN: k_attn_m<16,2,true> with 6 quads per CU at 3 x 32 pairs measured 45.6 - 47.1 us even, 47.5 at 5 (4 : 2), 53.8 at 6 (5 : 1)
+#endif
+// The launch geometry (host only; lg_debug_stage_decision reports it).  n <= 1: one stage.  per_cu: resident workgroups per CU, from the runtime.
+AttnMGeo attn_m_geometry(int HC, int h, int w, int B, int n, int grid_cap, int per_cu) {
+    AttnMGeo q;
+    q.nwin = B * (h / 8) * (w / 8);
+    q.nquads = (q.nwin + 3) / 4;
+    const int ncu = 256;
+    const int cap = ncu * per_cu;
+    const int rounds = (q.nquads + cap - 1) / cap;
+    q.grid = q.nquads < cap ? q.nquads : (q.nquads + rounds - 1) / rounds;
+    const bool multi = n > 1;
+    bool capped = false;
+    if (multi) {   // with more quads than slots exactly the resident workgroups
+        if (q.nquads > cap) q.grid = cap;
+        if (grid_cap > 0 && q.grid > grid_cap) { q.grid = grid_cap; capped = true; }
+    }
+    int u = (!multi && per_cu == 2 && q.grid == 512 && q.nquads == 4 * q.grid && q.nwin == 4 * q.nquads) ? LG_ATTN_UNEVEN : 0;   // the measured shape only
+    // several stages: two resident workgroups on every CU, no test cap, at least two quads for a CU's pair to share
+    if (multi && per_cu == 2 && q.grid == 2 * ncu && !capped && q.nquads >= 2 * ncu && (HC == 8 || HC == 16)) u = HC == 8 ? LG_ATTN_MULTI_UNEVEN : LG_ATTN_MULTI_UNEVEN16;
+    q.uneven = u == 4 ? 0 : u;
+    return q;
+}
+
 template <int HC, int NP, bool MULTI = false>
 static int launch_attn_m_t(const AttnArgs& a, hipStream_t s) {
     using G = am::Geo<HC>;
     constexpr int NPQ = NP == 2 ? 2 : NP, NPP = NP == 2 ? 3 : NP;
     constexpr int NKQ = am::cdiv(am::nprod(NPQ) * 4 * G::NY, 8), NKP = am::cdiv(am::nprod(NPP) * 4 * G::NCH, 8);
-    const int nwin = a.B * (a.h / 8) * (a.w / 8);
-    const int nquads = (nwin + 3) / 4;
     const size_t lds = (size_t)(2 * 4 * 4 * 64 + (G::MTQK + G::NTV) * NKQ * 64 + G::NCH * NKP * 64) * 16;
     static DeviceOnce attr_once;
     if (attr_once.need()) {
@@ -587,21 +628,12 @@ static int launch_attn_m_t(const AttnArgs& a, hipStream_t s) {
         per_cu = nb;
         per_cu_cache[DeviceOnce::dev()].store(per_cu, std::memory_order_release);
     }
-    int ncu = 256;
-    const int cap = ncu * per_cu;
-    const int rounds = (nquads + cap - 1) / cap;
-    int grid = nquads < cap ? nquads : (nquads + rounds - 1) / rounds;
     constexpr bool multi = MULTI;
-    if (multi) {   // whole quads per stage (a quad = the four windows of a workgroup's waves), and with more quads than slots exactly the resident workgroups
-        if (a.save_o || a.save_l || a.sg.Bs <= 0 || a.B != a.sg.n * a.sg.Bs || (a.sg.Bs * (a.h / 8) * (a.w / 8)) % 4) { lg_set_error("attn_m: a window quad would straddle the stages of the launch"); return -2; }
-        if (nquads > cap) grid = cap;
-        if (a.sg.grid_cap > 0 && grid > a.sg.grid_cap) grid = a.sg.grid_cap;
-    }
-#ifndef LG_ATTN_UNEVEN
-#define LG_ATTN_UNEVEN 5
-#endif
-    const int uneven = (!multi && per_cu == 2 && grid == 512 && nquads == 4 * grid && nwin == 4 * nquads) ? LG_ATTN_UNEVEN : 0;   // the measured shape only
-    k_attn_m<HC, NP, MULTI><<<grid, 256, lds, s>>>(a, nwin, nquads, uneven == 4 ? 0 : uneven);
+    // whole quads per stage (a quad = the four windows of a workgroup's waves)
+    if (multi && (a.save_o || a.save_l || a.sg.Bs <= 0 || a.B != a.sg.n * a.sg.Bs || (a.sg.Bs * (a.h / 8) * (a.w / 8)) % 4)) { lg_set_error("attn_m: a window quad would straddle the stages of the launch"); return -2; }
+    const AttnMGeo geo = attn_m_geometry(HC, a.h, a.w, a.B, multi ? a.sg.n : 1, a.sg.grid_cap, per_cu);
+    const int nwin = geo.nwin, nquads = geo.nquads, grid = geo.grid, uneven = geo.uneven;
+    k_attn_m<HC, NP, MULTI><<<grid, 256, lds, s>>>(a, nwin, nquads, uneven);
     LG_CHECK_LAUNCH();
     return 0;
 }

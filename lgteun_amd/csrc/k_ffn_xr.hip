@@ -59,6 +59,10 @@ extern "C" __attribute__((visibility("default"))) int lg_debug_xr_stamps(unsigne
 #ifndef LG_XR_UNEVEN
 #define LG_XR_UNEVEN 16   // rows (per 64-row strip) moved from the second workgroup of a CU to the first; 0: even strips
 #endif
+#ifndef LG_XR_MULTI_UNEVEN
+#define LG_XR_MULTI_UNEVEN 16   // the same in the multi-stage instances, whose workgroups walk runs of strip pairs (kernels.h: stage_run_pairs); 0: even strip runs
+                                // (k_ffn_xr<0,2,true> over 3 x 32 pairs, us per launch on one box: even 212.3, 8 rows 208.7, 16 rows 200.9, 24 rows 203.7)
+#endif
 #define XR_TAKE_TURNS() do { if (LG_XR_TURN) { \
         const unsigned long long tt__ = __builtin_amdgcn_s_memtime(); \
         if ((((unsigned)(tt__ >> LG_XR_TURN)) ^ slot_par) & 1u) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0); } } while (0)
@@ -182,14 +186,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     // per stage -- at a stage boundary the tables are staged again, behind a barrier, from that stage's weights (at 3 x 32 pairs two workgroups of 512).
     const StageSel sg = a1_.sg;
     constexpr bool multi = MULTI;
-    const int per_stage = multi ? sg.Bs * tiles_x * strips_y : nstrips;
-    const int run0 = multi ? __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (unsigned)nstrips / gridDim.x)) : (int)blockIdx.x;          // (grid x strips < 2^31: both are
-    const int run1 = multi ? __builtin_amdgcn_readfirstlane((int)((blockIdx.x + 1) * (unsigned)nstrips / gridDim.x)) : nstrips;              //  below 2^15 x 2^16)
+    // dS != 0 (launcher: the 512 resident workgroups): the units of the run are strip PAIRS, and the two workgroups of a CU walk the same run of them -- the
+    // first the tall strips, the second the short ones, at strip index pair + nstrips / 2.  The run is kept in strip indices (unit + base): the short strips of
+    // stage st are then [(n + st) per_stage, (n + st + 1) per_stage), and no base stays live across the kernel
+    const bool pairs = multi && dS != 0;
+    const int per_stage = multi ? (sg.Bs * tiles_x * strips_y) >> (pairs ? 1 : 0) : nstrips;
+    const StageRun rn = stage_run_halves(nstrips >> (pairs ? 1 : 0), (int)gridDim.x >> (pairs ? 1 : 0), (int)blockIdx.x);   // = stage_run_pairs : stage_run_even   (grid x strips < 2^31: both are
+    const int run0 = multi ? __builtin_amdgcn_readfirstlane(rn.run0 + rn.base) : (int)blockIdx.x;                                                             //  below 2^15 x 2^16)
+    const int run1 = multi ? __builtin_amdgcn_readfirstlane(rn.run1 + rn.base) : nstrips;
     const int rstep = multi ? 1 : (int)gridDim.x;
     int seg0 = run0;
     do {
-    const int st = multi ? __builtin_amdgcn_readfirstlane(seg0 / per_stage) : 0;   // (division runs on the vector pipe: kernels.h, stage_of)
-    const int seg1 = multi ? min(run1, (st + 1) * per_stage) : run1;
+    const int sq = multi ? __builtin_amdgcn_readfirstlane(seg0 / per_stage) : 0;   // (division runs on the vector pipe: kernels.h, stage_of)
+    const int st = sq >= sg.n ? sq - sg.n : sq;                                    // (short strips: see above)
+    const int seg1 = multi ? stage_seg_end(sq, run1, per_stage) : run1;
     Ffn1Args a1 = a1_;
     Ffn2Args a2 = a2_;
     {
@@ -768,6 +778,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     } while (MULTI && seg0 < run1);   // segments (stages) of this workgroup
 }
 
+// The launch geometry (host only; lg_debug_stage_decision reports it).  n <= 1: one stage of B samples.
+XrGeo ffn_xr_geometry(int h, int w, int B, int Bs, int n, int grid_cap) {
+    XrGeo q;
+    q.tiles_x = (w + 15) / 16;
+    // strip height: the tallest multiple of 8 rows that still yields >= 512 strips (two resident workgroups per CU), at least 16
+    // (several stages in the launch: the strip height of ONE stage's launch, so that a workgroup gets whole strips of that size -- three at 3 x 32 pairs)
+    const bool multi = n > 1;
+    const int Bsh = multi ? Bs : B;
+    int SH = (h + 7) / 8 * 8;
+    while (SH > 16 && (long)Bsh * q.tiles_x * ((h + SH - 1) / SH) < LG_XR_GRID) SH = (SH / 2 + 7) / 8 * 8;
+    q.SH = SH;
+    q.strips_y = (h + SH - 1) / SH;
+    q.nstrips = B * q.tiles_x * q.strips_y;
+    q.grid = q.nstrips < LG_XR_GRID ? q.nstrips : LG_XR_GRID;
+    const bool capped = multi && grid_cap > 0 && q.grid > grid_cap;
+    if (capped) q.grid = grid_cap;
+    // uneven split of strip pairs (strip_geo in the kernel): only in the shapes it was measured in, exactly two workgroups per CU.  One stage: one strip per
+    // workgroup.  Several: the 512 resident workgroups (a capped grid keeps the even strip runs), each pair of them on a run of strip pairs.
+    q.dS = 0;
+    const bool shape_ok = LG_XR_GRID == 512 && (q.strips_y & 1) == 0 && SH >= 32 && h % (2 * SH) == 0;
+    if (!multi && LG_XR_UNEVEN && q.nstrips == LG_XR_GRID && shape_ok) q.dS = (SH * LG_XR_UNEVEN / 64 + 7) / 8 * 8;
+    if (multi && LG_XR_MULTI_UNEVEN && !capped && q.grid == LG_XR_GRID && (q.grid & 1) == 0 && shape_ok) q.dS = (SH * LG_XR_MULTI_UNEVEN / 64 + 7) / 8 * 8;
+    return q;
+}
+
 int launch_ffn_xr(const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s) {
     using namespace xr;
     ProfScope prof__(LG_K_FFN2, s, a1.sg.n);
@@ -786,21 +821,10 @@ int launch_ffn_xr(const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s) {
     const bool save = a1.h2 != nullptr;
     if (save && (a1.a1s || a1.g1s || a2.g3s)) { lg_set_error("ffn_xr: saves h2 / h3 (or h2 alone: a3s null, the backward re-computes h3) only"); return -2; }
     if ((long)a2.B * a2.h * a2.w * N1 >= (1ll << 32)) { lg_set_error("ffn_xr: hidden tensor of %ld elements exceeds the 32-bit save index", (long)a2.B * a2.h * a2.w * N1); return -2; }
-    const int tiles_x = (a2.w + 15) / 16;
-    // strip height: the tallest multiple of 8 rows that still yields >= 512 strips (two resident workgroups per CU), at least 16
-    // (several stages in the launch: the strip height of ONE stage's launch, so that a workgroup gets whole strips of that size -- three at 3 x 32 pairs)
     const bool multi = a1.sg.n > 1;
-    const int Bsh = multi ? a1.sg.Bs : a2.B;
     if (multi && (save || a1.sg.Bs <= 0 || a2.B != a1.sg.n * a1.sg.Bs)) { lg_set_error("ffn_xr: B = %d is not %d stages of %d samples", a2.B, a1.sg.n, a1.sg.Bs); return -2; }
-    int SH = (a2.h + 7) / 8 * 8;
-    while (SH > 16 && (long)Bsh * tiles_x * ((a2.h + SH - 1) / SH) < LG_XR_GRID) SH = (SH / 2 + 7) / 8 * 8;
-    const int strips_y = (a2.h + SH - 1) / SH;
-    const int nstrips = a2.B * tiles_x * strips_y;
-    int grid = nstrips < LG_XR_GRID ? nstrips : LG_XR_GRID;
-    if (multi && a1.sg.grid_cap > 0 && grid > a1.sg.grid_cap) grid = a1.sg.grid_cap;
-    // uneven split of strip pairs (strip_geo in the kernel): only in the shape it was measured in -- one strip per workgroup, exactly two workgroups per CU
-    int dS = 0;
-    if (!multi && LG_XR_UNEVEN && nstrips == LG_XR_GRID && LG_XR_GRID == 512 && (strips_y & 1) == 0 && SH >= 32 && a2.h % (2 * SH) == 0) dS = (SH * LG_XR_UNEVEN / 64 + 7) / 8 * 8;
+    const XrGeo geo = ffn_xr_geometry(a2.h, a2.w, a2.B, a1.sg.Bs, a1.sg.n, a1.sg.grid_cap);
+    const int tiles_x = geo.tiles_x, strips_y = geo.strips_y, nstrips = geo.nstrips, SH = geo.SH, grid = geo.grid, dS = geo.dS;
     if (a1.hbf) {    // precision = 'bf16'
         if (save) k_ffn_xr<3, 1><<<grid, 256, LDS_BYTES, s>>>(a1, a2, tiles_x, strips_y, nstrips, SH, dS);
         else if (multi) k_ffn_xr<0, 1, true><<<grid, 256, LDS_BYTES, s>>>(a1, a2, tiles_x, strips_y, nstrips, SH, dS);

@@ -86,7 +86,41 @@ struct StageSel {
 __device__ __forceinline__ int stage_of(const StageSel& sg, int b) { return sg.n > 1 ? __builtin_amdgcn_readfirstlane(b / sg.Bs) : 0; }
 // ... of the workgroup, where a sample is `per_sample` consecutive workgroups (or other units) and `unit` this workgroup's
 __device__ __forceinline__ int stage_of_unit(const StageSel& sg, int unit, int per_sample) { return sg.n > 1 ? __builtin_amdgcn_readfirstlane(unit / (per_sample * sg.Bs)) : 0; }
+
+// ---- the units (strips, strip pairs, window quads) a workgroup of a persistent multi-stage launch walks: the run [run0, run1) of ascending units, cut
+// into one segment per stage.  ONE copy of the arithmetic for the kernels and for the host (lg_debug_stage_runs; tests/test_stage_runs_cpu.py).
+struct StageRun { int run0, run1, base; };   // base: k_ffn_xr only -- strip index = unit + base
+// `half` workgroups share the units evenly -- workgroup j takes [j units / half, (j + 1) units / half) -- and a workgroup j + half past them takes the run of
+// workgroup j again, at base `units`   (half x units < 2^32: the launchers check it)
+__host__ __device__ inline StageRun stage_run_halves(int units, int half, int wg) {
+    const int first = wg < half ? 1 : 0, j = wg - (first ? 0 : half);
+    return {(int)((unsigned)j * (unsigned)units / (unsigned)half), (int)(((unsigned)j + 1u) * (unsigned)units / (unsigned)half), first ? 0 : units};
+}
+// even: workgroup wg of `grid` takes units [wg units / grid, (wg + 1) units / grid)
+__host__ __device__ inline StageRun stage_run_even(int units, int grid, int wg) { return stage_run_halves(units, grid, wg); }
+// k_ffn_xr, uneven strip pairs (strip_geo with dS != 0: pair p = the tall strip p and the short strip p + npairs): workgroups j and j + grid / 2 -- the two
+// of a CU -- walk the SAME run of pairs, the first (the one the arbiter favours) their tall strips, the second their short ones
+__host__ __device__ inline StageRun stage_run_pairs(int npairs, int grid, int wg) { return stage_run_halves(npairs, grid >> 1, wg); }
+// k_attn_m, uneven quads: chunk c of grid / 2 (one per CU) is cut u : 8 - u between workgroups c and c + grid / 2, to the nearest whole quad and with at
+// least one quad each (an empty run would stage the tables of a stage that does not exist).  The launcher asks for >= 2 quads per chunk.  u = 0: even runs.
+__host__ __device__ inline StageRun stage_run_chunk(int units, int grid, int wg, int u) {
+    const StageRun ch = stage_run_halves(units, u ? grid >> 1 : grid, wg);
+    if (!u) return ch;
+    const int len = ch.run1 - ch.run0;
+    int n1 = (len * u + 4) >> 3;
+    n1 = n1 > len - 1 ? len - 1 : n1;
+    n1 = n1 < 1 ? 1 : n1;
+    return ch.base ? StageRun{ch.run0 + n1, ch.run1, 0} : StageRun{ch.run0, ch.run0 + n1, 0};
+}
+// end of the segment that starts at unit seg0 of stage st (= seg0 / per_stage)
+__host__ __device__ inline int stage_seg_end(int st, int run1, int per_stage) { return run1 < (st + 1) * per_stage ? run1 : (st + 1) * per_stage; }
 #endif
+
+// the launchers' geometry as host functions (no device, no launch): what lg_debug_stage_decision reports
+struct XrGeo { int tiles_x, SH, strips_y, nstrips, grid, dS; };
+XrGeo ffn_xr_geometry(int h, int w, int B, int Bs, int n, int grid_cap);                       // k_ffn_xr.hip; n <= 1: one stage of B samples
+struct AttnMGeo { int nwin, nquads, grid, uneven; };                                           // uneven: eighths of a CU's quads to its first workgroup, 0 = even
+AttnMGeo attn_m_geometry(int HC, int h, int w, int B, int n, int grid_cap, int per_cu);        // k_attn_m.hip; HC = e / 2 in { 8, 16, 32 }
 
 // ---------------- LGT pixelwise pieces (reference models/common/LGT.py) ----------------
 struct EmbedArgs {
