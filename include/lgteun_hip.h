@@ -80,18 +80,16 @@ typedef struct lg_config {
                       * (400x400 full-resolution scenes, rectangles) the Bluestein path -- same results, slower mixer */
     int32_t precision; /* 0 = fp32 storage/compute (parity mode); 1 = bf16 storage of FFN hidden tensors */
     uint32_t variant;  /* 0 = the product path.  LG_VAR_* bits select A/B kernels that compute the SAME function (tests compare them with
-                        * the default; the library itself reads no environment variable).  Bits this build does not carry are rejected. */
+                        * the default; the library itself reads no environment variable).  Words the library does not carry are rejected. */
 } lg_config;
 
 /* lg_config.variant: A/B switches (all default off).  lg_plan_create resolves them, with precision, C and the plane sizes, into the plan's
  * kernel routes in ONE function (lgteun_amd/csrc/route.hip: lg_resolve_route; the table of bit -> LG_* environment name -> effect is
  * there); lg_plan_describe shows the result. */
 #define LG_VAR_FFN_IMPL_MASK 3u   /* fused FFN forward: 0 = split-bf16 kernels; 1 = the exact f32-MFMA strip kernel (v_mfma_f32_16x16x4_f32: bit
-                                   * for bit an fp32 fma chain -- the yardstick of the arithmetic-criterion test); 2 = round 1's per-tile
-                                   * f32-MFMA kernel, 3 = the software-pipelined split kernel (both only in `make AB=1` builds) */
+                                   * for bit an fp32 fma chain -- the yardstick of the arithmetic-criterion test), precision = 0 only;
+                                   * 2 and 3 name nothing: lg_plan_create rejects them */
 #define LG_VAR_FFN_STRIP 1u
-#define LG_VAR_FFN_TILE 2u
-#define LG_VAR_FFN_XP 3u
 #define LG_VAR_FFN_SAVE_MASK (3u << 2) /* what the live stage's e = 16 FFN keeps for the backward: 0 = h2, h3 (default); 1 = h1, h2, h3; 2 = the
                                         * five-tensor GELU-free form */
 #define LG_VAR_FFN_SAVE3 (1u << 2)

@@ -28,7 +28,7 @@ class LgConfig(ctypes.Structure):
 
 
 # lg_config.variant bits (include/lgteun_hip.h): A/B kernels that compute the same function as the product path
-LG_VAR_FFN_STRIP, LG_VAR_FFN_TILE, LG_VAR_FFN_XP = 1, 2, 3
+LG_VAR_FFN_STRIP = 1
 LG_VAR_FFN_SAVE3, LG_VAR_FFN_SAVE5 = 1 << 2, 2 << 2
 LG_VAR_FFN_BWD32_PAIR, LG_VAR_FFN_DWBWD_TILE, LG_VAR_ATTN_BWD_R3 = 1 << 4, 1 << 5, 1 << 6
 LG_VAR_DSTEP_TILES = 1 << 7
@@ -52,7 +52,8 @@ def variant_from_env(env=None):
     """the variant word of a new plan from the diagnostic LG_* environment variables (read HERE, on the Python side, when an Engine
     builds a plan -- the shared library itself never looks at the environment).  Unset = 0 = the product path."""
     env = os.environ if env is None else env
-    v = {'strip': LG_VAR_FFN_STRIP, 'tile': LG_VAR_FFN_TILE, 'xp': LG_VAR_FFN_XP}.get(env.get('LG_FFN_IMPL', ''), 0)
+    # ('tile' and 'xp' named kernels the library no longer carries: they keep their field values, which lg_plan_create rejects by name)
+    v = {'strip': LG_VAR_FFN_STRIP, 'tile': 2, 'xp': 3}.get(env.get('LG_FFN_IMPL', ''), 0)
     v |= {'3': LG_VAR_FFN_SAVE3, '5': LG_VAR_FFN_SAVE5}.get(env.get('LG_FFN_SAVE', ''), 0)
     if env.get('LG_FFN_BWD32') == 'pair':
         v |= LG_VAR_FFN_BWD32_PAIR

@@ -2,7 +2,8 @@
 //   y = x + W3 gelu( dw3x3( W2 gelu( W1 LN(x) + b1 ) + b2 ) ) + b3
 // The three 1x1 convs are per-pixel GEMMs ([pixels, K] x [K, N], K,N in 16..256) and run on the matrix cores
 // with the exact-fp32 MFMA v_mfma_f32_16x16x4_f32 (parity mode: bit-for-bit an fp32 fma chain).
-// Two kernels, split at the depthwise conv (the only spatial coupling):
+// These are the exact-fp32 kernels of LG_VAR_FFN_STRIP (fp32 storage of the saved tensors only): k_ffn_strip at e = 16, k_ffn_fused at e = 32 and,
+// at e = 64, two kernels split at the depthwise conv (the only spatial coupling):
 //   k_ffn1: LN -> GEMM1 -> GELU -> GEMM2 -> h2            (hidden a1 never leaves LDS)
 //   k_ffn2: dw3x3 + GELU (halo read from h2 through L2) -> GEMM3 -> +residual, and emits the LayerNorm-ed
 //           global half the next block's FFT mixer consumes.
@@ -17,7 +18,7 @@
 // ------------------------------------------------------------------------------------------------
 // k_ffn1: each wave owns MW = 16*MT pixels end to end (no inter-wave dependency)
 // ------------------------------------------------------------------------------------------------
-template <int E, int MT, bool BF>
+template <int E, int MT>
 __global__ __launch_bounds__(256) void k_ffn1(Ffn1Args a) {
     constexpr int N1 = 4 * E, MW = 16 * MT, LDA = E + 4, LDH = N1 + 4;
     constexpr int LPP = 64 / MW;       // lanes per pixel in the load/LN phase (2 or 4)
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(256) void k_ffn1(Ffn1Args a) {
                     if (a.a1s) {
                         float av, gv;
                         gelu_both_f(h, av, gv);
-                        if (p0 + row < a.P) { HS<BF>::st1(a.a1s, (p0 + row) * N1 + col, av); HS<BF>::st1(a.g1s, (p0 + row) * N1 + col, gv); }
+                        if (p0 + row < a.P) { HS<false>::st1(a.a1s, (p0 + row) * N1 + col, av); HS<false>::st1(a.g1s, (p0 + row) * N1 + col, gv); }
                         bufH[row * LDH + col] = av;
                     } else {
                         bufH[row * LDH + col] = gelu_f(h);
@@ -105,7 +106,7 @@ __global__ __launch_bounds__(256) void k_ffn1(Ffn1Args a) {
 #pragma unroll
                 for (int v = 0; v < 4; ++v) {
                     const int row = mt * 16 + 4 * g + v;
-                    if (p0 + row < a.P) HS<BF>::st1(a.h2, (p0 + row) * N1 + col, acc[mt][nt][v] + bias);
+                    if (p0 + row < a.P) HS<false>::st1(a.h2, (p0 + row) * N1 + col, acc[mt][nt][v] + bias);
                 }
             }
     }
@@ -118,31 +119,28 @@ static int launch_ffn1_t(const Ffn1Args& a, hipStream_t s) {
     size_t lds = (size_t)4 * MW * ((E + 4) + (N1 + 4)) * sizeof(float);
     static DeviceOnce attr_once;
     if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_ffn1<E, MT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn1<E, MT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        hipError_t e = hipFuncSetAttribute((const void*)k_ffn1<E, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         if (e != hipSuccess) { lg_set_error("ffn1: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
         attr_once.done();
     }
     long per_wg = 4L * MW;
     int grid = (int)((a.P + per_wg - 1) / per_wg);
-    if (a.hbf) k_ffn1<E, MT, true><<<grid, 256, lds, s>>>(a);
-    else k_ffn1<E, MT, false><<<grid, 256, lds, s>>>(a);
+    k_ffn1<E, MT><<<grid, 256, lds, s>>>(a);
     LG_CHECK_LAUNCH();
     return 0;
 }
 
+// (the route runs the two-kernel form at e = 64 only -- FFN_FWD_UNFUSED -- and e = 64 keeps fp32 storage)
 int launch_ffn1(int e, const Ffn1Args& a, hipStream_t s) {
-    if (e == 16) return launch_ffn1_t<16, 2>(a, s);
-    if (e == 32) return launch_ffn1_t<32, 2>(a, s);
-    if (e == 64) return launch_ffn1_t<64, 1>(a, s);
-    lg_set_error("ffn1: e=%d unsupported", e);
+    if (e == 64 && !a.hbf) return launch_ffn1_t<64, 1>(a, s);
+    lg_set_error("ffn1: e=%d, hbf=%d unsupported", e, a.hbf);
     return -1;
 }
 
 // ------------------------------------------------------------------------------------------------
 // k_ffn2: workgroup = TY x TX pixel tile (M = TY*TX = 64*MT)
 // ------------------------------------------------------------------------------------------------
-template <int E, int MT, int TY, int TX, bool BF>
+template <int E, int MT, int TY, int TX>
 __global__ __launch_bounds__(256) void k_ffn2(Ffn2Args a, int tiles_x, int tiles_y) {
     constexpr int N1 = 4 * E, M = TY * TX, LDH = N1 + 4, LDO = E + 1, CQ = N1 / 4, NT3 = E / 16;
     static_assert(M == 64 * MT, "tile");
@@ -179,7 +177,7 @@ __global__ __launch_bounds__(256) void k_ffn2(Ffn2Args a, int tiles_x, int tiles
                     for (int dx = 0; dx < 3; ++dx) {
                         const int xx = x + dx - 1;
                         if (xx < 0 || xx >= a.w) continue;
-                        const float4 v = HS<BF>::ld4(a.h2, ((b * a.h + yy) * (long)a.w + xx) * N1 + 4 * q);
+                        const float4 v = HS<false>::ld4(a.h2, ((b * a.h + yy) * (long)a.w + xx) * N1 + 4 * q);
                         acc.x += wq[0][dy * 3 + dx] * v.x;
                         acc.y += wq[1][dy * 3 + dx] * v.y;
                         acc.z += wq[2][dy * 3 + dx] * v.z;
@@ -192,8 +190,8 @@ __global__ __launch_bounds__(256) void k_ffn2(Ffn2Args a, int tiles_x, int tiles
                     gelu_both_f(acc.x, av.x, gv.x); gelu_both_f(acc.y, av.y, gv.y);
                     gelu_both_f(acc.z, av.z, gv.z); gelu_both_f(acc.w, av.w, gv.w);
                     const long o = ((b * a.h + y) * (long)a.w + x) * N1 + 4 * q;
-                    HS<BF>::st4(a.a3s, o, av);
-                    HS<BF>::st4(a.g3s, o, gv);
+                    HS<false>::st4(a.a3s, o, av);
+                    HS<false>::st4(a.g3s, o, gv);
                     acc = av;
                 } else {
                     acc = make_float4(gelu_f(acc.x), gelu_f(acc.y), gelu_f(acc.z), gelu_f(acc.w));
@@ -256,46 +254,35 @@ static int launch_ffn2_t(const Ffn2Args& a, hipStream_t s) {
     size_t lds = (size_t)(M * (N1 + 4) + M * (E + 1)) * sizeof(float);
     static DeviceOnce attr_once;
     if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_ffn2<E, MT, TY, TX, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn2<E, MT, TY, TX, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        hipError_t e = hipFuncSetAttribute((const void*)k_ffn2<E, MT, TY, TX>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
         if (e != hipSuccess) { lg_set_error("ffn2: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
         attr_once.done();
     }
     int tiles_x = (a.w + TX - 1) / TX, tiles_y = (a.h + TY - 1) / TY;
     int grid = a.B * tiles_x * tiles_y;
-    if (a.hbf) k_ffn2<E, MT, TY, TX, true><<<grid, 256, lds, s>>>(a, tiles_x, tiles_y);
-    else k_ffn2<E, MT, TY, TX, false><<<grid, 256, lds, s>>>(a, tiles_x, tiles_y);
+    k_ffn2<E, MT, TY, TX><<<grid, 256, lds, s>>>(a, tiles_x, tiles_y);
     LG_CHECK_LAUNCH();
     return 0;
 }
 
 int launch_ffn2(int e, const Ffn2Args& a, hipStream_t s) {
-    if (e == 16) return launch_ffn2_t<16, 2, 8, 16>(a, s);
-    if (e == 32) return launch_ffn2_t<32, 2, 8, 16>(a, s);
-    if (e == 64) return launch_ffn2_t<64, 1, 8, 8>(a, s);
-    lg_set_error("ffn2: e=%d unsupported", e);
+    if (e == 64 && !a.hbf) return launch_ffn2_t<64, 1, 8, 8>(a, s);
+    lg_set_error("ffn2: e=%d, hbf=%d unsupported", e, a.hbf);
     return -1;
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_ffn_fused: the whole feed_forward half-block in one kernel.  A workgroup owns an 8x16 pixel tile; the two
+// k_ffn_fused (e = 32, fp32 storage): the whole feed_forward half-block in one kernel.  A workgroup owns an 8x16 pixel tile; the two
 // channel-mixing GEMMs are recomputed on the 10x18 halo tile (x1.41 of their flops) so that h2 -- the only tensor with
 // spatial coupling (depthwise 3x3) -- never leaves LDS.  HBM traffic drops from {x, h2 write, h2 read x taps, x, y}
-// to the algorithmic {x (+halo), y}.  LDS: LN(x) halo tile [192][e+4], h2 halo tile [180][4e+4], one [16][4e+4]
-// scratch per wave (a1 chunk, later gelu(dw(h2)) chunk): 81.7 KB at e=16 -> two workgroups per CU.
-// Optionally saves h1/h2/h3 of the inner pixels for the backward (live stage).
+// to the algorithmic {x (+halo), y}.  LDS: LN(x) halo tile [192][e+4], h2 halo tile [180][4e+4], a [48][4e+4] gelu(h1) row block
+// shared by the waves (later one [16][4e+4] gelu(dw(h2)) chunk per wave): one workgroup per CU.
+// SAVE: keeps gelu(h1) / gelu'(h1) / h2 / gelu(h3) / gelu'(h3) of the inner pixels for the backward (live stage).
 // ------------------------------------------------------------------------------------------------
-struct FfnFusedArgs {
-    Ffn1Args a1;
-    Ffn2Args a2;
-};
-
-template <int E, bool SAVE, bool BF>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E == 16 ? 2 : 1))) void k_ffn_fused(Ffn1Args a1, Ffn2Args a2, int tiles_x, int tiles_y, int ntiles) {
-    constexpr int N1 = 4 * E, TY = 8, TX = 16, HX = TX + 2, HY = TY + 2, NH = HX * HY /*180*/, MH = 192, M = TY * TX;
-    // LDA: at E = 16 the unpadded 64-byte row makes the A-fragment float4 reads one contiguous 1 KB (conflict-free) AND brings
-    // the workgroup under 80 KB of LDS, so two workgroups share a CU and one's MFMA phases overlap the other's GELU/LDS phases
-    constexpr int LDA = (E == 16 ? E : E + 4), LDH = N1 + 4, LDO = E + 1, CQ = N1 / 4, NT3 = E / 16;
+template <bool SAVE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void k_ffn_fused(Ffn1Args a1, Ffn2Args a2, int tiles_x, int tiles_y, int ntiles) {
+    constexpr int E = 32, N1 = 4 * E, TY = 8, TX = 16, HX = TX + 2, HY = TY + 2, NH = HX * HY /*180*/, MH = 192, M = TY * TX;
+    constexpr int LDA = E + 4, LDH = N1 + 4, LDO = E + 1, CQ = N1 / 4, NT3 = E / 16;
     static_assert(CQ <= 64 && 64 % CQ == 0, "quad mapping");
     extern __shared__ float smem[];
     float* bufA = smem;                       // [MH][LDA]   LN2(x) on the halo tile; later [M][LDO] output tile
@@ -318,30 +305,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E == 16 ? 2
     }
     for (int i = threadIdx.x; i < 9 * N1; i += 256) sDww[i] = a2.dww[i];
     for (int i = threadIdx.x; i < N1; i += 256) sDwb[i] = a2.dwb[i];
-    float b1r[4], b2r[4];   // biases of the h1 / h2 columns this lane holds in the MFMA C layout
+    float b1r[2], b2r[2];   // biases of the h1 / h2 columns this lane holds in the MFMA C layout
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-        const int col = (E == 32 ? wave * 32 : 0) + nt * 16 + r;
-        b1r[nt] = (nt < (E == 32 ? 2 : 4)) ? a1.b1[col] : 0.f;
-        b2r[nt] = (nt < (E == 32 ? 2 : 4)) ? a1.b2[col] : 0.f;
+    for (int nt = 0; nt < 2; ++nt) {
+        const int col = wave * 32 + nt * 16 + r;
+        b1r[nt] = a1.b1[col];
+        b2r[nt] = a1.b2[col];
     }
-    // weights as MFMA B fragments, resident in registers for ALL tiles of this (persistent) workgroup when they fit
-    // (e = 16: 16 + 64 + 16 VGPRs); otherwise every row chunk re-reads them through L1
-    constexpr bool RB = (E == 16);
-    float4 w1f[RB ? 4 : 1][1], w2f[RB ? 4 : 1][RB ? 4 : 1];
-    if (RB) {
-        load_bfrag<4, 1>(reinterpret_cast<float4(&)[4][1]>(w1f), a1.w1, E);
-        load_bfrag<4, 4>(reinterpret_cast<float4(&)[4][4]>(w2f), a1.w2, N1);
-    }
-    // e = 32: the weights do not fit one wave's registers (W2 alone is 64 KB), so P1 splits the OUTPUT COLUMNS across the four
+    // the weights do not fit one wave's registers (W2 alone is 64 KB), so P1 splits the OUTPUT COLUMNS across the four
     // waves instead of the rows: wave w owns columns [32w, 32w + 32) of h1 and h2 for all 192 halo rows and keeps exactly its
     // slices of W1 (16 VGPRs) and W2 (64 VGPRs) resident for the whole kernel -- no weight traffic in the tile loop
-    constexpr bool NS = (E == 32);
-    float4 w1p[NS ? 2 : 1][NS ? 2 : 1], w2p[NS ? 2 : 1][NS ? 8 : 1];
-    if (NS) {
-        load_bfrag<2, 2>(reinterpret_cast<float4(&)[2][2]>(w1p), a1.w1 + (size_t)(wave * 32) * E, E);
-        load_bfrag<2, 8>(reinterpret_cast<float4(&)[2][8]>(w2p), a1.w2 + (size_t)(wave * 32) * N1, N1);
-    }
+    float4 w1p[2][2], w2p[2][8];
+    load_bfrag<2, 2>(w1p, a1.w1 + (size_t)(wave * 32) * E, E);
+    load_bfrag<2, 8>(w2p, a1.w2 + (size_t)(wave * 32) * N1, N1);
 #pragma unroll 1
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     int t = tile;
@@ -378,8 +354,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E == 16 ? 2
             *reinterpret_cast<float4*>(bufA + m * LDA + 4 * k) = make_float4(xv[4 * k], xv[4 * k + 1], xv[4 * k + 2], xv[4 * k + 3]);
     }
     __syncthreads();
-    // ---- P1: per wave, 3 chunks of 16 halo pixels: GEMM1 -> GELU -> GEMM2 -> h2 tile
-    if constexpr (NS) {
+    // ---- P1: GEMM1 -> GELU -> GEMM2 -> h2 tile
+    {
         // four row blocks of 48 halo rows; per block: GEMM1 + GELU -> A2 (gelu(h1), shared by the waves) | barrier | GEMM2 -> h2 tile
         float* A2 = scr;   // [48][LDH]
         const int cw0 = wave * 32;
@@ -403,7 +379,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E == 16 ? 2
             for (int mt = 0; mt < 3; ++mt)
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            wave_gemm_rb<3, 2, 2>(acc, bufA + row0 * LDA, LDA, reinterpret_cast<const float4(&)[2][2]>(w1p));
+            wave_gemm_rb<3, 2, 2>(acc, bufA + row0 * LDA, LDA, w1p);
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) {
                 const int col = cw0 + nt * 16 + r;
@@ -417,8 +393,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E == 16 ? 2
                         if (SAVE) {
                             lg_v2f gv;
                             gelu2_both_f(hh, av, gv);
-                            if (inner[mt][v]) { HS<BF>::st1(a1.a1s, prow[mt][v] * N1 + col, av.x); HS<BF>::st1(a1.g1s, prow[mt][v] * N1 + col, gv.x); }
-                            if (inner[mt][v + 1]) { HS<BF>::st1(a1.a1s, prow[mt][v + 1] * N1 + col, av.y); HS<BF>::st1(a1.g1s, prow[mt][v + 1] * N1 + col, gv.y); }
+                            if (inner[mt][v]) { HS<false>::st1(a1.a1s, prow[mt][v] * N1 + col, av.x); HS<false>::st1(a1.g1s, prow[mt][v] * N1 + col, gv.x); }
+                            if (inner[mt][v + 1]) { HS<false>::st1(a1.a1s, prow[mt][v + 1] * N1 + col, av.y); HS<false>::st1(a1.g1s, prow[mt][v + 1] * N1 + col, gv.y); }
                         } else {
                             av = gelu2_f(hh);
                         }
@@ -431,7 +407,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E == 16 ? 2
             for (int mt = 0; mt < 3; ++mt)
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            wave_gemm_rb<3, 2, 8>(acc, A2, LDH, reinterpret_cast<const float4(&)[2][8]>(w2p));
+            wave_gemm_rb<3, 2, 8>(acc, A2, LDH, w2p);
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) {
                 const int col = cw0 + nt * 16 + r;
@@ -442,95 +418,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E == 16 ? 2
                     for (int v = 0; v < 4; ++v) {
                         const int m = row0 + mt * 16 + 4 * g + v;
                         const float hh = inimg[mt][v] ? acc[mt][nt][v] + bias : 0.f;   // dep_conv zero-pads h2
-                        if (SAVE && inner[mt][v]) HS<BF>::st1(a1.h2, prow[mt][v] * N1 + col, hh);
+                        if (SAVE && inner[mt][v]) HS<false>::st1(a1.h2, prow[mt][v] * N1 + col, hh);
                         if (m < NH) bufH2[m * LDH + col] = hh;
                     }
             }
             __syncthreads();   // A2 is rewritten by the next row block
         }
-    } else {
-    static_assert(NS || N1 == 64, "register-resident biases assume one 64-column block");
-    for (int ch = 0; ch < 3; ++ch) {
-        const int row0 = (wave * 3 + ch) * 16;
-        // validity / global pixel index of the 4 rows this lane owns in the C layout
-        long prow[4];
-        bool inner[4], inimg[4];
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int m = row0 + 4 * g + v;
-            const int hy = m / HX, hx = m - hy * HX;
-            const int y = y0 + hy - 1, x = x0 + hx - 1;
-            inimg[v] = (m < NH) && y >= 0 && y < h && x >= 0 && x < w;
-            inner[v] = inimg[v] && hy >= 1 && hy <= TY && hx >= 1 && hx <= TX;
-            prow[v] = (b * h + y) * (long)w + x;
-        }
-        for (int nc = 0; nc < N1; nc += 64) {
-            f32x4 acc[1][4];
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) acc[0][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (RB) wave_gemm_rb<1, 4, 1>(acc, bufA + row0 * LDA, LDA, reinterpret_cast<const float4(&)[4][1]>(w1f));
-            else wave_gemm<1, 4, E>(acc, bufA + row0 * LDA, LDA, a1.w1 + (size_t)nc * E);
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) {
-                const int col = nc + nt * 16 + r;
-                const float bias = b1r[nt];
-#pragma unroll
-                for (int v = 0; v < 4; v += 2) {   // packed pairs (v_pk_fma_f32)
-                    const lg_v2f hh = (lg_v2f){acc[0][nt][v] + bias, acc[0][nt][v + 1] + bias};
-                    lg_v2f av;
-                    if (SAVE) {
-                        lg_v2f gv;
-                        gelu2_both_f(hh, av, gv);
-                        if (inner[v]) { HS<BF>::st1(a1.a1s, prow[v] * N1 + col, av.x); HS<BF>::st1(a1.g1s, prow[v] * N1 + col, gv.x); }
-                        if (inner[v + 1]) { HS<BF>::st1(a1.a1s, prow[v + 1] * N1 + col, av.y); HS<BF>::st1(a1.g1s, prow[v + 1] * N1 + col, gv.y); }
-                    } else {
-                        av = gelu2_f(hh);
-                    }
-                    my[(4 * g + v) * LDH + col] = av.x;
-                    my[(4 * g + v + 1) * LDH + col] = av.y;
-                }
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        for (int nc = 0; nc < N1; nc += 64) {
-            f32x4 acc[1][4];
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) acc[0][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (RB) wave_gemm_rb<1, 4, 4>(acc, my, LDH, reinterpret_cast<const float4(&)[4][4]>(w2f));
-            else wave_gemm<1, 4, N1>(acc, my, LDH, a1.w2 + (size_t)nc * N1);
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) {
-                const int col = nc + nt * 16 + r;
-                const float bias = b2r[nt];
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int m = row0 + 4 * g + v;
-                    const float hh = inimg[v] ? acc[0][nt][v] + bias : 0.f;   // dep_conv zero-pads h2 (basic_module_unformer_v2.py:18)
-                    if (SAVE && inner[v]) HS<BF>::st1(a1.h2, prow[v] * N1 + col, hh);
-                    if (m < NH) bufH2[m * LDH + col] = hh;
-                }
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
     }
     __syncthreads();
     // ---- P2: per wave, 2 chunks of 16 inner pixels: dw3x3 + GELU -> scratch -> GEMM3 -> output tile (in bufA's space)
     float* bufO = bufA;
-    // the residual rows of P3 are requested now: their HBM round trip hides under the depthwise phase (e = 16 only: registers)
-    constexpr bool XPRE = (E == 16);
-    float4 xres[XPRE ? E / 4 : 1];
-    if (XPRE && threadIdx.x < M) {
-        const int ym = y0 + threadIdx.x / TX, xm = x0 + threadIdx.x % TX;
-        if (ym < h && xm < w) {
-            const float4* xs0 = reinterpret_cast<const float4*>(a2.x + ((b * h + ym) * (long)w + xm) * E);
-#pragma unroll
-            for (int k = 0; k < E / 4; ++k) xres[k] = xs0[k];
-        }
-    }
     {
-        // depthwise taps and the W3 fragments are (re)loaded per tile: keeping them live across P1 costs ~56 VGPRs
+        // depthwise taps are (re)loaded per tile: keeping them live across P1 costs ~40 VGPRs
         const int q = lane % CQ;
         float wq[4][9], bq[4];
 #pragma unroll
@@ -539,8 +438,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E == 16 ? 2
             for (int k = 0; k < 9; ++k) wq[u][k] = sDww[(4 * q + u) * 9 + k];
             bq[u] = sDwb[4 * q + u];
         }
-        float4 w3f[1][RB ? 4 : 1];
-        if (RB) load_bfrag<1, 4>(reinterpret_cast<float4(&)[1][4]>(w3f), a2.w3, N1);
         for (int ch = 0; ch < 2; ++ch) {
             const int m0 = (wave * 2 + ch) * 16;
             for (int mm = lane / CQ; mm < 16; mm += 64 / CQ) {
@@ -564,8 +461,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E == 16 ? 2
                     av = make_float4(a01.x, a01.y, a23.x, a23.y);
                     if (y < h && x < w) {
                         const long o = ((b * h + y) * (long)w + x) * N1 + 4 * q;
-                        HS<BF>::st4(a2.a3s, o, av);
-                        HS<BF>::st4(a2.g3s, o, make_float4(g01.x, g01.y, g23.x, g23.y));
+                        HS<false>::st4(a2.a3s, o, av);
+                        HS<false>::st4(a2.g3s, o, make_float4(g01.x, g01.y, g23.x, g23.y));
                     }
                 } else {
                     const lg_v2f a01 = gelu2_f((lg_v2f){acc.x, acc.y}), a23 = gelu2_f((lg_v2f){acc.z, acc.w});
@@ -578,8 +475,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E == 16 ? 2
             f32x4 acc3[1][NT3];
 #pragma unroll
             for (int nt = 0; nt < NT3; ++nt) acc3[0][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (RB) wave_gemm_rb<1, 1, 4>(reinterpret_cast<f32x4(&)[1][1]>(acc3), my, LDH, reinterpret_cast<const float4(&)[1][4]>(w3f));
-            else wave_gemm<1, NT3, N1>(acc3, my, LDH, a2.w3);
+            wave_gemm<1, NT3, N1>(acc3, my, LDH, a2.w3);
 #pragma unroll
             for (int nt = 0; nt < NT3; ++nt) {
                 const int col = nt * 16 + r;
@@ -602,7 +498,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E == 16 ? 2
             float4* yo = reinterpret_cast<float4*>(a2.y + p * E);
 #pragma unroll
             for (int k = 0; k < E / 4; ++k) {
-                float4 xr = XPRE ? xres[XPRE ? k : 0] : xs[k];
+                float4 xr = xs[k];
                 o[4 * k] = xr.x + bufO[m * LDO + 4 * k];
                 o[4 * k + 1] = xr.y + bufO[m * LDO + 4 * k + 1];
                 o[4 * k + 2] = xr.z + bufO[m * LDO + 4 * k + 2];
@@ -892,299 +788,23 @@ static int launch_ffn_strip(const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t 
     return 0;
 }
 
-template <int E>
-static int launch_ffn_fused_t(const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s) {
+static int launch_ffn_tile(const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s) {
     ProfScope prof__(LG_K_FFN2, s);
-    constexpr int N1 = 4 * E;
-    size_t lds = (size_t)(192 * (E == 16 ? E : E + 4) + 180 * (N1 + 4) + 4 * 16 * (N1 + 4)) * sizeof(float);
+    constexpr int E = 32, N1 = 4 * E;
+    size_t lds = (size_t)(192 * (E + 4) + 180 * (N1 + 4) + 4 * 16 * (N1 + 4)) * sizeof(float);
     static DeviceOnce attr_once;
     if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_ffn_fused<E, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_fused<E, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_fused<E, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
+        hipError_t e = hipFuncSetAttribute((const void*)k_ffn_fused<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_fused<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
         if (e != hipSuccess) { lg_set_error("ffn_fused: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
         attr_once.done();
     }
     int tiles_x = (a2.w + 15) / 16, tiles_y = (a2.h + 7) / 8;
     const int ntiles = a2.B * tiles_x * tiles_y;
-    const int cap = (E == 32) ? 256 : 512;   // persistent: resident workgroups per CU (2 at e = 16, 1 at e = 32) walk the tiles, weights stay in registers
-    const int grid = ntiles < cap ? ntiles : cap;
+    const int grid = ntiles < 256 ? ntiles : 256;   // persistent: one resident workgroup per CU walks the tiles, weights stay in registers
     const bool save = a1.a1s != nullptr;   // forward of the live stage: keep gelu / gelu' / h2 for the backward
-    if (save && a1.hbf) k_ffn_fused<E, true, true><<<grid, 256, lds, s>>>(a1, a2, tiles_x, tiles_y, ntiles);
-    else if (save) k_ffn_fused<E, true, false><<<grid, 256, lds, s>>>(a1, a2, tiles_x, tiles_y, ntiles);
-    else k_ffn_fused<E, false, false><<<grid, 256, lds, s>>>(a1, a2, tiles_x, tiles_y, ntiles);   // nothing stored: storage type irrelevant
-    LG_CHECK_LAUNCH();
-    return 0;
-}
-
-
-// ------------------------------------------------------------------------------------------------
-// k_ffn_fused_bf: throughput-mode variant of k_ffn_fused (lg_config.precision = 1): the three 1x1-conv GEMMs run on the
-// bf16 matrix cores (v_mfma_f32_16x16x32_bf16 / 16x16x16 for K = 16) with fp32 accumulation; their LDS operand tiles
-// (LN(x), gelu(h1) chunk, gelu(dw(h2)) chunk) are bf16; LayerNorm, bias, GELU, the h2 tile, the depthwise 3x3, the
-// residual and everything the backward saves are computed in fp32.  Weights stay fp32 in HBM and are converted to bf16
-// B fragments once per (persistent) workgroup.  Same tiling / phases as the fp32 kernel.
-// ------------------------------------------------------------------------------------------------
-template <int E, bool SAVE, bool BF>
-__global__ __launch_bounds__(256) void k_ffn_fused_bf(Ffn1Args a1, Ffn2Args a2, int tiles_x, int tiles_y, int ntiles) {
-    constexpr int N1 = 4 * E, TY = 8, TX = 16, HX = TX + 2, HY = TY + 2, NH = HX * HY /*180*/, MH = 192, M = TY * TX;
-    constexpr int LDA = E + 8, LDS16 = N1 + 8 /* halves */, LDH = N1 + 4, LDO = E + 1, CQ = N1 / 4, NT3 = E / 16;
-    constexpr int KB2 = N1 / 32;   // 32-deep k blocks of GEMM2 / GEMM3
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* bufH2 = smem;                                   // [NH][LDH] fp32  h2 on the halo tile (0 outside the image)
-    float* bufO = bufH2 + NH * LDH;                        // [M][LDO]  fp32  output tile
-    __bf16* bufA = reinterpret_cast<__bf16*>(bufO + M * LDO + 3);   // [MH][LDA] bf16 LN2(x) on the halo tile (16-byte aligned below)
-    bufA = reinterpret_cast<__bf16*>((reinterpret_cast<uintptr_t>(bufA) + 15) & ~(uintptr_t)15);
-    __bf16* scr = bufA + MH * LDA;                         // [4][16][LDS16] bf16 per-wave chunk
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
-    __bf16* my = scr + wave * 16 * LDS16;
-    const int h = a2.h, w = a2.w;
-    // small parameters staged once per workgroup (see k_ffn_fused); the wide biases stay global here (col varies per nc block)
-    __shared__ __attribute__((aligned(16))) float sPar[5 * E + 10 * N1 + 2 * N1];
-    float* sLn2g = sPar;            float* sLn2b = sPar + E;
-    float* sN1g = sPar + 2 * E;     float* sN1b = sPar + 3 * E;
-    float* sB3 = sPar + 4 * E;      float* sDww = sPar + 5 * E;     // [N1][9]
-    float* sDwb = sDww + 9 * N1;    float* sB1 = sDwb + N1;         float* sB2 = sB1 + N1;
-    for (int i = threadIdx.x; i < E; i += 256) {
-        sLn2g[i] = a1.ln2g[i]; sLn2b[i] = a1.ln2b[i]; sB3[i] = a2.b3[i];
-        sN1g[i] = a2.g ? a2.n1g[i] : 0.f; sN1b[i] = a2.g ? a2.n1b[i] : 0.f;
-    }
-    for (int i = threadIdx.x; i < 9 * N1; i += 256) sDww[i] = a2.dww[i];
-    for (int i = threadIdx.x; i < N1; i += 256) { sDwb[i] = a2.dwb[i]; sB1[i] = a1.b1[i]; sB2[i] = a1.b2[i]; }
-    // B fragments (bf16) for the whole life of the workgroup
-    s16x4 w1k16[4];
-    bf16x8 w2f[4][KB2], w3f[NT3][KB2];
-    if constexpr (E == 16) {
-        load_bfrag_bf16_k16<4>(w1k16, a1.w1);
-        load_bfrag_bf16<4, KB2>(w2f, a1.w2, N1);
-        load_bfrag_bf16<NT3, KB2>(w3f, a2.w3, N1);
-    }
-#pragma unroll 1
-    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    int t = tile;
-    const int tx_i = t % tiles_x;
-    t /= tiles_x;
-    const int ty_i = t % tiles_y;
-    const long b = t / tiles_y;
-    const int y0 = ty_i * TY, x0 = tx_i * TX;
-    __syncthreads();
-    // ---- P0: halo tile load + LayerNorm (fp32) -> bf16 rows
-    if (threadIdx.x < MH) {
-        const int m = threadIdx.x;
-        const int hy = m / HX, hx = m - hy * HX;
-        const int y = y0 + hy - 1, x = x0 + hx - 1;
-        float xv[E];
-        const bool in = (m < NH) && y >= 0 && y < h && x >= 0 && x < w;
-        if (in) {
-            const float4* src = reinterpret_cast<const float4*>(a1.x + ((b * h + y) * (long)w + x) * E);
-#pragma unroll
-            for (int k = 0; k < E / 4; ++k) {
-                float4 v = src[k];
-                xv[4 * k] = v.x; xv[4 * k + 1] = v.y; xv[4 * k + 2] = v.z; xv[4 * k + 3] = v.w;
-            }
-            float mu, rstd;
-            ln_stats<E>(xv, mu, rstd);
-#pragma unroll
-            for (int c = 0; c < E; ++c) xv[c] = (xv[c] - mu) * rstd * sLn2g[c] + sLn2b[c];
-        } else {
-#pragma unroll
-            for (int c = 0; c < E; ++c) xv[c] = 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < E / 4; ++k) {
-            const bf16x4 hv = (bf16x4){(__bf16)xv[4 * k], (__bf16)xv[4 * k + 1], (__bf16)xv[4 * k + 2], (__bf16)xv[4 * k + 3]};
-            *reinterpret_cast<bf16x4*>(bufA + m * LDA + 4 * k) = hv;
-        }
-    }
-    __syncthreads();
-    // ---- P1: per wave, 3 chunks of 16 halo pixels: GEMM1 -> GELU -> GEMM2 -> h2 tile
-    for (int ch = 0; ch < 3; ++ch) {
-        const int row0 = (wave * 3 + ch) * 16;
-        long prow[4];
-        bool inner[4], inimg[4];
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int m = row0 + 4 * g + v;
-            const int hy = m / HX, hx = m - hy * HX;
-            const int y = y0 + hy - 1, x = x0 + hx - 1;
-            inimg[v] = (m < NH) && y >= 0 && y < h && x >= 0 && x < w;
-            inner[v] = inimg[v] && hy >= 1 && hy <= TY && hx >= 1 && hx <= TX;
-            prow[v] = (b * h + y) * (long)w + x;
-        }
-        for (int nc = 0; nc < N1; nc += 64) {
-            f32x4 acc[1][4];
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) acc[0][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if constexpr (E == 16) {
-                wave_gemm_bf_k16<1, 4>(acc, bufA + row0 * LDA, LDA, w1k16);
-            } else {
-                constexpr int KB1 = E / 32;
-                bf16x8 wf[4][KB1];
-                load_bfrag_bf16<4, KB1>(wf, a1.w1 + (size_t)nc * E, E);
-                wave_gemm_bf<1, 4, KB1>(acc, bufA + row0 * LDA, LDA, wf);
-            }
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) {
-                const int col = nc + nt * 16 + r;
-                const float bias = sB1[col];
-#pragma unroll
-                for (int v = 0; v < 4; v += 2) {   // packed pairs (v_pk_fma_f32)
-                    const lg_v2f hh = (lg_v2f){acc[0][nt][v] + bias, acc[0][nt][v + 1] + bias};
-                    lg_v2f av;
-                    if (SAVE) {
-                        lg_v2f gv;
-                        gelu2_both_f(hh, av, gv);
-                        if (inner[v]) { HS<BF>::st1(a1.a1s, prow[v] * N1 + col, av.x); HS<BF>::st1(a1.g1s, prow[v] * N1 + col, gv.x); }
-                        if (inner[v + 1]) { HS<BF>::st1(a1.a1s, prow[v + 1] * N1 + col, av.y); HS<BF>::st1(a1.g1s, prow[v + 1] * N1 + col, gv.y); }
-                    } else {
-                        av = gelu2_f(hh);
-                    }
-                    my[(4 * g + v) * LDS16 + col] = (__bf16)av.x;
-                    my[(4 * g + v + 1) * LDS16 + col] = (__bf16)av.y;
-                }
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        for (int nc = 0; nc < N1; nc += 64) {
-            f32x4 acc[1][4];
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) acc[0][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if constexpr (E == 16) {
-                wave_gemm_bf<1, 4, KB2>(acc, my, LDS16, w2f);
-            } else {
-                bf16x8 wf[4][KB2];
-                load_bfrag_bf16<4, KB2>(wf, a1.w2 + (size_t)nc * N1, N1);
-                wave_gemm_bf<1, 4, KB2>(acc, my, LDS16, wf);
-            }
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) {
-                const int col = nc + nt * 16 + r;
-                const float bias = sB2[col];
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int m = row0 + 4 * g + v;
-                    const float hh = inimg[v] ? acc[0][nt][v] + bias : 0.f;   // dep_conv zero-pads h2 (basic_module_unformer_v2.py:18)
-                    if (SAVE && inner[v]) HS<BF>::st1(a1.h2, prow[v] * N1 + col, hh);
-                    if (m < NH) bufH2[m * LDH + col] = hh;
-                }
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-    __syncthreads();
-    // ---- P2: per wave, 2 chunks of 16 inner pixels: dw3x3 + GELU (fp32) -> bf16 scratch -> GEMM3 -> output tile
-    {
-        const int q = lane % CQ;
-        float wq[4][9], bq[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-#pragma unroll
-            for (int k = 0; k < 9; ++k) wq[u][k] = sDww[(4 * q + u) * 9 + k];
-            bq[u] = sDwb[4 * q + u];
-        }
-        for (int ch = 0; ch < 2; ++ch) {
-            const int m0 = (wave * 2 + ch) * 16;
-            for (int mm = lane / CQ; mm < 16; mm += 64 / CQ) {
-                const int m = m0 + mm;
-                const int ty = m / TX, tx = m - ty * TX;
-                float4 acc = make_float4(bq[0], bq[1], bq[2], bq[3]);
-#pragma unroll
-                for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                    for (int dx = 0; dx < 3; ++dx) {
-                        const float4 v = *reinterpret_cast<const float4*>(bufH2 + ((ty + dy) * HX + tx + dx) * LDH + 4 * q);
-                        acc.x += wq[0][dy * 3 + dx] * v.x; acc.y += wq[1][dy * 3 + dx] * v.y;
-                        acc.z += wq[2][dy * 3 + dx] * v.z; acc.w += wq[3][dy * 3 + dx] * v.w;
-                    }
-                const int y = y0 + ty, x = x0 + tx;
-                float4 av;
-                if (SAVE) {
-                    lg_v2f a01, a23, g01, g23;
-                    gelu2_both_f((lg_v2f){acc.x, acc.y}, a01, g01);
-                    gelu2_both_f((lg_v2f){acc.z, acc.w}, a23, g23);
-                    av = make_float4(a01.x, a01.y, a23.x, a23.y);
-                    if (y < h && x < w) {
-                        const long o = ((b * h + y) * (long)w + x) * N1 + 4 * q;
-                        HS<BF>::st4(a2.a3s, o, av);
-                        HS<BF>::st4(a2.g3s, o, make_float4(g01.x, g01.y, g23.x, g23.y));
-                    }
-                } else {
-                    const lg_v2f a01 = gelu2_f((lg_v2f){acc.x, acc.y}), a23 = gelu2_f((lg_v2f){acc.z, acc.w});
-                    av = make_float4(a01.x, a01.y, a23.x, a23.y);
-                }
-                *reinterpret_cast<bf16x4*>(my + mm * LDS16 + 4 * q) = (bf16x4){(__bf16)av.x, (__bf16)av.y, (__bf16)av.z, (__bf16)av.w};
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            f32x4 acc3[1][NT3];
-#pragma unroll
-            for (int nt = 0; nt < NT3; ++nt) acc3[0][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if constexpr (E == 16) {
-                wave_gemm_bf<1, NT3, KB2>(acc3, my, LDS16, w3f);
-            } else {
-                bf16x8 wf[NT3][KB2];
-                load_bfrag_bf16<NT3, KB2>(wf, a2.w3, N1);
-                wave_gemm_bf<1, NT3, KB2>(acc3, my, LDS16, wf);
-            }
-#pragma unroll
-            for (int nt = 0; nt < NT3; ++nt) {
-                const int col = nt * 16 + r;
-                const float bias = sB3[col];
-#pragma unroll
-                for (int v = 0; v < 4; ++v) bufO[(m0 + 4 * g + v) * LDO + col] = acc3[0][nt][v] + bias;
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
-    __syncthreads();
-    // ---- P3: residual, store, planar LN1 half for the next block (fp32)
-    if (threadIdx.x < M) {
-        const int m = threadIdx.x;
-        const int y = y0 + m / TX, x = x0 + m % TX;
-        if (y < h && x < w) {
-            const long p = (b * h + y) * (long)w + x;
-            float o[E];
-            const float4* xs = reinterpret_cast<const float4*>(a2.x + p * E);
-            float4* yo = reinterpret_cast<float4*>(a2.y + p * E);
-#pragma unroll
-            for (int k = 0; k < E / 4; ++k) {
-                float4 xr = xs[k];
-                o[4 * k] = xr.x + bufO[m * LDO + 4 * k];
-                o[4 * k + 1] = xr.y + bufO[m * LDO + 4 * k + 1];
-                o[4 * k + 2] = xr.z + bufO[m * LDO + 4 * k + 2];
-                o[4 * k + 3] = xr.w + bufO[m * LDO + 4 * k + 3];
-                yo[k] = make_float4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
-            }
-            if (a2.g) {
-                float mu, rstd;
-                ln_stats<E>(o, mu, rstd);
-                const long hw = (long)h * w, s = (long)y * w + x;
-#pragma unroll
-                for (int n = E / 2; n < E; ++n) a2.g[(b * (E / 2) + (n - E / 2)) * hw + s] = (o[n] - mu) * rstd * sN1g[n] + sN1b[n];
-            }
-        }
-    }
-    }   // tiles of this workgroup
-}
-
-template <int E>
-static int launch_ffn_fused_bf_t(const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s) {
-    ProfScope prof__(LG_K_FFN2, s);
-    constexpr int N1 = 4 * E;
-    const size_t lds = (size_t)(180 * (N1 + 4) + 128 * (E + 1) + 8) * sizeof(float) + (size_t)(192 * (E + 8) + 4 * 16 * (N1 + 8)) * 2;
-    static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_ffn_fused_bf<E, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_fused_bf<E, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e != hipSuccess) { lg_set_error("ffn_fused_bf: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_once.done();
-    }
-    int tiles_x = (a2.w + 15) / 16, tiles_y = (a2.h + 7) / 8;
-    const int ntiles = a2.B * tiles_x * tiles_y;
-    const int grid = ntiles < 512 ? ntiles : 512;
-    if (a1.a1s != nullptr) k_ffn_fused_bf<E, true, true><<<grid, 256, lds, s>>>(a1, a2, tiles_x, tiles_y, ntiles);
-    else k_ffn_fused_bf<E, false, true><<<grid, 256, lds, s>>>(a1, a2, tiles_x, tiles_y, ntiles);
+    if (save) k_ffn_fused<true><<<grid, 256, lds, s>>>(a1, a2, tiles_x, tiles_y, ntiles);   // (fp32 storage: launch_ffn_fused turns bf16 away)
+    else k_ffn_fused<false><<<grid, 256, lds, s>>>(a1, a2, tiles_x, tiles_y, ntiles);
     LG_CHECK_LAUNCH();
     return 0;
 }
@@ -1194,16 +814,6 @@ static int launch_ffn_fused_bf_t(const Ffn1Args& a1, const Ffn2Args& a2, hipStre
 int launch_ffn_fused(int e, const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s) {
     const bool five = a1.a1s && a1.g1s && a1.h2 && a2.a3s && a2.g3s, none = !a1.a1s && !a1.g1s && !a2.a3s && !a2.g3s;
     switch (a1.kernel) {
-#ifdef LG_BUILD_AB   // round 1's bf16 tile kernels, its f32 tile kernel at e = 16 and k_ffn_xp: A/B builds only (lg_plan_create rejects their variants otherwise)
-    case FFN_FWD_TILE_BF16:
-        if (!a1.hbf || !(five || none)) break;
-        if (e == 16) return launch_ffn_fused_bf_t<16>(a1, a2, s);
-        if (e == 32) return launch_ffn_fused_bf_t<32>(a1, a2, s);
-        break;
-    case FFN_FWD_XP:
-        if (e != 16 || a1.hbf || !(five || none)) break;
-        return launch_ffn_xp(a1, a2, s);
-#endif
     case FFN_FWD_XR:
         if (e != 16 || a1.a1s || a1.g1s || a2.g3s || (a2.a3s && !a1.h2)) break;
         return launch_ffn_xr(a1, a2, s);
@@ -1220,12 +830,8 @@ int launch_ffn_fused(int e, const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t 
         if (e != 16 || a1.hbf || !(five || none)) break;
         return launch_ffn_strip(a1, a2, s);
     case FFN_FWD_TILE:
-        if (a1.hbf || !(five || none)) break;
-#ifdef LG_BUILD_AB
-        if (e == 16) return launch_ffn_fused_t<16>(a1, a2, s);
-#endif
-        if (e == 32) return launch_ffn_fused_t<32>(a1, a2, s);
-        break;
+        if (e != 32 || a1.hbf || !(five || none)) break;
+        return launch_ffn_tile(a1, a2, s);
     default: break;
     }
     lg_set_error("ffn: forward kernel %d does not run e=%d, hbf=%d with these save slots (a1 %d, g1 %d, h2 %d, a3 %d, g3 %d)", a1.kernel, e, a1.hbf,

@@ -255,13 +255,14 @@ static int launch_ffn_dw_bwd_t(const FfnDwBwdArgs& a, hipStream_t s) {
     static DeviceOnce attr_once;
     if (attr_once.need()) {
         hipError_t e = hipFuncSetAttribute((const void*)k_ffn_dw_bwd<E, false, CG, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_dw_bwd<E, true, CG, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        if constexpr (E != 64) { if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_dw_bwd<E, true, CG, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); }
         if constexpr (E == 16) { if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_dw_bwd<E, false, CG, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); }
         if (e != hipSuccess) { lg_set_error("ffn_dw_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
         attr_once.done();
     }
     if (a.pre && (a.hbf || E != 16)) { lg_set_error("ffn_dw_bwd: pre-activation saves are fp32, e = 16"); return -2; }
-    if (a.hbf) k_ffn_dw_bwd<E, true, CG, false><<<grid, 256, lds, s>>>(a, tiles_x, tiles_y);
+    if (a.hbf && E == 64) { lg_set_error("ffn_dw_bwd: e = 64 keeps fp32 storage"); return -2; }   // (route.hip: hbf is off at e = 64 in both precisions)
+    if (a.hbf) { if constexpr (E != 64) k_ffn_dw_bwd<E, true, CG, false><<<grid, 256, lds, s>>>(a, tiles_x, tiles_y); }
     else if (a.pre) { if constexpr (E == 16) k_ffn_dw_bwd<E, false, CG, true><<<grid, 256, lds, s>>>(a, tiles_x, tiles_y); }
     else k_ffn_dw_bwd<E, false, CG, false><<<grid, 256, lds, s>>>(a, tiles_x, tiles_y);
     LG_CHECK_LAUNCH();
@@ -677,8 +678,10 @@ static int launch_ffn1_bwd_t(const Ffn1BwdArgs& a, hipStream_t s) {
     static DeviceOnce attr_once;
     if (attr_once.need()) {
         hipError_t e = hipFuncSetAttribute((const void*)k_ffn1_bwd<E, MT, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn1_bwd<E, MT, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if constexpr (E == 16) { if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn1_bwd<E, MT, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); }
+        if constexpr (E == 16) {
+            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn1_bwd<E, MT, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn1_bwd<E, MT, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        }
         if (e != hipSuccess) { lg_set_error("ffn1_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
         attr_once.done();
     }
@@ -690,7 +693,9 @@ static int launch_ffn1_bwd_t(const Ffn1BwdArgs& a, hipStream_t s) {
     if (!ffn1_bwd_fuses_w1(E) && (!a.dh1 || !a.y2)) { lg_set_error("ffn1_bwd: dh1 / y2 outputs missing"); return -2; }
     if (ffn1_bwd_fuses_w2(E, a.pre) && (!a.w2slab || !a.d_w2 || !a.d_b2)) { lg_set_error("ffn1_bwd: dW2 slab / destinations missing"); return -2; }
     if (a.pre && (a.hbf || E != 16)) { lg_set_error("ffn1_bwd: pre-activation saves are fp32, e = 16"); return -2; }
-    if (a.hbf) k_ffn1_bwd<E, MT, true, false><<<grid, 256, lds, s>>>(a, nchunks);
+    // (route.hip: the tile kernel is the pixelwise half at e = 32 only behind the fp32 kernels of LG_VAR_FFN_STRIP, and e = 64 keeps fp32 storage)
+    if (a.hbf && E != 16) { lg_set_error("ffn1_bwd: bf16 storage runs e = 16 only"); return -2; }
+    if (a.hbf) { if constexpr (E == 16) k_ffn1_bwd<E, MT, true, false><<<grid, 256, lds, s>>>(a, nchunks); }
     else if (a.pre) { if constexpr (E == 16) k_ffn1_bwd<E, MT, false, true><<<grid, 256, lds, s>>>(a, nchunks); }
     else k_ffn1_bwd<E, MT, false, false><<<grid, 256, lds, s>>>(a, nchunks);
     LG_CHECK_LAUNCH();

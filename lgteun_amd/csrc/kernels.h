@@ -235,7 +235,7 @@ int launch_ffn_scales(int n, const FfnPrepJob* jobs, float* out, hipStream_t s, 
 struct SplitWJob { const float *w1, *w2, *w3, *scales; void* out; int e, np; };
 struct SplitWTable { SplitWJob j[LG_MAX_FFN_PREP_JOBS]; };
 int launch_split_w_jobs(int n, const SplitWJob* jobs, hipStream_t s);
-int launch_ffn1(int e, const Ffn1Args& a, hipStream_t s);
+int launch_ffn1(int e, const Ffn1Args& a, hipStream_t s);   // k_ffn1 + k_ffn2 (FFN_FWD_UNFUSED): e = 64, fp32 storage
 struct Ffn2Args {
     const void* h2;   // [B,h,w,4e]
     const float* x;   // [B,h,w,e] residual input
@@ -252,7 +252,6 @@ int launch_ffn2(int e, const Ffn2Args& a, hipStream_t s);
 int launch_ffn_fused(int e, const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s);
 int launch_ffn_xs(const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s);   // e = 16, fp32 storage (k_ffn_x.hip)
 int launch_ffn_xr(const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s);   // e = 16, f16 pairs, fp32 storage: the register chain (k_ffn_xr.hip, round 6)
-int launch_ffn_xp(const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s);   // e = 16, software-pipelined halo pass (k_ffn_xp.hip)
 int launch_ffn_x32(const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s);  // e = 32, fp32 storage (k_ffn_x32.hip)
 size_t ffn_wsplit_bytes(int e);   // bytes of a1.wsplit for hidden width 4e
 // pre-split weight fragments: np = 3 three bf16 pieces, np = 1 one RNE bf16 piece, np = 2 f16 pairs of W * scales[3 + which matrix] (k_ffn_prep.hip)

@@ -12,9 +12,7 @@ enum FfnFwdKernel {
     FFN_FWD_X32,        // k_ffn_x32, e = 32
     FFN_FWD_X64,        // k_ffn1_x64 + k_ffn2_x64, e = 64 (h2 through HBM)
     FFN_FWD_STRIP,      // k_ffn_strip: f32-MFMA strip kernel, e = 16
-    FFN_FWD_TILE,       // k_ffn_fused: round 1's f32-MFMA tile kernel (e = 16: `make AB=1` builds only; e = 32: every build)
-    FFN_FWD_TILE_BF16,  // k_ffn_fused_bf: round 1's bf16 tile kernel (`make AB=1` builds only)
-    FFN_FWD_XP,         // k_ffn_xp: software-pipelined k_ffn_xs, e = 16 (`make AB=1` builds only)
+    FFN_FWD_TILE,       // k_ffn_fused: round 1's f32-MFMA tile kernel, e = 32
     FFN_FWD_UNFUSED     // k_ffn1 + k_ffn2
 };
 enum FfnArith { FFN_ARITH_F32, FFN_ARITH_BF16, FFN_ARITH_F16X2, FFN_ARITH_BF16X3 };   // f32 MFMA | one bf16 piece | f16 pairs with operand scales | three bf16 pieces
@@ -59,6 +57,6 @@ struct LgRoute {
     bool reduce_per_block;   // one parameter-gradient reduce launch per block instead of one per pass
 };
 
-// 0, or -2 with lg_set_error for a variant word this build does not carry
+// 0, or -2 with lg_set_error for a variant word the library does not carry
 int lg_resolve_route(const lg_config& cfg, LgRoute* r);
 int lg_describe_route(const lg_config& cfg, const LgRoute& r, char* buf, size_t n);

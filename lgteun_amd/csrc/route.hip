@@ -1,9 +1,9 @@
 // lg_resolve_route: the ONE place that turns lg_config.variant / precision / C / H / W into kernels (host code only).
 //
 // bit (include/lgteun_hip.h)     Python side (_lib.variant_from_env)   effect
-// LG_VAR_FFN_IMPL_MASK           LG_FFN_IMPL = strip | tile | xp       fused FFN forward: 1 the f32-MFMA strip kernel, 2 round 1's tile kernels, 3 k_ffn_xp
-//                                                                      (2, 3 and any of them with precision = 1: `make AB=1` builds); the backward then
-//                                                                      runs round 2's tile kernels on the five-tensor save
+// LG_VAR_FFN_IMPL_MASK           LG_FFN_IMPL = strip                   1 (LG_VAR_FFN_STRIP, precision = 0 only): round 1's f32-MFMA kernels -- k_ffn_strip at e = 16,
+//                                                                      k_ffn_fused at e = 32, k_ffn1 + k_ffn2 at e = 64; the backward then runs round 2's tile
+//                                                                      kernels on the five-tensor save.  2 and 3 are not carried: lg_plan_create rejects them
 // LG_VAR_FFN_SAVE3 / _SAVE5      LG_FFN_SAVE = 3 | 5                   e = 16: keep h1 / h2 / h3 (3; precision = 1: as 5) or gelu(h1), gelu'(h1), h2, gelu(h3),
 //                                                                      gelu'(h3) (5) instead of h2 / h3 (default: h1 re-computed by k_ffn1_bwd_xs)
 // LG_VAR_FFN_BWD32_PAIR          LG_FFN_BWD32 = pair                   e = 32 pixelwise half: k_ffn1_bwd_x32 + k_wgrad on saved gelu(h1) / gelu'(h1) instead of k_ffn1_bwd_xs<32>
@@ -31,14 +31,14 @@ static void resolve_ffn(const lg_config& cfg, int e, int h, int w, FfnRoute& f) 
     const uint32_t v = cfg.variant;
     const int impl = (int)(v & LG_VAR_FFN_IMPL_MASK);
     const uint32_t sv = v & LG_VAR_FFN_SAVE_MASK;
-    const bool split = impl == 0;   // the split-arithmetic kernels of rounds 2 - 6; otherwise round 1's f32-MFMA / bf16 kernels with round 2's tile backward
+    const bool split = impl == 0;   // the split-arithmetic kernels of rounds 2 - 6; otherwise (precision = 0 only) round 1's f32-MFMA kernels with round 2's tile backward
     const bool strips = (h & 7) == 0 && (w & 15) == 0;   // a strip is 16 columns wide, every output pixel of a step inside the plane (level 0: always)
     f.e = e; f.h = h; f.w = w;
     // precision = 1 applies where a plain-bf16 kernel exists: the e = 64 half-blocks have only the round-1 f32-MFMA pair in that form (436 + 372 us
     // against 123 + 95 us for the split-bf16 k_ffn_x64 pair), so they run the default kernels with fp32 storage in both modes
     f.hbf = cfg.precision == 1 && e != 64;
     f.scales = cfg.precision == 0 && split && !(v & LG_VAR_FFN_BF16X3);
-    f.arith = !split ? (f.hbf ? FFN_ARITH_BF16 : FFN_ARITH_F32) : f.hbf ? FFN_ARITH_BF16 : f.scales ? FFN_ARITH_F16X2 : FFN_ARITH_BF16X3;
+    f.arith = !split ? FFN_ARITH_F32 : f.hbf ? FFN_ARITH_BF16 : f.scales ? FFN_ARITH_F16X2 : FFN_ARITH_BF16X3;
     f.wsplit_np = e < 32 ? 0 : f.hbf ? 1 : f.scales ? 2 : 3;   // (prep_stages fills the slot of every e >= 32 block, whichever kernel runs)
 
     // ---- backward.  e = 16 keeps h2 / h3 (save form 2), h1 / h2 / h3 (3, fp32 storage only) or the five GELU-free tensors (5, and every other width)
@@ -62,10 +62,9 @@ static void resolve_ffn(const lg_config& cfg, int e, int h, int w, FfnRoute& f) 
 
     // ---- forward
     FfnFwdKernel k;
-    if (e == 16) k = impl == 3 ? FFN_FWD_XP : impl == 2 ? FFN_FWD_TILE : impl == 1 ? FFN_FWD_STRIP : FFN_FWD_XS;
+    if (e == 16) k = split ? FFN_FWD_XS : FFN_FWD_STRIP;
     else if (e == 32) k = split ? FFN_FWD_X32 : FFN_FWD_TILE;
     else k = split ? FFN_FWD_X64 : FFN_FWD_UNFUSED;
-    if (f.hbf && !split) k = FFN_FWD_TILE_BF16;
     f.fwd[0] = f.fwd[1] = k;
     if (e == 16 && xr_built) {   // the register chain where it exists: nothing saved, or h2 (/ h3)
         f.fwd[0] = FFN_FWD_XR;
@@ -89,10 +88,8 @@ int lg_resolve_route(const lg_config& cfg, LgRoute* r) {
     const uint32_t v = cfg.variant;
     if (v & ~LG_VAR_ALL) { lg_set_error("plan_create: unknown variant bits 0x%x", v & ~LG_VAR_ALL); return -2; }
     if ((v & LG_VAR_FFN_SAVE_MASK) == LG_VAR_FFN_SAVE_MASK) { lg_set_error("plan_create: invalid FFN save variant"); return -2; }
-#ifndef LG_BUILD_AB
-    if ((v & LG_VAR_FFN_IMPL_MASK) >= LG_VAR_FFN_TILE) { lg_set_error("plan_create: FFN variants 2 / 3 exist in `make AB=1` builds only"); return -2; }
-    if (cfg.precision == 1 && (v & LG_VAR_FFN_IMPL_MASK)) { lg_set_error("plan_create: precision = 1 with an FFN variant exists in `make AB=1` builds only"); return -2; }
-#endif
+    if ((v & LG_VAR_FFN_IMPL_MASK) > LG_VAR_FFN_STRIP) { lg_set_error("plan_create: FFN implementation field (LG_VAR_FFN_IMPL_MASK) = %u: only 0 and LG_VAR_FFN_STRIP exist", v & LG_VAR_FFN_IMPL_MASK); return -2; }
+    if (cfg.precision == 1 && (v & LG_VAR_FFN_IMPL_MASK)) { lg_set_error("plan_create: FFN implementation field (LG_VAR_FFN_IMPL_MASK): LG_VAR_FFN_STRIP is an fp32 kernel set, precision = 1 has none"); return -2; }
     const int E = 4 * cfg.C;
     resolve_ffn(cfg, E, cfg.H, cfg.W, r->ffn[0]);
     resolve_ffn(cfg, 2 * E, cfg.H / 2, cfg.W / 2, r->ffn[1]);
@@ -116,7 +113,7 @@ static const char* slots_text(unsigned slots, bool a1_pre, bool a3_pre, char (&b
 }
 
 int lg_describe_route(const lg_config& cfg, const LgRoute& r, char* buf, size_t n) {
-    static const char* const fwd_names[] = {"k_ffn_xr", "k_ffn_xs", "k_ffn_x32", "k_ffn1_x64+k_ffn2_x64", "k_ffn_strip", "k_ffn_fused", "k_ffn_fused_bf", "k_ffn_xp", "k_ffn1+k_ffn2"};
+    static const char* const fwd_names[] = {"k_ffn_xr", "k_ffn_xs", "k_ffn_x32", "k_ffn1_x64+k_ffn2_x64", "k_ffn_strip", "k_ffn_fused", "k_ffn1+k_ffn2"};
     static const char* const arith_names[] = {"f32", "bf16", "f16x2", "bf16x3"};
     static const char* const dw_names[] = {"k_ffn_dw_bwd_xs", "k_ffn_dw_bwd_h", "k_ffn_dw_bwd"};
     static const char* const px_names[] = {"k_ffn1_bwd_xs", "k_ffn1_bwd_x32", "k_ffn1_bwd"};

@@ -116,11 +116,28 @@ def test_variant_word_from_the_diagnostic_environment_variables():
     assert _lib.variant_from_env({'LG_ATTN_BWD_CORE': 'm'}) == _lib.LG_VAR_ATTN_BWD_CORE_M
     assert _lib.variant_from_env({'LG_ATTN_BWD_STATS': 'recompute'}) == _lib.LG_VAR_ATTN_BWD_RESTATS == 1 << 16
     hdr = open(os.path.join(ROOT, 'include', 'lgteun_hip.h')).read()
-    for name in ('LG_VAR_FFN_STRIP', 'LG_VAR_FFN_TILE', 'LG_VAR_FFN_XP'):
+    for name in ('LG_VAR_FFN_STRIP',):
         assert int(re.search(rf'#define {name} (\d+)u', hdr).group(1)) == getattr(_lib, name)
     for name in ('LG_VAR_FFN_SAVE3', 'LG_VAR_FFN_SAVE5', 'LG_VAR_FFN_BWD32_PAIR', 'LG_VAR_FFN_DWBWD_TILE', 'LG_VAR_ATTN_BWD_R3', 'LG_VAR_DSTEP_TILES', 'LG_VAR_ATTN_FWD_VALU', 'LG_VAR_FFN_BF16X3', 'LG_VAR_FFT_FULL', 'LG_VAR_FFN_BWD_BF16X3', 'LG_VAR_ATTN_BWD_CORE_M'):
         a, b = re.search(rf'#define {name} \((\d+)u << (\d+)\)', hdr).groups()
         assert int(a) << int(b) == getattr(_lib, name), name
+
+
+@pytest.mark.parametrize('impl', ['tile', 'xp'])
+def test_retired_ffn_implementations_are_refused_when_a_plan_is_created(impl):
+    """LG_FFN_IMPL=tile / xp named kernels the library no longer carries: they must not fall through to the default path -- the word still sets
+    the FFN implementation field, and lg_plan_create (the call Engine.plan makes, with the same arguments) refuses it by the field's name"""
+    from lgteun_amd import _lib
+    var = _lib.variant_from_env({'LG_FFN_IMPL': impl})
+    assert var & 3 >= 2
+    K = 1
+    offs = (ctypes.c_int64 * (12 + K + 119 * K))(*[4 * i for i in range(12 + K + 119 * K)])
+    for prec in (0, 1):
+        cfg = _lib.LgConfig(4, K, 32, 32, prec, var)
+        out = ctypes.c_void_p()
+        with pytest.raises(_lib.LgteunHipError, match='FFN implementation field'):
+            _lib.check(_lib.lib().lg_plan_create(ctypes.byref(cfg), offs, len(offs), ctypes.byref(out)), 'lg_plan_create')
+        assert not out.value
 
 
 def test_metrics_match_oracle():
