@@ -298,6 +298,26 @@ int launch_ffn_dw_bwd_xs(int e, const FfnDwBwdXArgs& a, hipStream_t s);   // e =
 #define FFN_DW_BWD_H_ROW 848      // [d dww 32 x 9 | d dwb 32 | dW3 16 x 32 | db3 16] per workgroup and channel half
 inline size_t ffn_dw_bwd_h_slab_floats() { return (size_t)2 * FFN_DW_BWD_H_WGS * FFN_DW_BWD_H_ROW; }
 int launch_ffn_dw_bwd_h(const FfnDwBwdXArgs& a, hipStream_t s);
+// the tail of both launchers: the slab rows of each channel half (gx rows of `row` floats: [d dww nh x 9 | d dwb nh at r_db | dW3 e x nh at r_w3 | db3 e at r_b3],
+// nh = 4 e / nhalf hidden channels), summed in a fixed order by the deferred reduce launch
+inline int reduce_ffn_dw_bwd_slab(const FfnDwBwdXArgs& a, int e, int nhalf, int gx, int r_db, int r_w3, int r_b3, int row, hipStream_t s) {
+    const int n1 = 4 * e, nh = n1 / nhalf;
+    ReduceJob j;
+    j.dst2 = nullptr; j.nslices = gx; j.slice_stride = row;
+    int rc = 0;
+    for (int half = 0; half < nhalf && !rc; ++half) {
+        const float* base = a.slab + (size_t)half * gx * row;
+        auto job = [&](int off, float* dst, int rows, int cols, int ld) {
+            j.slab = base + off; j.dst = dst; j.rows = rows; j.cols = cols; j.row_stride = cols; j.ld = ld; j.rows_valid = rows; j.cols_valid = cols;
+            return launch_reduce_job(j, s);
+        };
+        rc = job(0, a.d_dww + (size_t)half * nh * 9, nh, 9, 9);
+        if (!rc) rc = job(r_db, a.d_dwb + half * nh, 1, nh, nh);
+        if (!rc) rc = job(r_w3, a.d_w3 + half * nh, e, nh, n1);
+        if (!rc && half == 0) rc = job(r_b3, a.d_b3, 1, e, e);     // db3 = sum of dy: every half sums it, one is used
+    }
+    return rc;
+}
 int launch_transpose(const float* src, float* dst, int rows, int cols, hipStream_t s);  // dst[cols][rows]
 int launch_transpose3(const float* const* src, float* const* dst, const int* rows, const int* cols, int njobs, hipStream_t s);
 

@@ -54,6 +54,23 @@ struct DeviceOnce {
     bool need() const { return !((mask.load(std::memory_order_acquire) >> dev()) & 1); }
     void done() { mask.fetch_or(1ull << dev(), std::memory_order_release); }
 };
+// `bytes` of dynamic LDS for each of `kernels`, in order, up to the first error (message "<who>: hipFuncSetAttribute: <hip error string>", the
+// hip error code returned; 0 = all set)
+template <class... K>
+inline int lds_attr_set(const char* who, int bytes, K*... kernels) {
+    hipError_t e = hipSuccess;
+    ((e = e == hipSuccess ? hipFuncSetAttribute((const void*)kernels, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) : e), ...);
+    if (e != hipSuccess) lg_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
+    return (int)e;
+}
+// ... once per device: what a launcher calls first.  (Kernels with different byte counts: one lds_attr_set each between need() and done().)
+template <class... K>
+inline int lds_attr_once(DeviceOnce& once, const char* who, int bytes, K*... kernels) {
+    if (!once.need()) return 0;
+    const int rc = lds_attr_set(who, bytes, kernels...);
+    if (!rc) once.done();
+    return rc;
+}
 
 // per-(stage, block) dropout seed, shared by forward and backward
 #ifdef __HIPCC__
@@ -295,6 +312,31 @@ __device__ __forceinline__ float lane_group_sum(float v) {
     v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
     if (N >= 8) v += __shfl_xor(v, 4);
     if (N >= 16) v += __shfl_xor(v, 8);
+    return v;
+}
+// k_attn_m / k_attn_bwd_m are built with -fno-honor-nans (Makefile): fmaxf() on values the compiler cannot prove canonical (matrix-core results,
+// v_exp_f32 results) otherwise gets a canonicalising v_max_f32 x, x in front of every operand (IEEE mode).  NOT inline asm: an asm statement that
+// reads a matrix-core result gets none of the wait states the hardware needs between the two (NaNs on some waves of some launches).
+__device__ __forceinline__ float vmax2(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ float vmax3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
+// sum / max over the four lane groups of a wave (lanes c, c + 16, c + 32, c + 48: the lanes of one pixel or token in the matrix-core lane maps);
+// every lane gets it
+__device__ __forceinline__ float xg_sum(float v) {
+    auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+__device__ __forceinline__ float xg_max(float v) {
+    auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    v = vmax2(__uint_as_float(r[0]), __uint_as_float(r[1]));
+    r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return vmax2(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+__device__ __forceinline__ float wave_max(float v) {   // max over all 64 lanes
+    v = xg_max(v);
+#pragma unroll
+    for (int o = 8; o >= 1; o >>= 1) v = vmax2(v, __shfl_xor(v, o));
     return v;
 }
 // counter-hash RNG for dropout (keep probability 0.9, nn.Dropout(0.1) of LGT.py:197): a two-round 32-bit multiply-xorshift of a counter,

@@ -280,11 +280,7 @@ static int launch_attn_t(const AttnArgs& a, hipStream_t s) {
     int nquads = (nwin + 3) / 4;
     size_t lds = (2 * 64 * 64 + 2 * 4 * 64 * HC) * sizeof(float);
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_attn<HC>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        if (e != hipSuccess) { lg_set_error("attn: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_once.done();
-    }
+    if (int rc = lds_attr_once(attr_once, "attn", 128 * 1024, k_attn<HC>)) return rc;
     // persistent grid = the workgroups that are resident at once (LDS: 50 KB / 72 KB / 125 KB per workgroup -> 3 / 2 / 1 per CU;
     // the VGPR counts allow the same), each walking its window quads with pos_emb^T in LDS.  A larger grid runs in rounds and the
     // last round is ragged (HC = 16 at C = 8, 2048 quads: 768 workgroups on 512 slots took 6 quad-times instead of 4).

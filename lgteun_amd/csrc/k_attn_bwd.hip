@@ -632,12 +632,7 @@ static int launch_attn_bwd_t(const AttnBwdArgs& a, hipStream_t s) {
     int ngroups = (nwin + NW - 1) / NW;
     size_t lds = (size_t)(2 * 64 * 65 + NW * (4 * 64 * (HC / 2) + 64 * 4)) * sizeof(float);
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_attn_bwd_core<HC, NW, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_attn_bwd_core<HC, NW, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024);
-        if (e != hipSuccess) { lg_set_error("attn_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_once.done();
-    }
+    if (int rc = lds_attr_once(attr_once, "attn_bwd", 140 * 1024, k_attn_bwd_core<HC, NW, false>, k_attn_bwd_core<HC, NW, true>)) return rc;
     int grid = grid_t<HC, NW>(a.B, a.h, a.w);
     if (HC == 16 && a.core_m) {      // e = 32, A/B: the matrix-pipe core (k_attn_bwd_m.hip; same arguments, outputs and launch shape)
         int rc = launch_attn_bwd_core_m(2 * HC, a, grid, nwin, ngroups, s);

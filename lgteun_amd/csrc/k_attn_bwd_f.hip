@@ -961,12 +961,7 @@ int launch_attn_bwd_f(int e, const AttnBwdFArgs& a, hipStream_t s) {
     const int ngroups = nwin / F_NS;
     const size_t lds = (size_t)F_LDS_FLOATS * sizeof(float);
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t er = hipFuncSetAttribute((const void*)k_attn_bwd_f<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (er == hipSuccess) er = hipFuncSetAttribute((const void*)k_attn_bwd_f<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (er != hipSuccess) { lg_set_error("attn_bwd_f: hipFuncSetAttribute: %s", hipGetErrorString(er)); return (int)er; }
-        attr_once.done();
-    }
+    if (int rc = lds_attr_once(attr_once, "attn_bwd_f", (int)lds, k_attn_bwd_f<false>, k_attn_bwd_f<true>)) return rc;
     const int grid = attn_bwd_f_grid(a.B, a.h, a.w);
     if (nwin >= (1 << 24) || a.w / 8 >= 256 || a.h / 8 >= 256) { lg_set_error("attn_bwd_f: %d windows of a %d x %d plane are out of range", nwin, a.h, a.w); return -2; }
     AttnBwdFArgs ak = a;

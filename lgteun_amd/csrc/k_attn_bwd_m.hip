@@ -25,34 +25,6 @@
 #include "split_bf16.h"
 
 namespace abm {
-__device__ __forceinline__ float vmax2(float a, float b) { return fmaxf(a, b); }
-__device__ __forceinline__ float vmax3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-__device__ __forceinline__ float xg_sum(float v) {   // sum over the four lane groups (lanes c, c + 16, c + 32, c + 48); every lane gets it
-    u32x2_t r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(r.x) + __uint_as_float(r.y);
-    r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r.x) + __uint_as_float(r.y);
-}
-__device__ __forceinline__ float xg_max(float v) {
-    u32x2_t r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = vmax2(__uint_as_float(r.x), __uint_as_float(r.y));
-    r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return vmax2(__uint_as_float(r.x), __uint_as_float(r.y));
-}
-__device__ __forceinline__ float wave_max(float v) {
-    v = xg_max(v);
-#pragma unroll
-    for (int o = 8; o >= 1; o >>= 1) v = vmax2(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ f32x4_t mfma_h(u32x4_t a, u32x4_t b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-}
-// f16 pair of two scaled values as (hi dword, lo dword)
-__device__ __forceinline__ void pair2(float a, float b, uint32_t& hi, uint32_t& lo) {
-    hi = sb_cvt_f16x2(a, b);
-    lo = sb_cvt_f16x2(sb_res_lo(hi, a), sb_res_hi(hi, b));
-}
 // "row" fragment of a [D = 8][64 tokens] fp32 LDS tile for token tile t: lane (g, c) holds channels 2 g, 2 g + 1 of token 16 t + c.  A-side
 // order of the three piece products {lo, hi, hi}; the B-side order {hi, lo, hi} is bside() of it (a dword permutation).
 __device__ __forceinline__ u32x4_t row_frag(const float* tile, int t, int g, int c, int sh) {
@@ -83,12 +55,6 @@ __device__ __forceinline__ void tile_frag(const f32x4_t& t0, const f32x4_t& t1, 
     pair2(t1[2], t1[3], hi[3], lo[3]);
     hi4 = (u32x4_t){hi[0], hi[1], hi[2], hi[3]};
     lo4 = (u32x4_t){lo[0], lo[1], lo[2], lo[3]};
-}
-// acc += A (hi, lo) * B (hi, lo): the three piece products, small terms first
-__device__ __forceinline__ f32x4_t mfma3(u32x4_t ah, u32x4_t al, u32x4_t bh, u32x4_t bl, f32x4_t acc) {
-    acc = mfma_h(al, bh, acc);
-    acc = mfma_h(ah, bl, acc);
-    return mfma_h(ah, bh, acc);
 }
 }  // namespace abm
 
@@ -469,12 +435,7 @@ int launch_attn_bwd_core_m(int e, const AttnBwdArgs& a, int grid, int nwin, int 
     constexpr int HC = 16, NW = 4;
     const size_t lds = (size_t)(4192 + NW * (4 * 64 * (HC / 2) + 64 * 4)) * sizeof(float);
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t er = hipFuncSetAttribute((const void*)k_attn_bwd_core_m<HC, NW, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024);
-        if (er == hipSuccess) er = hipFuncSetAttribute((const void*)k_attn_bwd_core_m<HC, NW, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024);
-        if (er != hipSuccess) { lg_set_error("attn_bwd_core_m: hipFuncSetAttribute: %s", hipGetErrorString(er)); return (int)er; }
-        attr_once.done();
-    }
+    if (int rc = lds_attr_once(attr_once, "attn_bwd_core_m", 140 * 1024, k_attn_bwd_core_m<HC, NW, 0>, k_attn_bwd_core_m<HC, NW, 1>)) return rc;
     if (!a.stats) { lg_set_error("attn_bwd_core_m: statistics scratch missing"); return -2; }
     k_attn_bwd_core_m<HC, NW, 0><<<dim3(grid, 2), NW * 64, lds, s>>>(a, nwin, ngroups);
     LG_CHECK_LAUNCH();

@@ -41,30 +41,6 @@ template <int NP> __host__ __device__ constexpr int pwN(int prod) { return NP ==
 template <int NP> __host__ __device__ constexpr int pxN(int prod) { return NP == 2 ? px2(prod) : px(prod); }
 __host__ __device__ constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-// Built with -fno-honor-nans (Makefile): fmaxf() on values the compiler cannot prove canonical (matrix-core results, v_exp_f32 results)
-// otherwise gets a canonicalising v_max_f32 x, x in front of every operand (IEEE mode).  NOT inline asm: an asm statement that reads a
-// matrix-core result gets none of the wait states the hardware needs between the two (NaNs on some waves of some launches).
-__device__ __forceinline__ float vmax2(float a, float b) { return fmaxf(a, b); }
-__device__ __forceinline__ float vmax3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-__device__ __forceinline__ float xg_sum(float v) {   // sum over the four lane groups (lanes c, c + 16, c + 32, c + 48); every lane gets it
-    u32x2_t r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(r.x) + __uint_as_float(r.y);
-    r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r.x) + __uint_as_float(r.y);
-}
-__device__ __forceinline__ float xg_max(float v) {
-    u32x2_t r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = vmax2(__uint_as_float(r.x), __uint_as_float(r.y));
-    r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return vmax2(__uint_as_float(r.x), __uint_as_float(r.y));
-}
-__device__ __forceinline__ float wave_max(float v) {   // max over all 64 lanes
-    v = xg_max(v);
-#pragma unroll
-    for (int o = 8; o >= 1; o >>= 1) v = vmax2(v, __shfl_xor(v, o));
-    return v;
-}
-
 // fp32 patterns whose high halves are the 16-bit pieces of v (NP = 3: exact three-way bf16 split; NP = 2: f16 hi + lo; NP = 1: bf16 round to nearest)
 template <int NP>
 struct Pat { uint32_t p[3]; };
@@ -85,20 +61,8 @@ __device__ __forceinline__ Pat<NP> pat_of(float v) {
     return r;
 }
 
-// f16 pairs: round to nearest, and the exact residual a - f16(a) in one instruction each (split_bf16.h, NP = 2)
-__device__ __forceinline__ uint32_t cvt_f16x2(float a, float b) { return sb_cvt_f16x2(a, b); }
-__device__ __forceinline__ float res_lo(uint32_t h, float a) { return sb_res_lo(h, a); }
-__device__ __forceinline__ float res_hi(uint32_t h, float b) { return sb_res_hi(h, b); }
-
-__device__ __forceinline__ f32x4_t mfma_bf(u32x4_t a, u32x4_t b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4_t mfma_h(u32x4_t a, u32x4_t b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-}
-
 template <int NP>
-__device__ __forceinline__ f32x4_t mfma_n(u32x4_t a, u32x4_t b, f32x4_t c) { return NP == 2 ? mfma_h(a, b, c) : mfma_bf(a, b, c); }
+__device__ __forceinline__ f32x4_t mfma_n(u32x4_t a, u32x4_t b, f32x4_t c) { return NP == 2 ? mfma_h(a, b, c) : mfma_b(a, b, c); }
 
 // Operand fragment k of a lane that holds CH channels as piece patterns pat[ch].p[piece]: slot s = 8 k + j means product s / CH
 // (piece table A or B side) of channel s % CH; slots past the last product are zero.  CH = 1: a dword pairs two products of the one
@@ -439,8 +403,8 @@ __global__ __launch_bounds__(256, (HC <= 16 ? 2 : 1)) void k_attn_m(AttnArgs a_,
                 uint32_t hi[4], lo[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    hi[i] = cvt_f16x2(w8[2 * i], w8[2 * i + 1]);
-                    if (NPV == 2) lo[i] = cvt_f16x2(res_lo(hi[i], w8[2 * i]), res_hi(hi[i], w8[2 * i + 1]));
+                    hi[i] = sb_cvt_f16x2(w8[2 * i], w8[2 * i + 1]);
+                    if (NPV == 2) lo[i] = sb_cvt_f16x2(sb_res_lo(hi[i], w8[2 * i]), sb_res_hi(hi[i], w8[2 * i + 1]));
                 }
                 Vf[nt][s2][0] = (u32x4_t){hi[0], hi[1], hi[2], hi[3]};
                 if (NPV == 2) Vf[nt][s2][1] = (u32x4_t){lo[0], lo[1], lo[2], lo[3]};
@@ -499,8 +463,8 @@ __global__ __launch_bounds__(256, (HC <= 16 ? 2 : 1)) void k_attn_m(AttnArgs a_,
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const float p0 = S[2 * s2 + (i >> 1)][2 * (i & 1)], p1 = S[2 * s2 + (i >> 1)][2 * (i & 1) + 1];
-                        hi[i] = cvt_f16x2(p0, p1);
-                        if (NPV == 2) lo[i] = cvt_f16x2(res_lo(hi[i], p0), res_hi(hi[i], p1));
+                        hi[i] = sb_cvt_f16x2(p0, p1);
+                        if (NPV == 2) lo[i] = sb_cvt_f16x2(sb_res_lo(hi[i], p0), sb_res_hi(hi[i], p1));
                     }
                     const u32x4_t ph = {hi[0], hi[1], hi[2], hi[3]};
                     if (NPV == 2) {
@@ -544,7 +508,7 @@ __global__ __launch_bounds__(256, (HC <= 16 ? 2 : 1)) void k_attn_m(AttnArgs a_,
             for (int mt = 0; mt < MTP; ++mt) {
                 f32x4_t acc = {bp[mt][0], bp[mt][1], bp[mt][2], bp[mt][3]};
 #pragma unroll
-                for (int k = 0; k < NKP; ++k) acc = mfma_bf(sWp[(mt * NKP + k) * 64 + lane], cf[k], acc);
+                for (int k = 0; k < NKP; ++k) acc = mfma_b(sWp[(mt * NKP + k) * 64 + lane], cf[k], acc);
                 float o[4];
                 const uint64_t di = (uint64_t)((pix - dpix0) * E + 16 * mt + 4 * g);   // a multiple of 4: | v below never carries
 #pragma unroll
@@ -611,11 +575,7 @@ static int launch_attn_m_t(const AttnArgs& a, hipStream_t s) {
     constexpr int NKQ = am::cdiv(am::nprod(NPQ) * 4 * G::NY, 8), NKP = am::cdiv(am::nprod(NPP) * 4 * G::NCH, 8);
     const size_t lds = (size_t)(2 * 4 * 4 * 64 + (G::MTQK + G::NTV) * NKQ * 64 + G::NCH * NKP * 64) * 16;
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_attn_m<HC, NP, MULTI>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { lg_set_error("attn_m: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_once.done();
-    }
+    if (int rc = lds_attr_once(attr_once, "attn_m", 160 * 1024, k_attn_m<HC, NP, MULTI>)) return rc;
     // persistent grid: the workgroups that are RESIDENT at once (registers and LDS: asked of the runtime once per device), each walking its
     // window quads with pos_emb and the weight fragments in LDS.  A larger grid runs in rounds -- 683 workgroups on 512 slots: two stagings
     // and 2 x 3 windows per slot instead of one and 4.

@@ -96,12 +96,7 @@ int launch_resample_adj(int mode, const float* gout, float* gin, int planes, int
     const size_t lds = ((size_t)grows * (wo + wi) + (size_t)(wi + rt) * (NC + 1)) * sizeof(float);
     if (lds > 150 * 1024) { lg_set_error("resample_adj: plane width %d too large", wi); return -2; }
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_resample_adj<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_resample_adj<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (e != hipSuccess) { lg_set_error("resample_adj: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_once.done();
-    }
+    if (int rc = lds_attr_once(attr_once, "resample_adj", 150 * 1024, k_resample_adj<0>, k_resample_adj<1>)) return rc;
     dim3 grid((hi + rt - 1) / rt, planes);
     if (mode == 0) k_resample_adj<0><<<grid, 256, lds, s>>>(gout, gin, hi, wi, ho, wo, accumulate, rt, grows);
     else k_resample_adj<1><<<grid, 256, lds, s>>>(gout, gin, hi, wi, ho, wo, accumulate, rt, grows);

@@ -829,11 +829,7 @@ int launch_fwd_t(const DstepFwdArgs& a, hipStream_t s) {
     constexpr size_t lds = DsL<N>::FLOATS * sizeof(float);
     static_assert(lds <= 160 * 1024, "plane does not fit");
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_dstep_fwd<N, C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { lg_set_error("dstep_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_once.done();
-    }
+    if (int rc = lds_attr_once(attr_once, "dstep_fwd", (int)lds, k_dstep_fwd<N, C>)) return rc;
     const long total4 = (long)a.B * N * N / 4;
     k_dstep_pre_fwd<C><<<(int)((total4 + 255) / 256), 256, 0, s>>>(a.z, a.pan, a.rw, a.rb, a.pr, N * N / 4, total4);
     LG_CHECK_LAUNCH();
@@ -846,11 +842,7 @@ int launch_bwd_t(const DstepBwdArgs& a, hipStream_t s) {
     constexpr size_t lds = DsLB<N>::FLOATS * sizeof(float);
     static_assert(lds <= 160 * 1024, "plane does not fit");
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_dstep_bwd<N, C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { lg_set_error("dstep_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_once.done();
-    }
+    if (int rc = lds_attr_once(attr_once, "dstep_bwd", (int)lds, k_dstep_bwd<N, C>)) return rc;
     DstepPreBwdArgs p;
     p.z = a.z; p.g = a.g; p.pan = a.pan; p.dz = a.dz; p.rw = a.rw; p.rb = a.rb; p.rtw = a.rtw; p.rtb = a.rtb; p.eta = a.eta;
     p.part = a.part_pre; p.hw4 = N * N / 4;

@@ -118,11 +118,7 @@ static int launch_ffn1_t(const Ffn1Args& a, hipStream_t s) {
     constexpr int N1 = 4 * E, MW = 16 * MT;
     size_t lds = (size_t)4 * MW * ((E + 4) + (N1 + 4)) * sizeof(float);
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_ffn1<E, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        if (e != hipSuccess) { lg_set_error("ffn1: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_once.done();
-    }
+    if (int rc = lds_attr_once(attr_once, "ffn1", 128 * 1024, k_ffn1<E, MT>)) return rc;
     long per_wg = 4L * MW;
     int grid = (int)((a.P + per_wg - 1) / per_wg);
     k_ffn1<E, MT><<<grid, 256, lds, s>>>(a);
@@ -253,11 +249,7 @@ static int launch_ffn2_t(const Ffn2Args& a, hipStream_t s) {
     constexpr int N1 = 4 * E, M = TY * TX;
     size_t lds = (size_t)(M * (N1 + 4) + M * (E + 1)) * sizeof(float);
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_ffn2<E, MT, TY, TX>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (e != hipSuccess) { lg_set_error("ffn2: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_once.done();
-    }
+    if (int rc = lds_attr_once(attr_once, "ffn2", 150 * 1024, k_ffn2<E, MT, TY, TX>)) return rc;
     int tiles_x = (a.w + TX - 1) / TX, tiles_y = (a.h + TY - 1) / TY;
     int grid = a.B * tiles_x * tiles_y;
     k_ffn2<E, MT, TY, TX><<<grid, 256, lds, s>>>(a, tiles_x, tiles_y);
@@ -769,19 +761,9 @@ static int launch_ffn_strip(const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t 
     ProfScope prof__(LG_K_FFN2, s);
     const size_t lds = (size_t)(4 * 16 * 68 + 128 * 17 + 10 * 18 * 68) * sizeof(float);
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_ffn_strip<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_strip<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e != hipSuccess) { lg_set_error("ffn_strip: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_once.done();
-    }
-    const int tiles_x = (a2.w + 15) / 16;
-    // strip height: the tallest multiple of 8 rows that still yields >= 512 strips (two resident workgroups per CU), at least 16
-    int SH = (a2.h + 7) / 8 * 8;
-    while (SH > 16 && (long)a2.B * tiles_x * ((a2.h + SH - 1) / SH) < 512) SH = (SH / 2 + 7) / 8 * 8;
-    const int strips_y = (a2.h + SH - 1) / SH;
-    const int nstrips = a2.B * tiles_x * strips_y;
-    const int grid = nstrips < 512 ? nstrips : 512;
+    if (int rc = lds_attr_once(attr_once, "ffn_strip", 152 * 1024, k_ffn_strip<false>, k_ffn_strip<true>)) return rc;
+    const StripGeo geo = strip_geometry(a2.h, a2.w, a2.B, a2.B, 512, 0);   // two resident workgroups per CU
+    const int tiles_x = geo.tiles_x, strips_y = geo.strips_y, nstrips = geo.nstrips, SH = geo.SH, grid = geo.grid;
     if (a1.a1s != nullptr) k_ffn_strip<true><<<grid, 256, lds, s>>>(a1, a2, tiles_x, strips_y, nstrips, SH);
     else k_ffn_strip<false><<<grid, 256, lds, s>>>(a1, a2, tiles_x, strips_y, nstrips, SH);
     LG_CHECK_LAUNCH();
@@ -793,12 +775,7 @@ static int launch_ffn_tile(const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s
     constexpr int E = 32, N1 = 4 * E;
     size_t lds = (size_t)(192 * (E + 4) + 180 * (N1 + 4) + 4 * 16 * (N1 + 4)) * sizeof(float);
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_ffn_fused<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_fused<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e != hipSuccess) { lg_set_error("ffn_fused: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_once.done();
-    }
+    if (int rc = lds_attr_once(attr_once, "ffn_fused", 152 * 1024, k_ffn_fused<false>, k_ffn_fused<true>)) return rc;
     int tiles_x = (a2.w + 15) / 16, tiles_y = (a2.h + 7) / 8;
     const int ntiles = a2.B * tiles_x * tiles_y;
     const int grid = ntiles < 256 ? ntiles : 256;   // persistent: one resident workgroup per CU walks the tiles, weights stay in registers

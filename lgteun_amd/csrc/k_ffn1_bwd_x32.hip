@@ -28,8 +28,6 @@ constexpr size_t OFF_O = OFF_Y + (size_t)TP * LDY * 4;
 constexpr size_t LDS_BYTES = OFF_O + (size_t)TP * LDY * 4;
 constexpr int NF_W1 = 8, NF_W2 = 32;                 // fragment counts of k_split_w's first two matrices at e = 32
 
-__device__ __forceinline__ bf16x8_t lds_x8(const uint16_t* p) { return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4_t*>(p)); }
-
 template <int NP>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_ffn1_bwd_x32(Ffn1BwdArgs a, const u32x4_t* __restrict__ wsp, long ntiles) {
     constexpr bool BF = (NP == 1);
@@ -248,12 +246,7 @@ int launch_ffn1_bwd_x32(const Ffn1BwdArgs& a, const float* w1, void* wsplit, hip
     if (!wsplit) { lg_set_error("ffn1_bwd_x32: no weight-fragment scratch"); return -3; }
     if (!a.part || !a.w1slab || !a.d_w1 || !a.d_b1) { lg_set_error("ffn1_bwd_x32: partial-sum scratch / dW1 destinations missing"); return -2; }
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_ffn1_bwd_x32<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn1_bwd_x32<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e != hipSuccess) { lg_set_error("ffn1_bwd_x32: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_once.done();
-    }
+    if (int rc = lds_attr_once(attr_once, "ffn1_bwd_x32", (int)LDS_BYTES, k_ffn1_bwd_x32<3>, k_ffn1_bwd_x32<1>)) return rc;
     // A operands: W2^T [128 rows k][K = 128 n] = a.w2t, W1^T [32 rows c][K = 128 k] = a.w1t; the first slot of k_split_w (a [128][32]
     // matrix) is not used by this kernel and is fed the forward W1
     {

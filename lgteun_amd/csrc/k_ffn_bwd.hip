@@ -253,12 +253,12 @@ static int launch_ffn_dw_bwd_t(const FfnDwBwdArgs& a, hipStream_t s) {
     dim3 grid((unsigned)nwg, 4 * E / CG);
     const size_t lds = (size_t)(192 * (E + 4) + 2 * 180 * (CG + 4) + ((E == 32 && CG == 32) ? 0 : 4 * (CG / 4) * 40)) * sizeof(float);
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_ffn_dw_bwd<E, false, CG, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if constexpr (E != 64) { if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_dw_bwd<E, true, CG, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); }
-        if constexpr (E == 16) { if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_dw_bwd<E, false, CG, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); }
-        if (e != hipSuccess) { lg_set_error("ffn_dw_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_once.done();
+    {   // (only the instances a route can launch exist)
+        int rc;
+        if constexpr (E == 16) rc = lds_attr_once(attr_once, "ffn_dw_bwd", 150 * 1024, k_ffn_dw_bwd<E, false, CG, false>, k_ffn_dw_bwd<E, true, CG, false>, k_ffn_dw_bwd<E, false, CG, true>);
+        else if constexpr (E != 64) rc = lds_attr_once(attr_once, "ffn_dw_bwd", 150 * 1024, k_ffn_dw_bwd<E, false, CG, false>, k_ffn_dw_bwd<E, true, CG, false>);
+        else rc = lds_attr_once(attr_once, "ffn_dw_bwd", 150 * 1024, k_ffn_dw_bwd<E, false, CG, false>);
+        if (rc) return rc;
     }
     if (a.pre && (a.hbf || E != 16)) { lg_set_error("ffn_dw_bwd: pre-activation saves are fp32, e = 16"); return -2; }
     if (a.hbf && E == 64) { lg_set_error("ffn_dw_bwd: e = 64 keeps fp32 storage"); return -2; }   // (route.hip: hbf is off at e = 64 in both precisions)
@@ -676,14 +676,11 @@ static int launch_ffn1_bwd_t(const Ffn1BwdArgs& a, hipStream_t s) {
     size_t lds = (size_t)(4 * MW * (2 * (N1 + 4) + E + 1) + (E == 16 ? N1 * (N1 + 4) : 0)) * sizeof(float);
     if (ffn1_bwd_fuses_w2(E, a.pre)) lds += (size_t)4 * MW * (N1 + 4) * sizeof(float);   // gelu(h1) rows
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_ffn1_bwd<E, MT, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if constexpr (E == 16) {
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn1_bwd<E, MT, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn1_bwd<E, MT, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        }
-        if (e != hipSuccess) { lg_set_error("ffn1_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_once.done();
+    {
+        int rc;
+        if constexpr (E == 16) rc = lds_attr_once(attr_once, "ffn1_bwd", 150 * 1024, k_ffn1_bwd<E, MT, false, false>, k_ffn1_bwd<E, MT, true, false>, k_ffn1_bwd<E, MT, false, true>);
+        else rc = lds_attr_once(attr_once, "ffn1_bwd", 150 * 1024, k_ffn1_bwd<E, MT, false, false>);
+        if (rc) return rc;
     }
     long per_wg = 4L * MW;
     const long nchunks = (a.P + per_wg - 1) / per_wg;

@@ -64,7 +64,6 @@ struct KB {
     static_assert(NT / (N1 / 4) == 16 && NT / LPP == NPX, "loader / LayerNorm thread maps");
 };
 
-typedef __attribute__((address_space(3))) s16x4_t lds_s16x4_t;
 #ifndef LG_KB_DACHAINS
 #define LG_KB_DACHAINS 0
 #endif
@@ -76,27 +75,6 @@ typedef __attribute__((address_space(3))) s16x4_t lds_s16x4_t;
 #endif
 #define KB_FENCE() do { if (LG_KB_FENCE) __builtin_amdgcn_sched_barrier(0); } while (0)
 
-__device__ __forceinline__ float quad_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
-    return v;
-}
-__device__ __forceinline__ bf16x8_t lds_x8(const uint16_t* p) { return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4_t*>(p)); }
-__device__ __forceinline__ s16x4_t lds_x4(const uint16_t* p) { return __builtin_bit_cast(s16x4_t, *reinterpret_cast<const u32x2_t*>(p)); }
-// transposed read: the 16 lanes of a group hand in the addresses of a 4-row x 16-column block of 16-bit elements (lane 4 q + p: row q,
-// columns 4 p .. 4 p + 3) and lane i gets column i of the four rows
-__device__ __forceinline__ s16x4_t lds_tr4(const uint16_t* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)p);
-}
-// the six piece products of a fp32-equivalent 16x16x16 block: a, b = the three bf16 pieces of each operand (small terms first)
-__device__ __forceinline__ void mfma6_16(f32x4_t& acc, const s16x4_t (&a)[3], const s16x4_t (&b)[3]) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], b[2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[2], b[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[1], b[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], b[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[1], b[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], b[0], acc, 0, 0, 0);
-}
 __device__ __forceinline__ void mfma6_32(f32x4_t& acc, const bf16x8_t (&a)[3], const bf16x8_t (&b)[3]) {
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[2], acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[0], acc, 0, 0, 0);
@@ -105,34 +83,12 @@ __device__ __forceinline__ void mfma6_32(f32x4_t& acc, const bf16x8_t (&a)[3], c
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], acc, 0, 0, 0);
 }
-__device__ __forceinline__ bf16x8_t cat8(s16x4_t lo, s16x4_t hi) {
-    typedef short s16x8_t __attribute__((ext_vector_type(8)));
-    return __builtin_bit_cast(bf16x8_t, (s16x8_t)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-// The six piece products of a 16-deep block as THREE 32-deep MFMAs: two piece products share one instruction, their operands
-// concatenated along K (slots 0..3 of a lane = one piece pair, 4..7 = another; both operands use the same order, and any order of K is a
-// sum).  v_mfma_f32_16x16x16_bf16 costs the matrix pipe what the 32-deep form costs (16 busy cycles each, profiles/r03_sq_counters_*),
-// so this halves the pipe time of every K = 16 product: a1 b3 + a3 b1 | a2 b2 + a2 b1 | a1 b2 + a1 b1   (small terms first).
+// NP = 3: the six piece products (fp32-equivalent); NP = 1 (precision = 'bf16'): one product of round-to-nearest bf16 operands
+// NP = 2 (round 5): f16 pairs (split_bf16.h), three piece products; every operand arrives multiplied by a power of two (see the kernel)
+// K = 16 blocks (mfma_np16): the six products as three 32-deep MFMAs (split_bf16.h: mfma_split16_pair), half the matrix-pipe time of each
 #ifndef LG_KB_PAIR
 #define LG_KB_PAIR 1
 #endif
-__device__ __forceinline__ void mfma3_16(f32x4_t& acc, const s16x4_t (&a)[3], const s16x4_t (&b)[3]) {
-    const bf16x8_t b31 = cat8(b[2], b[0]), b21 = cat8(b[1], b[0]);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cat8(a[0], a[2]), b31, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cat8(a[1], a[1]), b21, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cat8(a[0], a[0]), b21, acc, 0, 0, 0);
-}
-// NP = 3: the six piece products (fp32-equivalent); NP = 1 (precision = 'bf16'): one product of round-to-nearest bf16 operands
-// NP = 2 (round 5): f16 pairs (split_bf16.h), three piece products; every operand arrives multiplied by a power of two (see the kernel)
-template <int NP>
-__device__ __forceinline__ void mfmaN_16(f32x4_t& acc, const s16x4_t (&a)[3], const s16x4_t (&b)[3]) {
-    if (NP == 3) { if (LG_KB_PAIR) mfma3_16(acc, a, b); else mfma6_16(acc, a, b); }
-    else if (NP == 2) {   // K = 16: two piece products share one 32-deep instruction: a_lo b_hi + a_hi b_lo | a_hi b_hi
-        const s16x4_t z = {0, 0, 0, 0};
-        acc = sb_mfma_h(cat8(a[1], a[0]), cat8(b[0], b[1]), acc);
-        acc = sb_mfma_h(cat8(a[0], z), cat8(b[0], z), acc);
-    } else acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], b[0], acc, 0, 0, 0);
-}
 template <int NP>
 __device__ __forceinline__ void mfmaN_32(f32x4_t& acc, const bf16x8_t (&a)[3], const bf16x8_t (&b)[3]) {
     if (NP == 3) mfma6_32(acc, a, b);
@@ -175,7 +131,7 @@ __device__ __forceinline__ float kb_pow2_below(float bound) { return __builtin_a
 template <int E, int NP>
 __global__ __launch_bounds__(KB<E>::NT) __attribute__((amdgpu_waves_per_eu(2))) void k_ffn1_bwd_xs(Ffn1BwdXArgs a, long ntiles, int uneven) {
     using C = KB<E>;
-    constexpr int N1 = C::N1, NW = C::NW, NT = C::NT, LDP = C::LDP, LPP = C::LPP, D2_PIECE = C::D2_PIECE, XN_PIECE = C::XN_PIECE, D1T_PIECE = C::D1T_PIECE;
+    constexpr int N1 = C::N1, NW = C::NW, LDP = C::LDP, LPP = C::LPP, D2_PIECE = C::D2_PIECE, XN_PIECE = C::XN_PIECE, D1T_PIECE = C::D1T_PIECE;
     constexpr int KB2 = N1 / 32;       // 32-deep K blocks of dh2 W2
     constexpr int NE = E / 16;         // 16-wide blocks of the e-channel axis (columns of dW1, rows of W1^T dh1)
     constexpr bool BF = (NP == 1);     // plain-bf16 mode: dh2 is stored as bf16 (hstore.h) and is its own (single) piece
@@ -310,7 +266,7 @@ __global__ __launch_bounds__(KB<E>::NT) __attribute__((amdgpu_waves_per_eu(2))) 
                 s16x4_t xa[3];
                 ld3_x4<NPE>(XN + (pbk * 16 + r) * E + 4 * g, XN_PIECE, xa);
                 KB_FENCE();
-                mfmaN_16<NPE>(h1, xa, w1f16.p);
+                mfma_np16<NPE, LG_KB_PAIR>(h1, xa, w1f16.p);
             } else {
                 bf16x8_t xa[3];
                 ld3_x8<NPE>(XN + (pbk * 16 + r) * E + 8 * g, XN_PIECE, xa);
@@ -363,14 +319,14 @@ __global__ __launch_bounds__(KB<E>::NT) __attribute__((amdgpu_waves_per_eu(2))) 
                 for (int cb = 0; cb < NE; ++cb) {
                     s16x4_t xt[3];
                     ld3_tr<NPE>(px + 16 * cb, XN_PIECE, xt);
-                    mfmaN_16<NPE>(acc1[cb], d1p, xt);
+                    mfma_np16<NPE, LG_KB_PAIR>(acc1[cb], d1p, xt);
                 }
                 const uint16_t* pt = D2 + (pbk * 16 + 4 * g + (r >> 2)) * LDP + 4 * (r & 3);
 #pragma unroll
                 for (int nb = 0; nb < NW; ++nb) {
                     s16x4_t dt[3];
                     ld3_tr<NP>(pt + 16 * nb, D2_PIECE, dt);
-                    mfmaN_16<NP>(acc2[nb], dt, a1p);
+                    mfma_np16<NP, LG_KB_PAIR>(acc2[nb], dt, a1p);
                 }
             }
             KB_FENCE();
@@ -389,7 +345,7 @@ __global__ __launch_bounds__(KB<E>::NT) __attribute__((amdgpu_waves_per_eu(2))) 
 #pragma unroll
                 for (int rb = 0; rb < NE; ++rb) {
                     f32x4_t o = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-                    mfmaN_16<NPE>(o, w1tf[rb].p, dtp);     // o[v] = (W1^T dh1)[out channel 16 rb + 4 g + v][pixel r], hidden channels 16 w .. 16 w + 15 only
+                    mfma_np16<NPE, LG_KB_PAIR>(o, w1tf[rb].p, dtp);     // o[v] = (W1^T dh1)[out channel 16 rb + 4 g + v][pixel r], hidden channels 16 w .. 16 w + 15 only
                     *reinterpret_cast<float4*>(red + ((size_t)wave * NPX + pbk * 16 + r) * E + 16 * rb + 4 * g) = make_float4(o[0], o[1], o[2], o[3]);
                 }
                 __builtin_amdgcn_wave_barrier();      // D1T is rewritten by the next pixel block
@@ -463,13 +419,7 @@ template <int E>
 int launch_t(const Ffn1BwdXArgs& a, hipStream_t s) {
     using C = KB<E>;
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_ffn1_bwd_xs<E, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn1_bwd_xs<E, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn1_bwd_xs<E, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
-        if (e != hipSuccess) { lg_set_error("ffn1_bwd_xs: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_once.done();
-    }
+    if (int rc = lds_attr_once(attr_once, "ffn1_bwd_xs", (int)C::LDS_BYTES, k_ffn1_bwd_xs<E, 3>, k_ffn1_bwd_xs<E, 1>, k_ffn1_bwd_xs<E, 2>)) return rc;
     const long ntiles = a.P / NPX;
     const int cap = ffn1_bwd_x_wgs(E);
     const int grid = (int)(ntiles < cap ? ntiles : cap);

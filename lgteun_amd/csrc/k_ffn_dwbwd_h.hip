@@ -56,16 +56,6 @@ static_assert((size_t)(4 * NQ * 40 + 4 * E * NH + 4 * E) * 4 <= LDS_BYTES - OFF_
 template <int N>
 struct IC { static constexpr int value = N; };
 
-typedef __attribute__((address_space(3))) s16x4_t lds_s16x4_t;
-__device__ __forceinline__ s16x4_t lds_tr4(const uint16_t* p) { return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)p); }
-__device__ __forceinline__ void mfma6_16(f32x4_t& acc, const s16x4_t (&a)[3], const s16x4_t (&b)[3]) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], b[2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[2], b[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[1], b[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], b[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[1], b[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], b[0], acc, 0, 0, 0);
-}
 #define DWH_FENCE() __builtin_amdgcn_sched_barrier(0)
 #ifndef DWH_ROWFENCE
 #define DWH_ROWFENCE 0
@@ -214,7 +204,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
                     WFrag16 wf;
 #pragma unroll
                     for (int pc = 0; pc < 3; ++pc) wf.p[pc] = __builtin_bit_cast(s16x4_t, sW3[(mt * 3 + pc) * 64 + lane]);
-                    mfma_split16(acc, wf, __builtin_bit_cast(s16x4_t, q1), __builtin_bit_cast(s16x4_t, q2), __builtin_bit_cast(s16x4_t, q3));
+                    const s16x4_t dyq[3] = {__builtin_bit_cast(s16x4_t, q1), __builtin_bit_cast(s16x4_t, q2), __builtin_bit_cast(s16x4_t, q3)};
+                    mfma_np16<3, LG_SPLIT16_PAIR>(acc, wf.p, dyq);
                     lg_v2f a01, a23, g01, g23;
                     gelu2_both_f(H01[nb][i], a01, g01);
                     gelu2_both_f(H23[nb][i], a23, g23);
@@ -235,7 +226,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
                         s16x4_t dt[3], at[3];
 #pragma unroll
                         for (int pc = 0; pc < 3; ++pc) { dt[pc] = lds_tr4(imgDy + pc * IMG_DY + off); at[pc] = lds_tr4(imgA3 + pc * IMG_A3 + off); }
-                        mfma6_16(acc3[mt], dt, at);
+                        mfma_split16(acc3[mt], dt, at);
                     }
                     __builtin_amdgcn_wave_barrier();   // the image is rewritten by the next tile
                     DWH_FENCE();
@@ -397,35 +388,10 @@ int launch_ffn_dw_bwd_h(const FfnDwBwdXArgs& a, hipStream_t s) {
     if (a.hbf) { lg_set_error("ffn_dw_bwd_h: fp32 storage only"); return -2; }
     if ((a.h & 7) || (a.w & 15)) { lg_set_error("ffn_dw_bwd_h: h must be a multiple of 8 and w of 16 (got %d x %d)", a.h, a.w); return -2; }
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_ffn_dw_bwd_h, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e != hipSuccess) { lg_set_error("ffn_dw_bwd_h: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_once.done();
-    }
-    const int tiles_x = (a.w + 15) / 16;
-    // strip height: the tallest multiple of 8 rows that still yields a strip per resident workgroup (512 = two per CU; the two channel halves share them)
-    const int wgs = FFN_DW_BWD_H_WGS;
-    int SH = (a.h + 7) / 8 * 8;
-    while (SH > 16 && (long)a.B * tiles_x * ((a.h + SH - 1) / SH) < wgs) SH = (SH / 2 + 7) / 8 * 8;
-    const int strips_y = (a.h + SH - 1) / SH;
-    const int nstrips = a.B * tiles_x * strips_y;
-    const int gx = nstrips < wgs ? nstrips : wgs;
+    if (int rc = lds_attr_once(attr_once, "ffn_dw_bwd_h", (int)LDS_BYTES, k_ffn_dw_bwd_h)) return rc;
+    const StripGeo geo = strip_geometry(a.h, a.w, a.B, a.B, FFN_DW_BWD_H_WGS, 0);   // a strip per resident workgroup (512 = two per CU; the two channel halves share them)
+    const int tiles_x = geo.tiles_x, strips_y = geo.strips_y, nstrips = geo.nstrips, SH = geo.SH, gx = geo.grid;
     k_ffn_dw_bwd_h<<<dim3(gx, 2), 256, LDS_BYTES, s>>>(a, tiles_x, strips_y, nstrips, SH);
     LG_CHECK_LAUNCH();
-    // the slab rows of each channel half, summed in a fixed order by the deferred reduce launch
-    ReduceJob j;
-    j.dst2 = nullptr; j.nslices = gx; j.slice_stride = ROW;
-    int rc = 0;
-    for (int half = 0; half < 2 && !rc; ++half) {
-        const float* base = a.slab + (size_t)half * gx * ROW;
-        auto job = [&](int off, float* dst, int rows, int cols, int ld) {
-            j.slab = base + off; j.dst = dst; j.rows = rows; j.cols = cols; j.row_stride = cols; j.ld = ld; j.rows_valid = rows; j.cols_valid = cols;
-            return launch_reduce_job(j, s);
-        };
-        rc = job(0, a.d_dww + (size_t)half * NH * 9, NH, 9, 9);
-        if (!rc) rc = job(R_DB, a.d_dwb + half * NH, 1, NH, NH);
-        if (!rc) rc = job(R_W3, a.d_w3 + half * NH, E, NH, N1);
-        if (!rc && half == 0) rc = job(R_B3, a.d_b3, 1, E, E);     // db3 = sum of dy: both halves sum it, one is used
-    }
-    return rc;
+    return reduce_ffn_dw_bwd_slab(a, E, 2, gx, R_DB, R_W3, R_B3, ROW, s);
 }

@@ -61,42 +61,12 @@ struct KA {
 static_assert(KA<16>::R_DB == FFN_DW_BWD_X_DB && KA<16>::R_W3 == FFN_DW_BWD_X_W3 && KA<16>::R_B3 == FFN_DW_BWD_X_B3 && KA<16>::ROW == FFN_DW_BWD_X_ROW, "slab row (bwd_kernels.h)");
 static_assert(KA<32>::ROW == FFN_DW_BWD_X32_ROW, "slab row (bwd_kernels.h)");
 
-typedef __attribute__((address_space(3))) s16x4_t lds_s16x4_t;
-__device__ __forceinline__ s16x4_t lds_x4(const uint16_t* p) { return __builtin_bit_cast(s16x4_t, *reinterpret_cast<const u32x2_t*>(p)); }
-__device__ __forceinline__ s16x4_t lds_tr4(const uint16_t* p) { return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)p); }
-__device__ __forceinline__ void mfma6_16(f32x4_t& acc, const s16x4_t (&a)[3], const s16x4_t (&b)[3]) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], b[2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[2], b[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[1], b[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], b[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[1], b[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], b[0], acc, 0, 0, 0);
-}
-
-__device__ __forceinline__ bf16x8_t cat8(s16x4_t lo, s16x4_t hi) {
-    typedef short s16x8_t __attribute__((ext_vector_type(8)));
-    return __builtin_bit_cast(bf16x8_t, (s16x8_t)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
 #ifndef LG_KA_ITEMFENCE
 #define LG_KA_ITEMFENCE 1   // P2: a scheduling fence behind every LG_KA_ITEMFENCE-th item (0: none)
 #endif
 #ifndef LG_KA_PAIR
-#define LG_KA_PAIR 0   // measured in THIS kernel (VALU / LDS bound, matrix pipe 10 % busy): the operand concatenation costs 133.7 vs 119.5 us per launch; off
+#define LG_KA_PAIR 0   // the K = 16 products as three 32-deep MFMAs (split_bf16.h: mfma_split16_pair).  Measured in THIS kernel (VALU / LDS bound, matrix pipe 10 % busy): the operand concatenation costs 133.7 vs 119.5 us per launch; off
 #endif
-// the six piece products as three 32-deep MFMAs, two products per instruction (k_ffn_bwd_x.hip: mfma3_16)
-__device__ __forceinline__ void mfma3_16(f32x4_t& acc, const s16x4_t (&a)[3], const s16x4_t (&b)[3]) {
-    const bf16x8_t b31 = cat8(b[2], b[0]), b21 = cat8(b[1], b[0]);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cat8(a[0], a[2]), b31, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cat8(a[1], a[1]), b21, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cat8(a[0], a[0]), b21, acc, 0, 0, 0);
-}
-template <int NP>
-__device__ __forceinline__ void mfmaN_16(f32x4_t& acc, const s16x4_t (&a)[3], const s16x4_t (&b)[3]) {
-    if (NP == 3) { if (LG_KA_PAIR) mfma3_16(acc, a, b); else mfma6_16(acc, a, b); }
-    else acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], b[0], acc, 0, 0, 0);
-}
-
-__device__ __forceinline__ bf16x8_t lds_x8(const uint16_t* p) { return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4_t*>(p)); }
 
 // NP = 3: fp32 storage of h2 / h3 / dh2, fp32-equivalent split products; NP = 1 (precision = 'bf16'): bf16 storage (hstore.h), plain bf16 products
 template <int E, int NP>
@@ -246,7 +216,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void k_
                     s16x4_t xb[3];
                     xb[0] = lds_x4(p);
                     if (NP == 3) { xb[1] = lds_x4(p + DY_PIECE); xb[2] = lds_x4(p + 2 * DY_PIECE); } else { xb[1] = xb[0]; xb[2] = xb[0]; }
-                    mfmaN_16<NP>(acc, w3f16.p, xb);
+                    mfma_np16<NP, LG_KA_PAIR>(acc, w3f16.p, xb);
                 } else {
                     const uint16_t* p = dyb + (pb * 16 + r) * E + 8 * g;
                     const bf16x8_t x1 = lds_x8(p);
@@ -288,7 +258,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void k_
                         s16x4_t dt[3];
                         dt[0] = lds_tr4(pa);
                         if (NP == 3) { dt[1] = lds_tr4(pa + DY_PIECE); dt[2] = lds_tr4(pa + 2 * DY_PIECE); } else { dt[1] = dt[0]; dt[2] = dt[0]; }
-                        mfmaN_16<NP>(acc3[mt], dt, at);
+                        mfma_np16<NP, LG_KA_PAIR>(acc3[mt], dt, at);
                     }
                 }
                 __builtin_amdgcn_wave_barrier();   // the image is rewritten by the next block
@@ -463,21 +433,11 @@ template <int E>
 static int launch_dw_t(const FfnDwBwdXArgs& a, hipStream_t s) {
     using C = KA<E>;
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_ffn_dw_bwd_xs<E, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_dw_bwd_xs<E, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
-        if (e != hipSuccess) { lg_set_error("ffn_dw_bwd_xs: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_once.done();
-    }
-    const int tiles_x = (a.w + 15) / 16;
-    // strip height as in the forward: the tallest multiple of 8 rows that still yields a strip per resident workgroup (512 = two per CU; at
-    // e = 32 the two channel halves share them), at least 16
+    if (int rc = lds_attr_once(attr_once, "ffn_dw_bwd_xs", (int)C::LDS_BYTES, k_ffn_dw_bwd_xs<E, 3>, k_ffn_dw_bwd_xs<E, 1>)) return rc;
+    // strips as in the forward, one per resident workgroup (512 = two per CU; at e = 32 the two channel halves share them)
     const int wgs = FFN_DW_BWD_X_WGS / C::NHALF;
-    int SH = (a.h + 7) / 8 * 8;
-    while (SH > 16 && (long)a.B * tiles_x * ((a.h + SH - 1) / SH) < wgs) SH = (SH / 2 + 7) / 8 * 8;
-    const int strips_y = (a.h + SH - 1) / SH;
-    const int nstrips = a.B * tiles_x * strips_y;
-    const int gx = nstrips < wgs ? nstrips : wgs;
+    const StripGeo geo = strip_geometry(a.h, a.w, a.B, a.B, wgs, 0);
+    const int tiles_x = geo.tiles_x, strips_y = geo.strips_y, nstrips = geo.nstrips, SH = geo.SH, gx = geo.grid;
     const dim3 grid(gx, C::NHALF);
 #ifndef LG_DWB_UNEVEN
 #define LG_DWB_UNEVEN 0   // measured: even strips 110.5 us, 9 : 7 steps 113.2, 10 : 6 110.5 -- this kernel gains nothing from the uneven split (unlike k_ffn_xr, k_attn_m, k_ffn1_bwd_xs)
@@ -487,22 +447,7 @@ static int launch_dw_t(const FfnDwBwdXArgs& a, hipStream_t s) {
     if (a.hbf) k_ffn_dw_bwd_xs<E, 1><<<grid, NT, C::LDS_BYTES, s>>>(a, tiles_x, strips_y, nstrips, SH, dS);   // precision = 'bf16'
     else k_ffn_dw_bwd_xs<E, 3><<<grid, NT, C::LDS_BYTES, s>>>(a, tiles_x, strips_y, nstrips, SH, dS);
     LG_CHECK_LAUNCH();
-    // the slab rows of each channel half, summed in a fixed order by the deferred reduce launch
-    ReduceJob j;
-    j.dst2 = nullptr; j.nslices = gx; j.slice_stride = C::ROW;
-    int rc = 0;
-    for (int half = 0; half < C::NHALF && !rc; ++half) {
-        const float* base = a.slab + (size_t)half * gx * C::ROW;
-        auto job = [&](int off, float* dst, int rows, int cols, int ld) {
-            j.slab = base + off; j.dst = dst; j.rows = rows; j.cols = cols; j.row_stride = cols; j.ld = ld; j.rows_valid = rows; j.cols_valid = cols;
-            return launch_reduce_job(j, s);
-        };
-        rc = job(0, a.d_dww + (size_t)half * NH * 9, NH, 9, 9);
-        if (!rc) rc = job(C::R_DB, a.d_dwb + half * NH, 1, NH, NH);
-        if (!rc) rc = job(C::R_W3, a.d_w3 + half * NH, E, NH, C::N1);
-        if (!rc && half == 0) rc = job(C::R_B3, a.d_b3, 1, E, E);     // db3 = sum of dy: every half sums it, one is used
-    }
-    return rc;
+    return reduce_ffn_dw_bwd_slab(a, E, C::NHALF, gx, C::R_DB, C::R_W3, C::R_B3, C::ROW, s);
 }
 
 }   // namespace

@@ -51,16 +51,6 @@ constexpr int G3_WAVE = 3 * 16 * LDP;            // 3456 halves per wave
 constexpr size_t LDS_BYTES = (size_t)RING * HX * LDR * 4 + (size_t)(A2_HALVES + 2 * XA_SLOT) * 2;
 static_assert(4 * G3_WAVE <= A2_HALVES + 2 * XA_SLOT, "gelu(h3) pieces must fit in the aliased region");
 
-// sum over the four lanes of a quad (lanes 4k .. 4k+3) with DPP quad_perm moves: VALU only, no LDS crossbar round trip
-__device__ __forceinline__ float quad_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
-    return v;
-}
-
-__device__ __forceinline__ bf16x8_t lds_x8(const uint16_t* p) { return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4_t*>(p)); }
-__device__ __forceinline__ s16x4_t lds_x4(const uint16_t* p) { return __builtin_bit_cast(s16x4_t, *reinterpret_cast<const u32x2_t*>(p)); }
-
 // SAVE: 0 nothing; 1 gelu(h1), gelu'(h1), h2, gelu(h3), gelu'(h3) (GELU-free backward: the precision = 'bf16' layout);
 // 2 the PRE-ACTIVATIONS h1, h2, h3 only (three tensors instead of five: the backward kernels re-evaluate gelu / gelu' from
 // them, bwd_kernels.h `pre`); 3 h2 and h3 only (the backward re-computes h1 from x: k_ffn1_bwd_xs)
@@ -144,10 +134,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     // LayerNorm of the fetched vector over its 16 channels (4 lanes of a quad), split into pieces -> XA[slot]
     auto ln_store = [&](int slot, const float4& xv, bool in) {
         if (!ln_thread) return;
-        const float s = quad_sum((xv.x + xv.y) + (xv.z + xv.w));
+        const float s = lane_group_sum<4>((xv.x + xv.y) + (xv.z + xv.w));
         const float mu = s * (1.0f / E);
         const float d0 = xv.x - mu, d1 = xv.y - mu, d2 = xv.z - mu, d3 = xv.w - mu;
-        const float v = quad_sum((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
+        const float v = lane_group_sum<4>((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
         const float rstd = __builtin_amdgcn_rsqf(v * (1.0f / E) + LG_EPS);
         const float m_ = in ? 1.0f : 0.0f;
         const float yv[4] = {(d0 * rstd * lng.x + lnb.x) * m_, (d1 * rstd * lng.y + lnb.y) * m_, (d2 * rstd * lng.z + lnb.z) * m_,
@@ -203,7 +193,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
             for (int pb = 0; pb < 3; ++pb) {
                 acc[pb] = (f32x4_t){b1v.x, b1v.y, b1v.z, b1v.w};
                 const uint16_t* p = xa + pb * 16 * E;
-                mfma_np16<NP>(acc[pb], w1f, lds_x4(p), lds_x4(p + CH * E), lds_x4(p + 2 * CH * E));
+                const s16x4_t xb[3] = {lds_x4(p), lds_x4(p + CH * E), lds_x4(p + 2 * CH * E)};
+                mfma_np16<NP, LG_SPLIT16_PAIR>(acc[pb], w1f.p, xb);
             }
             // ---- GELU, split, -> A2 (8 bytes per piece and pixel)
 #pragma unroll
@@ -418,28 +409,11 @@ int launch_ffn_xs(const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s) {
     constexpr int NPF = 3;
     ProfScope prof__(LG_K_FFN2, s);
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_ffn_xs<0, NPF>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_xs<1, NPF>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_xs<2, NPF>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_xs<3, NPF>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_xs<0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_xs<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_xs<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_xs<3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_xs<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_xs<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_xs<3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e != hipSuccess) { lg_set_error("ffn_xs: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_once.done();
-    }
-    const int tiles_x = (a2.w + 15) / 16;
-    // strip height: the tallest multiple of 8 rows that still yields >= 512 strips (two resident workgroups per CU), at least 16
-    int SH = (a2.h + 7) / 8 * 8;
-    while (SH > 16 && (long)a2.B * tiles_x * ((a2.h + SH - 1) / SH) < 512) SH = (SH / 2 + 7) / 8 * 8;
-    const int strips_y = (a2.h + SH - 1) / SH;
-    const int nstrips = a2.B * tiles_x * strips_y;
-    const int grid = nstrips < 512 ? nstrips : 512;
+    if (int rc = lds_attr_once(attr_once, "ffn_xs", 152 * 1024,
+                                     k_ffn_xs<0, NPF>, k_ffn_xs<1, NPF>, k_ffn_xs<2, NPF>, k_ffn_xs<3, NPF>, k_ffn_xs<0, 2>, k_ffn_xs<1, 2>, k_ffn_xs<2, 2>,
+                                     k_ffn_xs<3, 2>, k_ffn_xs<0, 1>, k_ffn_xs<1, 1>, k_ffn_xs<3, 1>)) return rc;
+    const StripGeo geo = strip_geometry(a2.h, a2.w, a2.B, a2.B, 512, 0);   // two resident workgroups per CU
+    const int tiles_x = geo.tiles_x, strips_y = geo.strips_y, nstrips = geo.nstrips, SH = geo.SH, grid = geo.grid;
     const bool save = a1.h2 != nullptr;           // h2 leaves the chip only for the backward
     const bool pre = save && a1.g1s == nullptr;   // pre-activation saves (h1 in a1s, h3 in a3s)
     const bool noh1 = pre && a1.a1s == nullptr;   // ... without h1 (the backward re-computes it)

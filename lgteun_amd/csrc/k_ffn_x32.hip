@@ -34,14 +34,8 @@ constexpr int G3_WAVE = 3 * 16 * 64;             // 3072 halves per wave (one K-
 constexpr size_t LDS_BYTES = (size_t)RING * HX * LDR * 4 + (size_t)(NA2 * A2_HALVES + 2 * XA_SLOT) * 2;
 static_assert(8 * G3_WAVE <= NA2 * A2_HALVES + 2 * XA_SLOT, "gelu(h3) pieces must fit in the aliased region");
 static_assert(LDS_BYTES + 4096 <= 160 * 1024, "LDS budget (dynamic + the static parameter / mask arrays)");
-constexpr int NF_W1 = 8, NF_W2 = 32, NF_W3 = 8;  // 16 x 32 fragments: W1 [128][32], W2 [128][128], W3 [32][128]
+constexpr int NF_W1 = 8, NF_W2 = 32;             // 16 x 32 fragments: W1 [128][32], W2 [128][128] (W3 [32][128]: 8 more)
 
-__device__ __forceinline__ bf16x8_t lds_x8(const uint16_t* p) { return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4_t*>(p)); }
-__device__ __forceinline__ float quad_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
-    return v;
-}
 // W [rows][K] fp32 -> fragments (mb, kb) of 16 x 32, three bf16 pieces each, in the order a wave loads them
 __device__ __forceinline__ void split_w_body(const float* __restrict__ w1, const float* __restrict__ w2, const float* __restrict__ w3,
                                              u32x4_t* __restrict__ out, int e, int np, const float* __restrict__ scales) {
@@ -177,11 +171,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // LayerNorm over the 32 channels of a pixel = 8 consecutive lanes; pieces -> XA[slot], halo mask -> sMask[mslot]
     auto ln_store = [&](int slot, int mslot, const float4& xv, bool in) {
         if (!ln_thread) return;
-        float s = quad_sum((xv.x + xv.y) + (xv.z + xv.w));
+        float s = lane_group_sum<4>((xv.x + xv.y) + (xv.z + xv.w));
         s += __shfl_xor(s, 4);
         const float mu = s * (1.0f / E);
         const float d0 = xv.x - mu, d1 = xv.y - mu, d2 = xv.z - mu, d3 = xv.w - mu;
-        float v = quad_sum((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
+        float v = lane_group_sum<4>((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
         v += __shfl_xor(v, 4);
         const float rstd = __builtin_amdgcn_rsqf(v * (1.0f / E) + LG_EPS);
         const float m_ = in ? 1.0f : 0.0f;
@@ -544,37 +538,18 @@ int launch_ffn_x32(const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s) {
     ProfScope prof__(LG_K_FFN2, s, a1.sg.n);
     if (!a1.wsplit) { lg_set_error("ffn_x32: no weight-fragment scratch in the workspace"); return -3; }
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_ffn_x32<0, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_x32<1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_x32<2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_x32<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_x32<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_x32<0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_x32<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_x32<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_x32<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_x32<0, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_x32<0, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e != hipSuccess) { lg_set_error("ffn_x32: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_once.done();
-    }
+    if (int rc = lds_attr_once(attr_once, "ffn_x32", (int)LDS_BYTES,
+                                     k_ffn_x32<0, 3>, k_ffn_x32<1, 3>, k_ffn_x32<2, 3>, k_ffn_x32<2, 2>, k_ffn_x32<2, 1>, k_ffn_x32<0, 2>, k_ffn_x32<1, 2>,
+                                     k_ffn_x32<0, 1>, k_ffn_x32<1, 1>, k_ffn_x32<0, 2, true>, k_ffn_x32<0, 1, true>)) return rc;
     const bool multi = a1.sg.n > 1;
     if (multi && (a1.h2 || (!a1.scales && !a1.hbf) || !a1.wsplit_ready || a1.sg.Bs <= 0 || a2.B != a1.sg.n * a1.sg.Bs)) { lg_set_error("ffn_x32: several stages need pre-split fragments and B = stages x samples"); return -2; }
     if (!a1.wsplit_ready) {
         const int rc = launch_split_w(a1.w1, a1.w2, a2.w3, a1.wsplit, E, a1.hbf ? 1 : (a1.scales ? 2 : 3), s, a1.scales);
         if (rc) return rc;
     }
-    const int tiles_x = (a2.w + 15) / 16;
-    // strip height: the tallest multiple of 8 rows that still yields >= 256 strips (one resident workgroup per CU), at least 16
-    // (several stages in the launch: the strip height of ONE stage's launch)
-    const int Bsh = multi ? a1.sg.Bs : a2.B;
-    int SH = (a2.h + 7) / 8 * 8;
-    while (SH > 16 && (long)Bsh * tiles_x * ((a2.h + SH - 1) / SH) < 256) SH = (SH / 2 + 7) / 8 * 8;
-    const int strips_y = (a2.h + SH - 1) / SH;
-    const int nstrips = a2.B * tiles_x * strips_y;
-    int grid = nstrips < 256 ? nstrips : 256;
-    if (multi && a1.sg.grid_cap > 0 && grid > a1.sg.grid_cap) grid = a1.sg.grid_cap;
+    // one resident workgroup per CU; several stages in the launch: the strip height of ONE stage's launch
+    const StripGeo geo = strip_geometry(a2.h, a2.w, a2.B, multi ? a1.sg.Bs : a2.B, 256, multi ? a1.sg.grid_cap : 0);
+    const int tiles_x = geo.tiles_x, strips_y = geo.strips_y, nstrips = geo.nstrips, SH = geo.SH, grid = geo.grid;
     const u32x4_t* wsp = reinterpret_cast<const u32x4_t*>(a1.wsplit);
     const bool save = a1.h2 != nullptr;           // h2 leaves the chip only for the backward
     if (a1.hbf) {   // precision = 'bf16'

@@ -24,7 +24,6 @@ constexpr int A2_HALVES = 3 * TP * N1;           // 49152 halves (rows of 512 B,
 constexpr size_t LDS1_BYTES = (size_t)(XA_HALVES + A2_HALVES) * 2;
 constexpr int NF_W1 = 32, NF_W2 = 128;           // fragments: W1 (16 mb x 2 kb), W2 (16 mb x 8 kb), W3 (4 mb x 8 kb)
 
-__device__ __forceinline__ bf16x8_t lds_x8(const uint16_t* p) { return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4_t*>(p)); }
 __device__ __forceinline__ float oct_sum(float v) {
     v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
     v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
@@ -385,11 +384,8 @@ template <int NP>
 static int launch_ffn_x64_t(const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s) {
     static DeviceOnce attr_once;
     if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_ffn1_x64<false, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS1_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn1_x64<true, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS1_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn2_x64<false, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS2_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn2_x64<true, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS2_BYTES);
-        if (e != hipSuccess) { lg_set_error("ffn_x64: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
+        if (int rc = lds_attr_set("ffn_x64", (int)LDS1_BYTES, k_ffn1_x64<false, NP>, k_ffn1_x64<true, NP>)) return rc;
+        if (int rc = lds_attr_set("ffn_x64", (int)LDS2_BYTES, k_ffn2_x64<false, NP>, k_ffn2_x64<true, NP>)) return rc;
         attr_once.done();
     }
     if (!a1.wsplit_ready) {

@@ -97,21 +97,6 @@ static_assert(OFF_RING % 16 == 0 && OFF_TAPS % 16 == 0 && OFF_PAR % 16 == 0, "16
 template <int N>
 struct IC { static constexpr int value = N; };
 
-__device__ __forceinline__ float xg_sum(float v) {   // sum over the four lane groups (lanes c, c + 16, c + 32, c + 48); every lane gets it
-    u32x2_t r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(r.x) + __uint_as_float(r.y);
-    r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r.x) + __uint_as_float(r.y);
-}
-__device__ __forceinline__ f32x4_t mfma_h(u32x4_t a, u32x4_t b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-}
-// f16 pair of two (scaled) values: hi dword, lo dword
-__device__ __forceinline__ void pair2(float a, float b, uint32_t& hi, uint32_t& lo) {
-    hi = sb_cvt_f16x2(a, b);
-    lo = sb_cvt_f16x2(sb_res_lo(hi, a), sb_res_hi(hi, b));
-}
-
 // NP = 2: f16 pairs (the default arithmetic); NP = 1 (precision = 'bf16'): ONE round-to-nearest bf16 piece per operand, plain bf16 MFMAs, the tanh-form
 // GELU and bf16 storage of the saved tensors, as the NP = 1 instances of k_ffn_xs
 template <int NP>
@@ -123,19 +108,6 @@ __device__ __forceinline__ void pairN(float a, float b, uint32_t& hi, uint32_t& 
         hi = __builtin_bit_cast(uint32_t, v);
         lo = 0u;
     }
-}
-__device__ __forceinline__ f32x4_t mfma_b(u32x4_t a, u32x4_t b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-// acc += W X for one 32-deep k-step: the three piece products of the pairs (small terms first: lo hi, hi lo, hi hi) or the one bf16 product
-template <int NP>
-__device__ __forceinline__ f32x4_t mfma3(u32x4_t wh, u32x4_t wl, u32x4_t bh, u32x4_t bl, f32x4_t acc) {
-    if (NP == 2) {
-        acc = mfma_h(wl, bh, acc);
-        acc = mfma_h(wh, bl, acc);
-        return mfma_h(wh, bh, acc);
-    }
-    return mfma_b(wh, bh, acc);
 }
 // GEMM1 (K = 16): pairs: A = {w_lo | w_hi}, {w_hi | 0} against B = {x_hi | x_lo}, {x_hi | 0}; bf16: the second product alone
 template <int NP>
@@ -484,7 +456,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
         // co-resident workgroups start in lockstep: with both waves of a SIMD in their GELUs, then both in their GEMM2s, steps took 17.4 k ticks
         // against 13.0 k once the workgroups had drifted apart).
         auto halo_pair = [&](int ya, int blk0, const float4* xin) {
-            constexpr int npx = TY * HX;
             int c = c_;
             asm volatile("" : "+v"(c));
             const int ring0 = ((ya - Y0 + 1) % RING) * HX;
@@ -780,26 +751,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 
 // The launch geometry (host only; lg_debug_stage_decision reports it).  n <= 1: one stage of B samples.
 XrGeo ffn_xr_geometry(int h, int w, int B, int Bs, int n, int grid_cap) {
-    XrGeo q;
-    q.tiles_x = (w + 15) / 16;
-    // strip height: the tallest multiple of 8 rows that still yields >= 512 strips (two resident workgroups per CU), at least 16
-    // (several stages in the launch: the strip height of ONE stage's launch, so that a workgroup gets whole strips of that size -- three at 3 x 32 pairs)
+    // several stages in the launch: the strip height of ONE stage's launch, so that a workgroup gets whole strips of that size -- three at 3 x 32 pairs
     const bool multi = n > 1;
-    const int Bsh = multi ? Bs : B;
-    int SH = (h + 7) / 8 * 8;
-    while (SH > 16 && (long)Bsh * q.tiles_x * ((h + SH - 1) / SH) < LG_XR_GRID) SH = (SH / 2 + 7) / 8 * 8;
-    q.SH = SH;
-    q.strips_y = (h + SH - 1) / SH;
-    q.nstrips = B * q.tiles_x * q.strips_y;
-    q.grid = q.nstrips < LG_XR_GRID ? q.nstrips : LG_XR_GRID;
-    const bool capped = multi && grid_cap > 0 && q.grid > grid_cap;
-    if (capped) q.grid = grid_cap;
+    XrGeo q{strip_geometry(h, w, B, multi ? Bs : B, LG_XR_GRID, multi ? grid_cap : 0), 0};
+    const int SH = q.SH;
     // uneven split of strip pairs (strip_geo in the kernel): only in the shapes it was measured in, exactly two workgroups per CU.  One stage: one strip per
-    // workgroup.  Several: the 512 resident workgroups (a capped grid keeps the even strip runs), each pair of them on a run of strip pairs.
-    q.dS = 0;
+    // workgroup.  Several: the 512 resident workgroups (a capped grid is smaller and keeps the even strip runs), each pair of them on a run of strip pairs.
     const bool shape_ok = LG_XR_GRID == 512 && (q.strips_y & 1) == 0 && SH >= 32 && h % (2 * SH) == 0;
     if (!multi && LG_XR_UNEVEN && q.nstrips == LG_XR_GRID && shape_ok) q.dS = (SH * LG_XR_UNEVEN / 64 + 7) / 8 * 8;
-    if (multi && LG_XR_MULTI_UNEVEN && !capped && q.grid == LG_XR_GRID && (q.grid & 1) == 0 && shape_ok) q.dS = (SH * LG_XR_MULTI_UNEVEN / 64 + 7) / 8 * 8;
+    if (multi && LG_XR_MULTI_UNEVEN && q.grid == LG_XR_GRID && (q.grid & 1) == 0 && shape_ok) q.dS = (SH * LG_XR_MULTI_UNEVEN / 64 + 7) / 8 * 8;
     return q;
 }
 
@@ -807,16 +767,8 @@ int launch_ffn_xr(const Ffn1Args& a1, const Ffn2Args& a2, hipStream_t s) {
     using namespace xr;
     ProfScope prof__(LG_K_FFN2, s, a1.sg.n);
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_ffn_xr<0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_xr<3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_xr<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_xr<3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_xr<0, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_ffn_xr<0, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e != hipSuccess) { lg_set_error("ffn_xr: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_once.done();
-    }
+    if (int rc = lds_attr_once(attr_once, "ffn_xr", (int)LDS_BYTES,
+                                     k_ffn_xr<0, 2>, k_ffn_xr<3, 2>, k_ffn_xr<0, 1>, k_ffn_xr<3, 1>, k_ffn_xr<0, 2, true>, k_ffn_xr<0, 1, true>)) return rc;
     if (!a1.hbf && !a1.scales) { lg_set_error("ffn_xr: the f16-pair instance needs the operand scales"); return -2; }
     const bool save = a1.h2 != nullptr;
     if (save && (a1.a1s || a1.g1s || a2.g3s)) { lg_set_error("ffn_xr: saves h2 / h3 (or h2 alone: a3s null, the backward re-computes h3) only"); return -2; }

@@ -781,14 +781,7 @@ template <int LG>
 static int launch_fft_split_t(const FftArgs* fa, const FftBwdArgs* ba, float2* S, int planes, hipStream_t s) {
     constexpr int n = 1 << LG;
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        const void* fns[4] = {(const void*)k_fft_rows_fwd<LG>, (const void*)k_fft_cols<false, LG>, (const void*)k_fft_cols<true, LG>, (const void*)k_fft_rows_inv<LG>};
-        for (int i = 0; i < 4; ++i) {
-            hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-            if (e != hipSuccess) { lg_set_error("fft split: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        }
-        attr_once.done();
-    }
+    if (int rc = lds_attr_once(attr_once, "fft split", 160 * 1024 - 1024, k_fft_rows_fwd<LG>, k_fft_cols<false, LG>, k_fft_cols<true, LG>, k_fft_rows_inv<LG>)) return rc;
     const int R = FFT_ROWS_PER_WG(n), CB = FFT_COLS_PER_WG(n), half = n / 2;
     const size_t lds_rows = ((size_t)R * (n + 1) + half) * sizeof(float2);
     const size_t lds_cols = ((size_t)n * CB + half) * sizeof(float2) + 64 * sizeof(float);
@@ -1046,14 +1039,7 @@ static int launch_fft_generic(const FftArgs* fa, const FftBwdArgs* ba, int h, in
         return -2;
     }
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        const void* fns[4] = {(const void*)k_gfft_rows_fwd, (const void*)k_gfft_cols<false>, (const void*)k_gfft_cols<true>, (const void*)k_gfft_rows_inv};
-        for (int i = 0; i < 4; ++i) {
-            hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-            if (e != hipSuccess) { lg_set_error("fft generic: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        }
-        attr_once.done();
-    }
+    if (int rc = lds_attr_once(attr_once, "fft generic", 160 * 1024 - 1024, k_gfft_rows_fwd, k_gfft_cols<false>, k_gfft_cols<true>, k_gfft_rows_inv)) return rc;
     const GDft dw = gdft_plan(w), dh = gdft_plan(h);
     const size_t lds_r = gdft_lds_bytes(dw), lds_c = gdft_lds_bytes(dh);
     dim3 grows(planes, (h + dw.L - 1) / dw.L), gcols(planes, fft_generic_col_groups(h, w));
@@ -1090,12 +1076,7 @@ int launch_fftmix(const FftArgs& a, hipStream_t s) {
     if (!a.full) {
         if (int rc = fft_const_twiddles()) return rc;
         static DeviceOnce attr_r;
-        if (attr_r.need()) {
-            hipError_t e = hipFuncSetAttribute((const void*)k_fftmix_r<7, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024 - 512);
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_fftmix_r<7, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024 - 512);
-            if (e != hipSuccess) { lg_set_error("fftmix: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-            attr_r.done();
-        }
+        if (int rc = lds_attr_once(attr_r, "fftmix", 80 * 1024 - 512, k_fftmix_r<7, 1024>, k_fftmix_r<7, 512>)) return rc;
         const size_t ldsr = ((size_t)n * FFT_HP(n) + n / 2) * sizeof(float2);
         switch (lg) {
             case 3: k_fftmix_r<3, fftr_threads(3)><<<a.planes, fftr_threads(3), ldsr, s>>>(a); break;
@@ -1112,11 +1093,7 @@ int launch_fftmix(const FftArgs& a, hipStream_t s) {
     }
     size_t lds = ((size_t)n * FFT_LD(n) + n / 2) * sizeof(float2);
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_fftmix<7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-        if (e != hipSuccess) { lg_set_error("fftmix: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_once.done();
-    }
+    if (int rc = lds_attr_once(attr_once, "fftmix", 160 * 1024 - 1024, k_fftmix<7>)) return rc;
     int threads = fft_threads(lg);
     switch (lg) {
         case 3: k_fftmix<3><<<a.planes, threads, lds, s>>>(a); break;
@@ -1350,12 +1327,7 @@ static int launch_fftmix_bwd_kernels(const FftBwdArgs& a, hipStream_t s) {
     if (!a.full) {
         if (int rc = fft_const_twiddles()) return rc;
         static DeviceOnce attr_r;
-        if (attr_r.need()) {
-            hipError_t e = hipFuncSetAttribute((const void*)k_fftmix_bwd_r<7, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024 - 512);
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_fftmix_bwd_r<7, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024 - 512);
-            if (e != hipSuccess) { lg_set_error("fftmix_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-            attr_r.done();
-        }
+        if (int rc = lds_attr_once(attr_r, "fftmix_bwd", 80 * 1024 - 512, k_fftmix_bwd_r<7, 1024>, k_fftmix_bwd_r<7, 512>)) return rc;
         const size_t ldsr = ((size_t)n * FFT_HP(n) + n / 2) * sizeof(float2) + 64 * sizeof(float);
         switch (lg) {
             case 3: k_fftmix_bwd_r<3, fftr_threads(3)><<<a.planes, fftr_threads(3), ldsr, s>>>(a); break;
@@ -1372,11 +1344,7 @@ static int launch_fftmix_bwd_kernels(const FftBwdArgs& a, hipStream_t s) {
     }
     size_t lds = ((size_t)n * FFT_LD(n) + n / 2) * sizeof(float2) + 64 * sizeof(float);
     static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_fftmix_bwd<7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-        if (e != hipSuccess) { lg_set_error("fftmix_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_once.done();
-    }
+    if (int rc = lds_attr_once(attr_once, "fftmix_bwd", 160 * 1024 - 1024, k_fftmix_bwd<7>)) return rc;
     int threads = fft_threads(lg);
     switch (lg) {
         case 3: k_fftmix_bwd<3><<<a.planes, threads, lds, s>>>(a); break;

@@ -483,7 +483,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E == 16 ? 4
     const int ly = threadIdx.x / TX, lx = threadIdx.x - ly * TX;
     const int oy = Y0 + ly, ox = X0 + lx;
     const bool inimg = oy < a.H && ox < a.W;
-    const long p = (b * a.H + min(oy, a.H - 1)) * (long)a.W + min(ox, a.W - 1);
     // NHWC rows move COALESCED: thread t takes the float4 items t, t + 256, ... of the tile's rows (one tile row = TX pixels = TX * E
     // contiguous floats) and the per-pixel vectors are exchanged through LDS (a thread reading / writing its own 64-byte pixel vector
     // touches 64 scattered 16-byte pieces per wave-instruction).  The skip rows are requested here, early: their latency hides under

@@ -117,7 +117,22 @@ __host__ __device__ inline int stage_seg_end(int st, int run1, int per_stage) { 
 #endif
 
 // the launchers' geometry as host functions (no device, no launch): what lg_debug_stage_decision reports
-struct XrGeo { int tiles_x, SH, strips_y, nstrips, grid, dS; };
+// The strip walkers (k_ffn_xs, k_ffn_strip, k_ffn_x32, k_ffn_xr, k_ffn_dw_bwd_xs, k_ffn_dw_bwd_h): 16-column strips of SH rows, dealt to a persistent grid.
+// Strip height: the tallest multiple of 8 rows that still yields a strip per resident workgroup (`wgs`), at least 16.  Bh: the batch that sets the height --
+// B, or with several stages in the launch the samples of ONE stage, so that a workgroup gets whole strips of that stage's own launch.  grid_cap: 0 = none.
+struct StripGeo { int tiles_x, SH, strips_y, nstrips, grid; };
+inline StripGeo strip_geometry(int h, int w, int B, int Bh, int wgs, int grid_cap) {
+    StripGeo q;
+    q.tiles_x = (w + 15) / 16;
+    q.SH = (h + 7) / 8 * 8;
+    while (q.SH > 16 && (long)Bh * q.tiles_x * ((h + q.SH - 1) / q.SH) < wgs) q.SH = (q.SH / 2 + 7) / 8 * 8;
+    q.strips_y = (h + q.SH - 1) / q.SH;
+    q.nstrips = B * q.tiles_x * q.strips_y;
+    q.grid = q.nstrips < wgs ? q.nstrips : wgs;
+    if (grid_cap > 0 && q.grid > grid_cap) q.grid = grid_cap;
+    return q;
+}
+struct XrGeo : StripGeo { int dS; };
 XrGeo ffn_xr_geometry(int h, int w, int B, int Bs, int n, int grid_cap);                       // k_ffn_xr.hip; n <= 1: one stage of B samples
 struct AttnMGeo { int nwin, nquads, grid, uneven; };                                           // uneven: eighths of a CU's quads to its first workgroup, 0 = even
 AttnMGeo attn_m_geometry(int HC, int h, int w, int B, int n, int grid_cap, int per_cu);        // k_attn_m.hip; HC = e / 2 in { 8, 16, 32 }

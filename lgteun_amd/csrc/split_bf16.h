@@ -110,33 +110,42 @@ __device__ __forceinline__ void mfma_split32(f32x4_t& acc, const WFrag32& w, bf1
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.p[1], x1, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.p[0], x1, acc, 0, 0, 0);
 }
-// K = 16 blocks: v_mfma_f32_16x16x16_bf16 costs the matrix pipe what the 32-deep form costs (16 busy cycles each), so two piece products
-// share one 32-deep instruction, their operands concatenated along K:  w1 x3 + w3 x1 | w2 x2 + w2 x1 | w1 x2 + w1 x1  (small terms first)
+// K = 16 blocks, acc += A(16 x 16) * B(16 x 16): a, b = the three bf16 pieces of each operand (a WFrag16's p, or pieces read from LDS); the six
+// piece products, small terms first
+__device__ __forceinline__ void mfma_split16(f32x4_t& acc, const s16x4_t (&a)[3], const s16x4_t (&b)[3]) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], b[2], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[2], b[0], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[1], b[1], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], b[1], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[1], b[0], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], b[0], acc, 0, 0, 0);
+}
+// The same six products as THREE 32-deep MFMAs: two piece products share one instruction, their operands concatenated along K (slots 0..3
+// of a lane = one piece pair, 4..7 = another; both operands use the same order, and any order of K is a sum).  v_mfma_f32_16x16x16_bf16
+// costs the matrix pipe what the 32-deep form costs (16 busy cycles each, profiles/r03_sq_counters_*), so this halves the pipe time of a
+// K = 16 product at the price of the concatenations:  a1 b3 + a3 b1 | a2 b2 + a2 b1 | a1 b2 + a1 b1   (small terms first).
+// Whether that pays is measured per kernel: each caller hands mfma_np16 its own switch (LG_SPLIT16_PAIR, LG_KB_PAIR, LG_KA_PAIR).
 #ifndef LG_SPLIT16_PAIR
-#define LG_SPLIT16_PAIR 1
+#define LG_SPLIT16_PAIR 1   // the forward k_ffn_xs and the W3^T dy product of k_ffn_dw_bwd_h
 #endif
 __device__ __forceinline__ bf16x8_t sb_cat8(s16x4_t lo, s16x4_t hi) {
     typedef short s16x8_t __attribute__((ext_vector_type(8)));
     return __builtin_bit_cast(bf16x8_t, (s16x8_t)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
-__device__ __forceinline__ void mfma_split16_pair(f32x4_t& acc, const WFrag16& w, s16x4_t x1, s16x4_t x2, s16x4_t x3) {
-    const bf16x8_t x31 = sb_cat8(x3, x1), x21 = sb_cat8(x2, x1);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sb_cat8(w.p[0], w.p[2]), x31, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sb_cat8(w.p[1], w.p[1]), x21, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sb_cat8(w.p[0], w.p[0]), x21, acc, 0, 0, 0);
+__device__ __forceinline__ void mfma_split16_pair(f32x4_t& acc, const s16x4_t (&a)[3], const s16x4_t (&b)[3]) {
+    const bf16x8_t b31 = sb_cat8(b[2], b[0]), b21 = sb_cat8(b[1], b[0]);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sb_cat8(a[0], a[2]), b31, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sb_cat8(a[1], a[1]), b21, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sb_cat8(a[0], a[0]), b21, acc, 0, 0, 0);
 }
-__device__ __forceinline__ void mfma_split16(f32x4_t& acc, const WFrag16& w, s16x4_t x1, s16x4_t x2, s16x4_t x3) {
-#if LG_SPLIT16_PAIR
-    mfma_split16_pair(acc, w, x1, x2, x3);
-    return;
-#endif
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(w.p[0], x3, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(w.p[2], x1, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(w.p[1], x2, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(w.p[0], x2, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(w.p[1], x1, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(w.p[0], x1, acc, 0, 0, 0);
-}
+
+// LDS reads of operand fragments out of [row][k] images of 16-bit pieces: 16 bytes (a 32-deep block's k-slots), 8 bytes (a 16-deep block's)
+__device__ __forceinline__ bf16x8_t lds_x8(const uint16_t* p) { return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4_t*>(p)); }
+__device__ __forceinline__ s16x4_t lds_x4(const uint16_t* p) { return __builtin_bit_cast(s16x4_t, *reinterpret_cast<const u32x2_t*>(p)); }
+// transposed read: the 16 lanes of a group hand in the addresses of a 4-row x 16-column block of 16-bit elements (lane 4 q + p: row q,
+// columns 4 p .. 4 p + 3) and lane i gets column i of the four rows
+typedef __attribute__((address_space(3))) s16x4_t lds_s16x4_t;
+__device__ __forceinline__ s16x4_t lds_tr4(const uint16_t* p) { return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)p); }
 
 // ---- NP = 2: TWO f16 pieces per operand (round 5).  v = hi + lo with hi = f16(v) and lo = f16(v - hi), both round-to-nearest: |lo| <= 2^-12 |hi|,
 // so the pair carries 24 significant bits as long as hi is a normal f16 and lo >= 2^-24 -- i.e. for 2^-2 <= |v| < 2^16 exactly, below that
@@ -169,6 +178,29 @@ __device__ __forceinline__ void split2_x4(const float (&v)[4], u32x2_t& q1, u32x
 }
 __device__ __forceinline__ f32x4_t sb_mfma_h(bf16x8_t a, bf16x8_t b, f32x4_t c) {   // operands carried in the bf16x8_t registers of the NP = 3 code; the bits are f16
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
+}
+// the 32-deep MFMAs on operands a kernel assembles dword by dword (k_ffn_xr, k_attn_m, k_attn_bwd_m): f16 and bf16 bits in u32x4_t carriers
+__device__ __forceinline__ f32x4_t mfma_h(u32x4_t a, u32x4_t b, f32x4_t c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x4_t mfma_b(u32x4_t a, u32x4_t b, f32x4_t c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
+}
+// f16 pair of two (scaled) values: hi dword, lo dword
+__device__ __forceinline__ void pair2(float a, float b, uint32_t& hi, uint32_t& lo) {
+    hi = sb_cvt_f16x2(a, b);
+    lo = sb_cvt_f16x2(sb_res_lo(hi, a), sb_res_hi(hi, b));
+}
+// acc += A (hi, lo) * B (hi, lo) for one 32-deep k-step: the three piece products of the pairs (small terms first: lo hi, hi lo, hi hi), or
+// (NP = 1) the one bf16 product of the hi operands
+template <int NP = 2>
+__device__ __forceinline__ f32x4_t mfma3(u32x4_t ah, u32x4_t al, u32x4_t bh, u32x4_t bl, f32x4_t acc) {
+    if (NP == 2) {
+        acc = mfma_h(al, bh, acc);
+        acc = mfma_h(ah, bl, acc);
+        return mfma_h(ah, bh, acc);
+    }
+    return mfma_b(ah, bh, acc);
 }
 // weight fragments as f16 pairs of W * wscale (wscale a power of two): p[0] = hi, p[1] = lo
 __device__ __forceinline__ WFrag32 load_wfrag32_h2(const float* __restrict__ W, int K, int kb, float wscale) {
@@ -223,14 +255,15 @@ __device__ __forceinline__ void mfma_np32(f32x4_t& acc, const WFrag32& w, bf16x8
         acc = sb_mfma_h(w.p[0], x1, acc);
     } else acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.p[0], x1, acc, 0, 0, 0);
 }
-template <int NP>
-__device__ __forceinline__ void mfma_np16(f32x4_t& acc, const WFrag16& w, s16x4_t x1, s16x4_t x2, s16x4_t x3) {
-    if (NP == 3) mfma_split16(acc, w, x1, x2, x3);
-    else if (NP == 2) {   // K = 16: two piece products share one 32-deep instruction (operands concatenated along K): w_lo x_hi + w_hi x_lo | w_hi x_hi
+// PAIR: the NP = 3 products in their paired form (mfma_split16_pair); the caller's own measured switch
+template <int NP, bool PAIR>
+__device__ __forceinline__ void mfma_np16(f32x4_t& acc, const s16x4_t (&a)[3], const s16x4_t (&b)[3]) {
+    if (NP == 3) { if (PAIR) mfma_split16_pair(acc, a, b); else mfma_split16(acc, a, b); }
+    else if (NP == 2) {   // K = 16: two piece products share one 32-deep instruction (operands concatenated along K): a_lo b_hi + a_hi b_lo | a_hi b_hi
         const s16x4_t z = {0, 0, 0, 0};
-        acc = sb_mfma_h(sb_cat8(w.p[1], w.p[0]), sb_cat8(x1, x2), acc);
-        acc = sb_mfma_h(sb_cat8(w.p[0], z), sb_cat8(x1, z), acc);
-    } else acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(w.p[0], x1, acc, 0, 0, 0);
+        acc = sb_mfma_h(sb_cat8(a[1], a[0]), sb_cat8(b[0], b[1]), acc);
+        acc = sb_mfma_h(sb_cat8(a[0], z), sb_cat8(b[0], z), acc);
+    } else acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], b[0], acc, 0, 0, 0);
 }
 // weight fragments for NP = 1: piece 0 rounded to nearest (pieces 1, 2 unused)
 __device__ __forceinline__ WFrag32 load_wfrag32_rne(const float* __restrict__ W, int K, int kb) {
