@@ -322,6 +322,39 @@ int lg_iqa_ref(const float* pred, const float* gt, double* out, int32_t B, int32
 int lg_iqa_no_ref(const float* pred, const float* pan, const float* ms, double* out, int32_t B, int32_t C, int32_t H, int32_t W,
                   float scale, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the no-reference training loss 1 - QNR and its gradient (Engine.train_step with noref_weight; kernels in lgteun_amd/csrc/k_qnr.hip) ----
+ * The reference's QNRLoss (models/base/losses.py:141-153) over D_lambda_torch / D_s_torch / QIndex_torch (models/base/metrics.py:336-397):
+ * NOT the 32-pixel-block indices of lg_iqa_no_ref.  out [B,C,H,W] is the fused image, pan [B,1,H,W], ms [B,C,H/4,W/4], pan_l [B,1,H/4,W/4],
+ * fp32.  Per sample n and pair (a, b), with E the mean over the sample's pixels,
+ *   Q_n(a, b) = 4 cov E[a] E[b] / ((var_a + var_b) (E[a]^2 + E[b]^2) + 1e-8)                                    (metrics.py:347-355)
+ * and over the P = C (C - 1) / 2 + C pairs -- the band pairs i < j in row-major order, then the C band-to-PAN pairs -- the table
+ *   d[p] = mean_n Q_n,fused[p] - mean_n Q_n,ms[p]   (fused: (out_i, out_j) | (out_i, pan); ms: (ms_i, ms_j) | (ms_i, pan_l)),
+ *   D_lambda = mean_{i<j} |d_ij| (:358-376), D_s = mean_i |d_iP| (:379-397), loss = 1 - (1 - D_lambda) (1 - D_s) (losses.py:150-153).
+ * The signs of d are known only after the batch mean -- under data parallelism after every rank has contributed -- so the call is split:
+ * lg_qnr_stats leaves THIS rank's sums in `table`, the caller SUM-all-reduces the P doubles (or does nothing on one rank), lg_qnr_grad
+ * takes the result with B_global = the samples behind it.  All sums are fp64 (the product of two fp32 values is exact there): per-workgroup
+ * partials in the workspace and fixed-order finishing passes, no atomics, so the same call gives the same bits every time; the number of
+ * workgroups per sample depends on H and W only, so a sample's q row has the same bits alone and inside any batch.
+ * Both calls validate their arguments before any HIP call and name the offending one in lg_last_error: C is 4 or 8; H and W are multiples
+ * of 4, at least 8; 1 <= B <= 65535; float tensors 16-byte aligned, doubles and the workspace 8-byte aligned.  All indexing is 64-bit.  They
+ * allocate nothing and synchronise nothing. */
+/* bytes of workspace both calls need for [B, C, H, W]; 0 for shapes the calls reject */
+size_t lg_qnr_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+/* q [B,2,P] (may be NULL): Q_n of every pair, fused side then MS side; table [P] = sum_n (Q_n,fused[p] - Q_n,ms[p]) over this call's samples,
+ * n ascending.  Leaves Q and dQ_fused / d(E[a], E[b], E[aa], E[bb], E[ab]) of every sample in the workspace for lg_qnr_grad. */
+int lg_qnr_stats(const float* out, const float* pan, const float* ms, const float* pan_l, double* q, double* table, int32_t B, int32_t C,
+                 int32_t H, int32_t W, void* workspace, size_t workspace_bytes, void* stream);
+/* table: the sum over all B_global samples (B_global >= B).  With d = table / B_global and sign(0) = 0 as torch.abs differentiates,
+ *   g[n,i,p] = d loss / d out[n,i,p] = alpha_ni + sum_j beta_nij out[n,j,p] + gamma_ni pan[n,p]
+ * (every moment is linear in the pixels; the per-sample coefficients come from the stored derivatives, the signs and the factors
+ * (1 - D_s) / (C (C - 1) / 2 B_global) and (1 - D_lambda) / (C B_global)), evaluated in fp64 and rounded once:
+ * dout = fl32(scale g), or with accumulate = 1 dout = dout + fl32(scale g) in fp32.  loss_accum[0] += (float)(loss B / B_global), this
+ * rank's share, by a plain read-add-write of one lane; `scale` applies to dout only, as in lg_l1_loss.  indices [3] (may be NULL) =
+ * D_lambda, D_s, loss.  Reads only what lg_qnr_stats left for the same (B, C, H, W) in that workspace. */
+int lg_qnr_grad(const float* out, const float* pan, const double* table, float* dout, float* loss_accum, double* indices, int32_t B,
+                int64_t B_global, int32_t C, int32_t H, int32_t W, float scale, int32_t accumulate, const void* workspace,
+                size_t workspace_bytes, void* stream);
+
 /* ---- device-resident dataset (lgteun_amd/resident.py; kernels in lgteun_amd/csrc/k_batch.hip) ----
  * The store holds a whole data set on the device in the files' sample type: pan [N,1,H,W], lr [N,C,h,w], mul [N,C,H,W] (optional) and the
  * fp32 pan_l [N,1,h,w], with H = 4 h and W = 4 w.  Arguments are validated before any HIP call. */

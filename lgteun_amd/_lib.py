@@ -146,6 +146,11 @@ SIGNATURES = {
     'lg_iqa_ref': (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_size_t, c_void_p]),
     'lg_iqa_no_ref': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_size_t,
                                 c_void_p]),
+    'lg_qnr_workspace_bytes': (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    'lg_qnr_stats': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_size_t,
+                               c_void_p]),
+    'lg_qnr_grad': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32, c_float,
+                              c_int32, c_void_p, c_size_t, c_void_p]),
     'lg_pyr_down2': (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
     'lg_batch_assemble': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, c_float, c_void_p]),

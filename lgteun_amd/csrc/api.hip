@@ -1082,6 +1082,17 @@ extern "C" int lg_optim_step(float* params, const float* grads, float* state0, f
 // ------------------------------------------------------------------------------------------------
 // the controls of a train step: gradient norm + clip coefficient (k_gradnorm.hip), clipped / averaging optimizer step
 // ------------------------------------------------------------------------------------------------
+extern "C" size_t lg_qnr_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W) { return qnr_workspace_bytes(B, C, H, W); }
+extern "C" int lg_qnr_stats(const float* out, const float* pan, const float* ms, const float* pan_l, double* q, double* table, int32_t B,
+                            int32_t C, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, void* stream) {
+    return launch_qnr_stats(out, pan, ms, pan_l, q, table, B, C, H, W, workspace, workspace_bytes, (hipStream_t)stream);
+}
+extern "C" int lg_qnr_grad(const float* out, const float* pan, const double* table, float* dout, float* loss_accum, double* indices, int32_t B,
+                           int64_t B_global, int32_t C, int32_t H, int32_t W, float scale, int32_t accumulate, const void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    return launch_qnr_grad(out, pan, table, dout, loss_accum, indices, B, B_global, C, H, W, scale, accumulate, workspace, workspace_bytes,
+                           (hipStream_t)stream);
+}
 extern "C" size_t lg_grad_norm_workspace_bytes(int32_t n_ranges, int64_t max_range) { return grad_norm_workspace_bytes(n_ranges, max_range); }
 extern "C" int lg_grad_norm(const float* grads, const int64_t* ranges, int32_t n_ranges, int64_t max_range, double max_norm, float* out,
                             void* workspace, size_t workspace_bytes, void* stream) {

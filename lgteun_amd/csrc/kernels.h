@@ -29,6 +29,14 @@ size_t grad_norm_workspace_bytes(int n_ranges, int64_t max_range);
 int launch_grad_norm(const float* grads, const int64_t* ranges, int n_ranges, int64_t max_range, double max_norm, float* out, void* workspace,
                      size_t workspace_bytes, hipStream_t s);
 
+// ---------------- the no-reference training loss 1 - QNR and its gradient (k_qnr.hip; arguments validated before any HIP call) ----------------
+size_t qnr_workspace_bytes(int B, int C, int H, int W);
+int launch_qnr_stats(const float* out, const float* pan, const float* ms, const float* pan_l, double* q, double* table, int B, int C, int H,
+                     int W, void* workspace, size_t workspace_bytes, hipStream_t s);
+int launch_qnr_grad(const float* out, const float* pan, const double* table, float* dout, float* loss_accum, double* indices, int B,
+                    int64_t B_global, int C, int H, int W, float scale, int accumulate, const void* workspace, size_t workspace_bytes,
+                    hipStream_t s);
+
 // ---------------- data module (reference models/unlg_former.py:29-37,58-61) ----------------
 struct DwArgs {
     const float* in;    // [planes, hi, wi]

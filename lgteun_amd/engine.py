@@ -159,6 +159,9 @@ class Engine:
         self._ws = {}
         self._ws_pool = {}             # autograd path: released training workspaces by (plan, B, train), see _WsLease
         self._loss = self._gbuf[total:total + 1]
+        # the second float of that slot (the fill launch clears all four; nothing else reads them): the no-reference (QNR) loss of the
+        # fused step, kept apart from the reconstruction loss so that a combined step can log both terms
+        self._noref = self._gbuf[total + 1:total + 2]
         self._seed_ctr = 0
         # opt-in (LG_OVERLAP_DEAD=1 / engine.overlap_dead = True): 'faithful' training enqueues the K-1 dead-stage LGT forwards on a
         # second stream behind the LGT backward, beside the K data-step backwards + Adam (a chain of small latency-bound launches).
@@ -180,6 +183,8 @@ class Engine:
         self.local_only = False        # True: the caller runs independent replicas inside an initialised process group on purpose
         self._clip = None              # TrainControls.max_grad_norm: [norm, clip coefficient] of the last optimizer step, on the device
         self._norm_ws = None
+        self._qnr_bufs = {}            # train_step with noref_weight: (workspace, table, indices) of lg_qnr_stats / lg_qnr_grad by (B, H, W)
+        self._qnr_last = None          # ... and what the last such call used: dict(table, indices, dout), on the device
         self._window_seen = 1          # train_step calls of the current accumulation window so far (global_loss divides by it)
         self._optim = None             # the fused optimizer of the last train_step: whose 'ema' state ema_weights() swaps in
 
@@ -221,11 +226,15 @@ class Engine:
             self.buckets = {ch: GradBuckets(rg, group) for ch, (_, rg) in self._live.items()}
         return self
 
-    def global_loss(self):
+    def global_loss(self, which='rec'):
         """the GLOBAL-mean loss of the last train_step as a Python float (host sync; under DDP one scalar all-reduce: `_loss`
         holds this rank's share of the global mean).  For the logging cadence only.  Inside an accumulation window
-        (TrainControls.accumulate) `_loss` is the sum over the window's calls so far: the mean over those micro-batches is returned."""
-        t = self._loss.clone()
+        (TrainControls.accumulate) `_loss` is the sum over the window's calls so far: the mean over those micro-batches is returned.
+        which='rec': the reconstruction term (l1 / l2); which='noref': the no-reference term (1 - QNR) of a step with noref_weight.
+        Both are the unweighted loss values."""
+        if which not in ('rec', 'noref'):
+            raise ValueError(f"which must be 'rec' or 'noref' (got {which!r})")
+        t = (self._loss if which == 'rec' else self._noref).clone()
         if self._window_seen > 1:
             t /= self._window_seen
         if self.world > 1:
@@ -365,14 +374,24 @@ class Engine:
         return _LgteunFn.apply(self, ms, pan, flags, *live)
 
     # ------------------------------------------------------------------------------------------
-    def train_step(self, ms, pan, gt, optim, loss_weight=1.0, loss_type='l1'):
+    def train_step(self, ms, pan, gt, optim, loss_weight=1.0, loss_type='l1', *, pan_l=None, noref_weight=0.0):
         """forward + L1 / L2 (mean) + backward + the fused optimizer's step as library calls; returns the device loss scalar (this
         rank's share).  With `optim.controls` (TrainControls) a call is one micro-batch of a window of `accumulate` calls: the first
         clears gradients and loss, every call adds its gradients at loss scale loss_weight / accumulate and its loss to the scalar, and
         only the last issues the all-reduce, the norm (max_grad_norm) and the optimizer launch.  The learning rate applied is the one
-        `optim.param_groups[0]['lr']` holds at that last call."""
+        `optim.param_groups[0]['lr']` holds at that last call.
+        noref_weight != 0 adds noref_weight * (1 - QNR) of (output, pan, ms, pan_l) (losses.QNRLoss; lg_qnr_stats + lg_qnr_grad): it
+        needs `pan_l`, the batch's `input_pan_l`, and not a ground truth -- with gt=None the reconstruction call is skipped, the step is
+        purely unsupervised and the scalar returned is the QNR one (`_noref`, which global_loss('noref') reads).  The QNR of a
+        micro-batch is its own (the loss is not additive over samples); under data parallelism it is the QNR of the GLOBAL micro-batch,
+        through one SUM all-reduce of the P-double table between the two library calls."""
         if loss_type not in ('l1', 'l2'):
             raise ValueError(f"loss_type must be 'l1' or 'l2' (got {loss_type!r})")
+        noref = float(noref_weight) != 0.0
+        if noref and pan_l is None:
+            raise ValueError("noref_weight != 0 needs pan_l, the PAN at MS resolution: the batch's 'input_pan_l' (every loader computes it)")
+        if gt is None and not noref:
+            raise ValueError('gt=None needs noref_weight != 0: without a ground truth only the no-reference loss can train')
         self._check_attached()
         ctl = getattr(optim, 'controls', None)
         acc = ctl.accumulate if ctl is not None else 1
@@ -392,13 +411,16 @@ class Engine:
         if defer:
             flags |= LG_FLAG_DEFER_DEAD
         out, saved = self.forward_raw(ms, pan, flags, seed)
-        gt = gt.contiguous()
         dout = torch.empty_like(out)
-        n_local = out.numel()
-        loss_fn = self.lib.lg_l1_loss if loss_type == 'l1' else self.lib.lg_l2_loss
-        scale = float(loss_weight) if acc == 1 else float(loss_weight) / acc
-        check(loss_fn(_ptr(out), _ptr(gt), _ptr(dout), _ptr(self._loss), n_local, n_local * self.world, scale,
-                      _stream_ptr()), f'lg_{loss_type}_loss')
+        if gt is not None:
+            gt = gt.contiguous()
+            n_local = out.numel()
+            loss_fn = self.lib.lg_l1_loss if loss_type == 'l1' else self.lib.lg_l2_loss
+            scale = float(loss_weight) if acc == 1 else float(loss_weight) / acc
+            check(loss_fn(_ptr(out), _ptr(gt), _ptr(dout), _ptr(self._loss), n_local, n_local * self.world, scale,
+                          _stream_ptr()), f'lg_{loss_type}_loss')
+        if noref:
+            self._qnr_loss(out, saved[3], saved[2], pan_l, dout, float(noref_weight) / acc, accumulate=gt is not None)
         bk = self.buckets[bool(flags & LG_FLAG_CHAINED)] if (last and (self.world > 1 or self.force_collectives)) else None
         overlap = bool(bk is not None and bk.overlap and not (flags & LG_FLAG_CHAINED))
         if defer or overlap:
@@ -432,7 +454,35 @@ class Engine:
             optim._window_gbuf = self._gbuf            # a checkpoint written inside the window carries the gradients so far
         if defer:
             torch.cuda.current_stream().wait_stream(self._side_stream)   # the step ends when its dead-stage work has ended
-        return self._loss
+        return self._loss if gt is not None else self._noref
+
+    def _qnr_loss(self, out, pan, ms, pan_l, dout, scale, accumulate):
+        """dout (+)= scale * d(1 - QNR)/d out and `_noref` += this rank's share of the loss: lg_qnr_stats, the SUM all-reduce of the
+        table on the engine's process group (issued here, not through GradBuckets: it is no gradient bucket), lg_qnr_grad.  The signs in
+        the gradient are those of the GLOBAL batch means, which is why the table travels and not the gradient.  No host synchronisation."""
+        B, C, H, W = out.shape
+        if pan_l.dim() != 4 or tuple(pan_l.shape) != (B, 1, H // 4, W // 4) or pan_l.dtype != torch.float32 or pan_l.device != self.device:
+            raise ValueError(f"pan_l (the batch's 'input_pan_l') must be float32 [B,1,h,w] = {(B, 1, H // 4, W // 4)} on {self.device}, got "
+                             f'{pan_l.dtype} {tuple(pan_l.shape)} on {pan_l.device}')
+        pan_l = pan_l.contiguous()
+        bufs = self._qnr_bufs.get((B, H, W))
+        if bufs is None:
+            need = int(self.lib.lg_qnr_workspace_bytes(B, C, H, W))
+            if need == 0:
+                raise ValueError(f'the QNR loss takes C = 4 or 8 and H, W multiples of 4, at least 8 (got C = {C}, {H} x {W})')
+            P = C * (C - 1) // 2 + C
+            bufs = (torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device),
+                    torch.empty(P, dtype=torch.float64, device=self.device), torch.empty(3, dtype=torch.float64, device=self.device))
+            self._qnr_bufs[(B, H, W)] = bufs
+        ws, table, indices = bufs
+        check(self.lib.lg_qnr_stats(_ptr(out), _ptr(pan), _ptr(ms), _ptr(pan_l), None, _ptr(table), B, C, H, W, _ptr(ws), ws.numel() * 8,
+                                    _stream_ptr()), 'lg_qnr_stats')
+        if self.world > 1 or self.force_collectives:
+            import torch.distributed as dist
+            dist.all_reduce(table, op=dist.ReduceOp.SUM, group=self.process_group)
+        check(self.lib.lg_qnr_grad(_ptr(out), _ptr(pan), _ptr(table), _ptr(dout), _ptr(self._noref), _ptr(indices), B, B * self.world, C, H, W,
+                                   float(scale), int(bool(accumulate)), _ptr(ws), ws.numel() * 8, _stream_ptr()), 'lg_qnr_grad')
+        self._qnr_last = dict(table=table, indices=indices, dout=dout)
 
     def grad_norm(self, max_norm):
         """lg_grad_norm over the live ranges of the gradient buffer into the engine's [norm, clip coefficient] pair on the device (no host

@@ -1,9 +1,12 @@
 """The loss surface the LGTEUN runner needs (reference models/base/losses.py: `ReconstructionLoss` :19-40 and the
 `get_loss_module` factory :222-249, as used by configs/unlg_former.py:88-90 -- one `rec_loss` entry of type l1 / l2 with weight w).
-The adversarial / QNR / mutual-information losses of the comparison methods are outside this build.
-The fused train step does not call this module: it computes the loss + its gradient in `lg_l1_loss` / `lg_l2_loss`; this is the autograd-path /
-torch-optimizer route and what `get_type()` callers see."""
+`QNRLoss` (:141-153) is the no-reference term for full-resolution data, configured as `noref_loss`.  The adversarial / mutual-information
+losses of the comparison methods are outside this build.
+The fused train step does not call this module: it computes the loss + its gradient in `lg_l1_loss` / `lg_l2_loss` / `lg_qnr_stats` +
+`lg_qnr_grad`; this is the autograd-path / torch-optimizer route and what `get_type()` callers see."""
+import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 _CRITERIA = {'l1': nn.L1Loss, 'l2': nn.MSELoss}
 
@@ -28,15 +31,72 @@ class ReconstructionLoss(nn.Module):
         return self.loss(out, gt)
 
 
+def q_index(a, b, eps=1e-8):
+    """Wang-Bovik Q of every sample over its WHOLE image (QIndex_torch, reference models/base/metrics.py:336-355, before its batch mean):
+    a, b [N, H, W] -> [N]"""
+    ea, eb = a.mean(dim=(1, 2)), b.mean(dim=(1, 2))
+    var_a = (a * a).mean(dim=(1, 2)) - ea * ea
+    var_b = (b * b).mean(dim=(1, 2)) - eb * eb
+    cov = (a * b).mean(dim=(1, 2)) - ea * eb
+    return 4 * cov * ea * eb / ((var_a + var_b) * (ea * ea + eb * eb) + eps)
+
+
+def qnr_table(pan, ms, out, pan_l):
+    """the C (C - 1) / 2 + C differences mean_n Q_n(fused pair) - mean_n Q_n(MS pair): band pairs i < j in row-major order, then the
+    band-to-PAN pairs (the layout of lg_qnr_stats's table, there as sums over n)"""
+    C = out.shape[1]
+    d = [q_index(out[:, i], out[:, j]).mean() - q_index(ms[:, i], ms[:, j]).mean() for i in range(C) for j in range(i + 1, C)]
+    d += [q_index(out[:, i], pan[:, 0]).mean() - q_index(ms[:, i], pan_l[:, 0]).mean() for i in range(C)]
+    return torch.stack(d)
+
+
+class QNRLoss(nn.Module):
+    """1 - QNR = 1 - (1 - D_lambda)(1 - D_s) for data without a ground truth (reference models/base/losses.py:141-153 with
+    D_lambda_torch / D_s_torch, metrics.py:358-397, p = q = 1): D_lambda the mean over band pairs of |Q(out_i, out_j) - Q(ms_i, ms_j)|,
+    D_s the mean over bands of |Q(out_i, pan) - Q(ms_i, pan_l)|, every Q a batch mean of whole-image indices.  Q is symmetric, so the
+    reference's sum over ordered pairs i != j divided by C (C - 1) is the mean over i < j taken here.  With pan_l=None the PAN is
+    down-sampled bicubically with align_corners=True (the reference's down_sample, models/base/utils.py:127-138)."""
+
+    def __init__(self, cfg=None, logger=None):
+        super().__init__()
+        self.cfg, self.logger = cfg, logger
+
+    def get_type(self):
+        return 'qnr'
+
+    def forward(self, pan, ms, out, pan_l=None):
+        if pan_l is None:
+            pan_l = F.interpolate(pan, size=[pan.shape[2] // 4, pan.shape[3] // 4], mode='bicubic', align_corners=True)
+        C = out.shape[1]
+        d = qnr_table(pan, ms, out, pan_l).abs()
+        n_pairs = C * (C - 1) // 2
+        d_lambda, d_s = d[:n_pairs].mean(), d[n_pairs:].mean()
+        return 1 - (1 - d_lambda) * (1 - d_s)
+
+
 def get_loss_module(full_cfg, logger):
-    """{name: module} for every configured loss whose weight is non-zero; only reconstruction losses exist on this path"""
+    """{name: module} for every configured loss whose weight is non-zero: `rec_loss` entries (type l1 / l2) and the no-reference entry
+    `noref_loss` (type 'qnr').  The reference spells the latter `QNR_loss`, without a type; that key keeps ending the run here, as it
+    always has on this build (configurations and tests rely on unknown names being fatal), and its message points to `noref_loss` --
+    a name that says what the term is for and leaves room for other no-reference types."""
     modules = {}
     table = full_cfg.get('loss_cfg') or {}
     for name in table:
-        if 'rec_loss' not in name:
-            raise SystemExit(f'loss "{name}" is outside the LGTEUN hot path of this build (only rec_loss)')
         cfg = table[name]                 # attribute-style entry (mmcv Config / compat.Config) or a plain dict
         field = (lambda k: cfg[k]) if isinstance(cfg, dict) else (lambda k: getattr(cfg, k))
+        if name == 'noref_loss':
+            if field('type') != 'qnr':
+                msg = f"No such type of noref_loss: {field('type')!r} (only 'qnr')"
+                if logger is not None:
+                    logger.error(msg)
+                raise SystemExit(msg)
+            if float(field('w')) != 0.0:
+                modules[name] = QNRLoss(cfg, logger)
+            continue
+        if name == 'QNR_loss':
+            raise SystemExit("loss 'QNR_loss' is configured on this build as loss_cfg['noref_loss'] = dict(type='qnr', w=...)")
+        if 'rec_loss' not in name:
+            raise SystemExit(f'loss "{name}" is outside the LGTEUN hot path of this build (only rec_loss and noref_loss)')
         if float(field('w')) != 0.0:
             modules[name] = ReconstructionLoss(cfg, logger, loss_type=field('type'))
     return modules

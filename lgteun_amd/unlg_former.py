@@ -187,19 +187,37 @@ class UnlgFormer(Base_model):
     def train_iter(self, iter_id, input_batch, log_freq=10):
         """Same contract as the reference train_iter.  With a fused optimizer (`set_optim` default on this
         build) and a rec_loss of type l1 or l2, forward + loss + backward + optimizer step run as four library calls with no
-        per-iteration host sync (the reference's two `.item()` syncs, unlg_former.py:105,107, happen only every `log_freq`)."""
+        per-iteration host sync (the reference's two `.item()` syncs, unlg_former.py:105,107, happen only every `log_freq`).
+        A `noref_loss` entry (type 'qnr': losses.QNRLoss on the output, the PAN, the MS input and the batch's `input_pan_l`) rides in the
+        same fused step, beside the rec_loss or -- for full-resolution data, which has no target -- on its own."""
         G = self.module_dict['core_module']
         G_optim = self.optim_dict['core_module']
         loss_cfg = self.cfg.get('loss_cfg', {})
         w = float(loss_cfg['rec_loss'].w) if 'rec_loss' in self.loss_module else 0.0
+        wn = float(loss_cfg['noref_loss'].w) if 'noref_loss' in self.loss_module else 0.0
         core = G.module if hasattr(G, 'module') else G
-        if getattr(G_optim, 'is_fused_lgteun', False) and 'rec_loss' in self.loss_module and \
-                self.loss_module['rec_loss'].get_type() in ('l1', 'l2'):
+        fused_rec = 'rec_loss' in self.loss_module and self.loss_module['rec_loss'].get_type() in ('l1', 'l2')
+        if getattr(G_optim, 'is_fused_lgteun', False) and fused_rec and not wn:
             loss_t = core.engine().train_step(input_batch['input_lr'], input_batch['input_pan'], input_batch['target'],
                                               G_optim, loss_weight=w, loss_type=self.loss_module['rec_loss'].get_type())
             if iter_id % log_freq == 0:
                 v = core.engine().global_loss()        # all ranks: under DDP `loss_t` is this rank's share of the global mean
                 self.print_train_log(iter_id, dict(rec_loss=v / w if w else 0.0, full_loss=v), log_freq)
+            return
+        if getattr(G_optim, 'is_fused_lgteun', False) and wn and (fused_rec or 'rec_loss' not in self.loss_module):
+            if 'input_pan_l' not in input_batch:
+                raise ValueError("loss_cfg['noref_loss'] needs the batch's 'input_pan_l' (the PAN at MS resolution; every loader of this build "
+                                 'computes it)')
+            eng = core.engine()
+            eng.train_step(input_batch['input_lr'], input_batch['input_pan'], input_batch['target'] if fused_rec else None, G_optim,
+                           loss_weight=w, loss_type=self.loss_module['rec_loss'].get_type() if fused_rec else 'l1',
+                           pan_l=input_batch['input_pan_l'], noref_weight=wn)
+            if iter_id % log_freq == 0:
+                res = dict(noref_loss=eng.global_loss('noref'))        # the unweighted terms, and their weighted sum
+                if fused_rec:
+                    res['rec_loss'] = eng.global_loss()
+                res['full_loss'] = wn * res['noref_loss'] + w * res.get('rec_loss', 0.0)
+                self.print_train_log(iter_id, res, log_freq)
             return
         output = G(input_batch['input_lr'], input_batch['input_pan'])
         loss_g = 0
@@ -208,6 +226,11 @@ class UnlgFormer(Base_model):
             rec_loss = self.loss_module['rec_loss'](out=output, gt=input_batch['target'])
             loss_g = loss_g + rec_loss * w
             loss_res['rec_loss'] = rec_loss.item()
+        if 'noref_loss' in self.loss_module:
+            noref_loss = self.loss_module['noref_loss'](pan=input_batch['input_pan'], ms=input_batch['input_lr'], out=output,
+                                                        pan_l=input_batch.get('input_pan_l'))
+            loss_g = loss_g + noref_loss * wn
+            loss_res['noref_loss'] = noref_loss.item()
         loss_res['full_loss'] = loss_g.item()
         ctl = getattr(G_optim, 'lgteun_controls', None)      # cfg.train_cfg on torch's own optimizer: the window with torch's functions
         acc = ctl.accumulate if ctl is not None else 1

@@ -8,7 +8,11 @@ Prints one JSON line.   python tools/time_train_configs.py [--steps N] [--reps R
 With `--train-cfg JSON` (may be repeated) the tool times the train-step controls instead: the fused route of ONE configuration (`--config`,
 default l1+Adam) without `train_cfg` against the same route with each given `cfg.train_cfg`, legs alternating in the same process, e.g.
     python tools/time_train_configs.py --train-cfg '{"max_grad_norm": 1.0}' --train-cfg '{"ema_decay": 0.999}' --train-cfg '{"accumulate": 2}'
-The unit stays ms per train_iter call: with accumulate = A that is the cost per micro-batch, averaged over the window."""
+The unit stays ms per train_iter call: with accumulate = A that is the cost per micro-batch, averaged over the window.
+
+With `--noref` the tool times the no-reference loss (`loss_cfg['noref_loss']`, type 'qnr') with `--config`'s optimizer: the fused `l1` step
+against `qnr` alone and `l1 + 0.1 qnr`, each on the fused route (lg_qnr_stats + lg_qnr_grad inside Engine.train_step) and on the `fused=False`
+route (losses.QNRLoss through autograd: the reference's C^2 + C torch reductions), legs alternating in the same process."""
 import argparse
 import json
 import os
@@ -35,14 +39,17 @@ def synth_batch(device):
 
     def dn(*shape):
         return (torch.randint(0, 2048, shape, generator=g).float() / 2047.5).to(device)
-    return dict(input_lr=dn(B, C, H // 4, H // 4), input_pan=dn(B, 1, H, H), target=dn(B, C, H, H), image_id=['x'] * B)
+    return dict(input_lr=dn(B, C, H // 4, H // 4), input_pan=dn(B, 1, H, H), target=dn(B, C, H, H), image_id=['x'] * B,
+                input_pan_l=dn(B, 1, H // 4, H // 4))
 
 
 class Leg:
     def __init__(self, loss, entry, fused, work_dir, train_cfg=None):
+        """loss: 'l1' / 'l2' (one rec_loss entry of weight 1), or a whole loss_cfg"""
         extra = {} if train_cfg is None else dict(train_cfg=dict(train_cfg))
+        loss_cfg = loss if isinstance(loss, dict) else {'rec_loss': dict(type=loss, w=1.)}
         cfg = Config(dict(ms_chans=C, work_dir=work_dir, datas='GF-2', cuda=True, max_iter=10 ** 9, bit_depth=11,
-                          loss_cfg={'rec_loss': dict(type=loss, w=1.)}, optim_cfg={'core_module': dict(entry, fused=fused)},
+                          loss_cfg=loss_cfg, optim_cfg={'core_module': dict(entry, fused=fused)},
                           sched_cfg=dict(step_size=25900, gamma=0.85), model_cfg={'core_module': dict(stage=K)}, **extra))
         torch.manual_seed(19971118)
         self.runner = lgteun_amd.build_model('UnlgFormer', cfg, None, None, None, None)
@@ -78,7 +85,8 @@ def main():
     ap.add_argument('--train-cfg', action='append', default=None, metavar='JSON',
                     help='a cfg.train_cfg as a JSON object, e.g. \'{"max_grad_norm": 1.0}\'; may be repeated.  Times the fused route of --config '
                          'without train_cfg against the fused route with each of them')
-    ap.add_argument('--config', default='l1+Adam', help='LOSS+OPTIMIZER of the --train-cfg comparison (default l1+Adam)')
+    ap.add_argument('--config', default='l1+Adam', help='LOSS+OPTIMIZER of the --train-cfg comparison (default l1+Adam); --noref takes its optimizer')
+    ap.add_argument('--noref', action='store_true', help='time the no-reference loss: l1 / qnr / l1+qnr, fused and fused=False routes')
     a = ap.parse_args()
     if a.steps < 100:
         ap.error('--steps must be at least 100')
@@ -94,6 +102,8 @@ def main():
     if a.work_dir is None:
         a.work_dir = tempfile.mkdtemp(prefix='lgteun_time_')
     batch = synth_batch(torch.device('cuda', 0))
+    if a.noref:
+        return time_noref(a, batch)
     if a.train_cfg is not None:
         return time_controls(a, batch)
     rows = {}
@@ -139,6 +149,26 @@ def time_controls(a, batch):
     print(json.dumps({'tool': 'time_train_configs', 'unit': 'ms per train_iter call (median of the legs; spread = max - min of the legs)',
                       'workload': f'{a.config}, fused route, C={C}, PAN {H}x{H}, K={K}, {B} pairs, faithful mode, dropout on',
                       'steps_per_leg': a.steps, 'legs_per_case': a.reps, 'device': torch.cuda.get_device_name(0), 'train_cfg': rows}))
+
+
+def time_noref(a, batch):
+    """l1 (the untouched path), qnr and l1 + 0.1 qnr on both routes; every leg alternates with every other"""
+    name = a.config.partition('+')[2]
+    if name not in OPTIMS:
+        raise SystemExit(f'--config names one of {list(OPTIMS)} behind the +')
+    l1, qnr = dict(type='l1', w=1.), dict(type='qnr', w=1.)
+    cases = {'l1': {'rec_loss': l1}, 'qnr': {'noref_loss': qnr}, 'l1+qnr': {'rec_loss': l1, 'noref_loss': dict(qnr, w=0.1)}}
+    legs = {f'{route} {c}': Leg(cfg, OPTIMS[name], route == 'fused', a.work_dir) for c, cfg in cases.items() for route in ('fused', 'torch')}
+    for leg in legs.values():
+        leg.run(batch, a.warmup)
+    ms = {k: [] for k in legs}
+    for _ in range(a.reps):
+        for k, leg in legs.items():
+            ms[k].append(leg.timed_ms(batch, a.steps))
+    rows = {k: dict(ms=round(statistics.median(v), 4), spread_ms=round(max(v) - min(v), 4)) for k, v in ms.items()}
+    print(json.dumps({'tool': 'time_train_configs', 'unit': 'ms per train_iter (median of the legs; spread = max - min of the legs)',
+                      'workload': f'{name}, C={C}, PAN {H}x{H}, K={K}, {B} pairs, faithful mode, dropout on', 'steps_per_leg': a.steps,
+                      'legs_per_case': a.reps, 'device': torch.cuda.get_device_name(0), 'noref': rows}))
 
 
 if __name__ == '__main__':
