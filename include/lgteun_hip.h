@@ -355,6 +355,31 @@ int lg_qnr_grad(const float* out, const float* pan, const double* table, float* 
                 int64_t B_global, int32_t C, int32_t H, int32_t W, float scale, int32_t accumulate, const void* workspace,
                 size_t workspace_bytes, void* stream);
 
+/* ---- the spectral (SAM) and the structural (1 - SSIM) training loss and their gradients (Engine.train_step with spectral_weight /
+ * struct_weight; kernels in lgteun_amd/csrc/k_recloss.hip; the definitions are lgteun_amd/losses.py SAMLoss / SSIMLoss) ----
+ * The contract of lg_l1_loss -- out, gt, dout [B,C,H,W] fp32, B_global the samples of all ranks, `scale` on dout only -- plus `accumulate`
+ * (0: dout = fl32(scale g); 1: dout = dout + fl32(scale g) in fp32, after an earlier term wrote dout) and the caller's loss_accum:
+ * loss_accum[0] += (float)(this rank's share of the global mean), one read-add-write of one lane.  Both losses are means over the global
+ * batch, so the shares of the ranks add up and no collective is needed.  All arithmetic is fp64, rounded to fp32 once per dout element;
+ * per-workgroup fp64 partials in the workspace and a one-workgroup finish in a fixed order, no atomics: the same call gives the same bits, and a
+ * sample's dout has the same bits alone and inside any batch.  Arguments are validated before any HIP call and the offending one is named
+ * in lg_last_error: C is 4 or 8; W is a multiple of 4; 1 <= B <= 65535; float tensors 16-byte aligned, the workspace 8-byte aligned.  All
+ * indexing is 64-bit.  The calls allocate nothing and synchronise nothing. */
+/* bytes of workspace either call needs for [B, C, H, W]; 0 for C not in {4, 8} or W not a multiple of 4.  lg_ssim_loss also needs H and W
+ * of at least 11 (one window) and says so itself: for smaller images the size returned is lg_sam_loss's. */
+size_t lg_recloss_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+/* the mean over all B_global H W pixels of the angle between out[n,:,p] and gt[n,:,p], in radians.  Per pixel o^ = o / |o|, g^ = g / |g|,
+ * c = <o^, g^>, u = g^ - c o^, s = |u|: theta = atan2(s, c), d theta / d o = -u / (s |o|) (acos is never differentiated).  As metrics.sam
+ * clips the cosine to [0, 1]: a pixel with c <= 0, |o| = 0 or |g| = 0 counts pi / 2 and has no gradient; one with s < 1e-6 counts its theta
+ * and has no gradient (u is rounding noise there). */
+int lg_sam_loss(const float* out, const float* gt, float* dout, float* loss_accum, int32_t B, int64_t B_global, int32_t C, int32_t H, int32_t W,
+                float scale, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
+/* 1 - the mean of the SSIM map over every image, band and window that lies fully inside the image (metrics._ssim_band: 11-tap Gaussian of
+ * sigma 1.5, c1 = (0.01 data_range)^2, c2 = (0.03 data_range)^2).  With the window sums m1 = sum g x, m2 = sum g x^2, m3 = sum g x y
+ * (x = out, y = gt) and T the transposed separable Gaussian, d loss / d x(p) = -(T(dS/dm1) + 2 x T(dS/dm2) + y T(dS/dm3))(p) / windows. */
+int lg_ssim_loss(const float* out, const float* gt, float* dout, float* loss_accum, int32_t B, int64_t B_global, int32_t C, int32_t H, int32_t W,
+                 float scale, float data_range, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- device-resident dataset (lgteun_amd/resident.py; kernels in lgteun_amd/csrc/k_batch.hip) ----
  * The store holds a whole data set on the device in the files' sample type: pan [N,1,H,W], lr [N,C,h,w], mul [N,C,H,W] (optional) and the
  * fp32 pan_l [N,1,h,w], with H = 4 h and W = 4 w.  Arguments are validated before any HIP call. */

@@ -151,6 +151,11 @@ SIGNATURES = {
                                c_void_p]),
     'lg_qnr_grad': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32, c_float,
                               c_int32, c_void_p, c_size_t, c_void_p]),
+    'lg_recloss_workspace_bytes': (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    'lg_sam_loss': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32, c_float, c_int32, c_void_p,
+                              c_size_t, c_void_p]),
+    'lg_ssim_loss': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32, c_float, c_float, c_int32,
+                               c_void_p, c_size_t, c_void_p]),
     'lg_pyr_down2': (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
     'lg_batch_assemble': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, c_float, c_void_p]),

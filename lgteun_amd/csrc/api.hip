@@ -1093,6 +1093,16 @@ extern "C" int lg_qnr_grad(const float* out, const float* pan, const double* tab
     return launch_qnr_grad(out, pan, table, dout, loss_accum, indices, B, B_global, C, H, W, scale, accumulate, workspace, workspace_bytes,
                            (hipStream_t)stream);
 }
+extern "C" size_t lg_recloss_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W) { return recloss_workspace_bytes(B, C, H, W); }
+extern "C" int lg_sam_loss(const float* out, const float* gt, float* dout, float* loss_accum, int32_t B, int64_t B_global, int32_t C, int32_t H,
+                           int32_t W, float scale, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+    return launch_sam_loss(out, gt, dout, loss_accum, B, B_global, C, H, W, scale, accumulate, workspace, workspace_bytes, (hipStream_t)stream);
+}
+extern "C" int lg_ssim_loss(const float* out, const float* gt, float* dout, float* loss_accum, int32_t B, int64_t B_global, int32_t C, int32_t H,
+                            int32_t W, float scale, float data_range, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+    return launch_ssim_loss(out, gt, dout, loss_accum, B, B_global, C, H, W, scale, data_range, accumulate, workspace, workspace_bytes,
+                            (hipStream_t)stream);
+}
 extern "C" size_t lg_grad_norm_workspace_bytes(int32_t n_ranges, int64_t max_range) { return grad_norm_workspace_bytes(n_ranges, max_range); }
 extern "C" int lg_grad_norm(const float* grads, const int64_t* ranges, int32_t n_ranges, int64_t max_range, double max_norm, float* out,
                             void* workspace, size_t workspace_bytes, void* stream) {

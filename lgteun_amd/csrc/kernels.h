@@ -37,6 +37,14 @@ int launch_qnr_grad(const float* out, const float* pan, const double* table, flo
                     int64_t B_global, int C, int H, int W, float scale, int accumulate, const void* workspace, size_t workspace_bytes,
                     hipStream_t s);
 
+// ---------------- the spectral (SAM) and structural (1 - SSIM) training losses and their gradients (k_recloss.hip; arguments validated
+// before any HIP call) ----------------
+size_t recloss_workspace_bytes(int B, int C, int H, int W);
+int launch_sam_loss(const float* out, const float* gt, float* dout, float* loss_accum, int B, int64_t B_global, int C, int H, int W, float scale,
+                    int accumulate, void* workspace, size_t workspace_bytes, hipStream_t s);
+int launch_ssim_loss(const float* out, const float* gt, float* dout, float* loss_accum, int B, int64_t B_global, int C, int H, int W, float scale,
+                     float data_range, int accumulate, void* workspace, size_t workspace_bytes, hipStream_t s);
+
 // ---------------- data module (reference models/unlg_former.py:29-37,58-61) ----------------
 struct DwArgs {
     const float* in;    // [planes, hi, wi]

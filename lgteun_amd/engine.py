@@ -162,6 +162,9 @@ class Engine:
         # the second float of that slot (the fill launch clears all four; nothing else reads them): the no-reference (QNR) loss of the
         # fused step, kept apart from the reconstruction loss so that a combined step can log both terms
         self._noref = self._gbuf[total + 1:total + 2]
+        # ... and the third and fourth: the spectral (SAM) and the structural (1 - SSIM) loss of a step with spectral_weight / struct_weight
+        self._sam = self._gbuf[total + 2:total + 3]
+        self._ssim = self._gbuf[total + 3:total + 4]
         self._seed_ctr = 0
         # opt-in (LG_OVERLAP_DEAD=1 / engine.overlap_dead = True): 'faithful' training enqueues the K-1 dead-stage LGT forwards on a
         # second stream behind the LGT backward, beside the K data-step backwards + Adam (a chain of small latency-bound launches).
@@ -185,6 +188,8 @@ class Engine:
         self._norm_ws = None
         self._qnr_bufs = {}            # train_step with noref_weight: (workspace, table, indices) of lg_qnr_stats / lg_qnr_grad by (B, H, W)
         self._qnr_last = None          # ... and what the last such call used: dict(table, indices, dout), on the device
+        self._recloss_ws = {}          # train_step with spectral_weight / struct_weight: the workspace of lg_sam_loss / lg_ssim_loss by (B, H, W)
+        self._recloss_last = None      # ... and what the last such call used: dict(dout), on the device
         self._window_seen = 1          # train_step calls of the current accumulation window so far (global_loss divides by it)
         self._optim = None             # the fused optimizer of the last train_step: whose 'ema' state ema_weights() swaps in
 
@@ -230,11 +235,13 @@ class Engine:
         """the GLOBAL-mean loss of the last train_step as a Python float (host sync; under DDP one scalar all-reduce: `_loss`
         holds this rank's share of the global mean).  For the logging cadence only.  Inside an accumulation window
         (TrainControls.accumulate) `_loss` is the sum over the window's calls so far: the mean over those micro-batches is returned.
-        which='rec': the reconstruction term (l1 / l2); which='noref': the no-reference term (1 - QNR) of a step with noref_weight.
-        Both are the unweighted loss values."""
-        if which not in ('rec', 'noref'):
-            raise ValueError(f"which must be 'rec' or 'noref' (got {which!r})")
-        t = (self._loss if which == 'rec' else self._noref).clone()
+        which='rec': the reconstruction term (l1 / l2); which='noref': the no-reference term (1 - QNR) of a step with noref_weight;
+        which='sam' / 'ssim': the spectral angle / 1 - SSIM of a step with spectral_weight / struct_weight.  All are the unweighted
+        loss values."""
+        slots = dict(rec=self._loss, noref=self._noref, sam=self._sam, ssim=self._ssim)
+        if which not in slots:
+            raise ValueError(f"which must be 'rec', 'noref', 'sam' or 'ssim' (got {which!r})")
+        t = slots[which].clone()
         if self._window_seen > 1:
             t /= self._window_seen
         if self.world > 1:
@@ -374,7 +381,8 @@ class Engine:
         return _LgteunFn.apply(self, ms, pan, flags, *live)
 
     # ------------------------------------------------------------------------------------------
-    def train_step(self, ms, pan, gt, optim, loss_weight=1.0, loss_type='l1', *, pan_l=None, noref_weight=0.0):
+    def train_step(self, ms, pan, gt, optim, loss_weight=1.0, loss_type='l1', *, pan_l=None, noref_weight=0.0, spectral_weight=0.0,
+                   struct_weight=0.0, data_range=1.0):
         """forward + L1 / L2 (mean) + backward + the fused optimizer's step as library calls; returns the device loss scalar (this
         rank's share).  With `optim.controls` (TrainControls) a call is one micro-batch of a window of `accumulate` calls: the first
         clears gradients and loss, every call adds its gradients at loss scale loss_weight / accumulate and its loss to the scalar, and
@@ -384,10 +392,20 @@ class Engine:
         needs `pan_l`, the batch's `input_pan_l`, and not a ground truth -- with gt=None the reconstruction call is skipped, the step is
         purely unsupervised and the scalar returned is the QNR one (`_noref`, which global_loss('noref') reads).  The QNR of a
         micro-batch is its own (the loss is not additive over samples); under data parallelism it is the QNR of the GLOBAL micro-batch,
-        through one SUM all-reduce of the P-double table between the two library calls."""
+        through one SUM all-reduce of the P-double table between the two library calls.
+        spectral_weight != 0 adds spectral_weight * SAM(output, gt) (losses.SAMLoss; lg_sam_loss), struct_weight != 0 adds
+        struct_weight * (1 - SSIM(output, gt)) with `data_range` (losses.SSIMLoss; lg_ssim_loss); both need `gt`.  The terms meet on dout
+        in the order reconstruction, SAM, SSIM, QNR: the first one present writes it, the later ones add to it.  With one of the two, a
+        loss_weight of 0 skips the reconstruction call, so SAM / SSIM can train alone.  Both are means over the global batch: every rank
+        adds its share to `_sam` / `_ssim` (global_loss('sam' / 'ssim')) and no collective is needed.  The scalar returned is that of the
+        first term present."""
         if loss_type not in ('l1', 'l2'):
             raise ValueError(f"loss_type must be 'l1' or 'l2' (got {loss_type!r})")
         noref = float(noref_weight) != 0.0
+        sam, ssim = float(spectral_weight) != 0.0, float(struct_weight) != 0.0
+        if (sam or ssim) and gt is None:
+            raise ValueError('spectral_weight / struct_weight != 0 need gt, the target: SAM and SSIM compare the output with a ground truth')
+        rec = gt is not None and (float(loss_weight) != 0.0 or not (sam or ssim))
         if noref and pan_l is None:
             raise ValueError("noref_weight != 0 needs pan_l, the PAN at MS resolution: the batch's 'input_pan_l' (every loader computes it)")
         if gt is None and not noref:
@@ -414,13 +432,16 @@ class Engine:
         dout = torch.empty_like(out)
         if gt is not None:
             gt = gt.contiguous()
+        if rec:
             n_local = out.numel()
             loss_fn = self.lib.lg_l1_loss if loss_type == 'l1' else self.lib.lg_l2_loss
             scale = float(loss_weight) if acc == 1 else float(loss_weight) / acc
             check(loss_fn(_ptr(out), _ptr(gt), _ptr(dout), _ptr(self._loss), n_local, n_local * self.world, scale,
                           _stream_ptr()), f'lg_{loss_type}_loss')
+        if sam or ssim:
+            self._spectral_struct_loss(out, gt, dout, float(spectral_weight) / acc, float(struct_weight) / acc, float(data_range), accumulate=rec)
         if noref:
-            self._qnr_loss(out, saved[3], saved[2], pan_l, dout, float(noref_weight) / acc, accumulate=gt is not None)
+            self._qnr_loss(out, saved[3], saved[2], pan_l, dout, float(noref_weight) / acc, accumulate=rec or sam or ssim)
         bk = self.buckets[bool(flags & LG_FLAG_CHAINED)] if (last and (self.world > 1 or self.force_collectives)) else None
         overlap = bool(bk is not None and bk.overlap and not (flags & LG_FLAG_CHAINED))
         if defer or overlap:
@@ -454,7 +475,28 @@ class Engine:
             optim._window_gbuf = self._gbuf            # a checkpoint written inside the window carries the gradients so far
         if defer:
             torch.cuda.current_stream().wait_stream(self._side_stream)   # the step ends when its dead-stage work has ended
-        return self._loss if gt is not None else self._noref
+        return self._loss if rec else (self._sam if sam else (self._ssim if ssim else self._noref))
+
+    def _spectral_struct_loss(self, out, gt, dout, w_sam, w_ssim, data_range, accumulate):
+        """dout (+)= w_sam * d SAM / d out + w_ssim * d(1 - SSIM) / d out, `_sam` / `_ssim` += this rank's share of the global means:
+        lg_sam_loss, then lg_ssim_loss, one workspace for both.  accumulate: an earlier term wrote dout.  No host synchronisation."""
+        B, C, H, W = out.shape
+        if tuple(gt.shape) != (B, C, H, W) or gt.dtype != torch.float32 or gt.device != self.device:
+            raise ValueError(f'gt must be float32 {(B, C, H, W)} on {self.device}, got {gt.dtype} {tuple(gt.shape)} on {gt.device}')
+        ws = self._recloss_ws.get((B, H, W))
+        if ws is None:
+            need = int(self.lib.lg_recloss_workspace_bytes(B, C, H, W))
+            if need == 0:
+                raise ValueError(f'the SAM / SSIM losses take C = 4 or 8 and W a multiple of 4 (got C = {C}, {H} x {W})')
+            ws = self._recloss_ws[(B, H, W)] = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
+        if w_sam != 0.0:
+            check(self.lib.lg_sam_loss(_ptr(out), _ptr(gt), _ptr(dout), _ptr(self._sam), B, B * self.world, C, H, W, w_sam, int(bool(accumulate)),
+                                       _ptr(ws), ws.numel() * 8, _stream_ptr()), 'lg_sam_loss')
+            accumulate = True
+        if w_ssim != 0.0:
+            check(self.lib.lg_ssim_loss(_ptr(out), _ptr(gt), _ptr(dout), _ptr(self._ssim), B, B * self.world, C, H, W, w_ssim, data_range,
+                                        int(bool(accumulate)), _ptr(ws), ws.numel() * 8, _stream_ptr()), 'lg_ssim_loss')
+        self._recloss_last = dict(dout=dout)
 
     def _qnr_loss(self, out, pan, ms, pan_l, dout, scale, accumulate):
         """dout (+)= scale * d(1 - QNR)/d out and `_noref` += this rank's share of the loss: lg_qnr_stats, the SUM all-reduce of the

@@ -189,34 +189,51 @@ class UnlgFormer(Base_model):
         build) and a rec_loss of type l1 or l2, forward + loss + backward + optimizer step run as four library calls with no
         per-iteration host sync (the reference's two `.item()` syncs, unlg_former.py:105,107, happen only every `log_freq`).
         A `noref_loss` entry (type 'qnr': losses.QNRLoss on the output, the PAN, the MS input and the batch's `input_pan_l`) rides in the
-        same fused step, beside the rec_loss or -- for full-resolution data, which has no target -- on its own."""
+        same fused step, beside the rec_loss or -- for full-resolution data, which has no target -- on its own.  So do a `spectral_loss`
+        entry (type 'sam': losses.SAMLoss) and a `struct_loss` entry (type 'ssim': losses.SSIMLoss), which compare the output with the
+        batch's `target`.  The fused step is taken when every configured term has a fused form; the log carries each unweighted term and
+        `full_loss`, their weighted sum."""
         G = self.module_dict['core_module']
         G_optim = self.optim_dict['core_module']
         loss_cfg = self.cfg.get('loss_cfg', {})
         w = float(loss_cfg['rec_loss'].w) if 'rec_loss' in self.loss_module else 0.0
         wn = float(loss_cfg['noref_loss'].w) if 'noref_loss' in self.loss_module else 0.0
+        ws = float(loss_cfg['spectral_loss'].w) if 'spectral_loss' in self.loss_module else 0.0
+        wt = float(loss_cfg['struct_loss'].w) if 'struct_loss' in self.loss_module else 0.0
         core = G.module if hasattr(G, 'module') else G
         fused_rec = 'rec_loss' in self.loss_module and self.loss_module['rec_loss'].get_type() in ('l1', 'l2')
-        if getattr(G_optim, 'is_fused_lgteun', False) and fused_rec and not wn:
+        if (ws or wt) and input_batch.get('target') is None:
+            raise ValueError("loss_cfg['spectral_loss'] / loss_cfg['struct_loss'] need the batch's 'target': SAM and SSIM compare the output "
+                             'with a ground truth (full-resolution data has none; train it with noref_loss)')
+        if getattr(G_optim, 'is_fused_lgteun', False) and fused_rec and not (wn or ws or wt):
             loss_t = core.engine().train_step(input_batch['input_lr'], input_batch['input_pan'], input_batch['target'],
                                               G_optim, loss_weight=w, loss_type=self.loss_module['rec_loss'].get_type())
             if iter_id % log_freq == 0:
                 v = core.engine().global_loss()        # all ranks: under DDP `loss_t` is this rank's share of the global mean
                 self.print_train_log(iter_id, dict(rec_loss=v / w if w else 0.0, full_loss=v), log_freq)
             return
-        if getattr(G_optim, 'is_fused_lgteun', False) and wn and (fused_rec or 'rec_loss' not in self.loss_module):
-            if 'input_pan_l' not in input_batch:
+        if getattr(G_optim, 'is_fused_lgteun', False) and (wn or ws or wt) and (fused_rec or 'rec_loss' not in self.loss_module):
+            if wn and 'input_pan_l' not in input_batch:
                 raise ValueError("loss_cfg['noref_loss'] needs the batch's 'input_pan_l' (the PAN at MS resolution; every loader of this build "
                                  'computes it)')
             eng = core.engine()
-            eng.train_step(input_batch['input_lr'], input_batch['input_pan'], input_batch['target'] if fused_rec else None, G_optim,
+            eng.train_step(input_batch['input_lr'], input_batch['input_pan'], input_batch['target'] if fused_rec or ws or wt else None, G_optim,
                            loss_weight=w, loss_type=self.loss_module['rec_loss'].get_type() if fused_rec else 'l1',
-                           pan_l=input_batch['input_pan_l'], noref_weight=wn)
+                           pan_l=input_batch['input_pan_l'] if wn else None, noref_weight=wn, spectral_weight=ws, struct_weight=wt,
+                           data_range=self.loss_module['struct_loss'].data_range if wt else 1.0)
             if iter_id % log_freq == 0:
-                res = dict(noref_loss=eng.global_loss('noref'))        # the unweighted terms, and their weighted sum
+                res = dict()                                           # the unweighted terms, and their weighted sum
+                if wn:
+                    res['noref_loss'] = eng.global_loss('noref')
                 if fused_rec:
                     res['rec_loss'] = eng.global_loss()
-                res['full_loss'] = wn * res['noref_loss'] + w * res.get('rec_loss', 0.0)
+                if ws:
+                    res['spectral_loss'] = eng.global_loss('sam')
+                if wt:
+                    res['struct_loss'] = eng.global_loss('ssim')
+                res['full_loss'] = wn * res.get('noref_loss', 0.0) + w * res.get('rec_loss', 0.0)
+                if ws or wt:
+                    res['full_loss'] += ws * res.get('spectral_loss', 0.0) + wt * res.get('struct_loss', 0.0)
                 self.print_train_log(iter_id, res, log_freq)
             return
         output = G(input_batch['input_lr'], input_batch['input_pan'])
@@ -226,6 +243,11 @@ class UnlgFormer(Base_model):
             rec_loss = self.loss_module['rec_loss'](out=output, gt=input_batch['target'])
             loss_g = loss_g + rec_loss * w
             loss_res['rec_loss'] = rec_loss.item()
+        for name, wk in (('spectral_loss', ws), ('struct_loss', wt)):
+            if name in self.loss_module:
+                term = self.loss_module[name](out=output, gt=input_batch['target'])
+                loss_g = loss_g + term * wk
+                loss_res[name] = term.item()
         if 'noref_loss' in self.loss_module:
             noref_loss = self.loss_module['noref_loss'](pan=input_batch['input_pan'], ms=input_batch['input_lr'], out=output,
                                                         pan_l=input_batch.get('input_pan_l'))

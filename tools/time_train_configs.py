@@ -12,7 +12,11 @@ The unit stays ms per train_iter call: with accumulate = A that is the cost per 
 
 With `--noref` the tool times the no-reference loss (`loss_cfg['noref_loss']`, type 'qnr') with `--config`'s optimizer: the fused `l1` step
 against `qnr` alone and `l1 + 0.1 qnr`, each on the fused route (lg_qnr_stats + lg_qnr_grad inside Engine.train_step) and on the `fused=False`
-route (losses.QNRLoss through autograd: the reference's C^2 + C torch reductions), legs alternating in the same process."""
+route (losses.QNRLoss through autograd: the reference's C^2 + C torch reductions), legs alternating in the same process.
+
+With `--recloss` the tool times the spectral and the structural loss (`loss_cfg['spectral_loss']`, type 'sam'; `loss_cfg['struct_loss']`,
+type 'ssim') the same way: the fused `l1` step against `l1 + 0.1 sam`, `l1 + 0.1 ssim` and `l1 + 0.1 sam + 0.1 ssim`, each on the fused
+route (lg_sam_loss / lg_ssim_loss inside Engine.train_step) and on the `fused=False` route (losses.SAMLoss / SSIMLoss through autograd)."""
 import argparse
 import json
 import os
@@ -87,6 +91,7 @@ def main():
                          'without train_cfg against the fused route with each of them')
     ap.add_argument('--config', default='l1+Adam', help='LOSS+OPTIMIZER of the --train-cfg comparison (default l1+Adam); --noref takes its optimizer')
     ap.add_argument('--noref', action='store_true', help='time the no-reference loss: l1 / qnr / l1+qnr, fused and fused=False routes')
+    ap.add_argument('--recloss', action='store_true', help='time the SAM and SSIM losses: l1 / l1+sam / l1+ssim / l1+sam+ssim, both routes')
     a = ap.parse_args()
     if a.steps < 100:
         ap.error('--steps must be at least 100')
@@ -104,6 +109,8 @@ def main():
     batch = synth_batch(torch.device('cuda', 0))
     if a.noref:
         return time_noref(a, batch)
+    if a.recloss:
+        return time_recloss(a, batch)
     if a.train_cfg is not None:
         return time_controls(a, batch)
     rows = {}
@@ -158,6 +165,21 @@ def time_noref(a, batch):
         raise SystemExit(f'--config names one of {list(OPTIMS)} behind the +')
     l1, qnr = dict(type='l1', w=1.), dict(type='qnr', w=1.)
     cases = {'l1': {'rec_loss': l1}, 'qnr': {'noref_loss': qnr}, 'l1+qnr': {'rec_loss': l1, 'noref_loss': dict(qnr, w=0.1)}}
+    time_loss_cases(a, batch, name, cases, 'noref')
+
+
+def time_recloss(a, batch):
+    """l1 (the untouched path), l1 + 0.1 sam, l1 + 0.1 ssim and all three on both routes; every leg alternates with every other"""
+    name = a.config.partition('+')[2]
+    if name not in OPTIMS:
+        raise SystemExit(f'--config names one of {list(OPTIMS)} behind the +')
+    l1, sam, ssim = dict(type='l1', w=1.), dict(type='sam', w=0.1), dict(type='ssim', w=0.1, data_range=1.0)
+    cases = {'l1': {'rec_loss': l1}, 'l1+sam': {'rec_loss': l1, 'spectral_loss': sam}, 'l1+ssim': {'rec_loss': l1, 'struct_loss': ssim},
+             'l1+sam+ssim': {'rec_loss': l1, 'spectral_loss': sam, 'struct_loss': ssim}}
+    time_loss_cases(a, batch, name, cases, 'recloss')
+
+
+def time_loss_cases(a, batch, name, cases, key):
     legs = {f'{route} {c}': Leg(cfg, OPTIMS[name], route == 'fused', a.work_dir) for c, cfg in cases.items() for route in ('fused', 'torch')}
     for leg in legs.values():
         leg.run(batch, a.warmup)
@@ -168,7 +190,7 @@ def time_noref(a, batch):
     rows = {k: dict(ms=round(statistics.median(v), 4), spread_ms=round(max(v) - min(v), 4)) for k, v in ms.items()}
     print(json.dumps({'tool': 'time_train_configs', 'unit': 'ms per train_iter (median of the legs; spread = max - min of the legs)',
                       'workload': f'{name}, C={C}, PAN {H}x{H}, K={K}, {B} pairs, faithful mode, dropout on', 'steps_per_leg': a.steps,
-                      'legs_per_case': a.reps, 'device': torch.cuda.get_device_name(0), 'noref': rows}))
+                      'legs_per_case': a.reps, 'device': torch.cuda.get_device_name(0), key: rows}))
 
 
 if __name__ == '__main__':
