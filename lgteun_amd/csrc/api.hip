@@ -1,4 +1,4 @@
-// C ABI entry points (include/lgteun_hip.h): plan, forward orchestration, per-op entries, L1 loss, Adam.
+// C ABI entry points (include/lgteun_hip.h): plan, forward orchestration, per-op entries, the optimizer steps; one-line forwards to the rest.
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -684,10 +684,8 @@ extern "C" int lg_op_lgt_bwd(const lg_plan* plan, const float* params, float* gr
 }
 
 // ------------------------------------------------------------------------------------------------
-// L1 loss (mean) forward + backward -- models/base/losses.py:19-40, unlg_former.py:99-104
+// the train-mode dropout mask, exported for the fp64 oracle
 // ------------------------------------------------------------------------------------------------
-// 16-byte accesses, four of them in flight per thread, and at most 256 workgroups: every workgroup ends in one float atomic on the
-// loss scalar, and those serialise in L2 (the 1024-workgroup scalar-load form spent its 21 us there and in load latency)
 __global__ __launch_bounds__(256) void k_dropout_mask(uint64_t seed, long first, long n, float* __restrict__ out) {
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += gridDim.x * 256L) out[i] = dropout_scale(seed, (uint64_t)(first + i));
 }
@@ -700,111 +698,16 @@ extern "C" int lg_dropout_mask(uint64_t seed, int32_t stage, int32_t blk, int64_
     return 0;
 }
 
-__global__ __launch_bounds__(256) void k_l1(const float* __restrict__ out, const float* __restrict__ gt, float* __restrict__ dout,
-                                            float* loss_accum, long n, float inv_n, float gscale) {
-    float part = 0.f;
-    const long n4 = n >> 2, stride = (long)gridDim.x * 256L;
-    const float4* __restrict__ o4 = reinterpret_cast<const float4*>(out);
-    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(gt);
-    float4* __restrict__ d4 = reinterpret_cast<float4*>(dout);
-    auto one = [&](float d) { part += fabsf(d); return d > 0.f ? gscale : (d < 0.f ? -gscale : 0.f); };
-    long i = blockIdx.x * 256L + threadIdx.x;
-    for (; i + 3 * stride < n4; i += 4 * stride) {
-        float4 a[4], b[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { a[u] = o4[i + u * stride]; b[u] = g4[i + u * stride]; }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            d4[i + u * stride] = make_float4(one(a[u].x - b[u].x), one(a[u].y - b[u].y), one(a[u].z - b[u].z), one(a[u].w - b[u].w));
-    }
-    for (; i < n4; i += stride) {
-        const float4 a = o4[i], b = g4[i];
-        d4[i] = make_float4(one(a.x - b.x), one(a.y - b.y), one(a.z - b.z), one(a.w - b.w));
-    }
-    for (long j = 4 * n4 + blockIdx.x * 256L + threadIdx.x; j < n; j += stride) dout[j] = one(out[j] - gt[j]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
-    __shared__ float sm[4];
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = part;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(loss_accum, (sm[0] + sm[1] + sm[2] + sm[3]) * inv_n);
-}
-
+// ------------------------------------------------------------------------------------------------
+// l1 / l2 training losses (k_recloss.hip)
+// ------------------------------------------------------------------------------------------------
 extern "C" int lg_l1_loss(const float* out, const float* gt, float* dout, float* loss_accum, int64_t n_local, int64_t n_global,
                           float scale, void* stream) {
-    if (!out || !gt || !dout || !loss_accum || n_local <= 0 || n_global <= 0) { lg_set_error("l1_loss: invalid argument"); return -1; }
-    if (((uintptr_t)out | (uintptr_t)gt | (uintptr_t)dout) & 15) { lg_set_error("l1_loss: tensors must be 16-byte aligned"); return -1; }
-    int grid = (int)((n_local / 4 + 255) / 256);
-    if (grid > 256) grid = 256;
-    if (grid < 1) grid = 1;
-    k_l1<<<grid, 256, 0, (hipStream_t)stream>>>(out, gt, dout, loss_accum, n_local, 1.0f / (float)n_global, scale / (float)n_global);
-    LG_CHECK_LAUNCH();
-    return 0;
+    return launch_l1_loss(out, gt, dout, loss_accum, n_local, n_global, scale, (hipStream_t)stream);
 }
-
-// ------------------------------------------------------------------------------------------------
-// L2 loss (nn.MSELoss, mean) forward + backward -- models/base/losses.py:19-40 with type 'l2'
-// ------------------------------------------------------------------------------------------------
-// k_l1's access pattern and reduction shape.  The squares are summed in fp64 and the workgroups meet in an fp64 slot of the library
-// (one per launch in flight, handed out round-robin), so loss_accum takes ONE float add per launch, by the workgroup that arrives
-// last: up to 256 float atomics on the scalar would each round at the loss's magnitude, in an order that changes from run to run.
-// dout = (fl(2 / n) d) scale, rounded after each product: the bits of torch's own MSE backward (norm * (input - target) * grad_output).
-#define LG_L2_SLOTS 64
-struct l2_slot { double acc; unsigned int arrived; unsigned int pad; };
-__device__ l2_slot g_l2_slots[LG_L2_SLOTS];
-
-__global__ __launch_bounds__(256) void k_l2(const float* __restrict__ out, const float* __restrict__ gt, float* __restrict__ dout,
-                                            float* loss_accum, long n, double inv_n, float norm, float scale, int slot_id) {
-    l2_slot* slot = &g_l2_slots[slot_id];
-    double part = 0.0;
-    const long n4 = n >> 2, stride = (long)gridDim.x * 256L;
-    const float4* __restrict__ o4 = reinterpret_cast<const float4*>(out);
-    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(gt);
-    float4* __restrict__ d4 = reinterpret_cast<float4*>(dout);
-    auto one = [&](float d) { part += (double)d * (double)d; return (norm * d) * scale; };
-    long i = blockIdx.x * 256L + threadIdx.x;
-    for (; i + 3 * stride < n4; i += 4 * stride) {
-        float4 a[4], b[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { a[u] = o4[i + u * stride]; b[u] = g4[i + u * stride]; }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            d4[i + u * stride] = make_float4(one(a[u].x - b[u].x), one(a[u].y - b[u].y), one(a[u].z - b[u].z), one(a[u].w - b[u].w));
-    }
-    for (; i < n4; i += stride) {
-        const float4 a = o4[i], b = g4[i];
-        d4[i] = make_float4(one(a.x - b.x), one(a.y - b.y), one(a.z - b.z), one(a.w - b.w));
-    }
-    for (long j = 4 * n4 + blockIdx.x * 256L + threadIdx.x; j < n; j += stride) dout[j] = one(out[j] - gt[j]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
-    __shared__ double sm[4];
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = part;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        atomicAdd(&slot->acc, sm[0] + sm[1] + sm[2] + sm[3]);
-        __threadfence();
-        if (atomicAdd(&slot->arrived, 1u) == gridDim.x - 1) {       // every workgroup's sum is in: hand the slot back empty
-            __threadfence();
-            const double total = __longlong_as_double((long long)atomicExch((unsigned long long*)&slot->acc, 0ull));
-            atomicExch(&slot->arrived, 0u);
-            atomicAdd(loss_accum, (float)(total * inv_n));
-        }
-    }
-}
-
 extern "C" int lg_l2_loss(const float* out, const float* gt, float* dout, float* loss_accum, int64_t n_local, int64_t n_global,
                           float scale, void* stream) {
-    if (!out || !gt || !dout || !loss_accum || n_local <= 0 || n_global <= 0) { lg_set_error("l2_loss: invalid argument"); return -1; }
-    if (((uintptr_t)out | (uintptr_t)gt | (uintptr_t)dout) & 15) { lg_set_error("l2_loss: tensors must be 16-byte aligned"); return -1; }
-    int grid = (int)((n_local / 4 + 255) / 256);
-    if (grid > 256) grid = 256;
-    if (grid < 1) grid = 1;
-    static std::atomic<unsigned> next_slot{0};
-    k_l2<<<grid, 256, 0, (hipStream_t)stream>>>(out, gt, dout, loss_accum, n_local, 1.0 / (double)n_global, (float)(2.0 / (double)n_global), scale,
-                                                (int)(next_slot.fetch_add(1) % LG_L2_SLOTS));
-    LG_CHECK_LAUNCH();
-    return 0;
+    return launch_l2_loss(out, gt, dout, loss_accum, n_local, n_global, scale, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@
 // patterns (lane = query, lane = key) are bank-conflict free; its gradient partials leave through a slab.
 #include "kernels.h"
 #include "bwd_kernels.h"
+#include "reduce.h"
 
 // STATS (round 6): the forward's saving launch left the log-sum-exp of every score row (log2 domain, a.sl) and the attention output (a.so): pass 1 is then ONE loop
 // over the keys (scores -> P = 2^(s - L) -> dP -> dS -> dq) that reads k and v once; D_i = dO_i . O_i and the cat image come out of the prologue (k_attn_bwd_f.hip).
@@ -454,8 +455,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_epi_px(AttnBwdArgs a, long tot
 #pragma unroll
     for (int i = 0; i < 2 * E; ++i) {
         float v = pl[i];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        v = wave_sum(v);
         if (ln == 0) red[wv * 2 * E + i] = v;
     }
     __syncthreads();

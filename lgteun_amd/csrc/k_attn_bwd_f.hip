@@ -23,6 +23,7 @@
 // Three workgroup barriers per window group (tiles complete / partial sums complete / LDS free for the next group).
 #include "kernels.h"
 #include "bwd_kernels.h"
+#include "reduce.h"
 #include "mfma.h"
 #include <utility>
 
@@ -937,8 +938,7 @@ __global__ __launch_bounds__(256) void k_proj_o2_bwd_k(ProjO2BwdKArgs a) {
 #pragma unroll
     for (int n = 0; n < E; ++n) {
         float v = db[n];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        v = wave_sum(v);
         if (ln == 0) red[wv][n] = v;
     }
     __syncthreads();

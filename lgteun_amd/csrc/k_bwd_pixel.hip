@@ -8,6 +8,7 @@
 
 #include "kernels.h"
 #include "bwd_kernels.h"
+#include "reduce.h"
 #include "resample_tile.h"
 
 // sum v[0..N) over the 256 threads of the block; result valid in threads 0..N-1 (returned value for index tid)
@@ -177,8 +178,7 @@ __global__ __launch_bounds__(64) void k_reduce_chan(const float* __restrict__ pa
         for (; i < m.nslices; i += 64) sv[0] += part[((size_t)i * m.C + cc) * m.NK + k];
     }
     float t = (sv[0] + sv[1]) + (sv[2] + sv[3]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
+    t = wave_sum(t);
     if (lane == 0) {
         const int o = allc ? 0 : c * m.stride[k];
         m.dst[k][o] += t;

@@ -4,24 +4,17 @@
 //
 //   k_gradnorm_part    grid (gx, n_ranges) like the optimizer launch: workgroup (x, y) strides through range y and writes ONE fp64 partial,
 //                      partial[y * gx + x] (0 for a workgroup the range does not reach).  The square of an fp32 value is exact in fp64;
-//                      the lanes of a wave meet by shuffles, the four waves in LDS, both in a fixed order.
-//   k_gradnorm_finish  one workgroup adds the partials in a fixed order (thread t takes t, t + 256, ...; then an LDS tree) and writes
+//                      the lanes of a wave meet by shuffles, the four waves in LDS, both in a fixed order (reduce.h block_sum4).
+//   k_gradnorm_finish  one workgroup adds the partials in a fixed order (reduce.h partials_sum) and writes
 //                      out[0] = (float)sqrt(sum), out[1] = min(1, max_norm / (out[0] + 1e-6)) in fp32.
-// No floating-point atomics anywhere, so the same call gives the same bits every time (the convention of k_iqa.hip).  Scalar 4-byte
+// No floating-point atomics anywhere, so the same call gives the same bits every time (the convention of reduce.h).  Scalar 4-byte
 // loads: a range may begin and end at any float offset, and nothing outside [begin, end) is read.
 #include "common.h"
 #include "kernels.h"
+#include "reduce.h"
 
-#define GN_NT 256
+#define GN_NT 256      // block_sum4 and partials_sum are written for this
 #define GN_MAX_GX 512
-
-__device__ __forceinline__ double gn_block_sum(double v, double* sm) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sm[0] + sm[1]) + (sm[2] + sm[3]);
-}
 
 __global__ __launch_bounds__(GN_NT) void k_gradnorm_part(const float* __restrict__ g, const int64_t* __restrict__ ranges,
                                                          double* __restrict__ partial) {
@@ -41,16 +34,14 @@ __global__ __launch_bounds__(GN_NT) void k_gradnorm_part(const float* __restrict
         const double a = (double)g[i];
         acc += a * a;
     }
-    const double total = gn_block_sum(acc, sm);
+    const double total = block_sum4(acc, sm);
     if (threadIdx.x == 0) partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(GN_NT) void k_gradnorm_finish(const double* __restrict__ partial, int n_partial, float max_norm,
                                                            float* __restrict__ out) {
     __shared__ double sm[GN_NT / 64];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < n_partial; i += GN_NT) acc += partial[i];
-    const double total = gn_block_sum(acc, sm);
+    const double total = partials_sum(partial, n_partial, sm);
     if (threadIdx.x == 0) {
         const float norm = (float)sqrt(total);
         const float q = max_norm / (norm + 1e-6f);

@@ -10,13 +10,15 @@
 //   k_iqa_mtf_rows / k_iqa_mtf_cols   PAN_lr = metrics.mtf_degrade(pan), evaluated at the decimated samples only
 //   k_iqa_win<Q>     Q maps of the band pairs l < r and of the band-to-PAN pairs, at PAN resolution and at MS resolution
 //   k_iqa_fin_noref  one wave per image
-// Every sum is a per-workgroup partial in the caller's workspace followed by a fixed-order pass; no atomics.  Two calls give the same bits,
+// Every sum is a per-workgroup partial in the caller's workspace followed by a fixed-order pass; no atomics (the wave butterfly and the
+// workspace layout are reduce.h's; the workgroup and per-image sums keep their own order, below).  Two calls give the same bits,
 // and no reduction mixes images: row b of a batch is the row of image b scored alone.
 #include <float.h>
 #include <math.h>
 
 #include "common.h"
 #include "kernels.h"
+#include "reduce.h"
 
 // Inputs are scaled in fp32 and each product is rounded on its own before it is widened (the rounding of data_denormalize on the host
 // path); a product contracted into an fma with the following subtraction would round differently.  Nothing in this file is contracted,
@@ -49,14 +51,8 @@ struct WinPlanes {
 
 __device__ __forceinline__ double ld_scaled(const float* __restrict__ p, long i, float s) { return (double)__fmul_rn(p[i], s); }
 
-// butterfly sum over the 64 lanes: every lane ends with the same bits (each stage adds the same two values on both partners)
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // sum over the workgroup, valid in thread 0; every thread calls it (red: IQA_NT / 64 doubles of LDS, reused call after call)
+// not reduce.h's block_sum4: this one is reuse-safe and meets the waves left to right; another association would move the indices' last bits
 __device__ __forceinline__ double block_sum(double v, double* red) {
     v = wave_sum(v);
     __syncthreads();
@@ -326,8 +322,6 @@ WinGrid win_grid(int H, int W, int n) {
     return {tx, tx * ((ho + IQA_TY - 1) / IQA_TY), (double)ho * wo};
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct IqaGeom {
     int npix, bsm;       // reduced resolution: pixel-pass workgroups per image; no-reference: the Q window at MS resolution
     WinGrid g0, g1;      // reduced resolution: SSIM and Q tiles; no-reference: PAN-resolution and MS-resolution tiles
@@ -368,11 +362,7 @@ bool iqa_geom(int B, int C, int H, int W, int no_ref, IqaGeom& g) {
         sz[2] = (size_t)B * np * g.g0.tiles * d;
         sz[3] = (size_t)B * np * g.g1.tiles * d;
     }
-    g.bytes = 0;
-    for (int i = 0; i < 4; ++i) {
-        g.off[i] = g.bytes;
-        g.bytes += align256(sz[i]);
-    }
+    g.bytes = ws_layout(4, sz, g.off);
     return true;
 }
 

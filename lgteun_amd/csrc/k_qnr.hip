@@ -6,7 +6,8 @@
 //   k_qnr_moments<C>  grid (gf + gm, B): the first gf workgroups of a sample stream out [b] and pan [b] (float4 loads, C + 1 of them in
 //                     flight per lane), the last gm walk ms [b] and pan_l [b].  A lane keeps the M = C + C (C + 1) / 2 + C + 2 sums
 //                     { x_i | x_i x_j, i <= j | x_i p | p, p p } in fp64 (the product of two fp32 values is exact there); the lanes of a
-//                     wave meet by shuffles, the four waves in LDS, and the workgroup writes ONE row of M partials.  gf and gm depend on
+//                     wave meet by shuffles (reduce.h wave_sum), the four waves in an LDS slab of M columns -- one barrier for all M, where
+//                     block_sum4 would take M -- and the workgroup writes ONE row of M partials.  gf and gm depend on
 //                     H and W only, so a sample's Q values have the same bits in any batch.
 //   k_qnr_finish<C>   one wave per sample: the partials in ascending workgroup order, Q of the P = C (C - 1) / 2 + C pairs on both sides
 //                     and dQ / d(E[a], E[b], E[aa], E[bb], E[ab]) of the fused-side pairs -> workspace (and the caller's q)
@@ -14,12 +15,10 @@
 //   k_qnr_grad<C>     grid (gf, B): every workgroup derives D_lambda, D_s and the signs from the P table values (after the caller's
 //                     all-reduce, if any) and its sample's alpha_i, beta_ij, gamma_i from the stored derivatives, then streams the
 //                     sample: dout[i] = fl32(scale * (alpha_i + sum_j beta_ij x_j + gamma_i pan)), evaluated in fp64 and rounded once.
-// No floating-point atomics: the same call gives the same bits every time (the convention of k_iqa.hip and k_gradnorm.hip).
-#include <initializer_list>
-#include <utility>
-
+// No floating-point atomics: the same call gives the same bits every time (the convention that reduce.h implements).
 #include "common.h"
 #include "kernels.h"
+#include "reduce.h"
 
 namespace {
 
@@ -40,12 +39,6 @@ __host__ __device__ constexpr int qnr_np(int C) { return C * (C - 1) / 2 + C; }
 __host__ __device__ constexpr int qnr_m(int C) { return C + C * (C + 1) / 2 + C + 2; }
 __device__ __forceinline__ constexpr int qnr_xx(int C, int i, int j) { return i * C - i * (i - 1) / 2 + (j - i); }      // i <= j
 __device__ __forceinline__ constexpr int qnr_pair(int C, int i, int j) { return i * C - i * (i + 1) / 2 + (j - i - 1); }  // i < j
-
-__device__ __forceinline__ double qnr_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 template <int C>
 __device__ __forceinline__ void qnr_accum(double (&acc)[QnrDims<C>::M], const float (&x)[C], float p) {
@@ -119,7 +112,7 @@ __global__ __launch_bounds__(QNR_NT) void k_qnr_moments(const float* __restrict_
     }
 #pragma unroll
     for (int m = 0; m < M; ++m) {
-        const double t = qnr_wave_sum(acc[m]);
+        const double t = wave_sum(acc[m]);
         if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6][m] = t;
     }
     __syncthreads();
@@ -296,8 +289,6 @@ __global__ __launch_bounds__(QNR_NT) void k_qnr_grad(const float* __restrict__ o
     }
 }
 
-size_t qnr_align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct QnrGeom {
     int gf, gm, np, m;
     long HW, hw;
@@ -307,10 +298,8 @@ struct QnrGeom {
 
 // false: not a shape the calls take (the reason, naming the argument, is in lg_last_error)
 bool qnr_geom(const char* who, int B, int C, int H, int W, QnrGeom& g) {
-    if (B < 1 || B > 65535) { lg_set_error("%s: B must be 1..65535 (got %d)", who, B); return false; }
-    if (C != 4 && C != 8) { lg_set_error("%s: C must be 4 or 8 (got %d)", who, C); return false; }
+    if (!check_shape(who, B, C, H, W)) return false;
     if (H < 8 || W < 8 || H % 4 || W % 4) { lg_set_error("%s: H and W must be multiples of 4 and at least 8 (got %d x %d)", who, H, W); return false; }
-    if (H > 65536 || W > 65536) { lg_set_error("%s: H and W must be <= 65536 (got %d x %d)", who, H, W); return false; }
     g.HW = (long)H * W;
     g.hw = g.HW / 16;
     const long f = (g.HW + 1023) / 1024, m = (g.hw + 1023) / 1024;
@@ -319,27 +308,7 @@ bool qnr_geom(const char* who, int B, int C, int H, int W, QnrGeom& g) {
     g.np = qnr_np(C);
     g.m = qnr_m(C);
     const size_t sz[3] = {(size_t)B * g.gf * g.m * sizeof(double), (size_t)B * g.gm * g.m * sizeof(double), (size_t)B * 7 * g.np * sizeof(double)};
-    g.bytes = 0;
-    for (int i = 0; i < 3; ++i) {
-        g.off[i] = g.bytes;
-        g.bytes += qnr_align256(sz[i]);
-    }
-    return true;
-}
-
-bool qnr_check_ws(const char* who, const void* workspace, size_t workspace_bytes, const QnrGeom& g) {
-    if (!workspace) { lg_set_error("%s: workspace is NULL", who); return false; }
-    if ((uintptr_t)workspace & 7) { lg_set_error("%s: workspace must be 8-byte aligned", who); return false; }
-    if (workspace_bytes < g.bytes) { lg_set_error("%s: workspace_bytes too small: %zu, need %zu (lg_qnr_workspace_bytes)", who, workspace_bytes, g.bytes); return false; }
-    return true;
-}
-
-// the first of the named float tensors that is NULL or not 16-byte aligned; false when one is
-bool qnr_check_tensors(const char* who, std::initializer_list<std::pair<const char*, const void*>> ts) {
-    for (const auto& t : ts) {
-        if (!t.second) { lg_set_error("%s: %s is NULL", who, t.first); return false; }
-        if ((uintptr_t)t.second & 15) { lg_set_error("%s: %s must be 16-byte aligned", who, t.first); return false; }
-    }
+    g.bytes = ws_layout(3, sz, g.off);
     return true;
 }
 
@@ -355,10 +324,10 @@ int launch_qnr_stats(const float* out, const float* pan, const float* ms, const 
     static const char* who = "qnr_stats";
     QnrGeom g;
     if (!qnr_geom(who, B, C, H, W, g)) return -1;
-    if (!qnr_check_tensors(who, {{"out", out}, {"pan", pan}, {"ms", ms}, {"pan_l", pan_l}})) return -1;
+    if (!check_tensors(who, {{"out", out}, {"pan", pan}, {"ms", ms}, {"pan_l", pan_l}})) return -1;
     if (!table) { lg_set_error("%s: table is NULL", who); return -1; }
     if (((uintptr_t)table | (uintptr_t)q) & 7) { lg_set_error("%s: q and table must be 8-byte aligned", who); return -1; }
-    if (!qnr_check_ws(who, workspace, workspace_bytes, g)) return -1;
+    if (!check_workspace(who, workspace, workspace_bytes, g.bytes, "lg_qnr_workspace_bytes")) return -1;
     char* ws = (char*)workspace;
     double *pf = (double*)(ws + g.off[0]), *pm = (double*)(ws + g.off[1]), *qd = (double*)(ws + g.off[2]);
     const dim3 grid(g.gf + g.gm, B);
@@ -383,15 +352,11 @@ int launch_qnr_grad(const float* out, const float* pan, const double* table, flo
     static const char* who = "qnr_grad";
     QnrGeom g;
     if (!qnr_geom(who, B, C, H, W, g)) return -1;
-    if (B_global < B) { lg_set_error("%s: B_global must be at least B (got %lld, B = %d)", who, (long long)B_global, B); return -1; }
-    if (!qnr_check_tensors(who, {{"out", out}, {"pan", pan}, {"dout", dout}})) return -1;
+    if (!check_tensors(who, {{"out", out}, {"pan", pan}, {"dout", dout}})) return -1;
     if (!table) { lg_set_error("%s: table is NULL", who); return -1; }
-    if (!loss_accum) { lg_set_error("%s: loss_accum is NULL", who); return -1; }
     if (((uintptr_t)table | (uintptr_t)indices) & 7) { lg_set_error("%s: table and indices must be 8-byte aligned", who); return -1; }
-    if ((uintptr_t)loss_accum & 3) { lg_set_error("%s: loss_accum must be 4-byte aligned", who); return -1; }
-    if (!(scale == scale) || scale - scale != 0.f) { lg_set_error("%s: scale must be finite", who); return -1; }
-    if (accumulate != 0 && accumulate != 1) { lg_set_error("%s: accumulate must be 0 or 1 (got %d)", who, accumulate); return -1; }
-    if (!qnr_check_ws(who, workspace, workspace_bytes, g)) return -1;
+    if (!check_loss_args(who, loss_accum, B, B_global, scale, accumulate)) return -1;
+    if (!check_workspace(who, workspace, workspace_bytes, g.bytes, "lg_qnr_workspace_bytes")) return -1;
     const double* qd = (const double*)((const char*)workspace + g.off[2]);
     const dim3 grid(g.gf, B);
     if (C == 4)

@@ -1,5 +1,6 @@
-// The spectral and the structural training loss beside l1 / l2 (C ABI: lg_sam_loss / lg_ssim_loss, include/lgteun_hip.h; the definitions
-// are those of lgteun_amd/metrics.py `sam` and `_ssim_band`, restated with their gradients in lgteun_amd/losses.py SAMLoss / SSIMLoss).
+// The training losses against a target and their gradients: l1 / l2 over a flat range, the spectral (SAM) and the structural (1 - SSIM)
+// loss per sample (C ABI: lg_l1_loss / lg_l2_loss / lg_sam_loss / lg_ssim_loss, include/lgteun_hip.h; SAM and SSIM are those of
+// lgteun_amd/metrics.py `sam` and `_ssim_band`, restated with their gradients in lgteun_amd/losses.py SAMLoss / SSIMLoss).
 //
 //   k_sam_loss<C>     grid (gx, B): one streaming pass over a sample, float4 loads along W with the C band planes of out and gt of a pixel
 //                     quad in flight together.  Per pixel in fp64: o^ = o / |o|, g^ = g / |g|, c = <o^, g^>, u = g^ - c o^, s = |u|,
@@ -13,17 +14,19 @@
 //                     dout = fl32(k (T(d1) + 2 x T(d2) + y T(d3))).  The workgroup writes ONE fp64 partial: the sum of S over the windows
 //                     whose top-left pixel lies in its tile.  The staged tile stays fp32 (it is fp32 data); 64,032 bytes of LDS: two
 //                     workgroups per CU.
-//   k_recloss_finish  one workgroup: the partials in a fixed order, one float read-add-write into loss_accum.
-// No atomics: the same call gives the same bits.  A workgroup sees one sample only and the grid of a sample depends on H and W only, so a
-// sample's dout has the same bits alone and inside any batch.
+//   k_recloss_finish  one workgroup: the partials in a fixed order (reduce.h partials_sum), one float read-add-write into loss_accum.
+//   k_l1 / k_l2       at the end of the file, with their own comments: one streaming body (rl_stream_diff), two element functors.
+// SAM and SSIM use no atomics (reduce.h): the same call gives the same bits.  A workgroup sees one sample only and the grid of a sample
+// depends on H and W only, so a sample's dout has the same bits alone and inside any batch.  k_l1 / k_l2 end in atomics, as their comments say.
 #include <cmath>
 
 #include "common.h"
 #include "kernels.h"
+#include "reduce.h"
 
 namespace {
 
-constexpr int RL_NT = 256;
+constexpr int RL_NT = 256;                       // block_sum4 and partials_sum (reduce.h) are written for this
 constexpr int SAM_MAX_GX = 64;                    // workgroups per sample of the SAM pass: ceil(H W / 1024), at most this
 constexpr double SAM_MIN_S = 1e-6;                // below this |u| is rounding noise: the direction of the gradient is undefined
 constexpr double RL_HALF_PI = 1.57079632679489661923;
@@ -42,20 +45,6 @@ static_assert(2 * (SS_LDS_BYTES + 64) <= 160 * 1024, "two workgroups per CU");
 struct SsimTaps {
     double w[SS_N];
 };
-
-__device__ __forceinline__ double rl_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// sum over the workgroup's four waves, valid in thread 0
-__device__ __forceinline__ double rl_block_sum(double v, double* red) {
-    v = rl_wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 __device__ __forceinline__ float rl_lane(const float4& v, int c) { return c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w)); }
 
@@ -127,7 +116,7 @@ __global__ __launch_bounds__(RL_NT) void k_sam_loss(const float* __restrict__ ou
             d4[i * nv + v] = w;
         }
     }
-    const double t = rl_block_sum(acc, red);
+    const double t = block_sum4(acc, red);
     if (threadIdx.x == 0) part[b * gx + blockIdx.x] = t;
 }
 
@@ -255,30 +244,16 @@ __global__ __launch_bounds__(RL_NT) void k_ssim_loss(const float* __restrict__ o
             *dst = accumulate ? *dst + g : g;
         }
     }
-    const double t = rl_block_sum(ssum, red);
+    const double t = block_sum4(ssum, red);
     if (tid == 0) part[((long)blockIdx.z * C + blockIdx.y) * gridDim.x + tile] = t;
 }
 
-// loss_accum[0] += (float)((offset + sum_j part[j]) * mul), one workgroup: thread t adds j = t, t + 256, ... in ascending order (eight loads
-// in flight at a time: one wave walking the 8,192 partials of 32 x 4 planes of 128 x 128 one load after the other took 30 us), then the
-// butterfly inside a wave and the four waves in LDS -- one order, always
+// loss_accum[0] += (float)((offset + sum_j part[j]) * mul), one workgroup, the partials in the fixed order of partials_sum
 __global__ __launch_bounds__(RL_NT) void k_recloss_finish(const double* __restrict__ part, long n, double offset, double mul, float* loss_accum) {
     __shared__ double red[RL_NT / 64];
-    double v = 0.0;
-    long j = threadIdx.x;
-    for (; j + 7 * RL_NT < n; j += 8 * RL_NT) {
-        double p[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) p[u] = part[j + u * RL_NT];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v += p[u];
-    }
-    for (; j < n; j += RL_NT) v += part[j];
-    v = rl_block_sum(v, red);
+    const double v = partials_sum(part, n, red);
     if (threadIdx.x == 0) loss_accum[0] += (float)((offset + v) * mul);
 }
-
-size_t rl_align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct RlGeom {
     long HW;
@@ -289,44 +264,124 @@ struct RlGeom {
 
 // false: not a shape the calls take (the reason, naming the argument, is in lg_last_error)
 bool rl_geom(const char* who, int B, int C, int H, int W, RlGeom& g) {
-    if (B < 1 || B > 65535) { lg_set_error("%s: B must be 1..65535 (got %d)", who, B); return false; }
-    if (C != 4 && C != 8) { lg_set_error("%s: C must be 4 or 8 (got %d)", who, C); return false; }
+    if (!check_shape(who, B, C, H, W)) return false;
     if (H < 1 || W < 4 || W % 4) { lg_set_error("%s: W must be a multiple of 4 and H at least 1 (got %d x %d)", who, H, W); return false; }
-    if (H > 65536 || W > 65536) { lg_set_error("%s: H and W must be <= 65536 (got %d x %d)", who, H, W); return false; }
     g.HW = (long)H * W;
     const long f = (g.HW + 1023) / 1024;
     g.gx = (int)(f < SAM_MAX_GX ? f : SAM_MAX_GX);
-    g.sam_bytes = rl_align256((size_t)B * g.gx * sizeof(double));
+    g.sam_bytes = align256((size_t)B * g.gx * sizeof(double));
     g.tiles_x = g.tiles = 0;
     g.ssim_bytes = 0;
     if (H >= SS_N && W >= SS_N) {
         g.tiles_x = (W + SS_T - 1) / SS_T;
         g.tiles = g.tiles_x * ((H + SS_T - 1) / SS_T);
-        g.ssim_bytes = rl_align256((size_t)B * C * g.tiles * sizeof(double));
+        g.ssim_bytes = align256((size_t)B * C * g.tiles * sizeof(double));
     }
     return true;
 }
 
 bool rl_check_args(const char* who, const float* out, const float* gt, const float* dout, const float* loss_accum, int B, int64_t B_global,
                    float scale, int accumulate, const void* workspace, size_t workspace_bytes, size_t need) {
-    const void* ts[3] = {out, gt, dout};
-    const char* names[3] = {"out", "gt", "dout"};
-    for (int i = 0; i < 3; ++i) {
-        if (!ts[i]) { lg_set_error("%s: %s is NULL", who, names[i]); return false; }
-        if ((uintptr_t)ts[i] & 15) { lg_set_error("%s: %s must be 16-byte aligned", who, names[i]); return false; }
+    return check_tensors(who, {{"out", out}, {"gt", gt}, {"dout", dout}}) && check_loss_args(who, loss_accum, B, B_global, scale, accumulate) &&
+           check_workspace(who, workspace, workspace_bytes, need, "lg_recloss_workspace_bytes");
+}
+
+// The streaming body of k_l1 / k_l2 over a flat range of n floats: dout[i] = one(out[i] - gt[i]).  16-byte accesses, four of them in flight
+// per thread, then the float4 tail and the scalar tail.  `one` also gathers the thread's share of the loss.
+template <class F>
+__device__ __forceinline__ void rl_stream_diff(const float* __restrict__ out, const float* __restrict__ gt, float* __restrict__ dout, long n, F one) {
+    const long n4 = n >> 2, stride = (long)gridDim.x * 256L;
+    const float4* __restrict__ o4 = reinterpret_cast<const float4*>(out);
+    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(gt);
+    float4* __restrict__ d4 = reinterpret_cast<float4*>(dout);
+    long i = blockIdx.x * 256L + threadIdx.x;
+    for (; i + 3 * stride < n4; i += 4 * stride) {
+        float4 a[4], b[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { a[u] = o4[i + u * stride]; b[u] = g4[i + u * stride]; }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            d4[i + u * stride] = make_float4(one(a[u].x - b[u].x), one(a[u].y - b[u].y), one(a[u].z - b[u].z), one(a[u].w - b[u].w));
     }
-    if (!loss_accum) { lg_set_error("%s: loss_accum is NULL", who); return false; }
-    if ((uintptr_t)loss_accum & 3) { lg_set_error("%s: loss_accum must be 4-byte aligned", who); return false; }
-    if (B_global < B) { lg_set_error("%s: B_global must be at least B (got %lld, B = %d)", who, (long long)B_global, B); return false; }
-    if (!(scale == scale) || scale - scale != 0.f) { lg_set_error("%s: scale must be finite", who); return false; }
-    if (accumulate != 0 && accumulate != 1) { lg_set_error("%s: accumulate must be 0 or 1 (got %d)", who, accumulate); return false; }
-    if (!workspace) { lg_set_error("%s: workspace is NULL", who); return false; }
-    if ((uintptr_t)workspace & 7) { lg_set_error("%s: workspace must be 8-byte aligned", who); return false; }
-    if (workspace_bytes < need) { lg_set_error("%s: workspace_bytes too small: %zu, need %zu (lg_recloss_workspace_bytes)", who, workspace_bytes, need); return false; }
-    return true;
+    for (; i < n4; i += stride) {
+        const float4 a = o4[i], b = g4[i];
+        d4[i] = make_float4(one(a.x - b.x), one(a.y - b.y), one(a.z - b.z), one(a.w - b.w));
+    }
+    for (long j = 4 * n4 + blockIdx.x * 256L + threadIdx.x; j < n; j += stride) dout[j] = one(out[j] - gt[j]);
+}
+
+// what lg_l1_loss / lg_l2_loss check; the grid of k_l1 / k_l2, 0 when an argument is not taken
+int rl_flat_grid(const char* who, const float* out, const float* gt, const float* dout, const float* loss_accum, int64_t n_local, int64_t n_global) {
+    if (!out || !gt || !dout || !loss_accum || n_local <= 0 || n_global <= 0) { lg_set_error("%s: invalid argument", who); return 0; }
+    if (((uintptr_t)out | (uintptr_t)gt | (uintptr_t)dout) & 15) { lg_set_error("%s: tensors must be 16-byte aligned", who); return 0; }
+    const int64_t grid = (n_local / 4 + 255) / 256;
+    return (int)(grid > 256 ? 256 : (grid < 1 ? 1 : grid));
 }
 
 }  // namespace
+
+// L1 loss (mean) forward + backward -- models/base/losses.py:19-40, unlg_former.py:99-104
+// At most 256 workgroups: every workgroup ends in one float atomic on the loss scalar, and those serialise in L2 (the 1024-workgroup
+// scalar-load form spent its 21 us there and in load latency).  The four waves meet left to right, here and in k_l2: block_sum4's pairwise
+// meet would move the last bit of the loss.
+__global__ __launch_bounds__(256) void k_l1(const float* __restrict__ out, const float* __restrict__ gt, float* __restrict__ dout,
+                                            float* loss_accum, long n, float inv_n, float gscale) {
+    float part = 0.f;
+    rl_stream_diff(out, gt, dout, n, [&](float d) { part += fabsf(d); return d > 0.f ? gscale : (d < 0.f ? -gscale : 0.f); });
+    part = wave_sum(part);
+    __shared__ float sm[4];
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = part;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(loss_accum, (sm[0] + sm[1] + sm[2] + sm[3]) * inv_n);
+}
+
+int launch_l1_loss(const float* out, const float* gt, float* dout, float* loss_accum, int64_t n_local, int64_t n_global, float scale, hipStream_t s) {
+    const int grid = rl_flat_grid("l1_loss", out, gt, dout, loss_accum, n_local, n_global);
+    if (!grid) return -1;
+    k_l1<<<grid, 256, 0, s>>>(out, gt, dout, loss_accum, n_local, 1.0f / (float)n_global, scale / (float)n_global);
+    LG_CHECK_LAUNCH();
+    return 0;
+}
+
+// L2 loss (nn.MSELoss, mean) forward + backward -- models/base/losses.py:19-40 with type 'l2'
+// k_l1's access pattern and reduction shape.  The squares are summed in fp64 and the workgroups meet in an fp64 slot of the library
+// (one per launch in flight, handed out round-robin), so loss_accum takes ONE float add per launch, by the workgroup that arrives
+// last: up to 256 float atomics on the scalar would each round at the loss's magnitude, in an order that changes from run to run.
+// dout = (fl(2 / n) d) scale, rounded after each product: the bits of torch's own MSE backward (norm * (input - target) * grad_output).
+#define LG_L2_SLOTS 64
+struct l2_slot { double acc; unsigned int arrived; unsigned int pad; };
+__device__ l2_slot g_l2_slots[LG_L2_SLOTS];
+
+__global__ __launch_bounds__(256) void k_l2(const float* __restrict__ out, const float* __restrict__ gt, float* __restrict__ dout,
+                                            float* loss_accum, long n, double inv_n, float norm, float scale, int slot_id) {
+    l2_slot* slot = &g_l2_slots[slot_id];
+    double part = 0.0;
+    rl_stream_diff(out, gt, dout, n, [&](float d) { part += (double)d * (double)d; return (norm * d) * scale; });
+    part = wave_sum(part);
+    __shared__ double sm[4];
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = part;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(&slot->acc, sm[0] + sm[1] + sm[2] + sm[3]);
+        __threadfence();
+        if (atomicAdd(&slot->arrived, 1u) == gridDim.x - 1) {       // every workgroup's sum is in: hand the slot back empty
+            __threadfence();
+            const double total = __longlong_as_double((long long)atomicExch((unsigned long long*)&slot->acc, 0ull));
+            atomicExch(&slot->arrived, 0u);
+            atomicAdd(loss_accum, (float)(total * inv_n));
+        }
+    }
+}
+
+int launch_l2_loss(const float* out, const float* gt, float* dout, float* loss_accum, int64_t n_local, int64_t n_global, float scale, hipStream_t s) {
+    const int grid = rl_flat_grid("l2_loss", out, gt, dout, loss_accum, n_local, n_global);
+    if (!grid) return -1;
+    static std::atomic<unsigned> next_slot{0};
+    k_l2<<<grid, 256, 0, s>>>(out, gt, dout, loss_accum, n_local, 1.0 / (double)n_global, (float)(2.0 / (double)n_global), scale,
+                              (int)(next_slot.fetch_add(1) % LG_L2_SLOTS));
+    LG_CHECK_LAUNCH();
+    return 0;
+}
 
 size_t recloss_workspace_bytes(int B, int C, int H, int W) {
     RlGeom g;

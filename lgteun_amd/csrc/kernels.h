@@ -37,8 +37,10 @@ int launch_qnr_grad(const float* out, const float* pan, const double* table, flo
                     int64_t B_global, int C, int H, int W, float scale, int accumulate, const void* workspace, size_t workspace_bytes,
                     hipStream_t s);
 
-// ---------------- the spectral (SAM) and structural (1 - SSIM) training losses and their gradients (k_recloss.hip; arguments validated
-// before any HIP call) ----------------
+// ---------------- the training losses against a target and their gradients: l1, l2, spectral (SAM), structural (1 - SSIM) (k_recloss.hip;
+// arguments validated before any HIP call) ----------------
+int launch_l1_loss(const float* out, const float* gt, float* dout, float* loss_accum, int64_t n_local, int64_t n_global, float scale, hipStream_t s);
+int launch_l2_loss(const float* out, const float* gt, float* dout, float* loss_accum, int64_t n_local, int64_t n_global, float scale, hipStream_t s);
 size_t recloss_workspace_bytes(int B, int C, int H, int W);
 int launch_sam_loss(const float* out, const float* gt, float* dout, float* loss_accum, int B, int64_t B_global, int C, int H, int W, float scale,
                     int accumulate, void* workspace, size_t workspace_bytes, hipStream_t s);

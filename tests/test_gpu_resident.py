@@ -306,7 +306,7 @@ def test_three_train_iterations_equal_the_host_loaders(tmp_path, train_dir, tiny
     fed by the host loader, bit for bit.
 
     What "bit for bit" can mean for the LOSS: lg_l1_loss adds one partial sum per workgroup to the loss scalar with a float atomicAdd, in
-    the order the workgroups arrive, and launches ceil(n / 1024) of them (api.hip: k_l1).  With more than one workgroup two runs on the SAME
+    the order the workgroups arrive, and launches ceil(n / 1024) of them (k_recloss.hip: k_l1).  With more than one workgroup two runs on the SAME
     batches may therefore differ in the last bits of the scalar (the gradients do not depend on it: tests/test_gpu_backward.py gates
     their reproducibility).  So the loss is compared bitwise where it is defined bitwise -- PAN 16 x 16, C = 4, one pair per batch:
     n = 1024, one workgroup -- and at PAN 32 x 32 with two pairs per batch (n = 8192, G = 8 workgroups) within the reordering bound: each of

@@ -123,7 +123,7 @@ def test_train_step_batched_against_stagewise(C, K, pan, B):
     """Engine.train_step (dropout on), two steps, default against dead_stagewise: every live gradient, the weights after Adam and every
     dead stage's discarded output bitwise; dead-stage gradient slots zero.  The loss: lg_l1_loss adds one float per workgroup with atomics,
     in arrival order, so the l1 scalar of the SAME build repeats only to fp32 rounding (bench.py says so) -- it is compared to 2 ulp here,
-    and bitwise under loss_type='l2', whose scalar takes ONE float add per launch (csrc/api.hip: k_l2)."""
+    and bitwise under loss_type='l2', whose scalar takes ONE float add per launch (csrc/k_recloss.hip: k_l2)."""
     a, b = _steps(C, K, pan, B, False), _steps(C, K, pan, B, True)
     assert a['stride'] > 0 and b['stride'] > 0                      # this plan keeps every dead stage's output
     assert torch.equal(a['g'], b['g']) and float(a['g'].abs().max()) > 0

@@ -106,6 +106,18 @@ def test_grad_norm_against_numpy_fp64():
         g1 = _norm_call(buf, [(a, b)], max_norm=1e30)
         assert abs(float(g1[0]) - w1) <= float(np.spacing(np.float32(w1))), (a, b)
         assert g1[1] == np.float32(1.0)
+    # ranges of ONE element: as many partials as ranges, so these counts sit on the edges of the finishing pass's 8 x 256 unrolled loop
+    # (fewer terms than above: the same gate holds)
+    one = np.full(2 * 4100 + 1, np.nan, dtype=np.float32)
+    one[1::2] = np.random.default_rng(11).standard_normal(4100).astype(np.float32)
+    buf1 = T(one).cuda()
+    for n in (1, 255, 256, 257, 2047, 2048, 2049, 4100):
+        r1 = [(2 * k + 1, 2 * k + 2) for k in range(n)]
+        w1, _ = _f64_norm(one, r1)
+        g1 = _norm_call(buf1, r1, max_norm=1e30)
+        print(f'{n} partials: norm {g1[0]!r} against fp64 {w1!r}')
+        assert abs(float(g1[0]) - w1) <= float(np.spacing(np.float32(w1))), n
+        assert _norm_call(buf1, r1, max_norm=1e30).tobytes() == g1.tobytes(), n
 
 
 def test_grad_norm_carries_fp64():
