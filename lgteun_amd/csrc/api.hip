@@ -229,61 +229,56 @@ static int data_step_fwd(const lg_plan* pl, const float* P, int stage, const flo
     return launch_resample_dw(1, 2, a, s);
 }
 
-static int block_mixer_fwd(const lg_plan* pl, const float* P, int stage, int j, const BlockBufs& bb, const float* posT, int B,
-                           int flags, uint64_t seed, hipStream_t s, float* fft_scratch = nullptr, const float* attn_scales = nullptr,
-                           const StageSel& sg = StageSel()) {
+static int block_mixer_fwd(const Blk& k, int B, int flags, uint64_t seed, hipStream_t s, const StageSel& sg = StageSel()) {
     int rc;
+    const lg_plan* pl = k.pl;
+    const BlockBufs& bb = k.b;
     const MixerRoute& mr = pl->mixer(bb.e);
     FftArgs f;
     f.g = bb.g; f.o = bb.o2;
     f.amp = (flags & LG_FLAG_SAVE) ? bb.amp : nullptr;
     f.pha = (flags & LG_FLAG_SAVE) ? bb.pha : nullptr;
     f.sgn = (flags & LG_FLAG_SAVE) ? bb.sgn : nullptr;
-    f.scratch = fft_scratch;
-    f.ampw = P + pl->blk(stage, j, B_AMPW); f.ampb = P + pl->blk(stage, j, B_AMPB);
-    f.phaw = P + pl->blk(stage, j, B_PHAW); f.phab = P + pl->blk(stage, j, B_PHAB);
+    f.scratch = k.fft_scratch;
+    f.ampw = k.p(B_AMPW); f.ampb = k.p(B_AMPB); f.phaw = k.p(B_PHAW); f.phab = k.p(B_PHAB);
     f.ch = bb.e / 2; f.planes = B * f.ch; f.n = bb.h; f.h = bb.h; f.w = bb.w; f.full = pl->route.fft_full;
     f.sg = sg;
     if ((rc = launch_fftmix(f, s))) return rc;
     AttnArgs t;
-    t.x = bb.xin; t.o2 = bb.o2; t.y = bb.xmid; t.posT = posT; t.pos = P + pl->blk(stage, j, B_POS);
+    t.x = bb.xin; t.o2 = bb.o2; t.y = bb.xmid; t.posT = k.posT; t.pos = k.p(B_POS);
     t.bf16 = mr.bf16 ? 1 : 0;
-    t.ln1g = P + pl->blk(stage, j, B_LN1G); t.ln1b = P + pl->blk(stage, j, B_LN1B);
-    t.qkvw = P + pl->blk(stage, j, B_QKVW); t.qkvb = P + pl->blk(stage, j, B_QKVB);
-    t.projw = P + pl->blk(stage, j, B_PROJW); t.projb = P + pl->blk(stage, j, B_PROJB);
+    t.ln1g = k.p(B_LN1G); t.ln1b = k.p(B_LN1B); t.qkvw = k.p(B_QKVW); t.qkvb = k.p(B_QKVB); t.projw = k.p(B_PROJW); t.projb = k.p(B_PROJB);
     t.B = B; t.h = bb.h; t.w = bb.w;
     t.dropout = (flags & LG_FLAG_DROPOUT) ? 1 : 0;
-    t.seed = mix_seed(seed, stage, j);
-    t.sg = sg; t.sg.seed = seed; t.sg.stage0 = stage; t.sg.blk = j;   // several stages: the kernel keys each stage's mask itself
-    t.scales = (attn_scales && mr.f16x2) ? attn_scales + ((size_t)stage * 5 + j) * 4 : nullptr;   // written by prep_stages for the stages of this call
+    t.seed = mix_seed(seed, k.st, k.j);
+    t.sg = sg; t.sg.seed = seed; t.sg.stage0 = k.st; t.sg.blk = k.j;   // several stages: the kernel keys each stage's mask itself
+    t.scales = mr.f16x2 ? k.attn_scales : nullptr;   // written by prep_stages for the stages of this call
     if ((flags & LG_FLAG_SAVE) && mr.stats) { t.save_o = bb.att_o; t.save_l = bb.att_l; }
     if (sg.n > 1 && mr.fwd == ATTN_FWD_VALU) { lg_set_error("mixer: the vector-pipe kernel takes one stage per launch"); return -2; }
     return mr.fwd == ATTN_FWD_VALU ? launch_attn(bb.e, t, s) : launch_attn_m(bb.e, t, s);
 }
 
-static int block_ffn_fwd(const lg_plan* pl, const float* P, int stage, int j, const BlockBufs& bb, float* g_next, int next_blk,
-                         int B, int flags, hipStream_t s, float* wsplit, const float* ffn_scales, const StageSel& sg = StageSel()) {
+// next: the block whose mixer reads this FFN's output directly (its LN1 + planar split ride in this FFN's epilogue), or null
+static int block_ffn_fwd(const Blk& k, const Blk* next, int B, int flags, hipStream_t s, const StageSel& sg = StageSel()) {
     int rc;
-    const FfnRoute& fr = pl->ffn(bb.e);
+    const BlockBufs& bb = k.b;
+    const FfnRoute& fr = k.pl->ffn(bb.e);
     const unsigned saves = (flags & LG_FLAG_SAVE) ? fr.saves : 0;   // the slots the backward's route reads (route.h)
     Ffn1Args a1;
     a1.x = bb.xmid; a1.a1s = (saves & FFN_SLOT_A1) ? bb.a1 : nullptr; a1.g1s = (saves & FFN_SLOT_G1) ? bb.g1 : nullptr;
-    a1.ln2g = P + pl->blk(stage, j, B_LN2G); a1.ln2b = P + pl->blk(stage, j, B_LN2B);
-    a1.w1 = P + pl->blk(stage, j, B_W1); a1.b1 = P + pl->blk(stage, j, B_B1);
-    a1.w2 = P + pl->blk(stage, j, B_W2); a1.b2 = P + pl->blk(stage, j, B_B2);
+    a1.ln2g = k.p(B_LN2G); a1.ln2b = k.p(B_LN2B); a1.w1 = k.p(B_W1); a1.b1 = k.p(B_B1); a1.w2 = k.p(B_W2); a1.b2 = k.p(B_B2);
     a1.P = (long)B * bb.h * bb.w;
     a1.hbf = fr.hbf ? 1 : 0;
     a1.kernel = fr.fwd[(flags & LG_FLAG_SAVE) ? 1 : 0];
-    a1.wsplit = wsplit ? wsplit + ((size_t)stage * 5 + j) * (ffn_wsplit_bytes(8 * pl->cfg.C) / sizeof(float)) : nullptr;   // this block's slot, filled by prep_stages
-    a1.wsplit_ready = (wsplit && bb.e >= 32) ? 1 : 0;
-    a1.scales = fr.scales ? ffn_scales + ((size_t)stage * 5 + j) * 8 : nullptr;   // written by prep_stages for the stages of this call
+    a1.wsplit = k.wsplit;   // this block's slot, filled by prep_stages
+    a1.wsplit_ready = bb.e >= 32 ? 1 : 0;
+    a1.scales = fr.scales ? k.ffn_scales : nullptr;   // written by prep_stages for the stages of this call
     Ffn2Args a2;
     a2.h2 = bb.h2; a2.x = bb.xmid; a2.a3s = (saves & FFN_SLOT_A3) ? bb.a3 : nullptr; a2.g3s = (saves & FFN_SLOT_G3) ? bb.g3 : nullptr; a2.y = bb.xout;   // g3s null with a3s set: a3 receives the PRE-activation h3
-    a2.g = g_next;
-    a2.dww = P + pl->blk(stage, j, B_DWW); a2.dwb = P + pl->blk(stage, j, B_DWB);
-    a2.w3 = P + pl->blk(stage, j, B_W3); a2.b3 = P + pl->blk(stage, j, B_B3);
-    a2.n1g = g_next ? P + pl->blk(stage, next_blk, B_LN1G) : nullptr;
-    a2.n1b = g_next ? P + pl->blk(stage, next_blk, B_LN1B) : nullptr;
+    a2.g = next ? next->b.g : nullptr;
+    a2.dww = k.p(B_DWW); a2.dwb = k.p(B_DWB); a2.w3 = k.p(B_W3); a2.b3 = k.p(B_B3);
+    a2.n1g = next ? next->p(B_LN1G) : nullptr;
+    a2.n1b = next ? next->p(B_LN1B) : nullptr;
     a2.B = B; a2.h = bb.h; a2.w = bb.w; a2.hbf = a1.hbf;
     a1.h2 = bb.h2;
     a1.sg = sg;
@@ -297,115 +292,92 @@ static int block_ffn_fwd(const lg_plan* pl, const float* P, int stage, int j, co
     return launch_ffn_fused(bb.e, a1, a2, s);
 }
 
-// pos_emb^T of stages [st0, st1) into nb.posT, all tables in ONE launch (a launch per stage was 5 us + a launch gap each)
-static int pos_transpose_stages(const lg_plan* pl, const float* P, int st0, int st1, float* posT_all, hipStream_t s) {
+// what the LGTs of stages [st0, st1) need in front of their first kernel, into the rows of their blocks (workspace.h) -- one launch each for all
+// stages of the call (a launch per stage was 5 us + a launch gap each): the transposed pos_emb tables (round 2's vector-pipe mixer, LG_ATTN_FWD=valu,
+// alone reads them), the operand scales of the f16-pair FFN arithmetic, and the pre-split weight fragments of every e >= 32 block, behind the scales
+// they are multiplied by (round 5: one launch per forward call instead of one in front of every FFN launch)
+static int prep_stages(const lg_plan* pl, const float* P, int st0, int st1, const NetBufs& nb, hipStream_t s) {
     if (st1 <= st0) return 0;
-    const float* src[5 * LG_MAX_K];
-    float* dst[5 * LG_MAX_K];
-    int n = 0;
+    const float* psrc[LG_NBLK * LG_MAX_K];
+    float* pdst[LG_NBLK * LG_MAX_K];
+    FfnPrepJob jobs[LG_NBLK * LG_MAX_K];
+    SplitWJob sj[LG_NBLK * LG_MAX_K];
+    int n = 0, ns = 0, rc;
     for (int st = st0; st < st1; ++st)
-        for (int j = 0; j < 5; ++j, ++n) { src[n] = P + pl->blk(st, j, B_POS); dst[n] = posT_all + ((size_t)st * 5 + j) * 2 * 64 * 64; }
-    return launch_pos_transpose_n(n, src, dst, s);
-}
-// what the LGTs of stages [st0, st1) need in front of their first kernel: the transposed pos_emb tables (round 2's vector-pipe mixer alone reads
-// them) and the operand scales of the f16-pair FFN arithmetic -- one launch each for all stages of the call
-static int prep_stages(const lg_plan* pl, const float* P, int st0, int st1, NetBufs& nb, hipStream_t s) {
-    int rc = pl->route.mix[0].fwd == ATTN_FWD_VALU ? pos_transpose_stages(pl, P, st0, st1, nb.posT, s) : 0;   // only round 2's vector-pipe forward (LG_ATTN_FWD=valu) reads the transposed tables
-    if (rc || st1 <= st0) return rc;
-    const int E = 4 * pl->cfg.C;
-    if (pl->route.ffn[0].scales) {   // (the same at both levels)
-        FfnPrepJob jobs[5 * LG_MAX_K];
-        int n = 0;
-        for (int st = st0; st < st1; ++st)
-            for (int j = 0; j < 5; ++j, ++n) {
-                FfnPrepJob& q = jobs[n];
-                q.ln2g = P + pl->blk(st, j, B_LN2G); q.ln2b = P + pl->blk(st, j, B_LN2B);
-                q.w1 = P + pl->blk(st, j, B_W1); q.b1 = P + pl->blk(st, j, B_B1); q.w2 = P + pl->blk(st, j, B_W2); q.b2 = P + pl->blk(st, j, B_B2);
-                q.dww = P + pl->blk(st, j, B_DWW); q.dwb = P + pl->blk(st, j, B_DWB); q.w3 = P + pl->blk(st, j, B_W3);
-                q.e = j == 2 ? 2 * E : E;
-                q.ln1g = P + pl->blk(st, j, B_LN1G); q.ln1b = P + pl->blk(st, j, B_LN1B); q.qkvw = P + pl->blk(st, j, B_QKVW); q.qkvb = P + pl->blk(st, j, B_QKVB);
-            }
-        if ((rc = launch_ffn_scales(n, jobs, nb.ffn_scales + (size_t)st0 * 5 * 8, s, pl->route.mix[0].f16x2 ? nb.attn_scales + (size_t)st0 * 5 * 4 : nullptr))) return rc;
-    }
-    // the pre-split weight fragments of every e >= 32 block of these stages, behind the scales they are multiplied by (round 5: one launch per
-    // forward call instead of one in front of every FFN launch)
-    SplitWJob sj[5 * LG_MAX_K];
-    int ns = 0;
-    const size_t slot = ffn_wsplit_bytes(2 * E) / sizeof(float);
-    for (int st = st0; st < st1; ++st)
-        for (int j = 0; j < 5; ++j) {
-            const int e = j == 2 ? 2 * E : E;
-            if (e < 32 || e % 32) continue;
-            SplitWJob& q = sj[ns++];
-            q.w1 = P + pl->blk(st, j, B_W1); q.w2 = P + pl->blk(st, j, B_W2); q.w3 = P + pl->blk(st, j, B_W3);
-            q.e = e; q.np = pl->ffn(e).wsplit_np;
-            q.scales = q.np == 2 ? nb.ffn_scales + ((size_t)st * 5 + j) * 8 : nullptr;
-            q.out = nb.wsplit + ((size_t)st * 5 + j) * slot;
+        for (int j = 0; j < LG_NBLK; ++j, ++n) {
+            const Blk k = nb.block(pl, P, nullptr, st, j);
+            psrc[n] = k.p(B_POS); pdst[n] = nb.posT_row(st, j);
+            FfnPrepJob& q = jobs[n];
+            q.ln2g = k.p(B_LN2G); q.ln2b = k.p(B_LN2B); q.w1 = k.p(B_W1); q.b1 = k.p(B_B1); q.w2 = k.p(B_W2); q.b2 = k.p(B_B2);
+            q.dww = k.p(B_DWW); q.dwb = k.p(B_DWB); q.w3 = k.p(B_W3);
+            q.e = k.b.e;
+            q.ln1g = k.p(B_LN1G); q.ln1b = k.p(B_LN1B); q.qkvw = k.p(B_QKVW); q.qkvb = k.p(B_QKVB);
+            if (k.b.e < 32 || k.b.e % 32) continue;
+            SplitWJob& w = sj[ns++];
+            w.w1 = k.p(B_W1); w.w2 = k.p(B_W2); w.w3 = k.p(B_W3);
+            w.e = k.b.e; w.np = pl->ffn(k.b.e).wsplit_np;
+            w.scales = w.np == 2 ? k.ffn_scales : nullptr;
+            w.out = k.wsplit;
         }
+    if (pl->route.mix[0].fwd == ATTN_FWD_VALU && (rc = launch_pos_transpose_n(n, psrc, pdst, s))) return rc;
+    if (pl->route.ffn[0].scales &&   // (the same at both levels)
+        (rc = launch_ffn_scales(n, jobs, nb.ffn_scales_row(st0, 0), s, pl->route.mix[0].f16x2 ? nb.attn_scales_row(st0, 0) : nullptr))) return rc;
     return ns ? launch_split_w_jobs(ns, sj, s) : 0;
 }
 
-// LGT.forward (LGT.py:314-344) on z -> out with the buffers of `nb`
-// pos_ready: nb.posT already holds this stage's transposed pos_emb tables (the net-level entries transpose all stages in one launch)
+// LGT.forward (LGT.py:314-344) on z -> out with the buffers of `nb`, whose rows of this stage the caller has filled (prep_stages)
 // nst > 1: the LGTs of stages stage .. stage + nst - 1 in ONE pass, every kernel launched once over nst * B samples (kernels.h: StageSel) -- stage
 // stage + i reads z + i * zstride, writes out + i * B C H W and uses samples [i B, (i + 1) B) of every buffer of `nb` (workspace.h carves them
 // that large for a plan with stage_batch).  Never with LG_FLAG_SAVE: only dead stages run this way.
-static int lgt_fwd(const lg_plan* pl, const float* P, int stage, const float* z, float* out, NetBufs& nb, int B, int flags,
-                   uint64_t seed, hipStream_t s, bool pos_ready = false, int nst = 1, long zstride = 0, int grid_cap = 0) {
+static int lgt_fwd(const lg_plan* pl, const float* P, int stage, const float* z, float* out, const NetBufs& nb, int B, int flags,
+                   uint64_t seed, hipStream_t s, int nst = 1, long zstride = 0, int grid_cap = 0) {
     const lg_config& c = pl->cfg;
     const int E = 4 * c.C;
     int rc;
     StageSel sg;
     if (nst > 1) {
-        if (!pl->stage_batch || (flags & LG_FLAG_SAVE) || !pos_ready) { lg_set_error("lgt_fwd: this plan / call runs one stage per pass"); return -2; }
+        if (!pl->stage_batch || (flags & LG_FLAG_SAVE)) { lg_set_error("lgt_fwd: this plan / call runs one stage per pass"); return -2; }
         sg.n = nst; sg.Bs = B; sg.pstride = pl->stage_stride; sg.zstride = zstride; sg.grid_cap = grid_cap;
-        sg.fs_stride = 5 * 8; sg.as_stride = 5 * 4; sg.ws_stride = 5 * (long)ffn_wsplit_bytes(8 * c.C);   // the rows prep_stages writes per stage
+        nb.stage_strides(sg);
     }
     B *= nst;   // what every kernel below sees: a plain batch
-    float* posT = nb.posT + (size_t)stage * 5 * 2 * 64 * 64;
-    if (!pos_ready && (rc = prep_stages(pl, P, stage, stage + 1, nb, s))) return rc;
+    const LgtSlots L{pl, P, nullptr, stage};
+    Blk k[LG_NBLK];
+    for (int j = 0; j < LG_NBLK; ++j) k[j] = nb.block(pl, P, nullptr, stage, j);
     EmbedArgs ea;
     ea.z = z; ea.x = nb.x0; ea.g = nb.blk[0].g;
-    ea.dww = P + pl->lgt(stage, L_PE_DWW); ea.dwb = P + pl->lgt(stage, L_PE_DWB);
-    ea.w = P + pl->lgt(stage, L_PE_W); ea.b = P + pl->lgt(stage, L_PE_B);
-    ea.lng = P + pl->lgt(stage, L_PE_LNG); ea.lnb = P + pl->lgt(stage, L_PE_LNB);
-    ea.n1g = P + pl->blk(stage, 0, B_LN1G); ea.n1b = P + pl->blk(stage, 0, B_LN1B);
+    ea.dww = L.p(L_PE_DWW); ea.dwb = L.p(L_PE_DWB); ea.w = L.p(L_PE_W); ea.b = L.p(L_PE_B); ea.lng = L.p(L_PE_LNG); ea.lnb = L.p(L_PE_LNB);
+    ea.n1g = k[0].p(B_LN1G); ea.n1b = k[0].p(B_LN1B);
     ea.HW = c.H * c.W; ea.total = (long)B * c.H * c.W; ea.sg = sg;
     if ((rc = launch_embed(c.C, ea, s))) return rc;
     // encoder LGB (2 blocks)
-    if ((rc = block_mixer_fwd(pl, P, stage, 0, nb.blk[0], posT + 0 * 8192, B, flags, seed, s, nb.fft_scratch, nb.attn_scales, sg))) return rc;
-    if ((rc = block_ffn_fwd(pl, P, stage, 0, nb.blk[0], nb.blk[1].g, 1, B, flags, s, nb.wsplit, nb.ffn_scales, sg))) return rc;
-    if ((rc = block_mixer_fwd(pl, P, stage, 1, nb.blk[1], posT + 1 * 8192, B, flags, seed, s, nb.fft_scratch, nb.attn_scales, sg))) return rc;
-    if ((rc = block_ffn_fwd(pl, P, stage, 1, nb.blk[1], nullptr, 0, B, flags, s, nb.wsplit, nb.ffn_scales, sg))) return rc;
+    if ((rc = block_mixer_fwd(k[0], B, flags, seed, s, sg)) || (rc = block_ffn_fwd(k[0], &k[1], B, flags, s, sg))) return rc;
+    if ((rc = block_mixer_fwd(k[1], B, flags, seed, s, sg)) || (rc = block_ffn_fwd(k[1], nullptr, B, flags, s, sg))) return rc;
     // down
     DownArgs da;
     da.x = nb.blk[1].xout; da.y = nb.blk[2].xin; da.g = nb.blk[2].g;
     da.u_save = (flags & LG_FLAG_SAVE) ? nb.u_down : nullptr;
-    da.w = P + pl->lgt(stage, L_DOWNW); da.b = P + pl->lgt(stage, L_DOWNB);
-    da.n1g = P + pl->blk(stage, 2, B_LN1G); da.n1b = P + pl->blk(stage, 2, B_LN1B);
+    da.w = L.p(L_DOWNW); da.b = L.p(L_DOWNB);
+    da.n1g = k[2].p(B_LN1G); da.n1b = k[2].p(B_LN1B);
     da.B = B; da.H = c.H; da.W = c.W; da.sg = sg;
     if ((rc = launch_down(E, da, s))) return rc;
     // bottleneck
-    if ((rc = block_mixer_fwd(pl, P, stage, 2, nb.blk[2], posT + 2 * 8192, B, flags, seed, s, nb.fft_scratch, nb.attn_scales, sg))) return rc;
-    if ((rc = block_ffn_fwd(pl, P, stage, 2, nb.blk[2], nullptr, 0, B, flags, s, nb.wsplit, nb.ffn_scales, sg))) return rc;
+    if ((rc = block_mixer_fwd(k[2], B, flags, seed, s, sg)) || (rc = block_ffn_fwd(k[2], nullptr, B, flags, s, sg))) return rc;
     // up + fusion
     UpFuseArgs ua;
     ua.xb = nb.blk[2].xout; ua.skip = nb.blk[1].xout; ua.y = nb.blk[3].xin; ua.g = nb.blk[3].g;
     ua.t_save = (flags & LG_FLAG_SAVE) ? nb.t_up : nullptr;
-    ua.upw = P + pl->lgt(stage, L_UPW); ua.upb = P + pl->lgt(stage, L_UPB);
-    ua.fw = P + pl->lgt(stage, L_FUSEW); ua.fb = P + pl->lgt(stage, L_FUSEB);
-    ua.n1g = P + pl->blk(stage, 3, B_LN1G); ua.n1b = P + pl->blk(stage, 3, B_LN1B);
+    ua.upw = L.p(L_UPW); ua.upb = L.p(L_UPB); ua.fw = L.p(L_FUSEW); ua.fb = L.p(L_FUSEB);
+    ua.n1g = k[3].p(B_LN1G); ua.n1b = k[3].p(B_LN1B);
     ua.B = B; ua.H = c.H; ua.W = c.W; ua.sg = sg;
     if ((rc = launch_upfuse(E, ua, s))) return rc;
     // decoder LGB (2 blocks)
-    if ((rc = block_mixer_fwd(pl, P, stage, 3, nb.blk[3], posT + 3 * 8192, B, flags, seed, s, nb.fft_scratch, nb.attn_scales, sg))) return rc;
-    if ((rc = block_ffn_fwd(pl, P, stage, 3, nb.blk[3], nb.blk[4].g, 4, B, flags, s, nb.wsplit, nb.ffn_scales, sg))) return rc;
-    if ((rc = block_mixer_fwd(pl, P, stage, 4, nb.blk[4], posT + 4 * 8192, B, flags, seed, s, nb.fft_scratch, nb.attn_scales, sg))) return rc;
-    if ((rc = block_ffn_fwd(pl, P, stage, 4, nb.blk[4], nullptr, 0, B, flags, s, nb.wsplit, nb.ffn_scales, sg))) return rc;
+    if ((rc = block_mixer_fwd(k[3], B, flags, seed, s, sg)) || (rc = block_ffn_fwd(k[3], &k[4], B, flags, s, sg))) return rc;
+    if ((rc = block_mixer_fwd(k[4], B, flags, seed, s, sg)) || (rc = block_ffn_fwd(k[4], nullptr, B, flags, s, sg))) return rc;
     // tail
     TailArgs ta;
     ta.x = nb.blk[4].xout; ta.z = z; ta.out = out;
-    ta.w = P + pl->lgt(stage, L_TAILW); ta.b = P + pl->lgt(stage, L_TAILB);
+    ta.w = L.p(L_TAILW); ta.b = L.p(L_TAILB);
     ta.HW = c.H * c.W; ta.total = (long)B * c.H * c.W; ta.sg = sg;
     return launch_tail(c.C, ta, s);
 }
@@ -414,9 +386,22 @@ static int lgt_fwd(const lg_plan* pl, const float* P, int stage, const float* z,
 static float* dead_out(const lg_plan* pl, const NetBufs& nb, int i, int B) {
     return nb.deadout + (pl->stage_batch ? (size_t)i * B * pl->cfg.C * pl->cfg.H * pl->cfg.W : 0);
 }
-// the K-1 dead-stage LGT forwards as one pass (lgt_fwd with nst = K-1): non-saving, Z[1 ..] in, deadout[0 ..] out
-static int dead_pass(const lg_plan* pl, const float* P, NetBufs& nb, int B, int flags, uint64_t seed, hipStream_t s) {
-    return lgt_fwd(pl, P, 0, nb.Z[1], nb.deadout, nb, B, flags & ~LG_FLAG_SAVE, seed, s, true, pl->cfg.K - 1, (long)(nb.Z[2] - nb.Z[1]));
+// do the K-1 dead-stage LGT forwards of this plan / call run as one pass?
+static bool dead_as_one_pass(const lg_plan* pl, int flags) { return pl->stage_batch && !(flags & LG_FLAG_STAGEWISE); }
+// the K-1 dead-stage LGT forwards behind the data steps: non-saving, Z[1 ..] in, deadout[0 ..] out -- one pass (lgt_fwd with nst = K-1) or one by one
+static int dead_stages(const lg_plan* pl, const float* P, const NetBufs& nb, int B, int flags, uint64_t seed, hipStream_t s) {
+    flags &= ~LG_FLAG_SAVE;
+    if (dead_as_one_pass(pl, flags)) return lgt_fwd(pl, P, 0, nb.Z[1], nb.deadout, nb, B, flags, seed, s, pl->cfg.K - 1, (long)(nb.Z[2] - nb.Z[1]));
+    for (int i = 0; i + 1 < pl->cfg.K; ++i)
+        if (int rc = lgt_fwd(pl, P, i, nb.Z[i + 1], dead_out(pl, nb, i, B), nb, B, flags, seed, s)) return rc;
+    return 0;
+}
+
+// the workspace of entry `who` carved into nb, or -3 if the caller's is too small for (plan, B, train)
+static int carve_checked(const char* who, const lg_plan* plan, int B, int train, void* workspace, size_t workspace_bytes, NetBufs& nb) {
+    if (workspace_bytes < lg_workspace_bytes(plan, B, train)) { lg_set_error("%s: workspace too small", who); return -3; }
+    carve(plan, B, train, workspace, nb);
+    return 0;
 }
 
 extern "C" int lgteun_forward(const lg_plan* plan, const float* params, const float* ms, const float* pan, float* out,
@@ -424,7 +409,7 @@ extern "C" int lgteun_forward(const lg_plan* plan, const float* params, const fl
     if (!plan || !params || !ms || !pan || !out || !workspace || B <= 0) { lg_set_error("forward: null/invalid argument"); return -1; }
     const bool chained = (flags & LG_FLAG_CHAINED) != 0;
     const int train = (flags & LG_FLAG_SAVE) ? (chained ? 2 : 1) : 0;
-    if (workspace_bytes < lg_workspace_bytes(plan, B, train)) {
+    if (workspace_bytes < lg_workspace_bytes(plan, B, train)) {   // (the one entry that reports both sizes)
         lg_set_error("forward: workspace too small (%zu < %zu)", workspace_bytes, lg_workspace_bytes(plan, B, train));
         return -3;
     }
@@ -433,7 +418,7 @@ extern "C" int lgteun_forward(const lg_plan* plan, const float* params, const fl
     NetBufs nb;
     carve(plan, B, train, workspace, nb);
     int rc;
-    // pos_emb^T of every stage whose LGT runs in this call
+    // the rows of every stage whose LGT runs in this call
     const bool all_stages = chained || ((flags & LG_FLAG_FAITHFUL) && !(flags & LG_FLAG_DEFER_DEAD));
     if ((rc = prep_stages(plan, params, all_stages ? 0 : c.K - 1, c.K, nb, s))) return rc;
     // Z0 = bicubic x4 (unlg_former.py:53)
@@ -443,7 +428,7 @@ extern "C" int lgteun_forward(const lg_plan* plan, const float* params, const fl
         for (int i = 0; i < c.K; ++i) {
             if ((rc = data_step_fwd(plan, params, i, nb.X[i], ms, pan, nb.Z[i + 1], nb.t1[i], nb.r[i], nb.s1[i], nb.pr, B, s))) return rc;
             NetBufs sv = (train == 2) ? stage_view(nb, i) : nb;
-            if ((rc = lgt_fwd(plan, params, i, nb.Z[i + 1], i == c.K - 1 ? out : nb.X[i + 1], sv, B, flags, seed, s, true))) return rc;
+            if ((rc = lgt_fwd(plan, params, i, nb.Z[i + 1], i == c.K - 1 ? out : nb.X[i + 1], sv, B, flags, seed, s))) return rc;
         }
         return 0;
     }
@@ -451,48 +436,36 @@ extern "C" int lgteun_forward(const lg_plan* plan, const float* params, const fl
     // the data steps alone produce, so with two or more of them (and a route whose kernels can: lg_plan_stage_batch) the K data steps run first and the
     // dead stages follow as ONE pass over (K-1) B samples; LG_FLAG_STAGEWISE keeps them one by one, each behind its data step.
     const bool dead = (flags & LG_FLAG_FAITHFUL) && !(flags & LG_FLAG_DEFER_DEAD) && c.K > 1;
-    const bool dead_batched = dead && plan->stage_batch && !(flags & LG_FLAG_STAGEWISE);
+    const bool one_pass = dead && dead_as_one_pass(plan, flags);
     for (int i = 0; i < c.K; ++i) {
         if ((rc = data_step_fwd(plan, params, i, nb.Z[i], ms, pan, nb.Z[i + 1], nb.t1[i], nb.r[i], nb.s1[i], nb.pr, B, s))) return rc;
-        if (i < c.K - 1 && dead && !dead_batched &&
-            (rc = lgt_fwd(plan, params, i, nb.Z[i + 1], dead_out(plan, nb, i, B), nb, B, flags & ~LG_FLAG_SAVE, seed, s, true))) return rc;
+        if (i < c.K - 1 && dead && !one_pass &&
+            (rc = lgt_fwd(plan, params, i, nb.Z[i + 1], dead_out(plan, nb, i, B), nb, B, flags & ~LG_FLAG_SAVE, seed, s))) return rc;
     }
-    if (dead_batched && (rc = dead_pass(plan, params, nb, B, flags, seed, s))) return rc;
-    return lgt_fwd(plan, params, c.K - 1, nb.Z[c.K], out, nb, B, flags, seed, s, true);
+    if (one_pass && (rc = dead_stages(plan, params, nb, B, flags, seed, s))) return rc;
+    return lgt_fwd(plan, params, c.K - 1, nb.Z[c.K], out, nb, B, flags, seed, s);
 }
 
 extern "C" int lgteun_dead_forward(const lg_plan* plan, const float* params, void* workspace, size_t workspace_bytes, int32_t B,
                                    int32_t flags, uint64_t seed, void* stream) {
     if (!plan || !params || !workspace || B <= 0) { lg_set_error("dead_forward: null/invalid argument"); return -1; }
     if ((flags & LG_FLAG_CHAINED) || !(flags & LG_FLAG_FAITHFUL)) { lg_set_error("dead_forward: only the faithful unfolding has dead stages"); return -2; }
-    const int train = (flags & LG_FLAG_SAVE) ? 1 : 0;
-    if (workspace_bytes < lg_workspace_bytes(plan, B, train)) { lg_set_error("dead_forward: workspace too small"); return -3; }
     NetBufs nb;
-    carve(plan, B, train, workspace, nb);
-    {
-        const int rc = prep_stages(plan, params, 0, plan->cfg.K - 1, nb, (hipStream_t)stream);
-        if (rc) return rc;
-    }
-    if (plan->stage_batch && !(flags & LG_FLAG_STAGEWISE)) return dead_pass(plan, params, nb, B, flags, seed, (hipStream_t)stream);
-    for (int i = 0; i + 1 < plan->cfg.K; ++i) {
-        const int rc = lgt_fwd(plan, params, i, nb.Z[i + 1], dead_out(plan, nb, i, B), nb, B, flags & ~LG_FLAG_SAVE, seed, (hipStream_t)stream, true);
-        if (rc) return rc;
-    }
-    return 0;
+    if (int rc = carve_checked("dead_forward", plan, B, (flags & LG_FLAG_SAVE) ? 1 : 0, workspace, workspace_bytes, nb)) return rc;
+    if (int rc = prep_stages(plan, params, 0, plan->cfg.K - 1, nb, (hipStream_t)stream)) return rc;
+    return dead_stages(plan, params, nb, B, flags, seed, (hipStream_t)stream);
 }
 
 extern "C" int lgteun_backward(const lg_plan* plan, const float* params, float* grads, const float* ms, const float* pan,
                                const float* dout, void* workspace, size_t workspace_bytes, int32_t B, int32_t flags, uint64_t seed,
                                void* stream) {
     if (!plan || !params || !grads || !ms || !pan || !dout || !workspace || B <= 0) { lg_set_error("backward: null/invalid argument"); return -1; }
-    const int train = (flags & LG_FLAG_CHAINED) ? 2 : 1;
     if ((flags & LG_FLAG_CHAINED) && (flags & (LG_FLAG_BWD_LGT | LG_FLAG_BWD_DATA))) {
         lg_set_error("backward: LG_FLAG_BWD_LGT / LG_FLAG_BWD_DATA do not apply to LG_FLAG_CHAINED");
         return -2;
     }
-    if (workspace_bytes < lg_workspace_bytes(plan, B, train)) { lg_set_error("backward: workspace too small"); return -3; }
     NetBufs nb;
-    carve(plan, B, train, workspace, nb);
+    if (int rc = carve_checked("backward", plan, B, (flags & LG_FLAG_CHAINED) ? 2 : 1, workspace, workspace_bytes, nb)) return rc;
     return net_backward(plan, params, grads, ms, pan, dout, nb, (char*)workspace + nb.bytes, B, flags, seed, (hipStream_t)stream);
 }
 
@@ -516,10 +489,9 @@ extern "C" int lg_op_data_step(const lg_plan* plan, const float* params, int32_t
 extern "C" int lg_op_lgt(const lg_plan* plan, const float* params, int32_t stage, const float* z, float* out, void* workspace,
                          size_t workspace_bytes, int32_t B, int32_t flags, uint64_t seed, void* stream) {
     if (!plan || !params || !z || !out || !workspace || stage < 0 || stage >= plan->cfg.K) { lg_set_error("op_lgt: invalid argument"); return -1; }
-    const int train = (flags & LG_FLAG_SAVE) ? 1 : 0;
-    if (workspace_bytes < lg_workspace_bytes(plan, B, train)) { lg_set_error("op_lgt: workspace too small"); return -3; }
     NetBufs nb;
-    carve(plan, B, train, workspace, nb);
+    if (int rc = carve_checked("op_lgt", plan, B, (flags & LG_FLAG_SAVE) ? 1 : 0, workspace, workspace_bytes, nb)) return rc;
+    if (int rc = prep_stages(plan, params, stage, stage + 1, nb, (hipStream_t)stream)) return rc;
     return lgt_fwd(plan, params, stage, z, out, nb, B, flags, seed, (hipStream_t)stream);
 }
 
@@ -528,12 +500,11 @@ extern "C" int lg_op_lgt_stages(const lg_plan* plan, const float* params, int32_
     if (!plan || !params || !z || !out || !workspace || B <= 0 || stage0 < 0 || n < 1 || stage0 + n > plan->cfg.K || grid_cap < 0) { lg_set_error("op_lgt_stages: invalid argument"); return -1; }
     if (flags & ~LG_FLAG_DROPOUT) { lg_set_error("op_lgt_stages: only LG_FLAG_DROPOUT applies (nothing is saved)"); return -2; }
     if (n > 1 && (!plan->stage_batch || n > plan->cfg.K - 1)) { lg_set_error("op_lgt_stages: this plan runs one stage per pass (lg_plan_stage_batch), or n > K-1"); return -2; }
-    if (workspace_bytes < lg_workspace_bytes(plan, B, 0)) { lg_set_error("op_lgt_stages: workspace too small"); return -3; }
     NetBufs nb;
-    carve(plan, B, 0, workspace, nb);
+    if (int rc = carve_checked("op_lgt_stages", plan, B, 0, workspace, workspace_bytes, nb)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (int rc = prep_stages(plan, params, stage0, stage0 + n, nb, s)) return rc;
-    return lgt_fwd(plan, params, stage0, z, out, nb, B, flags, seed, s, true, n, (long)B * plan->cfg.C * plan->cfg.H * plan->cfg.W, grid_cap);
+    return lgt_fwd(plan, params, stage0, z, out, nb, B, flags, seed, s, n, (long)B * plan->cfg.C * plan->cfg.H * plan->cfg.W, grid_cap);
 }
 
 // debug exports (tests/test_stage_runs_cpu.py; host only, no device, no launch): the partition of a persistent multi-stage launch, from the functions
@@ -583,40 +554,32 @@ extern "C" int lg_op_block(const lg_plan* plan, const float* params, int32_t sta
         lg_set_error("op_block: invalid argument");
         return -1;
     }
-    if (workspace_bytes < lg_workspace_bytes(plan, B, 0)) { lg_set_error("op_block: workspace too small"); return -3; }
     hipStream_t s = (hipStream_t)stream;
     NetBufs nb;
-    carve(plan, B, 0, workspace, nb);
-    BlockBufs bb = nb.blk[blk];
     int rc;
-    const size_t npix = (size_t)B * bb.h * bb.w;
+    if ((rc = carve_checked("op_block", plan, B, 0, workspace, workspace_bytes, nb))) return rc;
+    Blk k = nb.block(plan, params, nullptr, stage, blk);
+    BlockBufs& bb = k.b;
     if (which == 0 || which == 1) {
         // LN1 + planar split of the global half (normally emitted by the producing kernel's epilogue)
-        if ((rc = launch_ln_split(bb.e, x, params + plan->blk(stage, blk, B_LN1G), params + plan->blk(stage, blk, B_LN1B), bb.g, B,
-                                  bb.h * bb.w, s)))
-            return rc;
+        if ((rc = launch_ln_split(bb.e, x, k.p(B_LN1G), k.p(B_LN1B), bb.g, B, bb.h * bb.w, s))) return rc;
     }
     if (which == 0) {
         FftArgs f;
         f.g = bb.g; f.o = y; f.amp = nullptr; f.pha = nullptr; f.sgn = nullptr; f.scratch = nb.fft_scratch;
-        f.ampw = params + plan->blk(stage, blk, B_AMPW); f.ampb = params + plan->blk(stage, blk, B_AMPB);
-        f.phaw = params + plan->blk(stage, blk, B_PHAW); f.phab = params + plan->blk(stage, blk, B_PHAB);
+        f.ampw = k.p(B_AMPW); f.ampb = k.p(B_AMPB); f.phaw = k.p(B_PHAW); f.phab = k.p(B_PHAB);
         f.ch = bb.e / 2; f.planes = B * f.ch; f.n = bb.h; f.h = bb.h; f.w = bb.w; f.full = plan->route.fft_full;
         return launch_fftmix(f, s);
     }
+    if ((rc = prep_stages(plan, params, stage, stage + 1, nb, s))) return rc;   // the block's rows: pos_emb table and static operand scales (mixer), operand scales and weight fragments (FFN)
     if (which == 1) {
-        float* posT = nb.posT;
-        if ((rc = prep_stages(plan, params, stage, stage + 1, nb, s))) return rc;   // the mixer's static operand scales (and the stage's tables; this block's table goes to slot 0 below)
-        if ((rc = launch_pos_transpose(params + plan->blk(stage, blk, B_POS), posT, s))) return rc;
         bb.xin = const_cast<float*>(x);
         bb.xmid = y;
-        return block_mixer_fwd(plan, params, stage, blk, bb, posT, B, 0, 0, s, nb.fft_scratch, nb.attn_scales);
+        return block_mixer_fwd(k, B, 0, 0, s);
     }
     bb.xmid = const_cast<float*>(x);
     bb.xout = y;
-    (void)npix;
-    if ((rc = prep_stages(plan, params, stage, stage + 1, nb, s))) return rc;   // the FFN's operand scales
-    return block_ffn_fwd(plan, params, stage, blk, bb, nullptr, 0, B, 0, s, nb.wsplit, nb.ffn_scales);
+    return block_ffn_fwd(k, nullptr, B, 0, s);
 }
 
 extern "C" int lg_op_block_bwd(const lg_plan* plan, const float* params, float* grads, int32_t stage, int32_t blk, int32_t which,
@@ -627,27 +590,24 @@ extern "C" int lg_op_block_bwd(const lg_plan* plan, const float* params, float* 
         lg_set_error("op_block_bwd: invalid argument");
         return -1;
     }
-    if (workspace_bytes < lg_workspace_bytes(plan, B, 1)) { lg_set_error("op_block_bwd: workspace too small"); return -3; }
     hipStream_t s = (hipStream_t)stream;
     NetBufs nb;
-    carve(plan, B, 1, workspace, nb);
-    BlockBufs& bb = nb.blk[blk];
     int rc;
+    if ((rc = carve_checked("op_block_bwd", plan, B, 1, workspace, workspace_bytes, nb))) return rc;
+    Blk k = nb.block(plan, params, grads, stage, blk);
+    BlockBufs& bb = k.b;
     // forward of the half-block with everything saved
     if (which == 0 || which == 1) {
-        if ((rc = launch_ln_split(bb.e, x, params + plan->blk(stage, blk, B_LN1G), params + plan->blk(stage, blk, B_LN1B), bb.g, B,
-                                  bb.h * bb.w, s)))
-            return rc;
-        if ((rc = prep_stages(plan, params, stage, stage + 1, nb, s))) return rc;   // the mixer's static operand scales
-        if ((rc = launch_pos_transpose(params + plan->blk(stage, blk, B_POS), nb.posT, s))) return rc;
+        if ((rc = launch_ln_split(bb.e, x, k.p(B_LN1G), k.p(B_LN1B), bb.g, B, bb.h * bb.w, s))) return rc;
+        if ((rc = prep_stages(plan, params, stage, stage + 1, nb, s))) return rc;   // the mixer's pos_emb table and static operand scales
         bb.xin = const_cast<float*>(x);
-        if ((rc = block_mixer_fwd(plan, params, stage, blk, bb, nb.posT, B, LG_FLAG_SAVE, 0, s, nb.fft_scratch, nb.attn_scales))) return rc;
+        if ((rc = block_mixer_fwd(k, B, LG_FLAG_SAVE, 0, s))) return rc;
     } else {
         bb.xmid = const_cast<float*>(x);
         if ((rc = prep_stages(plan, params, stage, stage + 1, nb, s))) return rc;
-        if ((rc = block_ffn_fwd(plan, params, stage, blk, bb, nullptr, 0, B, LG_FLAG_SAVE, s, nb.wsplit, nb.ffn_scales))) return rc;
+        if ((rc = block_ffn_fwd(k, nullptr, B, LG_FLAG_SAVE, s))) return rc;
     }
-    return op_block_bwd(plan, params, grads, stage, blk, which, dy, dx, nb, (char*)workspace + nb.bytes, B, s);
+    return op_block_bwd(k, which, dy, dx, (char*)workspace + nb.bytes, B, s);
 }
 
 extern "C" int lg_op_data_step_bwd(const lg_plan* plan, const float* params, float* grads, int32_t stage, const float* z_in,
@@ -657,11 +617,10 @@ extern "C" int lg_op_data_step_bwd(const lg_plan* plan, const float* params, flo
         lg_set_error("op_data_step_bwd: invalid argument");
         return -1;
     }
-    if (workspace_bytes < lg_workspace_bytes(plan, B, 1)) { lg_set_error("op_data_step_bwd: workspace too small"); return -3; }
     hipStream_t s = (hipStream_t)stream;
     NetBufs nb;
-    carve(plan, B, 1, workspace, nb);
     int rc;
+    if ((rc = carve_checked("op_data_step_bwd", plan, B, 1, workspace, workspace_bytes, nb))) return rc;
     // forward of the step: fills the intermediates its backward reads (t1, r, s1)
     if ((rc = data_step_fwd(plan, params, stage, z_in, ms, pan, nb.Z[stage + 1], nb.t1[stage], nb.r[stage], nb.s1[stage], nb.pr, B, s))) return rc;
     return op_data_step_bwd(plan, params, grads, stage, nb, (char*)workspace + nb.bytes, z_in, pan, dz_out, dz_in, B, s);
@@ -674,11 +633,11 @@ extern "C" int lg_op_lgt_bwd(const lg_plan* plan, const float* params, float* gr
         return -1;
     }
     if (flags & ~LG_FLAG_DROPOUT) { lg_set_error("op_lgt_bwd: only LG_FLAG_DROPOUT applies"); return -2; }
-    if (workspace_bytes < lg_workspace_bytes(plan, B, 1)) { lg_set_error("op_lgt_bwd: workspace too small"); return -3; }
     hipStream_t s = (hipStream_t)stream;
     NetBufs nb;
-    carve(plan, B, 1, workspace, nb);
     int rc;
+    if ((rc = carve_checked("op_lgt_bwd", plan, B, 1, workspace, workspace_bytes, nb))) return rc;
+    if ((rc = prep_stages(plan, params, stage, stage + 1, nb, s))) return rc;
     if ((rc = lgt_fwd(plan, params, stage, z, nb.deadout, nb, B, flags | LG_FLAG_SAVE, seed, s))) return rc;
     return op_lgt_bwd(plan, params, grads, stage, nb, (char*)workspace + nb.bytes, z, dout, dz, B, flags, seed, s);
 }

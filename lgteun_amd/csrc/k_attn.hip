@@ -251,7 +251,7 @@ __global__ __launch_bounds__(256) void k_attn(AttnArgs a, int nwin, int nquads) 
 }
 
 #include "workspace.h"
-#define LG_MAX_POS_JOBS (5 * LG_MAX_K)
+#define LG_MAX_POS_JOBS (LG_NBLK * LG_MAX_K)
 struct PosTArgs { const float* src[LG_MAX_POS_JOBS]; float* dst[LG_MAX_POS_JOBS]; };
 __global__ void k_pos_transpose(PosTArgs a) {
     // pos [2][64][64] (h,i,j) -> posT [2][64][64] (h,j,i); blockIdx.y = block of the stage
@@ -271,7 +271,6 @@ int launch_pos_transpose_n(int n, const float* const* pos, float* const* posT, h
     LG_CHECK_LAUNCH();
     return 0;
 }
-int launch_pos_transpose(const float* pos, float* posT, hipStream_t s) { return launch_pos_transpose_n(1, &pos, &posT, s); }
 
 template <int HC>
 static int launch_attn_t(const AttnArgs& a, hipStream_t s) {

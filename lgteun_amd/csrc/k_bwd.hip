@@ -10,19 +10,19 @@ struct BwdBufs {
     float *dzA, *dzB, *gu3, *gs1, *gu1, *gr, *gd3, *gt1, *gd1;
     float *dx[3];
     float *dh2, *dh1, *y2, *do2, *dg, *dym, *cat, *y1, *dqkv;
-    float *w3t[5], *w2t[5], *w1t[5], *wsp, *dt, *dskip, *v, *du, *fft_scratch;   // transposed FFN weights, one set per block of the LGT
+    float *w3t[LG_NBLK], *w2t[LG_NBLK], *w1t[LG_NBLK], *wsp, *dt, *dskip, *v, *du;   // transposed FFN weights, one set per block of the LGT
     float* slab_arena;    // scratch of the deferred parameter-gradient reductions (ReduceQueue, bwd_kernels.h)
     float* attn_stats;    // [P0][2][4]: row statistics between the two launches of k_attn_bwd_core_m (LG_ATTN_BWD_CORE=m)
-    float* ffn_scales;    // NetBufs::ffn_scales of the forward this backward belongs to ([stage][5][8]); null: no f16-pair products in the backward
     size_t slab_cap;      // floats
     ReduceQueue rq;
     size_t bytes;
 };
 
 // the local mixer's pos_emb partial rows of one block: k_attn_bwd_f's rows (every parameter gradient of the half-block) or the three-kernel form's
+static const size_t R3_DPOS_SLAB = 512 * POS_TABLE;   // (AttnBwdArgs::dpos_slab: room for the tables of 512 workgroups)
 static size_t dpos_slab_floats() {
-    const size_t f = (size_t)ATTN_BWD_F_WGS * ATTN_BWD_F_ROW, r3 = (size_t)512 * 2 * 64 * 64;
-    return f > r3 ? f : r3;
+    const size_t f = (size_t)ATTN_BWD_F_WGS * ATTN_BWD_F_ROW;
+    return f > R3_DPOS_SLAB ? f : R3_DPOS_SLAB;
 }
 static void carve_bwd(const lg_plan* plan, int B, void* base, BwdBufs& bb) {
     const lg_config& c = plan->cfg;
@@ -37,7 +37,7 @@ static void carve_bwd(const lg_plan* plan, int B, void* base, BwdBufs& bb) {
     bb.dym = cv.take(P0 * E); bb.cat = cv.take(P0 * E); bb.y1 = cv.take(P0 * 16 > P0 * E / 2 ? P0 * 16 : P0 * E / 2);
     bb.dqkv = cv.take(P0 * 2 * E);
     bb.attn_stats = cv.take(P0 * 8);
-    for (int j = 0; j < 5; ++j) { bb.w3t[j] = cv.take(8 * E * 2 * E); bb.w2t[j] = cv.take(8 * E * 8 * E); bb.w1t[j] = cv.take(8 * E * 2 * E); }
+    for (int j = 0; j < LG_NBLK; ++j) { bb.w3t[j] = cv.take(8 * E * 2 * E); bb.w2t[j] = cv.take(8 * E * 8 * E); bb.w1t[j] = cv.take(8 * E * 2 * E); }
     bb.wsp = cv.take(ffn_wsplit_bytes(32) / sizeof(float));   // pre-split W2^T / W1^T fragments of k_ffn1_bwd_x32 (e = 32 blocks)
     size_t sl = wgrad_slab_floats((int)(8 * E), (int)(8 * E), (long)P0);
     size_t sl2 = wgrad_slab_floats(64, 64, (long)P0);
@@ -57,9 +57,8 @@ static void carve_bwd(const lg_plan* plan, int B, void* base, BwdBufs& bb) {
     if (ffn_dw_bwd_x_slab_floats(16) > sl) sl = ffn_dw_bwd_x_slab_floats(16);
     if (ffn_dw_bwd_x_slab_floats(32) > sl) sl = ffn_dw_bwd_x_slab_floats(32);
     if (ffn_dw_bwd_h_slab_floats() > sl) sl = ffn_dw_bwd_h_slab_floats();
-    bb.slab_cap = 5 * (4 * sl + dpos_slab_floats());
+    bb.slab_cap = LG_NBLK * (4 * sl + dpos_slab_floats());
     bb.slab_arena = cv.take(bb.slab_cap);
-    bb.ffn_scales = nullptr;
     bb.dt = cv.take(P0 * E); bb.dskip = cv.take(P0 * E); bb.v = cv.take(P1 * E); bb.du = cv.take(P1 * E);
     bb.bytes = cv.off;
 }
@@ -91,16 +90,17 @@ static int wgrad(const void* Y, int ldy, const void* X, int ldx, float* dW, int 
     return launch_wgrad(a, slab, s);
 }
 
-// W3^T / W2^T / W1^T of blocks [j0, j1) of stage st into bb.w?t[j], all in ONE launch (backward GEMMs read transposed weights)
-static int ffn_transposes(const lg_plan* pl, const float* P, int st, int j0, int j1, const NetBufs& nb, BwdBufs& bb, hipStream_t s) {
-    const float* tsrc[15];
-    float* tdst[15];
-    int trows[15], tcols[15], n = 0;
-    for (int j = j0; j < j1; ++j) {
-        const int e = nb.blk[j].e, n1 = 4 * e;
-        tsrc[n] = P + pl->blk(st, j, B_W3); tdst[n] = bb.w3t[j]; trows[n] = e; tcols[n] = n1; ++n;
-        tsrc[n] = P + pl->blk(st, j, B_W2); tdst[n] = bb.w2t[j]; trows[n] = n1; tcols[n] = n1; ++n;
-        tsrc[n] = P + pl->blk(st, j, B_W1); tdst[n] = bb.w1t[j]; trows[n] = n1; tcols[n] = e; ++n;
+// W3^T / W2^T / W1^T of the nk blocks k[] into bb.w?t[j], all in ONE launch (backward GEMMs read transposed weights)
+static int ffn_transposes(const Blk* blocks, int nk, BwdBufs& bb, hipStream_t s) {
+    const float* tsrc[3 * LG_NBLK];
+    float* tdst[3 * LG_NBLK];
+    int trows[3 * LG_NBLK], tcols[3 * LG_NBLK], n = 0;
+    for (int i = 0; i < nk; ++i) {
+        const Blk& k = blocks[i];
+        const int j = k.j, e = k.b.e, n1 = 4 * e;
+        tsrc[n] = k.p(B_W3); tdst[n] = bb.w3t[j]; trows[n] = e; tcols[n] = n1; ++n;
+        tsrc[n] = k.p(B_W2); tdst[n] = bb.w2t[j]; trows[n] = n1; tcols[n] = n1; ++n;
+        tsrc[n] = k.p(B_W1); tdst[n] = bb.w1t[j]; trows[n] = n1; tcols[n] = e; ++n;
     }
     return launch_transpose3(tsrc, tdst, trows, tcols, n, s);
 }
@@ -109,32 +109,32 @@ static int ffn_transposes(const lg_plan* pl, const float* P, int st, int j0, int
 // The spatial kernel of the block's route (dh2; the depthwise gradients; dW3 / db3 unless it is the tile kernel), then the pixelwise kernel
 // (dx, the LayerNorm gradients; dW1 / dW2 when it is k_ffn1_bwd_xs), then the weight-gradient launches the route lists; dh2 is the only tensor
 // between the halves
-static int ffn_half_bwd(const lg_plan* pl, const float* P, float* G, int st, int j, const BlockBufs& fb, BwdBufs& bb, const float* dy,
-                        float* tmp, int B, hipStream_t s) {
-    const FfnRoute& fr = pl->ffn(fb.e);
-    const int e = fb.e, n1 = 4 * e;
+static int ffn_half_bwd(const Blk& k, BwdBufs& bb, const float* dy, float* tmp, int B, hipStream_t s) {
+    const BlockBufs& fb = k.b;
+    const FfnRoute& fr = k.pl->ffn(fb.e);
+    const int j = k.j, e = fb.e, n1 = 4 * e;
     const int hbf = fr.hbf ? 1 : 0;   // bf16 storage of the hidden / saved FFN tensors
     const int pre = fr.pre ? 1 : 0;   // fb.a1 / fb.a3 hold h1 / h3 (fb.g1 / fb.g3 unused): GELU re-evaluated where needed
     const long Pn = (long)B * fb.h * fb.w;
     // f16-pair products in k_ffn1_bwd_xs (round 5): the forward's operand scales of this block + max |dh2|, which the spatial half leaves in word 6
-    float* fsc = (bb.ffn_scales && fr.bwd_scales) ? bb.ffn_scales + ((size_t)st * 5 + j) * 8 : nullptr;
+    float* fsc = fr.bwd_scales ? k.ffn_scales : nullptr;
     if (fr.dw == FFN_DWBWD_TILE) {
         FfnDwBwdArgs fd;
-        fd.dy = dy; fd.g3 = pre ? fb.a3 : fb.g3; fd.h2 = fb.h2; fd.dh2 = bb.dh2; fd.w3t = bb.w3t[j]; fd.dww = P + pl->blk(st, j, B_DWW);
+        fd.dy = dy; fd.g3 = pre ? fb.a3 : fb.g3; fd.h2 = fb.h2; fd.dh2 = bb.dh2; fd.w3t = bb.w3t[j]; fd.dww = k.p(B_DWW);
         fd.slab_w = bb.rq.take(ffn_dw_bwd_slab_floats(e, B, fb.h, fb.w));
         if (!fd.slab_w) return -3;
         fd.slab_b = fd.slab_w + ffn_dw_bwd_slab_floats(e, B, fb.h, fb.w) / 10 * 9;
-        fd.d_dww = G + pl->blk(st, j, B_DWW); fd.d_dwb = G + pl->blk(st, j, B_DWB);
+        fd.d_dww = k.g(B_DWW); fd.d_dwb = k.g(B_DWB);
         fd.B = B; fd.h = fb.h; fd.w = fb.w; fd.hbf = hbf; fd.pre = pre;
         RC(launch_ffn_dw_bwd(e, fd, s));
     } else {
         // the strip walk: dh3 in an LDS ring on the saved pre-activation h3, or (FFN_DWBWD_H, round 6) on h3 re-computed from h2 and the depthwise bias
         const bool h3re = fr.dw == FFN_DWBWD_H;
         FfnDwBwdXArgs fk;
-        fk.dy = dy; fk.h3 = h3re ? nullptr : fb.a3; fk.h2 = fb.h2; fk.dh2 = bb.dh2; fk.w3t = bb.w3t[j]; fk.dww = P + pl->blk(st, j, B_DWW); fk.dwb = P + pl->blk(st, j, B_DWB);
+        fk.dy = dy; fk.h3 = h3re ? nullptr : fb.a3; fk.h2 = fb.h2; fk.dh2 = bb.dh2; fk.w3t = bb.w3t[j]; fk.dww = k.p(B_DWW); fk.dwb = k.p(B_DWB);
         fk.slab = bb.rq.take(h3re ? ffn_dw_bwd_h_slab_floats() : ffn_dw_bwd_x_slab_floats(e));
         if (!fk.slab) return -3;
-        fk.d_dww = G + pl->blk(st, j, B_DWW); fk.d_dwb = G + pl->blk(st, j, B_DWB); fk.d_w3 = G + pl->blk(st, j, B_W3); fk.d_b3 = G + pl->blk(st, j, B_B3);
+        fk.d_dww = k.g(B_DWW); fk.d_dwb = k.g(B_DWB); fk.d_w3 = k.g(B_W3); fk.d_b3 = k.g(B_B3);
         fk.B = B; fk.h = fb.h; fk.w = fb.w; fk.hbf = hbf;
         fk.dh2_max = fsc ? fsc + 6 : nullptr;
         RC(h3re ? launch_ffn_dw_bwd_h(fk, s) : launch_ffn_dw_bwd_xs(e, fk, s));
@@ -144,144 +144,130 @@ static int ffn_half_bwd(const lg_plan* pl, const float* P, float* G, int st, int
         Ffn1BwdXArgs fx;
         fx.scales = fsc;
         fx.dh2 = bb.dh2; fx.x = fb.xmid; fx.dy = dy; fx.dx = tmp;
-        fx.w1 = P + pl->blk(st, j, B_W1); fx.b1 = P + pl->blk(st, j, B_B1); fx.w2t = bb.w2t[j]; fx.w1t = bb.w1t[j];
-        fx.ln2g = P + pl->blk(st, j, B_LN2G); fx.ln2b = P + pl->blk(st, j, B_LN2B);
+        fx.w1 = k.p(B_W1); fx.b1 = k.p(B_B1); fx.w2t = bb.w2t[j]; fx.w1t = bb.w1t[j]; fx.ln2g = k.p(B_LN2G); fx.ln2b = k.p(B_LN2B);
         fx.slab = bb.rq.take(ffn1_bwd_x_slab_floats(e));
         if (!fx.slab) return -3;
-        fx.d_w1 = G + pl->blk(st, j, B_W1); fx.d_b1 = G + pl->blk(st, j, B_B1); fx.d_w2 = G + pl->blk(st, j, B_W2); fx.d_b2 = G + pl->blk(st, j, B_B2);
-        fx.d_ln2g = G + pl->blk(st, j, B_LN2G); fx.d_ln2b = G + pl->blk(st, j, B_LN2B);
+        fx.d_w1 = k.g(B_W1); fx.d_b1 = k.g(B_B1); fx.d_w2 = k.g(B_W2); fx.d_b2 = k.g(B_B2); fx.d_ln2g = k.g(B_LN2G); fx.d_ln2b = k.g(B_LN2B);
         fx.P = Pn; fx.hbf = hbf;
         RC(launch_ffn1_bwd_xs(e, fx, s));
     } else {
         Ffn1BwdArgs f1;
         f1.dh2 = bb.dh2; f1.g1 = pre ? fb.a1 : fb.g1; f1.x = fb.xmid; f1.dy = dy; f1.dh1 = bb.dh1; f1.y2 = bb.y2; f1.dx = tmp;
         f1.w2t = bb.w2t[j]; f1.w1t = bb.w1t[j];
-        f1.ln2g = P + pl->blk(st, j, B_LN2G); f1.ln2b = P + pl->blk(st, j, B_LN2B);
-        f1.d_ln2g = G + pl->blk(st, j, B_LN2G); f1.d_ln2b = G + pl->blk(st, j, B_LN2B); f1.part = bb.rq.take((size_t)PIXEL_PART_WGS * 2 * e);
+        f1.ln2g = k.p(B_LN2G); f1.ln2b = k.p(B_LN2B);
+        f1.d_ln2g = k.g(B_LN2G); f1.d_ln2b = k.g(B_LN2B); f1.part = bb.rq.take((size_t)PIXEL_PART_WGS * 2 * e);
         if (!f1.part) return -3;
         f1.P = Pn; f1.hbf = hbf; f1.pre = pre;
         f1.w1 = nullptr; f1.wsplit = nullptr;
-        if (fr.px == FFN1_BWD_X32) { f1.w1 = P + pl->blk(st, j, B_W1); f1.wsplit = bb.wsp; }
+        if (fr.px == FFN1_BWD_X32) { f1.w1 = k.p(B_W1); f1.wsplit = bb.wsp; }
         f1.w1slab = nullptr; f1.d_w1 = nullptr; f1.d_b1 = nullptr;
         if (!fr.wgrad_w1) {   // dW1 / db1 come out of k_ffn1_bwd itself
             f1.w1slab = bb.rq.take((size_t)FFN1_BWD_WGS * ((size_t)n1 * e + n1));
             if (!f1.w1slab) return -3;
-            f1.d_w1 = G + pl->blk(st, j, B_W1); f1.d_b1 = G + pl->blk(st, j, B_B1);
+            f1.d_w1 = k.g(B_W1); f1.d_b1 = k.g(B_B1);
         }
         f1.w2slab = nullptr; f1.d_w2 = nullptr; f1.d_b2 = nullptr;
         if (!fr.wgrad_w2) {   // dW2 / db2 too
             f1.w2slab = bb.rq.take((size_t)FFN1_BWD_WGS * ((size_t)n1 * n1 + n1));
             if (!f1.w2slab) return -3;
-            f1.d_w2 = G + pl->blk(st, j, B_W2); f1.d_b2 = G + pl->blk(st, j, B_B2);
+            f1.d_w2 = k.g(B_W2); f1.d_b2 = k.g(B_B2);
         }
         RC(launch_ffn1_bwd(e, fr.px, f1, s));
     }
-    if (fr.wgrad_w2) RC(wgrad(bb.dh2, n1, fb.a1, n1, G + pl->blk(st, j, B_W2), n1, G + pl->blk(st, j, B_B2), Pn, n1, n1, n1, n1, hbf, hbf, bb, s, pre));
-    if (fr.wgrad_w1) RC(wgrad(bb.dh1, n1, bb.y2, e, G + pl->blk(st, j, B_W1), e, G + pl->blk(st, j, B_B1), Pn, n1, e, n1, e, hbf, 0, bb, s));
+    if (fr.wgrad_w2) RC(wgrad(bb.dh2, n1, fb.a1, n1, k.g(B_W2), n1, k.g(B_B2), Pn, n1, n1, n1, n1, hbf, hbf, bb, s, pre));
+    if (fr.wgrad_w1) RC(wgrad(bb.dh1, n1, bb.y2, e, k.g(B_W1), e, k.g(B_B1), Pn, n1, e, n1, e, hbf, 0, bb, s));
     // last: dh2's two readers run right behind its producer (Infinity Cache), this one only needs the saved h3 / gelu(h3) and dy
-    if (fr.wgrad_w3) RC(wgrad(dy, e, fb.a3, n1, G + pl->blk(st, j, B_W3), n1, G + pl->blk(st, j, B_B3), Pn, e, n1, e, n1, 0, hbf, bb, s, pre));
+    if (fr.wgrad_w3) RC(wgrad(dy, e, fb.a3, n1, k.g(B_W3), n1, k.g(B_B3), Pn, e, n1, e, n1, 0, hbf, bb, s, pre));
     return 0;
 }
 
-static int fft_bwd_call(const lg_plan* pl, const float* P, float* G, int st, int j, const BlockBufs& fb, const float* do2, float* dg,
-                        int B, hipStream_t s, float* fft_scratch, float* part) {
+static int fft_bwd_call(const Blk& k, const float* do2, float* dg, int B, hipStream_t s, float* part) {
+    const BlockBufs& fb = k.b;
     const int hc = fb.e / 2;
     FftBwdArgs fa;
-    fa.do2 = do2; fa.sgn = fb.sgn; fa.amp = fb.amp; fa.pha = fb.pha; fa.dg = dg; fa.scratch = fft_scratch;
-    fa.ampw = P + pl->blk(st, j, B_AMPW); fa.ampb = P + pl->blk(st, j, B_AMPB);
-    fa.phaw = P + pl->blk(st, j, B_PHAW); fa.phab = P + pl->blk(st, j, B_PHAB);
-    fa.d_ampw = G + pl->blk(st, j, B_AMPW); fa.d_ampb = G + pl->blk(st, j, B_AMPB);
-    fa.d_phaw = G + pl->blk(st, j, B_PHAW); fa.d_phab = G + pl->blk(st, j, B_PHAB);
-    fa.ch = hc; fa.planes = B * hc; fa.n = fb.h; fa.h = fb.h; fa.w = fb.w; fa.part = part; fa.full = pl->route.fft_full;
+    fa.do2 = do2; fa.sgn = fb.sgn; fa.amp = fb.amp; fa.pha = fb.pha; fa.dg = dg; fa.scratch = k.fft_scratch;
+    fa.ampw = k.p(B_AMPW); fa.ampb = k.p(B_AMPB); fa.phaw = k.p(B_PHAW); fa.phab = k.p(B_PHAB);
+    fa.d_ampw = k.g(B_AMPW); fa.d_ampb = k.g(B_AMPB); fa.d_phaw = k.g(B_PHAW); fa.d_phab = k.g(B_PHAB);
+    fa.ch = hc; fa.planes = B * hc; fa.n = fb.h; fa.h = fb.h; fa.w = fb.w; fa.part = part; fa.full = k.pl->route.fft_full;
     return launch_fftmix_bwd(fa, s);
 }
 
 // mixer half-block backward: tmp (grad wrt the mid activation) -> dx_out (grad wrt block input)
-static int mixer_half_bwd(const lg_plan* pl, const float* P, float* G, int st, int j, const BlockBufs& fb, BwdBufs& bb, const float* posT,
-                          const float* tmp, float* dx_out, int B, int flags, uint64_t seed, hipStream_t s) {
+static int mixer_half_bwd(const Blk& k, BwdBufs& bb, const float* tmp, float* dx_out, int B, int flags, uint64_t seed, hipStream_t s) {
+    const BlockBufs& fb = k.b;
     const int e = fb.e, hc = e / 2;
     const long Pn = (long)B * fb.h * fb.w;
     const int drop = (flags & LG_FLAG_DROPOUT) ? 1 : 0;
-    const MixerRoute& mr = pl->mixer(e);
+    const MixerRoute& mr = k.pl->mixer(e);
     if (mr.bwd == ATTN_BWD_F) {
         // round 4: three launches per half-block -- proj^T towards the global mixer (+ dropout keep bits, proj bias gradient), the FFT-mixer
         // backward, and ONE kernel for everything else (flash passes, to_qkv^T, LayerNorm backward, dx, every parameter gradient)
         uint32_t* keep = drop ? reinterpret_cast<uint32_t*>(bb.dym) : nullptr;
         ProjO2BwdKArgs pk;
-        pk.dy = tmp; pk.do2 = bb.do2; pk.keep = keep; pk.projw = P + pl->blk(st, j, B_PROJW);
+        pk.dy = tmp; pk.do2 = bb.do2; pk.keep = keep; pk.projw = k.p(B_PROJW);
         pk.slab = bb.rq.take((size_t)PROJ_O2_K_WGS * e);
         if (!pk.slab) return -3;
-        pk.d_projb = G + pl->blk(st, j, B_PROJB); pk.HW = fb.h * fb.w; pk.total = Pn; pk.seed = mix_seed(seed, st, j);
+        pk.d_projb = k.g(B_PROJB); pk.HW = fb.h * fb.w; pk.total = Pn; pk.seed = mix_seed(seed, k.st, k.j);
         RC(launch_proj_o2_bwd_k(e, pk, s));
         float* fpart = bb.rq.take(fft_bwd_part_floats(B * hc, fb.h, fb.w));
         if (!fpart) return -3;
-        RC(fft_bwd_call(pl, P, G, st, j, fb, bb.do2, bb.dg, B, s, bb.fft_scratch, fpart));
+        RC(fft_bwd_call(k, bb.do2, bb.dg, B, s, fpart));
         AttnBwdFArgs af;
         af.x = fb.xin; af.dy = tmp; af.keep = keep; af.o2 = fb.o2; af.dg = bb.dg; af.dx = dx_out;
-        af.pos = P + pl->blk(st, j, B_POS);
-        af.ln1g = P + pl->blk(st, j, B_LN1G); af.ln1b = P + pl->blk(st, j, B_LN1B);
-        af.qkvw = P + pl->blk(st, j, B_QKVW); af.qkvb = P + pl->blk(st, j, B_QKVB); af.projw = P + pl->blk(st, j, B_PROJW);
+        af.pos = k.p(B_POS); af.ln1g = k.p(B_LN1G); af.ln1b = k.p(B_LN1B); af.qkvw = k.p(B_QKVW); af.qkvb = k.p(B_QKVB); af.projw = k.p(B_PROJW);
         af.slab = bb.rq.take((size_t)ATTN_BWD_F_WGS * ATTN_BWD_F_ROW);   // a slab of its own per block: untouched until the pass's reduce launch
         if (!af.slab) return -3;
-        af.d_pos = G + pl->blk(st, j, B_POS); af.d_qkvw = G + pl->blk(st, j, B_QKVW); af.d_qkvb = G + pl->blk(st, j, B_QKVB);
-        af.d_projw = G + pl->blk(st, j, B_PROJW); af.d_ln1g = G + pl->blk(st, j, B_LN1G); af.d_ln1b = G + pl->blk(st, j, B_LN1B);
+        af.d_pos = k.g(B_POS); af.d_qkvw = k.g(B_QKVW); af.d_qkvb = k.g(B_QKVB); af.d_projw = k.g(B_PROJW); af.d_ln1g = k.g(B_LN1G); af.d_ln1b = k.g(B_LN1B);
         af.B = B; af.h = fb.h; af.w = fb.w;
         if (mr.stats) { af.so = fb.att_o; af.sl = fb.att_l; }   // left by the forward's saving launch (block_mixer_fwd)
         return launch_attn_bwd_f(e, af, s);
     }
     ProjO2BwdArgs po;
-    po.dy = tmp; po.do2 = bb.do2; po.dym = drop ? bb.dym : nullptr; po.projw = P + pl->blk(st, j, B_PROJW);
-    po.HW = fb.h * fb.w; po.total = Pn; po.dropout = drop; po.seed = mix_seed(seed, st, j);
+    po.dy = tmp; po.do2 = bb.do2; po.dym = drop ? bb.dym : nullptr; po.projw = k.p(B_PROJW);
+    po.HW = fb.h * fb.w; po.total = Pn; po.dropout = drop; po.seed = mix_seed(seed, k.st, k.j);
     RC(launch_proj_o2_bwd(e, po, s));
     const float* dym = drop ? bb.dym : tmp;
     float* fpart = bb.rq.take(fft_bwd_part_floats(B * hc, fb.h, fb.w));
     if (!fpart) return -3;
-    RC(fft_bwd_call(pl, P, G, st, j, fb, bb.do2, bb.dg, B, s, bb.fft_scratch, fpart));
+    RC(fft_bwd_call(k, bb.do2, bb.dg, B, s, fpart));
     AttnBwdArgs at;
     at.x = fb.xin; at.dy = tmp; at.dym = dym; at.o2 = fb.o2; at.dg = bb.dg; at.dx = dx_out;
     at.cat = bb.cat; at.y1 = bb.y1; at.dqkv = bb.dqkv;
-    at.pos = P + pl->blk(st, j, B_POS); at.posT = posT; at.dpos_slab = bb.rq.take((size_t)512 * 2 * 64 * 64);
+    at.pos = k.p(B_POS); at.dpos_slab = bb.rq.take(R3_DPOS_SLAB);
     if (!at.dpos_slab) return -3;
-    at.ln1g = P + pl->blk(st, j, B_LN1G); at.ln1b = P + pl->blk(st, j, B_LN1B);
-    at.qkvw = P + pl->blk(st, j, B_QKVW); at.qkvb = P + pl->blk(st, j, B_QKVB); at.projw = P + pl->blk(st, j, B_PROJW);
-    at.d_ln1g = G + pl->blk(st, j, B_LN1G); at.d_ln1b = G + pl->blk(st, j, B_LN1B); at.part = bb.rq.take(attn_bwd_part_floats(e));
-    at.d_qkvw = G + pl->blk(st, j, B_QKVW); at.d_qkvb = G + pl->blk(st, j, B_QKVB);
+    at.ln1g = k.p(B_LN1G); at.ln1b = k.p(B_LN1B); at.qkvw = k.p(B_QKVW); at.qkvb = k.p(B_QKVB); at.projw = k.p(B_PROJW);
+    at.d_ln1g = k.g(B_LN1G); at.d_ln1b = k.g(B_LN1B); at.part = bb.rq.take(attn_bwd_part_floats(e));
+    at.d_qkvw = k.g(B_QKVW); at.d_qkvb = k.g(B_QKVB);
     if (attn_bwd_fuses_qkv(e)) at.y1 = nullptr;   // the epilogue kernel forms y1 itself and accumulates the to_qkv weight gradient
     if (!at.part) return -3;
     at.B = B; at.h = fb.h; at.w = fb.w; at.core_m = mr.bwd == ATTN_BWD_R3_CORE_M ? 1 : 0; at.stats = bb.attn_stats;
     if (mr.stats) { at.so = fb.att_o; at.sl = fb.att_l; }   // left by the forward's saving launch (block_mixer_fwd)
     RC(launch_attn_bwd(e, at, s));
     const int grid = attn_bwd_grid(e, B, fb.h, fb.w);
-    RC(launch_reduce_slab(at.dpos_slab, grid, 1, 2 * 64 * 64, G + pl->blk(st, j, B_POS), 2 * 64 * 64, 1, 2 * 64 * 64, s));
-    RC(wgrad(dym, e, bb.cat, e, G + pl->blk(st, j, B_PROJW), e, G + pl->blk(st, j, B_PROJB), Pn, e, e, e, e, 0, 0, bb, s));
+    RC(launch_reduce_slab(at.dpos_slab, grid, 1, POS_TABLE, k.g(B_POS), POS_TABLE, 1, POS_TABLE, s));
+    RC(wgrad(dym, e, bb.cat, e, k.g(B_PROJW), e, k.g(B_PROJB), Pn, e, e, e, e, 0, 0, bb, s));
     if (!attn_bwd_fuses_qkv(e)) {
         const int y1ld = (hc + 15) / 16 * 16, dqld = (3 * hc + 15) / 16 * 16;
-        RC(wgrad(bb.dqkv, dqld, bb.y1, y1ld, G + pl->blk(st, j, B_QKVW), hc, G + pl->blk(st, j, B_QKVB), Pn, dqld, y1ld, 3 * hc, hc, 0, 0,
+        RC(wgrad(bb.dqkv, dqld, bb.y1, y1ld, k.g(B_QKVW), hc, k.g(B_QKVB), Pn, dqld, y1ld, 3 * hc, hc, 0, 0,
                  bb, s));
     }
     return 0;
 }
 
-static int block_bwd(const lg_plan* pl, const float* P, float* G, int st, int j, const BlockBufs& fb, BwdBufs& bb, const float* posT,
-                     const float* dy, float* tmp, float* dx_out, int B, int flags, uint64_t seed, hipStream_t s) {
-    RC(ffn_half_bwd(pl, P, G, st, j, fb, bb, dy, tmp, B, s));
-    RC(mixer_half_bwd(pl, P, G, st, j, fb, bb, posT, tmp, dx_out, B, flags, seed, s));
+static int block_bwd(const Blk& k, BwdBufs& bb, const float* dy, float* tmp, float* dx_out, int B, int flags, uint64_t seed, hipStream_t s) {
+    RC(ffn_half_bwd(k, bb, dy, tmp, B, s));
+    RC(mixer_half_bwd(k, bb, tmp, dx_out, B, flags, seed, s));
     return bb.rq.block_end();   // (per_block form: one reduce launch per block; merged form: the pass's launch takes these jobs)
 }
 
 // per-op backward entry (tests): which 0: global mixer (dy, dx planar), 1: mixer half-block, 2: ffn half-block
-int op_block_bwd(const lg_plan* pl, const float* P, float* G, int st, int j, int which, const float* dy, float* dx, NetBufs& nb,
-                 void* bwd_ws, int B, hipStream_t s) {
+int op_block_bwd(const Blk& k, int which, const float* dy, float* dx, void* bwd_ws, int B, hipStream_t s) {
     BwdBufs bb;
-    carve_bwd(pl, B, bwd_ws, bb);
-    bb.fft_scratch = nb.fft_scratch;
-    bb.ffn_scales = nb.ffn_scales;
-    const BlockBufs& fb = nb.blk[j];
-    if (which == 0) return fft_bwd_call(pl, P, G, st, j, fb, dy, dx, B, s, nb.fft_scratch, bb.slab_arena);   // no queue: summed at once
-    ReduceQueueScope rqs(bb, s, pl->route.reduce_per_block);
-    int rc = which == 1 ? 0 : ffn_transposes(pl, P, st, j, j + 1, nb, bb, s);
-    if (!rc) rc = which == 1 ? mixer_half_bwd(pl, P, G, st, j, fb, bb, nb.posT, dy, dx, B, 0, 0, s)
-                             : ffn_half_bwd(pl, P, G, st, j, fb, bb, dy, dx, B, s);
+    carve_bwd(k.pl, B, bwd_ws, bb);
+    if (which == 0) return fft_bwd_call(k, dy, dx, B, s, bb.slab_arena);   // no queue: summed at once
+    ReduceQueueScope rqs(bb, s, k.pl->route.reduce_per_block);
+    int rc = which == 1 ? 0 : ffn_transposes(&k, 1, bb, s);
+    if (!rc) rc = which == 1 ? mixer_half_bwd(k, bb, dy, dx, B, 0, 0, s) : ffn_half_bwd(k, bb, dy, dx, B, s);
     const int rc2 = reduce_queue_end();
     return rc ? rc : rc2;
 }
@@ -360,47 +346,47 @@ static int lgt_bwd(const lg_plan* pl, const float* P, float* G, int st, const Ne
     const lg_config& c = pl->cfg;
     const int E = 4 * c.C;
     const long P0 = (long)B * c.H * c.W, P1 = P0 / 4;
-    const float* posT = nb.posT + (size_t)st * 5 * 2 * 64 * 64;
+    const LgtSlots L{pl, P, G, st};
+    Blk k[LG_NBLK];
+    for (int j = 0; j < LG_NBLK; ++j) k[j] = nb.block(pl, P, G, st, j);
     float *A = bb.dx[0], *Bf = bb.dx[1], *Cf = bb.dx[2];
-    RC(ffn_transposes(pl, P, st, 0, 5, nb, bb, s));
+    RC(ffn_transposes(k, LG_NBLK, bb, s));
     TailBwdArgs tb;
-    tb.dout = dout; tb.x = nb.blk[4].xout; tb.dx = A; tb.dz = bb.dzA; tb.w = P + pl->lgt(st, L_TAILW);
-    tb.d_w = G + pl->lgt(st, L_TAILW); tb.d_b = G + pl->lgt(st, L_TAILB);   // the conv's own weight gradient comes out of the same kernel
+    tb.dout = dout; tb.x = nb.blk[4].xout; tb.dx = A; tb.dz = bb.dzA; tb.w = L.p(L_TAILW);
+    tb.d_w = L.g(L_TAILW); tb.d_b = L.g(L_TAILB);   // the conv's own weight gradient comes out of the same kernel
     tb.HW = c.H * c.W; tb.total = P0; tb.part = bb.rq.take(tail_bwd_part_floats(c.C));
     if (!tb.part) return -3;
     RC(launch_tail_bwd(c.C, tb, s));
-    RC(block_bwd(pl, P, G, st, 4, nb.blk[4], bb, posT + 4 * 8192, A, Bf, Cf, B, flags, seed, s));
-    RC(block_bwd(pl, P, G, st, 3, nb.blk[3], bb, posT + 3 * 8192, Cf, Bf, A, B, flags, seed, s));
+    RC(block_bwd(k[4], bb, A, Bf, Cf, B, flags, seed, s));
+    RC(block_bwd(k[3], bb, Cf, Bf, A, B, flags, seed, s));
     // up + fusion
     UpFuseBwdArgs ub;
     ub.dy = A; ub.dt = bb.dt; ub.dskip = bb.dskip; ub.v = bb.v; ub.dxb = Bf; ub.tmp = Cf;   // Cf is free until the bottleneck block
-    ub.fw = P + pl->lgt(st, L_FUSEW); ub.upw = P + pl->lgt(st, L_UPW);
+    ub.fw = L.p(L_FUSEW); ub.upw = L.p(L_UPW);
     ub.B = B; ub.H = c.H; ub.W = c.W;
     RC(launch_upfuse_bwd_a(E, ub, s));
-    RC(wgrad(A, E, nb.t_up, E, G + pl->lgt(st, L_FUSEW), 2 * E, G + pl->lgt(st, L_FUSEB), P0, E, E, E, E, 0, 0, bb, s));
-    RC(wgrad(A, E, nb.blk[1].xout, E, G + pl->lgt(st, L_FUSEW) + E, 2 * E, nullptr, P0, E, E, E, E, 0, 0, bb, s));
+    RC(wgrad(A, E, nb.t_up, E, L.g(L_FUSEW), 2 * E, L.g(L_FUSEB), P0, E, E, E, E, 0, 0, bb, s));
+    RC(wgrad(A, E, nb.blk[1].xout, E, L.g(L_FUSEW) + E, 2 * E, nullptr, P0, E, E, E, E, 0, 0, bb, s));
     RC(launch_upfuse_bwd_b(E, ub, s));
-    RC(wgrad(bb.v, E, nb.blk[2].xout, 2 * E, G + pl->lgt(st, L_UPW), 2 * E, G + pl->lgt(st, L_UPB), P1, E, 2 * E, E, 2 * E, 0, 0, bb, s));
+    RC(wgrad(bb.v, E, nb.blk[2].xout, 2 * E, L.g(L_UPW), 2 * E, L.g(L_UPB), P1, E, 2 * E, E, 2 * E, 0, 0, bb, s));
     // bottleneck
-    RC(block_bwd(pl, P, G, st, 2, nb.blk[2], bb, posT + 2 * 8192, Bf, Cf, A, B, flags, seed, s));
+    RC(block_bwd(k[2], bb, Bf, Cf, A, B, flags, seed, s));
     // down
     DownBwdArgs db;
-    db.dy = A; db.du = bb.du; db.dskip = bb.dskip; db.dx = Bf; db.w = P + pl->lgt(st, L_DOWNW);
+    db.dy = A; db.du = bb.du; db.dskip = bb.dskip; db.dx = Bf; db.w = L.p(L_DOWNW);
     db.B = B; db.H = c.H; db.W = c.W;
     RC(launch_down_bwd_a(E, db, s));
-    RC(wgrad(A, 2 * E, nb.u_down, E, G + pl->lgt(st, L_DOWNW), E, G + pl->lgt(st, L_DOWNB), P1, 2 * E, E, 2 * E, E, 0, 0, bb, s));
+    RC(wgrad(A, 2 * E, nb.u_down, E, L.g(L_DOWNW), E, L.g(L_DOWNB), P1, 2 * E, E, 2 * E, E, 0, 0, bb, s));
     RC(launch_down_bwd_b(E, db, s));
     // encoder
-    RC(block_bwd(pl, P, G, st, 1, nb.blk[1], bb, posT + 1 * 8192, Bf, Cf, A, B, flags, seed, s));
-    RC(block_bwd(pl, P, G, st, 0, nb.blk[0], bb, posT + 0 * 8192, A, Bf, Cf, B, flags, seed, s));
+    RC(block_bwd(k[1], bb, Bf, Cf, A, B, flags, seed, s));
+    RC(block_bwd(k[0], bb, A, Bf, Cf, B, flags, seed, s));
     // patch embed
     EmbedBwdArgs eb;
     eb.dx = Cf; eb.z = zin; eb.dz = bb.dzA;
-    eb.dww = P + pl->lgt(st, L_PE_DWW); eb.dwb = P + pl->lgt(st, L_PE_DWB); eb.w = P + pl->lgt(st, L_PE_W); eb.b = P + pl->lgt(st, L_PE_B);
-    eb.lng = P + pl->lgt(st, L_PE_LNG);
-    eb.d_dww = G + pl->lgt(st, L_PE_DWW); eb.d_dwb = G + pl->lgt(st, L_PE_DWB);
-    eb.d_lng = G + pl->lgt(st, L_PE_LNG); eb.d_lnb = G + pl->lgt(st, L_PE_LNB);
-    eb.d_w = G + pl->lgt(st, L_PE_W); eb.d_b = G + pl->lgt(st, L_PE_B);   // the conv's own weight gradient comes out of the same kernel
+    eb.dww = L.p(L_PE_DWW); eb.dwb = L.p(L_PE_DWB); eb.w = L.p(L_PE_W); eb.b = L.p(L_PE_B); eb.lng = L.p(L_PE_LNG);
+    eb.d_dww = L.g(L_PE_DWW); eb.d_dwb = L.g(L_PE_DWB); eb.d_lng = L.g(L_PE_LNG); eb.d_lnb = L.g(L_PE_LNB);
+    eb.d_w = L.g(L_PE_W); eb.d_b = L.g(L_PE_B);   // the conv's own weight gradient comes out of the same kernel
     eb.HW = c.H * c.W; eb.total = P0; eb.part = bb.rq.take(embed_bwd_part_floats(c.C));
     if (!eb.part) return -3;
     RC(launch_embed_bwd(c.C, eb, s));
@@ -423,8 +409,6 @@ int op_lgt_bwd(const lg_plan* pl, const float* P, float* G, int st, NetBufs& nb,
                int B, int flags, uint64_t seed, hipStream_t s) {
     BwdBufs bb;
     carve_bwd(pl, B, bwd_ws, bb);
-    bb.fft_scratch = nb.fft_scratch;
-    bb.ffn_scales = nb.ffn_scales;
     bb.dzA = dz;                       // lgt_bwd leaves the gradient wrt the LGT's input here
     ReduceQueueScope rqs(bb, s, pl->route.reduce_per_block);
     const int rc = lgt_bwd(pl, P, G, st, nb, bb, dout, z, B, flags, seed, s);
@@ -438,8 +422,6 @@ int net_backward(const lg_plan* pl, const float* P, float* G, const float* ms, c
     const lg_config& c = pl->cfg;
     BwdBufs bb;
     carve_bwd(pl, B, bwd_ws, bb);
-    bb.fft_scratch = nb.fft_scratch;
-    bb.ffn_scales = nb.ffn_scales;
     ReduceQueueScope rqs(bb, s, pl->route.reduce_per_block);
     if (flags & LG_FLAG_CHAINED) {
         // intended unfolding (every stage live): LGT_i then data step i, last stage first; each LGT reads its own activation set

@@ -240,7 +240,6 @@ struct AttnArgs {
 int launch_attn(int e, const AttnArgs& a, hipStream_t s);     // round 2's kernel: lane = token, every product on the vector pipe (LG_VAR_ATTN_FWD_VALU)
 int launch_attn_m(int e, const AttnArgs& a, hipStream_t s);   // round 5: every product on the matrix pipe (k_attn_m.hip)
 // posT[blk] for nblk blocks: src pointers via offsets into params
-int launch_pos_transpose(const float* pos, float* posT, hipStream_t s);
 int launch_pos_transpose_n(int n, const float* const* pos, float* const* posT, hipStream_t s);   // n <= 5 * LG_MAX_K tables in one launch
 
 // ---------------- feed_forward, LGT.py:91-109 ----------------

@@ -15,6 +15,14 @@ struct Carver {
 };
 
 #define LG_MAX_K 16
+#define LG_NBLK 5   // blocks of one LGT: encoder 0 1, bottleneck 2 (level 1), decoder 3 4
+
+// The per-block prep slots: four tables of [K][LG_NBLK] rows, written once per forward call (api.hip: prep_stages) and read by the kernels of
+// that (stage, block).  THE description of their layout: the row sizes here, the carving in carve(), the rows in NetBufs::*_row and
+// NetBufs::block, the stage-to-stage strides of the multi-stage kernels in NetBufs::stage_strides.
+constexpr size_t POS_TABLE = 2 * 64 * 64;   // floats of one pos_emb table [2][64][64] (posT; a row of the R3 backward's dpos slab too)
+constexpr size_t FFN_SCALES_ROW = 8;        // floats of a block's row of ffn_scales
+constexpr size_t ATTN_SCALES_ROW = 4;       // ... of attn_scales
 
 struct BlockBufs {
     int e, h, w;       // channels / spatial size of this block
@@ -26,23 +34,60 @@ struct BlockBufs {
     float *a1, *g1, *h2, *a3, *g3;  // [B,h,w,4e]: gelu(h1), gelu'(h1), h2, gelu(h3), gelu'(h3)  (a*, g* train only)
 };
 
+// One (stage, block) of an LGT, as every block function receives it: the block's buffers, its slots of the flat parameter / gradient buffers and
+// its rows of the prep tables (NetBufs::block).  `b` is a copy: the per-op entries point xin / xmid / xout at their caller's tensors.
+struct Blk {
+    const lg_plan* pl;
+    const float* P;
+    float* G;          // null in the forward
+    int st, j;
+    BlockBufs b;
+    float* fft_scratch;                     // NetBufs::fft_scratch
+    const float *posT, *attn_scales;        // this block's rows
+    float *ffn_scales, *wsplit;
+    const float* p(int slot) const { return P + pl->blk(st, j, slot); }   // parameter slot B_*
+    float* g(int slot) const { return G + pl->blk(st, j, slot); }         // its gradient
+};
+// ... and the LGT-level slots L_* of a stage
+struct LgtSlots {
+    const lg_plan* pl;
+    const float* P;
+    float* G;
+    int st;
+    const float* p(int slot) const { return P + pl->lgt(st, slot); }
+    float* g(int slot) const { return G + pl->lgt(st, slot); }
+};
+
 struct NetBufs {
     float* Z[LG_MAX_K + 1];                          // Z_0 .. Z_K  [B,C,H,W]: Z[i] -> data step i -> Z[i+1] (= input of LGT i)
     float* X[LG_MAX_K];                              // chained mode: input of data step i (X[0] = Z[0], X[i] = output of LGT i-1)
     float *t1[LG_MAX_K], *r[LG_MAX_K], *s1[LG_MAX_K];  // data-step intermediates per stage
     float* pr;                                       // [B,H,W] scratch of the one-launch data step (k_dstep.hip): R Z - pan of the stage in flight
-    float* posT;                                     // [K][5][2*64*64]
-    BlockBufs blk[5];
+    float* posT;                                     // [K][LG_NBLK][POS_TABLE]
+    BlockBufs blk[LG_NBLK];
     float* x0;        // embed output = blk[0].xin
     float* deadout;   // output of dead-stage LGTs (faithful mode)
     float* u_down;    // saved bicubic-downsampled encoder output [B,H/2,W/2,E] (train)
     float* t_up;      // saved up-path tensor [B,H,W,E] (train)
     float* fft_scratch;  // PAN > 128 only: half-spectrum scratch of the split FFT path
-    float* ffn_scales;   // [K][5][8] operand scales of the f16-pair FFN arithmetic (k_ffn_prep.hip), written once per forward call
-    float* attn_scales;  // [K][5][4] static operand scales of the local mixer's f16-pair products { s_y, s_w, s_q, s_k } (k_ffn_prep.hip), written once per forward call
-    float* wsplit;       // [K][5] slots of pre-split (and pre-scaled) weight fragments of the e >= 32 FFN blocks (k_ffn_x32.hip), written once per forward call
+    float* ffn_scales;   // [K][LG_NBLK][FFN_SCALES_ROW] operand scales of the f16-pair FFN arithmetic (k_ffn_prep.hip), written once per forward call
+    float* attn_scales;  // [K][LG_NBLK][ATTN_SCALES_ROW] static operand scales of the local mixer's f16-pair products { s_y, s_w, s_q, s_k } (k_ffn_prep.hip), written once per forward call
+    float* wsplit;       // [K][LG_NBLK][wsplit_slot] slots of pre-split (and pre-scaled) weight fragments of the e >= 32 FFN blocks (k_ffn_x32.hip), written once per forward call
     size_t set_off, set_bytes;  // the per-LGT activation set [set_off, set_off + set_bytes): train == 2 carves K of them back to back
+    size_t wsplit_slot;         // floats of one wsplit slot: sized for the widest block (level 1: e = 8 C)
     size_t bytes;
+    static size_t row(int st, int j) { return (size_t)st * LG_NBLK + j; }
+    float* posT_row(int st, int j) const { return posT + row(st, j) * POS_TABLE; }
+    float* ffn_scales_row(int st, int j) const { return ffn_scales + row(st, j) * FFN_SCALES_ROW; }
+    float* attn_scales_row(int st, int j) const { return attn_scales + row(st, j) * ATTN_SCALES_ROW; }
+    float* wsplit_row(int st, int j) const { return wsplit + row(st, j) * wsplit_slot; }
+    // from one stage's rows to the next one's, in the units the multi-stage kernels shift by (kernels.h: StageSel)
+    void stage_strides(StageSel& sg) const {
+        sg.fs_stride = (int)(LG_NBLK * FFN_SCALES_ROW); sg.as_stride = (int)(LG_NBLK * ATTN_SCALES_ROW); sg.ws_stride = (long)(LG_NBLK * wsplit_slot * sizeof(float));
+    }
+    Blk block(const lg_plan* pl, const float* P, float* G, int st, int j) const {
+        return Blk{pl, P, G, st, j, blk[j], fft_scratch, posT_row(st, j), attn_scales_row(st, j), ffn_scales_row(st, j), wsplit_row(st, j)};
+    }
 };
 
 // NetBufs of stage `i` when every stage keeps its own activation set (chained training): same layout, shifted by i sets
@@ -50,7 +95,7 @@ static inline NetBufs stage_view(const NetBufs& nb, int i) {
     NetBufs v = nb;
     const size_t sh = (size_t)i * nb.set_bytes;
     auto mv = [sh](float*& p) { if (p) p = reinterpret_cast<float*>(reinterpret_cast<char*>(p) + sh); };
-    for (int j = 0; j < 5; ++j) {
+    for (int j = 0; j < LG_NBLK; ++j) {
         BlockBufs& b = v.blk[j];
         mv(b.xin); mv(b.xmid); mv(b.xout); mv(b.g); mv(b.o2); mv(b.amp); mv(b.pha); mv(b.sgn); mv(b.att_o); mv(b.att_l);
         mv(b.a1); mv(b.g1); mv(b.h2); mv(b.a3); mv(b.g3);
@@ -76,17 +121,19 @@ static inline void carve(const lg_plan* plan, int B, int train, void* base, NetB
         nb.s1[i] = cv.take(B * c.C * P1);
     }
     nb.pr = cv.take(B * P0);
-    nb.posT = cv.take((size_t)c.K * 5 * 2 * 64 * 64);
-    nb.ffn_scales = cv.take((size_t)c.K * 5 * 8);
-    nb.attn_scales = cv.take((size_t)c.K * 5 * 4);
-    nb.wsplit = cv.take((size_t)c.K * 5 * (ffn_wsplit_bytes((int)(2 * E)) / sizeof(float)));   // [K][5] slots sized for the widest block (level 1: e = 8 C): written once per forward call (prep_stages)
+    const size_t rows = NetBufs::row(c.K, 0);
+    nb.posT = cv.take(rows * POS_TABLE);
+    nb.ffn_scales = cv.take(rows * FFN_SCALES_ROW);
+    nb.attn_scales = cv.take(rows * ATTN_SCALES_ROW);
+    nb.wsplit_slot = ffn_wsplit_bytes((int)(2 * E)) / sizeof(float);
+    nb.wsplit = cv.take(rows * nb.wsplit_slot);
     nb.deadout = cv.take(BT * c.C * P0);
     nb.X[0] = nb.Z[0];
     for (int i = 1; i < c.K; ++i) nb.X[i] = (train == 2) ? cv.take(B * c.C * P0) : nb.deadout;
     float* shared_h2 = nullptr;
     if (!train) shared_h2 = cv.take(B * P0 * 4 * E);  // largest (level-0) hidden tensor, reused by every block
     nb.set_off = cv.off;
-    for (int j = 0; j < 5; ++j) {
+    for (int j = 0; j < LG_NBLK; ++j) {
         BlockBufs& bb = nb.blk[j];
         const bool l1 = (j == 2);
         bb.e = (int)(l1 ? 2 * E : E);
