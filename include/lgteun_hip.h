@@ -114,7 +114,7 @@ typedef struct lg_plan lg_plan; /* host-side, immutable after creation */
 
 const char* lg_version(void);
 /* Bumped whenever a struct layout, an argument meaning or a caller-provided buffer size changes (2: lg_config.variant, the data step's
- * tmp of 3*B*C*H*W/4 + B*H*W floats).  Additions keep it: lg_op_lgt_stages, lg_workspace_deadout, LG_FLAG_STAGEWISE and the lg_debug_stage_* entries came without a bump (no struct,
+ * tmp of 3*B*C*H*W/4 + B*H*W floats).  Additions keep it: lg_op_lgt_stages, lg_workspace_deadout, LG_FLAG_STAGEWISE, the lg_debug_stage_* entries and the classical baselines (lg_classical_workspace_bytes, lg_interp23_up4, lg_sfim, lg_gsa) came without a bump (no struct,
  * argument or caller-sized buffer changed: workspaces are sized by lg_workspace_bytes, which grew for the plans that batch their dead stages).  A binding checks it at load time -- lgteun_amd/_lib.py does -- instead of passing a stale struct. */
 #define LG_ABI_VERSION 2
 int32_t lg_abi_version(void);
@@ -453,6 +453,32 @@ int lg_scene_blend(const float* tiles, float* scene, int64_t first, int32_t B, i
 /* dst[i] = clip(rint(src[i] * scale), 0, 65535) with one fp32 multiplication and round-half-even (NaN -> 0): data_denormalize followed by the
  * TIFF writer's conversion.  n: a multiple of 4; src 16-byte, dst 8-byte aligned. */
 int lg_scene_to_u16(const float* src, uint16_t* dst, int64_t n, float scale, void* stream);
+
+/* ---- the classical baselines: SFIM and GSA (global regression) on the 23-tap interpolator x4 (lgteun_amd/classical.py; kernels in
+ * lgteun_amd/csrc/k_classical.hip; the definitions are DESIGN.md 3.12) ----
+ * ms [B,C,h,w], pan [B,1,4h,4w], out [B,C,4h,4w]: contiguous fp32, normalised to [0, 1].  Every sample is fused on its own.  All arithmetic is
+ * fp64 with one rounding per output element; the moments are per-workgroup partials in the workspace plus a fixed-order pass (no atomics):
+ * repeated calls give the same bits, and sample b of a batch has the bits of that sample fused alone.  The workspace needs no
+ * initialisation.  2 <= C <= LG_IQA_MAX_BANDS; 4 <= h, w <= 4096; 1 <= B <= 65535; float tensors 16-byte aligned, workspace and stats 8-byte
+ * aligned.  Arguments are validated before any HIP call, the offender is named in lg_last_error; all indexing is 64-bit; the calls allocate
+ * nothing and synchronise nothing. */
+#define LG_CLASSICAL_SFIM 0
+#define LG_CLASSICAL_GSA 1
+/* bytes of workspace lg_sfim (method LG_CLASSICAL_SFIM) / lg_gsa (LG_CLASSICAL_GSA) needs; 0 for a shape or method the calls reject */
+size_t lg_classical_workspace_bytes(int32_t B, int32_t C, int32_t h, int32_t w, int32_t method);
+/* u = interp23(ms): two x2 levels of zero insertion and the circular 23-tap half-band interpolator along rows, then columns; ms sample (i, j)
+ * sits at u(4 i + 2, 4 j + 2) */
+int lg_interp23_up4(const float* ms, float* out, int32_t B, int32_t C, int32_t h, int32_t w, void* stream);
+/* out_k = clip(u_k p_k / (box5(p_k) + 1e-8), 0, 1), p_k = (pan - mean pan) std(u_k) / std(pan) + mean u_k (both std divide by N - 1), box5 the
+ * circular 5 x 5 mean.  A constant PAN has scale 0. */
+int lg_sfim(const float* ms, const float* pan, float* out, int32_t B, int32_t C, int32_t h, int32_t w, void* workspace, size_t workspace_bytes,
+            void* stream);
+/* out_k = clip(u_k + g_k (p~ - I0), 0, 1): p~ = pan - mean pan, I0 = sum_k alpha_k (u_k - mean u_k), alpha the least-squares fit of the 2 x 2
+ * centre means of p~ by [ms_k - mean ms_k, 1], g_k = cov(I0, u_k) / var(I0) (covariance / (N - 1), variance / N).  stats: NULL or a device
+ * array [B, 2 C + 1] of fp64 that receives alpha (C + 1 values, the intercept last), then g.  A sample whose regression is singular or whose
+ * I0 has no variance gets alpha_0..C-1 = g = 0: out = clip(u). */
+int lg_gsa(const float* ms, const float* pan, float* out, double* stats, int32_t B, int32_t C, int32_t h, int32_t w, void* workspace,
+           size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,150 @@
+"""The two non-learned rows of a pan-sharpening results table, for whole batches on the GPU: SFIM (smoothing-filter-based intensity
+modulation) and GSA (adaptive Gram-Schmidt with a global regression), both on top of the 23-tap interpolator x4 -- the reference's
+models/SFIM.py, models/GSA.py and models/common/model_based_utils.py:upsample_interp23.  The definitions, restated per sample of a batch, and
+the two deliberate deviations are in DESIGN.md 3.12; the HIP kernels are lgteun_amd/csrc/k_classical.hip (C ABI lg_interp23_up4 / lg_sfim /
+lg_gsa in include/lgteun_hip.h): fp64 arithmetic, one rounding per output element, no atomics.  There is no CPU path.
+
+`interp23`, `sfim` and `gsa` take normalised float32 NCHW tensors on the GPU -- ms [B, C, h, w], pan [B, 1, 4h, 4w] -- and return
+[B, C, 4h, 4w] on the same device; nothing is copied to the host and nothing synchronises.  `GSA` and `SFIM` are the runner classes the
+reference registers under those names: they have nothing to train, and `test()` scores them like any network."""
+import numpy as np
+import torch
+
+from . import _lib
+from .base_model import Base_model
+from .builder import MODELS
+from .engine import _ptr, _stream_ptr
+
+_workspaces = {}        # (device, method, B, C, h, w) -> float64 tensor: the partial sums and coefficients of lg_sfim / lg_gsa
+
+
+def _prepare(what, ms, pan=None):
+    for name, t in (('ms', ms), ('pan', pan))[:1 if pan is None else 2]:
+        if not torch.is_tensor(t) or t.dim() != 4 or t.dtype != torch.float32:
+            got = f'{t.dtype} {tuple(t.shape)}' if torch.is_tensor(t) else type(t).__name__
+            raise ValueError(f'{what}: {name} must be a float32 NCHW tensor (got {got})')
+        if not t.is_cuda:
+            raise ValueError(f'{what}: {name} is on {t.device}; the classical methods run on the GPU only (there is no CPU path)')
+    B, C, h, w = ms.shape
+    if pan is not None:
+        if pan.device != ms.device:
+            raise ValueError(f'{what}: ms is on {ms.device}, pan on {pan.device}')
+        if tuple(pan.shape) != (B, 1, 4 * h, 4 * w):
+            raise ValueError(f'{what}: expected pan {(B, 1, 4 * h, 4 * w)} for ms {tuple(ms.shape)}, got {tuple(pan.shape)}')
+        pan = pan.contiguous()
+    return ms.contiguous(), pan, (B, C, h, w)
+
+
+def _workspace(dev, method, shape):
+    key = (dev, method) + shape
+    ws = _workspaces.get(key)
+    if ws is None:
+        need = int(_lib.lib().lg_classical_workspace_bytes(*shape, method))      # 0 for a shape the library rejects: the call says why
+        ws = _workspaces[key] = torch.empty(max((need + 7) // 8, 1), dtype=torch.float64, device=dev)
+    return ws
+
+
+def interp23(ms):
+    """ms [B, C, h, w] -> [B, C, 4h, 4w]: two x2 levels of zero insertion and the circular 23-tap half-band interpolator"""
+    ms, _, (B, C, h, w) = _prepare('interp23', ms)
+    with torch.cuda.device(ms.device):
+        out = torch.empty(B, C, 4 * h, 4 * w, dtype=torch.float32, device=ms.device)
+        _lib.check(_lib.lib().lg_interp23_up4(_ptr(ms), _ptr(out), B, C, h, w, _stream_ptr()), 'lg_interp23_up4')
+    return out
+
+
+def sfim(ms, pan):
+    """SFIM of every sample: interp23(ms) modulated by the ratio of the histogram-matched PAN to its 5 x 5 circular box mean"""
+    ms, pan, shape = _prepare('sfim', ms, pan)
+    B, C, h, w = shape
+    with torch.cuda.device(ms.device):
+        ws = _workspace(ms.device, _lib.LG_CLASSICAL_SFIM, shape)
+        out = torch.empty(B, C, 4 * h, 4 * w, dtype=torch.float32, device=ms.device)
+        _lib.check(_lib.lib().lg_sfim(_ptr(ms), _ptr(pan), _ptr(out), B, C, h, w, _ptr(ws), ws.numel() * 8, _stream_ptr()), 'lg_sfim')
+    return out
+
+
+def gsa(ms, pan, return_stats=False):
+    """GSA of every sample.  return_stats: also a float64 [B, 2C + 1] device tensor, per sample the regression weights alpha (C + 1, the
+    intercept last) and the injection gains g (C)"""
+    ms, pan, shape = _prepare('gsa', ms, pan)
+    B, C, h, w = shape
+    with torch.cuda.device(ms.device):
+        ws = _workspace(ms.device, _lib.LG_CLASSICAL_GSA, shape)
+        out = torch.empty(B, C, 4 * h, 4 * w, dtype=torch.float32, device=ms.device)
+        stats = torch.empty(B, 2 * C + 1, dtype=torch.float64, device=ms.device) if return_stats else None
+        _lib.check(_lib.lib().lg_gsa(_ptr(ms), _ptr(pan), _ptr(out), _ptr(stats) if return_stats else None, B, C, h, w, _ptr(ws),
+                                     ws.numel() * 8, _stream_ptr()), 'lg_gsa')
+    return (out, stats) if return_stats else out
+
+
+def fuse_scene(method, ms, pan, bit_depth=None, norm_input=False, out_dtype='float32', device=None):
+    """One whole scene through `method` ('gsa' or 'sfim') in ONE call -- no tiles, no checkpoint: MS [C, h, w], PAN [1, 4h, 4w] -> [C, 4h, 4w]
+    on the device.  The arguments are scene.fuse_scene's: samples as numpy arrays or tensors (uint8, uint16 or its int16 view, float32);
+    bit_depth / norm_input: the normalisation of the tile gather (norm_input: one correctly rounded fp32 division by 2**bit_depth - 0.5, then
+    one multiplication by the fp32 reciprocal of that number); out_dtype 'uint16': digital numbers by lg_scene_to_u16 (needs bit_depth)."""
+    from . import scene as sc
+    if method not in ('gsa', 'sfim'):
+        raise ValueError(f"method must be 'gsa' or 'sfim' (got {method!r})")
+    if out_dtype not in ('float32', 'uint16'):
+        raise ValueError(f"out_dtype must be 'float32' or 'uint16' (got {out_dtype!r})")
+    if (norm_input or out_dtype == 'uint16') and bit_depth is None:
+        raise ValueError("norm_input and out_dtype='uint16' need bit_depth")
+    C, H, W = sc.check_shapes(ms.shape, pan.shape)
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    ms_t, kind = sc._to_device(ms, dev, 'ms')
+    pan_t, kind_p = sc._to_device(pan, dev, 'pan')
+    if kind != kind_p:
+        raise ValueError(f'ms ({kind}) and pan ({kind_p}) must have the same sample type')
+    divisor = float(2 ** bit_depth - .5) if bit_depth is not None else 1.0
+
+    def normalised(t):
+        if t.dtype == torch.int16:                        # the int16 view of uint16 samples
+            t = t.to(torch.int32) & 0xFFFF
+        t = t.to(torch.float32)
+        if norm_input:
+            t = torch.div(t, torch.tensor(divisor, dtype=torch.float32, device=dev))
+        if bit_depth is not None:
+            t = t * float(np.float32(1.0) / np.float32(divisor))        # scene.fuse_scene's post_scale
+        return t
+    with torch.cuda.device(dev):
+        fused = (gsa if method == 'gsa' else sfim)(normalised(ms_t).view(1, C, H // 4, W // 4), normalised(pan_t).view(1, 1, H, W))[0]
+        if out_dtype == 'float32':
+            return fused
+        out = torch.empty(C, H, W, dtype=torch.uint16, device=dev)
+        _lib.check(_lib.lib().lg_scene_to_u16(_ptr(fused), _ptr(out), fused.numel(), divisor, _stream_ptr()), 'lg_scene_to_u16')
+        return out
+
+
+class _Classical(Base_model):
+    """a runner without modules: `get_model_output` is the method itself, on the whole batch (the reference squeezes the batch to one image
+    and returns an HWC numpy array; models/GSA.py:49-52)"""
+    method = None
+
+    def _device(self):
+        return torch.device('cuda', torch.cuda.current_device())
+
+    def get_model_output(self, input_batch):
+        return type(self).method(input_batch['input_lr'], input_batch['input_pan'])
+
+    def train(self):
+        if self.logger is not None:
+            self.logger.info(f'{type(self).__name__} has nothing to train')
+
+    def train_iter(self, iter_id, input_batch, log_freq=10):
+        raise RuntimeError(f'{type(self).__name__} is a classical method: it has nothing to train')
+
+    def save(self, iter_id):
+        if self.logger is not None:
+            self.logger.info(f'{type(self).__name__} has no weights: nothing to save')
+        return None
+
+
+@MODELS.register_module()
+class GSA(_Classical):
+    method = staticmethod(gsa)
+
+
+@MODELS.register_module()
+class SFIM(_Classical):
+    method = staticmethod(sfim)

@@ -991,3 +991,21 @@ extern "C" int lg_optim_step_ex(float* params, const float* grads, float* state0
     return launch_adam(params, grads, state0, state1, ranges, n_ranges, max_range, step, (float)lr, (float)h0, (float)h1, (float)eps,
                        (float)grad_scale, c, (hipStream_t)stream);
 }
+
+// ------------------------------------------------------------------------------------------------
+// the classical baselines (k_classical.hip)
+// ------------------------------------------------------------------------------------------------
+extern "C" size_t lg_classical_workspace_bytes(int32_t B, int32_t C, int32_t h, int32_t w, int32_t method) {
+    return classical_workspace_bytes(B, C, h, w, method);
+}
+extern "C" int lg_interp23_up4(const float* ms, float* out, int32_t B, int32_t C, int32_t h, int32_t w, void* stream) {
+    return launch_interp23_up4(ms, out, B, C, h, w, (hipStream_t)stream);
+}
+extern "C" int lg_sfim(const float* ms, const float* pan, float* out, int32_t B, int32_t C, int32_t h, int32_t w, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    return launch_sfim(ms, pan, out, B, C, h, w, workspace, workspace_bytes, (hipStream_t)stream);
+}
+extern "C" int lg_gsa(const float* ms, const float* pan, float* out, double* stats, int32_t B, int32_t C, int32_t h, int32_t w, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    return launch_gsa(ms, pan, out, stats, B, C, h, w, workspace, workspace_bytes, (hipStream_t)stream);
+}

@@ -1,0 +1,470 @@
+// The two classical (training-free) pan-sharpening baselines, whole batches on the device: SFIM and GSA with global regression, on top of the
+// 23-tap half-band interpolator x4 (C ABI: lg_interp23_up4 / lg_sfim / lg_gsa, include/lgteun_hip.h; the definitions are in DESIGN.md 3.12,
+// the fp64 numpy restatement the tests compare with is tests/classical_ref.py).
+//
+//   cl_up_band       the upsampling of ONE band for a 16 x 32 tile of the output, in LDS, all fp64: the 20 x 24 ms samples the tile depends on
+//                    (cl_ms_load: loaded modulo h, w -- the circular boundary happens here and nowhere else -- into registers, one band
+//                    ahead of their use), level 1 rows then columns (19 x 27 of the 2h x 2w plane: the tile's own 8 x 16 plus the halo of
+//                    5 / 6 level 2 needs), level 2 rows then columns.  A level keeps the inserted samples (even / odd positions are copies)
+//                    and fills the rest with 12 products per axis; the copy and the filter run as two loops, so no wave does both.  u is
+//                    never stored in memory: every consumer recomputes its tile.
+//   k_cl_interp      grid (tile, band, sample): the tile, rounded to fp32 once.
+//   k_cl_moments     grid (gx, sample), gx = min(tiles, the workgroups resident at once); a workgroup walks the tiles gx apart: the C bands
+//                    of the tile, PAN minus the sample's first PAN pixel (the pivot: a constant PAN has EXACTLY zero moments) and the mask of the pixels inside the image as C + 2 vectors
+//                    in LDS, GSA also the C ms bands, the 2 x 2 centre mean of PAN and the mask at the tile's 4 x 8 low-resolution pixels.
+//                    Every sum the method needs is the sum of a product of two of those vectors: a wave owns the pairs e = wave, wave + 4,
+//                    ..., sums them over the tile and lane 0 adds to its slot in LDS -- one order, always.  The workgroup writes its slots.
+//   k_cl_finish      one workgroup per sample: the partials in ascending order, then one thread: SFIM's scales, or GSA's C x C Cholesky
+//                    solve for alpha and the gains g = N / (N - 1) Sigma_u alpha / (alpha' Sigma_u alpha).  A constant PAN gives scale 0;
+//                    a non-positive pivot, alpha' Sigma_u alpha <= 0 or a gain that is not finite gives alpha = g = 0.
+//   k_cl_apply       grid (tile, sample): the C bands of the tile again, then pointwise in fp64 with ONE rounding to fp32; SFIM stages
+//                    PAN with a circular halo of 2 for the 5 x 5 box.  Two adjacent pixels per thread: 8-byte stores.
+// No atomics; a workgroup sees one sample and the grid of a sample depends on C, h and w only, so a sample has the same bits alone and inside
+// any batch.  All indexing into tensors is 64-bit.
+#include <cmath>
+
+#include "common.h"
+#include "kernels.h"
+#include "reduce.h"
+
+namespace {
+
+constexpr int CL_NT = 256;
+constexpr int CL_TH = 16, CL_TW = 32, CL_PX = CL_TH * CL_TW;            // the output tile
+constexpr int CL_L1R = CL_TH / 2 + 11, CL_L1C = CL_TW / 2 + 11;         // 19 x 27: level-1 rows / columns a tile depends on
+constexpr int CL_MR = CL_TH / 4 + 16, CL_MC = CL_TW / 4 + 16;           // 20 x 24: ms rows / columns a tile depends on
+constexpr int CL_LR = CL_TH / 4, CL_LC = CL_TW / 4, CL_LPX = CL_LR * CL_LC;      // the tile's own 4 x 8 low-resolution pixels
+constexpr int CL_SCRATCH = CL_MR * CL_MC + CL_MR * CL_L1C + CL_L1R * CL_L1C + CL_L1R * CL_TW;      // doubles: M, R1, L1, R2
+constexpr int CL_MLOADS = (CL_MR * CL_MC + CL_NT - 1) / CL_NT;           // ms samples a thread loads per band and tile
+constexpr int CL_BOX = 5, CL_BH = CL_TH + CL_BOX - 1, CL_BW = CL_TW + CL_BOX - 1;      // SFIM's staged PAN: 20 x 36
+constexpr int CL_CUS = 256, CL_CU_LDS = 160 * 1024;                     // the MI355X: compute units, LDS bytes of one
+constexpr int CL_MAX_C = LG_IQA_MAX_BANDS;
+constexpr int CL_MAX_SUMS = (CL_MAX_C + 2) * (CL_MAX_C + 3);            // GSA: all pairs of C + 2 vectors, high and low resolution
+static_assert(CL_PX == 2 * CL_NT, "two adjacent pixels per thread in the apply pass");
+static_assert(CL_PX % 64 == 0 && CL_LPX <= 64, "a wave sums a pair over the tile");
+
+__host__ __device__ inline int cl_moment_lds_doubles(int C) { return CL_SCRATCH + (C + 2) * (CL_PX + CL_LPX) + CL_MAX_SUMS; }
+__host__ __device__ inline int cl_apply_lds_doubles(int C) { return CL_SCRATCH + C * CL_PX + CL_BH * CL_BW; }
+
+__device__ __forceinline__ int cl_mod(int i, int n) {
+    i %= n;
+    return i < 0 ? i + n : i;
+}
+
+// the 12 products of an interpolated sample: src[0], src[stride], ... are the inserted samples at offsets -11, -9, ..., 11 from it
+__device__ __forceinline__ double cl_fir(const double* src, int stride) {
+    constexpr double T[6] = {2 * 0.305334091185, -2 * 0.072698593239, 2 * 0.021809577942, -2 * 0.005192756653, 2 * 0.000807762146, -2 * 0.000060081482};
+    double a = 0.0, b = 0.0;      // two chains of six: a thread has one or two samples per pass, so the chain's latency is the pass's
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        a = fma(T[5 - j], src[j * stride], a);
+        b = fma(T[j], src[(j + 6) * stride], b);
+    }
+    return a + b;
+}
+
+// One axis of one level for `lines` lines of `nd` outputs: out[line * ol + d * os] from in[line * il + . * is].  By the tile geometry (origins
+// of the three grids at tile 4 k, level-1 2 k - 5, ms k - 8) output d of either level is a copy of input 5 + d / 2 when d is even and the
+// filter over inputs (d - 1) / 2 ... (d - 1) / 2 + 11 when d is odd.  Consecutive threads take consecutive addresses: along the line in the x passes, across
+// the lines (LINE_FAST) in the y passes, whose lines are a row stride apart -- 32 doubles in level 2: one LDS bank for every lane otherwise.
+template <bool LINE_FAST>
+__device__ __forceinline__ void cl_axis(const double* in, int il, int is, double* out, int ol, int os, int lines, int nd) {
+    const int n_odd = nd >> 1, n_even = nd - n_odd;
+    for (int i = threadIdx.x; i < lines * n_odd; i += CL_NT) {
+        const int line = LINE_FAST ? i % lines : i / n_odd, q = LINE_FAST ? i / lines : i - line * n_odd;
+        out[line * ol + (2 * q + 1) * os] = cl_fir(in + line * il + q * is, is);
+    }
+    for (int i = threadIdx.x; i < lines * n_even; i += CL_NT) {
+        const int line = LINE_FAST ? i % lines : i / n_even, q = LINE_FAST ? i / lines : i - line * n_even;
+        out[line * ol + 2 * q * os] = in[line * il + (5 + q) * is];
+    }
+}
+
+// the ms samples of one band the tile at (Y0, X0) depends on, CL_MLOADS per thread, into registers: a caller issues them for the NEXT band (or tile)
+// before it runs cl_up_band on the current one, so their latency passes under its four LDS passes
+__device__ __forceinline__ void cl_ms_load(const float* __restrict__ ms, int h, int w, int Y0, int X0, float (&v)[CL_MLOADS]) {
+    const int my0 = Y0 / 4 - 8, mx0 = X0 / 4 - 8;
+#pragma unroll
+    for (int u = 0; u < CL_MLOADS; ++u) {
+        const int i = threadIdx.x + u * CL_NT, r = i / CL_MC, c = i - r * CL_MC;
+        v[u] = 0.f;
+        if (i < CL_MR * CL_MC) v[u] = ms[(long)cl_mod(my0 + r, h) * w + cl_mod(mx0 + c, w)];
+    }
+}
+
+// u of one band for a tile from its loaded ms samples -> U[16][32].  S: CL_SCRATCH doubles.  Ends WITHOUT a barrier: the caller puts one in front of
+// its reads of U.  A following call may start at once: its first writes go to M, which was last read three barriers ago.
+__device__ __forceinline__ void cl_up_band(const float (&v)[CL_MLOADS], double* S, double* U) {
+    double* M = S;
+    double* R1 = M + CL_MR * CL_MC;
+    double* L1 = R1 + CL_MR * CL_L1C;
+    double* R2 = L1 + CL_L1R * CL_L1C;
+#pragma unroll
+    for (int u = 0; u < CL_MLOADS; ++u) {
+        const int i = threadIdx.x + u * CL_NT;
+        if (i < CL_MR * CL_MC) M[i] = (double)v[u];
+    }
+    __syncthreads();
+    cl_axis<false>(M, CL_MC, 1, R1, CL_L1C, 1, CL_MR, CL_L1C);          // level 1 along x: 20 lines of 27
+    __syncthreads();
+    cl_axis<true>(R1, 1, CL_L1C, L1, 1, CL_L1C, CL_L1C, CL_L1R);       // level 1 along y: 27 lines of 19
+    __syncthreads();
+    cl_axis<false>(L1, CL_L1C, 1, R2, CL_TW, 1, CL_L1R, CL_TW);         // level 2 along x: 19 lines of 32
+    __syncthreads();
+    cl_axis<true>(R2, 1, CL_TW, U, 1, CL_TW, CL_TW, CL_TH);            // level 2 along y: 32 lines of 16
+}
+
+__global__ __launch_bounds__(CL_NT) void k_cl_interp(const float* __restrict__ ms, float* __restrict__ out, int h, int w, int tiles_x) {
+    extern __shared__ double cl_lds[];
+    double* U = cl_lds + CL_SCRATCH;
+    const int H4 = 4 * h, W4 = 4 * w;
+    const int Y0 = (blockIdx.x / tiles_x) * CL_TH, X0 = (blockIdx.x % tiles_x) * CL_TW;
+    const long plane = (long)blockIdx.z * gridDim.y + blockIdx.y;
+    float v[CL_MLOADS];
+    cl_ms_load(ms + plane * ((long)h * w), h, w, Y0, X0, v);
+    cl_up_band(v, cl_lds, U);
+    __syncthreads();
+    const int p = 2 * threadIdx.x, y = Y0 + p / CL_TW, x = X0 + p % CL_TW;
+    if (y < H4 && x < W4)      // W4 is a multiple of 4 and x is even: both pixels or none
+        *reinterpret_cast<float2*>(out + plane * ((long)H4 * W4) + (long)y * W4 + x) = make_float2((float)U[p], (float)U[p + 1]);
+}
+
+// entry e of the sum list: vectors a and b, of the high- (lo = 0) or the low-resolution table
+__device__ __forceinline__ int cl_pair(int a, int b, int lo) { return a | (b << 8) | (lo << 16); }
+
+// part [B][gx][ns].  SFIM (ns = 2 C + 2): sum u_k, sum u_k^2 per band, then sum pc, sum pc^2 with pc = PAN - pivot.  GSA (ns = (C + 2)(C + 3)):
+// all pairs a <= b of the vectors [mask, u_0 .. u_C-1, pc] in row-major order of the upper triangle, then the same of [mask, ms_0 .. ms_C-1, q]
+// over the low-resolution pixels, q = the mean of pc over the 2 x 2 centre of the 4 x 4 block.
+__global__ __launch_bounds__(CL_NT) void k_cl_moments(const float* __restrict__ ms, const float* __restrict__ pan, double* __restrict__ part, int C,
+                                                      int h, int w, int tiles_x, int tiles, int gsa) {
+    extern __shared__ double cl_lds[];
+    __shared__ int pairs[CL_MAX_SUMS];
+    const int n = C + 2, tid = threadIdx.x, gx = gridDim.x;
+    double* Vhi = cl_lds + CL_SCRATCH;           // [n][512]: mask, u, pc
+    double* Vlo = Vhi + n * CL_PX;               // [n][32]: mask, ms, q
+    double* acc = Vlo + n * CL_LPX;              // [ns]
+    const int ns = gsa ? n * (n + 1) : 2 * C + 2;
+    const int H4 = 4 * h, W4 = 4 * w;
+    const long b = blockIdx.y;
+    const float* __restrict__ ms_b = ms + b * C * ((long)h * w);
+    const float* __restrict__ pan_b = pan + b * ((long)H4 * W4);
+    const double pv = (double)pan_b[0];
+    if (tid == 0) {
+        int e = 0;
+        if (gsa) {
+            for (int lo = 0; lo < 2; ++lo)
+                for (int a = 0; a < n; ++a)
+                    for (int c = a; c < n; ++c) pairs[e++] = cl_pair(a, c, lo);
+        } else {
+            for (int k = 0; k < C; ++k) {
+                pairs[e++] = cl_pair(0, k + 1, 0);
+                pairs[e++] = cl_pair(k + 1, k + 1, 0);
+            }
+            pairs[e++] = cl_pair(0, C + 1, 0);
+            pairs[e++] = cl_pair(C + 1, C + 1, 0);
+        }
+    }
+    for (int e = tid; e < ns; e += CL_NT) acc[e] = 0.0;
+    // (the barriers inside cl_up_band order both before their first use)
+    float v[CL_MLOADS], vn[CL_MLOADS] = {};
+    cl_ms_load(ms_b, h, w, (blockIdx.x / tiles_x) * CL_TH, (blockIdx.x % tiles_x) * CL_TW, v);
+    for (int t = blockIdx.x; t < tiles; t += gx) {
+        const int Y0 = (t / tiles_x) * CL_TH, X0 = (t % tiles_x) * CL_TW;
+        for (int k = 0; k < C; ++k) {
+            if (k + 1 < C)
+                cl_ms_load(ms_b + (k + 1) * ((long)h * w), h, w, Y0, X0, vn);
+            else if (t + gx < tiles)
+                cl_ms_load(ms_b, h, w, ((t + gx) / tiles_x) * CL_TH, ((t + gx) % tiles_x) * CL_TW, vn);
+            cl_up_band(v, cl_lds, Vhi + (k + 1) * CL_PX);
+#pragma unroll
+            for (int u = 0; u < CL_MLOADS; ++u) v[u] = vn[u];
+            if (gsa && tid < CL_LPX) {
+                const int gi = Y0 / 4 + tid / CL_LC, gj = X0 / 4 + tid % CL_LC;
+                Vlo[(k + 1) * CL_LPX + tid] = (gi < h && gj < w) ? (double)ms_b[k * ((long)h * w) + (long)gi * w + gj] : 0.0;
+            }
+        }
+        for (int p = tid; p < CL_PX; p += CL_NT) {
+            const int y = Y0 + p / CL_TW, x = X0 + p % CL_TW;
+            const bool in = y < H4 && x < W4;
+            Vhi[p] = in ? 1.0 : 0.0;
+            Vhi[(C + 1) * CL_PX + p] = in ? (double)pan_b[(long)y * W4 + x] - pv : 0.0;
+        }
+        __syncthreads();
+        for (int i = tid; i < C * CL_PX; i += CL_NT) Vhi[CL_PX + i] *= Vhi[i % CL_PX];      // what a ragged tile holds outside the image counts as 0
+        if (gsa && tid < CL_LPX) {
+            const int i = tid / CL_LC, j = tid % CL_LC;
+            const bool in = Y0 / 4 + i < h && X0 / 4 + j < w;
+            const double* P = Vhi + (C + 1) * CL_PX + (4 * i + 1) * CL_TW + 4 * j + 1;
+            Vlo[tid] = in ? 1.0 : 0.0;
+            Vlo[(C + 1) * CL_LPX + tid] = in ? 0.25 * ((P[0] + P[1]) + (P[CL_TW] + P[CL_TW + 1])) : 0.0;
+        }
+        __syncthreads();
+        const int lane = tid & 63;
+        for (int e = tid >> 6; e < ns; e += CL_NT / 64) {
+            const int pr = pairs[e], a = pr & 255, c = (pr >> 8) & 255;
+            double v = 0.0;
+            if (pr >> 16) {
+                if (lane < CL_LPX) v = Vlo[a * CL_LPX + lane] * Vlo[c * CL_LPX + lane];
+            } else {
+#pragma unroll
+                for (int u = 0; u < CL_PX / 64; ++u) v = fma(Vhi[a * CL_PX + lane + 64 * u], Vhi[c * CL_PX + lane + 64 * u], v);
+            }
+            v = wave_sum(v);
+            if (lane == 0) acc[e] += v;
+        }
+        __syncthreads();      // the next tile overwrites the vectors
+    }
+    for (int e = tid; e < ns; e += CL_NT) part[(b * gx + blockIdx.x) * ns + e] = acc[e];
+}
+
+// coef [B][3 C + 1]: mean of pc; mean u_k; SFIM's scale a_k or GSA's alpha_k; GSA's gain g_k (SFIM: unused).  stats: NULL or [B][2 C + 1].
+__global__ __launch_bounds__(CL_NT) void k_cl_finish(const double* __restrict__ part, double* __restrict__ coef, double* __restrict__ stats, int C,
+                                                     int gx, double N, double nl, int gsa) {
+    __shared__ double sums[CL_MAX_SUMS];
+    __shared__ double Lm[CL_MAX_C * CL_MAX_C], mu[CL_MAX_C], mm[CL_MAX_C], al[CL_MAX_C], v[CL_MAX_C];
+    const int n = C + 2, np = n * (n + 1) / 2, ns = gsa ? 2 * np : 2 * C + 2;
+    const long b = blockIdx.x;
+    for (int e = threadIdx.x; e < ns; e += CL_NT) {
+        const double* __restrict__ pe = part + b * gx * ns + e;
+        double s = 0.0;
+        int j = 0;
+        for (; j + 8 <= gx; j += 8) {      // eight loads in flight, added in ascending order
+            double q[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) q[u] = pe[(long)(j + u) * ns];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) s += q[u];
+        }
+        for (; j < gx; ++j) s += pe[(long)j * ns];
+        sums[e] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double* co = coef + b * (3 * C + 1);
+    if (!gsa) {
+        const double sp = sums[2 * C], var_p = (sums[2 * C + 1] - sp * sp / N) / (N - 1.0);
+        co[0] = sp / N;
+        for (int k = 0; k < C; ++k) {
+            const double su = sums[2 * k], var_u = (sums[2 * k + 1] - su * su / N) / (N - 1.0);
+            co[1 + k] = su / N;
+            co[1 + C + k] = var_p > 0.0 ? sqrt(fmax(var_u, 0.0) / var_p) : 0.0;
+            co[1 + 2 * C + k] = 0.0;
+        }
+        return;
+    }
+    auto at = [&](int lo, int a, int c) { return sums[lo * np + a * n - a * (a - 1) / 2 + (c - a)]; };      // a <= c
+    const double mpc = at(0, 0, C + 1) / N, mq = at(1, 0, C + 1) / nl;
+    for (int k = 0; k < C; ++k) {
+        mu[k] = at(0, 0, k + 1) / N;
+        mm[k] = at(1, 0, k + 1) / nl;
+    }
+    // Sigma_ms alpha = cov(ms, q) by Cholesky, the lower triangle in Lm
+    bool ok = true;
+    for (int k = 0; k < C; ++k)
+        for (int l = 0; l <= k; ++l) Lm[k * C + l] = at(1, l + 1, k + 1) / nl - mm[k] * mm[l];
+    for (int j = 0; j < C && ok; ++j) {
+        double d = Lm[j * C + j];
+        for (int p = 0; p < j; ++p) d -= Lm[j * C + p] * Lm[j * C + p];
+        if (!(d > 0.0)) { ok = false; break; }
+        d = sqrt(d);
+        Lm[j * C + j] = d;
+        for (int i = j + 1; i < C; ++i) {
+            double s = Lm[i * C + j];
+            for (int p = 0; p < j; ++p) s -= Lm[i * C + p] * Lm[j * C + p];
+            Lm[i * C + j] = s / d;
+        }
+    }
+    if (ok) {
+        for (int i = 0; i < C; ++i) {
+            double s = at(1, i + 1, C + 1) / nl - mm[i] * mq;
+            for (int p = 0; p < i; ++p) s -= Lm[i * C + p] * al[p];
+            al[i] = s / Lm[i * C + i];
+        }
+        for (int i = C - 1; i >= 0; --i) {
+            double s = al[i];
+            for (int p = i + 1; p < C; ++p) s -= Lm[p * C + i] * al[p];
+            al[i] = s / Lm[i * C + i];
+        }
+        double den = 0.0;
+        for (int k = 0; k < C; ++k) {
+            double s = 0.0;
+            for (int l = 0; l < C; ++l) s += (at(0, (k < l ? k : l) + 1, (k < l ? l : k) + 1) / N - mu[k] * mu[l]) * al[l];
+            v[k] = s;
+            den += al[k] * s;
+        }
+        ok = den > 0.0;
+        for (int k = 0; k < C && ok; ++k) {
+            v[k] = N / (N - 1.0) * v[k] / den;
+            ok = v[k] - v[k] == 0.0 && al[k] - al[k] == 0.0;
+        }
+    }
+    co[0] = mpc;
+    for (int k = 0; k < C; ++k) {
+        co[1 + k] = mu[k];
+        co[1 + C + k] = ok ? al[k] : 0.0;
+        co[1 + 2 * C + k] = ok ? v[k] : 0.0;
+    }
+    if (stats) {
+        double* st = stats + b * (2 * C + 1);
+        for (int k = 0; k < C; ++k) {
+            st[k] = ok ? al[k] : 0.0;
+            st[C + 1 + k] = ok ? v[k] : 0.0;
+        }
+        st[C] = mq - mpc;      // the intercept: the mean of the low-resolution PAN (the other columns are centred)
+    }
+}
+
+__device__ __forceinline__ float cl_clip(double o) { return (float)fmin(fmax(o, 0.0), 1.0); }      // the one rounding to fp32
+
+template <bool GSA>
+__global__ __launch_bounds__(CL_NT) void k_cl_apply(const float* __restrict__ ms, const float* __restrict__ pan, float* __restrict__ out,
+                                                    const double* __restrict__ coef, int C, int h, int w, int tiles_x) {
+    extern __shared__ double cl_lds[];
+    double* U = cl_lds + CL_SCRATCH;             // [C][512]
+    double* PT = U + C * CL_PX;                  // SFIM: [20][36], staged pixel (r, c) = PAN pixel (Y0 - 2 + r, X0 - 2 + c) modulo the sides, minus the pivot
+    const int tid = threadIdx.x, H4 = 4 * h, W4 = 4 * w;
+    const int Y0 = (blockIdx.x / tiles_x) * CL_TH, X0 = (blockIdx.x % tiles_x) * CL_TW;
+    const long b = blockIdx.y;
+    const float* __restrict__ ms_b = ms + b * C * ((long)h * w);
+    const float* __restrict__ pan_b = pan + b * ((long)H4 * W4);
+    float* __restrict__ out_b = out + b * C * ((long)H4 * W4);
+    const double* __restrict__ co = coef + b * (3 * C + 1);
+    const double pv = (double)pan_b[0];
+    float v[CL_MLOADS], vn[CL_MLOADS] = {};
+    cl_ms_load(ms_b, h, w, Y0, X0, v);
+    for (int k = 0; k < C; ++k) {
+        if (k + 1 < C) cl_ms_load(ms_b + (k + 1) * ((long)h * w), h, w, Y0, X0, vn);
+        cl_up_band(v, cl_lds, U + k * CL_PX);
+#pragma unroll
+        for (int u = 0; u < CL_MLOADS; ++u) v[u] = vn[u];
+    }
+    if (!GSA)
+        for (int i = tid; i < CL_BH * CL_BW; i += CL_NT) {
+            const int r = i / CL_BW, c = i - r * CL_BW;
+            PT[i] = (double)pan_b[(long)cl_mod(Y0 - CL_BOX / 2 + r, H4) * W4 + cl_mod(X0 - CL_BOX / 2 + c, W4)] - pv;
+        }
+    __syncthreads();
+    const int p = 2 * tid, oy = p / CL_TW, ox = p % CL_TW, y = Y0 + oy, x = X0 + ox;
+    if (y >= H4 || x >= W4) return;              // W4 is a multiple of 4 and x is even: both pixels or none
+    const long o = (long)y * W4 + x;
+    const double mpc = co[0];
+    if (GSA) {
+        const float2 pp = *reinterpret_cast<const float2*>(pan_b + o);
+        double d0 = ((double)pp.x - pv) - mpc, d1 = ((double)pp.y - pv) - mpc;      // p~ - I0
+        for (int k = 0; k < C; ++k) {
+            const double a = co[1 + C + k], m = co[1 + k];
+            d0 -= a * (U[k * CL_PX + p] - m);
+            d1 -= a * (U[k * CL_PX + p + 1] - m);
+        }
+        for (int k = 0; k < C; ++k) {
+            const double g = co[1 + 2 * C + k];
+            *reinterpret_cast<float2*>(out_b + k * ((long)H4 * W4) + o) =
+                make_float2(cl_clip(fma(g, d0, U[k * CL_PX + p])), cl_clip(fma(g, d1, U[k * CL_PX + p + 1])));
+        }
+    } else {
+        const double* q = PT + oy * CL_BW + ox;
+        double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+        for (int dy = 0; dy < CL_BOX; ++dy) {
+            double r[CL_BOX + 1];
+#pragma unroll
+            for (int dx = 0; dx < CL_BOX + 1; ++dx) r[dx] = q[dy * CL_BW + dx];
+#pragma unroll
+            for (int dx = 0; dx < CL_BOX; ++dx) {
+                s0 += r[dx];
+                s1 += r[dx + 1];
+            }
+        }
+        const double c0 = q[2 * CL_BW + 2] - mpc, c1 = q[2 * CL_BW + 3] - mpc;
+        const double b0 = s0 / (CL_BOX * CL_BOX) - mpc, b1 = s1 / (CL_BOX * CL_BOX) - mpc;
+        for (int k = 0; k < C; ++k) {
+            const double a = co[1 + C + k], m = co[1 + k];
+            const double o0 = U[k * CL_PX + p] * fma(a, c0, m) / (fma(a, b0, m) + 1e-8);
+            const double o1 = U[k * CL_PX + p + 1] * fma(a, c1, m) / (fma(a, b1, m) + 1e-8);
+            *reinterpret_cast<float2*>(out_b + k * ((long)H4 * W4) + o) = make_float2(cl_clip(o0), cl_clip(o1));
+        }
+    }
+}
+
+struct ClGeom {
+    int tiles_x, tiles, gx, ns;
+    size_t off[2], bytes;      // part, coef
+};
+
+// false: not a shape the calls take (the reason, naming the argument, is in lg_last_error)
+bool cl_geom(const char* who, int B, int C, int h, int w, int method, ClGeom& g) {
+    if (B < 1 || B > 65535) { lg_set_error("%s: B must be 1..65535 (got %d)", who, B); return false; }
+    if (C < 2 || C > CL_MAX_C) { lg_set_error("%s: C must be 2..%d (got %d)", who, CL_MAX_C, C); return false; }
+    if (h < 4 || h > 4096) { lg_set_error("%s: h must be 4..4096 (got %d)", who, h); return false; }
+    if (w < 4 || w > 4096) { lg_set_error("%s: w must be 4..4096 (got %d)", who, w); return false; }
+    if (method != LG_CLASSICAL_SFIM && method != LG_CLASSICAL_GSA) { lg_set_error("%s: method must be LG_CLASSICAL_SFIM or LG_CLASSICAL_GSA (got %d)", who, method); return false; }
+    g.tiles_x = (4 * w + CL_TW - 1) / CL_TW;
+    g.tiles = g.tiles_x * ((4 * h + CL_TH - 1) / CL_TH);
+    // the moments pass: at most as many workgroups per sample as are resident at once (768 at C = 4, 512 at C = 8, 256 at C = 16): a second,
+    // partial round of workgroups would leave most of the chip idle for as long as the first took
+    const int resident = CL_CUS * (CL_CU_LDS / (cl_moment_lds_doubles(C) * (int)sizeof(double) + CL_MAX_SUMS * (int)sizeof(int)));
+    g.gx = g.tiles < resident ? g.tiles : resident;
+    g.ns = method == LG_CLASSICAL_GSA ? (C + 2) * (C + 3) : 2 * C + 2;
+    const size_t sz[2] = {(size_t)B * g.gx * g.ns * sizeof(double), (size_t)B * (3 * C + 1) * sizeof(double)};
+    g.bytes = ws_layout(2, sz, g.off);
+    return true;
+}
+
+DeviceOnce cl_attr_once;
+int cl_lds_attr(const char* who) {
+    if (!cl_attr_once.need()) return 0;
+    if (int rc = lds_attr_set(who, cl_moment_lds_doubles(CL_MAX_C) * (int)sizeof(double), k_cl_moments)) return rc;
+    if (int rc = lds_attr_set(who, cl_apply_lds_doubles(CL_MAX_C) * (int)sizeof(double), k_cl_apply<false>, k_cl_apply<true>)) return rc;
+    cl_attr_once.done();
+    return 0;
+}
+
+int cl_fuse(const char* who, int method, const float* ms, const float* pan, float* out, double* stats, int B, int C, int h, int w, void* workspace,
+            size_t workspace_bytes, hipStream_t s) {
+    ClGeom g;
+    if (!cl_geom(who, B, C, h, w, method, g)) return -1;
+    if (!check_tensors(who, {{"ms", ms}, {"pan", pan}, {"out", out}})) return -1;
+    if ((uintptr_t)stats & 7) { lg_set_error("%s: stats must be 8-byte aligned", who); return -1; }
+    if (!check_workspace(who, workspace, workspace_bytes, g.bytes, "lg_classical_workspace_bytes")) return -1;
+    if (int rc = cl_lds_attr(who)) return rc;
+    const int gsa = method == LG_CLASSICAL_GSA;
+    double* part = (double*)((char*)workspace + g.off[0]);
+    double* coef = (double*)((char*)workspace + g.off[1]);
+    k_cl_moments<<<dim3(g.gx, B), CL_NT, cl_moment_lds_doubles(C) * sizeof(double), s>>>(ms, pan, part, C, h, w, g.tiles_x, g.tiles, gsa);
+    LG_CHECK_LAUNCH();
+    k_cl_finish<<<B, CL_NT, 0, s>>>(part, coef, stats, C, g.gx, 16.0 * h * w, (double)h * w, gsa);
+    LG_CHECK_LAUNCH();
+    const size_t lds = cl_apply_lds_doubles(C) * sizeof(double);
+    if (gsa)
+        k_cl_apply<true><<<dim3(g.tiles, B), CL_NT, lds, s>>>(ms, pan, out, coef, C, h, w, g.tiles_x);
+    else
+        k_cl_apply<false><<<dim3(g.tiles, B), CL_NT, lds, s>>>(ms, pan, out, coef, C, h, w, g.tiles_x);
+    LG_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // namespace
+
+size_t classical_workspace_bytes(int B, int C, int h, int w, int method) {
+    ClGeom g;
+    return cl_geom("classical_workspace_bytes", B, C, h, w, method, g) ? g.bytes : 0;
+}
+
+int launch_interp23_up4(const float* ms, float* out, int B, int C, int h, int w, hipStream_t s) {
+    static const char* who = "interp23_up4";
+    ClGeom g;
+    if (!cl_geom(who, B, C, h, w, LG_CLASSICAL_SFIM, g)) return -1;
+    if (!check_tensors(who, {{"ms", ms}, {"out", out}})) return -1;
+    k_cl_interp<<<dim3(g.tiles, C, B), CL_NT, (CL_SCRATCH + CL_PX) * sizeof(double), s>>>(ms, out, h, w, g.tiles_x);
+    LG_CHECK_LAUNCH();
+    return 0;
+}
+
+int launch_sfim(const float* ms, const float* pan, float* out, int B, int C, int h, int w, void* workspace, size_t workspace_bytes, hipStream_t s) {
+    return cl_fuse("sfim", LG_CLASSICAL_SFIM, ms, pan, out, nullptr, B, C, h, w, workspace, workspace_bytes, s);
+}
+
+int launch_gsa(const float* ms, const float* pan, float* out, double* stats, int B, int C, int h, int w, void* workspace, size_t workspace_bytes,
+               hipStream_t s) {
+    return cl_fuse("gsa", LG_CLASSICAL_GSA, ms, pan, out, stats, B, C, h, w, workspace, workspace_bytes, s);
+}

@@ -47,6 +47,13 @@ int launch_sam_loss(const float* out, const float* gt, float* dout, float* loss_
 int launch_ssim_loss(const float* out, const float* gt, float* dout, float* loss_accum, int B, int64_t B_global, int C, int H, int W, float scale,
                      float data_range, int accumulate, void* workspace, size_t workspace_bytes, hipStream_t s);
 
+// ---------------- the classical baselines: interp23 x4, SFIM, GSA (k_classical.hip; arguments validated before any HIP call) ----------------
+size_t classical_workspace_bytes(int B, int C, int h, int w, int method);
+int launch_interp23_up4(const float* ms, float* out, int B, int C, int h, int w, hipStream_t s);
+int launch_sfim(const float* ms, const float* pan, float* out, int B, int C, int h, int w, void* workspace, size_t workspace_bytes, hipStream_t s);
+int launch_gsa(const float* ms, const float* pan, float* out, double* stats, int B, int C, int h, int w, void* workspace, size_t workspace_bytes,
+               hipStream_t s);
+
 // ---------------- data module (reference models/unlg_former.py:29-37,58-61) ----------------
 struct DwArgs {
     const float* in;    // [planes, hi, wi]

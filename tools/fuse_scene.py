@@ -1,8 +1,12 @@
-"""Pan-sharpen one scene of any size with a trained network: reads PREFIX_lr.tif (MS, [h,w,C]) and PREFIX_pan.tif ([4h,4w]) with
+"""Pan-sharpen one scene of any size with a trained network or with a classical method: reads PREFIX_lr.tif (MS, [h,w,C]) and PREFIX_pan.tif ([4h,4w]) with
 dataset.read_tiff, fuses them tile by tile on the GPU (lgteun_amd/scene.py) and writes PREFIX_mul_hat.tif.
 
     python tools/fuse_scene.py PREFIX --checkpoint model.state.pth [--tile 128] [--overlap 32] [--bit-depth 11] [--norm-input]
                                [--batch B] [--float] [--out FILE]
+    python tools/fuse_scene.py PREFIX --method gsa|sfim [--bit-depth 11] [--norm-input] [--float] [--out FILE]
+
+--method gsa / sfim (lgteun_amd/classical.py) needs no checkpoint and no tiles: the whole scene is fused in one call, with the same
+normalisation and the same conversion to digital numbers.
 
 The checkpoint is a plain-tensor file ({'core_module': state_dict}, what Base_model.save writes and tools/convert_checkpoint.py makes of a
 reference-era file); the band count and the stage count are read from it.  The output holds uint16 digital numbers
@@ -34,7 +38,8 @@ def load_module(path, device='cuda:0'):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('prefix')
-    ap.add_argument('--checkpoint', required=True)
+    ap.add_argument('--method', choices=['network', 'gsa', 'sfim'], default='network')
+    ap.add_argument('--checkpoint', default=None, help='required for --method network')
     ap.add_argument('--tile', type=int, nargs='+', default=[128], help='one side, or height and width')
     ap.add_argument('--overlap', type=int, default=32)
     ap.add_argument('--batch', type=int, default=None)
@@ -45,15 +50,22 @@ def main():
     a = ap.parse_args()
     if len(a.tile) > 2:
         ap.error('--tile takes one or two values')
+    if a.method == 'network' and not a.checkpoint:
+        ap.error('--method network needs --checkpoint')
     tile = a.tile[0] if len(a.tile) == 1 else tuple(a.tile)
     ms, pan = read_tiff(f'{a.prefix}_lr.tif'), read_tiff(f'{a.prefix}_pan.tif')
     if ms.ndim != 3 or pan.ndim != 2:
         sys.exit(f'{a.prefix}: expected MS [h,w,C] and PAN [4h,4w], got {ms.shape} / {pan.shape}')
     if ms.dtype != pan.dtype or ms.dtype.name not in ('uint8', 'uint16'):
         ms, pan = ms.astype(np.float64).astype(np.float32), pan.astype(np.float64).astype(np.float32)      # like PSDataset
-    net = load_module(a.checkpoint)
-    fused = net.fuse_scene(np.ascontiguousarray(ms.transpose(2, 0, 1)), pan[np.newaxis], tile=tile, overlap=a.overlap, batch=a.batch,
-                           bit_depth=a.bit_depth, norm_input=a.norm_input, out_dtype='float32' if a.float else 'uint16')
+    ms_chw = np.ascontiguousarray(ms.transpose(2, 0, 1))
+    if a.method != 'network':
+        from lgteun_amd import classical
+        fused = classical.fuse_scene(a.method, ms_chw, pan[np.newaxis], bit_depth=a.bit_depth, norm_input=a.norm_input,
+                                     out_dtype='float32' if a.float else 'uint16')
+    else:
+        fused = load_module(a.checkpoint).fuse_scene(ms_chw, pan[np.newaxis], tile=tile, overlap=a.overlap, batch=a.batch, bit_depth=a.bit_depth,
+                                                      norm_input=a.norm_input, out_dtype='float32' if a.float else 'uint16')
     out = a.out or f'{a.prefix}_mul_hat.tif'
     write_tiff(out, fused.permute(1, 2, 0).contiguous().cpu().numpy())
     print(f'{out}: {tuple(fused.shape)} {fused.dtype}')

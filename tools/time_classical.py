@@ -1,0 +1,66 @@
+"""What the classical baselines cost on the GPU (lgteun_amd/classical.py): ms per call of `sfim` and `gsa` with the call synchronised, the
+median of 20 runs after 5 warm-up runs, at C = 4 and C = 8 with PAN 128 x 128 (batch 1 and batch 32) and for one 4096 x 4096 scene of C = 4.
+Beside each: the bytes the passes must move (the moments pass reads ms and pan, the apply pass reads them again and writes the output)
+divided by the time, as a fraction of the HBM bandwidth (--hbm-gbs, default 8000: the MI355X's 8 TB/s), and the ms per image of the float64
+numpy restatement (tests/classical_ref.py) on the same box (--no-host skips it).  Prints one JSON line.   python tools/time_classical.py"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, R)
+sys.path.insert(0, os.path.join(R, 'tests'))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import classical_ref as cr  # noqa: E402
+from lgteun_amd import classical  # noqa: E402
+
+CASES = [(1, 4, 32, 32), (32, 4, 32, 32), (1, 8, 32, 32), (32, 8, 32, 32), (1, 4, 1024, 1024)]      # B, C, h, w
+
+
+def median_ms(fn, warmup, runs):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(runs):
+        t = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t) * 1e3)
+    return statistics.median(ts)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--runs', type=int, default=20)
+    ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--hbm-gbs', type=float, default=8000.0)
+    ap.add_argument('--no-host', action='store_true')
+    a = ap.parse_args()
+    res = {}
+    for B, C, h, w in CASES:
+        ms_np, pan_np = cr.make_scene(C, h, w, seed=1)
+        ms = torch.from_numpy(ms_np).cuda()[None].repeat(B, 1, 1, 1)
+        pan = torch.from_numpy(pan_np).cuda()[None, None].repeat(B, 1, 1, 1)
+        moved = 4 * B * (2 * (C * h * w + 16 * h * w) + C * 16 * h * w)
+        row = dict(bytes_moved=moved)
+        for name, fn, host in (('sfim', classical.sfim, cr.sfim), ('gsa', classical.gsa, cr.gsa)):
+            ms_call = median_ms(lambda: fn(ms, pan), a.warmup, a.runs)
+            row[name] = dict(ms_per_call=round(ms_call, 4), ms_per_image=round(ms_call / B, 4), gb_per_s=round(moved / ms_call / 1e6, 1),
+                             hbm_fraction=round(moved / ms_call / 1e6 / a.hbm_gbs, 4))
+            if not a.no_host:
+                t = time.perf_counter()
+                host(ms_np, pan_np)
+                row[name]['numpy_ms_per_image'] = round((time.perf_counter() - t) * 1e3, 2)
+        res[f'B{B}_C{C}_pan{4 * h}x{4 * w}'] = row
+    print(json.dumps({'tool': 'time_classical', 'device': torch.cuda.get_device_name(0), 'runs': a.runs, 'warmup': a.warmup,
+                      'hbm_gbs': a.hbm_gbs, 'unit': 'ms per call, synchronised, median', 'cases': res}))
+
+
+if __name__ == '__main__':
+    main()
