@@ -4,7 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <atomic>
-#include "../../include/lgteun_hip.h"
+#include "abi.h"
 #include "route.h"
 
 // ----------------------------------------------------------------------------------------------
@@ -95,7 +95,7 @@ static inline uint64_t mix_seed(uint64_t seed, int stage, int blk) {
 
 #define LG_EPS 1e-5f
 
-// live per-kernel timing (api.hip): RAII scope used at the top of a launcher
+// live per-kernel timing (prof.hip): RAII scope used at the top of a launcher
 // units: how many stage-sized launches this one stands for (a launch over the samples of S stages records S: lg_prof_read's count, and with it the
 // time per launch a caller derives, stay those of one stage's launch)
 void lg_prof_begin(int kid, hipStream_t s);

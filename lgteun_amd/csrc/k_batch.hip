@@ -14,8 +14,8 @@
 //                        origins and scene widths, every other chunk goes the scalar way.
 //   k_window_pyr<T>      input_pan_l of those windows: pyr_tile, the arithmetic of k_pyr_down2, reflecting at the WINDOW's border, written
 //                        flipped and scaled like k_batch_assemble writes the stored pan_l.
+#include "abi.h"
 #include "common.h"
-#include "kernels.h"
 #include "sample_io.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -95,10 +95,11 @@ static const char* pyr_check(const void* pan, const float* pan_l, int64_t planes
     return nullptr;
 }
 
-int launch_pyr_down2(const void* pan, float* pan_l, int64_t planes, int H, int W, int dtype, hipStream_t s) {
+extern "C" int lg_pyr_down2(const void* pan, float* pan_l, int64_t planes, int32_t H, int32_t W, int32_t dtype, void* stream) {
     if (const char* why = pyr_check(pan, pan_l, planes, H, W, dtype)) { lg_set_error("pyr_down2: %s", why); return -1; }
     const int tiles_x = (W / 4 + PYR_T - 1) / PYR_T, tiles = tiles_x * ((H / 4 + PYR_T - 1) / PYR_T);
     const unsigned grid = (unsigned)(planes * tiles);
+    const hipStream_t s = (hipStream_t)stream;
     if (dtype == LG_DT_U8) k_pyr_down2<uint8_t><<<grid, PYR_NT, 0, s>>>((const uint8_t*)pan, pan_l, H, W, tiles_x, tiles);
     else if (dtype == LG_DT_U16) k_pyr_down2<uint16_t><<<grid, PYR_NT, 0, s>>>((const uint16_t*)pan, pan_l, H, W, tiles_x, tiles);
     else k_pyr_down2<float><<<grid, PYR_NT, 0, s>>>((const float*)pan, pan_l, H, W, tiles_x, tiles);
@@ -200,9 +201,9 @@ static void ba_launch(const BatchArgs& a, int B, hipStream_t s) {
     k_batch_assemble<T><<<dim3((total + BA_NT - 1) / BA_NT, B), BA_NT, 0, s>>>(a, cprW, cprw, cprp, n_pan, n_mul, n_lr, n_pl);
 }
 
-int launch_batch_assemble(const void* pan, const void* lr, const void* mul, const float* pan_l, int64_t N, const int32_t* idx, int64_t idx_offset,
-                          const uint32_t* flips, float* o_pan, float* o_lr, float* o_mul, float* o_pan_l, int B, int C, int H, int W, int h, int w,
-                          int dtype, float divisor, int n_div, float post_scale, hipStream_t s) {
+extern "C" int lg_batch_assemble(const void* pan, const void* lr, const void* mul, const float* pan_l, int64_t N, const int32_t* idx, int64_t idx_offset,
+                                 const uint32_t* flips, float* o_pan, float* o_lr, float* o_mul, float* o_pan_l, int32_t B, int32_t C, int32_t H, int32_t W,
+                                 int32_t h, int32_t w, int32_t dtype, float divisor, int32_t n_div, float post_scale, void* stream) {
     const char* why = nullptr;
     if (!pan || !lr || !pan_l || !idx || !o_pan || !o_lr || !o_pan_l || ((mul == nullptr) != (o_mul == nullptr))) why = "null pointer (mul and its output go together)";
     else if (B <= 0 || B > 65535) why = "B must be in 1 .. 65535";
@@ -223,6 +224,7 @@ int launch_batch_assemble(const void* pan, const void* lr, const void* mul, cons
     a.idx = idx + idx_offset; a.flips = flips;
     a.N = (int)N; a.C = C; a.H = H; a.W = W; a.h = h; a.w = w;
     a.sc.divisor = divisor; a.sc.post_scale = post_scale; a.sc.n_div = n_div; a.sc.has_scale = post_scale != 1.0f;
+    const hipStream_t s = (hipStream_t)stream;
     ProfScope prof(LG_K_BATCH, s);
     if (dtype == LG_DT_U8) ba_launch<uint8_t>(a, B, s);
     else if (dtype == LG_DT_U16) ba_launch<uint16_t>(a, B, s);
@@ -297,9 +299,9 @@ static void wa_launch(const WindowArgs& a, int B, hipStream_t s) {
     k_window_pyr<T><<<dim3(tiles_x * tiles_y, B), PYR_NT, 0, s>>>(a, tiles_x);
 }
 
-int launch_window_assemble(const void* pan, const void* lr, const void* mul, const int32_t* origins, int64_t n_windows, int64_t first,
-                           const uint32_t* flips, float* o_pan, float* o_lr, float* o_mul, float* o_pan_l, int B, int C, int Hs, int Ws, int P, int Q,
-                           int dtype, float divisor, int n_div, float post_scale, hipStream_t s) {
+extern "C" int lg_window_assemble(const void* pan, const void* lr, const void* mul, const int32_t* origins, int64_t n_windows, int64_t first,
+                                  const uint32_t* flips, float* o_pan, float* o_lr, float* o_mul, float* o_pan_l, int32_t B, int32_t C, int32_t Hs,
+                                  int32_t Ws, int32_t P, int32_t Q, int32_t dtype, float divisor, int32_t n_div, float post_scale, void* stream) {
     const char* why = nullptr;
     if (!pan || !lr || !origins || !o_pan || !o_lr || !o_pan_l || ((mul == nullptr) != (o_mul == nullptr))) why = "null pointer (mul and its output go together)";
     else if (B <= 0 || B > 65535) why = "B must be in 1 .. 65535";
@@ -322,6 +324,7 @@ int launch_window_assemble(const void* pan, const void* lr, const void* mul, con
     a.org = origins + 2 * first; a.flips = flips;
     a.C = C; a.Hs = Hs; a.Ws = Ws; a.P = P; a.Q = Q;
     a.sc.divisor = divisor; a.sc.post_scale = post_scale; a.sc.n_div = n_div; a.sc.has_scale = post_scale != 1.0f;
+    const hipStream_t s = (hipStream_t)stream;
     if (dtype == LG_DT_U8) wa_launch<uint8_t>(a, B, s);
     else if (dtype == LG_DT_U16) wa_launch<uint16_t>(a, B, s);
     else wa_launch<float>(a, B, s);

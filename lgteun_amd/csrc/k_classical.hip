@@ -23,8 +23,8 @@
 // any batch.  All indexing into tensors is 64-bit.
 #include <cmath>
 
+#include "abi.h"
 #include "common.h"
-#include "kernels.h"
 #include "reduce.h"
 
 namespace {
@@ -445,26 +445,27 @@ int cl_fuse(const char* who, int method, const float* ms, const float* pan, floa
 
 }  // namespace
 
-size_t classical_workspace_bytes(int B, int C, int h, int w, int method) {
+extern "C" size_t lg_classical_workspace_bytes(int32_t B, int32_t C, int32_t h, int32_t w, int32_t method) {
     ClGeom g;
     return cl_geom("classical_workspace_bytes", B, C, h, w, method, g) ? g.bytes : 0;
 }
 
-int launch_interp23_up4(const float* ms, float* out, int B, int C, int h, int w, hipStream_t s) {
+extern "C" int lg_interp23_up4(const float* ms, float* out, int32_t B, int32_t C, int32_t h, int32_t w, void* stream) {
     static const char* who = "interp23_up4";
     ClGeom g;
     if (!cl_geom(who, B, C, h, w, LG_CLASSICAL_SFIM, g)) return -1;
     if (!check_tensors(who, {{"ms", ms}, {"out", out}})) return -1;
-    k_cl_interp<<<dim3(g.tiles, C, B), CL_NT, (CL_SCRATCH + CL_PX) * sizeof(double), s>>>(ms, out, h, w, g.tiles_x);
+    k_cl_interp<<<dim3(g.tiles, C, B), CL_NT, (CL_SCRATCH + CL_PX) * sizeof(double), (hipStream_t)stream>>>(ms, out, h, w, g.tiles_x);
     LG_CHECK_LAUNCH();
     return 0;
 }
 
-int launch_sfim(const float* ms, const float* pan, float* out, int B, int C, int h, int w, void* workspace, size_t workspace_bytes, hipStream_t s) {
-    return cl_fuse("sfim", LG_CLASSICAL_SFIM, ms, pan, out, nullptr, B, C, h, w, workspace, workspace_bytes, s);
+extern "C" int lg_sfim(const float* ms, const float* pan, float* out, int32_t B, int32_t C, int32_t h, int32_t w, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    return cl_fuse("sfim", LG_CLASSICAL_SFIM, ms, pan, out, nullptr, B, C, h, w, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
-int launch_gsa(const float* ms, const float* pan, float* out, double* stats, int B, int C, int h, int w, void* workspace, size_t workspace_bytes,
-               hipStream_t s) {
-    return cl_fuse("gsa", LG_CLASSICAL_GSA, ms, pan, out, stats, B, C, h, w, workspace, workspace_bytes, s);
+extern "C" int lg_gsa(const float* ms, const float* pan, float* out, double* stats, int32_t B, int32_t C, int32_t h, int32_t w, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    return cl_fuse("gsa", LG_CLASSICAL_GSA, ms, pan, out, stats, B, C, h, w, workspace, workspace_bytes, (hipStream_t)stream);
 }

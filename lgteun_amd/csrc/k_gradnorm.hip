@@ -9,8 +9,8 @@
 //                      out[0] = (float)sqrt(sum), out[1] = min(1, max_norm / (out[0] + 1e-6)) in fp32.
 // No floating-point atomics anywhere, so the same call gives the same bits every time (the convention of reduce.h).  Scalar 4-byte
 // loads: a range may begin and end at any float offset, and nothing outside [begin, end) is read.
+#include "abi.h"
 #include "common.h"
-#include "kernels.h"
 #include "reduce.h"
 
 #define GN_NT 256      // block_sum4 and partials_sum are written for this
@@ -55,13 +55,13 @@ static int gn_grid_x(int64_t max_range) {
     return (int)(gx < 1 ? 1 : (gx > GN_MAX_GX ? GN_MAX_GX : gx));
 }
 
-size_t grad_norm_workspace_bytes(int n_ranges, int64_t max_range) {
+extern "C" size_t lg_grad_norm_workspace_bytes(int32_t n_ranges, int64_t max_range) {
     if (n_ranges <= 0 || n_ranges > 65535 || max_range <= 0) return 0;
     return (size_t)n_ranges * gn_grid_x(max_range) * sizeof(double);
 }
 
-int launch_grad_norm(const float* grads, const int64_t* ranges, int n_ranges, int64_t max_range, double max_norm, float* out, void* workspace,
-                     size_t workspace_bytes, hipStream_t s) {
+extern "C" int lg_grad_norm(const float* grads, const int64_t* ranges, int32_t n_ranges, int64_t max_range, double max_norm, float* out,
+                            void* workspace, size_t workspace_bytes, void* stream) {
     const char* why = nullptr;
     if (!grads || !ranges || !out || !workspace) why = "null pointer";
     else if (n_ranges <= 0 || n_ranges > 65535) why = "n_ranges must be in 1 .. 65535";
@@ -69,9 +69,10 @@ int launch_grad_norm(const float* grads, const int64_t* ranges, int n_ranges, in
     else if (!(max_norm > 0.0)) why = "max_norm must be positive";
     else if ((uintptr_t)workspace & 7) why = "the workspace must be 8-byte aligned";
     else if (((uintptr_t)grads | (uintptr_t)out) & 3) why = "grads and out must be 4-byte aligned";
-    else if (workspace_bytes < grad_norm_workspace_bytes(n_ranges, max_range)) why = "workspace too small (lg_grad_norm_workspace_bytes)";
+    else if (workspace_bytes < lg_grad_norm_workspace_bytes(n_ranges, max_range)) why = "workspace too small (lg_grad_norm_workspace_bytes)";
     if (why) { lg_set_error("grad_norm: %s", why); return -1; }
     const int gx = gn_grid_x(max_range);
+    const hipStream_t s = (hipStream_t)stream;
     k_gradnorm_part<<<dim3(gx, n_ranges), GN_NT, 0, s>>>(grads, ranges, (double*)workspace);
     LG_CHECK_LAUNCH();
     k_gradnorm_finish<<<1, GN_NT, 0, s>>>((const double*)workspace, gx * n_ranges, (float)max_norm, out);

@@ -16,8 +16,8 @@
 #include <float.h>
 #include <math.h>
 
+#include "abi.h"
 #include "common.h"
-#include "kernels.h"
 #include "reduce.h"
 
 // Inputs are scaled in fp32 and each product is rounded on its own before it is widened (the rounding of data_denormalize on the host
@@ -376,15 +376,16 @@ bool iqa_check_buffers(bool ptrs_ok, float scale, void* workspace, size_t worksp
 
 }  // namespace
 
-size_t iqa_workspace_bytes(int B, int C, int H, int W, int no_ref) {
+extern "C" size_t lg_iqa_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t no_ref) {
     IqaGeom g;
     return iqa_geom(B, C, H, W, no_ref, g) ? g.bytes : 0;
 }
 
-int launch_iqa_ref(const float* pred, const float* gt, double* out, int B, int C, int H, int W, float scale, void* workspace,
-                   size_t workspace_bytes, hipStream_t s) {
+extern "C" int lg_iqa_ref(const float* pred, const float* gt, double* out, int32_t B, int32_t C, int32_t H, int32_t W, float scale,
+                          void* workspace, size_t workspace_bytes, void* stream) {
     IqaGeom g;
     if (!iqa_geom(B, C, H, W, 0, g) || !iqa_check_buffers(pred && gt && out, scale, workspace, workspace_bytes, g)) return -1;
+    const hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
     double *pix = (double*)(ws + g.off[0]), *ssim = (double*)(ws + g.off[1]), *q = (double*)(ws + g.off[2]);
     const WinPlanes pl{pred, gt, nullptr, nullptr};
@@ -402,10 +403,11 @@ int launch_iqa_ref(const float* pred, const float* gt, double* out, int B, int C
     return 0;
 }
 
-int launch_iqa_no_ref(const float* pred, const float* pan, const float* ms, double* out, int B, int C, int H, int W, float scale,
-                      void* workspace, size_t workspace_bytes, hipStream_t s) {
+extern "C" int lg_iqa_no_ref(const float* pred, const float* pan, const float* ms, double* out, int32_t B, int32_t C, int32_t H, int32_t W,
+                             float scale, void* workspace, size_t workspace_bytes, void* stream) {
     IqaGeom g;
     if (!iqa_geom(B, C, H, W, 1, g) || !iqa_check_buffers(pred && pan && ms && out, scale, workspace, workspace_bytes, g)) return -1;
+    const hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
     double *rows = (double*)(ws + g.off[0]), *plr = (double*)(ws + g.off[1]), *qf = (double*)(ws + g.off[2]), *qm = (double*)(ws + g.off[3]);
     const int h = H / LG_IQA_RATIO, w = W / LG_IQA_RATIO, np = C * (C + 1) / 2;

@@ -3,8 +3,10 @@
 //  - LGT patch_embed, down, up+fusion, tail (reference models/common/LGT.py:64-88,280-281,294-295,302-303,337-342)
 // Activations inside an LGT are NHWC (one pixel = one contiguous channel vector); the data module works on
 // NCHW fp32 planes (C is 4 or 8).  One thread per pixel; weights are wave-uniform (scalar loads).
+#include "abi.h"
 #include "kernels.h"
 #include "resample_tile.h"
+#include "workspace.h"   // LG_MAX_K (lg_dropout_mask)
 
 // ------------------------------------------------------------------------------------------------
 // plain bicubic resample of planes (bmu.sampling_, basic_module_unformer_v2.py:21-23)
@@ -710,6 +712,21 @@ int launch_ln_split(int e, const float* x, const float* n1g, const float* n1b, f
     else if (e == 32) k_ln_split<32><<<grid, 256, 0, s>>>(x, n1g, n1b, g, HW, total);
     else if (e == 64) k_ln_split<64><<<grid, 256, 0, s>>>(x, n1g, n1b, g, HW, total);
     else { lg_set_error("ln_split: e=%d unsupported", e); return -1; }
+    LG_CHECK_LAUNCH();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the train-mode dropout mask, exported for the fp64 oracle
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_dropout_mask(uint64_t seed, long first, long n, float* __restrict__ out) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += gridDim.x * 256L) out[i] = dropout_scale(seed, (uint64_t)(first + i));
+}
+extern "C" int lg_dropout_mask(uint64_t seed, int32_t stage, int32_t blk, int64_t first, int64_t n, float* out, void* stream) {
+    if (!out || n < 0 || first < 0 || stage < 0 || stage >= LG_MAX_K || blk < 0 || blk > 4) { lg_set_error("dropout_mask: invalid argument"); return -1; }
+    if (n == 0) return 0;
+    const int grid = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
+    k_dropout_mask<<<grid, 256, 0, (hipStream_t)stream>>>(mix_seed(seed, stage, blk), first, n, out);
     LG_CHECK_LAUNCH();
     return 0;
 }

@@ -16,8 +16,8 @@
 //                     all-reduce, if any) and its sample's alpha_i, beta_ij, gamma_i from the stored derivatives, then streams the
 //                     sample: dout[i] = fl32(scale * (alpha_i + sum_j beta_ij x_j + gamma_i pan)), evaluated in fp64 and rounded once.
 // No floating-point atomics: the same call gives the same bits every time (the convention that reduce.h implements).
+#include "abi.h"
 #include "common.h"
-#include "kernels.h"
 #include "reduce.h"
 
 namespace {
@@ -314,13 +314,13 @@ bool qnr_geom(const char* who, int B, int C, int H, int W, QnrGeom& g) {
 
 }  // namespace
 
-size_t qnr_workspace_bytes(int B, int C, int H, int W) {
+extern "C" size_t lg_qnr_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W) {
     QnrGeom g;
     return qnr_geom("qnr_workspace_bytes", B, C, H, W, g) ? g.bytes : 0;
 }
 
-int launch_qnr_stats(const float* out, const float* pan, const float* ms, const float* pan_l, double* q, double* table, int B, int C, int H,
-                     int W, void* workspace, size_t workspace_bytes, hipStream_t s) {
+extern "C" int lg_qnr_stats(const float* out, const float* pan, const float* ms, const float* pan_l, double* q, double* table, int32_t B,
+                            int32_t C, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, void* stream) {
     static const char* who = "qnr_stats";
     QnrGeom g;
     if (!qnr_geom(who, B, C, H, W, g)) return -1;
@@ -331,6 +331,7 @@ int launch_qnr_stats(const float* out, const float* pan, const float* ms, const 
     char* ws = (char*)workspace;
     double *pf = (double*)(ws + g.off[0]), *pm = (double*)(ws + g.off[1]), *qd = (double*)(ws + g.off[2]);
     const dim3 grid(g.gf + g.gm, B);
+    const hipStream_t s = (hipStream_t)stream;
     if (C == 4) {
         k_qnr_moments<4><<<grid, QNR_NT, 0, s>>>(out, pan, ms, pan_l, g.HW, g.hw, g.gf, g.gm, pf, pm);
         LG_CHECK_LAUNCH();
@@ -346,9 +347,9 @@ int launch_qnr_stats(const float* out, const float* pan, const float* ms, const 
     return 0;
 }
 
-int launch_qnr_grad(const float* out, const float* pan, const double* table, float* dout, float* loss_accum, double* indices, int B,
-                    int64_t B_global, int C, int H, int W, float scale, int accumulate, const void* workspace, size_t workspace_bytes,
-                    hipStream_t s) {
+extern "C" int lg_qnr_grad(const float* out, const float* pan, const double* table, float* dout, float* loss_accum, double* indices, int32_t B,
+                           int64_t B_global, int32_t C, int32_t H, int32_t W, float scale, int32_t accumulate, const void* workspace,
+                           size_t workspace_bytes, void* stream) {
     static const char* who = "qnr_grad";
     QnrGeom g;
     if (!qnr_geom(who, B, C, H, W, g)) return -1;
@@ -359,6 +360,7 @@ int launch_qnr_grad(const float* out, const float* pan, const double* table, flo
     if (!check_workspace(who, workspace, workspace_bytes, g.bytes, "lg_qnr_workspace_bytes")) return -1;
     const double* qd = (const double*)((const char*)workspace + g.off[2]);
     const dim3 grid(g.gf, B);
+    const hipStream_t s = (hipStream_t)stream;
     if (C == 4)
         k_qnr_grad<4><<<grid, QNR_NT, 0, s>>>(out, pan, table, qd, dout, loss_accum, indices, B, (double)B_global, g.HW, g.gf, (double)scale, accumulate);
     else

@@ -20,8 +20,8 @@
 // depends on H and W only, so a sample's dout has the same bits alone and inside any batch.  k_l1 / k_l2 end in atomics, as their comments say.
 #include <cmath>
 
+#include "abi.h"
 #include "common.h"
-#include "kernels.h"
 #include "reduce.h"
 
 namespace {
@@ -335,10 +335,11 @@ __global__ __launch_bounds__(256) void k_l1(const float* __restrict__ out, const
     if (threadIdx.x == 0) atomicAdd(loss_accum, (sm[0] + sm[1] + sm[2] + sm[3]) * inv_n);
 }
 
-int launch_l1_loss(const float* out, const float* gt, float* dout, float* loss_accum, int64_t n_local, int64_t n_global, float scale, hipStream_t s) {
+extern "C" int lg_l1_loss(const float* out, const float* gt, float* dout, float* loss_accum, int64_t n_local, int64_t n_global, float scale,
+                          void* stream) {
     const int grid = rl_flat_grid("l1_loss", out, gt, dout, loss_accum, n_local, n_global);
     if (!grid) return -1;
-    k_l1<<<grid, 256, 0, s>>>(out, gt, dout, loss_accum, n_local, 1.0f / (float)n_global, scale / (float)n_global);
+    k_l1<<<grid, 256, 0, (hipStream_t)stream>>>(out, gt, dout, loss_accum, n_local, 1.0f / (float)n_global, scale / (float)n_global);
     LG_CHECK_LAUNCH();
     return 0;
 }
@@ -373,24 +374,25 @@ __global__ __launch_bounds__(256) void k_l2(const float* __restrict__ out, const
     }
 }
 
-int launch_l2_loss(const float* out, const float* gt, float* dout, float* loss_accum, int64_t n_local, int64_t n_global, float scale, hipStream_t s) {
+extern "C" int lg_l2_loss(const float* out, const float* gt, float* dout, float* loss_accum, int64_t n_local, int64_t n_global, float scale,
+                          void* stream) {
     const int grid = rl_flat_grid("l2_loss", out, gt, dout, loss_accum, n_local, n_global);
     if (!grid) return -1;
     static std::atomic<unsigned> next_slot{0};
-    k_l2<<<grid, 256, 0, s>>>(out, gt, dout, loss_accum, n_local, 1.0 / (double)n_global, (float)(2.0 / (double)n_global), scale,
-                              (int)(next_slot.fetch_add(1) % LG_L2_SLOTS));
+    k_l2<<<grid, 256, 0, (hipStream_t)stream>>>(out, gt, dout, loss_accum, n_local, 1.0 / (double)n_global, (float)(2.0 / (double)n_global), scale,
+                                                (int)(next_slot.fetch_add(1) % LG_L2_SLOTS));
     LG_CHECK_LAUNCH();
     return 0;
 }
 
-size_t recloss_workspace_bytes(int B, int C, int H, int W) {
+extern "C" size_t lg_recloss_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W) {
     RlGeom g;
     if (!rl_geom("recloss_workspace_bytes", B, C, H, W, g)) return 0;
     return g.sam_bytes > g.ssim_bytes ? g.sam_bytes : g.ssim_bytes;
 }
 
-int launch_sam_loss(const float* out, const float* gt, float* dout, float* loss_accum, int B, int64_t B_global, int C, int H, int W, float scale,
-                    int accumulate, void* workspace, size_t workspace_bytes, hipStream_t s) {
+extern "C" int lg_sam_loss(const float* out, const float* gt, float* dout, float* loss_accum, int32_t B, int64_t B_global, int32_t C, int32_t H,
+                           int32_t W, float scale, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream) {
     static const char* who = "sam_loss";
     RlGeom g;
     if (!rl_geom(who, B, C, H, W, g)) return -1;
@@ -398,6 +400,7 @@ int launch_sam_loss(const float* out, const float* gt, float* dout, float* loss_
     double* part = (double*)workspace;
     const double n_global = (double)B_global * (double)g.HW;
     const dim3 grid(g.gx, B);
+    const hipStream_t s = (hipStream_t)stream;
     if (C == 4)
         k_sam_loss<4><<<grid, RL_NT, 0, s>>>(out, gt, dout, part, g.HW, g.gx, (double)scale / n_global, accumulate);
     else
@@ -408,8 +411,8 @@ int launch_sam_loss(const float* out, const float* gt, float* dout, float* loss_
     return 0;
 }
 
-int launch_ssim_loss(const float* out, const float* gt, float* dout, float* loss_accum, int B, int64_t B_global, int C, int H, int W, float scale,
-                     float data_range, int accumulate, void* workspace, size_t workspace_bytes, hipStream_t s) {
+extern "C" int lg_ssim_loss(const float* out, const float* gt, float* dout, float* loss_accum, int32_t B, int64_t B_global, int32_t C, int32_t H,
+                            int32_t W, float scale, float data_range, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream) {
     static const char* who = "ssim_loss";
     RlGeom g;
     if (!rl_geom(who, B, C, H, W, g)) return -1;
@@ -430,6 +433,7 @@ int launch_ssim_loss(const float* out, const float* gt, float* dout, float* loss
     const double win_local = (double)B * C * (double)(H - SS_N + 1) * (double)(W - SS_N + 1);
     const double win_global = win_local / (double)B * (double)B_global;
     double* part = (double*)workspace;
+    const hipStream_t s = (hipStream_t)stream;
     k_ssim_loss<<<dim3(g.tiles, C, B), RL_NT, SS_LDS_BYTES, s>>>(out, gt, dout, part, C, H, W, g.tiles_x, taps, c1, c2,
                                                                  -(double)scale / win_global, accumulate);
     LG_CHECK_LAUNCH();

@@ -12,8 +12,8 @@
 //                      lane knows whether an earlier launch left a partial sum in the scene (it continues that fma chain) and whether a
 //                      later launch will add to it (it leaves the sum) or this one holds the last cover (it divides by the weight sum).
 //   k_scene_to_u16     clip(rint(x * scale), 0, 65535): the fused scene as digital numbers, 2 bytes per sample.
+#include "abi.h"
 #include "common.h"
-#include "kernels.h"
 #include "sample_io.h"
 
 #define SC_NT 256
@@ -124,8 +124,9 @@ static const char* scene_shape_check(int C, int H, int W, int th, int tw) {
     return nullptr;
 }
 
-int launch_scene_gather(const void* pan, const void* ms, const int32_t* origins, int64_t n_tiles, int64_t first, float* o_pan, float* o_ms,
-                        int B, int C, int H, int W, int th, int tw, int dtype, float divisor, int n_div, float post_scale, hipStream_t s) {
+extern "C" int lg_scene_gather(const void* pan, const void* ms, const int32_t* origins, int64_t n_tiles, int64_t first, float* o_pan, float* o_ms,
+                               int32_t B, int32_t C, int32_t H, int32_t W, int32_t th, int32_t tw, int32_t dtype, float divisor, int32_t n_div,
+                               float post_scale, void* stream) {
     const char* why = nullptr;
     if (!pan || !ms || !origins || !o_pan || !o_ms) why = "null pointer";
     else if (B <= 0 || B > 65535) why = "B must be in 1 .. 65535";
@@ -142,6 +143,7 @@ int launch_scene_gather(const void* pan, const void* ms, const int32_t* origins,
     a.pan = pan; a.ms = ms; a.org = origins + 2 * first; a.o_pan = o_pan; a.o_ms = o_ms;
     a.C = C; a.H = H; a.W = W; a.th = th; a.tw = tw;
     a.divisor = divisor; a.post_scale = post_scale; a.n_div = n_div; a.has_scale = post_scale != 1.0f;
+    const hipStream_t s = (hipStream_t)stream;
     ProfScope prof(LG_K_SCENE_GATHER, s);
     if (dtype == LG_DT_U8) sg_launch<uint8_t>(a, B, s);
     else if (dtype == LG_DT_U16) sg_launch<uint16_t>(a, B, s);
@@ -243,7 +245,8 @@ __global__ __launch_bounds__(SC_NT) void k_scene_blend(const float* __restrict__
     *sp = make_float4(acc[0], acc[1], acc[2], acc[3]);
 }
 
-int launch_scene_blend(const float* tiles, float* scene, int64_t first, int B, int C, int H, int W, int th, int tw, int overlap, hipStream_t s) {
+extern "C" int lg_scene_blend(const float* tiles, float* scene, int64_t first, int32_t B, int32_t C, int32_t H, int32_t W, int32_t th, int32_t tw,
+                              int32_t overlap, void* stream) {
     const char* why = nullptr;
     if (!tiles || !scene) why = "null pointer";
     else if (B <= 0 || B > 65535) why = "B must be in 1 .. 65535";
@@ -256,6 +259,7 @@ int launch_scene_blend(const float* tiles, float* scene, int64_t first, int B, i
     }
     if (why) { lg_set_error("scene_blend: %s", why); return -1; }
     const SceneAxis ay = scene_axis(H, th, overlap), ax = scene_axis(W, tw, overlap);
+    const hipStream_t s = (hipStream_t)stream;
     ProfScope prof(LG_K_SCENE_BLEND, s);
     k_scene_blend<<<dim3((th * (tw / 4) + SC_NT - 1) / SC_NT, C, B), SC_NT, 0, s>>>(tiles, scene, (int)first, B, C, ay, ax, overlap + 1);
     LG_CHECK_LAUNCH();
@@ -277,7 +281,7 @@ __global__ __launch_bounds__(SC_NT) void k_scene_to_u16(const float* __restrict_
     reinterpret_cast<uint2*>(dst)[q] = make_uint2(sc_u16(v.x, scale) | (sc_u16(v.y, scale) << 16), sc_u16(v.z, scale) | (sc_u16(v.w, scale) << 16));
 }
 
-int launch_scene_to_u16(const float* src, uint16_t* dst, int64_t n, float scale, hipStream_t s) {
+extern "C" int lg_scene_to_u16(const float* src, uint16_t* dst, int64_t n, float scale, void* stream) {
     const char* why = nullptr;
     if (!src || !dst) why = "null pointer";
     else if (n <= 0 || (n & 3) || n / 4 > (int64_t)0x7fffffff * SC_NT) why = "the sample count must be a positive multiple of 4 below 2^39";
@@ -285,7 +289,7 @@ int launch_scene_to_u16(const float* src, uint16_t* dst, int64_t n, float scale,
     else if (((uintptr_t)src & 15) || ((uintptr_t)dst & 7)) why = "the source must be 16-byte and the destination 8-byte aligned";
     if (why) { lg_set_error("scene_to_u16: %s", why); return -1; }
     const int64_t quads = n / 4;
-    k_scene_to_u16<<<(unsigned)((quads + SC_NT - 1) / SC_NT), SC_NT, 0, s>>>(src, dst, quads, scale);
+    k_scene_to_u16<<<(unsigned)((quads + SC_NT - 1) / SC_NT), SC_NT, 0, (hipStream_t)stream>>>(src, dst, quads, scale);
     LG_CHECK_LAUNCH();
     return 0;
 }

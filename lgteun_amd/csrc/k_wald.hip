@@ -8,8 +8,8 @@
 //                          taps alone -- not of the tile it falls into, nor of the other planes of the call -- and a numpy loop in the same
 //                          order gives the same fp64 bits.  One final rounding: to fp32, or to the input's integer type (half to even,
 //                          saturated, NaN -> 0).
+#include "abi.h"
 #include "common.h"
-#include "kernels.h"
 
 #define FIR_TO 16                                   // outputs per tile edge
 #define FIR_NT (FIR_TO * FIR_TO)
@@ -60,8 +60,8 @@ __global__ __launch_bounds__(FIR_NT) void k_fir_decimate4(const T* __restrict__ 
     fir_store(out + (size_t)plane * ho * wo + (size_t)(oy0 + ly) * wo + ox0 + lx, acc);
 }
 
-int launch_fir_decimate4(const void* in, void* out, const double* taps, int64_t planes, int H, int W, int n_taps, int phase, int dtype, int out_f32,
-                         hipStream_t s) {
+extern "C" int lg_fir_decimate4(const void* in, void* out, const double* taps, int64_t planes, int32_t H, int32_t W, int32_t n_taps, int32_t phase,
+                                int32_t dtype, int32_t out_f32, void* stream) {
     const char* why = nullptr;
     if (!in || !out || !taps) why = "null pointer";
     else if (dtype < LG_DT_U8 || dtype > LG_DT_F32) why = "unknown sample type (LG_DT_U8 / LG_DT_U16 / LG_DT_F32)";
@@ -78,6 +78,7 @@ int launch_fir_decimate4(const void* in, void* out, const double* taps, int64_t 
     if (why) { lg_set_error("fir_decimate4: %s", why); return -1; }
     const int tiles = tiles_x * tiles_y;
     const unsigned grid = (unsigned)(planes * tiles);
+    const hipStream_t s = (hipStream_t)stream;
 #define FIR_GO(T, O) k_fir_decimate4<T, O><<<grid, FIR_NT, 0, s>>>((const T*)in, (O*)out, taps, H, W, n_taps, phase, tiles_x, tiles)
     if (dtype == LG_DT_U8) { if (out_f32) FIR_GO(uint8_t, float); else FIR_GO(uint8_t, uint8_t); }
     else if (dtype == LG_DT_U16) { if (out_f32) FIR_GO(uint16_t, float); else FIR_GO(uint16_t, uint16_t); }

@@ -2,58 +2,6 @@
 #pragma once
 #include "common.h"
 
-// ---------------- device-resident dataset (k_batch.hip; arguments validated before any HIP call) ----------------
-int launch_pyr_down2(const void* pan, float* pan_l, int64_t planes, int H, int W, int dtype, hipStream_t s);
-int launch_batch_assemble(const void* pan, const void* lr, const void* mul, const float* pan_l, int64_t N, const int32_t* idx, int64_t idx_offset,
-                          const uint32_t* flips, float* o_pan, float* o_lr, float* o_mul, float* o_pan_l, int B, int C, int H, int W, int h, int w,
-                          int dtype, float divisor, int n_div, float post_scale, hipStream_t s);
-int launch_window_assemble(const void* pan, const void* lr, const void* mul, const int32_t* origins, int64_t n_windows, int64_t first,
-                           const uint32_t* flips, float* o_pan, float* o_lr, float* o_mul, float* o_pan_l, int B, int C, int Hs, int Ws, int P, int Q,
-                           int dtype, float divisor, int n_div, float post_scale, hipStream_t s);
-// ---------------- Wald degradation of a raw scene (k_wald.hip; arguments validated before any HIP call) ----------------
-int launch_fir_decimate4(const void* in, void* out, const double* taps, int64_t planes, int H, int W, int n_taps, int phase, int dtype, int out_f32,
-                         hipStream_t s);
-// ---------------- tiled scene fusion (k_scene.hip; arguments validated before any HIP call) ----------------
-int launch_scene_gather(const void* pan, const void* ms, const int32_t* origins, int64_t n_tiles, int64_t first, float* o_pan, float* o_ms,
-                        int B, int C, int H, int W, int th, int tw, int dtype, float divisor, int n_div, float post_scale, hipStream_t s);
-int launch_scene_blend(const float* tiles, float* scene, int64_t first, int B, int C, int H, int W, int th, int tw, int overlap, hipStream_t s);
-int launch_scene_to_u16(const float* src, uint16_t* dst, int64_t n, float scale, hipStream_t s);
-// ---------------- evaluation indices of lgteun_amd/metrics.py (k_iqa.hip; arguments validated before any HIP call) ----------------
-size_t iqa_workspace_bytes(int B, int C, int H, int W, int no_ref);
-int launch_iqa_ref(const float* pred, const float* gt, double* out, int B, int C, int H, int W, float scale, void* workspace,
-                   size_t workspace_bytes, hipStream_t s);
-int launch_iqa_no_ref(const float* pred, const float* pan, const float* ms, double* out, int B, int C, int H, int W, float scale,
-                      void* workspace, size_t workspace_bytes, hipStream_t s);
-// ---------------- gradient norm + clip coefficient of a train step (k_gradnorm.hip; arguments validated before any HIP call) ----------------
-size_t grad_norm_workspace_bytes(int n_ranges, int64_t max_range);
-int launch_grad_norm(const float* grads, const int64_t* ranges, int n_ranges, int64_t max_range, double max_norm, float* out, void* workspace,
-                     size_t workspace_bytes, hipStream_t s);
-
-// ---------------- the no-reference training loss 1 - QNR and its gradient (k_qnr.hip; arguments validated before any HIP call) ----------------
-size_t qnr_workspace_bytes(int B, int C, int H, int W);
-int launch_qnr_stats(const float* out, const float* pan, const float* ms, const float* pan_l, double* q, double* table, int B, int C, int H,
-                     int W, void* workspace, size_t workspace_bytes, hipStream_t s);
-int launch_qnr_grad(const float* out, const float* pan, const double* table, float* dout, float* loss_accum, double* indices, int B,
-                    int64_t B_global, int C, int H, int W, float scale, int accumulate, const void* workspace, size_t workspace_bytes,
-                    hipStream_t s);
-
-// ---------------- the training losses against a target and their gradients: l1, l2, spectral (SAM), structural (1 - SSIM) (k_recloss.hip;
-// arguments validated before any HIP call) ----------------
-int launch_l1_loss(const float* out, const float* gt, float* dout, float* loss_accum, int64_t n_local, int64_t n_global, float scale, hipStream_t s);
-int launch_l2_loss(const float* out, const float* gt, float* dout, float* loss_accum, int64_t n_local, int64_t n_global, float scale, hipStream_t s);
-size_t recloss_workspace_bytes(int B, int C, int H, int W);
-int launch_sam_loss(const float* out, const float* gt, float* dout, float* loss_accum, int B, int64_t B_global, int C, int H, int W, float scale,
-                    int accumulate, void* workspace, size_t workspace_bytes, hipStream_t s);
-int launch_ssim_loss(const float* out, const float* gt, float* dout, float* loss_accum, int B, int64_t B_global, int C, int H, int W, float scale,
-                     float data_range, int accumulate, void* workspace, size_t workspace_bytes, hipStream_t s);
-
-// ---------------- the classical baselines: interp23 x4, SFIM, GSA (k_classical.hip; arguments validated before any HIP call) ----------------
-size_t classical_workspace_bytes(int B, int C, int h, int w, int method);
-int launch_interp23_up4(const float* ms, float* out, int B, int C, int h, int w, hipStream_t s);
-int launch_sfim(const float* ms, const float* pan, float* out, int B, int C, int h, int w, void* workspace, size_t workspace_bytes, hipStream_t s);
-int launch_gsa(const float* ms, const float* pan, float* out, double* stats, int B, int C, int h, int w, void* workspace, size_t workspace_bytes,
-               hipStream_t s);
-
 // ---------------- data module (reference models/unlg_former.py:29-37,58-61) ----------------
 struct DwArgs {
     const float* in;    // [planes, hi, wi]
@@ -88,7 +36,7 @@ struct DstepFwdArgs {
 bool dstep_fused_ok(int C, int H, int W);
 int launch_dstep_fwd(const DstepFwdArgs& a, hipStream_t s);
 
-// ---------------- several stages in one launch (the dead-stage LGT forwards of a faithful step, api.hip: lgt_fwd) ----------------
+// ---------------- several stages in one launch (the dead-stage LGT forwards of a faithful step, k_fwd.hip: lgt_fwd) ----------------
 // A forward kernel of the LGT sees a plain batch of n * Bs samples; sample b belongs to stage b / Bs, and a workgroup moves its weight, scale and
 // table pointers by (b / Bs) x the stage strides before it stages anything.  The K LGTs have identical shapes, so every tensor of the flat
 // parameter buffer has the SAME stride from one stage to the next (lg_plan::stage_stride).  n <= 1: one stage, every shift is zero.

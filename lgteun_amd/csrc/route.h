@@ -1,9 +1,9 @@
 // Kernel routes of a plan: which kernel runs for every half-block, what the saving forward leaves for the backward and what the
 // backward reads.  lg_resolve_route (route.hip) fills them ONCE, in lg_plan_create, from lg_config.variant / precision / C / H / W;
-// the orchestrators (api.hip, k_bwd.hip) and the launchers that choose between kernels read the route and nothing else.
+// the orchestrators (k_fwd.hip, k_bwd.hip) and the launchers that choose between kernels read the route and nothing else.
 #pragma once
 #include <stddef.h>
-#include "../../include/lgteun_hip.h"
+#include "abi.h"
 
 // level 0: the four e = 4C blocks at H x W; level 1: the bottleneck block, e = 8C at H/2 x W/2
 enum FfnFwdKernel {

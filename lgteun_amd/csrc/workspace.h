@@ -17,7 +17,7 @@ struct Carver {
 #define LG_MAX_K 16
 #define LG_NBLK 5   // blocks of one LGT: encoder 0 1, bottleneck 2 (level 1), decoder 3 4
 
-// The per-block prep slots: four tables of [K][LG_NBLK] rows, written once per forward call (api.hip: prep_stages) and read by the kernels of
+// The per-block prep slots: four tables of [K][LG_NBLK] rows, written once per forward call (k_fwd.hip: prep_stages) and read by the kernels of
 // that (stage, block).  THE description of their layout: the row sizes here, the carving in carve(), the rows in NetBufs::*_row and
 // NetBufs::block, the stage-to-stage strides of the multi-stage kernels in NetBufs::stage_strides.
 constexpr size_t POS_TABLE = 2 * 64 * 64;   // floats of one pos_emb table [2][64][64] (posT; a row of the R3 backward's dpos slab too)
