@@ -114,7 +114,7 @@ typedef struct lg_plan lg_plan; /* host-side, immutable after creation */
 
 const char* lg_version(void);
 /* Bumped whenever a struct layout, an argument meaning or a caller-provided buffer size changes (2: lg_config.variant, the data step's
- * tmp of 3*B*C*H*W/4 + B*H*W floats).  Additions keep it: lg_op_lgt_stages, lg_workspace_deadout, LG_FLAG_STAGEWISE, the lg_debug_stage_* entries and the classical baselines (lg_classical_workspace_bytes, lg_interp23_up4, lg_sfim, lg_gsa) came without a bump (no struct,
+ * tmp of 3*B*C*H*W/4 + B*H*W floats).  Additions keep it: lg_op_lgt_stages, lg_workspace_deadout, LG_FLAG_STAGEWISE, the lg_debug_stage_* entries and the classical baselines (lg_classical_workspace_bytes, lg_interp23_up4, lg_sfim, lg_gsa, then lg_wavelet, lg_wavelet_taps) came without a bump (no struct,
  * argument or caller-sized buffer changed: workspaces are sized by lg_workspace_bytes, which grew for the plans that batch their dead stages).  A binding checks it at load time -- lgteun_amd/_lib.py does -- instead of passing a stale struct. */
 #define LG_ABI_VERSION 2
 int32_t lg_abi_version(void);
@@ -479,6 +479,14 @@ int lg_sfim(const float* ms, const float* pan, float* out, int32_t B, int32_t C,
  * I0 has no variance gets alpha_0..C-1 = g = 0: out = clip(u). */
 int lg_gsa(const float* ms, const float* pan, float* out, double* stats, int32_t B, int32_t C, int32_t h, int32_t w, void* workspace,
            size_t workspace_bytes, void* stream);
+/* ---- the third classical baseline: Wavelet, the two-level Haar substitution ----
+ * out_k(y, x) = clip(pan(y, x) - P(y / 4, x / 4) + M_k(y / 4, x / 4), 0, 1): the level-2 Haar approximation of PAN replaced by that of u_k = interp23(ms_k).
+ * The sides are 4h x 4w, so both levels split evenly: P is the 4 x 4 block mean of PAN, M_k that of u_k, and M_k = sum_a sum_b t_a t_b
+ * ms_k((i - a) mod h, (j - b) mod w) with the 17 taps of lg_wavelet_taps.  One launch, no workspace, no method code (the method has no global statistic:
+ * lg_classical_workspace_bytes knows no third method); tensors, limits, checks and guarantees are those of lg_sfim. */
+int lg_wavelet(const float* ms, const float* pan, float* out, int32_t B, int32_t C, int32_t h, int32_t w, void* stream);
+/* out17: a HOST array that receives the taps lg_wavelet uses, by offset -8 .. 8: the block means of the response of interp23 to a unit impulse */
+int lg_wavelet_taps(double* out17);
 
 #ifdef __cplusplus
 }

@@ -1,12 +1,13 @@
-"""The two non-learned rows of a pan-sharpening results table, for whole batches on the GPU: SFIM (smoothing-filter-based intensity
-modulation) and GSA (adaptive Gram-Schmidt with a global regression), both on top of the 23-tap interpolator x4 -- the reference's
-models/SFIM.py, models/GSA.py and models/common/model_based_utils.py:upsample_interp23.  The definitions, restated per sample of a batch, and
-the two deliberate deviations are in DESIGN.md 3.12; the HIP kernels are lgteun_amd/csrc/k_classical.hip (C ABI lg_interp23_up4 / lg_sfim /
-lg_gsa in include/lgteun_hip.h): fp64 arithmetic, one rounding per output element, no atomics.  There is no CPU path.
+"""The three non-learned rows of a pan-sharpening results table, for whole batches on the GPU: SFIM (smoothing-filter-based intensity
+modulation), GSA (adaptive Gram-Schmidt with a global regression) and Wavelet (two-level Haar substitution), all defined on top of the 23-tap
+interpolator x4 -- the reference's models/SFIM.py, models/GSA.py, models/Wavelet.py and models/common/model_based_utils.py:upsample_interp23.
+The definitions, restated per sample of a batch, and the two deliberate deviations are in DESIGN.md 3.12; the HIP kernels are
+lgteun_amd/csrc/k_classical.hip (C ABI lg_interp23_up4 / lg_sfim / lg_gsa / lg_wavelet in include/lgteun_hip.h): fp64 arithmetic, one rounding
+per output element, no atomics.  There is no CPU path.
 
-`interp23`, `sfim` and `gsa` take normalised float32 NCHW tensors on the GPU -- ms [B, C, h, w], pan [B, 1, 4h, 4w] -- and return
-[B, C, 4h, 4w] on the same device; nothing is copied to the host and nothing synchronises.  `GSA` and `SFIM` are the runner classes the
-reference registers under those names: they have nothing to train, and `test()` scores them like any network."""
+`interp23`, `sfim`, `gsa` and `wavelet` take normalised float32 NCHW tensors on the GPU -- ms [B, C, h, w], pan [B, 1, 4h, 4w] -- and return
+[B, C, 4h, 4w] on the same device; nothing is copied to the host and nothing synchronises.  `GSA`, `SFIM` and `Wavelet` are the runner classes
+the reference registers under those names: they have nothing to train, and `test()` scores them like any network."""
 import numpy as np
 import torch
 
@@ -78,14 +79,27 @@ def gsa(ms, pan, return_stats=False):
     return (out, stats) if return_stats else out
 
 
+def wavelet(ms, pan):
+    """Wavelet of every sample: PAN with the level-2 Haar approximation (the 4 x 4 block means) of interp23(ms) in place of its own, clipped to
+    [0, 1].  One launch: the block means of interp23(ms) are a 17-tap circular FIR on ms, so neither interp23(ms) nor a workspace is needed"""
+    ms, pan, (B, C, h, w) = _prepare('wavelet', ms, pan)
+    with torch.cuda.device(ms.device):
+        out = torch.empty(B, C, 4 * h, 4 * w, dtype=torch.float32, device=ms.device)
+        _lib.check(_lib.lib().lg_wavelet(_ptr(ms), _ptr(pan), _ptr(out), B, C, h, w, _stream_ptr()), 'lg_wavelet')
+    return out
+
+
+SCENE_METHODS = {'gsa': gsa, 'sfim': sfim, 'wavelet': wavelet}      # classical.fuse_scene, tools/fuse_scene.py --method
+
+
 def fuse_scene(method, ms, pan, bit_depth=None, norm_input=False, out_dtype='float32', device=None):
-    """One whole scene through `method` ('gsa' or 'sfim') in ONE call -- no tiles, no checkpoint: MS [C, h, w], PAN [1, 4h, 4w] -> [C, 4h, 4w]
+    """One whole scene through `method` ('gsa', 'sfim' or 'wavelet') in ONE call -- no tiles, no checkpoint: MS [C, h, w], PAN [1, 4h, 4w] -> [C, 4h, 4w]
     on the device.  The arguments are scene.fuse_scene's: samples as numpy arrays or tensors (uint8, uint16 or its int16 view, float32);
     bit_depth / norm_input: the normalisation of the tile gather (norm_input: one correctly rounded fp32 division by 2**bit_depth - 0.5, then
     one multiplication by the fp32 reciprocal of that number); out_dtype 'uint16': digital numbers by lg_scene_to_u16 (needs bit_depth)."""
     from . import scene as sc
-    if method not in ('gsa', 'sfim'):
-        raise ValueError(f"method must be 'gsa' or 'sfim' (got {method!r})")
+    if method not in SCENE_METHODS:
+        raise ValueError(f"method must be 'gsa', 'sfim' or 'wavelet' (got {method!r})")
     if out_dtype not in ('float32', 'uint16'):
         raise ValueError(f"out_dtype must be 'float32' or 'uint16' (got {out_dtype!r})")
     if (norm_input or out_dtype == 'uint16') and bit_depth is None:
@@ -108,7 +122,7 @@ def fuse_scene(method, ms, pan, bit_depth=None, norm_input=False, out_dtype='flo
             t = t * float(np.float32(1.0) / np.float32(divisor))        # scene.fuse_scene's post_scale
         return t
     with torch.cuda.device(dev):
-        fused = (gsa if method == 'gsa' else sfim)(normalised(ms_t).view(1, C, H // 4, W // 4), normalised(pan_t).view(1, 1, H, W))[0]
+        fused = SCENE_METHODS[method](normalised(ms_t).view(1, C, H // 4, W // 4), normalised(pan_t).view(1, 1, H, W))[0]
         if out_dtype == 'float32':
             return fused
         out = torch.empty(C, H, W, dtype=torch.uint16, device=dev)
@@ -148,3 +162,8 @@ class GSA(_Classical):
 @MODELS.register_module()
 class SFIM(_Classical):
     method = staticmethod(sfim)
+
+
+@MODELS.register_module()
+class Wavelet(_Classical):
+    method = staticmethod(wavelet)

@@ -1,6 +1,7 @@
-// The two classical (training-free) pan-sharpening baselines, whole batches on the device: SFIM and GSA with global regression, on top of the
-// 23-tap half-band interpolator x4 (C ABI: lg_interp23_up4 / lg_sfim / lg_gsa, include/lgteun_hip.h; the definitions are in DESIGN.md 3.12,
-// the fp64 numpy restatement the tests compare with is tests/classical_ref.py).
+// The three classical (training-free) pan-sharpening baselines, whole batches on the device: SFIM and GSA with global regression, on top of the
+// 23-tap half-band interpolator x4, and the two-level Haar substitution (Wavelet), which needs neither u nor a statistic (C ABI: lg_interp23_up4 /
+// lg_sfim / lg_gsa / lg_wavelet, include/lgteun_hip.h; the definitions are in DESIGN.md 3.12, the fp64 numpy restatements the tests compare with
+// are tests/classical_ref.py and tests/wavelet_ref.py).
 //
 //   cl_up_band       the upsampling of ONE band for a 16 x 32 tile of the output, in LDS, all fp64: the 20 x 24 ms samples the tile depends on
 //                    (cl_ms_load: loaded modulo h, w -- the circular boundary happens here and nowhere else -- into registers, one band
@@ -19,6 +20,9 @@
 //                    a non-positive pivot, alpha' Sigma_u alpha <= 0 or a gain that is not finite gives alpha = g = 0.
 //   k_cl_apply       grid (tile, sample): the C bands of the tile again, then pointwise in fp64 with ONE rounding to fp32; SFIM stages
 //                    PAN with a circular halo of 2 for the 5 x 5 box.  Two adjacent pixels per thread: 8-byte stores.
+//   k_cl_wavelet     grid (tile, sample), the whole method in one launch: out_k = clip(pan - P + M_k) with P the 4 x 4 block mean of PAN and M_k the
+//                    block mean of u_k, which is a separable 17-tap circular FIR on ms itself (cl_wavelet_taps).  A lane owns 4 x 4 blocks: 16-byte
+//                    PAN loads, 16-byte stores, M_k from an ms halo tile in LDS (columns, then rows).  No u, no moments, no workspace.
 // No atomics; a workgroup sees one sample and the grid of a sample depends on C, h and w only, so a sample has the same bits alone and inside
 // any batch.  All indexing into tensors is 64-bit.
 #include <cmath>
@@ -386,17 +390,152 @@ __global__ __launch_bounds__(CL_NT) void k_cl_apply(const float* __restrict__ ms
     }
 }
 
+// ---- Wavelet: the level-2 Haar approximation of PAN replaced by the band's.  With 4h x 4w sides both levels split evenly, the approximation is 1/4 of the
+// sum of a 4 x 4 block and its synthesis alone is the block mean, so out_k(y, x) = clip(pan(y, x) - P(Y, X) + M_k(Y, X)), Y = y / 4, X = x / 4.
+constexpr int CW_BY = 8, CW_BX = 64;                                    // the tile in 4 x 4 blocks: 32 x 256 output pixels
+constexpr int CW_REACH = 8, CW_TAPS = 2 * CW_REACH + 1;                 // the FIR's offsets -8 .. 8
+constexpr int CW_MR = CW_BY + 2 * CW_REACH, CW_MC = CW_BX + 2 * CW_REACH;      // 24 x 80: ms rows / columns a tile depends on
+constexpr int CW_LROWS = CL_NT / CW_MC, CW_MLOADS = CW_MR / CW_LROWS;    // a thread loads column tid % 80 of rows tid / 80 + 3 u, u < 8 (240 of the 256 threads)
+constexpr int CW_PER = CW_BY / (CL_NT / 64);                            // blocks of a lane: rows wave, wave + 4 of the tile, column lane
+static_assert(CW_BX == 64 && CW_BY % (CL_NT / 64) == 0, "a wave spans the tile's columns: 64 lanes x 16 bytes are 1 KiB contiguous");
+static_assert(CW_MR % CW_LROWS == 0 && CW_LROWS < 4, "the halo rows divide among the loads; a row index advanced by CW_LROWS wraps at most once (h >= 4)");
+
+// M_k(i, j) = sum_a sum_b t[a] t[b] ms_k((i - a) mod h, (j - b) mod w): the response of "level 1 (zero insertion at the odd positions, the 23 taps), level 2
+// (at the even positions, the 23 taps), mean of groups of 4" to a unit impulse, t[8 + a] for a = -8 .. 8.  An impulse at ms(0) is x1(1) = 1, so
+// y1(n) = T(1 - n), u(m) = sum_n T(2 n - m) y1(n) and t_a = the mean of u(4 a .. 4 a + 3); T the 23 taps by offset, zero beyond +-11.  Asymmetric: ms(i)
+// sits at u(4 i + 2), the block's centre at 4 i + 1.5.
+struct ClWaveletTaps { double t[CW_TAPS]; };
+__host__ __device__ constexpr ClWaveletTaps cl_wavelet_taps() {
+    constexpr double HB[6] = {0.305334091185, -0.072698593239, 0.021809577942, -0.005192756653, 0.000807762146, -0.000060081482};
+    double T[23] = {};
+    T[11] = 1.0;
+    for (int i = 0; i < 6; ++i) T[11 + 2 * i + 1] = T[11 - 2 * i - 1] = 2 * HB[i];
+    ClWaveletTaps r = {};
+    for (int a = -CW_REACH; a <= CW_REACH; ++a) {
+        double s = 0.0;
+        for (int m = 4 * a; m < 4 * a + 4; ++m) {
+            double um = 0.0;
+            for (int n = -10; n <= 12; ++n) {
+                const int k = 2 * n - m;
+                if (k >= -11 && k <= 11) um += T[11 + k] * T[11 + 1 - n];
+            }
+            s += um;
+        }
+        r.t[a + CW_REACH] = 0.25 * s;
+    }
+    return r;
+}
+
+// sum_a t_a src[(8 - a) stride]: src[0] is the sample at offset -8 (it takes tap t_8), src[16 stride] the one at offset +8 (tap t_-8); two chains, as in cl_fir
+__device__ __forceinline__ double cw_fir(const double* src, int stride) {
+    constexpr ClWaveletTaps W = cl_wavelet_taps();
+    double a = 0.0, b = W.t[CW_REACH] * src[CW_REACH * stride];
+#pragma unroll
+    for (int u = 0; u < CW_REACH; ++u) {
+        a = fma(W.t[CW_TAPS - 1 - u], src[u * stride], a);
+        b = fma(W.t[CW_REACH - 1 - u], src[(CW_REACH + 1 + u) * stride], b);
+    }
+    return a + b;
+}
+
+// the 24 x 80 ms samples of one band a tile depends on, modulo (h, w): the only place the circular boundary appears.  (r, c): the thread's first halo
+// row and its column, already modulo the sides
+__device__ __forceinline__ void cw_ms_load(const float* __restrict__ ms, int h, int w, int r, int c, float (&v)[CW_MLOADS]) {
+#pragma unroll
+    for (int u = 0; u < CW_MLOADS; ++u) {
+        v[u] = 0.f;
+        if (threadIdx.x < CW_LROWS * CW_MC) v[u] = ms[(long)r * w + c];
+        r += CW_LROWS;
+        if (r >= h) r -= h;
+    }
+}
+
+// Per band two LDS passes: the FIR along y on the halo tile (8 x 80 outputs), then along x straight into the register of the lane that owns the block.
+// Columns first because the tile is wide: 17 (80 / 64 + 1) products per block and band, against 17 (24 / 8 + 1) rows first.  In both passes consecutive lanes
+// read consecutive doubles.  V is double-buffered, so a band costs two barriers: band k + 1 writes M after barrier B of band k (M's last readers are in front
+// of it) and the other V, and a wave that writes V[k & 1] again (band k + 2) has passed barrier A of band k + 1, which every wave reaches after its reads of band k.
+__global__ __launch_bounds__(CL_NT, 4) void k_cl_wavelet(const float* __restrict__ ms, const float* __restrict__ pan, float* __restrict__ out, int C, int h, int w,
+                                                      int tiles_x) {
+    __shared__ double M[CW_MR * CW_MC];              // 15 KiB
+    __shared__ double V[2][CW_BY * CW_MC];           // 2 x 5 KiB
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int H4 = 4 * h, W4 = 4 * w;
+    const int i0 = (blockIdx.x / tiles_x) * CW_BY, j0 = (blockIdx.x % tiles_x) * CW_BX;
+    const long b = blockIdx.y, plane = (long)H4 * W4;
+    const float* __restrict__ ms_b = ms + b * C * ((long)h * w);
+    const float* __restrict__ pan_b = pan + b * plane;
+    float* __restrict__ out_b = out + b * C * plane;
+    const int lr = tid / CW_MC, lc = tid - lr * CW_MC;      // halo row (of the first load) and column this thread loads
+    const int mr = cl_mod(i0 - CW_REACH + lr, h), mc = cl_mod(j0 - CW_REACH + lc, w);
+    float v[CW_MLOADS];
+    cw_ms_load(ms_b, h, w, mr, mc, v);               // ahead of the PAN loads: the first M does not wait for them
+    float4 p[CW_PER][4] = {};
+    long o[CW_PER];
+    bool in[CW_PER];
+#pragma unroll
+    for (int q = 0; q < CW_PER; ++q) {
+        const int i = i0 + wave + q * (CL_NT / 64), j = j0 + lane;
+        in[q] = i < h && j < w;
+        o[q] = (long)(4 * i) * W4 + 4 * j;
+        if (in[q]) {
+#pragma unroll
+            for (int dy = 0; dy < 4; ++dy) p[q][dy] = *reinterpret_cast<const float4*>(pan_b + o[q] + (long)dy * W4);
+        }
+    }
+    double pm[CW_PER] = {};                           // the block mean of PAN
+    for (int k = 0; k < C; ++k) {
+#pragma unroll
+        for (int u = 0; u < CW_MLOADS; ++u)
+            if (tid < CW_LROWS * CW_MC) M[tid + u * (CW_LROWS * CW_MC)] = (double)v[u];
+        if (k + 1 < C) cw_ms_load(ms_b + (k + 1) * ((long)h * w), h, w, mr, mc, v);      // the next band's, under this band's two passes
+        __syncthreads();                             // A
+        double* Vk = V[k & 1];
+#pragma unroll 1
+        for (int i = tid; i < CW_BY * CW_MC; i += CL_NT) {
+            const int r = i / CW_MC, c = i - r * CW_MC;
+            Vk[i] = cw_fir(M + r * CW_MC + c, CW_MC);          // ms rows i0 + r - 8 .. i0 + r + 8
+        }
+        __syncthreads();                             // B
+        if (k == 0) {                                // here, not in front of the loop: the PAN loads have had the first band's passes to arrive
+#pragma unroll
+            for (int q = 0; q < CW_PER; ++q) {
+                double s = 0.0;
+#pragma unroll
+                for (int dy = 0; dy < 4; ++dy) s += ((double)p[q][dy].x + (double)p[q][dy].y) + ((double)p[q][dy].z + (double)p[q][dy].w);
+                pm[q] = 0.0625 * s;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < CW_PER; ++q) {
+            const double d = cw_fir(Vk + (wave + q * (CL_NT / 64)) * CW_MC + lane, 1) - pm[q];      // M_k - P of the block
+            if (in[q]) {
+                float* dst = out_b + k * plane + o[q];
+#pragma unroll
+                for (int dy = 0; dy < 4; ++dy)
+                    *reinterpret_cast<float4*>(dst + (long)dy * W4) = make_float4(cl_clip((double)p[q][dy].x + d), cl_clip((double)p[q][dy].y + d),
+                                                                                  cl_clip((double)p[q][dy].z + d), cl_clip((double)p[q][dy].w + d));
+            }
+        }
+    }
+}
+
 struct ClGeom {
     int tiles_x, tiles, gx, ns;
     size_t off[2], bytes;      // part, coef
 };
 
 // false: not a shape the calls take (the reason, naming the argument, is in lg_last_error)
-bool cl_geom(const char* who, int B, int C, int h, int w, int method, ClGeom& g) {
+bool cl_shape(const char* who, int B, int C, int h, int w) {
     if (B < 1 || B > 65535) { lg_set_error("%s: B must be 1..65535 (got %d)", who, B); return false; }
     if (C < 2 || C > CL_MAX_C) { lg_set_error("%s: C must be 2..%d (got %d)", who, CL_MAX_C, C); return false; }
     if (h < 4 || h > 4096) { lg_set_error("%s: h must be 4..4096 (got %d)", who, h); return false; }
     if (w < 4 || w > 4096) { lg_set_error("%s: w must be 4..4096 (got %d)", who, w); return false; }
+    return true;
+}
+
+// ... or method: the geometry of the moments pass and the workspace of lg_sfim / lg_gsa
+bool cl_geom(const char* who, int B, int C, int h, int w, int method, ClGeom& g) {
+    if (!cl_shape(who, B, C, h, w)) return false;
     if (method != LG_CLASSICAL_SFIM && method != LG_CLASSICAL_GSA) { lg_set_error("%s: method must be LG_CLASSICAL_SFIM or LG_CLASSICAL_GSA (got %d)", who, method); return false; }
     g.tiles_x = (4 * w + CL_TW - 1) / CL_TW;
     g.tiles = g.tiles_x * ((4 * h + CL_TH - 1) / CL_TH);
@@ -468,4 +607,21 @@ extern "C" int lg_sfim(const float* ms, const float* pan, float* out, int32_t B,
 extern "C" int lg_gsa(const float* ms, const float* pan, float* out, double* stats, int32_t B, int32_t C, int32_t h, int32_t w, void* workspace,
                       size_t workspace_bytes, void* stream) {
     return cl_fuse("gsa", LG_CLASSICAL_GSA, ms, pan, out, stats, B, C, h, w, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int lg_wavelet(const float* ms, const float* pan, float* out, int32_t B, int32_t C, int32_t h, int32_t w, void* stream) {
+    static const char* who = "wavelet";
+    if (!cl_shape(who, B, C, h, w)) return -1;
+    if (!check_tensors(who, {{"ms", ms}, {"pan", pan}, {"out", out}})) return -1;
+    const int tiles_x = (w + CW_BX - 1) / CW_BX, tiles = tiles_x * ((h + CW_BY - 1) / CW_BY);
+    k_cl_wavelet<<<dim3(tiles, B), CL_NT, 0, (hipStream_t)stream>>>(ms, pan, out, C, h, w, tiles_x);
+    LG_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int lg_wavelet_taps(double* out17) {
+    if (!out17) { lg_set_error("wavelet_taps: out17 is NULL"); return -1; }
+    constexpr ClWaveletTaps W = cl_wavelet_taps();
+    for (int a = 0; a < CW_TAPS; ++a) out17[a] = W.t[a];
+    return 0;
 }

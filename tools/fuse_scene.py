@@ -3,9 +3,9 @@ dataset.read_tiff, fuses them tile by tile on the GPU (lgteun_amd/scene.py) and 
 
     python tools/fuse_scene.py PREFIX --checkpoint model.state.pth [--tile 128] [--overlap 32] [--bit-depth 11] [--norm-input]
                                [--batch B] [--float] [--out FILE]
-    python tools/fuse_scene.py PREFIX --method gsa|sfim [--bit-depth 11] [--norm-input] [--float] [--out FILE]
+    python tools/fuse_scene.py PREFIX --method gsa|sfim|wavelet [--bit-depth 11] [--norm-input] [--float] [--out FILE]
 
---method gsa / sfim (lgteun_amd/classical.py) needs no checkpoint and no tiles: the whole scene is fused in one call, with the same
+--method gsa / sfim / wavelet (lgteun_amd/classical.py) needs no checkpoint and no tiles: the whole scene is fused in one call, with the same
 normalisation and the same conversion to digital numbers.
 
 The checkpoint is a plain-tensor file ({'core_module': state_dict}, what Base_model.save writes and tools/convert_checkpoint.py makes of a
@@ -35,10 +35,10 @@ def load_module(path, device='cuda:0'):
     return net.to(device).eval()
 
 
-def main():
+def parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('prefix')
-    ap.add_argument('--method', choices=['network', 'gsa', 'sfim'], default='network')
+    ap.add_argument('--method', choices=['network', 'gsa', 'sfim', 'wavelet'], default='network')
     ap.add_argument('--checkpoint', default=None, help='required for --method network')
     ap.add_argument('--tile', type=int, nargs='+', default=[128], help='one side, or height and width')
     ap.add_argument('--overlap', type=int, default=32)
@@ -47,6 +47,11 @@ def main():
     ap.add_argument('--norm-input', action='store_true', help="the dataset's extra division (cfg.norm_input of the training run)")
     ap.add_argument('--float', action='store_true', help='write the normalised float32 image instead of uint16 digital numbers')
     ap.add_argument('--out', default=None)
+    return ap
+
+
+def main():
+    ap = parser()
     a = ap.parse_args()
     if len(a.tile) > 2:
         ap.error('--tile takes one or two values')

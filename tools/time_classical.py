@@ -1,8 +1,8 @@
-"""What the classical baselines cost on the GPU (lgteun_amd/classical.py): ms per call of `sfim` and `gsa` with the call synchronised, the
+"""What the classical baselines cost on the GPU (lgteun_amd/classical.py): ms per call of `sfim`, `gsa` and `wavelet` with the call synchronised, the
 median of 20 runs after 5 warm-up runs, at C = 4 and C = 8 with PAN 128 x 128 (batch 1 and batch 32) and for one 4096 x 4096 scene of C = 4.
-Beside each: the bytes the passes must move (the moments pass reads ms and pan, the apply pass reads them again and writes the output)
-divided by the time, as a fraction of the HBM bandwidth (--hbm-gbs, default 8000: the MI355X's 8 TB/s), and the ms per image of the float64
-numpy restatement (tests/classical_ref.py) on the same box (--no-host skips it).  Prints one JSON line.   python tools/time_classical.py"""
+Beside each: the bytes the passes must move (SFIM and GSA: the moments pass reads ms and pan, the apply pass reads them again and writes the
+output; Wavelet: ms and pan read once, the output written once) divided by the time, as a fraction of the HBM bandwidth (--hbm-gbs, default 8000: the MI355X's 8 TB/s), and the ms per image of the float64
+numpy restatement (tests/classical_ref.py, tests/wavelet_ref.py) on the same box (--no-host skips it).  Prints one JSON line.   python tools/time_classical.py"""
 import argparse
 import json
 import os
@@ -17,6 +17,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import classical_ref as cr  # noqa: E402
+import wavelet_ref as wr  # noqa: E402
 from lgteun_amd import classical  # noqa: E402
 
 CASES = [(1, 4, 32, 32), (32, 4, 32, 32), (1, 8, 32, 32), (32, 8, 32, 32), (1, 4, 1024, 1024)]      # B, C, h, w
@@ -47,11 +48,11 @@ def main():
         ms_np, pan_np = cr.make_scene(C, h, w, seed=1)
         ms = torch.from_numpy(ms_np).cuda()[None].repeat(B, 1, 1, 1)
         pan = torch.from_numpy(pan_np).cuda()[None, None].repeat(B, 1, 1, 1)
-        moved = 4 * B * (2 * (C * h * w + 16 * h * w) + C * 16 * h * w)
-        row = dict(bytes_moved=moved)
-        for name, fn, host in (('sfim', classical.sfim, cr.sfim), ('gsa', classical.gsa, cr.gsa)):
+        row = {}
+        for name, fn, host, reads in (('sfim', classical.sfim, cr.sfim, 2), ('gsa', classical.gsa, cr.gsa, 2), ('wavelet', classical.wavelet, wr.wavelet, 1)):
+            moved = 4 * B * (reads * (C * h * w + 16 * h * w) + C * 16 * h * w)
             ms_call = median_ms(lambda: fn(ms, pan), a.warmup, a.runs)
-            row[name] = dict(ms_per_call=round(ms_call, 4), ms_per_image=round(ms_call / B, 4), gb_per_s=round(moved / ms_call / 1e6, 1),
+            row[name] = dict(bytes_moved=moved, ms_per_call=round(ms_call, 4), ms_per_image=round(ms_call / B, 4), gb_per_s=round(moved / ms_call / 1e6, 1),
                              hbm_fraction=round(moved / ms_call / 1e6 / a.hbm_gbs, 4))
             if not a.no_host:
                 t = time.perf_counter()
