@@ -3,7 +3,6 @@ and the routes through Engine.train_step / UnlgFormer.train_iter, against torch.
 against the `fused=False` route and against a fixture the reference runner itself produced."""
 import json
 import logging
-import types
 
 import numpy as np
 import pytest
@@ -11,6 +10,7 @@ import torch
 
 from conftest import load_gold
 from helpers import rel_l2, state_shapes
+from optim_helpers import flat_engine
 from oracle import detweights as dw
 
 pytestmark = pytest.mark.gpu
@@ -35,30 +35,19 @@ OPTION_SETS = [
     ('SGD', dict()),
     ('SGD', dict(weight_decay=1e-2)),
     ('SGD', dict(momentum=0.9)),
+    ('SGD', dict(momentum=0.9, weight_decay=1e-2)),
     ('SGD', dict(momentum=0.9, dampening=0.1)),
     ('SGD', dict(momentum=0.9, nesterov=True)),
     ('SGD', dict(momentum=0.9, nesterov=True, weight_decay=1e-2)),
     ('RMSprop', dict()),
     ('RMSprop', dict(weight_decay=1e-2)),
     ('RMSprop', dict(momentum=0.9)),
+    ('RMSprop', dict(momentum=0.9, weight_decay=1e-2)),
     ('RMSprop', dict(centered=True)),
+    ('RMSprop', dict(centered=True, weight_decay=1e-2)),
     ('RMSprop', dict(centered=True, momentum=0.9)),
     ('RMSprop', dict(alpha=0.9, eps=1e-6, weight_decay=1e-2, centered=True, momentum=0.5)),
 ]
-
-
-def _flat_engine(flat, gflat):
-    """what a fused optimizer's step_flat needs of an Engine, over synthetic flat buffers: the library, the buffers, the ranges and
-    Engine's own two launch methods"""
-    from lgteun_amd import _lib
-    from lgteun_amd.engine import Engine
-    assert all(0 <= a < b <= flat.numel() for a, b in RANGES) and gflat.numel() == flat.numel()
-    eng = types.SimpleNamespace(lib=_lib.lib(), flat=flat, gflat=gflat, total=flat.numel(), live_ranges=RANGES,
-                                ranges_dev=torch.tensor([v for r in RANGES for v in r], dtype=torch.int64, device=flat.device),
-                                max_range=max(b - a for a, b in RANGES))
-    eng.adam = types.MethodType(Engine.adam, eng)
-    eng.optim_step = types.MethodType(Engine.optim_step, eng)
-    return eng
 
 
 def _bits(t):
@@ -109,7 +98,7 @@ def test_optimizer_step_vs_torch(name, kwargs):
     p0, steps, inside, gen = _synthetic()
     flat = p0.clone().cuda()
     gflat = torch.zeros(N_FLAT, device='cuda')
-    eng = _flat_engine(flat, gflat)
+    eng = flat_engine(flat, gflat, RANGES)
     opt = getattr(lgteun_amd, 'Fused' + name)([torch.nn.Parameter(torch.zeros(1))], lr=1e-2, **kwargs)
     # state buffers: torch's initial zeros inside the ranges, a pattern outside them that must survive
     names = [n for n in opt.state_names() if n is not None]

@@ -158,14 +158,34 @@ def test_grad_norm_edge_values(case):
 N_FLAT = 100003
 RANGES = [(3, 30001), (40002, 70007), (70011, 99998)]          # gaps in front, between and behind; no start on a 16-byte boundary
 MAX_RANGE = max(b - a for a, b in RANGES)
-# (name, algo, flags, (lr, h0, h1, eps, weight_decay), state slots used, plain_adam): one option set of each algorithm + the plain-Adam route
+# (name, algo, flags, (lr, h0, h1, eps, weight_decay), state slots used, plain_adam): one row per instance of the switch in optim_step
+# (k_optim.hip; the OPT_FIRST instances are step 1 of the momentum rows) + the plain-Adam route.  tests/test_gpu_optim_bits.py ties every
+# instance without controls to torch's device bits; the clipped and the averaging launches are tied to those here.
+_ADAM_HP, _RMS_HP = (1e-2, 0.9, 0.999, 1e-8), (1e-2, 0.99, 0.0, 1e-8)
 EX_SETS = [
-    ('Adam-wd', 0, 0, (1e-2, 0.9, 0.999, 1e-8, 1e-2), (1, 1, 0), 0),
-    ('AdamW-amsgrad', 1, 1, (1e-2, 0.9, 0.999, 1e-8, 1e-2), (1, 1, 1), 0),
+    ('Adam', 0, 0, _ADAM_HP + (0.0,), (1, 1, 0), 0),
+    ('Adam-wd', 0, 0, _ADAM_HP + (1e-2,), (1, 1, 0), 0),
+    ('Adam-amsgrad', 0, 1, _ADAM_HP + (0.0,), (1, 1, 1), 0),
+    ('Adam-amsgrad-wd', 0, 1, _ADAM_HP + (1e-2,), (1, 1, 1), 0),
+    ('AdamW', 1, 0, _ADAM_HP + (1e-2,), (1, 1, 0), 0),
+    ('AdamW-amsgrad', 1, 1, _ADAM_HP + (1e-2,), (1, 1, 1), 0),
+    ('SGD', 2, 0, (1e-2, 0.0, 0.0, 0.0, 0.0), (0, 0, 0), 0),
+    ('SGD-wd', 2, 0, (1e-2, 0.0, 0.0, 0.0, 1e-2), (0, 0, 0), 0),
     ('SGD-momentum', 2, 0, (1e-2, 0.9, 0.0, 0.0, 0.0), (1, 0, 0), 0),
+    ('SGD-momentum-wd', 2, 0, (1e-2, 0.9, 0.0, 0.0, 1e-2), (1, 0, 0), 0),
+    ('SGD-nesterov', 2, 2, (1e-2, 0.9, 0.0, 0.0, 0.0), (1, 0, 0), 0),
+    ('SGD-nesterov-wd', 2, 2, (1e-2, 0.9, 0.0, 0.0, 1e-2), (1, 0, 0), 0),
+    ('RMSprop', 3, 0, _RMS_HP + (0.0,), (1, 0, 0), 0),
+    ('RMSprop-wd', 3, 0, _RMS_HP + (1e-2,), (1, 0, 0), 0),
+    ('RMSprop-centered', 3, 4, _RMS_HP + (0.0,), (1, 0, 1), 0),
+    ('RMSprop-centered-wd', 3, 4, _RMS_HP + (1e-2,), (1, 0, 1), 0),
+    ('RMSprop-momentum', 3, 0, (1e-2, 0.99, 0.9, 1e-8, 0.0), (1, 1, 0), 0),
+    ('RMSprop-momentum-wd', 3, 0, (1e-2, 0.99, 0.9, 1e-8, 1e-2), (1, 1, 0), 0),
     ('RMSprop-centered-momentum', 3, 4, (1e-2, 0.99, 0.9, 1e-8, 0.0), (1, 1, 1), 0),
-    ('Adam-plain', 0, 0, (1e-2, 0.9, 0.999, 1e-8, 0.0), (1, 1, 0), 1),
+    ('RMSprop-centered-momentum-wd', 3, 4, (1e-2, 0.99, 0.9, 1e-8, 1e-2), (1, 1, 1), 0),
+    ('Adam-plain', 0, 0, _ADAM_HP + (0.0,), (1, 1, 0), 1),
 ]
+EMA_SETS = [s for s in EX_SETS if s[0] in ('AdamW-amsgrad', 'SGD-momentum', 'Adam-plain')]
 
 
 class _Flat:
@@ -224,7 +244,7 @@ def test_clipped_step_is_bitwise_the_step_on_premultiplied_gradients(name, algo,
 
 
 @pytest.mark.parametrize('decay', [0.999, 0.9])
-@pytest.mark.parametrize('name,algo,flags,hp,slots,plain', [EX_SETS[1], EX_SETS[2], EX_SETS[4]], ids=[EX_SETS[i][0] for i in (1, 2, 4)])
+@pytest.mark.parametrize('name,algo,flags,hp,slots,plain', EMA_SETS, ids=[s[0] for s in EMA_SETS])
 def test_ema_in_the_optimizer_launch_is_torchs_lerp(name, algo, flags, hp, slots, plain, decay):
     """after each of three lg_optim_step_ex calls with `ema`: ema == torch._foreach_lerp_(previous average, new parameters, 1 - decay) on
     the device, inside the ranges; outside them the average keeps its initial bits; the parameters are those of the same calls without it"""
