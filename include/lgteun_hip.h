@@ -114,7 +114,7 @@ typedef struct lg_plan lg_plan; /* host-side, immutable after creation */
 
 const char* lg_version(void);
 /* Bumped whenever a struct layout, an argument meaning or a caller-provided buffer size changes (2: lg_config.variant, the data step's
- * tmp of 3*B*C*H*W/4 + B*H*W floats).  Additions keep it: lg_op_lgt_stages, lg_workspace_deadout, LG_FLAG_STAGEWISE, the lg_debug_stage_* entries and the classical baselines (lg_classical_workspace_bytes, lg_interp23_up4, lg_sfim, lg_gsa, then lg_wavelet, lg_wavelet_taps) came without a bump (no struct,
+ * tmp of 3*B*C*H*W/4 + B*H*W floats).  Additions keep it: lg_op_lgt_stages, lg_workspace_deadout, LG_FLAG_STAGEWISE, the lg_debug_stage_* entries and the classical baselines (lg_classical_workspace_bytes, lg_interp23_up4, lg_sfim, lg_gsa, then lg_wavelet, lg_wavelet_taps, then lg_mtfglp_workspace_bytes, lg_mtf_glp) came without a bump (no struct,
  * argument or caller-sized buffer changed: workspaces are sized by lg_workspace_bytes, which grew for the plans that batch their dead stages).  A binding checks it at load time -- lgteun_amd/_lib.py does -- instead of passing a stale struct. */
 #define LG_ABI_VERSION 2
 int32_t lg_abi_version(void);
@@ -487,6 +487,26 @@ int lg_gsa(const float* ms, const float* pan, float* out, double* stats, int32_t
 int lg_wavelet(const float* ms, const float* pan, float* out, int32_t B, int32_t C, int32_t h, int32_t w, void* stream);
 /* out17: a HOST array that receives the taps lg_wavelet uses, by offset -8 .. 8: the block means of the response of interp23 to a unit impulse */
 int lg_wavelet_taps(double* out17);
+/* ---- MTF-GLP: the generalised Laplacian pyramid with an MTF-matched Gaussian, three injection rules (lgteun_amd/mtf_glp.py) ----
+ * With u_k = interp23(ms)_k and SFIM's statistics (mu = mean pan, m_k = mean u_k, a_k = std(u_k) / std(pan), both std over N - 1; a_k = 0 for a constant
+ * PAN): p_k = a_k (pan - mu) + m_k; D_f(i, j) = sum_a sum_b t_f[a] t_f[b] pan(clamp(4 i + 2 + a - r), clamp(4 j + 2 + b - r)) with r = n_taps / 2 (replicate
+ * border, the rule of lg_fir_decimate4 at phase 2); q_k = a_k (D_k - mu) + m_k; L_k = interp23(q_k) (circular).  Then, clipped to [0, 1] with one rounding:
+ *   LG_MTFGLP_GLP  out_k = u_k + (p_k - L_k)
+ *   LG_MTFGLP_HPM  out_k = u_k p_k / (L_k + 1e-8)
+ *   LG_MTFGLP_CBD  out_k = u_k + g_k (p_k - L_k), g_k = sum (u_k - m_k)(L_k - mean L_k) / sum (L_k - mean L_k)^2; g_k = 0 where a_k = 0, where the
+ *                  denominator is not positive or not finite, or where the quotient is not finite: out_k = clip(u_k) bit for bit.
+ * taps: a DEVICE array [n_filters, n_taps] of fp64 (wald.mtf_taps: rows that sum to 1); n_filters is 1 (one filtered plane serves every band) or C; n_taps odd,
+ * in 1 .. 63.  stats: NULL or a device array [B, 2 C] of fp64 that receives a, then g (1 for GLP and HPM).  Launches: SFIM's moments and finish, one low-pass
+ * that writes D as fp64 [B, n_filters, h, w] into the workspace, for CBD a second moments pass and its finish, and the apply pass; neither u nor L is stored.
+ * Tensors, limits, alignment, checks and guarantees (same bits on every call, a sample's bits do not depend on its batch, the workspace needs no initialisation)
+ * are those of lg_sfim; taps 8-byte aligned. */
+#define LG_MTFGLP_GLP 0
+#define LG_MTFGLP_HPM 1
+#define LG_MTFGLP_CBD 2
+/* bytes of workspace lg_mtf_glp needs; 0 for anything the call rejects */
+size_t lg_mtfglp_workspace_bytes(int32_t B, int32_t C, int32_t h, int32_t w, int32_t n_filters, int32_t mode);
+int lg_mtf_glp(const float* ms, const float* pan, float* out, double* stats, const double* taps, int32_t n_filters, int32_t n_taps, int32_t mode, int32_t B,
+               int32_t C, int32_t h, int32_t w, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -46,6 +46,7 @@ LG_OPT_ADAM, LG_OPT_ADAMW, LG_OPT_SGD, LG_OPT_RMSPROP = 0, 1, 2, 3      # lg_opt
 LG_OPT_AMSGRAD, LG_OPT_NESTEROV, LG_OPT_CENTERED = 1, 2, 4             # lg_optim_step: flags
 LG_DT_U8, LG_DT_U16, LG_DT_F32 = 0, 1, 2                                # lg_pyr_down2 / lg_batch_assemble: sample type of the store
 LG_CLASSICAL_SFIM, LG_CLASSICAL_GSA = 0, 1                              # lg_classical_workspace_bytes: method
+LG_MTFGLP_GLP, LG_MTFGLP_HPM, LG_MTFGLP_CBD = 0, 1, 2                   # lg_mtf_glp: mode (the injection rule)
 LG_ABI_VERSION = 2   # include/lgteun_hip.h: checked against lg_abi_version() when the library is loaded
 
 
@@ -173,6 +174,9 @@ SIGNATURES = {
     'lg_gsa': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
     'lg_wavelet': (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     'lg_wavelet_taps': (c_int32, [c_void_p]),
+    'lg_mtfglp_workspace_bytes': (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    'lg_mtf_glp': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                             c_size_t, c_void_p]),
 }
 
 

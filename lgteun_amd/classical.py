@@ -97,9 +97,14 @@ def fuse_scene(method, ms, pan, bit_depth=None, norm_input=False, out_dtype='flo
     on the device.  The arguments are scene.fuse_scene's: samples as numpy arrays or tensors (uint8, uint16 or its int16 view, float32);
     bit_depth / norm_input: the normalisation of the tile gather (norm_input: one correctly rounded fp32 division by 2**bit_depth - 0.5, then
     one multiplication by the fp32 reciprocal of that number); out_dtype 'uint16': digital numbers by lg_scene_to_u16 (needs bit_depth)."""
-    from . import scene as sc
     if method not in SCENE_METHODS:
         raise ValueError(f"method must be 'gsa', 'sfim' or 'wavelet' (got {method!r})")
+    return _fuse_scene(SCENE_METHODS[method], ms, pan, bit_depth, norm_input, out_dtype, device)
+
+
+def _fuse_scene(fn, ms, pan, bit_depth, norm_input, out_dtype, device):
+    """classical.fuse_scene and mtf_glp.fuse_scene: the normalisation, `fn(ms [1, C, h, w], pan [1, 1, 4h, 4w])` on the whole scene, the conversion"""
+    from . import scene as sc
     if out_dtype not in ('float32', 'uint16'):
         raise ValueError(f"out_dtype must be 'float32' or 'uint16' (got {out_dtype!r})")
     if (norm_input or out_dtype == 'uint16') and bit_depth is None:
@@ -122,7 +127,7 @@ def fuse_scene(method, ms, pan, bit_depth=None, norm_input=False, out_dtype='flo
             t = t * float(np.float32(1.0) / np.float32(divisor))        # scene.fuse_scene's post_scale
         return t
     with torch.cuda.device(dev):
-        fused = SCENE_METHODS[method](normalised(ms_t).view(1, C, H // 4, W // 4), normalised(pan_t).view(1, 1, H, W))[0]
+        fused = fn(normalised(ms_t).view(1, C, H // 4, W // 4), normalised(pan_t).view(1, 1, H, W))[0]
         if out_dtype == 'float32':
             return fused
         out = torch.empty(C, H, W, dtype=torch.uint16, device=dev)

@@ -23,6 +23,7 @@
 //   k_cl_wavelet     grid (tile, sample), the whole method in one launch: out_k = clip(pan - P + M_k) with P the 4 x 4 block mean of PAN and M_k the
 //                    block mean of u_k, which is a separable 17-tap circular FIR on ms itself (cl_wavelet_taps).  A lane owns 4 x 4 blocks: 16-byte
 //                    PAN loads, 16-byte stores, M_k from an ms halo tile in LDS (columns, then rows).  No u, no moments, no workspace.
+//   k_mg_*           MTF-GLP with its three injection rules (lg_mtf_glp), on the same tiles: described where they stand, below k_cl_wavelet.
 // No atomics; a workgroup sees one sample and the grid of a sample depends on C, h and w only, so a sample has the same bits alone and inside
 // any batch.  All indexing into tensors is 64-bit.
 #include <cmath>
@@ -97,8 +98,10 @@ __device__ __forceinline__ void cl_ms_load(const float* __restrict__ ms, int h, 
 }
 
 // u of one band for a tile from its loaded ms samples -> U[16][32].  S: CL_SCRATCH doubles.  Ends WITHOUT a barrier: the caller puts one in front of
-// its reads of U.  A following call may start at once: its first writes go to M, which was last read three barriers ago.
-__device__ __forceinline__ void cl_up_band(const float (&v)[CL_MLOADS], double* S, double* U) {
+// its reads of U.  A following call may start at once: its first writes go to M, which was last read three barriers ago.  T: float (ms samples) or
+// double (MTF-GLP's low-resolution plane q_k, which exists in registers only).
+template <typename T>
+__device__ __forceinline__ void cl_up_band(const T (&v)[CL_MLOADS], double* S, double* U) {
     double* M = S;
     double* R1 = M + CL_MR * CL_MC;
     double* L1 = R1 + CL_MR * CL_L1C;
@@ -519,6 +522,216 @@ __global__ __launch_bounds__(CL_NT, 4) void k_cl_wavelet(const float* __restrict
     }
 }
 
+// ---- MTF-GLP: the generalised Laplacian pyramid with an MTF-matched Gaussian and three injection rules.  SFIM's moments and finish give
+// mu, m_k and a_k; then
+//   k_mg_lowpass   grid (tile, filter, sample): D_f(i, j) = the separable Gaussian of filter f on PAN minus the pivot at (4 i + 2, 4 j + 2), replicate border,
+//                  evaluated at the decimated positions only -- rows into LDS, then columns (k_wald.hip's scheme), fp64 [B, F, h, w] in the workspace.
+//   k_mg_moments   cbd only, grid (gx, sample) like k_cl_moments: per band the tiles of u_k (cl_up_band on ms) and of L_k (cl_up_band on q_k = a_k (D_k - mu) + m_k,
+//                  the affine map applied where D is loaded, modulo the sides), both minus m_k; wave j sums vector j of {u, L, u L, L L} over the tile and
+//                  lane 0 adds to its slot in LDS -- one order, always.  k_mg_finish: the partials in ascending order, then g_k per band.
+//   k_mg_apply     grid (tile, sample): per band the tile of u, the tile of L, the thread's two PAN pixels, the rule, ONE rounding; the next band's ms and D
+//                  samples are in flight under the current band's eight LDS passes.  The workgroup of tile 0 writes stats.
+// Neither u nor L is ever stored in memory.
+constexpr int MG_TO = 16, MG_MAX_TAPS = 63, MG_SPAN = 4 * (MG_TO - 1) + MG_MAX_TAPS;      // low-pass: outputs per tile edge, PAN rows under one tile's column taps
+constexpr int MG_LDS = CL_SCRATCH + 2 * CL_PX;                           // doubles: the scratch of cl_up_band, the tile of u, the tile of L
+constexpr int MG_PER_CU = 3, MG_RESIDENT = MG_PER_CU * CL_CUS;           // workgroups per sample of the second moments pass, at most
+static_assert(MG_PER_CU * (MG_LDS + 4 * CL_MAX_C) * (int)sizeof(double) <= CL_CU_LDS, "three workgroups of the tile kernels per CU");
+static_assert(CL_NT / 64 == 4 && MG_TO * MG_TO == CL_NT, "a wave per sum of the second moments pass; a thread per output of the low-pass tile");
+
+__device__ __forceinline__ int mg_clamp(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
+
+__global__ __launch_bounds__(CL_NT) void k_mg_lowpass(const float* __restrict__ pan, const double* __restrict__ taps, double* __restrict__ dlow, int h, int w,
+                                                      int n_taps, int tiles_x) {
+    __shared__ double tp[MG_MAX_TAPS];
+    __shared__ double rowf[MG_SPAN][MG_TO + 1];
+    const int H4 = 4 * h, W4 = 4 * w, r = n_taps >> 1, tid = threadIdx.x;
+    const int oy0 = (blockIdx.x / tiles_x) * MG_TO, ox0 = (blockIdx.x % tiles_x) * MG_TO;
+    const long b = blockIdx.z, f = blockIdx.y;
+    const float* __restrict__ pan_b = pan + b * ((long)H4 * W4);
+    const double pv = (double)pan_b[0];
+    if (tid < n_taps) tp[tid] = taps[f * n_taps + tid];
+    __syncthreads();
+    // row pass: slot s is PAN row 4 oy0 + 2 - r + s (clamped into the plane), column j the tile's j-th decimated position
+    const int rows = oy0 + MG_TO <= h ? MG_TO : h - oy0, span = 4 * (rows - 1) + n_taps;
+    const int y0 = 4 * oy0 + 2 - r, x0 = 4 * ox0 + 2 - r;
+    for (int t = tid; t < span * MG_TO; t += CL_NT) {
+        const int s = t / MG_TO, j = t - s * MG_TO;
+        if (ox0 + j >= w) continue;
+        const float* __restrict__ row = pan_b + (long)mg_clamp(y0 + s, H4) * W4;
+        const int xb = x0 + 4 * j;
+        double acc = 0.0;
+        for (int k = 0; k < n_taps; ++k) acc = fma(tp[k], (double)row[mg_clamp(xb + k, W4)] - pv, acc);
+        rowf[s][j] = acc;
+    }
+    __syncthreads();
+    const int ly = tid / MG_TO, lx = tid - ly * MG_TO;
+    if (ly >= rows || ox0 + lx >= w) return;
+    double acc = 0.0;
+    for (int k = 0; k < n_taps; ++k) acc = fma(tp[k], rowf[4 * ly + k][lx], acc);
+    dlow[(b * gridDim.y + f) * ((long)h * w) + (long)(oy0 + ly) * w + ox0 + lx] = acc;
+}
+
+// the samples of q_k = a (D - mu) + m the tile at (Y0, X0) depends on, where cl_ms_load takes those of ms: D is the filtered PAN minus the pivot, mpc = mu minus the pivot
+__device__ __forceinline__ void mg_q_load(const double* __restrict__ dl, int h, int w, int Y0, int X0, double a, double mpc, double m, double (&v)[CL_MLOADS]) {
+    const int my0 = Y0 / 4 - 8, mx0 = X0 / 4 - 8;
+#pragma unroll
+    for (int u = 0; u < CL_MLOADS; ++u) {
+        const int i = threadIdx.x + u * CL_NT, r = i / CL_MC, c = i - r * CL_MC;
+        v[u] = 0.0;
+        if (i < CL_MR * CL_MC) v[u] = fma(a, dl[(long)cl_mod(my0 + r, h) * w + cl_mod(mx0 + c, w)] - mpc, m);
+    }
+}
+
+// part [B][gx][4 C]: per band the sums over the sample of u - m, L - m, (u - m)(L - m), (L - m)^2 (m = m_k: both vectors have a mean near zero, so the
+// covariance and the variance lose nothing to cancellation)
+__global__ __launch_bounds__(CL_NT) void k_mg_moments(const float* __restrict__ ms, const double* __restrict__ dlow, const double* __restrict__ coef,
+                                                      double* __restrict__ part, int C, int F, int h, int w, int tiles_x, int tiles) {
+    extern __shared__ double cl_lds[];
+    double* U = cl_lds + CL_SCRATCH;
+    double* Lt = U + CL_PX;
+    double* acc = Lt + CL_PX;                    // [4 C]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, gx = gridDim.x;
+    const int H4 = 4 * h, W4 = 4 * w;
+    const long b = blockIdx.y, lp = (long)h * w;
+    const float* __restrict__ ms_b = ms + b * C * lp;
+    const double* __restrict__ dl_b = dlow + b * F * lp;
+    const double* __restrict__ co = coef + b * (3 * C + 1);
+    const double mpc = co[0];
+    for (int e = tid; e < 4 * C; e += CL_NT) acc[e] = 0.0;      // (the barriers inside cl_up_band order this before the first use)
+    float v[CL_MLOADS], vn[CL_MLOADS] = {};
+    double q[CL_MLOADS], qn[CL_MLOADS] = {};
+    {
+        const int Y0 = (blockIdx.x / tiles_x) * CL_TH, X0 = (blockIdx.x % tiles_x) * CL_TW;
+        cl_ms_load(ms_b, h, w, Y0, X0, v);
+        mg_q_load(dl_b, h, w, Y0, X0, co[1 + C], mpc, co[1], q);
+    }
+    for (int t = blockIdx.x; t < tiles; t += gx) {
+        const int Y0 = (t / tiles_x) * CL_TH, X0 = (t % tiles_x) * CL_TW;
+        for (int k = 0; k < C; ++k) {
+            const int kn = k + 1 < C ? k + 1 : 0, tn = k + 1 < C ? t : t + gx;
+            if (tn < tiles) {
+                const int Yn = (tn / tiles_x) * CL_TH, Xn = (tn % tiles_x) * CL_TW;
+                cl_ms_load(ms_b + kn * lp, h, w, Yn, Xn, vn);
+                mg_q_load(dl_b + (F == 1 ? 0 : kn) * lp, h, w, Yn, Xn, co[1 + C + kn], mpc, co[1 + kn], qn);
+            }
+            cl_up_band(v, cl_lds, U);
+            cl_up_band(q, cl_lds, Lt);
+            __syncthreads();
+            const double m = co[1 + k];
+            double s = 0.0;
+#pragma unroll
+            for (int u = 0; u < CL_PX / 64; ++u) {
+                const int p = lane + 64 * u;
+                const bool in = Y0 + p / CL_TW < H4 && X0 + p % CL_TW < W4;      // what a ragged tile holds outside the image counts as 0
+                const double uc = U[p] - m, lc = Lt[p] - m;
+                const double term = wave == 0 ? uc : wave == 1 ? lc : wave == 2 ? uc * lc : lc * lc;
+                s += in ? term : 0.0;
+            }
+            s = wave_sum(s);
+            if (lane == 0) acc[4 * k + wave] += s;
+#pragma unroll
+            for (int u = 0; u < CL_MLOADS; ++u) {
+                v[u] = vn[u];
+                q[u] = qn[u];
+            }
+            // no barrier: the next cl_up_band writes U and Lt in its last pass, four barriers from here
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < 4 * C; e += CL_NT) part[(b * gx + blockIdx.x) * (4 * C) + e] = acc[e];
+}
+
+// g_k = cov(u_k, L_k) / var(L_k) into coef[b][1 + 2 C + k]; 0 for a band whose a_k is 0 (a constant PAN), whose variance is not positive or not finite, or
+// whose gain is not finite
+__global__ __launch_bounds__(CL_NT) void k_mg_finish(const double* __restrict__ part, double* __restrict__ coef, int C, int gx, double N) {
+    __shared__ double sums[4 * CL_MAX_C];
+    const long b = blockIdx.x;
+    const int ns = 4 * C;
+    for (int e = threadIdx.x; e < ns; e += CL_NT) {
+        const double* __restrict__ pe = part + b * gx * ns + e;
+        double s = 0.0;
+        int j = 0;
+        for (; j + 8 <= gx; j += 8) {      // eight loads in flight, added in ascending order
+            double q[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) q[u] = pe[(long)(j + u) * ns];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) s += q[u];
+        }
+        for (; j < gx; ++j) s += pe[(long)j * ns];
+        sums[e] = s;
+    }
+    __syncthreads();
+    const int k = threadIdx.x;
+    if (k >= C) return;
+    double* co = coef + b * (3 * C + 1);
+    const double su = sums[4 * k], sl = sums[4 * k + 1], cov = sums[4 * k + 2] - su * sl / N, var = sums[4 * k + 3] - sl * sl / N;
+    const double g = cov / var;
+    const bool ok = co[1 + C + k] != 0.0 && var > 0.0 && var - var == 0.0 && g - g == 0.0;
+    co[1 + 2 * C + k] = ok ? g : 0.0;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(CL_NT) void k_mg_apply(const float* __restrict__ ms, const float* __restrict__ pan, const double* __restrict__ dlow,
+                                                    float* __restrict__ out, const double* __restrict__ coef, double* __restrict__ stats, int C, int F, int h,
+                                                    int w, int tiles_x) {
+    extern __shared__ double cl_lds[];
+    double* U = cl_lds + CL_SCRATCH;
+    double* Lt = U + CL_PX;
+    const int tid = threadIdx.x, H4 = 4 * h, W4 = 4 * w;
+    const int Y0 = (blockIdx.x / tiles_x) * CL_TH, X0 = (blockIdx.x % tiles_x) * CL_TW;
+    const long b = blockIdx.y, lp = (long)h * w, plane = (long)H4 * W4;
+    const float* __restrict__ ms_b = ms + b * C * lp;
+    const double* __restrict__ dl_b = dlow + b * F * lp;
+    const float* __restrict__ pan_b = pan + b * plane;
+    float* __restrict__ out_b = out + b * C * plane;
+    const double* __restrict__ co = coef + b * (3 * C + 1);
+    const double pv = (double)pan_b[0], mpc = co[0];
+    if (stats && blockIdx.x == 0 && tid < C) {      // a_k, then g_k (1 where the rule has no gain)
+        stats[b * (2 * C) + tid] = co[1 + C + tid];
+        stats[b * (2 * C) + C + tid] = MODE == LG_MTFGLP_CBD ? co[1 + 2 * C + tid] : 1.0;
+    }
+    float v[CL_MLOADS], vn[CL_MLOADS] = {};
+    double q[CL_MLOADS], qn[CL_MLOADS] = {};
+    cl_ms_load(ms_b, h, w, Y0, X0, v);
+    mg_q_load(dl_b, h, w, Y0, X0, co[1 + C], mpc, co[1], q);
+    const int p = 2 * tid, y = Y0 + p / CL_TW, x = X0 + p % CL_TW;
+    const bool in = y < H4 && x < W4;            // W4 is a multiple of 4 and x is even: both pixels or none
+    const long o = (long)y * W4 + x;
+    float2 pp = make_float2(0.f, 0.f);
+    if (in) pp = *reinterpret_cast<const float2*>(pan_b + o);
+    const double c0 = ((double)pp.x - pv) - mpc, c1 = ((double)pp.y - pv) - mpc;      // pan - mu
+    for (int k = 0; k < C; ++k) {
+        if (k + 1 < C) {
+            cl_ms_load(ms_b + (k + 1) * lp, h, w, Y0, X0, vn);
+            mg_q_load(dl_b + (F == 1 ? 0 : k + 1) * lp, h, w, Y0, X0, co[1 + C + k + 1], mpc, co[1 + k + 1], qn);
+        }
+        cl_up_band(v, cl_lds, U);
+        cl_up_band(q, cl_lds, Lt);
+        __syncthreads();
+        if (in) {
+            const double a = co[1 + C + k], m = co[1 + k];
+            const double u0 = U[p], u1 = U[p + 1], l0 = Lt[p], l1 = Lt[p + 1], p0 = fma(a, c0, m), p1 = fma(a, c1, m);
+            double o0, o1;
+            if (MODE == LG_MTFGLP_HPM) {
+                o0 = u0 * p0 / (l0 + 1e-8);
+                o1 = u1 * p1 / (l1 + 1e-8);
+            } else {
+                const double g = MODE == LG_MTFGLP_CBD ? co[1 + 2 * C + k] : 1.0;
+                o0 = fma(g, p0 - l0, u0);
+                o1 = fma(g, p1 - l1, u1);
+            }
+            *reinterpret_cast<float2*>(out_b + k * plane + o) = make_float2(cl_clip(o0), cl_clip(o1));
+        }
+#pragma unroll
+        for (int u = 0; u < CL_MLOADS; ++u) {
+            v[u] = vn[u];
+            q[u] = qn[u];
+        }
+        // no barrier: the next cl_up_band writes U and Lt in its last pass, four barriers from here
+    }
+}
+
 struct ClGeom {
     int tiles_x, tiles, gx, ns;
     size_t off[2], bytes;      // part, coef
@@ -582,7 +795,76 @@ int cl_fuse(const char* who, int method, const float* ms, const float* pan, floa
     return 0;
 }
 
+struct MgGeom {
+    ClGeom cl;                 // SFIM's: the tiles and the first moments pass
+    int gx2;                   // workgroups per sample of the second moments pass
+    size_t off[4], bytes;      // part, coef, D, part2 (cbd)
+};
+
+bool mg_geom(const char* who, int B, int C, int h, int w, int n_filters, int mode, MgGeom& g) {
+    if (!cl_geom(who, B, C, h, w, LG_CLASSICAL_SFIM, g.cl)) return false;
+    if (n_filters != 1 && n_filters != C) { lg_set_error("%s: n_filters must be 1 or C = %d (got %d)", who, C, n_filters); return false; }
+    if (mode != LG_MTFGLP_GLP && mode != LG_MTFGLP_HPM && mode != LG_MTFGLP_CBD) {
+        lg_set_error("%s: mode must be LG_MTFGLP_GLP, LG_MTFGLP_HPM or LG_MTFGLP_CBD (got %d)", who, mode);
+        return false;
+    }
+    g.gx2 = g.cl.tiles < MG_RESIDENT ? g.cl.tiles : MG_RESIDENT;
+    const size_t sz[4] = {(size_t)B * g.cl.gx * g.cl.ns * sizeof(double), (size_t)B * (3 * C + 1) * sizeof(double),
+                          (size_t)B * n_filters * h * w * sizeof(double), mode == LG_MTFGLP_CBD ? (size_t)B * g.gx2 * 4 * C * sizeof(double) : 0};
+    g.bytes = ws_layout(4, sz, g.off);
+    return true;
+}
+
+int mg_fuse(const char* who, const float* ms, const float* pan, float* out, double* stats, const double* taps, int n_filters, int n_taps, int mode, int B,
+            int C, int h, int w, void* workspace, size_t workspace_bytes, hipStream_t s) {
+    MgGeom g;
+    if (!mg_geom(who, B, C, h, w, n_filters, mode, g)) return -1;
+    if (n_taps < 1 || n_taps > MG_MAX_TAPS || !(n_taps & 1)) { lg_set_error("%s: n_taps must be odd, in 1..%d (got %d)", who, MG_MAX_TAPS, n_taps); return -1; }
+    if (!check_tensors(who, {{"ms", ms}, {"pan", pan}, {"out", out}})) return -1;
+    if (!taps) { lg_set_error("%s: taps is NULL", who); return -1; }
+    if ((uintptr_t)taps & 7) { lg_set_error("%s: taps must be 8-byte aligned", who); return -1; }
+    if ((uintptr_t)stats & 7) { lg_set_error("%s: stats must be 8-byte aligned", who); return -1; }
+    if (!check_workspace(who, workspace, workspace_bytes, g.bytes, "lg_mtfglp_workspace_bytes")) return -1;
+    if (int rc = cl_lds_attr(who)) return rc;
+    double* part = (double*)((char*)workspace + g.off[0]);
+    double* coef = (double*)((char*)workspace + g.off[1]);
+    double* dlow = (double*)((char*)workspace + g.off[2]);
+    double* part2 = (double*)((char*)workspace + g.off[3]);
+    const int tiles_x = g.cl.tiles_x, tiles = g.cl.tiles;
+    k_cl_moments<<<dim3(g.cl.gx, B), CL_NT, cl_moment_lds_doubles(C) * sizeof(double), s>>>(ms, pan, part, C, h, w, tiles_x, tiles, 0);
+    LG_CHECK_LAUNCH();
+    k_cl_finish<<<B, CL_NT, 0, s>>>(part, coef, nullptr, C, g.cl.gx, 16.0 * h * w, (double)h * w, 0);
+    LG_CHECK_LAUNCH();
+    const int lt_x = (w + MG_TO - 1) / MG_TO, lt = lt_x * ((h + MG_TO - 1) / MG_TO);
+    k_mg_lowpass<<<dim3(lt, n_filters, B), CL_NT, 0, s>>>(pan, taps, dlow, h, w, n_taps, lt_x);
+    LG_CHECK_LAUNCH();
+    const size_t lds = MG_LDS * sizeof(double);
+    if (mode == LG_MTFGLP_CBD) {
+        k_mg_moments<<<dim3(g.gx2, B), CL_NT, lds + 4 * C * sizeof(double), s>>>(ms, dlow, coef, part2, C, n_filters, h, w, tiles_x, tiles);
+        LG_CHECK_LAUNCH();
+        k_mg_finish<<<B, CL_NT, 0, s>>>(part2, coef, C, g.gx2, 16.0 * h * w);
+        LG_CHECK_LAUNCH();
+        k_mg_apply<LG_MTFGLP_CBD><<<dim3(tiles, B), CL_NT, lds, s>>>(ms, pan, dlow, out, coef, stats, C, n_filters, h, w, tiles_x);
+    } else if (mode == LG_MTFGLP_HPM) {
+        k_mg_apply<LG_MTFGLP_HPM><<<dim3(tiles, B), CL_NT, lds, s>>>(ms, pan, dlow, out, coef, stats, C, n_filters, h, w, tiles_x);
+    } else {
+        k_mg_apply<LG_MTFGLP_GLP><<<dim3(tiles, B), CL_NT, lds, s>>>(ms, pan, dlow, out, coef, stats, C, n_filters, h, w, tiles_x);
+    }
+    LG_CHECK_LAUNCH();
+    return 0;
+}
+
 }  // namespace
+
+extern "C" size_t lg_mtfglp_workspace_bytes(int32_t B, int32_t C, int32_t h, int32_t w, int32_t n_filters, int32_t mode) {
+    MgGeom g;
+    return mg_geom("mtfglp_workspace_bytes", B, C, h, w, n_filters, mode, g) ? g.bytes : 0;
+}
+
+extern "C" int lg_mtf_glp(const float* ms, const float* pan, float* out, double* stats, const double* taps, int32_t n_filters, int32_t n_taps, int32_t mode,
+                          int32_t B, int32_t C, int32_t h, int32_t w, void* workspace, size_t workspace_bytes, void* stream) {
+    return mg_fuse("mtf_glp", ms, pan, out, stats, taps, n_filters, n_taps, mode, B, C, h, w, workspace, workspace_bytes, (hipStream_t)stream);
+}
 
 extern "C" size_t lg_classical_workspace_bytes(int32_t B, int32_t C, int32_t h, int32_t w, int32_t method) {
     ClGeom g;

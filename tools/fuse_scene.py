@@ -4,9 +4,11 @@ dataset.read_tiff, fuses them tile by tile on the GPU (lgteun_amd/scene.py) and 
     python tools/fuse_scene.py PREFIX --checkpoint model.state.pth [--tile 128] [--overlap 32] [--bit-depth 11] [--norm-input]
                                [--batch B] [--float] [--out FILE]
     python tools/fuse_scene.py PREFIX --method gsa|sfim|wavelet [--bit-depth 11] [--norm-input] [--float] [--out FILE]
+    python tools/fuse_scene.py PREFIX --method mtf_glp|mtf_glp_hpm|mtf_glp_cbd [--mtf-gains g [g ...]] [--bit-depth 11] ...
 
---method gsa / sfim / wavelet (lgteun_amd/classical.py) needs no checkpoint and no tiles: the whole scene is fused in one call, with the same
-normalisation and the same conversion to digital numbers.
+--method gsa / sfim / wavelet (lgteun_amd/classical.py) and mtf_glp / mtf_glp_hpm / mtf_glp_cbd (lgteun_amd/mtf_glp.py) need no checkpoint and no
+tiles: the whole scene is fused in one call, with the same normalisation and the same conversion to digital numbers.  --mtf-gains: the sensor's MTF
+gains at Nyquist, one for all bands or one per band; without them a placeholder (0.3) applies, which is no sensor's value.
 
 The checkpoint is a plain-tensor file ({'core_module': state_dict}, what Base_model.save writes and tools/convert_checkpoint.py makes of a
 reference-era file); the band count and the stage count are read from it.  The output holds uint16 digital numbers
@@ -38,7 +40,9 @@ def load_module(path, device='cuda:0'):
 def parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('prefix')
-    ap.add_argument('--method', choices=['network', 'gsa', 'sfim', 'wavelet'], default='network')
+    ap.add_argument('--method', choices=['network', 'gsa', 'sfim', 'wavelet', 'mtf_glp', 'mtf_glp_hpm', 'mtf_glp_cbd'], default='network')
+    ap.add_argument('--mtf-gains', type=float, nargs='+', default=None, metavar='g',
+                    help="--method mtf_glp*: the sensor's MTF gain at Nyquist, one for all bands or one per band (default: a placeholder, 0.3)")
     ap.add_argument('--checkpoint', default=None, help='required for --method network')
     ap.add_argument('--tile', type=int, nargs='+', default=[128], help='one side, or height and width')
     ap.add_argument('--overlap', type=int, default=32)
@@ -64,7 +68,12 @@ def main():
     if ms.dtype != pan.dtype or ms.dtype.name not in ('uint8', 'uint16'):
         ms, pan = ms.astype(np.float64).astype(np.float32), pan.astype(np.float64).astype(np.float32)      # like PSDataset
     ms_chw = np.ascontiguousarray(ms.transpose(2, 0, 1))
-    if a.method != 'network':
+    if a.method.startswith('mtf_glp'):
+        from lgteun_amd import mtf_glp
+        gains = a.mtf_gains[0] if a.mtf_gains is not None and len(a.mtf_gains) == 1 else a.mtf_gains
+        fused = mtf_glp.fuse_scene(mtf_glp.SCENE_METHODS[a.method], ms_chw, pan[np.newaxis], gains_ms=gains, bit_depth=a.bit_depth, norm_input=a.norm_input,
+                                   out_dtype='float32' if a.float else 'uint16')
+    elif a.method != 'network':
         from lgteun_amd import classical
         fused = classical.fuse_scene(a.method, ms_chw, pan[np.newaxis], bit_depth=a.bit_depth, norm_input=a.norm_input,
                                      out_dtype='float32' if a.float else 'uint16')

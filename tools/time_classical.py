@@ -1,7 +1,8 @@
-"""What the classical baselines cost on the GPU (lgteun_amd/classical.py): ms per call of `sfim`, `gsa` and `wavelet` with the call synchronised, the
+"""What the classical baselines cost on the GPU (lgteun_amd/classical.py, lgteun_amd/mtf_glp.py): ms per call of `sfim`, `gsa`, `wavelet` and of
+`mtf_glp` with each of its three rules (default gains: one filtered plane per sample) in the same run, with the call synchronised, the
 median of 20 runs after 5 warm-up runs, at C = 4 and C = 8 with PAN 128 x 128 (batch 1 and batch 32) and for one 4096 x 4096 scene of C = 4.
 Beside each: the bytes the passes must move (SFIM and GSA: the moments pass reads ms and pan, the apply pass reads them again and writes the
-output; Wavelet: ms and pan read once, the output written once) divided by the time, as a fraction of the HBM bandwidth (--hbm-gbs, default 8000: the MI355X's 8 TB/s), and the ms per image of the float64
+output; Wavelet: ms and pan read once, the output written once; MTF-GLP: see the comment below) divided by the time, as a fraction of the HBM bandwidth (--hbm-gbs, default 8000: the MI355X's 8 TB/s), and the ms per image of the float64
 numpy restatement (tests/classical_ref.py, tests/wavelet_ref.py) on the same box (--no-host skips it).  Prints one JSON line.   python tools/time_classical.py"""
 import argparse
 import json
@@ -18,7 +19,8 @@ import torch  # noqa: E402
 
 import classical_ref as cr  # noqa: E402
 import wavelet_ref as wr  # noqa: E402
-from lgteun_amd import classical  # noqa: E402
+import mtf_glp_ref as mr  # noqa: E402
+from lgteun_amd import classical, mtf_glp  # noqa: E402
 
 CASES = [(1, 4, 32, 32), (32, 4, 32, 32), (1, 8, 32, 32), (32, 8, 32, 32), (1, 4, 1024, 1024)]      # B, C, h, w
 
@@ -49,8 +51,15 @@ def main():
         ms = torch.from_numpy(ms_np).cuda()[None].repeat(B, 1, 1, 1)
         pan = torch.from_numpy(pan_np).cuda()[None, None].repeat(B, 1, 1, 1)
         row = {}
-        for name, fn, host, reads in (('sfim', classical.sfim, cr.sfim, 2), ('gsa', classical.gsa, cr.gsa, 2), ('wavelet', classical.wavelet, wr.wavelet, 1)):
+        glp = {m: (lambda ms, pan, m=m: mtf_glp.mtf_glp(ms, pan, m), lambda ms, pan, m=m: mr.mtf_glp(ms, pan, m, [mr.EQUAL_GAIN] * ms.shape[0]))
+               for m in mr.MODES}
+        for name, fn, host, reads in (('sfim', classical.sfim, cr.sfim, 2), ('gsa', classical.gsa, cr.gsa, 2), ('wavelet', classical.wavelet, wr.wavelet, 1),
+                                      ('mtf_glp', *glp['glp'], 2), ('mtf_glp_hpm', *glp['hpm'], 2), ('mtf_glp_cbd', *glp['cbd'], 3)):
             moved = 4 * B * (reads * (C * h * w + 16 * h * w) + C * 16 * h * w)
+            if name.startswith('mtf_glp'):
+                # equal gains: ms is read by the moments pass, by cbd's second moments pass and by the apply pass; pan by the moments pass, the low-pass and
+                # the apply pass; the one fp64 plane D is written once and read by the apply pass and by cbd's second moments pass
+                moved = B * (4 * reads * C * h * w + 4 * 3 * 16 * h * w + 8 * reads * h * w + 4 * C * 16 * h * w)
             ms_call = median_ms(lambda: fn(ms, pan), a.warmup, a.runs)
             row[name] = dict(bytes_moved=moved, ms_per_call=round(ms_call, 4), ms_per_image=round(ms_call / B, 4), gb_per_s=round(moved / ms_call / 1e6, 1),
                              hbm_fraction=round(moved / ms_call / 1e6 / a.hbm_gbs, 4))
