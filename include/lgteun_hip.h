@@ -322,6 +322,31 @@ int lg_iqa_ref(const float* pred, const float* gt, double* out, int32_t B, int32
 int lg_iqa_no_ref(const float* pred, const float* pan, const float* ms, double* out, int32_t B, int32_t C, int32_t H, int32_t W,
                   float scale, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the extended indices (metrics.ref_evaluate_ext / no_ref_evaluate_ext; kernels in lgteun_amd/csrc/k_iqa_ext.hip; definitions:
+ * DESIGN.md 3.8.1) ----  The conventions of the block above: every element times `scale` in fp32 first, fp64 after that, per-workgroup partials
+ * in the workspace plus a fixed-order pass, no atomics, a partition that depends on the shape only -- repeated calls give the same bits and
+ * row b of a batch equals the row of image b scored alone.  Arguments are validated before any HIP call and lg_last_error says why; a rejected
+ * call launches and writes nothing.  Shapes: 1 <= B <= 65535; 2 <= C <= LG_IQA_Q2N_MAX_BANDS; LG_IQA_Q2N_BLOCK <= H, W <= 8192.  The workspace is
+ * 8-byte aligned; what it held before does not matter.
+ *   Q2n  the hypercomplex Q on N = 2, 4 or 8 components (the smallest N >= C; bands C .. N-1 are zero planes), the mean over the non-overlapping
+ *        32 x 32 blocks of the image extended to multiples of 32 by mirroring (lines L-1, L-2, ... follow line L-1; rows first).  Per block and
+ *        band the ground truth's mean a and deviation c (two passes, n - 1; c = 0 counts as 1) map BOTH images: v -> (v - a) / c + 1.  A block's
+ *        sums are one tree of pairwise additions, the one metrics._block_sum restates, so a flat block takes the host's t3 == 0 branch.
+ *   SCC  sum FG / sqrt(sum F^2 sum G^2) of the Sobel magnitudes at the (H-2)(W-2) interior pixels of all bands; 1 if both sums of squares are
+ *        zero, 0 if exactly one is.
+ *   CC   the mean over bands of Pearson's r (centred moments, two passes); NaN if a band of either image is constant (min == max). */
+#define LG_IQA_Q2N_BLOCK 32     /* Q2n block side                                     metrics.Q2N_BLOCK */
+#define LG_IQA_Q2N_MAX_BANDS 8  /* octonions: Q8                                      metrics.Q2N_MAX_BANDS */
+/* bytes of workspace lg_iqa_ref_ext / lg_iqa_q2n need for [B, C, H, W] images; 0 for a shape they reject */
+size_t lg_iqa_ext_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+/* pred, gt [B,C,H,W] fp32 -> out [B,3] fp64 = Q2n(gt, pred), SCC, CC: the three columns metrics.ref_evaluate_ext adds to lg_iqa_ref's five */
+int lg_iqa_ref_ext(const float* pred, const float* gt, double* out, int32_t B, int32_t C, int32_t H, int32_t W, float scale,
+                   void* workspace, size_t workspace_bytes, void* stream);
+/* gt, fused [B,C,H,W] fp32 -> out [B] fp64 = Q2n alone (gt's per-block statistics map both images).  D_lambda_K = 1 - Q2n(ms, the fused
+ * image low-passed per band by its MTF-matched Gaussian and decimated: lg_fir_decimate4 on fused * scale), composed in device_metrics.py. */
+int lg_iqa_q2n(const float* gt, const float* fused, double* out, int32_t B, int32_t C, int32_t H, int32_t W, float scale,
+               void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the no-reference training loss 1 - QNR and its gradient (Engine.train_step with noref_weight; kernels in lgteun_amd/csrc/k_qnr.hip) ----
  * The reference's QNRLoss (models/base/losses.py:141-153) over D_lambda_torch / D_s_torch / QIndex_torch (models/base/metrics.py:336-397):
  * NOT the 32-pixel-block indices of lg_iqa_no_ref.  out [B,C,H,W] is the fused image, pan [B,1,H,W], ms [B,C,H/4,W/4], pan_l [B,1,H/4,W/4],

@@ -255,16 +255,25 @@ class Base_model:
         to digital numbers before the metrics / the TIFF writer only with cfg.norm_input (base_model.py:296,311-316).
         cfg.eval_metrics: 'host' (default) scores every image with the float64 numpy functions of metrics.py; 'device' scores every batch
         on the GPU (device_metrics.py: the same definitions in fp64 HIP kernels), keeps the rows there and copies them to the host once,
-        at the end -- the fused images leave the device only for the TIFF writer (save=True)."""
+        at the end -- the fused images leave the device only for the TIFF writer (save=True).
+        cfg.eval_indices: 'standard' (default) or 'extended', which adds the literature's columns on either route: Q2n / SCC / CC behind the
+        five, D_lambda_K / HQNR behind the three (MTF gains: cfg.mtf_gains_ms, else wald.DEFAULT_GAIN_MS).  The extended set needs 2 .. 8
+        bands and images of at least 32 x 32 (ref=True) or 128 x 128 (ref=False): Q2n works on 32 x 32 blocks."""
         from .dataset import save_image
         metrics_on = self.cfg.get('eval_metrics', 'host')
         if metrics_on not in ('host', 'device'):
             raise ValueError(f"cfg.eval_metrics must be 'host' or 'device' (got {metrics_on!r})")
+        indices = self.cfg.get('eval_indices', 'standard')
+        if indices not in ('standard', 'extended'):
+            raise ValueError(f"cfg.eval_indices must be 'standard' or 'extended' (got {indices!r})")
+        ext, gains_ms = indices == 'extended', self.cfg.get('mtf_gains_ms')
         loader = self.test_data_loader1 if ref else self.test_data_loader0
         for module in self.module_dict.values():
             module.eval()
         dev = self._device()
         names = ['PSNR', 'SSIM', 'Q', 'SAM', 'ERGAS'] if ref else ['D_lambda', 'D_s', 'QNR']
+        if ext:
+            names = list(dmt.REF_EXT_NAMES if ref else dmt.NO_REF_EXT_NAMES)
         denorm = bool(self.cfg.get('norm_input', False))
         out_dir = osp.join(self.test_out1 if ref else self.test_out0, f'iter_{iter_id}')
         # one process per GPU: the evaluation set is SPLIT over the ranks (the reference is one process).  A loader built with this rank's
@@ -298,9 +307,19 @@ class Base_model:
                 input_batch = data_normalize(input_batch, self.cfg.bit_depth)
             fused = self.get_model_output(input_batch)
             nb = fused.shape[0]
+            if ext:
+                side = mtc.Q2N_BLOCK if ref else 4 * mtc.Q2N_BLOCK
+                if not 2 <= fused.shape[1] <= mtc.Q2N_MAX_BANDS or min(fused.shape[2:]) < side:
+                    raise ValueError(f"cfg.eval_indices = 'extended' needs 2 .. {mtc.Q2N_MAX_BANDS} bands and {'reduced' if ref else 'full'}-resolution "
+                                     f'images of at least {side} x {side} (Q2n works on {mtc.Q2N_BLOCK} x {mtc.Q2N_BLOCK} blocks'
+                                     f"{'' if ref else ' of the MS image'}); got {tuple(fused.shape[1:])}")
             if metrics_on == 'device':
                 if ref:
-                    dev_rows.append(dmt.ref_evaluate_batch(fused.contiguous(), input_batch['target'].contiguous(), scale))
+                    score = dmt.ref_evaluate_ext_batch if ext else dmt.ref_evaluate_batch
+                    dev_rows.append(score(fused.contiguous(), input_batch['target'].contiguous(), scale))
+                elif ext:
+                    dev_rows.append(dmt.no_ref_evaluate_ext_batch(fused.contiguous(), input_batch['input_pan'].contiguous(),
+                                                                  input_batch['input_lr'].contiguous(), scale, gains_ms=gains_ms))
                 else:
                     dev_rows.append(dmt.no_ref_evaluate_batch(fused.contiguous(), input_batch['input_pan'].contiguous(),
                                                               input_batch['input_lr'].contiguous(), scale))
@@ -309,10 +328,14 @@ class Base_model:
                 out = to_np(fused)
                 if ref:
                     gt = to_np(input_batch['target'])
-                    res.extend(mtc.ref_evaluate(out[i], gt[i]) for i in range(nb))
+                    score = mtc.ref_evaluate_ext if ext else mtc.ref_evaluate
+                    res.extend(score(out[i], gt[i]) for i in range(nb))
                 else:                                            # full-resolution set: no target (base_model.py:330-334)
                     pan_np, lr_np = to_np(input_batch['input_pan']), to_np(input_batch['input_lr'])
-                    res.extend(mtc.no_ref_evaluate(out[i], pan_np[i], lr_np[i]) for i in range(nb))
+                    if ext:
+                        res.extend(mtc.no_ref_evaluate_ext(out[i], pan_np[i], lr_np[i], gains_ms) for i in range(nb))
+                    else:
+                        res.extend(mtc.no_ref_evaluate(out[i], pan_np[i], lr_np[i]) for i in range(nb))
             if own_idx is not None:
                 ids.extend(('idx', own_idx[seen_here + i]) for i in range(nb))
             elif not sharded:

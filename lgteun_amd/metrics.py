@@ -22,6 +22,10 @@ Nyquist frequency is the sensor's MTF value, then decimation.  The reference bui
 scipy.ndimage and a per-satellite table; this is the separable Gaussian of the same MTF gain, so the family is PARITY-UNPINNED like SSIM / Q
 and is checked against brute-force evaluations of its definitions only.
 Device versions for whole batches (fp64 HIP kernels, tested against these functions): lgteun_amd/device_metrics.py.
+The extended set (`ref_evaluate_ext`, `no_ref_evaluate_ext`) adds the columns of the pan-sharpening literature: Q2n (Garzelli & Nencini, 2009:
+Q4 for four bands, Q8 for eight), SCC (Zhou et al., 1998, on Sobel magnitudes), CC (the reference's `scc`, metrics.py:58: Pearson's r per band)
+and D_lambda_K / HQNR (Khan et al., 2009; Aiazzi et al., 2014).  They are written from DESIGN.md 3.8.1, which is their definition here where it
+differs from the MATLAB toolbox (two deviations, recorded there).
 """
 import numpy as np
 from numpy.lib.stride_tricks import sliding_window_view
@@ -190,3 +194,197 @@ def no_ref_evaluate(pred, pan, ms):
     """the three no-reference indices in the order of the reference's result tables: D_lambda, D_s, QNR"""
     dl, ds = d_lambda(pred, ms), d_s(pred, ms, pan)
     return [dl, ds, (1.0 - dl) * (1.0 - ds)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the extended set: Q2n, SCC, CC at reduced resolution, D_lambda_K and HQNR at full resolution (definitions: DESIGN.md 3.8.1)
+# ---------------------------------------------------------------------------------------------------------------------
+Q2N_BLOCK, Q2N_MAX_BANDS = 32, 8
+
+
+def hconj(a):
+    """the hypercomplex conjugate: every component but the first negated (components on the last axis)"""
+    a = np.asarray(a, np.float64)
+    return np.concatenate([a[..., :1], -a[..., 1:]], axis=-1)
+
+
+def hmul(x, y):
+    """the hypercomplex product of vectors of length N = 2^m on the last axis (N = 1: the plain product); with halves x = (a, b) and
+    y = (c, d):  x * y = ( a*c - conj(d)*b , conj(a)*conj(d) + c*conj(b) )"""
+    x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+    n = x.shape[-1]
+    if n != y.shape[-1] or n < 1 or n & (n - 1):
+        raise ValueError(f'the hypercomplex product takes two vectors of one power-of-two length (got {x.shape[-1]} and {y.shape[-1]})')
+    if n == 1:
+        return x * y
+    a, b, c, d = x[..., :n // 2], x[..., n // 2:], y[..., :n // 2], y[..., n // 2:]
+    return np.concatenate([hmul(a, c) - hmul(hconj(d), b), hmul(hconj(a), hconj(d)) + hmul(c, hconj(b))], axis=-1)
+
+
+def _block_sum(v):
+    """the sum over the 1024 pixels of a block (first axis, row-major) as ONE fixed tree of pairwise additions -- the tree of the device
+    kernel (k_iqa_q2n: pixel p belongs to thread p % 256, which adds its four; lanes halve inside a wave; the four waves meet pairwise).
+    A tree of halvings adds 1024 equal values exactly, whatever their bits: a block that is flat in both images has P2 = M2 to the
+    last bit and reaches the t3 == 0 branch.  np.sum, which runs eight sequential accumulators, forms 3 v and may round."""
+    v = v.reshape((4, 4, 64) + v.shape[1:])
+    v = (v[0] + v[1]) + (v[2] + v[3])
+    for half in (32, 16, 8, 4, 2, 1):
+        v = v[:, :half] + v[:, half:2 * half]
+    return ((v[0] + v[1]) + (v[2] + v[3]))[0]
+
+
+def _q2n_block(x, y):
+    """one block: x (ground truth), y (fused) as [1024, N] float64, bands past the image's own are zero"""
+    n, N = x.shape
+    k = n / (n - 1.0)
+    a = _block_sum(x) / n
+    d = x - a
+    c = np.sqrt(_block_sum(d * d) / (n - 1.0))
+    c = np.where(c == 0.0, 1.0, c)            # a flat block keeps its scale (the toolbox divides by eps here: DESIGN.md 3.8.1)
+    xn = d / c + 1.0
+    z = (y - a) / c + 1.0                     # the ground truth's map on both images
+    z[:, 1:] = -z[:, 1:]
+    m1, m2 = _block_sum(xn) / n, _block_sum(z) / n
+    sq1, sq2 = np.zeros(n), np.zeros(n)
+    M1 = M2 = 0.0
+    for i in range(N):                        # ascending band order, as the kernel adds them
+        sq1, sq2 = sq1 + xn[:, i] * xn[:, i], sq2 + z[:, i] * z[:, i]
+        M1, M2 = M1 + m1[i] * m1[i], M2 + m2[i] * m2[i]
+    P1, P2 = _block_sum(sq1) / n, _block_sum(sq2) / n
+    t3 = k * P1 + k * P2 - k * (M1 + M2)
+    bias = 2.0 * np.sqrt(M1) * np.sqrt(M2) / (M1 + M2)
+    if t3 == 0.0:
+        return abs(bias)
+    u = _block_sum(hmul(xn, z)) / n
+    q = (k * u - k * hmul(m1, m2)) * bias * (2.0 / t3)
+    s = 0.0
+    for i in range(N):
+        s = s + q[i] * q[i]
+    return float(np.sqrt(s))
+
+
+def _q2n_planes(gt, fused):
+    """-> the two images as float64 [H', W', N]: bands padded with zero planes to N = 2^m, sides mirrored (edge included) to multiples of 32"""
+    g, f = _as_pair(gt, fused)
+    if g.ndim != 3 or not 2 <= g.shape[2] <= Q2N_MAX_BANDS:
+        raise ValueError(f'Q2n takes (H, W, bands) images of 2 .. {Q2N_MAX_BANDS} bands (got shape {g.shape})')
+    if min(g.shape[:2]) < Q2N_BLOCK:
+        raise ValueError(f'Q2n needs H and W >= {Q2N_BLOCK}, one block (got {g.shape[0]} x {g.shape[1]})')
+    N = 1 << (g.shape[2] - 1).bit_length()
+    out = []
+    for v in (g, f):
+        v = np.concatenate([v, np.zeros(v.shape[:2] + (N - v.shape[2],))], axis=2)
+        e = -v.shape[0] % Q2N_BLOCK
+        if e:
+            v = np.concatenate([v, v[:-e - 1:-1]], axis=0)          # lines L-1, L-2, ..., L-e: rows first
+        e = -v.shape[1] % Q2N_BLOCK
+        if e:
+            v = np.concatenate([v, v[:, :-e - 1:-1]], axis=1)
+        out.append(v)
+    return out
+
+
+def q2n_blocks(gt, fused):
+    """the Q2n value of every 32 x 32 block of the extended image, row-major"""
+    g, f = _q2n_planes(gt, fused)
+    bs, N = Q2N_BLOCK, g.shape[2]
+    return np.array([_q2n_block(g[r:r + bs, c:c + bs].reshape(-1, N), f[r:r + bs, c:c + bs].reshape(-1, N))
+                     for r in range(0, g.shape[0], bs) for c in range(0, g.shape[1], bs)])
+
+
+def q2n(gt, fused, block=Q2N_BLOCK):
+    """Q2n, the hypercomplex extension of Q to 2 .. 8 bands (Q4, Q8): the mean over non-overlapping 32 x 32 blocks"""
+    if block != Q2N_BLOCK:
+        raise ValueError(f'Q2n is defined here on {Q2N_BLOCK} x {Q2N_BLOCK} blocks (got block = {block})')
+    return float(np.mean(q2n_blocks(gt, fused)))
+
+
+def _sobel_magnitude(x):
+    """(H, W, bands) -> (H-2, W-2, bands): sqrt(gx^2 + gy^2) of the Sobel pair at the interior pixels, no padding"""
+    gx = (x[:-2, 2:] - x[:-2, :-2]) + 2.0 * (x[1:-1, 2:] - x[1:-1, :-2]) + (x[2:, 2:] - x[2:, :-2])
+    gy = (x[2:, :-2] - x[:-2, :-2]) + 2.0 * (x[2:, 1:-1] - x[:-2, 1:-1]) + (x[2:, 2:] - x[:-2, 2:])
+    return np.sqrt(gx * gx + gy * gy)
+
+
+def scc(gt, fused):
+    """spatial correlation: sum FG / sqrt(sum F^2 sum G^2) of the Sobel magnitudes F (fused) and G (ground truth) over all bands; 1 when
+    neither image has an edge, 0 when exactly one has none"""
+    g, f = _as_pair(gt, fused)
+    if g.ndim == 2:
+        g, f = g[..., None], f[..., None]
+    if min(g.shape[:2]) < 3:
+        raise ValueError('SCC needs H and W >= 3 (one interior pixel)')
+    F, G = _sobel_magnitude(f), _sobel_magnitude(g)
+    ff, gg = float(np.sum(F * F)), float(np.sum(G * G))
+    if ff == 0.0 or gg == 0.0:
+        return 1.0 if ff == gg else 0.0
+    return float(np.sum(F * G) / np.sqrt(ff * gg))
+
+
+def cc(gt, fused):
+    """the reference's `scc` (models/base/metrics.py:58): the mean over bands of Pearson's r; NaN if a band of either image is constant"""
+    g, f = _as_pair(gt, fused)
+    if g.ndim == 2:
+        g, f = g[..., None], f[..., None]
+    rs = []
+    for k in range(g.shape[2]):
+        x, y = g[..., k].ravel(), f[..., k].ravel()
+        rs.append(np.nan if x.min() == x.max() or y.min() == y.max() else np.corrcoef(x, y)[0, 1])
+    return float(np.mean(rs))
+
+
+def fir_decimate4(x, taps, phase=2):
+    """the arithmetic lg_fir_decimate4 documents (include/lgteun_hip.h), on the host: (H, W) float32 samples -> float32 (H/4, W/4).  fp64; the
+    pass along the rows, then the pass along the columns, replicate borders, each sum in ascending k from 0.0, one rounding to fp32"""
+    x, taps = np.asarray(x), np.asarray(taps, np.float64)
+    H, W = x.shape
+    if H % 4 or W % 4:
+        raise ValueError(f'decimation by 4 needs sides that are multiples of 4 (got {H} x {W})')
+    r = taps.size // 2
+    xp = np.pad(x.astype(np.float64), r, mode='edge')
+    rows = np.zeros((H + 2 * r, W // 4))
+    for k in range(taps.size):
+        rows = rows + taps[k] * xp[:, phase + k::4][:, :W // 4]
+    out = np.zeros((H // 4, W // 4))
+    for k in range(taps.size):
+        out = out + taps[k] * rows[phase + k::4][:H // 4]
+    return out.astype(np.float32)
+
+
+def mtf_degrade_ms(fused, gains_ms=None, n_taps=MTF_TAPS, phase=2):
+    """every band of the fused image (H, W, bands; float32 samples) through its MTF-matched Gaussian (wald.mtf_taps of the band's gain;
+    default gains: wald.DEFAULT_GAIN_MS, as mtf_glp) and decimated by 4 -> float32 (H/4, W/4, bands)"""
+    from . import wald
+    f = np.asarray(fused)
+    if f.ndim != 3:
+        raise ValueError('the fused image is (H, W, bands)')
+    gains = wald._gain_rows(gains_ms, f.shape[2], wald.DEFAULT_GAIN_MS, 'gains_ms')
+    return np.stack([fir_decimate4(f[..., k].astype(np.float32), wald.mtf_taps(g, n_taps), phase) for k, g in enumerate(gains)], axis=-1)
+
+
+def d_lambda_k(fused, ms, gains_ms=None, n_taps=MTF_TAPS, phase=2):
+    """Khan's spectral distortion: 1 - Q2n(MS, the fused image brought to MS resolution through the sensor's MTF)"""
+    f, m = np.asarray(fused), np.asarray(ms)
+    if f.ndim != 3 or m.ndim != 3 or f.shape[2] != m.shape[2]:
+        raise ValueError('fused and MS images are (H, W, bands) with the same number of bands')
+    if f.shape[0] % 4 or f.shape[1] % 4 or min(f.shape[:2]) < 4 * Q2N_BLOCK or m.shape[:2] != (f.shape[0] // 4, f.shape[1] // 4):
+        raise ValueError(f'D_lambda_K needs H and W >= {4 * Q2N_BLOCK} (MS sides >= {Q2N_BLOCK}) and multiples of 4, and MS at a quarter of '
+                         f'them (got fused {f.shape[:2]}, MS {m.shape[:2]})')
+    return 1.0 - q2n(m, mtf_degrade_ms(f, gains_ms, n_taps, phase))
+
+
+def hqnr(fused, ms, pan, gains_ms=None, n_taps=MTF_TAPS, phase=2):
+    """hybrid QNR: (1 - D_lambda_K)(1 - D_s), D_s as in `qnr`"""
+    return float((1.0 - d_lambda_k(fused, ms, gains_ms, n_taps, phase)) * (1.0 - d_s(fused, ms, pan)))
+
+
+def ref_evaluate_ext(pred, gt):
+    """ref_evaluate's five, then Q2n, SCC, CC"""
+    return ref_evaluate(pred, gt) + [q2n(gt, pred), scc(gt, pred), cc(gt, pred)]
+
+
+def no_ref_evaluate_ext(pred, pan, ms, gains_ms=None):
+    """no_ref_evaluate's three, then D_lambda_K, HQNR"""
+    dl, ds = d_lambda(pred, ms), d_s(pred, ms, pan)
+    dk = d_lambda_k(pred, ms, gains_ms)
+    return [dl, ds, (1.0 - dl) * (1.0 - ds), dk, (1.0 - dk) * (1.0 - ds)]

@@ -2,7 +2,10 @@
 every image of a batch, synchronised (the host path ends with its numpy scores, the device path with the one copy of its rows).
 Reduced resolution (PSNR / SSIM / Q / SAM / ERGAS): PAN 128^2 at C = 4 and 8, batch 1 (the reference's test loaders) and 32.
 Full resolution (D_lambda / D_s / QNR): the 400^2 scene at C = 4 and 8, batch 1.  Every shape is warmed up before it is timed.
-Prints one JSON line.   python tools/time_eval.py [--reps N]"""
+The extended leg (cfg.eval_indices = 'extended': + Q2n / SCC / CC, + D_lambda_K / HQNR) times forward alone / standard device / extended
+device / extended host of every case in alternating rounds, so that a drift of the box falls on all four alike; the extended device figure
+is to be read against the standard device figure of the same run and against the extended host figure.
+Prints one JSON line.   python tools/time_eval.py [--reps N] [--rounds R]"""
 import argparse
 import json
 import os
@@ -38,12 +41,17 @@ def run(net, ref, ms, pan, gt, how):
         if how == 'device':
             rows = dmt.ref_evaluate_batch(out, gt, PEAK) if ref else dmt.no_ref_evaluate_batch(out, pan, ms, PEAK)
             return rows.cpu().numpy()
+        if how == 'device_ext':
+            rows = dmt.ref_evaluate_ext_batch(out, gt, PEAK) if ref else dmt.no_ref_evaluate_ext_batch(out, pan, ms, PEAK)
+            return rows.cpu().numpy()
         o = host_np(out)
         if ref:
             g = host_np(gt)
-            return np.array([mtc.ref_evaluate(o[i], g[i]) for i in range(o.shape[0])])
+            score = mtc.ref_evaluate_ext if how == 'host_ext' else mtc.ref_evaluate
+            return np.array([score(o[i], g[i]) for i in range(o.shape[0])])
         p, m = host_np(pan), host_np(ms)
-        return np.array([mtc.no_ref_evaluate(o[i], p[i], m[i]) for i in range(o.shape[0])])
+        score = mtc.no_ref_evaluate_ext if how == 'host_ext' else mtc.no_ref_evaluate
+        return np.array([score(o[i], p[i], m[i]) for i in range(o.shape[0])])
 
 
 def per_image_ms(fn, B, reps):
@@ -56,9 +64,26 @@ def per_image_ms(fn, B, reps):
     return (time.perf_counter() - t) / reps / B * 1e3
 
 
+def alternating_ms(legs, B, rounds):
+    """legs: {name: (fn, repetitions per round)} -> {name: ms per image}, the median over `rounds` rounds that time every leg in turn"""
+    for fn, _ in legs.values():
+        for _ in range(3):
+            fn()
+    seen = {name: [] for name in legs}
+    for _ in range(rounds):
+        for name, (fn, n) in legs.items():
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            for _ in range(n):
+                fn()
+            seen[name].append((time.perf_counter() - t) / n / B * 1e3)
+    return {name: float(np.median(v)) for name, v in seen.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=20, help='timed repetitions of the forward and device paths (host path: fewer)')
+    ap.add_argument('--rounds', type=int, default=5, help='alternating rounds of the extended leg')
     a = ap.parse_args()
     nets, res = {}, {}
     for name, ref, C, h, B in CASES:
@@ -72,6 +97,12 @@ def main():
         row['max_abs_diff'] = float(np.max(np.abs(d - hst)[np.isfinite(hst)]))
         row['speedup'] = row['host_ms'] / row['device_ms']
         res[name] = {k: round(v, 4) if k != 'max_abs_diff' else v for k, v in row.items()}
+        leg = lambda how, n: (lambda: run(net, ref, ms, pan, gt, how), n)      # noqa: E731
+        ext = alternating_ms({'forward_ms': leg('forward', a.reps), 'device_ms': leg('device', a.reps), 'device_ext_ms': leg('device_ext', a.reps),
+                              'host_ext_ms': leg('host_ext', 1)}, B, a.rounds)
+        d, hst = run(net, ref, ms, pan, gt, 'device_ext'), run(net, ref, ms, pan, gt, 'host_ext')
+        res[name]['extended'] = {k: round(v, 4) for k, v in ext.items()}
+        res[name]['extended']['max_abs_diff'] = float(np.max(np.abs(d - hst)[np.isfinite(hst)]))
     print(json.dumps({'tool': 'time_eval', 'unit': 'ms per image (forward K = 2 + indices, synchronised)',
                       'device': torch.cuda.get_device_name(0), 'cases': res}))
 
