@@ -114,7 +114,7 @@ typedef struct lg_plan lg_plan; /* host-side, immutable after creation */
 
 const char* lg_version(void);
 /* Bumped whenever a struct layout, an argument meaning or a caller-provided buffer size changes (2: lg_config.variant, the data step's
- * tmp of 3*B*C*H*W/4 + B*H*W floats).  Additions keep it: lg_op_lgt_stages, lg_workspace_deadout, LG_FLAG_STAGEWISE, the lg_debug_stage_* entries and the classical baselines (lg_classical_workspace_bytes, lg_interp23_up4, lg_sfim, lg_gsa, then lg_wavelet, lg_wavelet_taps, then lg_mtfglp_workspace_bytes, lg_mtf_glp) came without a bump (no struct,
+ * tmp of 3*B*C*H*W/4 + B*H*W floats).  Additions keep it: lg_op_lgt_stages, lg_workspace_deadout, LG_FLAG_STAGEWISE, the lg_debug_stage_* entries and the classical baselines (lg_classical_workspace_bytes, lg_interp23_up4, lg_sfim, lg_gsa, then lg_wavelet, lg_wavelet_taps, then lg_mtfglp_workspace_bytes, lg_mtf_glp, then lg_bdsd_workspace_bytes, lg_bdsd) came without a bump (no struct,
  * argument or caller-sized buffer changed: workspaces are sized by lg_workspace_bytes, which grew for the plans that batch their dead stages).  A binding checks it at load time -- lgteun_amd/_lib.py does -- instead of passing a stale struct. */
 #define LG_ABI_VERSION 2
 int32_t lg_abi_version(void);
@@ -532,6 +532,22 @@ int lg_wavelet_taps(double* out17);
 size_t lg_mtfglp_workspace_bytes(int32_t B, int32_t C, int32_t h, int32_t w, int32_t n_filters, int32_t mode);
 int lg_mtf_glp(const float* ms, const float* pan, float* out, double* stats, const double* taps, int32_t n_filters, int32_t n_taps, int32_t mode, int32_t B,
                int32_t C, int32_t h, int32_t w, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- BDSD: the band-dependent spatial detail method, global or block-wise (lgteun_amd/bdsd.py) ----
+ * With u_k = interp23(ms)_k, A_k(i, j) = sum_a sum_b t_k[a] t_k[b] ms_k(clamp(i + a - r), clamp(j + b - r)) (the band low-passed on its own grid, replicate
+ * border, r = n_taps / 2) and D = the raw PAN filtered with taps_pan at (4 i + 2, 4 j + 2) (lg_mtf_glp's rule): per block and band the weights gamma_k in
+ * R^(C + 1) minimise sum (ms_k - A_k - x' gamma)^2 over the block's MS pixels, x = [A_1 .. A_C, D] (no intercept), by a Cholesky solve of the normal equations
+ * in fp64; out_k = clip(u_k + sum_j gamma_k[j] u_j + gamma_k[C] pan, 0, 1) with one rounding, gamma that of the block the PAN pixel lies in.
+ * block: 0 = one block is the whole sample (needs h w >= 2 (C + 1)); else the block's side in PAN pixels, a multiple of 32 that divides 4 h and 4 w; block
+ * (I, J) holds the MS pixels i / (block / 4) = I, j / (block / 4) = J.  A block with a pivot d_j <= 1e-12 G_jj, a pivot or a weight that is not finite has
+ * gamma = 0: its output is clip(u) bit for bit.  taps_ms: a DEVICE array [n_filters, n_taps] of fp64, n_filters 1 (one filter for every band) or C; taps_pan:
+ * [n_taps]; rows sum to 1 (wald.mtf_taps); n_taps odd, in 1 .. 63.  stats: NULL or a device array [B, 4 h / block, 4 w / block, C, C + 1] of fp64 ([B, 1, 1, C,
+ * C + 1] for block 0) that receives gamma.  Launches: the low-pass of PAN and of the bands (fp64 [B, h, w] and [B, C, h, w] in the workspace), the Gram pass,
+ * the solve, the apply pass; neither u nor A is stored at PAN size.  Tensors, limits, alignment, checks and guarantees (same bits on every call, a sample's
+ * bits do not depend on its batch, the workspace needs no initialisation, a rejected call writes nothing) are those of lg_mtf_glp. */
+/* bytes of workspace lg_bdsd needs; 0 for anything the call rejects */
+size_t lg_bdsd_workspace_bytes(int32_t B, int32_t C, int32_t h, int32_t w, int32_t block);
+int lg_bdsd(const float* ms, const float* pan, float* out, double* stats, const double* taps_ms, int32_t n_filters, const double* taps_pan, int32_t n_taps,
+            int32_t block, int32_t B, int32_t C, int32_t h, int32_t w, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,7 @@ from .engine import Engine, FusedAdam, FusedAdamW, FusedRMSprop, FusedSGD, Train
 from .dataset import DATASETS, PSDataset, PrefetchLoader, SceneDataset, ShardedSampler, build_dataset, build_loader  # noqa: F401
 from .classical import GSA, SFIM, Wavelet, gsa, interp23, sfim, wavelet  # noqa: F401
 from .mtf_glp import MTF_GLP, MTF_GLP_CBD, MTF_GLP_HPM  # noqa: F401  (the function is mtf_glp.mtf_glp: its name is the module's)
+from .bdsd import BDSD  # noqa: F401  (the function is bdsd.bdsd: its name is the module's)
 from .device_metrics import no_ref_evaluate_batch, no_ref_evaluate_ext_batch, ref_evaluate_batch, ref_evaluate_ext_batch  # noqa: F401
 from .resident import ResidentLoader, ResidentStore  # noqa: F401
 from .scene import fuse_scene, tile_grid  # noqa: F401

@@ -24,6 +24,7 @@
 //                    block mean of u_k, which is a separable 17-tap circular FIR on ms itself (cl_wavelet_taps).  A lane owns 4 x 4 blocks: 16-byte
 //                    PAN loads, 16-byte stores, M_k from an ms halo tile in LDS (columns, then rows).  No u, no moments, no workspace.
 //   k_mg_*           MTF-GLP with its three injection rules (lg_mtf_glp), on the same tiles: described where they stand, below k_cl_wavelet.
+//   k_bd_*           BDSD, global and block-wise (lg_bdsd; restated in tests/bdsd_ref.py): described where they stand, below k_mg_*.
 // No atomics; a workgroup sees one sample and the grid of a sample depends on C, h and w only, so a sample has the same bits alone and inside
 // any batch.  All indexing into tensors is 64-bit.
 #include <cmath>
@@ -854,7 +855,301 @@ int mg_fuse(const char* who, const float* ms, const float* pan, float* out, doub
     return 0;
 }
 
+// ---- BDSD: the band-dependent spatial detail method, global or per block of block x block PAN pixels.  Per block and band the weights gamma
+// are the least-squares fit of ms_k - A_k on x = [A_1 .. A_C, D] at the MS scale (A_k: the band low-passed on its own grid, D: the raw PAN low-passed at the
+// decimated positions, k_mg_lowpass's plane plus the pivot); out_k = clip(u_k + sum_j gamma_kj u_j + gamma_kC pan).
+//   k_bd_lowpass_ms  grid (tile, band, sample): A_k on 16 x 16 tiles of the MS grid, replicate border -- rows into LDS, then columns; fp64 [B, C, h, w].
+//   k_bd_gram        grid (block x workgroup of the block, sample): a workgroup walks the block's pixels (row-major inside the block) in chunks of 256, gpb
+//                    chunks apart: the 2 C + 1 vectors [x, y] of the chunk in LDS, zero past the block's end; every entry of G = sum x x' (upper triangle) and
+//                    of r_k = sum x y_k is the sum of a product of two of them: a wave owns the entries e = wave, wave + 4, ..., sums them over the chunk and
+//                    lane 0 adds to its slot in LDS -- one order, always.  The workgroup writes its slots.
+//   k_bd_solve       one wave per block: the partials in ascending order, one thread's Cholesky of G, then thread k solves for gamma_k.  A pivot at or below
+//                    1e-12 G_jj or not finite, or a weight that is not finite, gives the block gamma = 0: its output is clip(u) bit for bit.
+//   k_bd_apply       grid (tile, sample), k_cl_apply's structure: the C bands of the tile and the weights of the tile's block in LDS (block edges are
+//                    multiples of 32: a tile lies in one block), two adjacent pixels per thread, ONE rounding, 8-byte stores.
+// Neither u nor A is stored at PAN size.  The geometry of a sample depends on C, h, w and block only.
+constexpr int BD_CHUNK = CL_NT;                                          // MS pixels of a block a Gram workgroup takes at a time: one per thread
+constexpr int BD_MAX_N = CL_MAX_C + 1;                                   // regressors, at most
+constexpr int BD_MAX_NS = BD_MAX_N * (BD_MAX_N + 1) / 2 + CL_MAX_C * BD_MAX_N;      // entries of G and of the C right-hand sides
+constexpr int BD_GRAM_WGS = 128;                                         // Gram workgroups per sample, at most, where blocks are larger than a chunk
+constexpr int BD_SOLVE_NT = 64;
+constexpr double BD_PIVOT_TOL = 1e-12;
+static_assert(BD_SOLVE_NT >= CL_MAX_C, "a thread per band solves");
+
+__host__ __device__ inline int bd_ns(int C) { return (C + 1) * (C + 2) / 2 + C * (C + 1); }
+__host__ __device__ inline int bd_gram_lds_doubles(int C) { return (2 * C + 1) * BD_CHUNK + bd_ns(C); }
+__host__ __device__ inline int bd_apply_lds_doubles(int C) { return CL_SCRATCH + C * CL_PX + C * (C + 1); }
+
+__global__ __launch_bounds__(CL_NT) void k_bd_lowpass_ms(const float* __restrict__ ms, const double* __restrict__ taps, double* __restrict__ alow, int F, int h,
+                                                         int w, int n_taps, int tiles_x) {
+    __shared__ double tp[MG_MAX_TAPS];
+    __shared__ double rowf[MG_TO + MG_MAX_TAPS - 1][MG_TO + 1];
+    const int r = n_taps >> 1, tid = threadIdx.x;
+    const int oy0 = (blockIdx.x / tiles_x) * MG_TO, ox0 = (blockIdx.x % tiles_x) * MG_TO;
+    const long plane = (long)blockIdx.z * gridDim.y + blockIdx.y;
+    const float* __restrict__ ms_k = ms + plane * ((long)h * w);
+    if (tid < n_taps) tp[tid] = taps[(F == 1 ? 0 : blockIdx.y) * n_taps + tid];
+    __syncthreads();
+    // row pass: slot s is ms row oy0 - r + s (clamped into the plane), column j the tile's j-th column
+    const int rows = oy0 + MG_TO <= h ? MG_TO : h - oy0, span = rows + n_taps - 1;
+    for (int t = tid; t < span * MG_TO; t += CL_NT) {
+        const int s = t / MG_TO, j = t - s * MG_TO;
+        if (ox0 + j >= w) continue;
+        const float* __restrict__ row = ms_k + (long)mg_clamp(oy0 - r + s, h) * w;
+        const int xb = ox0 + j - r;
+        double acc = 0.0;
+        for (int k = 0; k < n_taps; ++k) acc = fma(tp[k], (double)row[mg_clamp(xb + k, w)], acc);
+        rowf[s][j] = acc;
+    }
+    __syncthreads();
+    const int ly = tid / MG_TO, lx = tid - ly * MG_TO;
+    if (ly >= rows || ox0 + lx >= w) return;
+    double acc = 0.0;
+    for (int k = 0; k < n_taps; ++k) acc = fma(tp[k], rowf[ly + k][lx], acc);
+    alow[plane * ((long)h * w) + (long)(oy0 + ly) * w + ox0 + lx] = acc;
+}
+
+// part [B][nblocks][gpb][ns]: the upper triangle of G in row-major order (a <= c < C + 1), then r_k[j] at (C + 1)(C + 2) / 2 + k (C + 1) + j.  A block is bh x bw
+// MS pixels (the whole sample in the global form), nbx blocks in a row of blocks.
+__global__ __launch_bounds__(CL_NT) void k_bd_gram(const float* __restrict__ ms, const float* __restrict__ pan, const double* __restrict__ alow,
+                                                   const double* __restrict__ dlow, double* __restrict__ part, int C, int h, int w, int bh, int bw, int nbx,
+                                                   int gpb) {
+    extern __shared__ double cl_lds[];
+    __shared__ int pairs[BD_MAX_NS];
+    const int n = C + 1, nv = 2 * C + 1, ns = bd_ns(C), tid = threadIdx.x, lane = tid & 63;
+    double* V = cl_lds;                          // [nv][256]: A_0 .. A_C-1, D, y_0 .. y_C-1
+    double* acc = V + nv * BD_CHUNK;             // [ns]
+    const int blk = blockIdx.x / gpb, g = blockIdx.x - blk * gpb;
+    const int i0 = (blk / nbx) * bh, j0 = (blk % nbx) * bw, npx = bh * bw;
+    const long b = blockIdx.y, lp = (long)h * w;
+    const float* __restrict__ ms_b = ms + b * C * lp;
+    const double* __restrict__ al_b = alow + b * C * lp;
+    const double* __restrict__ dl_b = dlow + b * lp;
+    const double pv = (double)pan[b * 16 * lp];  // k_mg_lowpass filters PAN minus the sample's first pixel; the taps sum to 1
+    if (tid == 0) {
+        int e = 0;
+        for (int a = 0; a < n; ++a)
+            for (int c = a; c < n; ++c) pairs[e++] = cl_pair(a, c, 0);
+        for (int k = 0; k < C; ++k)
+            for (int j = 0; j < n; ++j) pairs[e++] = cl_pair(j, n + k, 0);
+    }
+    for (int e = tid; e < ns; e += CL_NT) acc[e] = 0.0;
+    for (int c0 = g * BD_CHUNK; c0 < npx; c0 += gpb * BD_CHUNK) {
+        const int q = c0 + tid, live = npx - c0 < BD_CHUNK ? npx - c0 : BD_CHUNK;
+        if (q < npx) {
+            const int ii = q / bw, jj = q - ii * bw;
+            const long o = (long)(i0 + ii) * w + j0 + jj;
+            for (int k = 0; k < C; ++k) {
+                const double a = al_b[k * lp + o];
+                V[k * BD_CHUNK + tid] = a;
+                V[(n + k) * BD_CHUNK + tid] = (double)ms_b[k * lp + o] - a;
+            }
+            V[C * BD_CHUNK + tid] = dl_b[o] + pv;
+        } else {
+            for (int v = 0; v < nv; ++v) V[v * BD_CHUNK + tid] = 0.0;
+        }
+        __syncthreads();
+        for (int e = tid >> 6; e < ns; e += CL_NT / 64) {
+            const int pr = pairs[e], a = pr & 255, c = (pr >> 8) & 255;
+            double v = 0.0;
+            for (int u = 0; u < live; u += 64) v = fma(V[a * BD_CHUNK + lane + u], V[c * BD_CHUNK + lane + u], v);      // past the last live wave: zeros
+            v = wave_sum(v);
+            if (lane == 0) acc[e] += v;
+        }
+        __syncthreads();      // the next chunk overwrites the vectors
+    }
+    for (int e = tid; e < ns; e += CL_NT) part[(b * gridDim.x + blockIdx.x) * ns + e] = acc[e];
+}
+
+// gamma [B][nblocks][C][C + 1] (stats: NULL or the same layout): per block G gamma_k = r_k by Cholesky, the lower triangle in Lm
+__global__ __launch_bounds__(BD_SOLVE_NT) void k_bd_solve(const double* __restrict__ part, double* __restrict__ gamma, double* __restrict__ stats, int C,
+                                                          int gpb) {
+    __shared__ double sums[BD_MAX_NS];
+    __shared__ double Lm[BD_MAX_N * BD_MAX_N], gam[CL_MAX_C * BD_MAX_N];
+    __shared__ int bad_pivot, bad_weight;
+    const int n = C + 1, ng = n * (n + 1) / 2, ns = bd_ns(C), tid = threadIdx.x;
+    const long blk = (long)blockIdx.y * gridDim.x + blockIdx.x;
+    for (int e = tid; e < ns; e += BD_SOLVE_NT) {
+        const double* __restrict__ pe = part + blk * gpb * ns + e;
+        double s = 0.0;
+        int j = 0;
+        for (; j + 8 <= gpb; j += 8) {      // eight loads in flight, added in ascending order
+            double q[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) q[u] = pe[(long)(j + u) * ns];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) s += q[u];
+        }
+        for (; j < gpb; ++j) s += pe[(long)j * ns];
+        sums[e] = s;
+    }
+    if (tid == 0) bad_pivot = bad_weight = 0;
+    __syncthreads();
+    auto G = [&](int a, int c) { return sums[a * n - a * (a - 1) / 2 + (c - a)]; };      // a <= c
+    if (tid == 0) {
+        for (int j = 0; j < n; ++j) {
+            const double gjj = G(j, j);
+            double d = gjj;
+            for (int p = 0; p < j; ++p) d -= Lm[j * n + p] * Lm[j * n + p];
+            if (!(d > BD_PIVOT_TOL * gjj) || d - d != 0.0) { bad_pivot = 1; break; }
+            d = sqrt(d);
+            Lm[j * n + j] = d;
+            for (int i = j + 1; i < n; ++i) {
+                double s = G(j, i);
+                for (int p = 0; p < j; ++p) s -= Lm[i * n + p] * Lm[j * n + p];
+                Lm[i * n + j] = s / d;
+            }
+        }
+    }
+    __syncthreads();
+    if (!bad_pivot && tid < C) {
+        double* x = gam + tid * n;
+        const double* rk = sums + ng + tid * n;
+        bool ok = true;
+        for (int i = 0; i < n; ++i) {
+            double s = rk[i];
+            for (int p = 0; p < i; ++p) s -= Lm[i * n + p] * x[p];
+            x[i] = s / Lm[i * n + i];
+        }
+        for (int i = n - 1; i >= 0; --i) {
+            double s = x[i];
+            for (int p = i + 1; p < n; ++p) s -= Lm[p * n + i] * x[p];
+            x[i] = s / Lm[i * n + i];
+            ok = ok && x[i] - x[i] == 0.0;
+        }
+        if (!ok) bad_weight = 1;
+    }
+    __syncthreads();
+    const bool ok = !bad_pivot && !bad_weight;
+    for (int i = tid; i < C * n; i += BD_SOLVE_NT) {
+        const double v = ok ? gam[i] : 0.0;
+        gamma[blk * (C * n) + i] = v;
+        if (stats) stats[blk * (C * n) + i] = v;
+    }
+}
+
+__global__ __launch_bounds__(CL_NT) void k_bd_apply(const float* __restrict__ ms, const float* __restrict__ pan, const double* __restrict__ gamma,
+                                                    float* __restrict__ out, int C, int h, int w, int tiles_x, int block, int nbx, int nblocks) {
+    extern __shared__ double cl_lds[];
+    double* U = cl_lds + CL_SCRATCH;             // [C][512]
+    double* Gm = U + C * CL_PX;                  // [C][C + 1]: the weights of the tile's block
+    const int tid = threadIdx.x, H4 = 4 * h, W4 = 4 * w, n = C + 1;
+    const int Y0 = (blockIdx.x / tiles_x) * CL_TH, X0 = (blockIdx.x % tiles_x) * CL_TW;
+    const long b = blockIdx.y, lp = (long)h * w, plane = (long)H4 * W4;
+    const float* __restrict__ ms_b = ms + b * C * lp;
+    const float* __restrict__ pan_b = pan + b * plane;
+    float* __restrict__ out_b = out + b * C * plane;
+    const int blk = block ? (Y0 / block) * nbx + X0 / block : 0;
+    const double* __restrict__ gm = gamma + (b * nblocks + blk) * (C * n);
+    for (int i = tid; i < C * n; i += CL_NT) Gm[i] = gm[i];      // (the barriers inside cl_up_band order this before its use)
+    const int p = 2 * tid, y = Y0 + p / CL_TW, x = X0 + p % CL_TW;
+    const bool in = y < H4 && x < W4;            // W4 is a multiple of 4 and x is even: both pixels or none
+    const long o = (long)y * W4 + x;
+    float2 pp = make_float2(0.f, 0.f);
+    if (in) pp = *reinterpret_cast<const float2*>(pan_b + o);
+    float v[CL_MLOADS], vn[CL_MLOADS] = {};
+    cl_ms_load(ms_b, h, w, Y0, X0, v);
+    for (int k = 0; k < C; ++k) {
+        if (k + 1 < C) cl_ms_load(ms_b + (k + 1) * lp, h, w, Y0, X0, vn);
+        cl_up_band(v, cl_lds, U + k * CL_PX);
+#pragma unroll
+        for (int u = 0; u < CL_MLOADS; ++u) v[u] = vn[u];
+    }
+    __syncthreads();
+    if (!in) return;
+    const double p0 = (double)pp.x, p1 = (double)pp.y;
+    for (int k = 0; k < C; ++k) {
+        const double* g = Gm + k * n;
+        double s0 = g[C] * p0, s1 = g[C] * p1;
+        for (int j = 0; j < C; ++j) {
+            s0 = fma(g[j], U[j * CL_PX + p], s0);
+            s1 = fma(g[j], U[j * CL_PX + p + 1], s1);
+        }
+        *reinterpret_cast<float2*>(out_b + k * plane + o) = make_float2(cl_clip(U[k * CL_PX + p] + s0), cl_clip(U[k * CL_PX + p + 1] + s1));
+    }
+}
+
+struct BdGeom {
+    int tiles_x, tiles, bh, bw, nbx, nblocks, gpb;
+    size_t off[4], bytes;      // D, A, part, gamma
+};
+
+// false: not a shape or a block the call takes (the reason, naming the argument, is in lg_last_error)
+bool bd_geom(const char* who, int B, int C, int h, int w, int block, BdGeom& g) {
+    if (!cl_shape(who, B, C, h, w)) return false;
+    if (block == 0) {
+        if ((long)h * w < 2 * (C + 1)) { lg_set_error("%s: the global form needs h * w >= 2 (C + 1) = %d (got %d x %d)", who, 2 * (C + 1), h, w); return false; }
+        g.bh = h;
+        g.bw = w;
+    } else {
+        if (block < 32 || block % 32) { lg_set_error("%s: block must be 0 (global) or a multiple of 32 (got %d)", who, block); return false; }
+        if ((4 * h) % block || (4 * w) % block) { lg_set_error("%s: block must divide 4 h = %d and 4 w = %d (got %d)", who, 4 * h, 4 * w, block); return false; }
+        g.bh = g.bw = block / 4;
+    }
+    g.tiles_x = (4 * w + CL_TW - 1) / CL_TW;
+    g.tiles = g.tiles_x * ((4 * h + CL_TH - 1) / CL_TH);
+    g.nbx = w / g.bw;
+    g.nblocks = g.nbx * (h / g.bh);
+    const int chunks = (g.bh * g.bw + BD_CHUNK - 1) / BD_CHUNK, cap = BD_GRAM_WGS / g.nblocks > 1 ? BD_GRAM_WGS / g.nblocks : 1;
+    g.gpb = chunks < cap ? chunks : cap;
+    const size_t lp = (size_t)h * w * sizeof(double), nb = (size_t)B * g.nblocks * sizeof(double);
+    const size_t sz[4] = {B * lp, (size_t)B * C * lp, nb * g.gpb * bd_ns(C), nb * C * (C + 1)};
+    g.bytes = ws_layout(4, sz, g.off);
+    return true;
+}
+
+DeviceOnce bd_attr_once;
+int bd_lds_attr(const char* who) {
+    if (!bd_attr_once.need()) return 0;
+    if (int rc = lds_attr_set(who, bd_gram_lds_doubles(CL_MAX_C) * (int)sizeof(double), k_bd_gram)) return rc;
+    if (int rc = lds_attr_set(who, bd_apply_lds_doubles(CL_MAX_C) * (int)sizeof(double), k_bd_apply)) return rc;
+    bd_attr_once.done();
+    return 0;
+}
+
+int bd_fuse(const char* who, const float* ms, const float* pan, float* out, double* stats, const double* taps_ms, int n_filters, const double* taps_pan,
+            int n_taps, int block, int B, int C, int h, int w, void* workspace, size_t workspace_bytes, hipStream_t s) {
+    BdGeom g;
+    if (!bd_geom(who, B, C, h, w, block, g)) return -1;
+    if (n_filters != 1 && n_filters != C) { lg_set_error("%s: n_filters must be 1 or C = %d (got %d)", who, C, n_filters); return -1; }
+    if (n_taps < 1 || n_taps > MG_MAX_TAPS || !(n_taps & 1)) { lg_set_error("%s: n_taps must be odd, in 1..%d (got %d)", who, MG_MAX_TAPS, n_taps); return -1; }
+    if (!check_tensors(who, {{"ms", ms}, {"pan", pan}, {"out", out}})) return -1;
+    if (!taps_ms) { lg_set_error("%s: taps_ms is NULL", who); return -1; }
+    if (!taps_pan) { lg_set_error("%s: taps_pan is NULL", who); return -1; }
+    if ((uintptr_t)taps_ms & 7) { lg_set_error("%s: taps_ms must be 8-byte aligned", who); return -1; }
+    if ((uintptr_t)taps_pan & 7) { lg_set_error("%s: taps_pan must be 8-byte aligned", who); return -1; }
+    if ((uintptr_t)stats & 7) { lg_set_error("%s: stats must be 8-byte aligned", who); return -1; }
+    if (!check_workspace(who, workspace, workspace_bytes, g.bytes, "lg_bdsd_workspace_bytes")) return -1;
+    if (int rc = bd_lds_attr(who)) return rc;
+    double* dlow = (double*)((char*)workspace + g.off[0]);
+    double* alow = (double*)((char*)workspace + g.off[1]);
+    double* part = (double*)((char*)workspace + g.off[2]);
+    double* gamma = (double*)((char*)workspace + g.off[3]);
+    const int lt_x = (w + MG_TO - 1) / MG_TO, lt = lt_x * ((h + MG_TO - 1) / MG_TO);
+    k_mg_lowpass<<<dim3(lt, 1, B), CL_NT, 0, s>>>(pan, taps_pan, dlow, h, w, n_taps, lt_x);
+    LG_CHECK_LAUNCH();
+    k_bd_lowpass_ms<<<dim3(lt, C, B), CL_NT, 0, s>>>(ms, taps_ms, alow, n_filters, h, w, n_taps, lt_x);
+    LG_CHECK_LAUNCH();
+    k_bd_gram<<<dim3(g.nblocks * g.gpb, B), CL_NT, bd_gram_lds_doubles(C) * sizeof(double), s>>>(ms, pan, alow, dlow, part, C, h, w, g.bh, g.bw, g.nbx, g.gpb);
+    LG_CHECK_LAUNCH();
+    k_bd_solve<<<dim3(g.nblocks, B), BD_SOLVE_NT, 0, s>>>(part, gamma, stats, C, g.gpb);
+    LG_CHECK_LAUNCH();
+    k_bd_apply<<<dim3(g.tiles, B), CL_NT, bd_apply_lds_doubles(C) * sizeof(double), s>>>(ms, pan, gamma, out, C, h, w, g.tiles_x, block, g.nbx, g.nblocks);
+    LG_CHECK_LAUNCH();
+    return 0;
+}
+
 }  // namespace
+
+extern "C" size_t lg_bdsd_workspace_bytes(int32_t B, int32_t C, int32_t h, int32_t w, int32_t block) {
+    BdGeom g;
+    return bd_geom("bdsd_workspace_bytes", B, C, h, w, block, g) ? g.bytes : 0;
+}
+
+extern "C" int lg_bdsd(const float* ms, const float* pan, float* out, double* stats, const double* taps_ms, int32_t n_filters, const double* taps_pan,
+                       int32_t n_taps, int32_t block, int32_t B, int32_t C, int32_t h, int32_t w, void* workspace, size_t workspace_bytes, void* stream) {
+    return bd_fuse("bdsd", ms, pan, out, stats, taps_ms, n_filters, taps_pan, n_taps, block, B, C, h, w, workspace, workspace_bytes, (hipStream_t)stream);
+}
 
 extern "C" size_t lg_mtfglp_workspace_bytes(int32_t B, int32_t C, int32_t h, int32_t w, int32_t n_filters, int32_t mode) {
     MgGeom g;

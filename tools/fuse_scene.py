@@ -5,10 +5,13 @@ dataset.read_tiff, fuses them tile by tile on the GPU (lgteun_amd/scene.py) and 
                                [--batch B] [--float] [--out FILE]
     python tools/fuse_scene.py PREFIX --method gsa|sfim|wavelet [--bit-depth 11] [--norm-input] [--float] [--out FILE]
     python tools/fuse_scene.py PREFIX --method mtf_glp|mtf_glp_hpm|mtf_glp_cbd [--mtf-gains g [g ...]] [--bit-depth 11] ...
+    python tools/fuse_scene.py PREFIX --method bdsd [--bdsd-block N] [--mtf-gains g [g ...]] [--mtf-gain-pan g] [--bit-depth 11] ...
 
 --method gsa / sfim / wavelet (lgteun_amd/classical.py) and mtf_glp / mtf_glp_hpm / mtf_glp_cbd (lgteun_amd/mtf_glp.py) need no checkpoint and no
 tiles: the whole scene is fused in one call, with the same normalisation and the same conversion to digital numbers.  --mtf-gains: the sensor's MTF
-gains at Nyquist, one for all bands or one per band; without them a placeholder (0.3) applies, which is no sensor's value.
+gains at Nyquist, one for all bands or one per band; without them a placeholder (0.3) applies, which is no sensor's value.  --method bdsd
+(lgteun_amd/bdsd.py) takes them too, with --mtf-gain-pan for PAN (placeholder 0.15), and --bdsd-block N fits its weights per block of N x N PAN pixels (a
+multiple of 32 that divides both sides of PAN; without it one fit serves the whole scene).
 
 The checkpoint is a plain-tensor file ({'core_module': state_dict}, what Base_model.save writes and tools/convert_checkpoint.py makes of a
 reference-era file); the band count and the stage count are read from it.  The output holds uint16 digital numbers
@@ -40,9 +43,12 @@ def load_module(path, device='cuda:0'):
 def parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('prefix')
-    ap.add_argument('--method', choices=['network', 'gsa', 'sfim', 'wavelet', 'mtf_glp', 'mtf_glp_hpm', 'mtf_glp_cbd'], default='network')
+    ap.add_argument('--method', choices=['network', 'gsa', 'sfim', 'wavelet', 'mtf_glp', 'mtf_glp_hpm', 'mtf_glp_cbd', 'bdsd'], default='network')
     ap.add_argument('--mtf-gains', type=float, nargs='+', default=None, metavar='g',
-                    help="--method mtf_glp*: the sensor's MTF gain at Nyquist, one for all bands or one per band (default: a placeholder, 0.3)")
+                    help="--method mtf_glp* / bdsd: the sensor's MTF gain at Nyquist, one for all bands or one per band (default: a placeholder, 0.3)")
+    ap.add_argument('--mtf-gain-pan', type=float, default=None, metavar='g', help="--method bdsd: PAN's MTF gain at Nyquist (default: a placeholder, 0.15)")
+    ap.add_argument('--bdsd-block', type=int, default=None, metavar='N',
+                    help='--method bdsd: fit the weights per block of N x N PAN pixels, N a multiple of 32 that divides both sides (default: one global fit)')
     ap.add_argument('--checkpoint', default=None, help='required for --method network')
     ap.add_argument('--tile', type=int, nargs='+', default=[128], help='one side, or height and width')
     ap.add_argument('--overlap', type=int, default=32)
@@ -68,9 +74,13 @@ def main():
     if ms.dtype != pan.dtype or ms.dtype.name not in ('uint8', 'uint16'):
         ms, pan = ms.astype(np.float64).astype(np.float32), pan.astype(np.float64).astype(np.float32)      # like PSDataset
     ms_chw = np.ascontiguousarray(ms.transpose(2, 0, 1))
-    if a.method.startswith('mtf_glp'):
+    gains = a.mtf_gains[0] if a.mtf_gains is not None and len(a.mtf_gains) == 1 else a.mtf_gains
+    if a.method == 'bdsd':
+        from lgteun_amd import bdsd
+        fused = bdsd.fuse_scene(ms_chw, pan[np.newaxis], block=a.bdsd_block, gains_ms=gains, gain_pan=a.mtf_gain_pan, bit_depth=a.bit_depth,
+                                norm_input=a.norm_input, out_dtype='float32' if a.float else 'uint16')
+    elif a.method.startswith('mtf_glp'):
         from lgteun_amd import mtf_glp
-        gains = a.mtf_gains[0] if a.mtf_gains is not None and len(a.mtf_gains) == 1 else a.mtf_gains
         fused = mtf_glp.fuse_scene(mtf_glp.SCENE_METHODS[a.method], ms_chw, pan[np.newaxis], gains_ms=gains, bit_depth=a.bit_depth, norm_input=a.norm_input,
                                    out_dtype='float32' if a.float else 'uint16')
     elif a.method != 'network':

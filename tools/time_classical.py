@@ -1,9 +1,10 @@
-"""What the classical baselines cost on the GPU (lgteun_amd/classical.py, lgteun_amd/mtf_glp.py): ms per call of `sfim`, `gsa`, `wavelet` and of
-`mtf_glp` with each of its three rules (default gains: one filtered plane per sample) in the same run, with the call synchronised, the
+"""What the classical baselines cost on the GPU (lgteun_amd/classical.py, lgteun_amd/mtf_glp.py, lgteun_amd/bdsd.py): ms per call of `sfim`, `gsa`, `wavelet`,
+of `mtf_glp` with each of its three rules (default gains: one filtered plane per sample) and of `bdsd`, global and with blocks of 128, in the same run, with the call synchronised, the
 median of 20 runs after 5 warm-up runs, at C = 4 and C = 8 with PAN 128 x 128 (batch 1 and batch 32) and for one 4096 x 4096 scene of C = 4.
 Beside each: the bytes the passes must move (SFIM and GSA: the moments pass reads ms and pan, the apply pass reads them again and writes the
 output; Wavelet: ms and pan read once, the output written once; MTF-GLP: see the comment below) divided by the time, as a fraction of the HBM bandwidth (--hbm-gbs, default 8000: the MI355X's 8 TB/s), and the ms per image of the float64
-numpy restatement (tests/classical_ref.py, tests/wavelet_ref.py) on the same box (--no-host skips it).  Prints one JSON line.   python tools/time_classical.py"""
+numpy restatement (tests/classical_ref.py, tests/wavelet_ref.py, ...) on the same box (--no-host skips it).  Per case also `alternating`: sfim, mtf_glp_cbd
+and the two forms of bdsd again, one call of each per round, so that what else the machine does falls on all four alike.  Prints one JSON line.   python tools/time_classical.py"""
 import argparse
 import json
 import os
@@ -20,7 +21,8 @@ import torch  # noqa: E402
 import classical_ref as cr  # noqa: E402
 import wavelet_ref as wr  # noqa: E402
 import mtf_glp_ref as mr  # noqa: E402
-from lgteun_amd import classical, mtf_glp  # noqa: E402
+import bdsd_ref as br  # noqa: E402
+from lgteun_amd import bdsd, classical, mtf_glp  # noqa: E402
 
 CASES = [(1, 4, 32, 32), (32, 4, 32, 32), (1, 8, 32, 32), (32, 8, 32, 32), (1, 4, 1024, 1024)]      # B, C, h, w
 
@@ -38,6 +40,22 @@ def median_ms(fn, warmup, runs):
     return statistics.median(ts)
 
 
+def alternating_ms(fns, warmup, runs):
+    """{name: median ms per call}: one synchronised call of every function per round"""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    ts = {name: [] for name in fns}
+    for _ in range(runs):
+        for name, fn in fns.items():
+            t = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts[name].append((time.perf_counter() - t) * 1e3)
+    return {name: round(statistics.median(v), 4) for name, v in ts.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--runs', type=int, default=20)
@@ -53,13 +71,20 @@ def main():
         row = {}
         glp = {m: (lambda ms, pan, m=m: mtf_glp.mtf_glp(ms, pan, m), lambda ms, pan, m=m: mr.mtf_glp(ms, pan, m, [mr.EQUAL_GAIN] * ms.shape[0]))
                for m in mr.MODES}
+        bd = {blk: (lambda ms, pan, blk=blk: bdsd.bdsd(ms, pan, blk), lambda ms, pan, blk=blk: br.bdsd(ms, pan, [br.EQUAL_GAIN] * ms.shape[0], blk))
+              for blk in (None, 128)}
         for name, fn, host, reads in (('sfim', classical.sfim, cr.sfim, 2), ('gsa', classical.gsa, cr.gsa, 2), ('wavelet', classical.wavelet, wr.wavelet, 1),
-                                      ('mtf_glp', *glp['glp'], 2), ('mtf_glp_hpm', *glp['hpm'], 2), ('mtf_glp_cbd', *glp['cbd'], 3)):
+                                      ('mtf_glp', *glp['glp'], 2), ('mtf_glp_hpm', *glp['hpm'], 2), ('mtf_glp_cbd', *glp['cbd'], 3),
+                                      ('bdsd', *bd[None], 3), ('bdsd_128', *bd[128], 3)):
             moved = 4 * B * (reads * (C * h * w + 16 * h * w) + C * 16 * h * w)
             if name.startswith('mtf_glp'):
                 # equal gains: ms is read by the moments pass, by cbd's second moments pass and by the apply pass; pan by the moments pass, the low-pass and
                 # the apply pass; the one fp64 plane D is written once and read by the apply pass and by cbd's second moments pass
                 moved = B * (4 * reads * C * h * w + 4 * 3 * 16 * h * w + 8 * reads * h * w + 4 * C * 16 * h * w)
+            if name.startswith('bdsd'):
+                # ms is read by its low-pass, by the Gram pass and by the apply pass; pan by its low-pass and by the apply pass; the fp64 planes D and A_k are
+                # written once and read by the Gram pass
+                moved = B * (4 * reads * C * h * w + 4 * 2 * 16 * h * w + 2 * 8 * (C + 1) * h * w + 4 * C * 16 * h * w)
             ms_call = median_ms(lambda: fn(ms, pan), a.warmup, a.runs)
             row[name] = dict(bytes_moved=moved, ms_per_call=round(ms_call, 4), ms_per_image=round(ms_call / B, 4), gb_per_s=round(moved / ms_call / 1e6, 1),
                              hbm_fraction=round(moved / ms_call / 1e6 / a.hbm_gbs, 4))
@@ -67,6 +92,8 @@ def main():
                 t = time.perf_counter()
                 host(ms_np, pan_np)
                 row[name]['numpy_ms_per_image'] = round((time.perf_counter() - t) * 1e3, 2)
+        row['alternating'] = alternating_ms({'sfim': lambda: classical.sfim(ms, pan), 'mtf_glp_cbd': lambda: mtf_glp.mtf_glp(ms, pan, 'cbd'),
+                                             'bdsd': lambda: bdsd.bdsd(ms, pan), 'bdsd_128': lambda: bdsd.bdsd(ms, pan, 128)}, a.warmup, a.runs)
         res[f'B{B}_C{C}_pan{4 * h}x{4 * w}'] = row
     print(json.dumps({'tool': 'time_classical', 'device': torch.cuda.get_device_name(0), 'runs': a.runs, 'warmup': a.warmup,
                       'hbm_gbs': a.hbm_gbs, 'unit': 'ms per call, synchronised, median', 'cases': res}))
