@@ -128,7 +128,16 @@ void lg_plan_destroy(lg_plan* plan);
  * the backward (with the slots it reads).  -3 when n is too small (1 KiB is enough). */
 int lg_plan_describe(const lg_plan* plan, char* buf, size_t n);
 /* bytes of workspace lgteun_forward/backward need for batch B: train = 0 forward only, 1 = forward with LG_FLAG_SAVE + backward,
- * 2 = the same with LG_FLAG_CHAINED (K saved activation sets). */
+ * 2 = the same with LG_FLAG_CHAINED (K saved activation sets).
+ * The workspace contract of every entry that takes one (lgteun_forward / _backward / _dead_forward, lg_op_*), pinned bit for bit by
+ * tests/test_gpu_workspace_contract.py:
+ *  - what the workspace holds ON ENTRY is arbitrary -- zeros, NaNs, huge values, what an earlier call on other inputs left: every region is
+ *    written in a call before that call reads it, and results do not depend on it.  It holds data only (floats, bf16, keep-bit words), never an
+ *    index or a pointer.  256-byte alignment is enough; bytes beyond lg_workspace_bytes are not written and change nothing.
+ *  - a call with workspace_bytes below lg_workspace_bytes, or a null workspace, returns an error and launches nothing.
+ *  - between a forward with LG_FLAG_SAVE and its backward (same plan, B, flags, seed, pointer) the WHOLE workspace must stay untouched: the
+ *    saved activation set(s), the data steps' intermediates and the per-block tables of that forward live there.  Nothing else has to survive
+ *    from one call to the next. */
 size_t lg_workspace_bytes(const lg_plan* plan, int32_t B, int32_t train);
 
 /* Pansharpening.forward (unlg_former.py:50-67).  seed: dropout counter seed (used with LG_FLAG_DROPOUT). */
@@ -144,7 +153,10 @@ int lgteun_dead_forward(const lg_plan* plan, const float* params, void* workspac
 
 /* Backward of the same graph (autograd of unlg_former.py:50-67): needs the workspace of a forward run
  * with LG_FLAG_SAVE.  dout [B,C,H,W].  Accumulates (+=) into `grads` for the live tensors only
- * (shared D/DT/R/RT, eta, last stage's LGT); dead-stage slots are never written. */
+ * (shared D/DT/R/RT, eta, last stage's LGT); dead-stage slots are never written.
+ * A backward reads the saved forward and leaves it as it found it, so it MAY run more than once per forward (autograd's retain_graph): every
+ * run gives the bits of a fresh forward + backward with its dout (the one word a backward accumulates in the forward's tables, max |dh2| in
+ * ffn_scales, is reset by the backward itself).  Not behind lgteun_dead_forward, which overwrites the activation set (above). */
 int lgteun_backward(const lg_plan* plan, const float* params, float* grads, const float* ms, const float* pan,
                     const float* dout, void* workspace, size_t workspace_bytes, int32_t B, int32_t flags,
                     uint64_t seed, void* stream);

@@ -283,7 +283,7 @@ struct FfnDwBwdXArgs {
     float* slab;       // FFN_DW_BWD_X_WGS rows of FFN_DW_BWD_X_ROW floats (per-workgroup partial sums)
     float *d_dww, *d_dwb, *d_w3, *d_b3;   // accumulated (+=) by the deferred reduce launch
     int B, h, w;
-    float* dh2_max = nullptr;   // optional: max |dh2| of the launch is atomically max-ed into this word (float bits; zeroed by k_ffn_scales every forward)
+    float* dh2_max = nullptr;   // optional: max |dh2| of the launch is atomically max-ed into this word (float bits; zeroed by the backward's transpose launch, k_bwd.hip: ffn_transposes)
 };
 #define FFN_DW_BWD_X_WGS 512      // e = 16: two resident workgroups per CU
 #define FFN_DW_BWD_X_DB 576
@@ -319,7 +319,9 @@ inline int reduce_ffn_dw_bwd_slab(const FfnDwBwdXArgs& a, int e, int nhalf, int 
     return rc;
 }
 int launch_transpose(const float* src, float* dst, int rows, int cols, hipStream_t s);  // dst[cols][rows]
-int launch_transpose3(const float* const* src, float* const* dst, const int* rows, const int* cols, int njobs, hipStream_t s);
+// clear[nclear] (at most one word per block of an LGT): words the same launch sets to zero -- max |dh2| of the blocks' ffn_scales rows, so that
+// the start value of the spatial FFN kernel's atomic max belongs to the backward and a second backward on one saved forward begins at zero too
+int launch_transpose3(const float* const* src, float* const* dst, const int* rows, const int* cols, int njobs, hipStream_t s, float* const* clear = nullptr, int nclear = 0);
 
 // ---------------- mixer backward ----------------
 struct ProjO2BwdArgs {

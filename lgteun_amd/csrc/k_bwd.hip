@@ -90,19 +90,23 @@ static int wgrad(const void* Y, int ldy, const void* X, int ldx, float* dW, int 
     return launch_wgrad(a, slab, s);
 }
 
-// W3^T / W2^T / W1^T of the nk blocks k[] into bb.w?t[j], all in ONE launch (backward GEMMs read transposed weights)
+// W3^T / W2^T / W1^T of the nk blocks k[] into bb.w?t[j], all in ONE launch (backward GEMMs read transposed weights).  The same launch sets word 6
+// of the blocks' ffn_scales rows (max |dh2|, ffn_half_bwd) to zero: the forward's k_ffn_scales does so once, but a saved forward may be followed by more
+// than one backward (retain_graph), and the second must not start from the first one's maximum
 static int ffn_transposes(const Blk* blocks, int nk, BwdBufs& bb, hipStream_t s) {
     const float* tsrc[3 * LG_NBLK];
     float* tdst[3 * LG_NBLK];
-    int trows[3 * LG_NBLK], tcols[3 * LG_NBLK], n = 0;
+    float* clear[LG_NBLK];
+    int trows[3 * LG_NBLK], tcols[3 * LG_NBLK], n = 0, nclear = 0;
     for (int i = 0; i < nk; ++i) {
         const Blk& k = blocks[i];
         const int j = k.j, e = k.b.e, n1 = 4 * e;
         tsrc[n] = k.p(B_W3); tdst[n] = bb.w3t[j]; trows[n] = e; tcols[n] = n1; ++n;
         tsrc[n] = k.p(B_W2); tdst[n] = bb.w2t[j]; trows[n] = n1; tcols[n] = n1; ++n;
         tsrc[n] = k.p(B_W1); tdst[n] = bb.w1t[j]; trows[n] = n1; tcols[n] = e; ++n;
+        if (k.pl->ffn(e).bwd_scales) clear[nclear++] = k.ffn_scales + 6;
     }
-    return launch_transpose3(tsrc, tdst, trows, tcols, n, s);
+    return launch_transpose3(tsrc, tdst, trows, tcols, n, s, clear, nclear);
 }
 
 // feed_forward half-block backward: dy (grad wrt block output) -> tmp (grad wrt the mid activation); bb.w?t[j] hold the transposed weights.

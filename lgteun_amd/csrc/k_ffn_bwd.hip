@@ -12,9 +12,14 @@
 #include "hstore.h"
 
 #define LG_MAX_TRANSPOSE_JOBS 15   // W3 / W2 / W1 of the five blocks of an LGT in one launch
-struct TransposeJobs { const float* src[LG_MAX_TRANSPOSE_JOBS]; float* dst[LG_MAX_TRANSPOSE_JOBS]; int rows[LG_MAX_TRANSPOSE_JOBS], cols[LG_MAX_TRANSPOSE_JOBS]; };
+#define LG_MAX_TRANSPOSE_CLEARS 5   // one word per block of an LGT
+struct TransposeJobs {
+    const float* src[LG_MAX_TRANSPOSE_JOBS]; float* dst[LG_MAX_TRANSPOSE_JOBS]; int rows[LG_MAX_TRANSPOSE_JOBS], cols[LG_MAX_TRANSPOSE_JOBS];
+    float* clear[LG_MAX_TRANSPOSE_CLEARS]; int nclear;   // words this launch sets to zero (the start value of a max the kernels behind it take)
+};
 __global__ __launch_bounds__(256) void k_transpose(TransposeJobs t) {
     const int q = blockIdx.y;
+    if (q == 0 && blockIdx.x == 0 && (int)threadIdx.x < t.nclear) *t.clear[threadIdx.x] = 0.f;
     const float* __restrict__ src = t.src[q];
     float* __restrict__ dst = t.dst[q];
     const int rows = t.rows[q], cols = t.cols[q];
@@ -24,9 +29,11 @@ __global__ __launch_bounds__(256) void k_transpose(TransposeJobs t) {
         dst[(long)c * rows + r] = src[i];
     }
 }
-int launch_transpose3(const float* const* src, float* const* dst, const int* rows, const int* cols, int njobs, hipStream_t s) {
-    if (njobs < 1 || njobs > LG_MAX_TRANSPOSE_JOBS) { lg_set_error("transpose: njobs=%d", njobs); return -2; }
+int launch_transpose3(const float* const* src, float* const* dst, const int* rows, const int* cols, int njobs, hipStream_t s, float* const* clear, int nclear) {
+    if (njobs < 1 || njobs > LG_MAX_TRANSPOSE_JOBS || nclear < 0 || nclear > LG_MAX_TRANSPOSE_CLEARS) { lg_set_error("transpose: njobs=%d nclear=%d", njobs, nclear); return -2; }
     TransposeJobs t;
+    t.nclear = nclear;
+    for (int q = 0; q < LG_MAX_TRANSPOSE_CLEARS; ++q) t.clear[q] = q < nclear ? clear[q] : nullptr;
     long nmax = 0;
     for (int q = 0; q < LG_MAX_TRANSPOSE_JOBS; ++q) {
         const int u = q < njobs ? q : 0;

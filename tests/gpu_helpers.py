@@ -34,12 +34,12 @@ def device_drop_masks(seed, dtype=torch.float64):
     return masks
 
 
-def make_ops(C, H, W, K=1, precision=None):
-    """Ops on a fresh module with the deterministic weights (a fresh module builds a fresh plan); precision: None or 'bf16'"""
+def make_ops(C, H, W, K=1, precision=None, ws_fill=None):
+    """Ops on a fresh module with the deterministic weights (a fresh module builds a fresh plan); precision: None or 'bf16'; ws_fill: see Ops"""
     net = make_module(C, K)
     if precision is not None:
         net.precision = precision
-    return Ops(net, H, W)
+    return Ops(net, H, W, ws_fill=ws_fill)
 
 
 GUARD = 1024        # floats of NaN band on each side of a guarded output (4 KiB: the output keeps its 16-byte alignment)
@@ -58,16 +58,63 @@ def assert_guards_intact(buf, what):
     assert bool(lo.all()) and bool(hi.all()), (what, 'written outside the output', int((~lo).sum()), int((~hi).sum()))
 
 
+WS_GUARD_BYTES = 1 << 20      # NaN band on each side of a guarded workspace: the level-0 slabs are megabytes, a band of 4 KiB would only catch near misses
+# what a workspace holds on entry: every byte 0x00, 0xFF (every float a NaN) or 0x5A (every float a finite 1.5e16, every bf16 the same)
+WS_FILLS = {'zero': 0x00, 'nan': 0xFF, 'big': 0x5A}
+
+
+def guarded_workspace(need_bytes, fill, device='cuda'):
+    """(buffer, ws_view): ws_view is a uint8 view of exactly need_bytes that starts 256-byte aligned (the granule of carve()) inside a larger
+    float buffer, WS_GUARD_BYTES of NaN floats on each side, and is filled with `fill` (a key of WS_FILLS or a byte)"""
+    need_bytes = int(need_bytes)
+    inner = (need_bytes + 3) // 4 * 4
+    buf = torch.full(((2 * WS_GUARD_BYTES + inner) // 4,), float('nan'), device=device)
+    view = buf.view(torch.uint8)[WS_GUARD_BYTES:WS_GUARD_BYTES + need_bytes]
+    assert view.data_ptr() % 256 == 0, view.data_ptr()
+    fill_workspace(view, fill)
+    return buf, view
+
+
+def fill_workspace(ws_view, fill):
+    ws_view.fill_(WS_FILLS.get(fill, fill))
+
+
+def assert_workspace_guards(buf, what):
+    """both bands of a guarded_workspace buffer are still all-NaN: nothing was written in front of or behind the workspace"""
+    n = WS_GUARD_BYTES // 4
+    lo, hi = torch.isnan(buf[:n]), torch.isnan(buf[-n:])
+    assert bool(lo.all()) and bool(hi.all()), (what, 'written outside the workspace', int((~lo).sum()), int((~hi).sum()))
+
+
 class Ops:
-    def __init__(self, net, H, W):
+    def __init__(self, net, H, W, ws_fill=None):
+        """ws_fill=None: the engine's cached torch.empty workspace.  A key of WS_FILLS: every call runs on a guarded workspace of the test's own
+        (guarded_workspace, allocated once per (B, train)) that is re-filled before the call, and whose bands are checked behind it.
+        'stale': the same workspace, NOT re-filled: exactly what the previous call on it left (set `ops.ws_fill` between calls)"""
         self.net = net
         self.eng = net.engine()
         self.lib = self.eng.lib
         self.plan = self.eng.plan(H, W)   # precision follows net.precision
         self.H, self.W = H, W
+        self.ws_fill = ws_fill
+        self._guarded = {}
 
     def ws(self, B, train=False):
-        return self.eng.workspace(self.plan, B, train)
+        if self.ws_fill is None:
+            return self.eng.workspace(self.plan, B, train)
+        key = (B, int(train))
+        if key not in self._guarded:
+            need = int(self.lib.lg_workspace_bytes(self.plan, B, int(train)))
+            assert need > 0, key
+            self._guarded[key] = guarded_workspace(need, 'nan' if self.ws_fill == 'stale' else self.ws_fill, self.eng.device)
+        elif self.ws_fill != 'stale':
+            fill_workspace(self._guarded[key][1], self.ws_fill)
+        return self._guarded[key][1]
+
+    def _ws_intact(self, what):
+        """behind a call: the bands of every guarded workspace handed out so far (nothing to do without ws_fill)"""
+        for key, (buf, _) in self._guarded.items():
+            assert_workspace_guards(buf, (what, key))
 
     @staticmethod
     def _out(shape, device, guard):
@@ -106,8 +153,21 @@ class Ops:
         ws = self.ws(B, train=bool(flags & _lib.LG_FLAG_SAVE))                 # LG_FLAG_SAVE writes the training workspace's save slots
         _lib.check(self.lib.lg_op_lgt(self.plan, _ptr(self.eng.flat), stage, _ptr(z), _ptr(out), _ptr(ws), ws.numel(), B, flags, seed,
                                       _stream_ptr()), 'lg_op_lgt')
+        self._ws_intact('lg_op_lgt')
         if guard:
             assert_guards_intact(buf, 'lg_op_lgt')
+        return out
+
+    def lgt_stages(self, stage0, n, z, flags=0, seed=0, grid_cap=0, guard=False):
+        """lg_op_lgt_stages: z [n,B,C,H,W] -> out [n,B,C,H,W], the stages stage0 .. stage0 + n - 1 as one pass"""
+        B = z.shape[1]
+        buf, out = self._out(z.shape, z.device, guard)
+        ws = self.ws(B)
+        _lib.check(self.lib.lg_op_lgt_stages(self.plan, _ptr(self.eng.flat), stage0, n, _ptr(z), _ptr(out), _ptr(ws), ws.numel(), B, flags, seed,
+                                             grid_cap, _stream_ptr()), 'lg_op_lgt_stages')
+        self._ws_intact('lg_op_lgt_stages')
+        if guard:
+            assert_guards_intact(buf, 'lg_op_lgt_stages')
         return out
 
     def block(self, stage, blk, which, x, guard=False):
@@ -117,6 +177,7 @@ class Ops:
         ws = self.ws(B)
         _lib.check(self.lib.lg_op_block(self.plan, _ptr(self.eng.flat), stage, blk, which, _ptr(x), _ptr(y), _ptr(ws),
                                         ws.numel(), B, _stream_ptr()), 'lg_op_block')
+        self._ws_intact('lg_op_block')
         if guard:
             assert_guards_intact(buf, 'lg_op_block')
         return y
@@ -157,6 +218,7 @@ class Ops:
         ws = self.ws(B, train=True)
         _lib.check(self.lib.lg_op_block_bwd(self.plan, _ptr(self.eng.flat), _ptr(grads), stage, blk, which, _ptr(x), _ptr(dy),
                                             _ptr(dx), _ptr(ws), ws.numel(), B, _stream_ptr()), 'lg_op_block_bwd')
+        self._ws_intact('lg_op_block_bwd')
         if guard:
             assert_guards_intact(buf, 'lg_op_block_bwd')
         self._grads_intact(state, grads, 'lg_op_block_bwd')
@@ -170,6 +232,7 @@ class Ops:
         ws = self.ws(B, train=True)
         _lib.check(self.lib.lg_op_data_step_bwd(self.plan, _ptr(self.eng.flat), _ptr(grads), stage, _ptr(z), _ptr(ms), _ptr(pan),
                                                 _ptr(dz_out), _ptr(dz), _ptr(ws), ws.numel(), B, _stream_ptr()), 'lg_op_data_step_bwd')
+        self._ws_intact('lg_op_data_step_bwd')
         if guard:
             assert_guards_intact(buf, 'lg_op_data_step_bwd')
         self._grads_intact(state, grads, 'lg_op_data_step_bwd')
@@ -183,6 +246,7 @@ class Ops:
         ws = self.ws(B, train=True)
         _lib.check(self.lib.lg_op_lgt_bwd(self.plan, _ptr(self.eng.flat), _ptr(grads), stage, _ptr(z), _ptr(dout), _ptr(dz), _ptr(ws),
                                           ws.numel(), B, flags, seed, _stream_ptr()), 'lg_op_lgt_bwd')
+        self._ws_intact('lg_op_lgt_bwd')
         if guard:
             assert_guards_intact(buf, 'lg_op_lgt_bwd')
         self._grads_intact(state, grads, 'lg_op_lgt_bwd')
