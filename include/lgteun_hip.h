@@ -66,6 +66,16 @@ extern "C" {
  * same arithmetic, bitwise the same results; other plans run one by one whatever the bit says. */
 #define LG_FLAG_STAGEWISE 128
 
+/* forward, with LG_FLAG_FAITHFUL on a plan that runs its dead stages as one pass (and neither LG_FLAG_STAGEWISE nor LG_FLAG_DEFER_DEAD): keep the
+ * dead pass and the live stage's pass APART, one after the other, as the library ran them before the live stage rode along.  Default (bit clear):
+ * the plane and pixel kernels -- patch embedding, FFT mixer, down, up + fusion, tail -- launch ONCE over all K B samples, stages 0 .. K-2 dead and
+ * stage K-1 live (it alone saves for the backward, and its output goes to `out`); the persistent local-mixer and FFN kernels still launch twice,
+ * non-saving over the (K-1) B dead samples and saving over the live B.  At C = 4, B = 32, 128 x 128 the level-0 FFT mixer then runs 1 024 planes in
+ * two full rounds of the chip instead of 768 in one and a half plus 256 at one plane per CU.  Same work, same arithmetic, bitwise the same results.
+ * Such a plan keeps the transient forward buffers of K stages of B samples side by side: dead stage i in slot i, the live stage ALWAYS in slot K-1,
+ * whichever of these paths ran it; lgteun_backward reads it there.  (Other plans -- K = 2, C = 8, chained training -- have one slot, as before.) */
+#define LG_FLAG_LIVE_APART 256
+
 /* kernel ids for the live HIP-event timing facility (lg_prof_*) */
 enum lg_kernel_id {
     LG_K_NONE = 0, LG_K_FFN1, LG_K_FFN2, LG_K_FFT, LG_K_ATTN, LG_K_UPFUSE, LG_K_DOWN, LG_K_EMBED, LG_K_TAIL, LG_K_DATASTEP,
@@ -114,7 +124,7 @@ typedef struct lg_plan lg_plan; /* host-side, immutable after creation */
 
 const char* lg_version(void);
 /* Bumped whenever a struct layout, an argument meaning or a caller-provided buffer size changes (2: lg_config.variant, the data step's
- * tmp of 3*B*C*H*W/4 + B*H*W floats).  Additions keep it: lg_op_lgt_stages, lg_workspace_deadout, LG_FLAG_STAGEWISE, the lg_debug_stage_* entries and the classical baselines (lg_classical_workspace_bytes, lg_interp23_up4, lg_sfim, lg_gsa, then lg_wavelet, lg_wavelet_taps, then lg_mtfglp_workspace_bytes, lg_mtf_glp, then lg_bdsd_workspace_bytes, lg_bdsd) came without a bump (no struct,
+ * tmp of 3*B*C*H*W/4 + B*H*W floats).  Additions keep it: lg_op_lgt_stages, lg_workspace_deadout, LG_FLAG_STAGEWISE, LG_FLAG_LIVE_APART, the lg_debug_stage_* entries and lg_debug_live_slot and the classical baselines (lg_classical_workspace_bytes, lg_interp23_up4, lg_sfim, lg_gsa, then lg_wavelet, lg_wavelet_taps, then lg_mtfglp_workspace_bytes, lg_mtf_glp, then lg_bdsd_workspace_bytes, lg_bdsd) came without a bump (no struct,
  * argument or caller-sized buffer changed: workspaces are sized by lg_workspace_bytes, which grew for the plans that batch their dead stages).  A binding checks it at load time -- lgteun_amd/_lib.py does -- instead of passing a stale struct. */
 #define LG_ABI_VERSION 2
 int32_t lg_abi_version(void);
@@ -129,6 +139,9 @@ void lg_plan_destroy(lg_plan* plan);
 int lg_plan_describe(const lg_plan* plan, char* buf, size_t n);
 /* bytes of workspace lgteun_forward/backward need for batch B: train = 0 forward only, 1 = forward with LG_FLAG_SAVE + backward,
  * 2 = the same with LG_FLAG_CHAINED (K saved activation sets).
+ * A plan that runs its dead stages as one pass (C = 4, K >= 3, planes up to 128 x 128; LG_FLAG_STAGEWISE above) keeps the transient LGT forward
+ * buffers of K stages side by side, train = 0 and 1 alike (LG_FLAG_LIVE_APART above): C = 4, K = 4, 128 x 128, B = 32 needs 2 263 MiB (train = 0) /
+ * 6 482 MiB (train = 1), 512 MiB more than with K - 1 slots.  Saved tensors stay B-sized; K = 2, C = 8 and train = 2 sizes are unchanged.
  * The workspace contract of every entry that takes one (lgteun_forward / _backward / _dead_forward, lg_op_*), pinned bit for bit by
  * tests/test_gpu_workspace_contract.py:
  *  - what the workspace holds ON ENTRY is arbitrary -- zeros, NaNs, huge values, what an earlier call on other inputs left: every region is
@@ -269,6 +282,11 @@ int lg_op_lgt_stages(const lg_plan* plan, const float* params, int32_t stage0, i
  * [B,C,H,W] at byte offset *offset + i * *stage_stride.  *stage_stride is 0 for a plan that keeps one slot (every dead stage overwrites the
  * previous one's). */
 int lg_workspace_deadout(const lg_plan* plan, int32_t B, int32_t train, size_t* offset, size_t* stage_stride);
+/* Debug, host only: where the transient forward buffers lie in the workspace of (plan, B, train), as byte offsets.  out53 = { end offset of the
+ * forward carving, bytes of the backward's part behind it (0 for train = 0), first sample of the live stage's slot ((K-1) B for a plan that keeps K
+ * slots, else 0), then for each of the five blocks and each of its buffers xin, xmid, xout, g, o2 the pair { offset of slot 0, offset of the live
+ * stage's slot } }.  lg_workspace_bytes = out53[0] + out53[1]. */
+int lg_debug_live_slot(const lg_plan* plan, int32_t B, int32_t train, size_t* out53);
 /* Debug, host only (no device, no launch): the units the workgroups of a persistent multi-stage launch walk, from the functions the kernels call.
  * kind 0: the fused FFN (k_ffn_xr) -- split 0: `units` strips in even runs; split != 0: `units` strip PAIRS, the two workgroups w and w + grid/2
  * on the same run of pairs, the second at strip base `units`.  kind 1: the local mixer (k_attn_m) -- `units` window quads; split = eighths of a

@@ -19,6 +19,7 @@ LG_FLAG_BWD_DATA = 16
 LG_FLAG_CHAINED = 32
 LG_FLAG_DEFER_DEAD = 64
 LG_FLAG_STAGEWISE = 128
+LG_FLAG_LIVE_APART = 256
 KERNEL_IDS = {n: i for i, n in enumerate(['none', 'ffn1', 'ffn', 'fft', 'attn', 'upfuse', 'down', 'embed', 'tail', 'datastep', 'ffn1_bwd',
                                            'ffn2_bwd', 'fft_bwd', 'attn_bwd', 'wgrad', 'batch', 'scene_gather', 'scene_blend'])}
 
@@ -129,6 +130,7 @@ SIGNATURES = {
     'lg_debug_stage_runs': (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), c_int32]),
     'lg_debug_stage_decision': (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32)]),
     'lg_workspace_deadout': (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_size_t), POINTER(c_size_t)]),
+    'lg_debug_live_slot': (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_size_t)]),
     'lg_op_block': (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_int32,
                               c_void_p]),
     'lg_dropout_mask': (c_int32, [c_uint64, c_int32, c_int32, c_int64, c_int64, c_void_p, c_void_p]),

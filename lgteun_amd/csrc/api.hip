@@ -100,6 +100,24 @@ extern "C" int lg_workspace_deadout(const lg_plan* plan, int32_t B, int32_t trai
     return 0;
 }
 
+extern "C" int lg_debug_live_slot(const lg_plan* plan, int32_t B, int32_t train, size_t* out53) {
+    if (!plan || B <= 0 || train < 0 || train > 2 || !out53) { lg_set_error("debug_live_slot: invalid argument"); return -1; }
+    NetBufs nb;
+    char base[1];   // carve() only adds offsets to the base it is given
+    carve(plan, B, train, base, nb);
+    const NetBufs lv = live_view(nb);
+    size_t* o = out53;
+    *o++ = nb.bytes; *o++ = train ? bwd_workspace_bytes(plan, B) : 0; *o++ = nb.live_s0;
+    auto off = [&](const float* p) { return (size_t)(reinterpret_cast<const char*>(p) - base); };
+    for (int j = 0; j < LG_NBLK; ++j) {
+        const BlockBufs &a = nb.blk[j], &l = lv.blk[j];
+        const float* pa[5] = {a.xin, a.xmid, a.xout, a.g, a.o2};
+        const float* pl[5] = {l.xin, l.xmid, l.xout, l.g, l.o2};
+        for (int f = 0; f < 5; ++f) { *o++ = off(pa[f]); *o++ = off(pl[f]); }
+    }
+    return 0;
+}
+
 extern "C" int lgteun_backward(const lg_plan* plan, const float* params, float* grads, const float* ms, const float* pan,
                                const float* dout, void* workspace, size_t workspace_bytes, int32_t B, int32_t flags, uint64_t seed,
                                void* stream) {
@@ -135,6 +153,7 @@ extern "C" int lg_op_lgt(const lg_plan* plan, const float* params, int32_t stage
     if (!plan || !params || !z || !out || !workspace || stage < 0 || stage >= plan->cfg.K) { lg_set_error("op_lgt: invalid argument"); return -1; }
     NetBufs nb;
     if (int rc = carve_checked("op_lgt", plan, B, (flags & LG_FLAG_SAVE) ? 1 : 0, workspace, workspace_bytes, nb)) return rc;
+    nb = live_view(nb);   // a single stage runs where the live stage does: slot K-1 of the transient buffers (workspace.h)
     if (int rc = prep_stages(plan, params, stage, stage + 1, nb, (hipStream_t)stream)) return rc;
     return lgt_fwd(plan, params, stage, z, out, nb, B, flags, seed, (hipStream_t)stream);
 }
@@ -202,6 +221,7 @@ extern "C" int lg_op_block(const lg_plan* plan, const float* params, int32_t sta
     NetBufs nb;
     int rc;
     if ((rc = carve_checked("op_block", plan, B, 0, workspace, workspace_bytes, nb))) return rc;
+    nb = live_view(nb);   // a single stage runs where the live stage does: slot K-1 of the transient buffers (workspace.h)
     Blk k = nb.block(plan, params, nullptr, stage, blk);
     BlockBufs& bb = k.b;
     if (which == 0 || which == 1) {
@@ -238,6 +258,7 @@ extern "C" int lg_op_block_bwd(const lg_plan* plan, const float* params, float* 
     NetBufs nb;
     int rc;
     if ((rc = carve_checked("op_block_bwd", plan, B, 1, workspace, workspace_bytes, nb))) return rc;
+    nb = live_view(nb);   // a single stage runs where the live stage does: slot K-1 of the transient buffers (workspace.h)
     Blk k = nb.block(plan, params, grads, stage, blk);
     BlockBufs& bb = k.b;
     // forward of the half-block with everything saved
@@ -281,6 +302,7 @@ extern "C" int lg_op_lgt_bwd(const lg_plan* plan, const float* params, float* gr
     NetBufs nb;
     int rc;
     if ((rc = carve_checked("op_lgt_bwd", plan, B, 1, workspace, workspace_bytes, nb))) return rc;
+    nb = live_view(nb);   // a single stage runs where the live stage does: slot K-1 of the transient buffers (workspace.h)
     if ((rc = prep_stages(plan, params, stage, stage + 1, nb, s))) return rc;
     if ((rc = lgt_fwd(plan, params, stage, z, nb.deadout, nb, B, flags | LG_FLAG_SAVE, seed, s))) return rc;
     return op_lgt_bwd(plan, params, grads, stage, nb, (char*)workspace + nb.bytes, z, dout, dz, B, flags, seed, s);

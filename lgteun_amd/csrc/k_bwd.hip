@@ -443,7 +443,7 @@ int net_backward(const lg_plan* pl, const float* P, float* G, const float* ms, c
     const bool do_lgt = !(flags & (LG_FLAG_BWD_LGT | LG_FLAG_BWD_DATA)) || (flags & LG_FLAG_BWD_LGT);
     const bool do_data = !(flags & (LG_FLAG_BWD_LGT | LG_FLAG_BWD_DATA)) || (flags & LG_FLAG_BWD_DATA);
     // ---------------- LGT of the last stage: the only live one
-    if (do_lgt) RC(lgt_bwd(pl, P, G, c.K - 1, nb, bb, dout, nb.Z[c.K], B, flags, seed, s));
+    if (do_lgt) RC(lgt_bwd(pl, P, G, c.K - 1, live_view(nb), bb, dout, nb.Z[c.K], B, flags, seed, s));   // its xin / xmid / xout: slot K-1 (workspace.h)
     if (!do_data) return reduce_queue_end();
     // merged form: the LGT's gradients are complete here (LG_FLAG_BWD_LGT / _DATA, the two-bucket all-reduce), the K data steps follow in ONE launch
     if (do_lgt && !bb.rq.per_block) RC(bb.rq.flush());

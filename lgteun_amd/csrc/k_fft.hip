@@ -513,13 +513,14 @@ __global__ void __launch_bounds__(NTH, (LG >= 7 && NTH == 512) ? 4 : 1) k_fftmix
     // ---- amplitude / phase edit (LGT.py:168-177)
     const long po = stage_of_unit(a.sg, plane, a.ch) * a.sg.pstride + ch;   // several stages in one launch (kernels.h: StageSel): sample = plane / ch
     const float aw = a.ampw[po], ab = a.ampb[po], pw = a.phaw[po], pb = a.phab[po];
+    const int splane = plane - a.sg.s0 * a.ch;   // the save tensors hold the planes of samples s0 .. only (kernels.h: StageSel::s0); < 0: this plane saves nothing
     for (int it = threadIdx.x; it < n * (half + 1); it += NTH) {
         int q, c;
         fftr_bin(it, n, lg, q, c);
         float amp, pha;
         const float2 ed = bin_edit_fwd(buf[q * HP + c], aw, ab, pw, pb, amp, pha);
-        if (a.amp) {
-            size_t o = ((size_t)plane * n + q) * (half + 1) + c;
+        if (a.amp && splane >= 0) {
+            size_t o = ((size_t)splane * n + q) * (half + 1) + c;
             __builtin_nontemporal_store(amp, a.amp + o);      // saved for the backward only: streaming stores
             __builtin_nontemporal_store(pha, a.pha + o);
         }
@@ -544,11 +545,11 @@ __global__ void __launch_bounds__(NTH, (LG >= 7 && NTH == 512) ? 4 : 1) k_fftmix
         const float2 r0 = r[0], r1 = r[1];
         const float v[4] = {r0.x * sc, r0.y * sc, r1.x * sc, r1.y * sc};
         *reinterpret_cast<float4*>(o + i) = make_float4(fabsf(v[0]), fabsf(v[1]), fabsf(v[2]), fabsf(v[3]));
-        if (a.sgn) {
+        if (a.sgn && splane >= 0) {
             float sg[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) sg[u] = (v[u] > 0.f) ? 1.0f : ((v[u] < 0.f) ? -1.0f : 0.0f);
-            { typedef float f4 __attribute__((ext_vector_type(4))); __builtin_nontemporal_store((f4){sg[0], sg[1], sg[2], sg[3]}, reinterpret_cast<f4*>(a.sgn + (size_t)plane * n * n + i)); }
+            { typedef float f4 __attribute__((ext_vector_type(4))); __builtin_nontemporal_store((f4){sg[0], sg[1], sg[2], sg[3]}, reinterpret_cast<f4*>(a.sgn + (size_t)splane * n * n + i)); }
         }
     }
     FFT_STAMP(7);

@@ -42,11 +42,10 @@ int data_step_fwd(const lg_plan* pl, const float* P, int stage, const float* z_i
     return launch_resample_dw(1, 2, a, s);
 }
 
-int block_mixer_fwd(const Blk& k, int B, int flags, uint64_t seed, hipStream_t s, const StageSel& sg) {
-    int rc;
+// the two launches of a block's mixer: the global (FFT) half, a plane kernel, and the local half + proj + residual, a persistent one
+static int mixer_fft_fwd(const Blk& k, int B, int flags, hipStream_t s, const StageSel& sg) {
     const lg_plan* pl = k.pl;
     const BlockBufs& bb = k.b;
-    const MixerRoute& mr = pl->mixer(bb.e);
     FftArgs f;
     f.g = bb.g; f.o = bb.o2;
     f.amp = (flags & LG_FLAG_SAVE) ? bb.amp : nullptr;
@@ -56,7 +55,12 @@ int block_mixer_fwd(const Blk& k, int B, int flags, uint64_t seed, hipStream_t s
     f.ampw = k.p(B_AMPW); f.ampb = k.p(B_AMPB); f.phaw = k.p(B_PHAW); f.phab = k.p(B_PHAB);
     f.ch = bb.e / 2; f.planes = B * f.ch; f.n = bb.h; f.h = bb.h; f.w = bb.w; f.full = pl->route.fft_full;
     f.sg = sg;
-    if ((rc = launch_fftmix(f, s))) return rc;
+    return launch_fftmix(f, s);
+}
+static int mixer_local_fwd(const Blk& k, int B, int flags, uint64_t seed, hipStream_t s, const StageSel& sg) {
+    const lg_plan* pl = k.pl;
+    const BlockBufs& bb = k.b;
+    const MixerRoute& mr = pl->mixer(bb.e);
     AttnArgs t;
     t.x = bb.xin; t.o2 = bb.o2; t.y = bb.xmid; t.posT = k.posT; t.pos = k.p(B_POS);
     t.bf16 = mr.bf16 ? 1 : 0;
@@ -69,6 +73,10 @@ int block_mixer_fwd(const Blk& k, int B, int flags, uint64_t seed, hipStream_t s
     if ((flags & LG_FLAG_SAVE) && mr.stats) { t.save_o = bb.att_o; t.save_l = bb.att_l; }
     if (sg.n > 1 && mr.fwd == ATTN_FWD_VALU) { lg_set_error("mixer: the vector-pipe kernel takes one stage per launch"); return -2; }
     return mr.fwd == ATTN_FWD_VALU ? launch_attn(bb.e, t, s) : launch_attn_m(bb.e, t, s);
+}
+int block_mixer_fwd(const Blk& k, int B, int flags, uint64_t seed, hipStream_t s, const StageSel& sg) {
+    if (int rc = mixer_fft_fwd(k, B, flags, s, sg)) return rc;
+    return mixer_local_fwd(k, B, flags, seed, s, sg);
 }
 
 // next: the block whose mixer reads this FFN's output directly (its LN1 + planar split ride in this FFN's epilogue), or null
@@ -141,22 +149,45 @@ int prep_stages(const lg_plan* pl, const float* P, int st0, int st1, const NetBu
 // LGT.forward (LGT.py:314-344) on z -> out with the buffers of `nb`, whose rows of this stage the caller has filled (prep_stages)
 // nst > 1: the LGTs of stages stage .. stage + nst - 1 in ONE pass, every kernel launched once over nst * B samples (kernels.h: StageSel) -- stage
 // stage + i reads z + i * zstride, writes out + i * B C H W and uses samples [i B, (i + 1) B) of every buffer of `nb` (workspace.h carves them
-// that large for a plan with stage_batch).  Never with LG_FLAG_SAVE: only dead stages run this way.
+// that large for a plan with stage_batch).
+// live_out == null: never with LG_FLAG_SAVE, only dead stages run this way.
+// live_out != null: the LIVE stage rides along as the last of the nst = K stages (stage = 0; its slot K-1 is the one live_view(nb) names).  The plane and
+// pixel kernels -- embed, FFT mixer, down, up + fusion, tail -- launch once over all K B samples and save (LG_FLAG_SAVE) from sample (K-1) B on only; the
+// persistent kernels -- local mixer, FFN -- launch twice, the same two launches a dead pass and a live pass make: the live stage's own (saving) launch on
+// slot K-1 and the multi-stage non-saving instance over the K-1 dead stages (per block: the live pair first, see `block` below).  The last stage's output
+// goes to live_out.
 int lgt_fwd(const lg_plan* pl, const float* P, int stage, const float* z, float* out, const NetBufs& nb, int B, int flags, uint64_t seed,
-            hipStream_t s, int nst, long zstride, int grid_cap) {
+            hipStream_t s, int nst, long zstride, int grid_cap, float* live_out) {
     const lg_config& c = pl->cfg;
     const int E = 4 * c.C;
+    const bool ride = live_out != nullptr;
     int rc;
     StageSel sg;
     if (nst > 1) {
-        if (!pl->stage_batch || (flags & LG_FLAG_SAVE)) { lg_set_error("lgt_fwd: this plan / call runs one stage per pass"); return -2; }
+        if (!pl->stage_batch || (!ride && (flags & LG_FLAG_SAVE))) { lg_set_error("lgt_fwd: this plan / call runs one stage per pass"); return -2; }
         sg.n = nst; sg.Bs = B; sg.pstride = pl->stage_stride; sg.zstride = zstride; sg.grid_cap = grid_cap;
         nb.stage_strides(sg);
     }
-    B *= nst;   // what every kernel below sees: a plain batch
+    if (ride && (stage != 0 || nst != c.K || nb.live_s0 != (size_t)(nst - 1) * B)) { lg_set_error("lgt_fwd: the live stage rides behind all K-1 dead ones, in slot K-1"); return -2; }
+    const int Bs = B, fdead = flags & ~LG_FLAG_SAVE;
+    StageSel sgd = sg;           // the persistent kernels' dead launch: stages 0 .. nst - 2
+    if (ride) { sg.s0 = (nst - 1) * Bs; sgd.n = nst - 1; }
+    B *= nst;   // what every plane / pixel kernel below sees: a plain batch
     const LgtSlots L{pl, P, nullptr, stage};
-    Blk k[LG_NBLK];
-    for (int j = 0; j < LG_NBLK; ++j) k[j] = nb.block(pl, P, nullptr, stage, j);
+    Blk k[LG_NBLK], kl[LG_NBLK];   // kl: the live stage's blocks (ride)
+    const NetBufs lv = ride ? live_view(nb) : nb;
+    for (int j = 0; j < LG_NBLK; ++j) { k[j] = nb.block(pl, P, nullptr, stage, j); kl[j] = lv.block(pl, P, nullptr, stage + nst - 1, j); }
+    // one LGB block j: mixer, then FFN; next: the block whose LN1 + planar split ride in this FFN's epilogue, or -1.  Riding: the FFT mixer over all K B samples,
+    // then the live stage's persistent pair (local mixer, FFN: saving), then the dead stages' -- the launch that follows reads K-1 stages' worth of what the dead
+    // pair wrote last and finds it in the caches; behind the live pair's saved tensors it would not
+    auto block = [&](int j, int next) -> int {
+        int r;
+        if (!ride) return (r = block_mixer_fwd(k[j], B, flags, seed, s, sg)) ? r : block_ffn_fwd(k[j], next < 0 ? nullptr : &k[next], B, flags, s, sg);
+        if ((r = mixer_fft_fwd(k[j], B, flags, s, sg))) return r;
+        if ((r = mixer_local_fwd(kl[j], Bs, flags, seed, s, StageSel())) || (r = block_ffn_fwd(kl[j], next < 0 ? nullptr : &kl[next], Bs, flags, s, StageSel()))) return r;
+        if ((r = mixer_local_fwd(k[j], sgd.n * Bs, fdead, seed, s, sgd))) return r;
+        return block_ffn_fwd(k[j], next < 0 ? nullptr : &k[next], sgd.n * Bs, fdead, s, sgd);
+    };
     EmbedArgs ea;
     ea.z = z; ea.x = nb.x0; ea.g = nb.blk[0].g;
     ea.dww = L.p(L_PE_DWW); ea.dwb = L.p(L_PE_DWB); ea.w = L.p(L_PE_W); ea.b = L.p(L_PE_B); ea.lng = L.p(L_PE_LNG); ea.lnb = L.p(L_PE_LNB);
@@ -164,8 +195,8 @@ int lgt_fwd(const lg_plan* pl, const float* P, int stage, const float* z, float*
     ea.HW = c.H * c.W; ea.total = (long)B * c.H * c.W; ea.sg = sg;
     if ((rc = launch_embed(c.C, ea, s))) return rc;
     // encoder LGB (2 blocks)
-    if ((rc = block_mixer_fwd(k[0], B, flags, seed, s, sg)) || (rc = block_ffn_fwd(k[0], &k[1], B, flags, s, sg))) return rc;
-    if ((rc = block_mixer_fwd(k[1], B, flags, seed, s, sg)) || (rc = block_ffn_fwd(k[1], nullptr, B, flags, s, sg))) return rc;
+    if ((rc = block(0, 1))) return rc;
+    if ((rc = block(1, -1))) return rc;
     // down
     DownArgs da;
     da.x = nb.blk[1].xout; da.y = nb.blk[2].xin; da.g = nb.blk[2].g;
@@ -175,7 +206,7 @@ int lgt_fwd(const lg_plan* pl, const float* P, int stage, const float* z, float*
     da.B = B; da.H = c.H; da.W = c.W; da.sg = sg;
     if ((rc = launch_down(E, da, s))) return rc;
     // bottleneck
-    if ((rc = block_mixer_fwd(k[2], B, flags, seed, s, sg)) || (rc = block_ffn_fwd(k[2], nullptr, B, flags, s, sg))) return rc;
+    if ((rc = block(2, -1))) return rc;
     // up + fusion
     UpFuseArgs ua;
     ua.xb = nb.blk[2].xout; ua.skip = nb.blk[1].xout; ua.y = nb.blk[3].xin; ua.g = nb.blk[3].g;
@@ -185,11 +216,11 @@ int lgt_fwd(const lg_plan* pl, const float* P, int stage, const float* z, float*
     ua.B = B; ua.H = c.H; ua.W = c.W; ua.sg = sg;
     if ((rc = launch_upfuse(E, ua, s))) return rc;
     // decoder LGB (2 blocks)
-    if ((rc = block_mixer_fwd(k[3], B, flags, seed, s, sg)) || (rc = block_ffn_fwd(k[3], &k[4], B, flags, s, sg))) return rc;
-    if ((rc = block_mixer_fwd(k[4], B, flags, seed, s, sg)) || (rc = block_ffn_fwd(k[4], nullptr, B, flags, s, sg))) return rc;
+    if ((rc = block(3, 4))) return rc;
+    if ((rc = block(4, -1))) return rc;
     // tail
     TailArgs ta;
-    ta.x = nb.blk[4].xout; ta.z = z; ta.out = out;
+    ta.x = nb.blk[4].xout; ta.z = z; ta.out = out; ta.out_last = live_out;
     ta.w = L.p(L_TAILW); ta.b = L.p(L_TAILB);
     ta.HW = c.H * c.W; ta.total = (long)B * c.H * c.W; ta.sg = sg;
     return launch_tail(c.C, ta, s);
@@ -255,8 +286,13 @@ extern "C" int lgteun_forward(const lg_plan* plan, const float* params, const fl
         if (i < c.K - 1 && dead && !one_pass &&
             (rc = lgt_fwd(plan, params, i, nb.Z[i + 1], dead_out(plan, nb, i, B), nb, B, flags & ~LG_FLAG_SAVE, seed, s))) return rc;
     }
+    // One pass: the live stage rides along in the plane and pixel launches of the dead ones (lgt_fwd: live_out), 1 024 instead of 768 + 256 planes of
+    // the level-0 FFT mixer at B = 32; LG_FLAG_LIVE_APART keeps the dead pass and the live pass apart.  Either way, and on every other path, the live
+    // stage's transient buffers are slot K-1 (workspace.h: live_view) -- the backward reads them there.
+    if (one_pass && !(flags & LG_FLAG_LIVE_APART))
+        return lgt_fwd(plan, params, 0, nb.Z[1], nb.deadout, nb, B, flags, seed, s, c.K, (long)(nb.Z[2] - nb.Z[1]), 0, out);
     if (one_pass && (rc = dead_stages(plan, params, nb, B, flags, seed, s))) return rc;
-    return lgt_fwd(plan, params, c.K - 1, nb.Z[c.K], out, nb, B, flags, seed, s);
+    return lgt_fwd(plan, params, c.K - 1, nb.Z[c.K], out, live_view(nb), B, flags, seed, s);
 }
 
 extern "C" int lgteun_dead_forward(const lg_plan* plan, const float* params, void* workspace, size_t workspace_bytes, int32_t B,

@@ -290,7 +290,7 @@ __global__ __launch_bounds__(256) void k_down(DownArgs a) {
             u4.x += wgt * v.x; u4.y += wgt * v.y; u4.z += wgt * v.z; u4.w += wgt * v.w;
         }
     }
-    if (a.u_save && pv) *reinterpret_cast<float4*>(a.u_save + p * E + 4 * q) = u4;
+    if (a.u_save && pv && b >= a.sg.s0) *reinterpret_cast<float4*>(a.u_save + (p - (long)a.sg.s0 * ho * wo) * E + 4 * q) = u4;   // (one sample per workgroup when s0 != 0: uniform)
     *reinterpret_cast<float4*>(ux + slot * LDU + 4 * q) = u4;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();     // the lanes of a pixel sit in one wave
@@ -590,7 +590,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E == 16 ? 4
     for (int k = 0; k < Q4; ++k) *reinterpret_cast<float4*>(stg + threadIdx.x * LDT + 4 * k) = make_float4(tt[4 * k], tt[4 * k + 1], tt[4 * k + 2], tt[4 * k + 3]);
     __syncthreads();
     USTAMP(6);
-    if (a.t_save) rows_out(a.t_save);
+    if (a.t_save && b >= a.sg.s0) rows_out(a.t_save - (long)a.sg.s0 * a.H * a.W * E);   // saved from sample s0 on, indexed from it
     gemm_half(0);
     USTAMP(7);
     __syncthreads();
@@ -646,6 +646,7 @@ __global__ __launch_bounds__(256) void k_tail(TailArgs a) {
         const long po = st * a.sg.pstride;
         a.w += po; a.b += po;
         a.z += st * (a.sg.zstride - (long)a.sg.Bs * C * a.HW);
+        if (a.out_last && st == a.sg.n - 1) a.out = a.out_last - (long)st * a.sg.Bs * C * a.HW;   // the last stage's samples land at out_last[0 ..]
     }
     float4 xv[E / 4];
     float zv[C];

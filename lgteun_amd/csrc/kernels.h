@@ -49,6 +49,8 @@ struct StageSel {
     int as_stride = 0;   // ... of attn_scales
     long ws_stride = 0;  // bytes between the stages' rows of wsplit
     int grid_cap = 0;    // test entry (lg_op_lgt_stages): upper bound of a persistent kernel's grid, 0 = none
+    int s0 = 0;          // the plane and pixel kernels: the launch's save pointers (FftArgs::amp / pha / sgn, DownArgs::u_save, UpFuseArgs::t_save) hold samples
+                         // s0 .. only, indexed from s0 -- the live stage riding behind the dead ones (k_fwd.hip: lgt_fwd).  0: every sample saves
     // dropout: the mask of stage s is keyed by mix_seed(seed, stage0 + s, blk) and counts its elements from the start of the stage's own tensor
     uint64_t seed = 0;
     int stage0 = 0, blk = 0;
@@ -149,6 +151,7 @@ struct TailArgs {
     const float* x;  // [B,H,W,E]
     const float* z;  // [B,C,H,W]
     float* out;      // [B,C,H,W]
+    float* out_last = nullptr;   // several stages: where the LAST stage's [Bs,C,H,W] goes instead of its part of `out` (the live stage: the caller's tensor); null: `out`
     const float *w, *b;
     int HW;
     long total;

@@ -74,6 +74,7 @@ struct NetBufs {
     float* attn_scales;  // [K][LG_NBLK][ATTN_SCALES_ROW] static operand scales of the local mixer's f16-pair products { s_y, s_w, s_q, s_k } (k_ffn_prep.hip), written once per forward call
     float* wsplit;       // [K][LG_NBLK][wsplit_slot] slots of pre-split (and pre-scaled) weight fragments of the e >= 32 FFN blocks (k_ffn_x32.hip), written once per forward call
     size_t set_off, set_bytes;  // the per-LGT activation set [set_off, set_off + set_bytes): train == 2 carves K of them back to back
+    size_t live_s0;             // first sample of the live stage's slot in the transient forward buffers (live_view): (K-1) B with stage_batch, else 0
     size_t wsplit_slot;         // floats of one wsplit slot: sized for the widest block (level 1: e = 8 C)
     size_t bytes;
     static size_t row(int st, int j) { return (size_t)st * LG_NBLK + j; }
@@ -104,6 +105,22 @@ static inline NetBufs stage_view(const NetBufs& nb, int i) {
     return v;
 }
 
+// NetBufs of the LIVE stage (and of every single-stage call): a plan with stage_batch carves the transient forward buffers for K slots of B samples,
+// dead stage i in slot i and the live stage ALWAYS in slot K-1 -- whether it rides behind the dead pass or runs alone, forward and backward alike.
+// Saved tensors are B-sized and stay where they are; any other plan: nb itself.
+static inline NetBufs live_view(const NetBufs& nb) {
+    NetBufs v = nb;
+    if (!nb.live_s0) return v;
+    for (int j = 0; j < LG_NBLK; ++j) {
+        BlockBufs& b = v.blk[j];
+        const size_t px = nb.live_s0 * b.h * b.w;   // pixels in front of the slot
+        b.xin += px * b.e; b.xmid += px * b.e; b.xout += px * b.e; b.g += px * (b.e / 2); b.o2 += px * (b.e / 2);
+    }
+    v.x0 = v.blk[0].xin;
+    v.live_s0 = 0;   // (a view of a view is itself)
+    return v;
+}
+
 // train: 0 = inference, 1 = training (one saved activation set: only the last stage's LGT is live),
 // 2 = chained training (LG_FLAG_CHAINED: every stage's LGT is live and keeps its own set)
 static inline void carve(const lg_plan* plan, int B, int train, void* base, NetBufs& nb) {
@@ -111,9 +128,12 @@ static inline void carve(const lg_plan* plan, int B, int train, void* base, NetB
     Carver cv{reinterpret_cast<char*>(base), 0};
     const size_t P0 = (size_t)c.H * c.W, P1 = P0 / 4, E = 4 * (size_t)c.C;
     // A plan whose dead stages run as one pass (lg_plan::stage_batch: K-1 >= 2 of them) carves the TRANSIENT forward buffers -- what a non-saving
-    // LGT forward writes -- for S = K-1 stages of B samples: stage s's part follows stage s-1's, so a kernel sees a plain batch of S B samples.  The live
-    // stage uses the first B samples' worth.  Saved tensors, the data steps' buffers and every other plan (K = 2 among them) are unchanged.
-    const size_t BT = (size_t)B * ((plan->stage_batch && train != 2) ? c.K - 1 : 1);
+    // LGT forward writes -- for K slots of B samples: stage s's part follows stage s-1's, so a kernel sees a plain batch of up to K B samples.  The live
+    // stage owns slot K-1 on every path (live_view), the dead stages slots 0 .. K-2; deadout holds the K-1 dead outputs.  Saved tensors, the data steps'
+    // buffers and every other plan (K = 2 among them) are unchanged.
+    const bool slots = plan->stage_batch && train != 2;
+    const size_t BT = (size_t)B * (slots ? c.K : 1);
+    nb.live_s0 = slots ? (size_t)B * (c.K - 1) : 0;
     for (int i = 0; i <= c.K; ++i) nb.Z[i] = cv.take(B * c.C * P0);
     for (int i = 0; i < c.K; ++i) {
         nb.t1[i] = cv.take(B * c.C * P1);
@@ -127,7 +147,7 @@ static inline void carve(const lg_plan* plan, int B, int train, void* base, NetB
     nb.attn_scales = cv.take(rows * ATTN_SCALES_ROW);
     nb.wsplit_slot = ffn_wsplit_bytes((int)(2 * E)) / sizeof(float);
     nb.wsplit = cv.take(rows * nb.wsplit_slot);
-    nb.deadout = cv.take(BT * c.C * P0);
+    nb.deadout = cv.take((slots ? nb.live_s0 : (size_t)B) * c.C * P0);
     nb.X[0] = nb.Z[0];
     for (int i = 1; i < c.K; ++i) nb.X[i] = (train == 2) ? cv.take(B * c.C * P0) : nb.deadout;
     float* shared_h2 = nullptr;

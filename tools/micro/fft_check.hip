@@ -5,12 +5,13 @@
 #include "../../lgteun_amd/csrc/k_fft.hip"
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <cmath>
 #include <vector>
 #include <cstdarg>
 void lg_set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); fputc('\n', stderr); }
 void lg_prof_begin(int, hipStream_t) {}
-void lg_prof_end(int, hipStream_t) {}
+void lg_prof_end(int, hipStream_t, int) {}
 int launch_reduce_job(const ReduceJob&, hipStream_t) { return 0; }
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s:%d %s\n", __FILE__, __LINE__, hipGetErrorString(e_)); exit(1); } } while (0)
 static uint64_t rs = 0x1234567ull;
@@ -57,7 +58,51 @@ static void edit_accuracy() {
            hw[0] / 1000.0, hw[6] / 1000.0, hw[1] / 1000.0, hw[4] / 1000.0, hw[2] / 1000.0, hw[5] / 1000.0, hw[3] / 1000.0);
 }
 
+// `fft_check rounds [reps=200]`: k_fftmix_r at n = 128, ch = 8 with 256 / 512 / 768 / 1 024 planes -- how a launch fills the chip's rounds (two 512-thread
+// workgroups per CU).  Per count: nothing saved, everything saved, only the LAST 256 planes saved (StageSel::s0: the live stage riding behind the dead
+// ones); the 512-thread instance, and at 256 planes the 1 024-thread one a launch of that size gets from launch_fftmix.  Times are the mean of `reps`
+// back-to-back launches between two events, in microseconds.
+static int rounds_probe(int reps) {
+    const int n = 128, ch = 8, maxp = 1024, live = 256;
+    const size_t N = (size_t)maxp * n * n, NB = (size_t)live * n * (n / 2 + 1), NBall = (size_t)maxp * n * (n / 2 + 1);
+    std::vector<float> g(N), par(4 * ch);
+    for (auto& v : g) v = (float)nrand();
+    for (int c = 0; c < ch; ++c) { par[c] = (float)(1 + 0.1 * nrand()); par[ch + c] = (float)(0.05 * nrand()); par[2 * ch + c] = (float)(1 + 0.1 * nrand()); par[3 * ch + c] = (float)(0.05 * nrand()); }
+    float *dg = dev(g), *dp = dev(par), *o, *amp, *pha, *sgn;
+    CK(hipMalloc(&o, N * 4)); CK(hipMalloc(&sgn, N * 4)); CK(hipMalloc(&amp, NBall * 4)); CK(hipMalloc(&pha, NBall * 4));
+    (void)NB;
+    hipStream_t s; CK(hipStreamCreate(&s));
+    hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    FftArgs a; a.g = dg; a.o = o; a.amp = nullptr; a.pha = nullptr; a.sgn = nullptr; a.scratch = nullptr; a.ampw = dp; a.ampb = dp + ch; a.phaw = dp + 2 * ch; a.phab = dp + 3 * ch;
+    a.planes = 256; a.ch = ch; a.n = n; a.h = n; a.w = n; a.full = 0;
+    if (launch_fftmix(a, s)) return 1;      // twiddles and the LDS attribute of both instances
+    CK(hipStreamSynchronize(s));
+    const size_t ldsr = ((size_t)n * FFT_HP(n) + n / 2) * sizeof(float2);
+    auto run = [&](int planes, int nth, int save) {   // save 0: none, 1: all, 2: the last `live` planes
+        FftArgs b = a;
+        b.planes = planes;
+        if (save) { b.amp = amp; b.pha = pha; b.sgn = sgn; }
+        if (save == 2) { b.sg.n = planes / live; b.sg.Bs = live / ch; b.sg.s0 = (planes - live) / ch; }   // (pstride 0: every "stage" reads the same parameters)
+        auto go = [&]() { if (nth == 1024) k_fftmix_r<7, 1024><<<planes, 1024, ldsr, s>>>(b); else k_fftmix_r<7, 512><<<planes, 512, ldsr, s>>>(b); };
+        for (int r = 0; r < 5; ++r) go();
+        CK(hipStreamSynchronize(s));
+        CK(hipEventRecord(e0, s));
+        for (int r = 0; r < reps; ++r) go();
+        CK(hipEventRecord(e1, s)); CK(hipEventSynchronize(e1));
+        CK(hipGetLastError());
+        float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+        return ms * 1e3 / reps;
+    };
+    printf("k_fftmix_r n=128 ch=8, us per launch (mean of %d): planes threads none all last256\n", reps);
+    for (int rep = 0; rep < 2; ++rep) {   // twice: the spread of the box
+        printf("rounds  256 1024 %7.2f %7.2f       -\n", run(256, 1024, 0), run(256, 1024, 1));
+        for (int planes = 256; planes <= maxp; planes += 256) printf("rounds %4d  512 %7.2f %7.2f %7.2f\n", planes, run(planes, 512, 0), run(planes, 512, 1), run(planes, 512, planes > 256 ? 2 : 1));
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc > 1 && !strcmp(argv[1], "rounds")) return rounds_probe(argc > 2 ? atoi(argv[2]) : 200);
     if (argc > 1 && atoi(argv[1]) == 0) { edit_accuracy(); return 0; }
     const int n = argc > 1 ? atoi(argv[1]) : 128, planes = argc > 2 ? atoi(argv[2]) : 256, reps = argc > 3 ? atoi(argv[3]) : 50;
     const int ch = 8;
