@@ -339,7 +339,7 @@ int lg_op_lgt_bwd(const lg_plan* plan, const float* params, float* grads, int32_
 #define LG_IQA_Q_BLOCK 8       /* Q: box window of the reduced-resolution pass        metrics.Q_BLOCK */
 #define LG_IQA_RATIO 4         /* ERGAS ratio = PAN / MS resolution                   metrics.ERGAS_RATIO */
 #define LG_IQA_QNR_BLOCK 32    /* Q window of D_lambda / D_s                          metrics.QNR_BLOCK */
-#define LG_IQA_MTF_TAPS 41     /* PAN low-pass (MTF-matched Gaussian) taps            metrics.MTF_TAPS */
+#define LG_IQA_MTF_TAPS 41     /* PAN low-pass (window-method MTF filter) taps        metrics.MTF_TAPS */
 #define LG_IQA_MTF_GAIN 0.15   /*   and its gain at the MS Nyquist frequency          metrics.MTF_GAIN_PAN */
 #define LG_IQA_MAX_BANDS 16
 /* bytes of workspace a call on [B, C, H, W] images needs (no_ref = 0: lg_iqa_ref, 1: lg_iqa_no_ref); 0 for a shape the indices
@@ -351,6 +351,10 @@ int lg_iqa_ref(const float* pred, const float* gt, double* out, int32_t B, int32
 /* metrics.no_ref_evaluate of every image: pred [B,C,H,W], pan [B,1,H,W], ms [B,C,H/4,W/4] fp32 -> out [B,3] fp64 = D_lambda, D_s, QNR */
 int lg_iqa_no_ref(const float* pred, const float* pan, const float* ms, double* out, int32_t B, int32_t C, int32_t H, int32_t W,
                   float scale, void* workspace, size_t workspace_bytes, void* stream);
+/* the LG_IQA_MTF_TAPS taps of lg_iqa_no_ref's PAN low-pass into the HOST array out41: metrics.mtf_taps(LG_IQA_MTF_GAIN), the row sums of
+ * the reference's 41 x 41 window-method filter (Gaussian frequency samples, inverse DFT, radial Kaiser window with beta 0.5, normalised).
+ * Host code: computed once, no device call.  An addition without an ABI bump, like lg_wavelet_taps. */
+int lg_iqa_mtf_taps(double* out41);
 
 /* ---- the extended indices (metrics.ref_evaluate_ext / no_ref_evaluate_ext; kernels in lgteun_amd/csrc/k_iqa_ext.hip; definitions:
  * DESIGN.md 3.8.1) ----  The conventions of the block above: every element times `scale` in fp32 first, fp64 after that, per-workgroup partials

@@ -150,6 +150,7 @@ SIGNATURES = {
     'lg_iqa_ref': (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_size_t, c_void_p]),
     'lg_iqa_no_ref': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_size_t,
                                 c_void_p]),
+    'lg_iqa_mtf_taps': (c_int32, [c_void_p]),
     'lg_iqa_ext_workspace_bytes': (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     'lg_iqa_ref_ext': (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_size_t, c_void_p]),
     'lg_iqa_q2n': (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_size_t, c_void_p]),

@@ -251,7 +251,7 @@ class Base_model:
     def _test(self, iter_id, save=False, ref=True):
         """evaluation (base_model.py:267-352).  ref=True: reduced-resolution set, PSNR / SSIM / Q / SAM / ERGAS against the target,
         `<metric>_mean` / `<metric>_std` lists in self.eval_results like the reference.  ref=False: the full-resolution set, no target:
-        D_lambda / D_s / QNR from the fused image, the PAN and the MS input (lgteun_amd/metrics.py: parity-unpinned).  Inputs are always normalised; arrays are brought back
+        D_lambda / D_s / QNR from the fused image, the PAN and the MS input (lgteun_amd/metrics.py: pinned to the reference's values).  Inputs are always normalised; arrays are brought back
         to digital numbers before the metrics / the TIFF writer only with cfg.norm_input (base_model.py:296,311-316).
         cfg.eval_metrics: 'host' (default) scores every image with the float64 numpy functions of metrics.py; 'device' scores every batch
         on the GPU (device_metrics.py: the same definitions in fp64 HIP kernels), keeps the rows there and copies them to the host once,

@@ -308,9 +308,56 @@ Taps box_taps(int n) {   // np.full(block, 1.0 / block)
     for (int k = 0; k < n; ++k) t.w[k] = 1.0 / n;
     return t;
 }
-Taps mtf_taps() {        // metrics.mtf_taps(MTF_GAIN_PAN, ERGAS_RATIO)
-    const double f = 1.0 / (2.0 * LG_IQA_RATIO);
-    return gaussian_taps(LG_IQA_MTF_TAPS, sqrt(-log(LG_IQA_MTF_GAIN) / (2.0 * (M_PI * M_PI) * (f * f))));
+double bessel_i0(double x) {   // metrics._bessel_i0: the power series, 24 terms
+    double term = 1.0, total = 1.0;
+    for (int k = 1; k < 25; ++k) {
+        term = term * (0.5 * x / k) * (0.5 * x / k);
+        total = total + term;
+    }
+    return total;
+}
+// metrics.mtf_taps(MTF_GAIN_PAN, ERGAS_RATIO): the row sums of the window-method filter (metrics.mtf_window_filter, operation for operation
+// up to the order of the sums).  Computed on the first call; a function-local static is initialised once, whatever thread asks first.
+Taps mtf_taps_compute() {
+    constexpr int N = LG_IQA_MTF_TAPS, HALF = N / 2;
+    static_assert(N % 2 == 1 && N >= 3, "the window method is written for an odd number of taps");
+    const double alpha = sqrt(((N - 1) * (0.5 / LG_IQA_RATIO)) * ((N - 1) * (0.5 / LG_IQA_RATIO)) / (-2.0 * log(LG_IQA_MTF_GAIN)));
+    double resp[N], g[N], kaiser[HALF + 1], t[N];
+    for (int k = 0; k < N; ++k) {
+        const double q = (k - HALF) / alpha;
+        resp[k] = exp(-0.5 * (q * q));
+        t[k] = (double)(k - HALF) / (N - 1.0);
+    }
+    for (int m = 0; m < N; ++m) {     // the centred inverse DFT of the (even, real) response
+        double s = 0.0;
+        for (int k = 0; k < N; ++k) s += resp[k] * cos(2.0 * M_PI * (k - HALF) * (m - HALF) / N);
+        g[m] = s / N;
+    }
+    const double i0_beta = bessel_i0(0.5);
+    for (int j = 0; j <= HALF; ++j) kaiser[j] = bessel_i0(0.5 * sqrt(1.0 - ((double)j / HALF) * ((double)j / HALF))) / i0_beta;
+    double rows[N], total = 0.0;
+    for (int i = 0; i < N; ++i) {
+        rows[i] = 0.0;
+        for (int j = 0; j < N; ++j) {
+            const double radius = sqrt(t[i] * t[i] + t[j] * t[j]);
+            double win = 0.0;
+            if (!(radius > t[N - 1])) {   // the radial Kaiser window, read between its samples; zero beyond the radius 1/2
+                const double x = radius * (N - 1.0);
+                int lo = (int)x;
+                if (lo > HALF - 1) lo = HALF - 1;
+                win = kaiser[lo] + (x - lo) * (kaiser[lo + 1] - kaiser[lo]);
+            }
+            rows[i] += (g[i] * g[j]) * win;
+        }
+        total += rows[i];
+    }
+    Taps out{};
+    for (int i = 0; i < N; ++i) out.w[i] = rows[i] / total;
+    return out;
+}
+const Taps& mtf_taps() {
+    static const Taps taps = mtf_taps_compute();
+    return taps;
 }
 
 struct WinGrid {
@@ -379,6 +426,13 @@ bool iqa_check_buffers(bool ptrs_ok, float scale, void* workspace, size_t worksp
 extern "C" size_t lg_iqa_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t no_ref) {
     IqaGeom g;
     return iqa_geom(B, C, H, W, no_ref, g) ? g.bytes : 0;
+}
+
+extern "C" int lg_iqa_mtf_taps(double* out41) {
+    if (!out41) { lg_set_error("iqa_mtf_taps: out41 is NULL"); return -1; }
+    const Taps& t = mtf_taps();
+    for (int k = 0; k < LG_IQA_MTF_TAPS; ++k) out41[k] = t.w[k];
+    return 0;
 }
 
 extern "C" int lg_iqa_ref(const float* pred, const float* gt, double* out, int32_t B, int32_t C, int32_t H, int32_t W, float scale,

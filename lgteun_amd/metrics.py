@@ -12,15 +12,17 @@ value 2047.5 (11-bit data); a multi-band SSIM / Q is the plain mean of the per-b
 (sigma 1.5) and Q an 8 x 8 box, and both average only over windows that lie fully inside the image; SAM is in radians with
 the cosine clipped to [0, 1]; ERGAS uses ratio 4.
 
-Parity status: PSNR / SAM / ERGAS are pinned by values the reference itself produced (tests/golden/net_*.npz `metrics`).
-SSIM / Q call cv2.filter2D in the reference and cv2 is not installed in the build image, so they are PARITY-UNPINNED: they
-are checked against brute-force evaluations of the definitions above only (tests/test_metrics_cpu.py).  Restricting the
-average to fully covered windows makes the result independent of any border rule.
-The no-reference family of the full-resolution pass (`no_ref_evaluate`: D_lambda, D_s, QNR; Alparone et al., 2008) is written from the
-published definitions as well: Q on 32 x 32 windows, the PAN image brought to MS resolution by a Gaussian low-pass whose gain at the MS
-Nyquist frequency is the sensor's MTF value, then decimation.  The reference builds that filter with a 2-D window method on top of cv2 /
-scipy.ndimage and a per-satellite table; this is the separable Gaussian of the same MTF gain, so the family is PARITY-UNPINNED like SSIM / Q
-and is checked against brute-force evaluations of its definitions only.
+Parity status: every index of `ref_evaluate` and `no_ref_evaluate`, and `cc`, is pinned by values the reference itself produced
+(tests/golden/net_*.npz `metrics` for PSNR / SAM / ERGAS; tests/golden/parity_metrics_*.npz for all of them, tests/test_reference_parity_cpu.py).
+SSIM / Q call cv2.filter2D in the reference and cv2 is not installed, so the reference ran over three stand-ins for the OpenCV calls it
+makes (tools/_ref_import.py).  Restricting the average to fully covered windows makes the result independent of any border
+rule, and the generator proves that the reference never reads one.  Host against reference: PSNR, SAM, ERGAS, CC equal; SSIM 4e-15, Q 2e-14,
+D_lambda 1.4e-13 relative.
+The no-reference family of the full-resolution pass (`no_ref_evaluate`: D_lambda, D_s, QNR; Alparone et al., 2008): Q on 32 x 32 windows,
+the PAN image brought to MS resolution by the reference's MTF low-pass (`mtf_window_filter`: the window method with the QuickBird PAN gain
+0.15), replicated edges, then every fourth sample.  The low-pass is applied as its separable factor (`mtf_taps`, the row sums of the 2-D
+filter); the rank-1 residual that drops is all that separates D_s and QNR from the reference's values: at most 8.9e-7 and 1.1e-8 relative
+(gates 3.6e-6 and 4.5e-8).
 Device versions for whole batches (fp64 HIP kernels, tested against these functions): lgteun_amd/device_metrics.py.
 The extended set (`ref_evaluate_ext`, `no_ref_evaluate_ext`) adds the columns of the pan-sharpening literature: Q2n (Garzelli & Nencini, 2009:
 Q4 for four bands, Q8 for eight), SCC (Zhou et al., 1998, on Sobel magnitudes), CC (the reference's `scc`, metrics.py:58: Pearson's r per band)
@@ -136,14 +138,56 @@ def ref_evaluate(pred, gt):
 # ---------------------------------------------------------------------------------------------------------------------
 # no-reference indices of the full-resolution pass (reference models/base/metrics.py:290-408, `no_ref_evaluate`)
 # ---------------------------------------------------------------------------------------------------------------------
-def mtf_taps(gain_at_nyquist, ratio=ERGAS_RATIO, n=MTF_TAPS):
-    """n samples of the Gaussian low-pass whose FREQUENCY response has the value `gain_at_nyquist` at the Nyquist frequency of the
-    coarser grid (1 / (2 ratio) cycles per fine pixel): H(f) = exp(-2 pi^2 s^2 f^2) for a spatial Gaussian of standard deviation s"""
+KAISER_BETA = 0.5
+
+
+def _bessel_i0(x):
+    """the modified Bessel function I0 by its power series sum_k ((x/2)^k / k!)^2: for the x <= 0.5 of the window 12 terms reach the last bit"""
+    term, total = 1.0, 1.0
+    for k in range(1, 25):
+        term = term * (0.5 * x / k) * (0.5 * x / k)
+        total = total + term
+    return total
+
+
+def mtf_window_filter(gain_at_nyquist, ratio=ERGAS_RATIO, n=MTF_TAPS):
+    """the n x n MTF-matched low-pass of the reference's no-reference indices (its `GNyq2win`, models/base/metrics.py:223-235), designed
+    by the window method:
+      1. the wanted frequency response is a Gaussian sampled on the n x n DFT grid, G(k) = exp(-k^2 / (2 a^2)) for k = -(n-1)/2 .. (n-1)/2 in
+         each direction, with a chosen so that a continuous Gaussian would have the value `gain_at_nyquist` at the coarse grid's Nyquist
+         frequency, k = (n - 1) / (2 ratio);
+      2. its inverse DFT, centred: separable, g(m) = 1/n sum_k G(k) cos(2 pi k m / n) per direction;
+      3. times a radial Kaiser window (beta 0.5): the 1-D window of n samples over [-1/2, 1/2], read at the radius sqrt(i^2 + j^2) / (n - 1)
+         by linear interpolation between its samples, zero beyond the radius 1/2;
+      4. normalised to sum 1.
+    The radial window is what keeps the filter from being exactly separable (second singular value 5.3e-6 of the first at gain 0.15)."""
     if not 0.0 < gain_at_nyquist < 1.0:
         raise ValueError('the MTF gain at Nyquist lies in (0, 1)')
-    f_nyq = 1.0 / (2.0 * ratio)
-    sigma = np.sqrt(-np.log(gain_at_nyquist) / (2.0 * np.pi ** 2 * f_nyq ** 2))
-    return gaussian_taps(n, sigma)
+    if n < 3 or n % 2 == 0:
+        raise ValueError('the window method is written for an odd number of taps >= 3')
+    half = n // 2
+    k = np.arange(-half, half + 1, dtype=np.float64)
+    alpha = np.sqrt(((n - 1) * (0.5 / ratio)) ** 2 / (-2.0 * np.log(gain_at_nyquist)))
+    resp = np.exp(-0.5 * (k / alpha) ** 2)
+    g = np.array([np.sum(resp * np.cos(2.0 * np.pi * k * m / n)) for m in k]) / n
+    i0_beta = _bessel_i0(KAISER_BETA)
+    kaiser = np.array([_bessel_i0(KAISER_BETA * np.sqrt(1.0 - (j / half) ** 2)) / i0_beta for j in range(half + 1)])   # by distance from the centre
+    t = k / (n - 1.0)
+    radius = np.sqrt(t[:, None] * t[:, None] + t[None, :] * t[None, :])
+    x = radius * (n - 1.0)
+    lo = np.minimum(x.astype(np.int64), half - 1)
+    window = kaiser[lo] + (x - lo) * (kaiser[lo + 1] - kaiser[lo])
+    window[radius > t[-1]] = 0.0
+    h = np.outer(g, g) * window
+    return h / h.sum()
+
+
+def mtf_taps(gain_at_nyquist, ratio=ERGAS_RATIO, n=MTF_TAPS):
+    """the separable factor of `mtf_window_filter`: the row sums of the 2-D filter, n taps that sum to 1.  outer(taps, taps) is the 2-D
+    filter up to its rank-1 residual (DESIGN.md 3.8 has the measured figures).  The design puts `gain_at_nyquist` on DFT bin
+    (n - 1) / (2 ratio) of an n-point grid, that is at (n - 1) / (2 ratio n) cycles per fine pixel, not at the coarse grid's Nyquist frequency
+    1 / (2 ratio) itself: for 0.15, ratio 4 and 41 taps the gain is 0.1506 at 5/41 and 0.1368 at 1/8.  That is the reference's filter, kept as it is"""
+    return mtf_window_filter(gain_at_nyquist, ratio, n).sum(axis=1)
 
 
 def mtf_degrade(img, gain_at_nyquist=MTF_GAIN_PAN, ratio=ERGAS_RATIO):

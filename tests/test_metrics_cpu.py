@@ -1,6 +1,6 @@
 """CPU: the reference-based image-quality indices (lgteun_amd/metrics.py) against brute-force evaluations of their
-definitions.  cv2 is absent here, so SSIM / Q cannot be pinned against the reference code itself (parity unpinned);
-PSNR / SAM / ERGAS are pinned by the reference's own values (tests/golden, test_oracle_golden.py, test_boundary_cpu.py)."""
+definitions.  The same functions against values the reference itself produced: tests/test_reference_parity_cpu.py (all of them),
+test_oracle_golden.py and test_boundary_cpu.py (PSNR / SAM / ERGAS)."""
 import numpy as np
 import pytest
 
@@ -75,8 +75,7 @@ def test_psnr_sam_ergas_properties():
 
 def test_no_reference_indices_follow_their_definitions():
     """D_lambda / D_s / QNR (Alparone et al. 2008; reference models/base/metrics.py:290-408 `no_ref_evaluate`), written from the
-    definitions: checked against brute-force evaluations on small images (parity-unpinned like SSIM / Q: the reference's MTF filter
-    needs cv2 / scipy.ndimage tables that are not in the image)"""
+    definitions: checked against brute-force evaluations on small images (against the reference's values: test_reference_parity_cpu.py)"""
     from lgteun_amd import metrics as mtc
     rng = np.random.default_rng(7)
     H = 64
@@ -106,11 +105,14 @@ def test_no_reference_indices_follow_their_definitions():
     # a fusion whose inter-band and band-to-PAN similarities are those of the inputs has no distortion: QNR = 1
     same = np.repeat(np.repeat(ms, 4, axis=0), 4, axis=1)
     assert mtc.d_lambda(same, same, 8) == 0.0
-    # the MTF low-pass: unit DC gain, the prescribed gain at the coarse grid's Nyquist frequency, decimation by the ratio
+    # the MTF low-pass (the reference's window-method filter, tests/test_reference_parity_cpu.py): unit DC gain, the prescribed gain where
+    # the design puts it -- DFT bin (n - 1) / (2 ratio) = 5 of the 41-point grid, 5/41 cycles per pixel -- and decimation by the ratio.  At the
+    # coarse grid's Nyquist frequency itself, 1/8, that filter's gain is 0.1368 (the Gaussian this test once held to 0.15 there is the
+    # negative control of the parity test)
     taps = mtc.mtf_taps(0.15, 4)
-    f = 1.0 / 8.0
-    gain = abs(np.sum(taps * np.exp(-2j * np.pi * f * (np.arange(taps.size) - taps.size // 2))))
-    assert abs(taps.sum() - 1) < 1e-12 and abs(gain - 0.15) < 2e-3
+    gain = lambda f: abs(np.sum(taps * np.exp(-2j * np.pi * f * (np.arange(taps.size) - taps.size // 2))))      # noqa: E731
+    assert abs(taps.sum() - 1) < 1e-12 and abs(gain(5.0 / 41.0) - 0.15) < 2e-3 and abs(gain(1.0 / 8.0) - 0.1368) < 2e-3
+    assert np.allclose(taps, taps[::-1], rtol=0, atol=1e-16) and taps.argmax() == 20
     assert mtc.mtf_degrade(np.full((32, 48), 5.0)).shape == (8, 12) and np.allclose(mtc.mtf_degrade(np.full((32, 48), 5.0)), 5.0)
     with pytest.raises(ValueError):
         mtc.d_s(fused, ms, pan[:-4])

@@ -4,6 +4,8 @@ arrays); weights are regenerated everywhere from oracle/detweights.py.  Run:
 
     python tools/gen_goldens.py            # writes tests/golden/
     python tools/gen_goldens.py --check    # additionally checks oracle/lgteun_oracle.py against them
+    python tools/gen_goldens.py --only-parity   # only parity_*.npz: the reference's metrics, classical baselines and QNR loss over the
+                                                # OpenCV stand-ins of tools/_ref_import.py, with the border self-check (seconds)
 
 Never runs on the GPU box (there is no /root/reference there).
 """
@@ -257,8 +259,115 @@ def train3_l2_adamw(R):
     print('train3 l2 + AdamW losses', logged, 'lrs', lrs)
 
 
+CLASSICAL_CASES = [(4, 4, 4, 1), (4, 5, 7, 2), (8, 12, 8, 3), (4, 20, 12, 1)]     # (C, h, w, B); the seed rule is tests/test_gpu_classical.py's
+QNR_LOSS_CASES = [(3, 4, 32, 32, 31), (3, 8, 32, 32, 32)]                          # (B, C, H, W, seed) of qnr_helpers.make_inputs
+MAX_CLIP_SHARE = 0.02
+
+
+def parity(manifest):
+    """tests/golden/parity_*.npz: what the reference's OWN metrics (ref_evaluate, scc, no_ref_evaluate, mtf_resize, GNyq2win), classical
+    baselines (upsample_interp23, SFIM_, GSA_) and QNRLoss give, run over the three OpenCV stand-ins of tools/_ref_import.py.  Every
+    fixture that passes through filter2D is produced under two border rules and must come out bitwise equal: the reference crops the border
+    rows away, so the rule is never read.  Wavelet is left out: pywt is not installed and a Haar stand-in would be our reading again."""
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import classical_ref as cr
+    import parity_inputs as pin
+    import qnr_helpers as qh
+    import _ref_import as ri
+    P = ri.import_reference_parity()
+    mtc, cv2 = P.mtc, P.cv2
+    sizes = {}
+
+    def save(name, out):
+        path = os.path.join(GOLD, name + '.npz')
+        np.savez_compressed(path, **out)
+        sizes[name] = os.path.getsize(path)
+        assert sizes[name] < (1 << 20), (name, sizes[name])
+
+    def both_borders(fn):
+        res = []
+        for border in ri.BORDERS:
+            cv2.border = border
+            before = cv2.calls['filter2D']
+            res.append(np.asarray(fn(), np.float64))
+            assert cv2.calls['filter2D'] > before, 'the border check did not pass through filter2D'
+        cv2.border = 'mirror'
+        assert res[0].tobytes() == res[1].tobytes(), ('a border rule was read', res)
+        return res[0]
+
+    # ---------------------------------------------------------------- classical baselines, per sample, float64 tensors
+    for C, h, w, B in CLASSICAL_CASES:
+        ms, pan = cr.make_batch(B, C, h, w, seed=C * 100 + h)
+        out = dict(ms=ms, pan=pan)
+        res = {m: [] for m in ('interp23', 'sfim', 'gsa')}
+        for b in range(B):
+            hs, pn = t(ms[b:b + 1], torch.float64), t(pan[b:b + 1], torch.float64)
+            res['interp23'].append(P.upsample_interp23(ms[b].astype(np.float64).transpose(1, 2, 0), 4).transpose(2, 0, 1))
+            res['sfim'].append(P.SFIM_(hs, pn)[0].transpose(2, 0, 1))
+            res['gsa'].append(P.GSA_(hs, pn)[0].transpose(2, 0, 1))
+        for m, v in res.items():
+            out[m] = np.ascontiguousarray(np.stack(v))
+            assert out[m].dtype == np.float64 and out[m].shape == (B, C, 4 * h, 4 * w)
+            share = float(((out[m] <= 0) | (out[m] >= 1)).mean())
+            assert share <= MAX_CLIP_SHARE, (m, C, h, w, B, share)
+            print(f'classical C={C} h={h} w={w} B={B} {m}: clip share {share:.4f}, vs tests/classical_ref.py '
+                  f'{np.abs(out[m] - np.stack([getattr(cr, m)(*((ms[b],) if m == "interp23" else (ms[b], pan[b, 0]))) for b in range(B)])).max():.2e}')
+        save(f'parity_classical_c{C}_{h}x{w}_b{B}', out)
+
+    # ---------------------------------------------------------------- reference-based indices
+    out = {}
+    for name, (pred, gt) in pin.ref_cases().items():
+        pin.store_input(out, name + '/pred', pred, None)
+        pin.store_input(out, name + '/gt', gt, None)
+        out[name + '/ref_evaluate'] = both_borders(lambda: mtc.ref_evaluate(pred, gt))
+        with np.errstate(invalid='ignore', divide='ignore'):
+            out[name + '/scc'] = np.array(mtc.scc(gt, pred))
+        print(name, 'ref_evaluate', out[name + '/ref_evaluate'], 'scc', out[name + '/scc'])
+    save('parity_metrics_ref', out)
+
+    # ---------------------------------------------------------------- no-reference indices (square only: mtf_resize hands cv2.resize
+    # dsize as (rows, cols))
+    out = {'gnyq2win_0.15': mtc.GNyq2win(0.15, 4, N=41)}
+    for name, (C, H, seed) in pin.NOREF_CASES.items():
+        pred, pan, ms = pin.noref_case(C, H, seed)
+        pin.store_input(out, name + '/pred', pred, seed)
+        pin.store_input(out, name + '/pan', pan, seed)
+        pin.store_input(out, name + '/ms', ms, seed)
+        out[name + '/no_ref_evaluate'] = both_borders(lambda: mtc.no_ref_evaluate(pred, pan, ms))
+        out[name + '/mtf_resize_pan'] = mtc.mtf_resize(pan[..., None])
+        assert out[name + '/mtf_resize_pan'].shape == (H // 4, H // 4) and np.isfinite(out[name + '/no_ref_evaluate']).all()
+        print(name, 'no_ref_evaluate', out[name + '/no_ref_evaluate'], flush=True)
+    save('parity_metrics_noref', out)
+
+    # ---------------------------------------------------------------- QNR loss and its gradient, float64
+    out = {}
+    for B, C, H, W, seed in QNR_LOSS_CASES:
+        o, pan, ms, pan_l = qh.make_inputs(B, C, H, W, seed)
+        x = o.double().requires_grad_(True)
+        loss = P.QNRLoss(None, None)(pan.double(), ms.double(), x, pan_l.double())
+        loss.backward()
+        name = f'c{C}'
+        out.update({name + '/out': o.numpy(), name + '/pan': pan.numpy(), name + '/ms': ms.numpy(), name + '/pan_l': pan_l.numpy(),
+                    name + '/loss': loss.detach().numpy().reshape(()), name + '/grad': x.grad.numpy()})
+        assert out[name + '/grad'].dtype == np.float64
+        print(f'QNRLoss C={C}: loss {float(loss):.12f}, max |grad| {np.abs(out[name + "/grad"]).max():.3e}')
+    save('parity_qnr_loss', out)
+
+    manifest['reference_parity'] = dict(
+        files=sizes, standins=ri.STANDINS, shims=ri.SHIMS, borders={k: {a: repr(b) for a, b in v.items()} for k, v in ri.BORDERS.items()},
+        border_check='every ref_evaluate / no_ref_evaluate row was computed under both border rules and came out bitwise equal',
+        standin_calls=dict(cv2.calls), classical_cases=CLASSICAL_CASES, qnr_loss_cases=QNR_LOSS_CASES, max_clip_share=MAX_CLIP_SHARE,
+        scipy_own_calls='ndimage.correlate (mode wrap / nearest), signal.convolve2d, np.kaiser, np.interp, np.fft are the reference\'s own '
+                        'calls of libraries that are installed; they are not stand-ins',
+        not_included='Wavelet: pywt is not installed, and a Haar stand-in would be a restatement of ours, not the reference\'s output; '
+                     'no-reference fixtures are square only: mtf_resize passes dsize as (rows, cols), so the reference is wrong on rectangles')
+    print('parity fixtures:', sizes, 'total', sum(sizes.values()))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--only-parity', action='store_true', help='write only the reference-parity fixtures (parity_*.npz: the reference\'s metrics, '
+                                                               'classical baselines and QNR loss over the OpenCV stand-ins); the manifest is merged')
     ap.add_argument('--only-train3-l2-adamw', action='store_true', help='write only train3_l2_adamw_c4_k2_p32.npz (three reference '
                                                                         'iterations with loss type l2 and AdamW); no manifest entry')
     ap.add_argument('--only-r7', action='store_true', help='write only the round-7 fixtures (a reference checkpoint, its config\'s values)')
@@ -272,6 +381,13 @@ def main():
     os.makedirs(GOLD, exist_ok=True)
     if args.only_r5:
         round5()
+        return
+    if args.only_parity:
+        with open(os.path.join(GOLD, 'manifest.json')) as f:
+            manifest = json.load(f)
+        parity(manifest)
+        with open(os.path.join(GOLD, 'manifest.json'), 'w') as f:
+            json.dump(manifest, f, indent=1, sort_keys=True)
         return
     torch.manual_seed(0)
     torch.set_num_threads(8)
@@ -424,6 +540,7 @@ def main():
     print('train3 losses', logged, 'lrs', lrs)
 
     round2(R, manifest)
+    parity(manifest)
     with open(os.path.join(GOLD, 'manifest.json'), 'w') as f:
         json.dump(manifest, f, indent=1, sort_keys=True)
     round3(R, manifest)
