@@ -331,8 +331,8 @@ int lg_op_lgt_bwd(const lg_plan* plan, const float* params, float* grads, int32_
  * Same definitions as the host functions; only the order of summation differs.  Every input element is first multiplied by `scale` in
  * fp32 (2^bit_depth - 0.5 for normalised inputs, as data_denormalize does; 1 for digital numbers), then widened to fp64.  Reductions
  * are per-workgroup partials in the workspace plus a fixed-order pass (no atomics): repeated calls give the same bits, and row b of a
- * batch equals the row of image b scored alone.  Shapes: 2 <= C <= LG_IQA_MAX_BANDS; H, W >= LG_IQA_SSIM_TAPS (one SSIM window); the
- * no-reference indices also need H, W >= LG_IQA_QNR_BLOCK and multiples of LG_IQA_RATIO. */
+ * batch equals the row of image b scored alone.  Shapes: 1 <= B <= 65535; 2 <= C <= LG_IQA_MAX_BANDS; LG_IQA_SSIM_TAPS (one SSIM window) <= H, W
+ * <= 8192; the no-reference indices also need H, W >= LG_IQA_QNR_BLOCK and multiples of LG_IQA_RATIO. */
 #define LG_IQA_PEAK 2047.5     /* dynamic range of PSNR / SSIM (11-bit data)          metrics.PEAK */
 #define LG_IQA_SSIM_TAPS 11    /* SSIM: Gaussian window taps                          metrics.SSIM_TAPS */
 #define LG_IQA_SSIM_SIGMA 1.5  /*       and its sigma                                 metrics.SSIM_SIGMA */
@@ -395,7 +395,7 @@ int lg_iqa_q2n(const float* gt, const float* fused, double* out, int32_t B, int3
  * partials in the workspace and fixed-order finishing passes, no atomics, so the same call gives the same bits every time; the number of
  * workgroups per sample depends on H and W only, so a sample's q row has the same bits alone and inside any batch.
  * Both calls validate their arguments before any HIP call and name the offending one in lg_last_error: C is 4 or 8; H and W are multiples
- * of 4, at least 8; 1 <= B <= 65535; float tensors 16-byte aligned, doubles and the workspace 8-byte aligned.  All indexing is 64-bit.  They
+ * of 4 in 8 .. 65536; 1 <= B <= 65535; float tensors 16-byte aligned, doubles and the workspace 8-byte aligned.  All indexing is 64-bit.  They
  * allocate nothing and synchronise nothing. */
 /* bytes of workspace both calls need for [B, C, H, W]; 0 for shapes the calls reject */
 size_t lg_qnr_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
@@ -422,7 +422,7 @@ int lg_qnr_grad(const float* out, const float* pan, const double* table, float* 
  * batch, so the shares of the ranks add up and no collective is needed.  All arithmetic is fp64, rounded to fp32 once per dout element;
  * per-workgroup fp64 partials in the workspace and a one-workgroup finish in a fixed order, no atomics: the same call gives the same bits, and a
  * sample's dout has the same bits alone and inside any batch.  Arguments are validated before any HIP call and the offending one is named
- * in lg_last_error: C is 4 or 8; W is a multiple of 4; 1 <= B <= 65535; float tensors 16-byte aligned, the workspace 8-byte aligned.  All
+ * in lg_last_error: C is 4 or 8; W is a multiple of 4; H, W <= 65536; 1 <= B <= 65535; float tensors 16-byte aligned, the workspace 8-byte aligned.  All
  * indexing is 64-bit.  The calls allocate nothing and synchronise nothing. */
 /* bytes of workspace either call needs for [B, C, H, W]; 0 for C not in {4, 8} or W not a multiple of 4.  lg_ssim_loss also needs H and W
  * of at least 11 (one window) and says so itself: for smaller images the size returned is lg_sam_loss's. */
@@ -453,7 +453,8 @@ int lg_pyr_down2(const void* pan, float* pan_l, int64_t planes, int32_t H, int32
  * clamped into 0 .. N-1), converted to fp32, flipped as the device word *flips says (bit 0: up-down, bit 1: left-right; flips == NULL: no
  * flip) and scaled: n_div (0, 1 or 2) correctly rounded fp32 divisions by `divisor`, then one fp32 multiplication by post_scale unless it
  * is 1.  Outputs are contiguous fp32 NCHW: o_pan [B,1,H,W], o_lr [B,C,h,w], o_mul [B,C,H,W] (NULL together with mul), o_pan_l [B,1,h,w].
- * All arrays 16-byte aligned.  1 <= B <= 65535, 1 <= C <= 16. */
+ * All arrays 16-byte aligned.  1 <= B <= 65535, 1 <= C <= 16, h, w <= 8192, 1 <= N < 2^31; an item's 16-byte chunks are counted in 32 bits:
+ * (C + 1) (H ceil(W / 4) + h w) < 2^31. */
 int lg_batch_assemble(const void* pan, const void* lr, const void* mul, const float* pan_l, int64_t N, const int32_t* idx, int64_t idx_offset,
                       const uint32_t* flips, float* o_pan, float* o_lr, float* o_mul, float* o_pan_l, int32_t B, int32_t C, int32_t H, int32_t W,
                       int32_t h, int32_t w, int32_t dtype, float divisor, int32_t n_div, float post_scale, void* stream);

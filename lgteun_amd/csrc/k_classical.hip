@@ -758,7 +758,7 @@ bool cl_geom(const char* who, int B, int C, int h, int w, int method, ClGeom& g)
     const int resident = CL_CUS * (CL_CU_LDS / (cl_moment_lds_doubles(C) * (int)sizeof(double) + CL_MAX_SUMS * (int)sizeof(int)));
     g.gx = g.tiles < resident ? g.tiles : resident;
     g.ns = method == LG_CLASSICAL_GSA ? (C + 2) * (C + 3) : 2 * C + 2;
-    const size_t sz[2] = {(size_t)B * g.gx * g.ns * sizeof(double), (size_t)B * (3 * C + 1) * sizeof(double)};
+    const size_t sz[2] = {ws_region(B, (size_t)g.gx * g.ns * sizeof(double)), ws_region(B, (size_t)(3 * C + 1) * sizeof(double))};
     g.bytes = ws_layout(2, sz, g.off);
     return true;
 }
@@ -810,8 +810,9 @@ bool mg_geom(const char* who, int B, int C, int h, int w, int n_filters, int mod
         return false;
     }
     g.gx2 = g.cl.tiles < MG_RESIDENT ? g.cl.tiles : MG_RESIDENT;
-    const size_t sz[4] = {(size_t)B * g.cl.gx * g.cl.ns * sizeof(double), (size_t)B * (3 * C + 1) * sizeof(double),
-                          (size_t)B * n_filters * h * w * sizeof(double), mode == LG_MTFGLP_CBD ? (size_t)B * g.gx2 * 4 * C * sizeof(double) : 0};
+    const size_t sz[4] = {ws_region(B, (size_t)g.cl.gx * g.cl.ns * sizeof(double)), ws_region(B, (size_t)(3 * C + 1) * sizeof(double)),
+                          ws_region(B, (size_t)n_filters * h * w * sizeof(double)),
+                          mode == LG_MTFGLP_CBD ? ws_region(B, (size_t)g.gx2 * 4 * C * sizeof(double)) : 0};
     g.bytes = ws_layout(4, sz, g.off);
     return true;
 }

@@ -334,7 +334,7 @@ bool ext_geom(const char* who, int B, int C, int H, int W, ExtGeom& g) {
     g.tiles_x = (W - 2 + SCC_TX - 1) / SCC_TX;
     g.ntile = g.tiles_x * ((H - 2 + SCC_TY - 1) / SCC_TY);
     const size_t d = sizeof(double);
-    const size_t sz[3] = {(size_t)B * g.nblk * d, (size_t)B * C * g.ntile * 3 * d, (size_t)B * C * d};
+    const size_t sz[3] = {ws_region(B, (size_t)g.nblk * d), ws_region(B, (size_t)C * g.ntile * 3 * d), ws_region(B, (size_t)C * d)};
     g.bytes = ws_layout(3, sz, g.off);
     return true;
 }

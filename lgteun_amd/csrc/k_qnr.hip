@@ -307,7 +307,8 @@ bool qnr_geom(const char* who, int B, int C, int H, int W, QnrGeom& g) {
     g.gm = (int)(m < QNR_MAX_GM ? m : QNR_MAX_GM);
     g.np = qnr_np(C);
     g.m = qnr_m(C);
-    const size_t sz[3] = {(size_t)B * g.gf * g.m * sizeof(double), (size_t)B * g.gm * g.m * sizeof(double), (size_t)B * 7 * g.np * sizeof(double)};
+    const size_t sz[3] = {ws_region(B, (size_t)g.gf * g.m * sizeof(double)), ws_region(B, (size_t)g.gm * g.m * sizeof(double)),
+                          ws_region(B, (size_t)7 * g.np * sizeof(double))};
     g.bytes = ws_layout(3, sz, g.off);
     return true;
 }

@@ -47,6 +47,12 @@ __device__ __forceinline__ double partials_sum(const double* __restrict__ part, 
 
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
+// bytes of a workspace region that holds one slice of `per` bytes for each of B samples: every sample's share is reserved in whole 128-byte units
+// (the kernels keep indexing with the slice's own size; the rest stays unused), so the region of two samples is whole 256-byte lines already and a
+// workspace of B samples is never below B / 2 times the workspace of two -- ws_layout's rounding of a region's end no longer weighs more at a small
+// batch than at a large one
+inline size_t ws_region(size_t B, size_t per) { return B * ((per + 127) & ~(size_t)127); }
+
 // n workspace regions of sz[i] bytes, each starting 256-byte aligned: their offsets -> off[i], the total is returned
 inline size_t ws_layout(int n, const size_t* sz, size_t* off) {
     size_t bytes = 0;
