@@ -63,9 +63,9 @@ static void lg_plan_stage_batch(lg_plan* p) {
     for (int st = 1; ok && st < c.K; ++st)
         for (int slot = 0; slot < L_NSLOT; ++slot)
             if (p->lgt(st, slot) - p->lgt(0, slot) != st * p->stage_stride) { ok = false; break; }
-    ok = ok && r.ffn[0].fwd[0] == FFN_FWD_XR && r.ffn[1].fwd[0] == FFN_FWD_X32 && r.mix[0].fwd == ATTN_FWD_M && r.mix[1].fwd == ATTN_FWD_M && !r.fft_full;
+    ok = ok && r.ffn[0].fwd[0] == FFN_FWD_XR && r.ffn[1].fwd[0] == FFN_FWD_X32 && r.mix[0].fwd == ATTN_FWD_M && r.mix[1].fwd == ATTN_FWD_M;
     ok = ok && (r.ffn[1].scales || r.ffn[1].hbf);                        // (k_ffn_x32's three-piece arithmetic has no multi-stage instance)
-    ok = ok && !fft_is_generic(c.H, c.W) && c.H <= 128;                 // both levels' planes in LDS
+    ok = ok && r.fft[0].path == FFT_PATH_LDS_R && r.fft[1].path == FFT_PATH_LDS_R;   // the one FFT kernel that takes several stages
     ok = ok && ((c.H / 16) * (c.W / 16)) % 4 == 0;                      // level 1: whole window quads per sample (k_attn_m); the pixel kernels' tiles follow
     p->stage_batch = ok;
 }
@@ -232,8 +232,8 @@ extern "C" int lg_op_block(const lg_plan* plan, const float* params, int32_t sta
         FftArgs f;
         f.g = bb.g; f.o = y; f.amp = nullptr; f.pha = nullptr; f.sgn = nullptr; f.scratch = nb.fft_scratch;
         f.ampw = k.p(B_AMPW); f.ampb = k.p(B_AMPB); f.phaw = k.p(B_PHAW); f.phab = k.p(B_PHAB);
-        f.ch = bb.e / 2; f.planes = B * f.ch; f.n = bb.h; f.h = bb.h; f.w = bb.w; f.full = plan->route.fft_full;
-        return launch_fftmix(f, s);
+        f.ch = bb.e / 2; f.planes = B * f.ch;
+        return launch_fftmix(plan->fft(bb.e), f, s);
     }
     if ((rc = prep_stages(plan, params, stage, stage + 1, nb, s))) return rc;   // the block's rows: pos_emb table and static operand scales (mixer), operand scales and weight fragments (FFN)
     if (which == 1) {

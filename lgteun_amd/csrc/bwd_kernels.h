@@ -342,16 +342,14 @@ struct FftBwdArgs {
     const float* amp;  // [planes,n,n/2+1]
     const float* pha;
     float* dg;         // [planes,n,n]
-    float* scratch;    // n > 128 only: half-spectrum scratch
+    float* scratch;    // three-launch paths only: half-spectrum scratch (FftRoute::scratch_floats per plane)
     const float *ampw, *ampb, *phaw, *phab;
     float *d_ampw, *d_ampb, *d_phaw, *d_phab;
-    float* part;       // scratch: per-workgroup partial sums of the four parameter gradients, fft_bwd_part_floats()
-    int planes, ch, n;
-    int h, w;          // plane size (when non-zero; n = side of a square plane otherwise)
-    int full = 0;      // 1: the complex-row in-LDS kernels (A/B variant LG_VAR_FFT_FULL); 0: the real-input kernels (k_fftmix_r / k_fftmix_bwd_r)
+    float* part;       // scratch: per-workgroup partial sums of the four parameter gradients, FftRoute::bwd_part_floats(planes)
+    int planes, ch;
+    int unread_[4] = {0, 0, 0, 0};   // as in FftArgs: read by nothing, they keep the kernels' argument layout
 };
-size_t fft_bwd_part_floats(int planes, int h, int w);
-int launch_fftmix_bwd(const FftBwdArgs& a, hipStream_t s);
+int launch_fftmix_bwd(const FftRoute& r, const FftBwdArgs& a, hipStream_t s);
 
 struct AttnBwdArgs {
     const float* x;     // [P,e] block input

@@ -35,6 +35,7 @@ struct lg_plan {
     LgRoute route;   // which kernels run, what they save and read: resolved once by lg_resolve_route (route.hip), read everywhere else
     const FfnRoute& ffn(int e) const { return route.ffn[e != 4 * cfg.C]; }
     const MixerRoute& mixer(int e) const { return route.mix[e != 4 * cfg.C]; }
+    const FftRoute& fft(int e) const { return route.fft[e != 4 * cfg.C]; }
     int64_t* off;  // host copy of offsets
     int64_t stage_stride = 0;   // floats from a tensor of LGT s to the same tensor of LGT s + 1 (the K LGTs have identical shapes)
     bool stage_batch = false;   // the K-1 dead-stage LGT forwards of a faithful step can run as ONE pass over (K-1) B samples (api.hip: lg_plan_stage_batch)

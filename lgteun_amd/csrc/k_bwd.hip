@@ -192,8 +192,8 @@ static int fft_bwd_call(const Blk& k, const float* do2, float* dg, int B, hipStr
     fa.do2 = do2; fa.sgn = fb.sgn; fa.amp = fb.amp; fa.pha = fb.pha; fa.dg = dg; fa.scratch = k.fft_scratch;
     fa.ampw = k.p(B_AMPW); fa.ampb = k.p(B_AMPB); fa.phaw = k.p(B_PHAW); fa.phab = k.p(B_PHAB);
     fa.d_ampw = k.g(B_AMPW); fa.d_ampb = k.g(B_AMPB); fa.d_phaw = k.g(B_PHAW); fa.d_phab = k.g(B_PHAB);
-    fa.ch = hc; fa.planes = B * hc; fa.n = fb.h; fa.h = fb.h; fa.w = fb.w; fa.part = part; fa.full = k.pl->route.fft_full;
-    return launch_fftmix_bwd(fa, s);
+    fa.ch = hc; fa.planes = B * hc; fa.part = part;
+    return launch_fftmix_bwd(k.pl->fft(fb.e), fa, s);
 }
 
 // mixer half-block backward: tmp (grad wrt the mid activation) -> dx_out (grad wrt block input)
@@ -213,7 +213,7 @@ static int mixer_half_bwd(const Blk& k, BwdBufs& bb, const float* tmp, float* dx
         if (!pk.slab) return -3;
         pk.d_projb = k.g(B_PROJB); pk.HW = fb.h * fb.w; pk.total = Pn; pk.seed = mix_seed(seed, k.st, k.j);
         RC(launch_proj_o2_bwd_k(e, pk, s));
-        float* fpart = bb.rq.take(fft_bwd_part_floats(B * hc, fb.h, fb.w));
+        float* fpart = bb.rq.take(k.pl->fft(e).bwd_part_floats((size_t)B * hc));
         if (!fpart) return -3;
         RC(fft_bwd_call(k, bb.do2, bb.dg, B, s, fpart));
         AttnBwdFArgs af;
@@ -231,7 +231,7 @@ static int mixer_half_bwd(const Blk& k, BwdBufs& bb, const float* tmp, float* dx
     po.HW = fb.h * fb.w; po.total = Pn; po.dropout = drop; po.seed = mix_seed(seed, k.st, k.j);
     RC(launch_proj_o2_bwd(e, po, s));
     const float* dym = drop ? bb.dym : tmp;
-    float* fpart = bb.rq.take(fft_bwd_part_floats(B * hc, fb.h, fb.w));
+    float* fpart = bb.rq.take(k.pl->fft(e).bwd_part_floats((size_t)B * hc));
     if (!fpart) return -3;
     RC(fft_bwd_call(k, bb.do2, bb.dg, B, s, fpart));
     AttnBwdArgs at;

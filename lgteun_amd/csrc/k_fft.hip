@@ -10,6 +10,7 @@
 // angle() takes the same branch as pocketfft's r2c (+pi for negative DC).  fp32 throughout.
 #include <math.h>
 #include <string.h>
+#include <type_traits>
 
 #include "kernels.h"
 #include "bwd_kernels.h"
@@ -771,53 +772,6 @@ __global__ void k_fft_rows_inv(const float2* __restrict__ S, float* __restrict__
     }
 }
 
-size_t fft_scratch_floats(int planes, int n) { return n > 128 ? (size_t)planes * n * (n / 2 + 1) * 2 : 0; }
-bool fft_is_generic(int h, int w);
-// half-spectrum scratch of the paths that go through HBM (split: square powers of two above 128; generic: everything else)
-size_t fft_scratch_floats_hw(int planes, int h, int w) {
-    return (fft_is_generic(h, w) || h > 128) ? (size_t)planes * h * (w / 2 + 1) * 2 : 0;
-}
-
-template <int LG>
-static int launch_fft_split_t(const FftArgs* fa, const FftBwdArgs* ba, float2* S, int planes, hipStream_t s) {
-    constexpr int n = 1 << LG;
-    static DeviceOnce attr_once;
-    if (int rc = lds_attr_once(attr_once, "fft split", 160 * 1024 - 1024, k_fft_rows_fwd<LG>, k_fft_cols<false, LG>, k_fft_cols<true, LG>, k_fft_rows_inv<LG>)) return rc;
-    const int R = FFT_ROWS_PER_WG(n), CB = FFT_COLS_PER_WG(n), half = n / 2;
-    const size_t lds_rows = ((size_t)R * (n + 1) + half) * sizeof(float2);
-    const size_t lds_cols = ((size_t)n * CB + half) * sizeof(float2) + 64 * sizeof(float);
-    dim3 grows(planes, n / R), gcols(planes, (half + 1 + CB - 1) / CB);
-    if (fa) {
-        k_fft_rows_fwd<LG><<<grows, FFT_ROWS_NT, lds_rows, s>>>(fa->g, nullptr, S, 1);
-        LG_CHECK_LAUNCH();
-        FftBwdArgs dummy;
-        memset(&dummy, 0, sizeof(dummy));
-        k_fft_cols<false, LG><<<gcols, 512, lds_cols, s>>>(*fa, dummy, S);
-        LG_CHECK_LAUNCH();
-        k_fft_rows_inv<LG><<<grows, FFT_ROWS_NT, lds_rows, s>>>(S, fa->o, fa->sgn, 1);
-        LG_CHECK_LAUNCH();
-    } else {
-        k_fft_rows_fwd<LG><<<grows, FFT_ROWS_NT, lds_rows, s>>>(ba->do2, ba->sgn, S, 0);
-        LG_CHECK_LAUNCH();
-        FftArgs dummy;
-        memset(&dummy, 0, sizeof(dummy));
-        k_fft_cols<true, LG><<<gcols, 512, lds_cols, s>>>(dummy, *ba, S);
-        LG_CHECK_LAUNCH();
-        k_fft_rows_inv<LG><<<grows, FFT_ROWS_NT, lds_rows, s>>>(S, ba->dg, nullptr, 0);
-        LG_CHECK_LAUNCH();
-    }
-    return 0;
-}
-static int launch_fft_split(const FftArgs* fa, const FftBwdArgs* ba, hipStream_t s) {
-    const int n = fa ? fa->n : ba->n, planes = fa ? fa->planes : ba->planes;
-    float2* S = reinterpret_cast<float2*>(fa ? fa->scratch : ba->scratch);
-    if (!S) { lg_set_error("fftmix: plane size %d needs the split path but no scratch buffer was given", n); return -2; }
-    if (n == 256) return launch_fft_split_t<8>(fa, ba, S, planes, s);
-    if (n == 512) return launch_fft_split_t<9>(fa, ba, S, planes, s);
-    lg_set_error("fftmix: the split path exists for planes of 256 and 512 (got %d)", n);
-    return -2;
-}
-
 
 // ================================================================================================
 // Generic path: any plane h x w (sides multiples of 8 up to 1024: 400 x 400 full-resolution scenes, rectangular
@@ -842,7 +796,6 @@ static GDft gdft_plan(int n) {
     return d;
 }
 static size_t gdft_lds_bytes(const GDft& d) { return ((size_t)d.L * d.M + d.M + d.n + d.M / 2) * sizeof(float2) + 64 * sizeof(float); }
-bool fft_is_generic(int h, int w) { return !(h == w && (h & (h - 1)) == 0 && h >= 8 && h <= 512); }
 
 struct GLds { float2 *lines, *bf, *wch, *tw; float* red; };
 __device__ __forceinline__ GLds gdft_carve(float2* smem, const GDft& d) {
@@ -1027,84 +980,6 @@ __global__ void k_gfft_rows_inv(const float2* __restrict__ S, float* __restrict_
             out[o] = v;
         }
     }
-}
-
-static int fft_generic_col_groups(int h, int w) { const GDft dh = gdft_plan(h); return (w / 2 + 1 + dh.L - 1) / dh.L; }
-
-static int launch_fft_generic(const FftArgs* fa, const FftBwdArgs* ba, int h, int w, hipStream_t s) {
-    const int planes = fa ? fa->planes : ba->planes;
-    float2* S = reinterpret_cast<float2*>(fa ? fa->scratch : ba->scratch);
-    if (!S) { lg_set_error("fftmix: plane %dx%d needs the generic path but no scratch buffer was given", h, w); return -2; }
-    if (h < 8 || w < 8 || h > 1024 || w > 1024 || (h & 7) || (w & 7)) {
-        lg_set_error("fftmix: plane %dx%d unsupported (sides: multiples of 8, 8..1024)", h, w);
-        return -2;
-    }
-    static DeviceOnce attr_once;
-    if (int rc = lds_attr_once(attr_once, "fft generic", 160 * 1024 - 1024, k_gfft_rows_fwd, k_gfft_cols<false>, k_gfft_cols<true>, k_gfft_rows_inv)) return rc;
-    const GDft dw = gdft_plan(w), dh = gdft_plan(h);
-    const size_t lds_r = gdft_lds_bytes(dw), lds_c = gdft_lds_bytes(dh);
-    dim3 grows(planes, (h + dw.L - 1) / dw.L), gcols(planes, fft_generic_col_groups(h, w));
-    if (fa) {
-        k_gfft_rows_fwd<<<grows, 1024, lds_r, s>>>(fa->g, nullptr, S, h, w, dw, 1);
-        LG_CHECK_LAUNCH();
-        FftBwdArgs dummy;
-        memset(&dummy, 0, sizeof(dummy));
-        k_gfft_cols<false><<<gcols, 1024, lds_c, s>>>(*fa, dummy, S, h, w, dh);
-        LG_CHECK_LAUNCH();
-        k_gfft_rows_inv<<<grows, 1024, lds_r, s>>>(S, fa->o, fa->sgn, h, w, dw, 1);
-        LG_CHECK_LAUNCH();
-    } else {
-        k_gfft_rows_fwd<<<grows, 1024, lds_r, s>>>(ba->do2, ba->sgn, S, h, w, dw, 0);
-        LG_CHECK_LAUNCH();
-        FftArgs dummy;
-        memset(&dummy, 0, sizeof(dummy));
-        k_gfft_cols<true><<<gcols, 1024, lds_c, s>>>(dummy, *ba, S, h, w, dh);
-        LG_CHECK_LAUNCH();
-        k_gfft_rows_inv<<<grows, 1024, lds_r, s>>>(S, ba->dg, nullptr, h, w, dw, 0);
-        LG_CHECK_LAUNCH();
-    }
-    return 0;
-}
-
-int launch_fftmix(const FftArgs& a, hipStream_t s) {
-    ProfScope prof__(LG_K_FFT, s, a.sg.n);
-    const int ph = a.h ? a.h : a.n, pw = a.w ? a.w : a.n;
-    if (a.sg.n > 1 && (a.full || fft_is_generic(ph, pw) || ph > 128)) { lg_set_error("fftmix: only the real-input in-LDS kernel takes several stages in one launch"); return -2; }
-    if (fft_is_generic(ph, pw)) return launch_fft_generic(&a, nullptr, ph, pw, s);
-    int n = ph, lg = 0;
-    while ((1 << lg) < n) ++lg;
-    if (n > 128) return launch_fft_split(&a, nullptr, s);
-    if (!a.full) {
-        if (int rc = fft_const_twiddles()) return rc;
-        static DeviceOnce attr_r;
-        if (int rc = lds_attr_once(attr_r, "fftmix", 80 * 1024 - 512, k_fftmix_r<7, 1024>, k_fftmix_r<7, 512>)) return rc;
-        const size_t ldsr = ((size_t)n * FFT_HP(n) + n / 2) * sizeof(float2);
-        switch (lg) {
-            case 3: k_fftmix_r<3, fftr_threads(3)><<<a.planes, fftr_threads(3), ldsr, s>>>(a); break;
-            case 4: k_fftmix_r<4, fftr_threads(4)><<<a.planes, fftr_threads(4), ldsr, s>>>(a); break;
-            case 5: k_fftmix_r<5, fftr_threads(5)><<<a.planes, fftr_threads(5), ldsr, s>>>(a); break;
-            case 6: k_fftmix_r<6, fftr_threads(6)><<<a.planes, fftr_threads(6), ldsr, s>>>(a); break;
-            default:
-                if (a.planes <= lg_num_cus()) k_fftmix_r<7, 1024><<<a.planes, 1024, ldsr, s>>>(a);
-                else k_fftmix_r<7, 512><<<a.planes, 512, ldsr, s>>>(a);
-                break;
-        }
-        LG_CHECK_LAUNCH();
-        return 0;
-    }
-    size_t lds = ((size_t)n * FFT_LD(n) + n / 2) * sizeof(float2);
-    static DeviceOnce attr_once;
-    if (int rc = lds_attr_once(attr_once, "fftmix", 160 * 1024 - 1024, k_fftmix<7>)) return rc;
-    int threads = fft_threads(lg);
-    switch (lg) {
-        case 3: k_fftmix<3><<<a.planes, threads, lds, s>>>(a); break;
-        case 4: k_fftmix<4><<<a.planes, threads, lds, s>>>(a); break;
-        case 5: k_fftmix<5><<<a.planes, threads, lds, s>>>(a); break;
-        case 6: k_fftmix<6><<<a.planes, threads, lds, s>>>(a); break;
-        default: k_fftmix<7><<<a.planes, threads, lds, s>>>(a); break;
-    }
-    LG_CHECK_LAUNCH();
-    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1294,66 +1169,169 @@ __global__ void __launch_bounds__(NTH, (LG >= 7 && NTH == 512) ? 4 : 1) k_fftmix
     }
 }
 
-static int fft_bwd_col_groups(int h, int w) {
-    if (fft_is_generic(h, w)) return fft_generic_col_groups(h, w);
-    return h > 128 ? (h / 2 + 1 + FFT_COLS_PER_WG(h) - 1) / FFT_COLS_PER_WG(h) : 1;
+
+// ================================================================================================
+// Launch, both directions.  Which of the four paths a plane takes, its column groups and its scratch are the level's FftRoute (route.h), resolved
+// once per plan by resolve_fft (route.hip): nothing below looks at the plane's size to choose a kernel.
+// ================================================================================================
+int fft_split_cols_per_wg(int n) { return FFT_COLS_PER_WG(n); }
+int fft_bluestein_lines_per_wg(int n) { return gdft_plan(n).L; }
+
+// f(std::integral_constant<int, LG>()) for the LG in LO .. HI that equals lg: the one place a run-time log2 n becomes a template argument
+template <int LO, int HI, class F>
+static int fft_with_lg(int lg, F&& f) {
+    if constexpr (LO > HI) {
+        lg_set_error("fftmix: no kernel instance for planes of %d", 1 << lg);
+        return -2;
+    } else {
+        return lg == LO ? f(std::integral_constant<int, LO>()) : fft_with_lg<LO + 1, HI>(lg, f);
+    }
 }
-size_t fft_bwd_part_floats(int planes, int h, int w) { return (size_t)planes * fft_bwd_col_groups(h, w) * 4; }
+
+template <class A> constexpr bool fft_is_bwd = std::is_same<A, FftBwdArgs>::value;   // A: FftArgs (forward) or FftBwdArgs
+
+// ---- in LDS: one launch per direction.  The four kernel families are named here and nowhere else on the host side
+template <bool REAL, int LG, int NTH, class A>
+static auto fft_lds_kernel() -> void (*)(A) {
+    if constexpr (REAL && fft_is_bwd<A>) return k_fftmix_bwd_r<LG, NTH>;
+    else if constexpr (REAL) return k_fftmix_r<LG, NTH>;
+    else if constexpr (fft_is_bwd<A>) return k_fftmix_bwd<LG>;
+    else return k_fftmix<LG>;
+}
+// real-input kernels at 128 x 128, forward and backward alike: 1 024 threads while every plane of the launch has a compute unit of its own, the
+// 512-thread instance (several workgroups per CU) beyond that.  The plane count belongs to the launch, not to the plan: decided here
+static bool fftr_128_narrow(int planes) { return planes > lg_num_cus(); }
+
+template <bool REAL, class A>
+static int launch_fft_lds(const FftRoute& r, const A& a, hipStream_t s) {
+    constexpr bool BWD = fft_is_bwd<A>;
+    static DeviceOnce attr_once;
+    if constexpr (REAL) {
+        if (int rc = fft_const_twiddles()) return rc;
+        if (int rc = lds_attr_once(attr_once, BWD ? "fftmix_bwd" : "fftmix", 80 * 1024 - 512, fft_lds_kernel<true, 7, 1024, A>(), fft_lds_kernel<true, 7, 512, A>())) return rc;
+    } else {
+        if (int rc = lds_attr_once(attr_once, BWD ? "fftmix_bwd" : "fftmix", 160 * 1024 - 1024, fft_lds_kernel<false, 7, 1024, A>())) return rc;
+    }
+    return fft_with_lg<3, 7>(r.lg, [&](auto LG) {
+        constexpr int lg = decltype(LG)::value, n = 1 << lg, NTH = REAL ? fftr_threads(lg) : fft_threads(lg);
+        const size_t lds = ((size_t)n * (REAL ? FFT_HP(n) : FFT_LD(n)) + n / 2) * sizeof(float2) + (BWD ? 64 * sizeof(float) : 0);
+        if constexpr (REAL && lg == 7) {
+            if (fftr_128_narrow(a.planes)) {
+                fft_lds_kernel<true, 7, 512, A>()<<<a.planes, 512, lds, s>>>(a);
+                LG_CHECK_LAUNCH();
+                return 0;
+            }
+        }
+        fft_lds_kernel<REAL, lg, NTH, A>()<<<a.planes, NTH, lds, s>>>(a);
+        LG_CHECK_LAUNCH();
+        return 0;
+    });
+}
+
+// ---- through HBM: rows, columns + edit, rows.  One direction as these three launches see it: the row kernels' operands, and the argument pair of the
+// column kernels -- k_fft_cols<BWD, LG> / k_gfft_cols<BWD> read the struct of their direction only, the other one is zeroed here
+struct FftDir {
+    FftArgs fa;
+    FftBwdArgs ba;
+    const float *in, *mul;   // first row pass: input and optional elementwise factor (backward: the saved sign of the forward output)
+    float *out, *sgn;        // last row pass
+    float2* S;               // half spectrum [planes][h][w/2 + 1]
+    int planes, fwd;         // fwd: the row kernels' force_real / absout
+};
+static FftDir fft_dir(const FftArgs& a) {
+    FftDir d;
+    memset(&d.ba, 0, sizeof(d.ba));
+    d.fa = a; d.in = a.g; d.mul = nullptr; d.out = a.o; d.sgn = a.sgn; d.S = reinterpret_cast<float2*>(a.scratch); d.planes = a.planes; d.fwd = 1;
+    return d;
+}
+static FftDir fft_dir(const FftBwdArgs& a) {
+    FftDir d;
+    memset(&d.fa, 0, sizeof(d.fa));
+    d.ba = a; d.in = a.do2; d.mul = a.sgn; d.out = a.dg; d.sgn = nullptr; d.S = reinterpret_cast<float2*>(a.scratch); d.planes = a.planes; d.fwd = 0;
+    return d;
+}
+
+template <bool BWD, int LG>
+static int launch_fft_split(const FftRoute& r, const FftDir& d, hipStream_t s) {
+    constexpr int n = 1 << LG;
+    static DeviceOnce attr_once;
+    if (int rc = lds_attr_once(attr_once, "fft split", 160 * 1024 - 1024, k_fft_rows_fwd<LG>, k_fft_cols<BWD, LG>, k_fft_rows_inv<LG>)) return rc;
+    const int R = FFT_ROWS_PER_WG(n), CB = FFT_COLS_PER_WG(n), half = n / 2;
+    const size_t lds_rows = ((size_t)R * (n + 1) + half) * sizeof(float2);
+    const size_t lds_cols = ((size_t)n * CB + half) * sizeof(float2) + 64 * sizeof(float);
+    dim3 grows(d.planes, n / R), gcols(d.planes, r.col_groups);
+    k_fft_rows_fwd<LG><<<grows, FFT_ROWS_NT, lds_rows, s>>>(d.in, d.mul, d.S, d.fwd);
+    LG_CHECK_LAUNCH();
+    k_fft_cols<BWD, LG><<<gcols, 512, lds_cols, s>>>(d.fa, d.ba, d.S);
+    LG_CHECK_LAUNCH();
+    k_fft_rows_inv<LG><<<grows, FFT_ROWS_NT, lds_rows, s>>>(d.S, d.out, d.sgn, d.fwd);
+    LG_CHECK_LAUNCH();
+    return 0;
+}
+
+template <bool BWD>
+static int launch_fft_bluestein(const FftRoute& r, const FftDir& d, hipStream_t s) {
+    const int h = r.h, w = r.w;
+    if (h < 8 || w < 8 || h > 1024 || w > 1024 || (h & 7) || (w & 7)) {
+        lg_set_error("fftmix: plane %dx%d unsupported (sides: multiples of 8, 8..1024)", h, w);
+        return -2;
+    }
+    static DeviceOnce attr_once;
+    if (int rc = lds_attr_once(attr_once, "fft generic", 160 * 1024 - 1024, k_gfft_rows_fwd, k_gfft_cols<BWD>, k_gfft_rows_inv)) return rc;
+    const GDft dw = gdft_plan(w), dh = gdft_plan(h);
+    const size_t lds_r = gdft_lds_bytes(dw), lds_c = gdft_lds_bytes(dh);
+    dim3 grows(d.planes, (h + dw.L - 1) / dw.L), gcols(d.planes, r.col_groups);
+    k_gfft_rows_fwd<<<grows, 1024, lds_r, s>>>(d.in, d.mul, d.S, h, w, dw, d.fwd);
+    LG_CHECK_LAUNCH();
+    k_gfft_cols<BWD><<<gcols, 1024, lds_c, s>>>(d.fa, d.ba, d.S, h, w, dh);
+    LG_CHECK_LAUNCH();
+    k_gfft_rows_inv<<<grows, 1024, lds_r, s>>>(d.S, d.out, d.sgn, h, w, dw, d.fwd);
+    LG_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- THE cascade: one dispatch on the route's path, forward (A = FftArgs) and backward (A = FftBwdArgs)
+template <class A>
+static int launch_fft_path(const FftRoute& r, const A& a, hipStream_t s) {
+    constexpr bool BWD = fft_is_bwd<A>;
+    switch (r.path) {
+        case FFT_PATH_LDS_R: return launch_fft_lds<true>(r, a, s);
+        case FFT_PATH_LDS_C: return launch_fft_lds<false>(r, a, s);
+        case FFT_PATH_SPLIT:
+            if (!a.scratch) { lg_set_error("fftmix: plane size %d needs the split path but no scratch buffer was given", r.h); return -2; }
+            return fft_with_lg<8, 9>(r.lg, [&](auto LG) { return launch_fft_split<BWD, decltype(LG)::value>(r, fft_dir(a), s); });
+        case FFT_PATH_BLUESTEIN:
+            if (!a.scratch) { lg_set_error("fftmix: plane %dx%d needs the generic path but no scratch buffer was given", r.h, r.w); return -2; }
+            return launch_fft_bluestein<BWD>(r, fft_dir(a), s);
+    }
+    lg_set_error("fftmix: unknown path %d", (int)r.path);
+    return -2;
+}
+
+int launch_fftmix(const FftRoute& r, const FftArgs& a, hipStream_t s) {
+    ProfScope prof__(LG_K_FFT, s, a.sg.n);
+    if (a.sg.n > 1 && r.path != FFT_PATH_LDS_R) { lg_set_error("fftmix: only the real-input in-LDS kernel takes several stages in one launch"); return -2; }
+    return launch_fft_path(r, a, s);
+}
+
 // the four per-channel parameter gradients from the partial rows [sample][column group][channel][4]
-static int fft_bwd_reduce(const FftBwdArgs& a, hipStream_t s) {
+static int fft_bwd_reduce(const FftRoute& r, const FftBwdArgs& a, hipStream_t s) {
     float* dst[4] = {a.d_ampw, a.d_ampb, a.d_phaw, a.d_phab};
     for (int k = 0; k < 4; ++k) {
         ReduceJob j;
         j.slab = a.part + k; j.dst = dst[k]; j.dst2 = nullptr;
-        j.nslices = (long)(a.planes / a.ch) * fft_bwd_col_groups(a.h ? a.h : a.n, a.w ? a.w : a.n); j.slice_stride = (long)a.ch * 4;
+        j.nslices = (long)(a.planes / a.ch) * r.col_groups; j.slice_stride = (long)a.ch * 4;
         j.rows = a.ch; j.cols = 1; j.row_stride = 4; j.ld = 1; j.rows_valid = a.ch; j.cols_valid = 1;
         int rc = launch_reduce_job(j, s);
         if (rc) return rc;
     }
     return 0;
 }
-static int launch_fftmix_bwd_kernels(const FftBwdArgs& a, hipStream_t s);
-int launch_fftmix_bwd(const FftBwdArgs& a, hipStream_t s) {
+int launch_fftmix_bwd(const FftRoute& r, const FftBwdArgs& a, hipStream_t s) {
     if (!a.part) { lg_set_error("fftmix_bwd: partial-sum scratch missing"); return -2; }
-    int rc = launch_fftmix_bwd_kernels(a, s);
-    return rc ? rc : fft_bwd_reduce(a, s);
-}
-static int launch_fftmix_bwd_kernels(const FftBwdArgs& a, hipStream_t s) {
-    ProfScope prof__(LG_K_FFT_BWD, s);
-    const int ph = a.h ? a.h : a.n, pw = a.w ? a.w : a.n;
-    if (fft_is_generic(ph, pw)) return launch_fft_generic(nullptr, &a, ph, pw, s);
-    int n = ph, lg = 0;
-    while ((1 << lg) < n) ++lg;
-    if (n > 128) return launch_fft_split(nullptr, &a, s);
-    if (!a.full) {
-        if (int rc = fft_const_twiddles()) return rc;
-        static DeviceOnce attr_r;
-        if (int rc = lds_attr_once(attr_r, "fftmix_bwd", 80 * 1024 - 512, k_fftmix_bwd_r<7, 1024>, k_fftmix_bwd_r<7, 512>)) return rc;
-        const size_t ldsr = ((size_t)n * FFT_HP(n) + n / 2) * sizeof(float2) + 64 * sizeof(float);
-        switch (lg) {
-            case 3: k_fftmix_bwd_r<3, fftr_threads(3)><<<a.planes, fftr_threads(3), ldsr, s>>>(a); break;
-            case 4: k_fftmix_bwd_r<4, fftr_threads(4)><<<a.planes, fftr_threads(4), ldsr, s>>>(a); break;
-            case 5: k_fftmix_bwd_r<5, fftr_threads(5)><<<a.planes, fftr_threads(5), ldsr, s>>>(a); break;
-            case 6: k_fftmix_bwd_r<6, fftr_threads(6)><<<a.planes, fftr_threads(6), ldsr, s>>>(a); break;
-            default:
-                if (a.planes <= lg_num_cus()) k_fftmix_bwd_r<7, 1024><<<a.planes, 1024, ldsr, s>>>(a);
-                else k_fftmix_bwd_r<7, 512><<<a.planes, 512, ldsr, s>>>(a);
-                break;
-        }
-        LG_CHECK_LAUNCH();
-        return 0;
+    {
+        ProfScope prof__(LG_K_FFT_BWD, s);   // (the mixer's own launches, not the reduce behind them)
+        if (int rc = launch_fft_path(r, a, s)) return rc;
     }
-    size_t lds = ((size_t)n * FFT_LD(n) + n / 2) * sizeof(float2) + 64 * sizeof(float);
-    static DeviceOnce attr_once;
-    if (int rc = lds_attr_once(attr_once, "fftmix_bwd", 160 * 1024 - 1024, k_fftmix_bwd<7>)) return rc;
-    int threads = fft_threads(lg);
-    switch (lg) {
-        case 3: k_fftmix_bwd<3><<<a.planes, threads, lds, s>>>(a); break;
-        case 4: k_fftmix_bwd<4><<<a.planes, threads, lds, s>>>(a); break;
-        case 5: k_fftmix_bwd<5><<<a.planes, threads, lds, s>>>(a); break;
-        case 6: k_fftmix_bwd<6><<<a.planes, threads, lds, s>>>(a); break;
-        default: k_fftmix_bwd<7><<<a.planes, threads, lds, s>>>(a); break;
-    }
-    LG_CHECK_LAUNCH();
-    return 0;
+    return fft_bwd_reduce(r, a, s);
 }

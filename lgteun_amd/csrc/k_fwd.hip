@@ -53,9 +53,9 @@ static int mixer_fft_fwd(const Blk& k, int B, int flags, hipStream_t s, const St
     f.sgn = (flags & LG_FLAG_SAVE) ? bb.sgn : nullptr;
     f.scratch = k.fft_scratch;
     f.ampw = k.p(B_AMPW); f.ampb = k.p(B_AMPB); f.phaw = k.p(B_PHAW); f.phab = k.p(B_PHAB);
-    f.ch = bb.e / 2; f.planes = B * f.ch; f.n = bb.h; f.h = bb.h; f.w = bb.w; f.full = pl->route.fft_full;
+    f.ch = bb.e / 2; f.planes = B * f.ch;
     f.sg = sg;
-    return launch_fftmix(f, s);
+    return launch_fftmix(pl->fft(bb.e), f, s);
 }
 static int mixer_local_fwd(const Blk& k, int B, int flags, uint64_t seed, hipStream_t s, const StageSel& sg) {
     const lg_plan* pl = k.pl;

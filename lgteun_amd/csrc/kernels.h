@@ -166,17 +166,16 @@ struct FftArgs {
     float* amp;       // optional save [B,ch,n,n/2+1]
     float* pha;       // optional save
     float* sgn;       // optional save: sign of the irfft2 output [B,ch,n,n]
-    float* scratch;   // n > 128 only: half-spectrum scratch [planes][n][n/2+1] complex
+    float* scratch;   // three-launch paths only: half-spectrum scratch [planes][h][w/2+1] complex (FftRoute::scratch_floats per plane)
     const float *ampw, *ampb, *phaw, *phab;  // [ch]
-    int planes, ch, n;   // n: side of a square plane (legacy callers); h, w (when non-zero) override it
-    int h, w;
-    int full = 0;      // 1: the complex-row in-LDS kernels (A/B variant LG_VAR_FFT_FULL); 0: the real-input kernels (k_fftmix_r / k_fftmix_bwd_r)
+    int planes, ch;
+    int unread_[4] = {0, 0, 0, 0};   // no kernel and no launcher reads these (once n, h, w, full: FftRoute holds them now); they keep the kernels' argument layout
     StageSel sg;       // k_fftmix_r only
 };
-int launch_fftmix(const FftArgs& a, hipStream_t s);
-size_t fft_scratch_floats(int planes, int n);
-size_t fft_scratch_floats_hw(int planes, int h, int w);
-bool fft_is_generic(int h, int w);   // true: Bluestein three-kernel path (anything but a square power of two 8..512)
+int launch_fftmix(const FftRoute& r, const FftArgs& a, hipStream_t s);   // r: the level's route -- path, plane, grids (route.h)
+// what resolve_fft (route.hip) takes from k_fft.hip: columns per workgroup of the column launch of the split / the Bluestein path, planes of height n
+int fft_split_cols_per_wg(int n);
+int fft_bluestein_lines_per_wg(int n);
 
 // ---------------- local mixer + proj + residual, LGT.py:112-146,183-219,231-248 ----------------
 struct AttnArgs {

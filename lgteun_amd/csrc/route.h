@@ -49,11 +49,28 @@ struct MixerRoute {
     AttnBwdKernel bwd;
 };
 
+// The global (FFT) mixer of a level.  The plane's size picks the path -- resolve_fft (route.hip) holds that rule and nothing else does: workspace.h sizes the
+// scratch, k_bwd.hip the partial sums and k_fft.hip's launchers their grids from what is written here.
+enum FftPath {
+    FFT_PATH_LDS_R,       // k_fftmix_r / k_fftmix_bwd_r: real-input in-LDS kernels, one launch per direction
+    FFT_PATH_LDS_C,       // k_fftmix / k_fftmix_bwd: complex-row in-LDS kernels (LG_VAR_FFT_FULL)
+    FFT_PATH_SPLIT,       // rows -> half spectrum in HBM -> columns + edit -> rows: three launches, radix-2 (256 x 256, 512 x 512)
+    FFT_PATH_BLUESTEIN    // the same three launches on Bluestein lines: every other plane
+};
+struct FftRoute {
+    FftPath path;
+    int h, w;                // the plane
+    int lg;                  // log2 h on the three power-of-two paths (h = w there); 0: Bluestein
+    int col_groups;          // column groups per plane: grid.y of the column launch of the three-launch paths = partial rows a plane's backward writes (in LDS: 1)
+    size_t scratch_floats;   // per plane: the half spectrum h x (w/2 + 1), complex, of the three-launch paths; in LDS: 0
+    size_t bwd_part_floats(size_t planes) const { return planes * col_groups * 4; }   // FftBwdArgs::part: four parameter-gradient partial sums per row
+};
+
 struct LgRoute {
     FfnRoute ffn[2];     // by level
     MixerRoute mix[2];
+    FftRoute fft[2];
     bool dstep_fused;        // the one-launch data step (k_dstep.hip) instead of the tile kernels
-    bool fft_full;           // complex-row in-LDS FFT mixer kernels instead of the real-input ones
     bool reduce_per_block;   // one parameter-gradient reduce launch per block instead of one per pass
 };
 

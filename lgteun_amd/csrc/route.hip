@@ -14,7 +14,9 @@
 // LG_VAR_ATTN_FWD_VALU           LG_ATTN_FWD = valu                    local-mixer forward: the vector-pipe k_attn instead of the matrix-pipe k_attn_m
 // LG_VAR_FFN_BF16X3              LG_FFN_SPLIT = bf16x3                 fused FFN forward (and with it the local mixer, whose scales ride in the same prep launch):
 //                                                                      three bf16 pieces / six products instead of f16 pairs with operand scales
-// LG_VAR_FFT_FULL                LG_FFT = full                         global mixer: complex-row in-LDS kernels instead of the real-input ones
+// LG_VAR_FFT_FULL                LG_FFT = full                         global mixer, planes that run in LDS (square powers of two up to 128): the complex-row kernels
+//                                                                      instead of the real-input ones.  The path itself follows from the plane's size alone
+//                                                                      (resolve_fft); lg_plan_describe names it per level: fft=k_fftmix_r | k_fftmix | split | bluestein
 // LG_VAR_FFN_BWD_BF16X3          LG_FFN_BWD_SPLIT = bf16x3             k_ffn1_bwd_xs: three bf16 pieces instead of f16 pairs
 // LG_VAR_ATTN_BWD_CORE_M         LG_ATTN_BWD_CORE = m                  e = 32 local-mixer backward core: k_attn_bwd_core_m (re-derives the row statistics) instead of k_attn_bwd_core
 // LG_VAR_FFN_XS                  LG_FFN_FWD = xs                       e = 16 fused FFN forward: the channel-split k_ffn_xs instead of the register chain k_ffn_xr
@@ -84,6 +86,19 @@ static void resolve_mixer(const lg_config& cfg, int e, MixerRoute& m) {
     m.stats = cfg.precision == 0 && m.fwd == ATTN_FWD_M && !(v & LG_VAR_ATTN_BWD_RESTATS) && m.bwd != ATTN_BWD_R3_CORE_M;
 }
 
+// THE size rule of the global mixer: a square power of two of 8 .. 512 stays radix-2 -- in LDS up to 128, through HBM above -- and every other plane
+// takes Bluestein lines.  LG_VAR_FFT_FULL swaps the in-LDS kernel pair and touches nothing else.
+static void resolve_fft(const lg_config& cfg, int h, int w, FftRoute& f) {
+    const bool pow2 = h == w && (h & (h - 1)) == 0 && h >= 8 && h <= 512;
+    f.h = h; f.w = w; f.lg = 0;
+    while (pow2 && (1 << f.lg) < h) ++f.lg;
+    f.path = !pow2 ? FFT_PATH_BLUESTEIN : h > 128 ? FFT_PATH_SPLIT : (cfg.variant & LG_VAR_FFT_FULL) ? FFT_PATH_LDS_C : FFT_PATH_LDS_R;
+    // columns a workgroup of the column launch transforms; the in-LDS kernels hold the whole plane
+    const int cols_per_wg = f.path == FFT_PATH_SPLIT ? fft_split_cols_per_wg(h) : f.path == FFT_PATH_BLUESTEIN ? fft_bluestein_lines_per_wg(h) : 0;
+    f.col_groups = cols_per_wg ? (w / 2 + 1 + cols_per_wg - 1) / cols_per_wg : 1;
+    f.scratch_floats = cols_per_wg ? (size_t)h * (w / 2 + 1) * 2 : 0;
+}
+
 int lg_resolve_route(const lg_config& cfg, LgRoute* r) {
     const uint32_t v = cfg.variant;
     if (v & ~LG_VAR_ALL) { lg_set_error("plan_create: unknown variant bits 0x%x", v & ~LG_VAR_ALL); return -2; }
@@ -95,8 +110,9 @@ int lg_resolve_route(const lg_config& cfg, LgRoute* r) {
     resolve_ffn(cfg, 2 * E, cfg.H / 2, cfg.W / 2, r->ffn[1]);
     resolve_mixer(cfg, E, r->mix[0]);
     resolve_mixer(cfg, 2 * E, r->mix[1]);
+    resolve_fft(cfg, cfg.H, cfg.W, r->fft[0]);
+    resolve_fft(cfg, cfg.H / 2, cfg.W / 2, r->fft[1]);
     r->dstep_fused = !(v & LG_VAR_DSTEP_TILES) && dstep_fused_ok(cfg.C, cfg.H, cfg.W);
-    r->fft_full = (v & LG_VAR_FFT_FULL) != 0;
     r->reduce_per_block = (v & LG_VAR_REDUCE_PER_BLOCK) != 0;
     return 0;
 }
@@ -117,6 +133,7 @@ int lg_describe_route(const lg_config& cfg, const LgRoute& r, char* buf, size_t 
     static const char* const arith_names[] = {"f32", "bf16", "f16x2", "bf16x3"};
     static const char* const dw_names[] = {"k_ffn_dw_bwd_xs", "k_ffn_dw_bwd_h", "k_ffn_dw_bwd"};
     static const char* const px_names[] = {"k_ffn1_bwd_xs", "k_ffn1_bwd_x32", "k_ffn1_bwd"};
+    static const char* const fft_names[] = {"k_fftmix_r", "k_fftmix", "split", "bluestein"};
     static const char* const attn_bwd_names[] = {"k_attn_bwd_f", "k_attn_bwd_core+k_attn_bwd_epi", "k_attn_bwd_core_m+k_attn_bwd_epi"};
     size_t off = 0;
     bool full = false;
@@ -126,15 +143,15 @@ int lg_describe_route(const lg_config& cfg, const LgRoute& r, char* buf, size_t 
     };
     if (!buf || n == 0) { lg_set_error("plan_describe: null argument"); return -1; }
     put("net C=%d %dx%d precision=%d variant=0x%x: dstep=%s fft=%s reduce=%s\n", cfg.C, cfg.H, cfg.W, cfg.precision, cfg.variant,
-        r.dstep_fused ? "fused" : "tiles", r.fft_full ? "k_fftmix" : "k_fftmix_r", r.reduce_per_block ? "per_block" : "merged");
+        r.dstep_fused ? "fused" : "tiles", (cfg.variant & LG_VAR_FFT_FULL) ? "k_fftmix" : "k_fftmix_r", r.reduce_per_block ? "per_block" : "merged");
     for (int l = 0; l < 2 && !full; ++l) {
         const FfnRoute& f = r.ffn[l];
         const MixerRoute& m = r.mix[l];
         const char* attn = m.fwd == ATTN_FWD_M ? "k_attn_m" : "k_attn";
         const char* attn_arith = m.fwd == ATTN_FWD_VALU ? "f32" : m.bf16 ? "bf16" : m.f16x2 ? "f16x2" : "bf16x3";
         char sb[48];
-        put("L%d e=%d %dx%d fwd: ffn=%s arith=%s hidden=%s | mixer=%s arith=%s\n", l, f.e, f.h, f.w, fwd_names[f.fwd[0]], arith_names[f.arith],
-            f.hbf ? "bf16" : "fp32", attn, attn_arith);
+        put("L%d e=%d %dx%d fwd: ffn=%s arith=%s hidden=%s | mixer=%s arith=%s | fft=%s\n", l, f.e, f.h, f.w, fwd_names[f.fwd[0]], arith_names[f.arith],
+            f.hbf ? "bf16" : "fp32", attn, attn_arith, fft_names[r.fft[l].path]);
         put("L%d e=%d %dx%d save: ffn=%s writes=%s | mixer=%s writes=%s\n", l, f.e, f.h, f.w, fwd_names[f.fwd[1]],
             slots_text(f.saves, f.pre, f.a3_pre(), sb), attn, m.stats ? "o,l" : "-");
         unsigned reads = FFN_SLOT_H2;   // by kernel: the spatial half, the pixelwise half, the weight-gradient launches

@@ -69,7 +69,7 @@ struct NetBufs {
     float* deadout;   // output of dead-stage LGTs (faithful mode)
     float* u_down;    // saved bicubic-downsampled encoder output [B,H/2,W/2,E] (train)
     float* t_up;      // saved up-path tensor [B,H,W,E] (train)
-    float* fft_scratch;  // PAN > 128 only: half-spectrum scratch of the split FFT path
+    float* fft_scratch;  // half-spectrum scratch of the FFT mixer's three-launch paths (FftRoute::scratch_floats); null where both levels run in LDS
     float* ffn_scales;   // [K][LG_NBLK][FFN_SCALES_ROW] operand scales of the f16-pair FFN arithmetic (k_ffn_prep.hip), written once per forward call
     float* attn_scales;  // [K][LG_NBLK][ATTN_SCALES_ROW] static operand scales of the local mixer's f16-pair products { s_y, s_w, s_q, s_k } (k_ffn_prep.hip), written once per forward call
     float* wsplit;       // [K][LG_NBLK][wsplit_slot] slots of pre-split (and pre-scaled) weight fragments of the e >= 32 FFN blocks (k_ffn_x32.hip), written once per forward call
@@ -194,7 +194,7 @@ static inline void carve(const lg_plan* plan, int B, int train, void* base, NetB
     if (train == 2) cv.off += (size_t)(c.K - 1) * nb.set_bytes;
     {
         // level 0: B * E/2 planes of H x W; level 1: B * E planes of H/2 x W/2 -- level 0's is the larger whenever both need one
-        const size_t f0 = fft_scratch_floats_hw((int)(BT * (E / 2)), c.H, c.W), f1 = fft_scratch_floats_hw((int)(BT * E), c.H / 2, c.W / 2);
+        const size_t f0 = BT * (E / 2) * plan->route.fft[0].scratch_floats, f1 = BT * E * plan->route.fft[1].scratch_floats;
         const size_t fl = f0 > f1 ? f0 : f1;
         nb.fft_scratch = fl ? cv.take(fl) : nullptr;
     }

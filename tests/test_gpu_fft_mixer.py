@@ -11,9 +11,10 @@ Re F < 0 is within 0.05 ||plane|| of the cut, no amplitude below 0.05 ||plane||,
 there: helpers.fft_kink_mask) and that the fp32 oracle is within 2e-6 of fp64 -- so the fp32 oracle is a yardstick.  Each case:
 
   * PRECONDITIONS FIRST (helpers.fft_assert_preconditions), ahead of any launch; then ROUTE: `fft=k_fftmix_r` (or `fft=k_fftmix` under
-    LG_FFT=full) from the net line of lg_plan_describe.  The description does not tell the in-LDS, split and Bluestein paths apart: those follow
-    from the plane's size alone (k_fft.hip: fft_is_generic, then h > 128), restated in _expected_family and asserted against the case's family,
-    with the Bluestein length M = next power of two >= 2n - 1 deciding 'blue' (M <= 512) / 'blue1k' (M >= 1024);
+    LG_FFT=full) from the net line of lg_plan_describe, and from the fwd line of the block's level the path the plan resolved for that plane
+    (route.hip: resolve_fft): `fft=k_fftmix_r`, `k_fftmix`, `split` or `bluestein`, asserted against the case's family.  The path follows from the
+    plane's size alone; _expected_family restates that rule on its own and is asserted against the case's family as well, with the Bluestein
+    length M = next power of two >= 2n - 1 deciding 'blue' (M <= 512) / 'blue1k' (M >= 1024);
   * FORWARD in a NaN-filled buffer with 1024 floats of band on each side: no NaN left, both bands intact; relative L2 at the existing 2e-4;
     element by element, max |got - fp64| over the plane's fp64 RMS, maximised over planes, at most BAR_FWD x the same figure of the fp32 oracle.
     The edited spectrum's phases are nearly coherent (conv_pha's weights are small): the output has a peak of 6 .. 450 x RMS around pixel (0, 0),
@@ -101,18 +102,24 @@ def _bluestein_m(n):
 
 
 def _expected_family(h, w):
-    """the size rule of launch_fftmix (k_fft.hip: fft_is_generic, then h > 128), restated; lg_plan_describe does not tell these paths apart"""
+    """the size rule of the plan's FFT route (route.hip: resolve_fft), restated on its own: lg_plan_describe's per-level fft= token is held against it"""
     if h == w and h & (h - 1) == 0 and 8 <= h <= 512:
         return 'split' if h > 128 else 'lds'
     return 'blue1k' if max(_bluestein_m(h), _bluestein_m(w)) >= 1024 else 'blue'
 
 
+FFT_TOKEN = {'lds': 'k_fftmix_r', 'full': 'k_fftmix', 'split': 'split', 'blue': 'bluestein', 'blue1k': 'bluestein'}
+
+
 def _assert_route(ops, family, blk, H, W):
-    """route first: what lg_plan_describe reports (the in-LDS kernel family), and the size rule for what it does not"""
-    net_line = ops.eng.describe(H, W).splitlines()[0]
+    """route first: the switch on the net line of lg_plan_describe, the path on the fwd line of the block's level, and the size rule restated"""
+    lines = ops.eng.describe(H, W).splitlines()
     want = 'fft=k_fftmix' if family == 'full' else 'fft=k_fftmix_r'
-    assert want in net_line.split(': ')[1].split(), (want, net_line)
-    assert _expected_family(*fft_plane(blk, H, W)) == ('lds' if family == 'full' else family), (family, blk, H, W)
+    assert want in lines[0].split(': ')[1].split(), (want, lines[0])
+    h, w = fft_plane(blk, H, W)
+    fwd = [ln for ln in lines if ln.startswith(f'L{1 if blk == 2 else 0} ') and ' fwd: ' in ln]   # (block 2 is the bottleneck: level 1)
+    assert len(fwd) == 1 and fwd[0].split(' | ')[-1] == 'fft=' + FFT_TOKEN[family], (family, blk, H, W, fwd)
+    assert _expected_family(h, w) == ('lds' if family == 'full' else family), (family, blk, H, W)
 
 
 def _elementwise(tag, what, got, ref64, ref32, gate, bar, bad):

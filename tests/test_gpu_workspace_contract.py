@@ -317,7 +317,9 @@ def _fwd_route(ops, H, W, level, e):
     lines = [ln for ln in ops.eng.describe(H, W).splitlines() if ln.startswith(f'L{level} ') and ' fwd: ' in ln]
     assert len(lines) == 1, lines
     ffn = {16: 'k_ffn_xr', 32: 'k_ffn_x32', 64: 'k_ffn1_x64+k_ffn2_x64'}[e]
-    assert lines[0].split(' fwd: ')[1] == f'ffn={ffn} arith=f16x2 hidden=fp32 | mixer=k_attn_m arith=f16x2', lines[0]
+    from test_route_cpu import fft_path_by_size
+    fft = fft_path_by_size(H >> level, W >> level, False)
+    assert lines[0].split(' fwd: ')[1] == f'ffn={ffn} arith=f16x2 hidden=fp32 | mixer=k_attn_m arith=f16x2 | fft={fft}', lines[0]
 
 
 def _fills_agree(ops, tag, call, stale_call=None):

@@ -58,14 +58,17 @@ class Plan:
 
 
 def parse(text):
-    """{(level, mode): (ffn fields, mixer fields)} of the per-level lines, and the net line"""
+    """{(level, mode): (ffn fields, mixer fields)} of the per-level lines -- a 'fwd' line carries a third group, the global mixer's {'fft': path} --
+    and the net line"""
     lines = text.splitlines()
     assert lines[0].startswith('net ') and len(lines) == 7, text
     out = {}
     for line in lines[1:]:
         head, rest = line.split(': ', 1)
-        ffn, mixer = rest.split(' | ')
-        out[(int(head[1]), head.split()[-1])] = (dict(kv.split('=', 1) for kv in ffn.split()), dict(kv.split('=', 1) for kv in mixer.split()))
+        mode = head.split()[-1]
+        groups = tuple(dict(kv.split('=', 1) for kv in part.split()) for part in rest.split(' | '))
+        assert len(groups) == (3 if mode == 'fwd' else 2) and (mode != 'fwd' or list(groups[2]) == ['fft']), line
+        out[(int(head[1]), mode)] = groups
     assert sorted(out) == [(lvl, mode) for lvl in (0, 1) for mode in ('bwd', 'fwd', 'save')], text
     return lines[0], out
 
@@ -138,10 +141,12 @@ def test_level_1_planes_without_whole_strips_fall_back_to_the_tile_kernel(C, pre
 
 
 def test_bit_groups_are_independent():
-    """a bit outside a group leaves that group's part of the text alone, on the default and on every single switch"""
+    """a bit outside a group leaves that group's part of the text alone, on the default and on every single switch; the global mixer's path is part
+    of the net group (LG_VAR_FFT_FULL alone moves it)"""
     def parts(text):
         net, r = parse(text)
-        return net.split(': ')[1], [r[k][0] for k in sorted(r)], [r[k][1] for k in sorted(r)]
+        fft = [r[k][2] for k in sorted(r) if k[1] == 'fwd']
+        return (net.split(': ')[1], fft), [r[k][0] for k in sorted(r)], [r[k][1] for k in sorted(r)]
     for C, prec in ((4, 0), (8, 0), (4, 1)):
         for base in [0] + SINGLE:
             p0 = Plan(C, prec, 128, 128, base)
@@ -169,37 +174,37 @@ def test_invalid_variant_words_are_rejected():
 DEFAULT_ROUTES = {
     (4, 0): """\
 net C=4 128x128 precision=0 variant=0x0: dstep=fused fft=k_fftmix_r reduce=merged
-L0 e=16 128x128 fwd: ffn=k_ffn_xr arith=f16x2 hidden=fp32 | mixer=k_attn_m arith=f16x2
+L0 e=16 128x128 fwd: ffn=k_ffn_xr arith=f16x2 hidden=fp32 | mixer=k_attn_m arith=f16x2 | fft=k_fftmix_r
 L0 e=16 128x128 save: ffn=k_ffn_xr writes=h2,a3:h3 | mixer=k_attn_m writes=o,l
 L0 e=16 128x128 bwd: ffn=k_ffn_dw_bwd_xs+k_ffn1_bwd_xs arith=f16x2 reads=h2,a3:h3 | mixer=k_attn_bwd_f stats=saved
-L1 e=32 64x64 fwd: ffn=k_ffn_x32 arith=f16x2 hidden=fp32 | mixer=k_attn_m arith=f16x2
+L1 e=32 64x64 fwd: ffn=k_ffn_x32 arith=f16x2 hidden=fp32 | mixer=k_attn_m arith=f16x2 | fft=k_fftmix_r
 L1 e=32 64x64 save: ffn=k_ffn_x32 writes=h2,a3:h3 | mixer=k_attn_m writes=o,l
 L1 e=32 64x64 bwd: ffn=k_ffn_dw_bwd_xs+k_ffn1_bwd_xs arith=f16x2 reads=h2,a3:h3 | mixer=k_attn_bwd_core+k_attn_bwd_epi stats=saved
 """,
     (4, 1): """\
 net C=4 128x128 precision=1 variant=0x0: dstep=fused fft=k_fftmix_r reduce=merged
-L0 e=16 128x128 fwd: ffn=k_ffn_xr arith=bf16 hidden=bf16 | mixer=k_attn_m arith=bf16
+L0 e=16 128x128 fwd: ffn=k_ffn_xr arith=bf16 hidden=bf16 | mixer=k_attn_m arith=bf16 | fft=k_fftmix_r
 L0 e=16 128x128 save: ffn=k_ffn_xr writes=h2,a3:h3 | mixer=k_attn_m writes=-
 L0 e=16 128x128 bwd: ffn=k_ffn_dw_bwd_xs+k_ffn1_bwd_xs arith=bf16 reads=h2,a3:h3 | mixer=k_attn_bwd_f stats=recomputed
-L1 e=32 64x64 fwd: ffn=k_ffn_x32 arith=bf16 hidden=bf16 | mixer=k_attn_m arith=bf16
+L1 e=32 64x64 fwd: ffn=k_ffn_x32 arith=bf16 hidden=bf16 | mixer=k_attn_m arith=bf16 | fft=k_fftmix_r
 L1 e=32 64x64 save: ffn=k_ffn_x32 writes=h2,a3:h3 | mixer=k_attn_m writes=-
 L1 e=32 64x64 bwd: ffn=k_ffn_dw_bwd_xs+k_ffn1_bwd_xs arith=bf16 reads=h2,a3:h3 | mixer=k_attn_bwd_core+k_attn_bwd_epi stats=recomputed
 """,
     (8, 0): """\
 net C=8 128x128 precision=0 variant=0x0: dstep=fused fft=k_fftmix_r reduce=merged
-L0 e=32 128x128 fwd: ffn=k_ffn_x32 arith=f16x2 hidden=fp32 | mixer=k_attn_m arith=f16x2
+L0 e=32 128x128 fwd: ffn=k_ffn_x32 arith=f16x2 hidden=fp32 | mixer=k_attn_m arith=f16x2 | fft=k_fftmix_r
 L0 e=32 128x128 save: ffn=k_ffn_x32 writes=h2,a3:h3 | mixer=k_attn_m writes=o,l
 L0 e=32 128x128 bwd: ffn=k_ffn_dw_bwd_xs+k_ffn1_bwd_xs arith=f16x2 reads=h2,a3:h3 | mixer=k_attn_bwd_core+k_attn_bwd_epi stats=saved
-L1 e=64 64x64 fwd: ffn=k_ffn1_x64+k_ffn2_x64 arith=f16x2 hidden=fp32 | mixer=k_attn_m arith=f16x2
+L1 e=64 64x64 fwd: ffn=k_ffn1_x64+k_ffn2_x64 arith=f16x2 hidden=fp32 | mixer=k_attn_m arith=f16x2 | fft=k_fftmix_r
 L1 e=64 64x64 save: ffn=k_ffn1_x64+k_ffn2_x64 writes=a1,g1,h2,a3,g3 | mixer=k_attn_m writes=o,l
 L1 e=64 64x64 bwd: ffn=k_ffn_dw_bwd+k_ffn1_bwd+k_wgrad(W2)+k_wgrad(W1)+k_wgrad(W3) arith=f32 reads=a1,g1,h2,a3,g3 | mixer=k_attn_bwd_core+k_attn_bwd_epi stats=saved
 """,
     (8, 1): """\
 net C=8 128x128 precision=1 variant=0x0: dstep=fused fft=k_fftmix_r reduce=merged
-L0 e=32 128x128 fwd: ffn=k_ffn_x32 arith=bf16 hidden=bf16 | mixer=k_attn_m arith=bf16
+L0 e=32 128x128 fwd: ffn=k_ffn_x32 arith=bf16 hidden=bf16 | mixer=k_attn_m arith=bf16 | fft=k_fftmix_r
 L0 e=32 128x128 save: ffn=k_ffn_x32 writes=h2,a3:h3 | mixer=k_attn_m writes=-
 L0 e=32 128x128 bwd: ffn=k_ffn_dw_bwd_xs+k_ffn1_bwd_xs arith=bf16 reads=h2,a3:h3 | mixer=k_attn_bwd_core+k_attn_bwd_epi stats=recomputed
-L1 e=64 64x64 fwd: ffn=k_ffn1_x64+k_ffn2_x64 arith=bf16x3 hidden=fp32 | mixer=k_attn_m arith=bf16
+L1 e=64 64x64 fwd: ffn=k_ffn1_x64+k_ffn2_x64 arith=bf16x3 hidden=fp32 | mixer=k_attn_m arith=bf16 | fft=k_fftmix_r
 L1 e=64 64x64 save: ffn=k_ffn1_x64+k_ffn2_x64 writes=a1,g1,h2,a3,g3 | mixer=k_attn_m writes=-
 L1 e=64 64x64 bwd: ffn=k_ffn_dw_bwd+k_ffn1_bwd+k_wgrad(W2)+k_wgrad(W1)+k_wgrad(W3) arith=f32 reads=a1,g1,h2,a3,g3 | mixer=k_attn_bwd_core+k_attn_bwd_epi stats=recomputed
 """,
@@ -211,6 +216,55 @@ def test_default_routes_are_pinned(C, prec):
     p = Plan(C, prec, 128, 128, 0)
     assert p.error is None
     assert p.describe() == DEFAULT_ROUTES[(C, prec)]
+
+
+# PAN sizes on every path of the global (FFT) mixer, level 0 then level 1: in LDS on both (16, 32, 128); split, then in LDS (256); split on both (512);
+# Bluestein, then split (1024); Bluestein on both (rectangles, sides that are no power of two).  24 x 8 is no multiple of 16: no plan takes it
+FFT_SIZES = [(16, 16), (32, 32), (128, 128), (256, 256), (512, 512), (1024, 1024), (80, 48), (208, 176), (400, 400), (1024, 32), (24, 8)]
+
+
+def fft_path_by_size(h, w, full):
+    """the size rule of the global mixer, restated: a square power of two of 8 .. 512 stays radix-2 -- through HBM above 128, in LDS otherwise, where
+    LG_VAR_FFT_FULL picks the kernel pair -- and everything else takes Bluestein lines"""
+    if h == w and h & (h - 1) == 0 and 8 <= h <= 512:
+        return 'split' if h > 128 else 'k_fftmix' if full else 'k_fftmix_r'
+    return 'bluestein'
+
+
+@pytest.mark.parametrize('C', [4, 8])
+@pytest.mark.parametrize('H,W', FFT_SIZES)
+def test_fft_path_follows_the_plane_size(C, H, W):
+    """each level's fft= token of lg_plan_describe is the size rule's answer for that level's plane, with and without LG_VAR_FFT_FULL, and the switch
+    changes the token of the in-LDS levels only"""
+    tokens = {}
+    for full in (False, True):
+        p = Plan(C, 0, H, W, _lib.LG_VAR_FFT_FULL if full else 0)
+        if H % 16 or W % 16:
+            assert p.error is not None and 'multiples of 16' in p.error, (H, W, p.error)
+            return
+        assert p.error is None, p.error
+        net, r = parse(p.describe())
+        assert ('fft=k_fftmix' if full else 'fft=k_fftmix_r') in net.split(': ')[1].split(), net   # the net line: the switch, as before
+        tokens[full] = [r[(lvl, 'fwd')][2]['fft'] for lvl in (0, 1)]
+        assert tokens[full] == [fft_path_by_size(H >> lvl, W >> lvl, full) for lvl in (0, 1)], (C, H, W, full, tokens[full])
+    for plain, switched in zip(tokens[False], tokens[True]):
+        assert (plain, switched) == ('k_fftmix_r', 'k_fftmix') or (plain == switched and plain in ('split', 'bluestein')), tokens
+
+
+def test_workspace_bytes_on_every_fft_path_are_those_before_the_fft_route():
+    """lg_workspace_bytes at FFT_SIZES (both C, both precisions, with and without LG_VAR_FFT_FULL): the half-spectrum scratch of the split and the
+    Bluestein path and the backward's partial rows, sized from FftRoute, against the figures of the library that derived them from the plane size"""
+    with open(os.path.join(GOLD, 'workspace_bytes_fft.json')) as f:
+        gold = json.load(f)
+    assert gold['K'] == K
+    seen = set()
+    for c in gold['cases']:
+        p = Plan(c['C'], c['precision'], c['H'], c['W'], c['variant'])
+        assert p.error is None, (c, p.error)
+        assert p.workspace_bytes() == c['bytes'], c
+        seen.add((c['C'], c['precision'], c['H'], c['W'], c['variant']))
+    assert seen == {(C, prec, H, W, v) for C in (4, 8) for prec in (0, 1) for H, W in FFT_SIZES if H % 16 == 0 and W % 16 == 0
+                    for v in (0, _lib.LG_VAR_FFT_FULL)}
 
 
 def test_describe_reports_a_short_buffer():

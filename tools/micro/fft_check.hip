@@ -13,6 +13,13 @@ void lg_set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vfprint
 void lg_prof_begin(int, hipStream_t) {}
 void lg_prof_end(int, hipStream_t, int) {}
 int launch_reduce_job(const ReduceJob&, hipStream_t) { return 0; }
+// the route of an n x n plane held in LDS (n a power of two up to 128), as resolve_fft (route.hip) fills it
+static FftRoute lds_route(int n, bool full) {
+    FftRoute r;
+    r.path = full ? FFT_PATH_LDS_C : FFT_PATH_LDS_R; r.h = r.w = n; r.lg = 0; r.col_groups = 1; r.scratch_floats = 0;
+    while ((1 << r.lg) < n) ++r.lg;
+    return r;
+}
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s:%d %s\n", __FILE__, __LINE__, hipGetErrorString(e_)); exit(1); } } while (0)
 static uint64_t rs = 0x1234567ull;
 static double urand() { rs = rs * 6364136223846793005ull + 1442695040888963407ull; return (double)(rs >> 11) / 9007199254740992.0; }
@@ -74,8 +81,8 @@ static int rounds_probe(int reps) {
     hipStream_t s; CK(hipStreamCreate(&s));
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     FftArgs a; a.g = dg; a.o = o; a.amp = nullptr; a.pha = nullptr; a.sgn = nullptr; a.scratch = nullptr; a.ampw = dp; a.ampb = dp + ch; a.phaw = dp + 2 * ch; a.phab = dp + 3 * ch;
-    a.planes = 256; a.ch = ch; a.n = n; a.h = n; a.w = n; a.full = 0;
-    if (launch_fftmix(a, s)) return 1;      // twiddles and the LDS attribute of both instances
+    a.planes = 256; a.ch = ch;
+    if (launch_fftmix(lds_route(n, false), a, s)) return 1;      // twiddles and the LDS attribute of both instances
     CK(hipStreamSynchronize(s));
     const size_t ldsr = ((size_t)n * FFT_HP(n) + n / 2) * sizeof(float2);
     auto run = [&](int planes, int nth, int save) {   // save 0: none, 1: all, 2: the last `live` planes
@@ -117,11 +124,12 @@ int main(int argc, char** argv) {
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     for (int k = 0; k < 2; ++k) {
         FftArgs a; a.g = dg; a.o = o[k]; a.amp = amp[k]; a.pha = pha[k]; a.sgn = sgn[k]; a.scratch = nullptr; a.ampw = daw; a.ampb = dab; a.phaw = dpw; a.phab = dpb;
-        a.planes = planes; a.ch = ch; a.n = n; a.h = n; a.w = n; a.full = k == 0;
-        for (int r = 0; r < 3; ++r) if (launch_fftmix(a, s)) return 1;
+        a.planes = planes; a.ch = ch;
+        const FftRoute route = lds_route(n, k == 0);
+        for (int r = 0; r < 3; ++r) if (launch_fftmix(route, a, s)) return 1;
         CK(hipStreamSynchronize(s));
         CK(hipEventRecord(e0, s));
-        for (int r = 0; r < reps; ++r) launch_fftmix(a, s);
+        for (int r = 0; r < reps; ++r) launch_fftmix(route, a, s);
         CK(hipEventRecord(e1, s)); CK(hipEventSynchronize(e1));
         float ms; CK(hipEventElapsedTime(&ms, e0, e1));
         printf("%s n=%d planes=%d: %.2f us per launch\n", k == 0 ? "k_fftmix  (complex rows)" : "k_fftmix_r (real input) ", n, planes, ms * 1e3 / reps);
