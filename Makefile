@@ -2,7 +2,7 @@
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
 CSRC  := lgteun_amd/csrc
-SRCS  := $(CSRC)/api.hip $(CSRC)/prof.hip $(CSRC)/route.hip $(CSRC)/k_fwd.hip $(CSRC)/k_pixel.hip $(CSRC)/k_dstep.hip $(CSRC)/k_fft.hip $(CSRC)/k_attn.hip $(CSRC)/k_attn_m.hip $(CSRC)/k_ffn.hip $(CSRC)/k_ffn_prep.hip $(CSRC)/k_ffn_x.hip $(CSRC)/k_ffn_xr.hip $(CSRC)/k_ffn_x32.hip $(CSRC)/k_ffn_x64.hip $(CSRC)/k_bwd.hip $(CSRC)/k_bwd_pixel.hip $(CSRC)/k_wgrad.hip $(CSRC)/k_ffn_bwd.hip $(CSRC)/k_ffn_bwd_x.hip $(CSRC)/k_ffn_dwbwd_x.hip $(CSRC)/k_ffn_dwbwd_h.hip $(CSRC)/k_ffn1_bwd_x32.hip $(CSRC)/k_attn_bwd.hip $(CSRC)/k_attn_bwd_f.hip $(CSRC)/k_attn_bwd_m.hip $(CSRC)/k_iqa.hip $(CSRC)/k_iqa_ext.hip $(CSRC)/k_batch.hip $(CSRC)/k_scene.hip $(CSRC)/k_wald.hip $(CSRC)/k_gradnorm.hip $(CSRC)/k_optim.hip $(CSRC)/k_qnr.hip $(CSRC)/k_recloss.hip $(CSRC)/k_classical.hip
+SRCS  := $(CSRC)/api.hip $(CSRC)/prof.hip $(CSRC)/route.hip $(CSRC)/k_fwd.hip $(CSRC)/k_pixel.hip $(CSRC)/k_dstep.hip $(CSRC)/k_fft.hip $(CSRC)/k_attn.hip $(CSRC)/k_attn_m.hip $(CSRC)/k_ffn.hip $(CSRC)/k_ffn_prep.hip $(CSRC)/k_ffn_x.hip $(CSRC)/k_ffn_xr.hip $(CSRC)/k_ffn_x32.hip $(CSRC)/k_ffn_x64.hip $(CSRC)/k_bwd.hip $(CSRC)/k_bwd_pixel.hip $(CSRC)/k_wgrad.hip $(CSRC)/k_ffn_bwd.hip $(CSRC)/k_ffn_bwd_x.hip $(CSRC)/k_ffn_dwbwd_x.hip $(CSRC)/k_ffn_dwbwd_h.hip $(CSRC)/k_ffn1_bwd_x32.hip $(CSRC)/k_attn_bwd.hip $(CSRC)/k_attn_bwd_f.hip $(CSRC)/k_attn_bwd_m.hip $(CSRC)/k_iqa.hip $(CSRC)/k_iqa_ext.hip $(CSRC)/k_batch.hip $(CSRC)/k_scene.hip $(CSRC)/k_wald.hip $(CSRC)/k_gradnorm.hip $(CSRC)/k_optim.hip $(CSRC)/k_qnr.hip $(CSRC)/k_recloss.hip $(CSRC)/k_classical.hip $(CSRC)/k_cs.hip
 LIB   := lgteun_amd/_lgteun_hip.so
 OBJS  := $(SRCS:.hip=.o)
 # -fno-slp-vectorize: the SLP vectoriser turns scalar fp32 chains into v_pk_mul_f32 / v_pk_add_f32 pairs; packed fp32 issues at

@@ -584,6 +584,33 @@ size_t lg_bdsd_workspace_bytes(int32_t B, int32_t C, int32_t h, int32_t w, int32
 int lg_bdsd(const float* ms, const float* pan, float* out, double* stats, const double* taps_ms, int32_t n_filters, const double* taps_pan, int32_t n_taps,
             int32_t block, int32_t B, int32_t C, int32_t h, int32_t w, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the component-substitution baselines: generalised IHS, Brovey, Gram-Schmidt, PCA (lgteun_amd/cs.py) ----
+ * Per sample, with u = interp23(ms), N = 16 h w, m_k = mean u_k, m_p = mean pan, Sigma = cov of the bands of u, r_k = cov(u_k, pan), v_p = var(pan) (all over
+ * N - 1): intensity weights w -- 1 / C or the caller's `weights` for IHS, Brovey and GS, for PCA the unit eigenvector of Sigma's largest eigenvalue, signed so
+ * that w'r >= 0 (if w'r = 0: sum w >= 0) -- I = sum_k w_k (u_k - m_k), m_I = sum_k w_k m_k, v_I = w'Sigma w, a = sqrt(v_I / v_p), P = a (pan - m_p).  Then
+ *   LG_CS_IHS     out_k = clip(u_k + (P - I))                        g_k = 1
+ *   LG_CS_BROVEY  out_k = clip(u_k (P + m_I) / (I + m_I + 2^-52))    g_k = 1 in stats
+ *   LG_CS_GS      out_k = clip(u_k + g_k (P - I))                    g_k = (Sigma w)_k / v_I
+ *   LG_CS_PCA     out_k = clip(u_k + g_k (P - I))                    g_k = w_k
+ * clipped to [0, 1] by fmin(fmax()) with one rounding to fp32.  A sample with v_p <= 0, v_I <= 0, a not finite or (PCA) a largest eigenvalue <= 0 is
+ * degenerate: out = clip(u) bit for bit (stats: a = 0, g = 0).  PAN and every band enter the moments minus their first sample, so a constant PAN or band has
+ * exactly zero moments.  weights: a HOST array of C finite doubles, used as given (not normalised), or NULL; must be NULL for LG_CS_PCA.  stats: NULL or a
+ * device array [B, 2 C + 2] of fp64 that receives w (C), g (C), a, m_I.  The moments are formed at the MS scale (the adjoint of interp23 on PAN, its Gram
+ * operator on ms: lg_cs_taps), u only in the apply pass and never stored.  Launches: the adjoint pass, the Gram pass, the finish, the apply pass.  Tensors,
+ * limits, alignment, checks and guarantees (same bits on every call, a sample's bits do not depend on its batch, the workspace needs no initialisation, a
+ * rejected call launches nothing) are those of lg_sfim. */
+#define LG_CS_IHS 0
+#define LG_CS_BROVEY 1
+#define LG_CS_GS 2
+#define LG_CS_PCA 3
+/* bytes of workspace lg_cs needs; 0 for a shape the call rejects */
+size_t lg_cs_workspace_bytes(int32_t B, int32_t C, int32_t h, int32_t w);
+int lg_cs(const float* ms, const float* pan, float* out, double* stats, const double* weights, int32_t mode, int32_t B, int32_t C, int32_t h, int32_t w,
+          void* workspace, size_t workspace_bytes, void* stream);
+/* HOST arrays: t67 receives interp23's 1-D impulse response by offset -33 .. 33 (u(y) = sum_i t(y - 4 i - 2) ms(i), circular), r33 its Gram taps R(d) = sum_m
+ * t(m) t(m - 4 d) by offset -16 .. 16 */
+int lg_cs_taps(double* t67, double* r33);
+
 #ifdef __cplusplus
 }
 #endif

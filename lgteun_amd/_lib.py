@@ -48,6 +48,7 @@ LG_OPT_AMSGRAD, LG_OPT_NESTEROV, LG_OPT_CENTERED = 1, 2, 4             # lg_opti
 LG_DT_U8, LG_DT_U16, LG_DT_F32 = 0, 1, 2                                # lg_pyr_down2 / lg_batch_assemble: sample type of the store
 LG_CLASSICAL_SFIM, LG_CLASSICAL_GSA = 0, 1                              # lg_classical_workspace_bytes: method
 LG_MTFGLP_GLP, LG_MTFGLP_HPM, LG_MTFGLP_CBD = 0, 1, 2                   # lg_mtf_glp: mode (the injection rule)
+LG_CS_IHS, LG_CS_BROVEY, LG_CS_GS, LG_CS_PCA = 0, 1, 2, 3                  # lg_cs: mode (the method)
 LG_ABI_VERSION = 2   # include/lgteun_hip.h: checked against lg_abi_version() when the library is loaded
 
 
@@ -186,6 +187,9 @@ SIGNATURES = {
     'lg_bdsd_workspace_bytes': (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     'lg_bdsd': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
                           c_size_t, c_void_p]),
+    'lg_cs_workspace_bytes': (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    'lg_cs': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_double), c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
+    'lg_cs_taps': (c_int32, [POINTER(c_double), POINTER(c_double)]),
 }
 
 

@@ -5,13 +5,15 @@ dataset.read_tiff, fuses them tile by tile on the GPU (lgteun_amd/scene.py) and 
                                [--batch B] [--float] [--out FILE]
     python tools/fuse_scene.py PREFIX --method gsa|sfim|wavelet [--bit-depth 11] [--norm-input] [--float] [--out FILE]
     python tools/fuse_scene.py PREFIX --method mtf_glp|mtf_glp_hpm|mtf_glp_cbd [--mtf-gains g [g ...]] [--bit-depth 11] ...
+    python tools/fuse_scene.py PREFIX --method ihs|brovey|gs|pca [--cs-weights w [w ...]] [--bit-depth 11] ...
     python tools/fuse_scene.py PREFIX --method bdsd [--bdsd-block N] [--mtf-gains g [g ...]] [--mtf-gain-pan g] [--bit-depth 11] ...
 
 --method gsa / sfim / wavelet (lgteun_amd/classical.py) and mtf_glp / mtf_glp_hpm / mtf_glp_cbd (lgteun_amd/mtf_glp.py) need no checkpoint and no
 tiles: the whole scene is fused in one call, with the same normalisation and the same conversion to digital numbers.  --mtf-gains: the sensor's MTF
 gains at Nyquist, one for all bands or one per band; without them a placeholder (0.3) applies, which is no sensor's value.  --method bdsd
 (lgteun_amd/bdsd.py) takes them too, with --mtf-gain-pan for PAN (placeholder 0.15), and --bdsd-block N fits its weights per block of N x N PAN pixels (a
-multiple of 32 that divides both sides of PAN; without it one fit serves the whole scene).
+multiple of 32 that divides both sides of PAN; without it one fit serves the whole scene).  --method ihs / brovey / gs / pca (lgteun_amd/cs.py) are the
+component-substitution baselines; --cs-weights gives the intensity weights of the first three, one per band (without them 1 / C each).
 
 The checkpoint is a plain-tensor file ({'core_module': state_dict}, what Base_model.save writes and tools/convert_checkpoint.py makes of a
 reference-era file); the band count and the stage count are read from it.  The output holds uint16 digital numbers
@@ -43,12 +45,15 @@ def load_module(path, device='cuda:0'):
 def parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('prefix')
-    ap.add_argument('--method', choices=['network', 'gsa', 'sfim', 'wavelet', 'mtf_glp', 'mtf_glp_hpm', 'mtf_glp_cbd', 'bdsd'], default='network')
+    ap.add_argument('--method', choices=['network', 'gsa', 'sfim', 'wavelet', 'mtf_glp', 'mtf_glp_hpm', 'mtf_glp_cbd', 'bdsd', 'ihs', 'brovey', 'gs', 'pca'],
+                    default='network')
     ap.add_argument('--mtf-gains', type=float, nargs='+', default=None, metavar='g',
                     help="--method mtf_glp* / bdsd: the sensor's MTF gain at Nyquist, one for all bands or one per band (default: a placeholder, 0.3)")
     ap.add_argument('--mtf-gain-pan', type=float, default=None, metavar='g', help="--method bdsd: PAN's MTF gain at Nyquist (default: a placeholder, 0.15)")
     ap.add_argument('--bdsd-block', type=int, default=None, metavar='N',
                     help='--method bdsd: fit the weights per block of N x N PAN pixels, N a multiple of 32 that divides both sides (default: one global fit)')
+    ap.add_argument('--cs-weights', type=float, nargs='+', default=None, metavar='w',
+                    help='--method ihs / brovey / gs: the intensity weights, one per band, used as given (default: 1 / C each)')
     ap.add_argument('--checkpoint', default=None, help='required for --method network')
     ap.add_argument('--tile', type=int, nargs='+', default=[128], help='one side, or height and width')
     ap.add_argument('--overlap', type=int, default=32)
@@ -79,6 +84,10 @@ def main():
         from lgteun_amd import bdsd
         fused = bdsd.fuse_scene(ms_chw, pan[np.newaxis], block=a.bdsd_block, gains_ms=gains, gain_pan=a.mtf_gain_pan, bit_depth=a.bit_depth,
                                 norm_input=a.norm_input, out_dtype='float32' if a.float else 'uint16')
+    elif a.method in ('ihs', 'brovey', 'gs', 'pca'):
+        from lgteun_amd import cs
+        fused = cs.fuse_scene(a.method, ms_chw, pan[np.newaxis], weights=a.cs_weights, bit_depth=a.bit_depth, norm_input=a.norm_input,
+                              out_dtype='float32' if a.float else 'uint16')
     elif a.method.startswith('mtf_glp'):
         from lgteun_amd import mtf_glp
         fused = mtf_glp.fuse_scene(mtf_glp.SCENE_METHODS[a.method], ms_chw, pan[np.newaxis], gains_ms=gains, bit_depth=a.bit_depth, norm_input=a.norm_input,
