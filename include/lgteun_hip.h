@@ -11,11 +11,41 @@
  *
  * Conventions
  *  - plain pointers and sizes only; every pointer is a DEVICE pointer unless marked host.
- *  - the caller (PyTorch) owns all memory: parameters, gradients, optimizer state, workspace.
- *    The library allocates no device memory.  Its only mutable process-global state is the event table of the opt-in
- *    timing facility (lg_prof_*, mutex-protected; off by default) and per-device "kernel attribute set" bits; plans are
- *    immutable after creation, so forward / backward calls on different streams or threads do not interact.
- *  - all work is enqueued on `stream` (a hipStream_t passed as void*); no implicit sync.
+ *  - the caller (PyTorch) owns all memory: parameters, gradients, optimizer state, workspace -- with ONE exception, the
+ *    reduce-image cache below.  Plans are immutable after creation.
+ *  - all work of a call -- kernels and copies -- is enqueued on `stream` (a hipStream_t passed as void*), and the call returns without
+ *    waiting for the device, EXCEPT the two cases listed under "may synchronise" below.  tests/test_gpu_streams.py holds every entry to
+ *    this: called on a stream that is still asleep, it must return at once and read inputs that arrive on that stream later.
+ *  - calls on different streams, or from different host threads, do not interact as long as they share no buffer: a workspace, a
+ *    gradient buffer or a loss scalar belongs to one stream at a time (tests/test_gpu_streams.py, test_gpu_threads.py: bitwise the
+ *    results of each call sequence run alone).  lg_last_error is per thread.  The library's mutable process-global state, all of it:
+ *      (a) per-device once-bits (one 64-bit mask per kernel family, indexed by hipGetDevice() & 63, so devices 64 apart share a bit):
+ *          "dynamic-LDS attribute set" and "twiddles uploaded", and a per-device cache of the compute-unit count.  A race between
+ *          threads only repeats an idempotent call.
+ *      (b) __constant__ c_tw512, the 256 twiddles of the radix-2 FFT paths: written once per device by a hipMemcpyToSymbol at the first
+ *          FFT-mixer launch there, read-only afterwards.
+ *      (c) 64 fp64 accumulator slots in device memory (a __device__ array of the code object, per device) and one process-wide
+ *          round-robin counter: lg_l2_loss launch number n uses slot n mod 64 and hands it back zeroed.  Two lg_l2_loss launches
+ *          collide only if 64 or more were issued -- on any streams, threads and devices of the process -- between them while the
+ *          first had not finished: keep fewer than 64 lg_l2_loss launches pending.
+ *      (d) the reduce-image cache of lgteun_backward / lg_op_*_bwd (default variant: LG_VAR_REDUCE_PER_BLOCK clear): per device 16
+ *          job tables (630 KB) that the LIBRARY allocates with hipMalloc at the first backward on that device and never frees, with
+ *          host copies, behind one process-wide mutex.  A table is the list of gradient reductions of one launch and is found again by
+ *          content; the content is a function of (plan, B, flags, the workspace pointer, the gradient-buffer pointer) and, for a
+ *          per-op entry, of its stage, block and piece.
+ *      (e) process-wide atomic counters of the reduce queue (a debug export reads them) and the mutex-protected event table of the
+ *          opt-in timing facility (lg_prof_*; off by default).
+ *    Host-side staging of a call (the reduce queue, its job table) is thread_local.
+ *  - a call may synchronise, and only then:
+ *      1. FIRST USE PER DEVICE of a kernel family: hipFuncSetAttribute, the twiddle upload (b), the hipMalloc of (d).  These may wait
+ *         for work pending on the device.  Warm every entry you use once per device (any shape of the same C) before relying on 2.
+ *      2. a backward whose job table is NOT in the cache (d) -- a new combination of (plan, B, flags, workspace pointer, gradient
+ *         pointer), or one evicted by 16 newer ones (slots are reused in the order they were filled) -- drains the WHOLE DEVICE
+ *         (hipDeviceSynchronize), uploads the table on `stream` and waits for `stream`.  A training loop that keeps its workspace and
+ *         gradient buffer (Engine.train_step does) misses twice, in its first step, and never again; a caller whose buffers move from
+ *         step to step pays a device drain in every backward.  Results are the same either way.
+ *    Everything else -- every forward, loss, optimizer, metric, classical, data-preparation and scene entry, and a backward whose
+ *    table is cached -- allocates nothing and synchronises nothing.
  *  - return value: 0 ok; <0 invalid argument / unsupported shape (see lg_last_error());
  *    >0 a hipError_t.  Nothing throws across the boundary.
  *  - parameters live in ONE flat fp32 buffer; `offsets[i]` (in floats) locates the i-th tensor of

@@ -13,11 +13,9 @@ import torch
 
 from . import _lib, wald
 from .builder import MODELS
-from .classical import _Classical, _fuse_scene, _prepare
+from .classical import _Classical, _fuse_scene, _prepare, _scratch
 from .engine import _ptr, _stream_ptr
 from .mtf_glp import _device_taps, _gains
-
-_workspaces = {}        # (device, block, B, C, h, w) -> float64 tensor
 
 
 def _block(block, C, h, w):
@@ -49,11 +47,7 @@ def bdsd(ms, pan, block=None, gains_ms=None, gain_pan=None, n_taps=wald.DEFAULT_
     F, L = taps_ms.shape[0], _lib.lib()
     nby, nbx = (4 * h // blk, 4 * w // blk) if blk else (1, 1)
     with torch.cuda.device(ms.device):
-        key = (ms.device, blk) + shape
-        ws = _workspaces.get(key)
-        if ws is None:
-            need = int(L.lg_bdsd_workspace_bytes(B, C, h, w, blk))      # 0 for a shape the library rejects: the call says why
-            ws = _workspaces[key] = torch.empty(max((need + 7) // 8, 1), dtype=torch.float64, device=ms.device)
+        ws = _scratch(ms.device, 'lg_bdsd_workspace_bytes', B, C, h, w, blk)
         out = torch.empty(B, C, 4 * h, 4 * w, dtype=torch.float32, device=ms.device)
         stats = torch.empty(B, nby, nbx, C, C + 1, dtype=torch.float64, device=ms.device) if return_stats else None
         _lib.check(L.lg_bdsd(_ptr(ms), _ptr(pan), _ptr(out), _ptr(stats) if return_stats else None, _ptr(taps_ms), F, _ptr(taps_pan), int(n_taps), blk, B, C, h,

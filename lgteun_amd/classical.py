@@ -8,6 +8,8 @@ per output element, no atomics.  There is no CPU path.
 `interp23`, `sfim`, `gsa` and `wavelet` take normalised float32 NCHW tensors on the GPU -- ms [B, C, h, w], pan [B, 1, 4h, 4w] -- and return
 [B, C, 4h, 4w] on the same device; nothing is copied to the host and nothing synchronises.  `GSA`, `SFIM` and `Wavelet` are the runner classes
 the reference registers under those names: they have nothing to train, and `test()` scores them like any network."""
+import functools
+
 import numpy as np
 import torch
 
@@ -15,8 +17,6 @@ from . import _lib
 from .base_model import Base_model
 from .builder import MODELS
 from .engine import _ptr, _stream_ptr
-
-_workspaces = {}        # (device, method, B, C, h, w) -> float64 tensor: the partial sums and coefficients of lg_sfim / lg_gsa
 
 
 def _prepare(what, ms, pan=None):
@@ -36,13 +36,21 @@ def _prepare(what, ms, pan=None):
     return ms.contiguous(), pan, (B, C, h, w)
 
 
+@functools.lru_cache(maxsize=256)
+def _scratch_doubles(sizer, args):
+    return max((int(getattr(_lib.lib(), sizer)(*args)) + 7) // 8, 1)      # 0 bytes for a shape the library rejects: the call says why
+
+
+def _scratch(dev, sizer, *args):
+    """the workspace of ONE call (partial sums and coefficients between a method's statistics pass and its apply pass), sized by the library's
+    `sizer(*args)`, from torch's caching allocator: a block freed behind the call returns to the pool of the stream it was allocated on, so
+    calls on different streams or from different threads never share one, and a second call on the same stream reuses it in stream order.
+    Only the SIZE is remembered from call to call, never a buffer"""
+    return torch.empty(_scratch_doubles(sizer, args), dtype=torch.float64, device=dev)
+
+
 def _workspace(dev, method, shape):
-    key = (dev, method) + shape
-    ws = _workspaces.get(key)
-    if ws is None:
-        need = int(_lib.lib().lg_classical_workspace_bytes(*shape, method))      # 0 for a shape the library rejects: the call says why
-        ws = _workspaces[key] = torch.empty(max((need + 7) // 8, 1), dtype=torch.float64, device=dev)
-    return ws
+    return _scratch(dev, 'lg_classical_workspace_bytes', *shape, method)
 
 
 def interp23(ms):

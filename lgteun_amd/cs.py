@@ -14,13 +14,11 @@ import torch
 
 from . import _lib
 from .builder import MODELS
-from .classical import _Classical, _fuse_scene, _prepare
+from .classical import _Classical, _fuse_scene, _prepare, _scratch
 from .engine import _ptr, _stream_ptr
 
 MODES = {'ihs': _lib.LG_CS_IHS, 'brovey': _lib.LG_CS_BROVEY, 'gs': _lib.LG_CS_GS, 'pca': _lib.LG_CS_PCA}
 SCENE_METHODS = ('ihs', 'brovey', 'gs', 'pca')      # cs.fuse_scene, tools/fuse_scene.py --method
-
-_workspaces = {}        # (device, B, C, h, w) -> float64 tensor: q, the partial sums and the coefficients of lg_cs
 
 
 def _mode(mode):
@@ -47,12 +45,7 @@ def _weights(mode, weights, C):
 
 
 def _workspace(dev, shape):
-    key = (dev,) + shape
-    ws = _workspaces.get(key)
-    if ws is None:
-        need = int(_lib.lib().lg_cs_workspace_bytes(*shape))      # 0 for a shape the library rejects: the call says why
-        ws = _workspaces[key] = torch.empty(max((need + 7) // 8, 1), dtype=torch.float64, device=dev)
-    return ws
+    return _scratch(dev, 'lg_cs_workspace_bytes', *shape)      # q, the partial sums and the coefficients of lg_cs, for this call only
 
 
 def fuse(ms, pan, mode, weights=None, return_stats=False):

@@ -13,14 +13,13 @@ import torch
 
 from . import _lib, wald
 from .builder import MODELS
-from .classical import _Classical, _fuse_scene, _prepare
+from .classical import _Classical, _fuse_scene, _prepare, _scratch
 from .engine import _ptr, _stream_ptr
 
 MODES = {'glp': _lib.LG_MTFGLP_GLP, 'hpm': _lib.LG_MTFGLP_HPM, 'cbd': _lib.LG_MTFGLP_CBD}
 SCENE_METHODS = {'mtf_glp': 'glp', 'mtf_glp_hpm': 'hpm', 'mtf_glp_cbd': 'cbd'}      # tools/fuse_scene.py --method -> mode
 
-_workspaces = {}        # (device, mode, F, B, C, h, w) -> float64 tensor
-_taps = {}              # (device, gains, n_taps) -> float64 [F, n_taps] on the device
+_taps = {}              # (device, gains, n_taps) -> float64 [F, n_taps] on the device: written once, in _device_taps, then only read
 
 
 def _gains(gains_ms, C):
@@ -48,11 +47,7 @@ def mtf_glp(ms, pan, mode='glp', gains_ms=None, n_taps=wald.DEFAULT_TAPS, return
     taps = _device_taps(ms.device, _gains(gains_ms, C), n_taps)
     F, L = taps.shape[0], _lib.lib()
     with torch.cuda.device(ms.device):
-        key = (ms.device, mode, F) + shape
-        ws = _workspaces.get(key)
-        if ws is None:
-            need = int(L.lg_mtfglp_workspace_bytes(B, C, h, w, F, MODES[mode]))      # 0 for a shape the library rejects: the call says why
-            ws = _workspaces[key] = torch.empty(max((need + 7) // 8, 1), dtype=torch.float64, device=ms.device)
+        ws = _scratch(ms.device, 'lg_mtfglp_workspace_bytes', B, C, h, w, F, MODES[mode])
         out = torch.empty(B, C, 4 * h, 4 * w, dtype=torch.float32, device=ms.device)
         stats = torch.empty(B, 2 * C, dtype=torch.float64, device=ms.device) if return_stats else None
         _lib.check(L.lg_mtf_glp(_ptr(ms), _ptr(pan), _ptr(out), _ptr(stats) if return_stats else None, _ptr(taps), F, taps.shape[1], MODES[mode], B, C, h, w,

@@ -1,7 +1,7 @@
 """Helper, not a test: what tests/test_gpu_abi_limits.py and tests/test_abi_limits_cpu.py share -- the probe arithmetic around element offset
 2^31, input makers whose samples are all distinct, the memory gate, a peak-memory / time reporter, and one raw C-ABI call per classical
-method with a workspace that is freed with the call (the wrappers of lgteun_amd/classical.py, mtf_glp.py and bdsd.py keep theirs in a
-module-level cache, which a test that allocates gigabytes must not fill).
+method with a workspace of the test's own that is freed with the call and synchronised behind it (the wrappers of lgteun_amd/classical.py,
+mtf_glp.py and bdsd.py allocate theirs per call too, but return stats and outputs in their own shapes and do not synchronise).
 
 Nothing here imports torch at module level, so the CPU file can use the arithmetic without it."""
 import ctypes
