@@ -1,6 +1,9 @@
-// What the kernels of the classical baselines share (k_classical.hip: SFIM, GSA, Wavelet, MTF-GLP, BDSD; k_cs.hip: IHS, Brovey, GS, PCA): the 16 x 32 output
-// tile, the upsampling of one band of a tile in LDS (cl_up_band), the one rounding to fp32 (cl_clip) and the shape check of the entries.  Everything is
-// internal to the translation unit that includes it.
+// What the kernels of the classical baselines share (k_classical.hip: SFIM, GSA, Wavelet, MTF-GLP, BDSD; k_cs.hip: IHS, Brovey, GS, PCA), each written once.
+// Device: the 16 x 32 output tile and its origin (cl_tile), the upsampling of one band of a tile in LDS (cl_up_band) and of all C bands with the next band's
+// loads in flight (cl_up_bands), the one rounding to fp32 (cl_clip), the sum of a column of per-workgroup partials (cl_partials_column), the sums of products of
+// two LDS vectors with a wave per entry (cl_pair, cl_lane_dot, cl_pair_sums), and the Cholesky factor and solve in LDS (cl_cholesky, cl_chol_solve).  Every one
+// of them fixes an order of additions that the outputs' bits depend on.  Host: the shape check (cl_shape), the tile count (cl_tiles), the argument checks every
+// fused entry makes after its shape (cl_check_args) and a region of the workspace (cl_ws).  Everything is internal to the translation unit that includes it.
 #pragma once
 #include <cmath>
 
@@ -60,10 +63,14 @@ __device__ __forceinline__ void cl_axis(const double* in, int il, int is, double
     }
 }
 
-// the ms samples of one band the tile at (Y0, X0) depends on, CL_MLOADS per thread, into registers: a caller issues them for the NEXT band (or tile)
+// the origin of output tile t, tiles_x tiles in a row:   const auto [Y0, X0] = cl_tile(t, tiles_x);
+struct ClTile { int Y0, X0; };
+__device__ __forceinline__ ClTile cl_tile(int t, int tiles_x) { return {(t / tiles_x) * CL_TH, (t % tiles_x) * CL_TW}; }
+
+// the ms samples of one band the tile at o depends on, CL_MLOADS per thread, into registers: a caller issues them for the NEXT band (or tile)
 // before it runs cl_up_band on the current one, so their latency passes under its four LDS passes
-__device__ __forceinline__ void cl_ms_load(const float* __restrict__ ms, int h, int w, int Y0, int X0, float (&v)[CL_MLOADS]) {
-    const int my0 = Y0 / 4 - 8, mx0 = X0 / 4 - 8;
+__device__ __forceinline__ void cl_ms_load(const float* __restrict__ ms, int h, int w, ClTile o, float (&v)[CL_MLOADS]) {
+    const int my0 = o.Y0 / 4 - 8, mx0 = o.X0 / 4 - 8;
 #pragma unroll
     for (int u = 0; u < CL_MLOADS; ++u) {
         const int i = threadIdx.x + u * CL_NT, r = i / CL_MC, c = i - r * CL_MC;
@@ -96,7 +103,114 @@ __device__ __forceinline__ void cl_up_band(const T (&v)[CL_MLOADS], double* S, d
     cl_axis<true>(R2, 1, CL_TW, U, 1, CL_TW, CL_TW, CL_TH);            // level 2 along y: 32 lines of 16
 }
 
+// v = vn: the samples loaded ahead become the current ones
+template <typename T>
+__device__ __forceinline__ void cl_next(T (&v)[CL_MLOADS], const T (&vn)[CL_MLOADS]) {
+#pragma unroll
+    for (int u = 0; u < CL_MLOADS; ++u) v[u] = vn[u];
+}
+
+// u of all C bands of the tile at (Y0, X0) -> U[C][16][32]; ms_b: the sample's bands, lp = h w apart.  Band k + 1's samples are loaded before band k's four LDS
+// passes.  Ends WITHOUT a barrier, like cl_up_band.
+__device__ __forceinline__ void cl_up_bands(const float* __restrict__ ms_b, long lp, int C, int h, int w, int Y0, int X0, double* S, double* U) {
+    float v[CL_MLOADS], vn[CL_MLOADS] = {};
+    cl_ms_load(ms_b, h, w, {Y0, X0}, v);
+    for (int k = 0; k < C; ++k) {
+        if (k + 1 < C) cl_ms_load(ms_b + (k + 1) * lp, h, w, {Y0, X0}, vn);
+        cl_up_band(v, S, U + k * CL_PX);
+        cl_next(v, vn);
+    }
+}
+
 __device__ __forceinline__ float cl_clip(double o) { return (float)fmin(fmax(o, 0.0), 1.0); }      // the one rounding to fp32
+
+// pe[0] + pe[stride] + ... + pe[(n - 1) stride] by one thread: the partials of n workgroups for one entry, one accumulator, ascending order.  (k_cs_finish is not
+// a caller: it sums with a wave per entry and a butterfly, and its bits depend on that order.)
+__device__ __forceinline__ double cl_partials_column(const double* __restrict__ pe, int n, long stride) {
+    double s = 0.0;
+    int j = 0;
+    for (; j + 8 <= n; j += 8) {      // eight loads in flight, added in ascending order
+        double q[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) q[u] = pe[(j + u) * stride];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += q[u];
+    }
+    for (; j < n; ++j) s += pe[j * stride];
+    return s;
+}
+
+// entry e of a sum list: vectors a and b, of the high- (lo = 0) or the low-resolution table
+__device__ __forceinline__ int cl_pair(int a, int b, int lo) { return a | (b << 8) | (lo << 16); }
+
+// a lane's share of sum_i a[i] b[i] over N (a multiple of 64) elements of two LDS vectors: elements lane, lane + 64, ... in ascending order on ONE fma chain --
+// the chain fixes the bits.  N at compile time: unrolled.
+template <int N>
+__device__ __forceinline__ double cl_lane_dot(const double* a, const double* b, int lane) {
+    double v = 0.0;
+#pragma unroll
+    for (int u = 0; u < N / 64; ++u) v = fma(a[lane + 64 * u], b[lane + 64 * u], v);
+    return v;
+}
+// the same over the first n elements, n at run time (the vectors hold zeros from n up to the next multiple of 64)
+__device__ __forceinline__ double cl_lane_dot(const double* a, const double* b, int lane, int n) {
+    double v = 0.0;
+    for (int u = 0; u < n; u += 64) v = fma(a[lane + u], b[lane + u], v);
+    return v;
+}
+
+// acc[e] += the sum over the wave of term(a, b, lo, lane) for every entry e < ns, (a, b, lo) = pairs[e] (cl_pair): wave j of the four owns the entries j, j + 4,
+// ...; lane 0 adds.  The caller puts a barrier behind it before the vectors change.
+template <typename F>
+__device__ __forceinline__ void cl_pair_sums(const int* pairs, int ns, double* acc, F term) {
+    const int lane = threadIdx.x & 63;
+    for (int e = threadIdx.x >> 6; e < ns; e += CL_NT / 64) {
+        const int pr = pairs[e];
+        const double v = wave_sum(term(pr & 255, (pr >> 8) & 255, pr >> 16, lane));
+        if (lane == 0) acc[e] += v;
+    }
+}
+
+// The Cholesky factor L of a symmetric n x n matrix into the lower triangle of Lm (rows `pitch` apart), by ONE thread.  A(i, j): the matrix's entry, asked for
+// i >= j, once, before L(i, j) is written (so A may read Lm itself).  bad_pivot(d, a_jj): the caller's rule for a column's pivot d before its root; true ends the
+// factorisation with false returned.  The order of the subtractions inside a row fixes the bits.
+template <typename M, typename P>
+__device__ __forceinline__ bool cl_cholesky(double* Lm, int n, int pitch, M A, P bad_pivot) {
+    for (int j = 0; j < n; ++j) {
+        const double ajj = A(j, j);
+        double d = ajj;
+        for (int p = 0; p < j; ++p) d -= Lm[j * pitch + p] * Lm[j * pitch + p];
+        if (bad_pivot(d, ajj)) return false;
+        d = sqrt(d);
+        Lm[j * pitch + j] = d;
+        for (int i = j + 1; i < n; ++i) {
+            double s = A(i, j);
+            for (int p = 0; p < j; ++p) s -= Lm[i * pitch + p] * Lm[j * pitch + p];
+            Lm[i * pitch + j] = s / d;
+        }
+    }
+    return true;
+}
+
+// x = (L L')^-1 rhs by one thread, forward then back; x may be rhs.  each(x_i): the caller's look at every component as the back substitution forms it (a pass
+// of its own over x afterwards cost BDSD's one-wave solve 0.5 - 1 us)
+template <typename E>
+__device__ __forceinline__ void cl_chol_solve(const double* Lm, int n, int pitch, const double* rhs, double* x, E each) {
+    for (int i = 0; i < n; ++i) {
+        double s = rhs[i];
+        for (int p = 0; p < i; ++p) s -= Lm[i * pitch + p] * x[p];
+        x[i] = s / Lm[i * pitch + i];
+    }
+    for (int i = n - 1; i >= 0; --i) {
+        double s = x[i];
+        for (int p = i + 1; p < n; ++p) s -= Lm[p * pitch + i] * x[p];
+        x[i] = s / Lm[i * pitch + i];
+        each(x[i]);
+    }
+}
+__device__ __forceinline__ void cl_chol_solve(const double* Lm, int n, int pitch, const double* rhs, double* x) {
+    cl_chol_solve(Lm, n, pitch, rhs, x, [](double) {});
+}
 #endif  // __HIPCC__
 
 // false: not a shape the calls take (the reason, naming the argument, is in lg_last_error)
@@ -107,5 +221,32 @@ inline bool cl_shape(const char* who, int B, int C, int h, int w) {
     if (w < 4 || w > 4096) { lg_set_error("%s: w must be 4..4096 (got %d)", who, w); return false; }
     return true;
 }
+
+// the 16 x 32 output tiles of a sample: those in a row of tiles -> tiles_x, all of them returned
+inline int cl_tiles(int h, int w, int& tiles_x) {
+    tiles_x = (4 * w + CL_TW - 1) / CL_TW;
+    return tiles_x * ((4 * h + CL_TH - 1) / CL_TH);
+}
+
+// the named fp64 arrays: all of them given (where `required`), then all of them 8-byte aligned
+inline bool check_doubles(const char* who, std::initializer_list<std::pair<const char*, const void*>> ds, bool required) {
+    if (required)
+        for (const auto& d : ds)
+            if (!d.second) { lg_set_error("%s: %s is NULL", who, d.first); return false; }
+    for (const auto& d : ds)
+        if ((uintptr_t)d.second & 7) { lg_set_error("%s: %s must be 8-byte aligned", who, d.first); return false; }
+    return true;
+}
+
+// what every fused entry checks once its shape is known, in this order: the three float tensors, the fp64 arrays it cannot do without (`doubles`), stats (which
+// may be NULL), the workspace (`sizer`: the C ABI function that returns `need`)
+inline bool cl_check_args(const char* who, const float* ms, const float* pan, const float* out, std::initializer_list<std::pair<const char*, const void*>> doubles,
+                          const double* stats, const void* workspace, size_t workspace_bytes, size_t need, const char* sizer) {
+    return check_tensors(who, {{"ms", ms}, {"pan", pan}, {"out", out}}) && check_doubles(who, doubles, true) && check_doubles(who, {{"stats", stats}}, false) &&
+           check_workspace(who, workspace, workspace_bytes, need, sizer);
+}
+
+// the workspace region at byte offset off (ws_layout)
+inline double* cl_ws(void* workspace, size_t off) { return (double*)((char*)workspace + off); }
 
 }  // namespace

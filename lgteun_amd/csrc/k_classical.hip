@@ -14,11 +14,12 @@
 //                    of the tile, PAN minus the sample's first PAN pixel (the pivot: a constant PAN has EXACTLY zero moments) and the mask of the pixels inside the image as C + 2 vectors
 //                    in LDS, GSA also the C ms bands, the 2 x 2 centre mean of PAN and the mask at the tile's 4 x 8 low-resolution pixels.
 //                    Every sum the method needs is the sum of a product of two of those vectors: a wave owns the pairs e = wave, wave + 4,
-//                    ..., sums them over the tile and lane 0 adds to its slot in LDS -- one order, always.  The workgroup writes its slots.
-//   k_cl_finish      one workgroup per sample: the partials in ascending order, then one thread: SFIM's scales, or GSA's C x C Cholesky
-//                    solve for alpha and the gains g = N / (N - 1) Sigma_u alpha / (alpha' Sigma_u alpha).  A constant PAN gives scale 0;
-//                    a non-positive pivot, alpha' Sigma_u alpha <= 0 or a gain that is not finite gives alpha = g = 0.
-//   k_cl_apply       grid (tile, sample): the C bands of the tile again, then pointwise in fp64 with ONE rounding to fp32; SFIM stages
+//                    ..., sums them over the tile and lane 0 adds to its slot in LDS -- one order, always (cl_pair_sums, classical_tiles.h, shared
+//                    with k_bd_gram and k_cs_gram).  The workgroup writes its slots.
+//   k_cl_finish      one workgroup per sample: the partials in ascending order (cl_partials_column), then one thread: SFIM's scales, or GSA's
+//                    C x C Cholesky solve (cl_cholesky, cl_chol_solve) for alpha and the gains g = N / (N - 1) Sigma_u alpha / (alpha' Sigma_u alpha).
+//                    A constant PAN gives scale 0; a non-positive pivot, alpha' Sigma_u alpha <= 0 or a gain that is not finite gives alpha = g = 0.
+//   k_cl_apply       grid (tile, sample): the C bands of the tile again (cl_up_bands), then pointwise in fp64 with ONE rounding to fp32; SFIM stages
 //                    PAN with a circular halo of 2 for the 5 x 5 box.  Two adjacent pixels per thread: 8-byte stores.
 //   k_cl_wavelet     grid (tile, sample), the whole method in one launch: out_k = clip(pan - P + M_k) with P the 4 x 4 block mean of PAN and M_k the
 //                    block mean of u_k, which is a separable 17-tap circular FIR on ms itself (cl_wavelet_taps).  A lane owns 4 x 4 blocks: 16-byte
@@ -46,19 +47,16 @@ __global__ __launch_bounds__(CL_NT) void k_cl_interp(const float* __restrict__ m
     extern __shared__ double cl_lds[];
     double* U = cl_lds + CL_SCRATCH;
     const int H4 = 4 * h, W4 = 4 * w;
-    const int Y0 = (blockIdx.x / tiles_x) * CL_TH, X0 = (blockIdx.x % tiles_x) * CL_TW;
+    const auto [Y0, X0] = cl_tile(blockIdx.x, tiles_x);
     const long plane = (long)blockIdx.z * gridDim.y + blockIdx.y;
     float v[CL_MLOADS];
-    cl_ms_load(ms + plane * ((long)h * w), h, w, Y0, X0, v);
+    cl_ms_load(ms + plane * ((long)h * w), h, w, {Y0, X0}, v);
     cl_up_band(v, cl_lds, U);
     __syncthreads();
     const int p = 2 * threadIdx.x, y = Y0 + p / CL_TW, x = X0 + p % CL_TW;
     if (y < H4 && x < W4)      // W4 is a multiple of 4 and x is even: both pixels or none
         *reinterpret_cast<float2*>(out + plane * ((long)H4 * W4) + (long)y * W4 + x) = make_float2((float)U[p], (float)U[p + 1]);
 }
-
-// entry e of the sum list: vectors a and b, of the high- (lo = 0) or the low-resolution table
-__device__ __forceinline__ int cl_pair(int a, int b, int lo) { return a | (b << 8) | (lo << 16); }
 
 // part [B][gx][ns].  SFIM (ns = 2 C + 2): sum u_k, sum u_k^2 per band, then sum pc, sum pc^2 with pc = PAN - pivot.  GSA (ns = (C + 2)(C + 3)):
 // all pairs a <= b of the vectors [mask, u_0 .. u_C-1, pc] in row-major order of the upper triangle, then the same of [mask, ms_0 .. ms_C-1, q]
@@ -95,17 +93,16 @@ __global__ __launch_bounds__(CL_NT) void k_cl_moments(const float* __restrict__ 
     for (int e = tid; e < ns; e += CL_NT) acc[e] = 0.0;
     // (the barriers inside cl_up_band order both before their first use)
     float v[CL_MLOADS], vn[CL_MLOADS] = {};
-    cl_ms_load(ms_b, h, w, (blockIdx.x / tiles_x) * CL_TH, (blockIdx.x % tiles_x) * CL_TW, v);
+    cl_ms_load(ms_b, h, w, cl_tile(blockIdx.x, tiles_x), v);
     for (int t = blockIdx.x; t < tiles; t += gx) {
-        const int Y0 = (t / tiles_x) * CL_TH, X0 = (t % tiles_x) * CL_TW;
+        const auto [Y0, X0] = cl_tile(t, tiles_x);
         for (int k = 0; k < C; ++k) {
             if (k + 1 < C)
-                cl_ms_load(ms_b + (k + 1) * ((long)h * w), h, w, Y0, X0, vn);
+                cl_ms_load(ms_b + (k + 1) * ((long)h * w), h, w, {Y0, X0}, vn);
             else if (t + gx < tiles)
-                cl_ms_load(ms_b, h, w, ((t + gx) / tiles_x) * CL_TH, ((t + gx) % tiles_x) * CL_TW, vn);
+                cl_ms_load(ms_b, h, w, cl_tile(t + gx, tiles_x), vn);
             cl_up_band(v, cl_lds, Vhi + (k + 1) * CL_PX);
-#pragma unroll
-            for (int u = 0; u < CL_MLOADS; ++u) v[u] = vn[u];
+            cl_next(v, vn);
             if (gsa && tid < CL_LPX) {
                 const int gi = Y0 / 4 + tid / CL_LC, gj = X0 / 4 + tid % CL_LC;
                 Vlo[(k + 1) * CL_LPX + tid] = (gi < h && gj < w) ? (double)ms_b[k * ((long)h * w) + (long)gi * w + gj] : 0.0;
@@ -127,19 +124,10 @@ __global__ __launch_bounds__(CL_NT) void k_cl_moments(const float* __restrict__ 
             Vlo[(C + 1) * CL_LPX + tid] = in ? 0.25 * ((P[0] + P[1]) + (P[CL_TW] + P[CL_TW + 1])) : 0.0;
         }
         __syncthreads();
-        const int lane = tid & 63;
-        for (int e = tid >> 6; e < ns; e += CL_NT / 64) {
-            const int pr = pairs[e], a = pr & 255, c = (pr >> 8) & 255;
-            double v = 0.0;
-            if (pr >> 16) {
-                if (lane < CL_LPX) v = Vlo[a * CL_LPX + lane] * Vlo[c * CL_LPX + lane];
-            } else {
-#pragma unroll
-                for (int u = 0; u < CL_PX / 64; ++u) v = fma(Vhi[a * CL_PX + lane + 64 * u], Vhi[c * CL_PX + lane + 64 * u], v);
-            }
-            v = wave_sum(v);
-            if (lane == 0) acc[e] += v;
-        }
+        cl_pair_sums(pairs, ns, acc, [&](int a, int c, int lo, int lane) {
+            if (lo) return lane < CL_LPX ? Vlo[a * CL_LPX + lane] * Vlo[c * CL_LPX + lane] : 0.0;
+            return cl_lane_dot<CL_PX>(Vhi + a * CL_PX, Vhi + c * CL_PX, lane);
+        });
         __syncthreads();      // the next tile overwrites the vectors
     }
     for (int e = tid; e < ns; e += CL_NT) part[(b * gx + blockIdx.x) * ns + e] = acc[e];
@@ -152,20 +140,7 @@ __global__ __launch_bounds__(CL_NT) void k_cl_finish(const double* __restrict__ 
     __shared__ double Lm[CL_MAX_C * CL_MAX_C], mu[CL_MAX_C], mm[CL_MAX_C], al[CL_MAX_C], v[CL_MAX_C];
     const int n = C + 2, np = n * (n + 1) / 2, ns = gsa ? 2 * np : 2 * C + 2;
     const long b = blockIdx.x;
-    for (int e = threadIdx.x; e < ns; e += CL_NT) {
-        const double* __restrict__ pe = part + b * gx * ns + e;
-        double s = 0.0;
-        int j = 0;
-        for (; j + 8 <= gx; j += 8) {      // eight loads in flight, added in ascending order
-            double q[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) q[u] = pe[(long)(j + u) * ns];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += q[u];
-        }
-        for (; j < gx; ++j) s += pe[(long)j * ns];
-        sums[e] = s;
-    }
+    for (int e = threadIdx.x; e < ns; e += CL_NT) sums[e] = cl_partials_column(part + b * gx * ns + e, gx, ns);
     __syncthreads();
     if (threadIdx.x != 0) return;
     double* co = coef + b * (3 * C + 1);
@@ -187,32 +162,12 @@ __global__ __launch_bounds__(CL_NT) void k_cl_finish(const double* __restrict__ 
         mm[k] = at(1, 0, k + 1) / nl;
     }
     // Sigma_ms alpha = cov(ms, q) by Cholesky, the lower triangle in Lm
-    bool ok = true;
     for (int k = 0; k < C; ++k)
         for (int l = 0; l <= k; ++l) Lm[k * C + l] = at(1, l + 1, k + 1) / nl - mm[k] * mm[l];
-    for (int j = 0; j < C && ok; ++j) {
-        double d = Lm[j * C + j];
-        for (int p = 0; p < j; ++p) d -= Lm[j * C + p] * Lm[j * C + p];
-        if (!(d > 0.0)) { ok = false; break; }
-        d = sqrt(d);
-        Lm[j * C + j] = d;
-        for (int i = j + 1; i < C; ++i) {
-            double s = Lm[i * C + j];
-            for (int p = 0; p < j; ++p) s -= Lm[i * C + p] * Lm[j * C + p];
-            Lm[i * C + j] = s / d;
-        }
-    }
+    bool ok = cl_cholesky(Lm, C, C, [&](int i, int j) { return Lm[i * C + j]; }, [](double d, double) { return !(d > 0.0); });
     if (ok) {
-        for (int i = 0; i < C; ++i) {
-            double s = at(1, i + 1, C + 1) / nl - mm[i] * mq;
-            for (int p = 0; p < i; ++p) s -= Lm[i * C + p] * al[p];
-            al[i] = s / Lm[i * C + i];
-        }
-        for (int i = C - 1; i >= 0; --i) {
-            double s = al[i];
-            for (int p = i + 1; p < C; ++p) s -= Lm[p * C + i] * al[p];
-            al[i] = s / Lm[i * C + i];
-        }
+        for (int i = 0; i < C; ++i) al[i] = at(1, i + 1, C + 1) / nl - mm[i] * mq;
+        cl_chol_solve(Lm, C, C, al, al);
         double den = 0.0;
         for (int k = 0; k < C; ++k) {
             double s = 0.0;
@@ -249,21 +204,13 @@ __global__ __launch_bounds__(CL_NT) void k_cl_apply(const float* __restrict__ ms
     double* U = cl_lds + CL_SCRATCH;             // [C][512]
     double* PT = U + C * CL_PX;                  // SFIM: [20][36], staged pixel (r, c) = PAN pixel (Y0 - 2 + r, X0 - 2 + c) modulo the sides, minus the pivot
     const int tid = threadIdx.x, H4 = 4 * h, W4 = 4 * w;
-    const int Y0 = (blockIdx.x / tiles_x) * CL_TH, X0 = (blockIdx.x % tiles_x) * CL_TW;
-    const long b = blockIdx.y;
-    const float* __restrict__ ms_b = ms + b * C * ((long)h * w);
+    const auto [Y0, X0] = cl_tile(blockIdx.x, tiles_x);
+    const long b = blockIdx.y, lp = (long)h * w;
     const float* __restrict__ pan_b = pan + b * ((long)H4 * W4);
     float* __restrict__ out_b = out + b * C * ((long)H4 * W4);
     const double* __restrict__ co = coef + b * (3 * C + 1);
     const double pv = (double)pan_b[0];
-    float v[CL_MLOADS], vn[CL_MLOADS] = {};
-    cl_ms_load(ms_b, h, w, Y0, X0, v);
-    for (int k = 0; k < C; ++k) {
-        if (k + 1 < C) cl_ms_load(ms_b + (k + 1) * ((long)h * w), h, w, Y0, X0, vn);
-        cl_up_band(v, cl_lds, U + k * CL_PX);
-#pragma unroll
-        for (int u = 0; u < CL_MLOADS; ++u) v[u] = vn[u];
-    }
+    cl_up_bands(ms + b * C * lp, lp, C, h, w, Y0, X0, cl_lds, U);
     if (!GSA)
         for (int i = tid; i < CL_BH * CL_BW; i += CL_NT) {
             const int r = i / CL_BW, c = i - r * CL_BW;
@@ -447,10 +394,11 @@ __global__ __launch_bounds__(CL_NT, 4) void k_cl_wavelet(const float* __restrict
 //                  evaluated at the decimated positions only -- rows into LDS, then columns (k_wald.hip's scheme), fp64 [B, F, h, w] in the workspace.
 //   k_mg_moments   cbd only, grid (gx, sample) like k_cl_moments: per band the tiles of u_k (cl_up_band on ms) and of L_k (cl_up_band on q_k = a_k (D_k - mu) + m_k,
 //                  the affine map applied where D is loaded, modulo the sides), both minus m_k; wave j sums vector j of {u, L, u L, L L} over the tile and
-//                  lane 0 adds to its slot in LDS -- one order, always.  k_mg_finish: the partials in ascending order, then g_k per band.
+//                  lane 0 adds to its slot in LDS -- one order, always.  k_mg_finish: the partials in ascending order (cl_partials_column), then g_k per band.
 //   k_mg_apply     grid (tile, sample): per band the tile of u, the tile of L, the thread's two PAN pixels, the rule, ONE rounding; the next band's ms and D
 //                  samples are in flight under the current band's eight LDS passes.  The workgroup of tile 0 writes stats.
-// Neither u nor L is ever stored in memory.
+// Neither u nor L is ever stored in memory.  The two tile kernels carry a second stream of samples (q) beside ms and k_mg_moments loads across tiles, so
+// they keep their own band loops, not cl_up_bands.
 constexpr int MG_TO = 16, MG_MAX_TAPS = 63, MG_SPAN = 4 * (MG_TO - 1) + MG_MAX_TAPS;      // low-pass: outputs per tile edge, PAN rows under one tile's column taps
 constexpr int MG_LDS = CL_SCRATCH + 2 * CL_PX;                           // doubles: the scratch of cl_up_band, the tile of u, the tile of L
 constexpr int MG_PER_CU = 3, MG_RESIDENT = MG_PER_CU * CL_CUS;           // workgroups per sample of the second moments pass, at most
@@ -490,9 +438,9 @@ __global__ __launch_bounds__(CL_NT) void k_mg_lowpass(const float* __restrict__ 
     dlow[(b * gridDim.y + f) * ((long)h * w) + (long)(oy0 + ly) * w + ox0 + lx] = acc;
 }
 
-// the samples of q_k = a (D - mu) + m the tile at (Y0, X0) depends on, where cl_ms_load takes those of ms: D is the filtered PAN minus the pivot, mpc = mu minus the pivot
-__device__ __forceinline__ void mg_q_load(const double* __restrict__ dl, int h, int w, int Y0, int X0, double a, double mpc, double m, double (&v)[CL_MLOADS]) {
-    const int my0 = Y0 / 4 - 8, mx0 = X0 / 4 - 8;
+// the samples of q_k = a (D - mu) + m the tile at o depends on, where cl_ms_load takes those of ms: D is the filtered PAN minus the pivot, mpc = mu minus the pivot
+__device__ __forceinline__ void mg_q_load(const double* __restrict__ dl, int h, int w, ClTile o, double a, double mpc, double m, double (&v)[CL_MLOADS]) {
+    const int my0 = o.Y0 / 4 - 8, mx0 = o.X0 / 4 - 8;
 #pragma unroll
     for (int u = 0; u < CL_MLOADS; ++u) {
         const int i = threadIdx.x + u * CL_NT, r = i / CL_MC, c = i - r * CL_MC;
@@ -519,19 +467,15 @@ __global__ __launch_bounds__(CL_NT) void k_mg_moments(const float* __restrict__ 
     for (int e = tid; e < 4 * C; e += CL_NT) acc[e] = 0.0;      // (the barriers inside cl_up_band order this before the first use)
     float v[CL_MLOADS], vn[CL_MLOADS] = {};
     double q[CL_MLOADS], qn[CL_MLOADS] = {};
-    {
-        const int Y0 = (blockIdx.x / tiles_x) * CL_TH, X0 = (blockIdx.x % tiles_x) * CL_TW;
-        cl_ms_load(ms_b, h, w, Y0, X0, v);
-        mg_q_load(dl_b, h, w, Y0, X0, co[1 + C], mpc, co[1], q);
-    }
+    cl_ms_load(ms_b, h, w, cl_tile(blockIdx.x, tiles_x), v);
+    mg_q_load(dl_b, h, w, cl_tile(blockIdx.x, tiles_x), co[1 + C], mpc, co[1], q);
     for (int t = blockIdx.x; t < tiles; t += gx) {
-        const int Y0 = (t / tiles_x) * CL_TH, X0 = (t % tiles_x) * CL_TW;
+        const auto [Y0, X0] = cl_tile(t, tiles_x);
         for (int k = 0; k < C; ++k) {
             const int kn = k + 1 < C ? k + 1 : 0, tn = k + 1 < C ? t : t + gx;
             if (tn < tiles) {
-                const int Yn = (tn / tiles_x) * CL_TH, Xn = (tn % tiles_x) * CL_TW;
-                cl_ms_load(ms_b + kn * lp, h, w, Yn, Xn, vn);
-                mg_q_load(dl_b + (F == 1 ? 0 : kn) * lp, h, w, Yn, Xn, co[1 + C + kn], mpc, co[1 + kn], qn);
+                cl_ms_load(ms_b + kn * lp, h, w, cl_tile(tn, tiles_x), vn);
+                mg_q_load(dl_b + (F == 1 ? 0 : kn) * lp, h, w, cl_tile(tn, tiles_x), co[1 + C + kn], mpc, co[1 + kn], qn);
             }
             cl_up_band(v, cl_lds, U);
             cl_up_band(q, cl_lds, Lt);
@@ -548,11 +492,8 @@ __global__ __launch_bounds__(CL_NT) void k_mg_moments(const float* __restrict__ 
             }
             s = wave_sum(s);
             if (lane == 0) acc[4 * k + wave] += s;
-#pragma unroll
-            for (int u = 0; u < CL_MLOADS; ++u) {
-                v[u] = vn[u];
-                q[u] = qn[u];
-            }
+            cl_next(v, vn);
+            cl_next(q, qn);
             // no barrier: the next cl_up_band writes U and Lt in its last pass, four barriers from here
         }
     }
@@ -566,20 +507,7 @@ __global__ __launch_bounds__(CL_NT) void k_mg_finish(const double* __restrict__ 
     __shared__ double sums[4 * CL_MAX_C];
     const long b = blockIdx.x;
     const int ns = 4 * C;
-    for (int e = threadIdx.x; e < ns; e += CL_NT) {
-        const double* __restrict__ pe = part + b * gx * ns + e;
-        double s = 0.0;
-        int j = 0;
-        for (; j + 8 <= gx; j += 8) {      // eight loads in flight, added in ascending order
-            double q[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) q[u] = pe[(long)(j + u) * ns];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += q[u];
-        }
-        for (; j < gx; ++j) s += pe[(long)j * ns];
-        sums[e] = s;
-    }
+    for (int e = threadIdx.x; e < ns; e += CL_NT) sums[e] = cl_partials_column(part + b * gx * ns + e, gx, ns);
     __syncthreads();
     const int k = threadIdx.x;
     if (k >= C) return;
@@ -598,7 +526,7 @@ __global__ __launch_bounds__(CL_NT) void k_mg_apply(const float* __restrict__ ms
     double* U = cl_lds + CL_SCRATCH;
     double* Lt = U + CL_PX;
     const int tid = threadIdx.x, H4 = 4 * h, W4 = 4 * w;
-    const int Y0 = (blockIdx.x / tiles_x) * CL_TH, X0 = (blockIdx.x % tiles_x) * CL_TW;
+    const auto [Y0, X0] = cl_tile(blockIdx.x, tiles_x);
     const long b = blockIdx.y, lp = (long)h * w, plane = (long)H4 * W4;
     const float* __restrict__ ms_b = ms + b * C * lp;
     const double* __restrict__ dl_b = dlow + b * F * lp;
@@ -612,8 +540,8 @@ __global__ __launch_bounds__(CL_NT) void k_mg_apply(const float* __restrict__ ms
     }
     float v[CL_MLOADS], vn[CL_MLOADS] = {};
     double q[CL_MLOADS], qn[CL_MLOADS] = {};
-    cl_ms_load(ms_b, h, w, Y0, X0, v);
-    mg_q_load(dl_b, h, w, Y0, X0, co[1 + C], mpc, co[1], q);
+    cl_ms_load(ms_b, h, w, {Y0, X0}, v);
+    mg_q_load(dl_b, h, w, {Y0, X0}, co[1 + C], mpc, co[1], q);
     const int p = 2 * tid, y = Y0 + p / CL_TW, x = X0 + p % CL_TW;
     const bool in = y < H4 && x < W4;            // W4 is a multiple of 4 and x is even: both pixels or none
     const long o = (long)y * W4 + x;
@@ -622,8 +550,8 @@ __global__ __launch_bounds__(CL_NT) void k_mg_apply(const float* __restrict__ ms
     const double c0 = ((double)pp.x - pv) - mpc, c1 = ((double)pp.y - pv) - mpc;      // pan - mu
     for (int k = 0; k < C; ++k) {
         if (k + 1 < C) {
-            cl_ms_load(ms_b + (k + 1) * lp, h, w, Y0, X0, vn);
-            mg_q_load(dl_b + (F == 1 ? 0 : k + 1) * lp, h, w, Y0, X0, co[1 + C + k + 1], mpc, co[1 + k + 1], qn);
+            cl_ms_load(ms_b + (k + 1) * lp, h, w, {Y0, X0}, vn);
+            mg_q_load(dl_b + (F == 1 ? 0 : k + 1) * lp, h, w, {Y0, X0}, co[1 + C + k + 1], mpc, co[1 + k + 1], qn);
         }
         cl_up_band(v, cl_lds, U);
         cl_up_band(q, cl_lds, Lt);
@@ -642,11 +570,8 @@ __global__ __launch_bounds__(CL_NT) void k_mg_apply(const float* __restrict__ ms
             }
             *reinterpret_cast<float2*>(out_b + k * plane + o) = make_float2(cl_clip(o0), cl_clip(o1));
         }
-#pragma unroll
-        for (int u = 0; u < CL_MLOADS; ++u) {
-            v[u] = vn[u];
-            q[u] = qn[u];
-        }
+        cl_next(v, vn);
+        cl_next(q, qn);
         // no barrier: the next cl_up_band writes U and Lt in its last pass, four barriers from here
     }
 }
@@ -660,8 +585,7 @@ struct ClGeom {
 bool cl_geom(const char* who, int B, int C, int h, int w, int method, ClGeom& g) {
     if (!cl_shape(who, B, C, h, w)) return false;
     if (method != LG_CLASSICAL_SFIM && method != LG_CLASSICAL_GSA) { lg_set_error("%s: method must be LG_CLASSICAL_SFIM or LG_CLASSICAL_GSA (got %d)", who, method); return false; }
-    g.tiles_x = (4 * w + CL_TW - 1) / CL_TW;
-    g.tiles = g.tiles_x * ((4 * h + CL_TH - 1) / CL_TH);
+    g.tiles = cl_tiles(h, w, g.tiles_x);
     // the moments pass: at most as many workgroups per sample as are resident at once (768 at C = 4, 512 at C = 8, 256 at C = 16): a second,
     // partial round of workgroups would leave most of the chip idle for as long as the first took
     const int resident = CL_CUS * (CL_CU_LDS / (cl_moment_lds_doubles(C) * (int)sizeof(double) + CL_MAX_SUMS * (int)sizeof(int)));
@@ -685,13 +609,10 @@ int cl_fuse(const char* who, int method, const float* ms, const float* pan, floa
             size_t workspace_bytes, hipStream_t s) {
     ClGeom g;
     if (!cl_geom(who, B, C, h, w, method, g)) return -1;
-    if (!check_tensors(who, {{"ms", ms}, {"pan", pan}, {"out", out}})) return -1;
-    if ((uintptr_t)stats & 7) { lg_set_error("%s: stats must be 8-byte aligned", who); return -1; }
-    if (!check_workspace(who, workspace, workspace_bytes, g.bytes, "lg_classical_workspace_bytes")) return -1;
+    if (!cl_check_args(who, ms, pan, out, {}, stats, workspace, workspace_bytes, g.bytes, "lg_classical_workspace_bytes")) return -1;
     if (int rc = cl_lds_attr(who)) return rc;
     const int gsa = method == LG_CLASSICAL_GSA;
-    double* part = (double*)((char*)workspace + g.off[0]);
-    double* coef = (double*)((char*)workspace + g.off[1]);
+    double *part = cl_ws(workspace, g.off[0]), *coef = cl_ws(workspace, g.off[1]);
     k_cl_moments<<<dim3(g.gx, B), CL_NT, cl_moment_lds_doubles(C) * sizeof(double), s>>>(ms, pan, part, C, h, w, g.tiles_x, g.tiles, gsa);
     LG_CHECK_LAUNCH();
     k_cl_finish<<<B, CL_NT, 0, s>>>(part, coef, stats, C, g.gx, 16.0 * h * w, (double)h * w, gsa);
@@ -711,9 +632,19 @@ struct MgGeom {
     size_t off[4], bytes;      // part, coef, D, part2 (cbd)
 };
 
+// the two rules of the low-pass filters lg_mtf_glp and lg_bdsd take: one for all bands or one per band; an odd number of taps that fits the kernel's LDS
+bool mg_filters_ok(const char* who, int C, int n_filters) {
+    if (n_filters != 1 && n_filters != C) { lg_set_error("%s: n_filters must be 1 or C = %d (got %d)", who, C, n_filters); return false; }
+    return true;
+}
+bool mg_taps_ok(const char* who, int n_taps) {
+    if (n_taps < 1 || n_taps > MG_MAX_TAPS || !(n_taps & 1)) { lg_set_error("%s: n_taps must be odd, in 1..%d (got %d)", who, MG_MAX_TAPS, n_taps); return false; }
+    return true;
+}
+
 bool mg_geom(const char* who, int B, int C, int h, int w, int n_filters, int mode, MgGeom& g) {
     if (!cl_geom(who, B, C, h, w, LG_CLASSICAL_SFIM, g.cl)) return false;
-    if (n_filters != 1 && n_filters != C) { lg_set_error("%s: n_filters must be 1 or C = %d (got %d)", who, C, n_filters); return false; }
+    if (!mg_filters_ok(who, C, n_filters)) return false;
     if (mode != LG_MTFGLP_GLP && mode != LG_MTFGLP_HPM && mode != LG_MTFGLP_CBD) {
         lg_set_error("%s: mode must be LG_MTFGLP_GLP, LG_MTFGLP_HPM or LG_MTFGLP_CBD (got %d)", who, mode);
         return false;
@@ -730,17 +661,10 @@ int mg_fuse(const char* who, const float* ms, const float* pan, float* out, doub
             int C, int h, int w, void* workspace, size_t workspace_bytes, hipStream_t s) {
     MgGeom g;
     if (!mg_geom(who, B, C, h, w, n_filters, mode, g)) return -1;
-    if (n_taps < 1 || n_taps > MG_MAX_TAPS || !(n_taps & 1)) { lg_set_error("%s: n_taps must be odd, in 1..%d (got %d)", who, MG_MAX_TAPS, n_taps); return -1; }
-    if (!check_tensors(who, {{"ms", ms}, {"pan", pan}, {"out", out}})) return -1;
-    if (!taps) { lg_set_error("%s: taps is NULL", who); return -1; }
-    if ((uintptr_t)taps & 7) { lg_set_error("%s: taps must be 8-byte aligned", who); return -1; }
-    if ((uintptr_t)stats & 7) { lg_set_error("%s: stats must be 8-byte aligned", who); return -1; }
-    if (!check_workspace(who, workspace, workspace_bytes, g.bytes, "lg_mtfglp_workspace_bytes")) return -1;
+    if (!mg_taps_ok(who, n_taps)) return -1;
+    if (!cl_check_args(who, ms, pan, out, {{"taps", taps}}, stats, workspace, workspace_bytes, g.bytes, "lg_mtfglp_workspace_bytes")) return -1;
     if (int rc = cl_lds_attr(who)) return rc;
-    double* part = (double*)((char*)workspace + g.off[0]);
-    double* coef = (double*)((char*)workspace + g.off[1]);
-    double* dlow = (double*)((char*)workspace + g.off[2]);
-    double* part2 = (double*)((char*)workspace + g.off[3]);
+    double *part = cl_ws(workspace, g.off[0]), *coef = cl_ws(workspace, g.off[1]), *dlow = cl_ws(workspace, g.off[2]), *part2 = cl_ws(workspace, g.off[3]);
     const int tiles_x = g.cl.tiles_x, tiles = g.cl.tiles;
     k_cl_moments<<<dim3(g.cl.gx, B), CL_NT, cl_moment_lds_doubles(C) * sizeof(double), s>>>(ms, pan, part, C, h, w, tiles_x, tiles, 0);
     LG_CHECK_LAUNCH();
@@ -768,15 +692,18 @@ int mg_fuse(const char* who, const float* ms, const float* pan, float* out, doub
 // ---- BDSD: the band-dependent spatial detail method, global or per block of block x block PAN pixels.  Per block and band the weights gamma
 // are the least-squares fit of ms_k - A_k on x = [A_1 .. A_C, D] at the MS scale (A_k: the band low-passed on its own grid, D: the raw PAN low-passed at the
 // decimated positions, k_mg_lowpass's plane plus the pivot); out_k = clip(u_k + sum_j gamma_kj u_j + gamma_kC pan).
-//   k_bd_lowpass_ms  grid (tile, band, sample): A_k on 16 x 16 tiles of the MS grid, replicate border -- rows into LDS, then columns; fp64 [B, C, h, w].
+//   k_bd_lowpass_ms  grid (tile, band, sample): A_k on 16 x 16 tiles of the MS grid, replicate border -- rows into LDS, then columns; fp64 [B, C, h, w].  It is
+//                    k_mg_lowpass on the band's own grid without the pivot, and stays a kernel of its own: as two instances of one template the pair cost a
+//                    call of lg_bdsd 0.5 us at PAN 128 x 128 (HISTORY.md).
 //   k_bd_gram        grid (block x workgroup of the block, sample): a workgroup walks the block's pixels (row-major inside the block) in chunks of 256, gpb
 //                    chunks apart: the 2 C + 1 vectors [x, y] of the chunk in LDS, zero past the block's end; every entry of G = sum x x' (upper triangle) and
-//                    of r_k = sum x y_k is the sum of a product of two of them: a wave owns the entries e = wave, wave + 4, ..., sums them over the chunk and
-//                    lane 0 adds to its slot in LDS -- one order, always.  The workgroup writes its slots.
-//   k_bd_solve       one wave per block: the partials in ascending order, one thread's Cholesky of G, then thread k solves for gamma_k.  A pivot at or below
-//                    1e-12 G_jj or not finite, or a weight that is not finite, gives the block gamma = 0: its output is clip(u) bit for bit.
-//   k_bd_apply       grid (tile, sample), k_cl_apply's structure: the C bands of the tile and the weights of the tile's block in LDS (block edges are
-//                    multiples of 32: a tile lies in one block), two adjacent pixels per thread, ONE rounding, 8-byte stores.
+//                    of r_k = sum x y_k is the sum of a product of two of them, summed over the chunk in k_cl_moments's order (cl_pair_sums).  The workgroup
+//                    writes its slots.
+//   k_bd_solve       one wave per block: the partials in ascending order (cl_partials_column), one thread's Cholesky of G (cl_cholesky), then thread k solves
+//                    for gamma_k (cl_chol_solve).  A pivot at or below 1e-12 G_jj or not finite, or a weight that is not finite, gives the block gamma = 0: its
+//                    output is clip(u) bit for bit.
+//   k_bd_apply       grid (tile, sample), k_cl_apply's structure: the C bands of the tile (cl_up_bands) and the weights of the tile's block in LDS (block edges
+//                    are multiples of 32: a tile lies in one block), two adjacent pixels per thread, ONE rounding, 8-byte stores.
 // Neither u nor A is stored at PAN size.  The geometry of a sample depends on C, h, w and block only.
 constexpr int BD_CHUNK = CL_NT;                                          // MS pixels of a block a Gram workgroup takes at a time: one per thread
 constexpr int BD_MAX_N = CL_MAX_C + 1;                                   // regressors, at most
@@ -826,7 +753,7 @@ __global__ __launch_bounds__(CL_NT) void k_bd_gram(const float* __restrict__ ms,
                                                    int gpb) {
     extern __shared__ double cl_lds[];
     __shared__ int pairs[BD_MAX_NS];
-    const int n = C + 1, nv = 2 * C + 1, ns = bd_ns(C), tid = threadIdx.x, lane = tid & 63;
+    const int n = C + 1, nv = 2 * C + 1, ns = bd_ns(C), tid = threadIdx.x;
     double* V = cl_lds;                          // [nv][256]: A_0 .. A_C-1, D, y_0 .. y_C-1
     double* acc = V + nv * BD_CHUNK;             // [ns]
     const int blk = blockIdx.x / gpb, g = blockIdx.x - blk * gpb;
@@ -859,13 +786,7 @@ __global__ __launch_bounds__(CL_NT) void k_bd_gram(const float* __restrict__ ms,
             for (int v = 0; v < nv; ++v) V[v * BD_CHUNK + tid] = 0.0;
         }
         __syncthreads();
-        for (int e = tid >> 6; e < ns; e += CL_NT / 64) {
-            const int pr = pairs[e], a = pr & 255, c = (pr >> 8) & 255;
-            double v = 0.0;
-            for (int u = 0; u < live; u += 64) v = fma(V[a * BD_CHUNK + lane + u], V[c * BD_CHUNK + lane + u], v);      // past the last live wave: zeros
-            v = wave_sum(v);
-            if (lane == 0) acc[e] += v;
-        }
+        cl_pair_sums(pairs, ns, acc, [&](int a, int c, int, int lane) { return cl_lane_dot(V + a * BD_CHUNK, V + c * BD_CHUNK, lane, live); });
         __syncthreads();      // the next chunk overwrites the vectors
     }
     for (int e = tid; e < ns; e += CL_NT) part[(b * gridDim.x + blockIdx.x) * ns + e] = acc[e];
@@ -879,54 +800,16 @@ __global__ __launch_bounds__(BD_SOLVE_NT) void k_bd_solve(const double* __restri
     __shared__ int bad_pivot, bad_weight;
     const int n = C + 1, ng = n * (n + 1) / 2, ns = bd_ns(C), tid = threadIdx.x;
     const long blk = (long)blockIdx.y * gridDim.x + blockIdx.x;
-    for (int e = tid; e < ns; e += BD_SOLVE_NT) {
-        const double* __restrict__ pe = part + blk * gpb * ns + e;
-        double s = 0.0;
-        int j = 0;
-        for (; j + 8 <= gpb; j += 8) {      // eight loads in flight, added in ascending order
-            double q[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) q[u] = pe[(long)(j + u) * ns];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += q[u];
-        }
-        for (; j < gpb; ++j) s += pe[(long)j * ns];
-        sums[e] = s;
-    }
+    for (int e = tid; e < ns; e += BD_SOLVE_NT) sums[e] = cl_partials_column(part + blk * gpb * ns + e, gpb, ns);
     if (tid == 0) bad_pivot = bad_weight = 0;
     __syncthreads();
-    auto G = [&](int a, int c) { return sums[a * n - a * (a - 1) / 2 + (c - a)]; };      // a <= c
-    if (tid == 0) {
-        for (int j = 0; j < n; ++j) {
-            const double gjj = G(j, j);
-            double d = gjj;
-            for (int p = 0; p < j; ++p) d -= Lm[j * n + p] * Lm[j * n + p];
-            if (!(d > BD_PIVOT_TOL * gjj) || d - d != 0.0) { bad_pivot = 1; break; }
-            d = sqrt(d);
-            Lm[j * n + j] = d;
-            for (int i = j + 1; i < n; ++i) {
-                double s = G(j, i);
-                for (int p = 0; p < j; ++p) s -= Lm[i * n + p] * Lm[j * n + p];
-                Lm[i * n + j] = s / d;
-            }
-        }
-    }
+    auto G = [&](int i, int j) { return sums[j * n - j * (j - 1) / 2 + (i - j)]; };      // i >= j: the upper triangle, row-major, holds (j, i)
+    if (tid == 0 && !cl_cholesky(Lm, n, n, G, [](double d, double gjj) { return !(d > BD_PIVOT_TOL * gjj) || d - d != 0.0; })) bad_pivot = 1;
     __syncthreads();
     if (!bad_pivot && tid < C) {
         double* x = gam + tid * n;
-        const double* rk = sums + ng + tid * n;
         bool ok = true;
-        for (int i = 0; i < n; ++i) {
-            double s = rk[i];
-            for (int p = 0; p < i; ++p) s -= Lm[i * n + p] * x[p];
-            x[i] = s / Lm[i * n + i];
-        }
-        for (int i = n - 1; i >= 0; --i) {
-            double s = x[i];
-            for (int p = i + 1; p < n; ++p) s -= Lm[p * n + i] * x[p];
-            x[i] = s / Lm[i * n + i];
-            ok = ok && x[i] - x[i] == 0.0;
-        }
+        cl_chol_solve(Lm, n, n, sums + ng + tid * n, x, [&](double xi) { ok = ok && xi - xi == 0.0; });
         if (!ok) bad_weight = 1;
     }
     __syncthreads();
@@ -944,9 +827,8 @@ __global__ __launch_bounds__(CL_NT) void k_bd_apply(const float* __restrict__ ms
     double* U = cl_lds + CL_SCRATCH;             // [C][512]
     double* Gm = U + C * CL_PX;                  // [C][C + 1]: the weights of the tile's block
     const int tid = threadIdx.x, H4 = 4 * h, W4 = 4 * w, n = C + 1;
-    const int Y0 = (blockIdx.x / tiles_x) * CL_TH, X0 = (blockIdx.x % tiles_x) * CL_TW;
+    const auto [Y0, X0] = cl_tile(blockIdx.x, tiles_x);
     const long b = blockIdx.y, lp = (long)h * w, plane = (long)H4 * W4;
-    const float* __restrict__ ms_b = ms + b * C * lp;
     const float* __restrict__ pan_b = pan + b * plane;
     float* __restrict__ out_b = out + b * C * plane;
     const int blk = block ? (Y0 / block) * nbx + X0 / block : 0;
@@ -957,14 +839,7 @@ __global__ __launch_bounds__(CL_NT) void k_bd_apply(const float* __restrict__ ms
     const long o = (long)y * W4 + x;
     float2 pp = make_float2(0.f, 0.f);
     if (in) pp = *reinterpret_cast<const float2*>(pan_b + o);
-    float v[CL_MLOADS], vn[CL_MLOADS] = {};
-    cl_ms_load(ms_b, h, w, Y0, X0, v);
-    for (int k = 0; k < C; ++k) {
-        if (k + 1 < C) cl_ms_load(ms_b + (k + 1) * lp, h, w, Y0, X0, vn);
-        cl_up_band(v, cl_lds, U + k * CL_PX);
-#pragma unroll
-        for (int u = 0; u < CL_MLOADS; ++u) v[u] = vn[u];
-    }
+    cl_up_bands(ms + b * C * lp, lp, C, h, w, Y0, X0, cl_lds, U);
     __syncthreads();
     if (!in) return;
     const double p0 = (double)pp.x, p1 = (double)pp.y;
@@ -996,8 +871,7 @@ bool bd_geom(const char* who, int B, int C, int h, int w, int block, BdGeom& g) 
         if ((4 * h) % block || (4 * w) % block) { lg_set_error("%s: block must divide 4 h = %d and 4 w = %d (got %d)", who, 4 * h, 4 * w, block); return false; }
         g.bh = g.bw = block / 4;
     }
-    g.tiles_x = (4 * w + CL_TW - 1) / CL_TW;
-    g.tiles = g.tiles_x * ((4 * h + CL_TH - 1) / CL_TH);
+    g.tiles = cl_tiles(h, w, g.tiles_x);
     g.nbx = w / g.bw;
     g.nblocks = g.nbx * (h / g.bh);
     const int chunks = (g.bh * g.bw + BD_CHUNK - 1) / BD_CHUNK, cap = BD_GRAM_WGS / g.nblocks > 1 ? BD_GRAM_WGS / g.nblocks : 1;
@@ -1021,20 +895,11 @@ int bd_fuse(const char* who, const float* ms, const float* pan, float* out, doub
             int n_taps, int block, int B, int C, int h, int w, void* workspace, size_t workspace_bytes, hipStream_t s) {
     BdGeom g;
     if (!bd_geom(who, B, C, h, w, block, g)) return -1;
-    if (n_filters != 1 && n_filters != C) { lg_set_error("%s: n_filters must be 1 or C = %d (got %d)", who, C, n_filters); return -1; }
-    if (n_taps < 1 || n_taps > MG_MAX_TAPS || !(n_taps & 1)) { lg_set_error("%s: n_taps must be odd, in 1..%d (got %d)", who, MG_MAX_TAPS, n_taps); return -1; }
-    if (!check_tensors(who, {{"ms", ms}, {"pan", pan}, {"out", out}})) return -1;
-    if (!taps_ms) { lg_set_error("%s: taps_ms is NULL", who); return -1; }
-    if (!taps_pan) { lg_set_error("%s: taps_pan is NULL", who); return -1; }
-    if ((uintptr_t)taps_ms & 7) { lg_set_error("%s: taps_ms must be 8-byte aligned", who); return -1; }
-    if ((uintptr_t)taps_pan & 7) { lg_set_error("%s: taps_pan must be 8-byte aligned", who); return -1; }
-    if ((uintptr_t)stats & 7) { lg_set_error("%s: stats must be 8-byte aligned", who); return -1; }
-    if (!check_workspace(who, workspace, workspace_bytes, g.bytes, "lg_bdsd_workspace_bytes")) return -1;
+    if (!mg_filters_ok(who, C, n_filters) || !mg_taps_ok(who, n_taps)) return -1;
+    if (!cl_check_args(who, ms, pan, out, {{"taps_ms", taps_ms}, {"taps_pan", taps_pan}}, stats, workspace, workspace_bytes, g.bytes, "lg_bdsd_workspace_bytes"))
+        return -1;
     if (int rc = bd_lds_attr(who)) return rc;
-    double* dlow = (double*)((char*)workspace + g.off[0]);
-    double* alow = (double*)((char*)workspace + g.off[1]);
-    double* part = (double*)((char*)workspace + g.off[2]);
-    double* gamma = (double*)((char*)workspace + g.off[3]);
+    double *dlow = cl_ws(workspace, g.off[0]), *alow = cl_ws(workspace, g.off[1]), *part = cl_ws(workspace, g.off[2]), *gamma = cl_ws(workspace, g.off[3]);
     const int lt_x = (w + MG_TO - 1) / MG_TO, lt = lt_x * ((h + MG_TO - 1) / MG_TO);
     k_mg_lowpass<<<dim3(lt, 1, B), CL_NT, 0, s>>>(pan, taps_pan, dlow, h, w, n_taps, lt_x);
     LG_CHECK_LAUNCH();

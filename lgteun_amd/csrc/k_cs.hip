@@ -16,13 +16,13 @@
 //                  pixels and q over its outputs: three partials per tile.
 //   k_cs_gram      grid (gx, sample), gx = min(tiles, 512); a workgroup walks the 16 x 16 tiles of the MS grid gx apart: per band the 48 x 48 samples of ms'
 //                  around the tile (modulo h, w), the 33 taps of R along x, then along y -> v_l; then every sum the method needs is the sum of a product of
-//                  two of the vectors {ms'_k} x {v_l (l >= k), q, 1} over the tile: a wave owns the entries e = wave, wave + 4, ..., sums them over the tile and
-//                  lane 0 adds to its slot in LDS -- one order, always.  The workgroup writes its slots.
+//                  two of the vectors {ms'_k} x {v_l (l >= k), q, 1} over the tile, summed in k_cl_moments's order (cl_pair_sums, classical_tiles.h).  The
+//                  workgroup writes its slots.
 //   k_cs_finish    one workgroup per sample: the partials in a fixed order (a wave per sum), then one thread: the centred moments, the method's w (PCA:
 //                  a cyclic Jacobi eigen-solve of Sigma in fp64 by the whole workgroup, at most 30 sweeps, until the off-diagonal squares fall below 1e-32 of the
 //                  diagonal's), then
 //                  a, g and the degenerate flag into coef and, on request, stats.
-//   k_cs_apply     grid (tile, sample), k_cl_apply's structure: the C bands of the 16 x 32 output tile by cl_up_band, I accumulated over the bands, the additive
+//   k_cs_apply     grid (tile, sample), k_cl_apply's structure: the C bands of the 16 x 32 output tile by cl_up_bands, I accumulated over the bands, the additive
 //                  or the multiplicative rule in fp64 with ONE rounding to fp32; two adjacent pixels per thread: 8-byte stores.
 // No atomics; a workgroup sees one sample and the grid of a sample depends on C, h and w only, so a sample has the same bits alone and inside any batch.
 // All indexing into tensors is 64-bit.  Nothing is allocated, nothing synchronises.
@@ -191,16 +191,16 @@ __global__ __launch_bounds__(CL_NT) void k_cs_gram(const float* __restrict__ ms,
     double* X = rf + CS_GH * (CS_GT + 1);        // [C][256]: ms'_k, 0 outside the image
     double* Y = X + C * CS_GPX;                  // [C + 1][256]: v_l, then q
     double* acc = Y + (C + 1) * CS_GPX;          // [ns]
-    const int tid = threadIdx.x, lane = tid & 63, gx = gridDim.x, ns = cs_ns(C);
+    const int tid = threadIdx.x, gx = gridDim.x, ns = cs_ns(C);
     const long b = blockIdx.y, lp = (long)h * w;
     const float* __restrict__ ms_b = ms + b * C * lp;
     const double* __restrict__ q_b = qlow + b * lp;
     if (tid == 0) {
         int e = 0;
         for (int k = 0; k < C; ++k)
-            for (int l = k; l < C; ++l) pairs[e++] = k | (l << 8);
-        for (int k = 0; k < C; ++k) pairs[e++] = k | (C << 8);
-        for (int k = 0; k < C; ++k) pairs[e++] = k | (255 << 8);
+            for (int l = k; l < C; ++l) pairs[e++] = cl_pair(k, l, 0);
+        for (int k = 0; k < C; ++k) pairs[e++] = cl_pair(k, C, 0);
+        for (int k = 0; k < C; ++k) pairs[e++] = cl_pair(k, 255, 0);      // 255: the plain sum of ms'_k
     }
     for (int e = tid; e < ns; e += CL_NT) acc[e] = 0.0;
     // (the barriers of the first band order both before their first use)
@@ -245,17 +245,13 @@ __global__ __launch_bounds__(CL_NT) void k_cs_gram(const float* __restrict__ ms,
         }
         Y[C * CS_GPX + tid] = in ? q_b[(long)(i0 + ly) * w + j0 + lx] : 0.0;
         __syncthreads();
-        for (int e = tid >> 6; e < ns; e += CL_NT / 64) {
-            const int pr = pairs[e], k = pr & 255, l = pr >> 8;
+        cl_pair_sums(pairs, ns, acc, [&](int k, int l, int, int lane) {
+            if (l != 255) return cl_lane_dot<CS_GPX>(X + k * CS_GPX, Y + l * CS_GPX, lane);
             double v = 0.0;
 #pragma unroll
-            for (int u = 0; u < CS_GPX / 64; ++u) {
-                const double x = X[k * CS_GPX + lane + 64 * u];
-                v = l == 255 ? v + x : fma(x, Y[l * CS_GPX + lane + 64 * u], v);
-            }
-            v = wave_sum(v);
-            if (lane == 0) acc[e] += v;
-        }
+            for (int u = 0; u < CS_GPX / 64; ++u) v += X[k * CS_GPX + lane + 64 * u];
+            return v;
+        });
         __syncthreads();      // the next tile overwrites the vectors
     }
     for (int e = tid; e < ns; e += CL_NT) part[(b * ns + e) * gx + blockIdx.x] = acc[e];
@@ -412,21 +408,13 @@ __global__ __launch_bounds__(CL_NT) void k_cs_apply(const float* __restrict__ ms
     extern __shared__ double cs_lds[];
     double* U = cs_lds + CL_SCRATCH;             // [C][512]
     const int tid = threadIdx.x, H4 = 4 * h, W4 = 4 * w;
-    const int Y0 = (blockIdx.x / tiles_x) * CL_TH, X0 = (blockIdx.x % tiles_x) * CL_TW;
-    const long b = blockIdx.y, plane = (long)H4 * W4;
-    const float* __restrict__ ms_b = ms + b * C * ((long)h * w);
+    const auto [Y0, X0] = cl_tile(blockIdx.x, tiles_x);
+    const long b = blockIdx.y, lp = (long)h * w, plane = (long)H4 * W4;
     const float* __restrict__ pan_b = pan + b * plane;
     float* __restrict__ out_b = out + b * C * plane;
     const double* __restrict__ co = coef + b * (CS_COEF + 3 * C);
     const double pv = (double)pan_b[0];
-    float v[CL_MLOADS], vn[CL_MLOADS] = {};
-    cl_ms_load(ms_b, h, w, Y0, X0, v);
-    for (int k = 0; k < C; ++k) {
-        if (k + 1 < C) cl_ms_load(ms_b + (k + 1) * ((long)h * w), h, w, Y0, X0, vn);
-        cl_up_band(v, cs_lds, U + k * CL_PX);
-#pragma unroll
-        for (int u = 0; u < CL_MLOADS; ++u) v[u] = vn[u];
-    }
+    cl_up_bands(ms + b * C * lp, lp, C, h, w, Y0, X0, cs_lds, U);
     __syncthreads();
     const int p = 2 * tid, y = Y0 + p / CL_TW, x = X0 + p % CL_TW;
     if (y >= H4 || x >= W4) return;              // W4 is a multiple of 4 and x is even: both pixels or none
@@ -467,8 +455,7 @@ bool cs_geom(const char* who, int B, int C, int h, int w, CsGeom& g) {
     g.at = g.at_x * ((h + CS_AT - 1) / CS_AT);
     g.gx = g.at < CS_GRAM_WGS ? g.at : CS_GRAM_WGS;
     g.ns = cs_ns(C);
-    g.tiles_x = (4 * w + CL_TW - 1) / CL_TW;
-    g.tiles = g.tiles_x * ((4 * h + CL_TH - 1) / CL_TH);
+    g.tiles = cl_tiles(h, w, g.tiles_x);
     const size_t sz[4] = {(size_t)B * h * w * sizeof(double), ws_region(B, (size_t)3 * g.at * sizeof(double)),
                           ws_region(B, (size_t)g.ns * g.gx * sizeof(double)), ws_region(B, (size_t)(CS_COEF + 3 * C) * sizeof(double))};
     g.bytes = ws_layout(4, sz, g.off);
@@ -506,15 +493,10 @@ extern "C" int lg_cs(const float* ms, const float* pan, float* out, double* stat
         wt.w[k] = weights ? weights[k] : 1.0 / C;
         if (wt.w[k] - wt.w[k] != 0.0) { lg_set_error("%s: weights[%d] must be finite", who, k); return -1; }
     }
-    if (!check_tensors(who, {{"ms", ms}, {"pan", pan}, {"out", out}})) return -1;
-    if ((uintptr_t)stats & 7) { lg_set_error("%s: stats must be 8-byte aligned", who); return -1; }
-    if (!check_workspace(who, workspace, workspace_bytes, g.bytes, "lg_cs_workspace_bytes")) return -1;
+    if (!cl_check_args(who, ms, pan, out, {}, stats, workspace, workspace_bytes, g.bytes, "lg_cs_workspace_bytes")) return -1;
     if (int rc = cs_lds_attr(who)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    double* qlow = (double*)((char*)workspace + g.off[0]);
-    double* part1 = (double*)((char*)workspace + g.off[1]);
-    double* part2 = (double*)((char*)workspace + g.off[2]);
-    double* coef = (double*)((char*)workspace + g.off[3]);
+    double *qlow = cl_ws(workspace, g.off[0]), *part1 = cl_ws(workspace, g.off[1]), *part2 = cl_ws(workspace, g.off[2]), *coef = cl_ws(workspace, g.off[3]);
     k_cs_adjoint<<<dim3(g.at, B), CL_NT, 0, s>>>(pan, qlow, part1, h, w, g.at_x, g.at);
     LG_CHECK_LAUNCH();
     k_cs_gram<<<dim3(g.gx, B), CL_NT, cs_gram_lds_doubles(C) * sizeof(double), s>>>(ms, qlow, part2, C, h, w, g.at_x, g.at);
