@@ -230,7 +230,8 @@ struct Ffn1BwdArgs {
     // e <= 32: the first conv's weight / bias gradient (dW1 = sum_p dh1 (x) LN2(x), db1 = sum_p dh1) is accumulated in this
     // kernel (dh1 and LN2(x) are already on chip), so dh1 / y2 never go to HBM: w1slab = FFN1_BWD_WGS * (4e*e + 4e) floats
     float *w1slab, *d_w1, *d_b1;
-    // e = 16 with pre-activation saves: dW2 / db2 as well (gelu(h1) is evaluated here): w2slab = FFN1_BWD_WGS * (4e*4e + 4e) floats
+    // unused (null): dW2 / db2 come from k_wgrad_t.  Tried: accumulated here in the pre-activation mode at e = 16, 64 extra f32 MFMAs per chunk: 7.51 against
+    // 7.43 ms per step, slower.  The fields keep the kernel-argument layout.
     float *w2slab, *d_w2, *d_b2;
     long P;
     int hbf;           // hidden storage: 0 fp32, 1 bf16
@@ -242,10 +243,6 @@ struct Ffn1BwdArgs {
 };
 #define FFN1_BWD_WGS 512   // persistent grid cap of k_ffn1_bwd
 inline bool ffn1_bwd_fuses_w1(int e) { return e <= 32; }
-#ifndef LG_FW2
-#define LG_FW2 0   // 1: k_ffn1_bwd accumulates dW2 itself in the pre-activation mode (64 extra f32 MFMAs per chunk: 7.51 ms against 7.43 with dW2 from k_wgrad_t, gelu evaluated on its X operand)
-#endif
-inline bool ffn1_bwd_fuses_w2(int e, int pre) { return LG_FW2 && pre && e == 16; }
 int launch_ffn1_bwd(int e, Ffn1BwdKernel k, const Ffn1BwdArgs& a, hipStream_t s);   // k: FFN1_BWD_TILE | FFN1_BWD_X32 (route.h)
 int launch_ffn1_bwd_x32(const Ffn1BwdArgs& a, const float* w1, void* wsplit, hipStream_t s);   // k_ffn1_bwd_x32.hip
 // e = 16 | 32 (k_ffn_bwd_x.hip): everything that hangs off dh2 in ONE pass on the bf16 matrix pipe (split arithmetic) --
@@ -375,10 +372,7 @@ struct AttnBwdArgs {
     int core_m = 0;     // 1 (lg_config.variant LG_VAR_ATTN_BWD_CORE_M): the matrix-pipe core k_attn_bwd_core_m at e = 32 instead of the vector-pipe k_attn_bwd_core
 };
 int launch_attn_bwd_core_m(int e, const AttnBwdArgs& a, int grid, int nwin, int ngroups, hipStream_t s);   // k_attn_bwd_m.hip
-#ifndef LG_ATTN_FUSE_QKV
-#define LG_ATTN_FUSE_QKV 1
-#endif
-constexpr bool attn_bwd_fuses_qkv(int e) { return LG_ATTN_FUSE_QKV && e == 16; }
+constexpr bool attn_bwd_fuses_qkv(int e) { return e == 16; }
 inline size_t attn_bwd_part_floats(int e) { return (size_t)PIXEL_PART_WGS * 2 * e + (attn_bwd_fuses_qkv(e) ? (size_t)1024 * ((3 * e / 2) * (e / 2) + 3 * e / 2) : 0); }
 int attn_bwd_grid(int e, int B, int h, int w);
 int launch_attn_bwd(int e, const AttnBwdArgs& a, hipStream_t s);
@@ -398,9 +392,7 @@ struct ProjO2BwdKArgs {
     long total;
     uint64_t seed;
 };
-#ifndef PROJ_O2_K_WGS
-#define PROJ_O2_K_WGS 512   // 1 024 workgroups: the same kernel time, but the bias-gradient reduce job behind it walks twice the slices (step 6.31 -> 6.285 ms)
-#endif
+constexpr int PROJ_O2_K_WGS = 512;   // 1 024 workgroups: the same kernel time, but the bias-gradient reduce job behind it walks twice the slices (step 6.31 -> 6.285 ms)
 int launch_proj_o2_bwd_k(int e, const ProjO2BwdKArgs& a, hipStream_t s);
 struct AttnBwdFArgs {
     const float* x;        // [P,e] block input

@@ -42,29 +42,19 @@ extern "C" __attribute__((visibility("default"))) int lg_debug_kf_stamps(unsigne
 #define STAMP(i) do { } while (0)
 #endif
 
-#ifndef LG_ATTNF_SB
-#define LG_ATTNF_SB 2   // a scheduling fence behind every LG_ATTNF_SB-th key / query group of the flash passes (0: none).  Same-box A/B of the kernel's
-                        // average launch: none 140.5 us, every group 123.3, every 2nd 122.9 (kept), every 4th 128.9, every 8th 130.3
-#endif
-#ifndef LG_ATTNF_DPP
-#define LG_ATTNF_DPP 0    // A/B build (-DLG_ATTNF_DPP=1): broadcast operands of the recomputing flash passes through DPP row broadcasts instead of wave-uniform LDS reads.
-                          // Measured SLOWER (142.7 against 124.7 us): a DPP multiply-add issues at the 4-cycle rate of the SDWA / conversion class and does ONE
-                          // multiply-add per lane where v_pk_fma_f32 does two in 4.7 cycles -- the LDS pipe was relieved, the vector pipe got twice the work
-#endif
-#ifndef LG_ATTNF_PRIO
-#define LG_ATTNF_PRIO 1
-#endif
-// (one opaque asm statement with its own scalar branch inside: as a C++ `if` around two s_setprio builtins the basic block was split in front of each pass and the
-// register allocator spilled 470 registers)
-#define ATTNF_PRIO(lead) do { if (LG_ATTNF_PRIO) asm volatile("s_cmp_lg_u32 %0, 0\n\ts_cbranch_scc1 1f\n\ts_setprio 0\n\ts_branch 2f\n1:\ts_setprio 3\n2:" :: "s"(__builtin_amdgcn_readfirstlane((int)(lead))) : "scc"); } while (0)
-#define PASS_FENCE(g) do { if (LG_ATTNF_SB && ((g) % LG_ATTNF_SB) == LG_ATTNF_SB - 1) __builtin_amdgcn_sched_barrier(0); } while (0)
 namespace {
-#ifndef LG_ATTNF_NS
-#define LG_ATTNF_NS 4   // window slots per workgroup: 4 = one 8-wave workgroup per CU (155 KB of LDS); 2 = 4-wave workgroups, TWO per CU (81 KB each), so that
-                        // one workgroup's prologue / epilogue could run beside the other's flash passes -- measured 142.8 vs 135.8 us: the kernel is
-                        // vector-issue bound in EVERY phase (stamps: a window group costs 33 k ticks either way), decoupling the phases buys nothing
-#endif
-constexpr int F_HC = 8, F_E = 16, F_D = 4, F_NS = LG_ATTNF_NS, F_NW = 2 * F_NS, F_NT = 64 * F_NW;
+// wave priority 3 for the waves that lead a pass, 0 for the others (one opaque asm statement with its own scalar branch inside: as a C++ `if` around two s_setprio
+// builtins the basic block was split in front of each pass and the register allocator spilled 470 registers)
+__device__ __forceinline__ void pass_prio(bool lead) {
+    asm volatile("s_cmp_lg_u32 %0, 0\n\ts_cbranch_scc1 1f\n\ts_setprio 0\n\ts_branch 2f\n1:\ts_setprio 3\n2:" :: "s"(__builtin_amdgcn_readfirstlane((int)lead)) : "scc");
+}
+constexpr int F_SB = 2;   // a scheduling fence behind every F_SB-th key / query group of the flash passes (0: none).  Same-box A/B of the kernel's
+                          // average launch: none 140.5 us, every group 123.3, every 2nd 122.9 (kept), every 4th 128.9, every 8th 130.3
+#define PASS_FENCE(g) do { if (F_SB && ((g) % F_SB) == F_SB - 1) __builtin_amdgcn_sched_barrier(0); } while (0)
+constexpr int F_NS = 4;   // window slots per workgroup: 4 = one 8-wave workgroup per CU (155 KB of LDS).  Tried: 2 = 4-wave workgroups, two per CU (81 KB each):
+                          // 142.8 vs 135.8 us, the kernel is vector-issue bound in EVERY phase (stamps: a window group costs 33 k ticks either way)
+// (tried: the flash passes' broadcast operands through DPP row broadcasts instead of wave-uniform LDS reads: 142.7 against 124.7 us, slower)
+constexpr int F_HC = 8, F_E = 16, F_D = 4, F_NW = 2 * F_NS, F_NT = 64 * F_NW;
 constexpr int F_PLD = 68;                       // padded pos_emb row (16-byte aligned): lane = query reads its row as 16-byte pieces, lane = key a column;
                                                 // both conflict-free (68 = 4 mod 64: the 16 lanes of a ds_read_b128 group sit 4 banks apart)
 constexpr int F_Y1LD = 12;                      // [y1 (8) | 1 | 0 0 0] per token: B operand of the to_qkv weight-gradient product
@@ -85,7 +75,7 @@ constexpr int F_LOOP_FLOATS = F_OFF_SLOT + F_NS * F_PS;
 constexpr int F_DPW = 64 * 65;                  // write-out: a wave's pos_emb-gradient columns [i][65] ...
 constexpr int F_OUT_FLOATS = F_NW * F_DPW + F_NW * (32 + 512);   // ... + its LayerNorm sums [32] and the two MFMA accumulators [256] each
 constexpr int F_LDS_FLOATS = F_LOOP_FLOATS > F_OUT_FLOATS ? F_LOOP_FLOATS : F_OUT_FLOATS;
-static_assert(F_LDS_FLOATS * 4 <= (F_NS == 2 ? 80 : 160) * 1024, "LDS budget: two workgroups per CU at F_NS = 2");
+static_assert(F_LDS_FLOATS * 4 <= 160 * 1024, "LDS budget");
 static_assert(F_OFF_WAVE % 4 == 0 && F_PW % 4 == 0 && F_PS % 4 == 0, "16-byte alignment of the LDS regions");
 
 __device__ __forceinline__ float dpp_xor1(float v) {   // the other lane of the token's pair
@@ -108,30 +98,6 @@ __device__ __forceinline__ float row8_sum(float v) {
     v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x128, 0xF, 0xF, true));   // row_ror:8
     return v;
 }
-// Lane-broadcast operands (round 6).  In the flash passes every lane needs the SAME k / v (pass 1) or q / dO / row statistics (pass 2) of one token per
-// multiply-add.  Read from LDS those are wave-uniform 16-byte reads: 64 lanes x 16 bytes through a 128-byte port = 8 cycles of the CU's ONE LDS pipe for 16
-// useful bytes, ~450 of them per wave and window -- 8 waves x 3.6 k cycles = 29 k of a window group's 33.7 k cycles (SQ counters: 62 % LDS-busy, 56 %
-// vector-busy; profiles/r06_sq_counters_step.txt).  Here a lane keeps the values of the four tokens 16 r + (lane & 15) in registers (one conflict-free
-// ds_read_b32 each) and the multiply-adds take them through the DPP row broadcast of gfx90a+ (row_newbcast:n = lane n of the reader's own 16-lane row):
-// the same fused multiply-adds in the same order, as plain instead of packed fp32 (same issue rate on this chip), and no LDS traffic.
-// DPP hazard (2 wait states between a VALU write of a register and its use as the DPP source): the broadcast sources are only ever registers loaded from
-// LDS a phase earlier; tools/check_dpp_hazards.py verifies it on the assembly.
-template <int N> __device__ __forceinline__ float fmac_bc(float acc, float src, float b) {   // acc + src[lane N of the row] * b
-    asm("v_fmac_f32_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(b), "n"(N));
-    return acc;
-}
-template <int N> __device__ __forceinline__ float sub_bc(float a, float src) {               // a - src[lane N of the row]
-    float d;
-    asm("v_subrev_f32_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "=v"(d) : "v"(src), "v"(a), "n"(N));
-    return d;
-}
-template <int N> __device__ __forceinline__ float mul_bc(float a, float src) {               // a * src[lane N of the row]
-    float d;
-    asm("v_mul_f32_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "=v"(d) : "v"(src), "v"(a), "n"(N));
-    return d;
-}
-template <class F, int... Is> __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, Is...>) { (f(std::integral_constant<int, Is>{}), ...); }
-template <int N, class F> __device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 __device__ __forceinline__ float dpp_even(float v) {   // the even lane's value on both lanes of the pair
     return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xA0, 0xF, 0xF, true));   // quad_perm [0,0,2,2]
 }
@@ -328,9 +294,9 @@ __global__ __launch_bounds__(F_NT) __attribute__((amdgpu_waves_per_eu(2))) void 
         lds_barrier();   // B1: the tiles of every wave are complete
         STAMP(2);
         // The two waves of a SIMD (wave w and w + 4: slots of different windows) are not served alike: the arbiter issues the OLDER one first (stamps of round 4: pass 1
-        // takes waves 0 - 3 10 k cycles and waves 4 - 7 13.4 k, and the first four then wait 5.8 k at the barrier).  LG_ATTNF_PRIO: the older half leads in pass 1, the
+        // takes waves 0 - 3 10 k cycles and waves 4 - 7 13.4 k, and the first four then wait 5.8 k at the barrier).  pass_prio: the older half leads in pass 1, the
         // younger half in pass 2 -- each wave has the SIMD for one of the two long passes and both halves reach the barrier together.
-        ATTNF_PRIO(uw < 4);
+        pass_prio(uw < 4);
         float dqkv[12];
         {
             // ---------------- pass 1: lane = query i, packed over KEY pairs (as k_attn_bwd_core)
@@ -374,84 +340,6 @@ __global__ __launch_bounds__(F_NT) __attribute__((amdgpu_waves_per_eu(2))) void 
 #pragma unroll
                 for (int c = 0; c < D; ++c) dqkv[c] = (dq2[c].x + dq2[c].y) * scale;
             } else {
-#if LG_ATTNF_DPP
-            const int l15 = lane & 15;
-            float Kr[4][D], Vr[4][D];   // [r][c] = k / v channel c of token 16 r + (lane & 15)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int c = 0; c < D; ++c) { Kr[r][c] = sK[c * 64 + 16 * r + l15]; Vr[r][c] = sV[c * 64 + 16 * r + l15]; }
-            const float* prow = sPosH + lane * PLD;
-            float sc[64];
-            float mx = -3.0e38f;
-            static_for<16>([&](auto gg) {
-                constexpr int g = decltype(gg)::value, r = g >> 2, n0 = 4 * (g & 3);
-                const float4 pr4 = reinterpret_cast<const float4*>(prow)[g];
-                float s0 = pr4.x, s1 = pr4.y, s2 = pr4.z, s3 = pr4.w;
-#pragma unroll
-                for (int c = 0; c < D; ++c) {
-                    s0 = fmac_bc<n0>(s0, Kr[r][c], q[c]);
-                    s1 = fmac_bc<n0 + 1>(s1, Kr[r][c], q[c]);
-                    s2 = fmac_bc<n0 + 2>(s2, Kr[r][c], q[c]);
-                    s3 = fmac_bc<n0 + 3>(s3, Kr[r][c], q[c]);
-                }
-                sc[4 * g] = s0; sc[4 * g + 1] = s1; sc[4 * g + 2] = s2; sc[4 * g + 3] = s3;
-                mx = fmaxf(mx, fmaxf(fmaxf(s0, s1), fmaxf(s2, s3)));
-                PASS_FENCE(g);
-            });
-            float le = 0.f, lo = 0.f;   // even / odd keys: the two halves of the packed sum of rounds 4 - 5 (same additions in the same order)
-#pragma unroll
-            for (int k = 0; k < 32; ++k) {
-                sc[2 * k] = __builtin_amdgcn_exp2f(sc[2 * k] - mx);
-                sc[2 * k + 1] = __builtin_amdgcn_exp2f(sc[2 * k + 1] - mx);
-                le += sc[2 * k]; lo += sc[2 * k + 1];
-            }
-            const float inv = __builtin_amdgcn_rcpf(le + lo);
-            float Oe[D], Oo[D];
-#pragma unroll
-            for (int c = 0; c < D; ++c) { Oe[c] = 0.f; Oo[c] = 0.f; }
-            static_for<16>([&](auto gg) {
-                constexpr int g = decltype(gg)::value, r = g >> 2, n0 = 4 * (g & 3);
-                sc[4 * g] *= inv; sc[4 * g + 1] *= inv; sc[4 * g + 2] *= inv; sc[4 * g + 3] *= inv;
-#pragma unroll
-                for (int c = 0; c < D; ++c) {
-                    Oe[c] = fmac_bc<n0>(Oe[c], Vr[r][c], sc[4 * g]);
-                    Oo[c] = fmac_bc<n0 + 1>(Oo[c], Vr[r][c], sc[4 * g + 1]);
-                    Oe[c] = fmac_bc<n0 + 2>(Oe[c], Vr[r][c], sc[4 * g + 2]);
-                    Oo[c] = fmac_bc<n0 + 3>(Oo[c], Vr[r][c], sc[4 * g + 3]);
-                }
-                PASS_FENCE(g);
-            });
-            float O[D];
-            float Dv = 0.f;   // D_i = sum_j P_ij dP_ij = dO_i . O_i
-#pragma unroll
-            for (int c = 0; c < D; ++c) { O[c] = Oe[c] + Oo[c]; Dv += dOi[c] * O[c]; }
-            float dqe[D], dqo[D];
-#pragma unroll
-            for (int c = 0; c < D; ++c) { dqe[c] = 0.f; dqo[c] = 0.f; }
-            static_for<16>([&](auto gg) {
-                constexpr int g = decltype(gg)::value, r = g >> 2, n0 = 4 * (g & 3);
-                float dP0 = 0.f, dP1 = 0.f, dP2 = 0.f, dP3 = 0.f;
-#pragma unroll
-                for (int c = 0; c < D; ++c) {
-                    dP0 = fmac_bc<n0>(dP0, Vr[r][c], dOi[c]);
-                    dP1 = fmac_bc<n0 + 1>(dP1, Vr[r][c], dOi[c]);
-                    dP2 = fmac_bc<n0 + 2>(dP2, Vr[r][c], dOi[c]);
-                    dP3 = fmac_bc<n0 + 3>(dP3, Vr[r][c], dOi[c]);
-                }
-                const float dS0 = sc[4 * g] * (dP0 - Dv), dS1 = sc[4 * g + 1] * (dP1 - Dv), dS2 = sc[4 * g + 2] * (dP2 - Dv), dS3 = sc[4 * g + 3] * (dP3 - Dv);
-#pragma unroll
-                for (int c = 0; c < D; ++c) {
-                    dqe[c] = fmac_bc<n0>(dqe[c], Kr[r][c], dS0);
-                    dqo[c] = fmac_bc<n0 + 1>(dqo[c], Kr[r][c], dS1);
-                    dqe[c] = fmac_bc<n0 + 2>(dqe[c], Kr[r][c], dS2);
-                    dqo[c] = fmac_bc<n0 + 3>(dqo[c], Kr[r][c], dS3);
-                }
-                PASS_FENCE(g);
-            });
-#pragma unroll
-            for (int c = 0; c < D; ++c) dqkv[c] = (dqe[c] + dqo[c]) * scale;
-#else
             const float* prow = sPosH + lane * PLD;
             lg_v2f sc[32];
             float mx = -3.0e38f;
@@ -467,39 +355,24 @@ __global__ __launch_bounds__(F_NT) __attribute__((amdgpu_waves_per_eu(2))) void 
                     sp1 = qq * (lg_v2f){kv.z, kv.w} + sp1;
                 }
                 sc[2 * g] = sp0; sc[2 * g + 1] = sp1;
-#ifndef LG_ATTNF_DIAG_FWDSTATS
                 mx = fmaxf(mx, fmaxf(fmaxf(sp0.x, sp0.y), fmaxf(sp1.x, sp1.y)));
-#endif
                 PASS_FENCE(g);
             }
             asm volatile("" ::: "memory");
-#ifdef LG_ATTNF_DIAG_FWDSTATS
-            // TIMING-ONLY diagnostic (never in the product build; results are wrong): what pass 1 would cost if the forward had saved the rows'
-            // log-sum-exp and the attention output (VERDICT r5 lever a, "light" form): no row maximum, no row sum, no normalisation, no P V
-            mx = q[0];
-#endif
             lg_v2f l2 = (lg_v2f){0.f, 0.f};
             const lg_v2f mx2 = (lg_v2f){mx, mx};
 #pragma unroll
             for (int g = 0; g < 32; ++g) {
                 const lg_v2f t = sc[g] - mx2;
                 sc[g] = (lg_v2f){__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
-#ifndef LG_ATTNF_DIAG_FWDSTATS
                 l2 += sc[g];
-#endif
             }
-#ifdef LG_ATTNF_DIAG_FWDSTATS
-            l2 = (lg_v2f){dOi[0], dOi[1]};
-#endif
             const float inv = __builtin_amdgcn_rcpf(l2.x + l2.y);
             const lg_v2f inv2 = (lg_v2f){inv, inv};
             lg_v2f O2[D];
 #pragma unroll
             for (int c = 0; c < D; ++c) O2[c] = (lg_v2f){0.f, 0.f};
 #pragma unroll
-#ifdef LG_ATTNF_DIAG_FWDSTATS
-            for (int c = 0; c < D; ++c) O2[c] = (lg_v2f){q[c] * inv, dOi[c]};
-#else
             for (int g = 0; g < 16; ++g) {
                 sc[2 * g] *= inv2; sc[2 * g + 1] *= inv2;
 #pragma unroll
@@ -510,7 +383,6 @@ __global__ __launch_bounds__(F_NT) __attribute__((amdgpu_waves_per_eu(2))) void 
                 }
                 PASS_FENCE(g);
             }
-#endif
             float O[D];
             float Dv = 0.f;   // D_i = sum_j P_ij dP_ij = dO_i . O_i
 #pragma unroll
@@ -542,7 +414,6 @@ __global__ __launch_bounds__(F_NT) __attribute__((amdgpu_waves_per_eu(2))) void 
             }
 #pragma unroll
             for (int c = 0; c < D; ++c) dqkv[c] = (dq2[c].x + dq2[c].y) * scale;
-#endif
             // this head's attention output into the window's cat image (proj input: B operand of the proj weight-gradient product)
             *reinterpret_cast<float4*>(sCat + lane * E + D * hd) = make_float4(O[0], O[1], O[2], O[3]);
             sSt[lane] = mx;
@@ -551,7 +422,7 @@ __global__ __launch_bounds__(F_NT) __attribute__((amdgpu_waves_per_eu(2))) void 
                     }
         }
         STAMP(3);
-        ATTNF_PRIO(uw >= 4);
+        pass_prio(uw >= 4);
         // the epilogue's global operands of this group, requested across pass 2
         float4 ex0, ex1, ed0, ed1;
         uint32_t ekw;
@@ -575,64 +446,6 @@ __global__ __launch_bounds__(F_NT) __attribute__((amdgpu_waves_per_eu(2))) void 
             // ---------------- pass 2: lane = key j, packed over QUERY pairs
             // the lane's own k / v as FULL register pairs: a splat by op_sel reads one half of a pair whose other half the allocator
             // gives to anything -- here to the destinations of the loads in flight, and the wait for those then sits in front of pass 2
-#if LG_ATTNF_DPP
-            const int l15 = lane & 15;
-            float Qr[4][D], dOr[4][D], Mr[4], Ir[4], Dr[4];   // q / dO channel c and the row statistics of query 16 r + (lane & 15)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-#pragma unroll
-                for (int c = 0; c < D; ++c) { Qr[r][c] = sQ[c * 64 + 16 * r + l15]; dOr[r][c] = sDO[c * 64 + 16 * r + l15]; }
-                Mr[r] = sSt[16 * r + l15]; Ir[r] = sSt[64 + 16 * r + l15]; Dr[r] = sSt[128 + 16 * r + l15];
-            }
-            float kj[D], vj[D], dke[D], dko[D], dve[D], dvo[D];
-#pragma unroll
-            for (int c = 0; c < D; ++c) { kj[c] = sK[c * 64 + lane]; vj[c] = sV[c * 64 + lane]; dke[c] = 0.f; dko[c] = 0.f; dve[c] = 0.f; dvo[c] = 0.f; }
-            const float* pcol = sPosH + lane;
-            static_for<16>([&](auto gg) {
-                constexpr int g = decltype(gg)::value, r = g >> 2, n0 = 4 * (g & 3);
-                float t0 = pcol[(4 * g) * PLD], t1 = pcol[(4 * g + 1) * PLD], t2 = pcol[(4 * g + 2) * PLD], t3 = pcol[(4 * g + 3) * PLD];
-                float dP0 = 0.f, dP1 = 0.f, dP2 = 0.f, dP3 = 0.f;
-#pragma unroll
-                for (int c = 0; c < D; ++c) {
-                    t0 = fmac_bc<n0>(t0, Qr[r][c], kj[c]);
-                    t1 = fmac_bc<n0 + 1>(t1, Qr[r][c], kj[c]);
-                    t2 = fmac_bc<n0 + 2>(t2, Qr[r][c], kj[c]);
-                    t3 = fmac_bc<n0 + 3>(t3, Qr[r][c], kj[c]);
-                    dP0 = fmac_bc<n0>(dP0, dOr[r][c], vj[c]);
-                    dP1 = fmac_bc<n0 + 1>(dP1, dOr[r][c], vj[c]);
-                    dP2 = fmac_bc<n0 + 2>(dP2, dOr[r][c], vj[c]);
-                    dP3 = fmac_bc<n0 + 3>(dP3, dOr[r][c], vj[c]);
-                }
-                const float P0 = mul_bc<n0>(__builtin_amdgcn_exp2f(sub_bc<n0>(t0, Mr[r])), Ir[r]);
-                const float P1 = mul_bc<n0 + 1>(__builtin_amdgcn_exp2f(sub_bc<n0 + 1>(t1, Mr[r])), Ir[r]);
-                const float P2 = mul_bc<n0 + 2>(__builtin_amdgcn_exp2f(sub_bc<n0 + 2>(t2, Mr[r])), Ir[r]);
-                const float P3 = mul_bc<n0 + 3>(__builtin_amdgcn_exp2f(sub_bc<n0 + 3>(t3, Mr[r])), Ir[r]);
-                const float dS0 = P0 * sub_bc<n0>(dP0, Dr[r]), dS1 = P1 * sub_bc<n0 + 1>(dP1, Dr[r]);
-                const float dS2 = P2 * sub_bc<n0 + 2>(dP2, Dr[r]), dS3 = P3 * sub_bc<n0 + 3>(dP3, Dr[r]);
-#ifdef LG_DEGRADE_DPOS   // diagnostic variant only (never in the product build): a 5 % error in what enters the pos_emb gradient -- what
-                        // tests/test_gpu_benchsize.py::test_cancelling_sum_gradient_kinds_band_against_band must turn red on
-                dpacc[2 * g] += (lg_v2f){dS0, dS1} * 1.05f;
-                dpacc[2 * g + 1] += (lg_v2f){dS2, dS3} * 1.05f;
-#else
-                dpacc[2 * g] += (lg_v2f){dS0, dS1};
-                dpacc[2 * g + 1] += (lg_v2f){dS2, dS3};
-#endif
-                PASS_FENCE(g);
-#pragma unroll
-                for (int c = 0; c < D; ++c) {
-                    dve[c] = fmac_bc<n0>(dve[c], dOr[r][c], P0);
-                    dvo[c] = fmac_bc<n0 + 1>(dvo[c], dOr[r][c], P1);
-                    dve[c] = fmac_bc<n0 + 2>(dve[c], dOr[r][c], P2);
-                    dvo[c] = fmac_bc<n0 + 3>(dvo[c], dOr[r][c], P3);
-                    dke[c] = fmac_bc<n0>(dke[c], Qr[r][c], dS0);
-                    dko[c] = fmac_bc<n0 + 1>(dko[c], Qr[r][c], dS1);
-                    dke[c] = fmac_bc<n0 + 2>(dke[c], Qr[r][c], dS2);
-                    dko[c] = fmac_bc<n0 + 3>(dko[c], Qr[r][c], dS3);
-                }
-            });
-#pragma unroll
-            for (int c = 0; c < D; ++c) { dqkv[4 + c] = (dke[c] + dko[c]) * LN2; dqkv[8 + c] = dve[c] + dvo[c]; }   // sQ carries log2(e)
-#else
             lg_v2f kj2[D], vj2[D];
             lg_v2f dk2[D], dv2[D];
 #pragma unroll
@@ -667,14 +480,8 @@ __global__ __launch_bounds__(F_NT) __attribute__((amdgpu_waves_per_eu(2))) void 
                 lg_v2f P1 = (lg_v2f){__builtin_amdgcn_exp2f(e1.x), __builtin_amdgcn_exp2f(e1.y)};
                 if constexpr (!STATS) { P0 *= (lg_v2f){sinv.x, sinv.y}; P1 *= (lg_v2f){sinv.z, sinv.w}; }   // (STATS: the row's log-sum-exp is in smx)
                 const lg_v2f dS0 = P0 * (dP0 - (lg_v2f){sdv.x, sdv.y}), dS1 = P1 * (dP1 - (lg_v2f){sdv.z, sdv.w});
-#ifdef LG_DEGRADE_DPOS   // diagnostic variant only (never in the product build): a 5 % error in what enters the pos_emb gradient -- what
-                        // tests/test_gpu_benchsize.py::test_cancelling_sum_gradient_kinds_band_against_band must turn red on
-                dpacc[2 * g] += dS0 * 1.05f;
-                dpacc[2 * g + 1] += dS1 * 1.05f;
-#else
                 dpacc[2 * g] += dS0;
                 dpacc[2 * g + 1] += dS1;
-#endif
                 PASS_FENCE(g);
 #pragma unroll
                 for (int c = 0; c < D; ++c) {
@@ -686,10 +493,9 @@ __global__ __launch_bounds__(F_NT) __attribute__((amdgpu_waves_per_eu(2))) void 
             }
 #pragma unroll
             for (int c = 0; c < D; ++c) { dqkv[4 + c] = (dk2[c].x + dk2[c].y) * LN2; dqkv[8 + c] = dv2[c].x + dv2[c].y; }   // sQ carries log2(e)
-        #endif
         }
         STAMP(4);
-        if (LG_ATTNF_PRIO) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();   // every lane is done with the wave's K / V / Q / dO tiles: they become the dqkv image
         {   // the next group's prologue operands (a repeat of this group's addresses when there is no next one)
@@ -899,10 +705,7 @@ __global__ __launch_bounds__(256) void k_proj_o2_bwd_k(ProjO2BwdKArgs a) {
         float dy[E];
 #pragma unroll
         for (int k = 0; k < E / 4; ++k) { dy[4 * k] = nx[k].x; dy[4 * k + 1] = nx[k].y; dy[4 * k + 2] = nx[k].z; dy[4 * k + 3] = nx[k].w; }
-#ifndef LG_O2_PREF
-#define LG_O2_PREF 1
-#endif
-        if (LG_O2_PREF) {
+        {   // the next pixel's dy, requested in front of this one's arithmetic
             const long pn = p + stride < a.total ? p + stride : p;
             const float4* src = reinterpret_cast<const float4*>(a.dy + pn * E);
 #pragma unroll
@@ -927,11 +730,6 @@ __global__ __launch_bounds__(256) void k_proj_o2_bwd_k(ProjO2BwdKArgs a) {
 #pragma unroll
             for (int n = 0; n < E; ++n) acc += sProj[n * HC + c] * dy[n];
             a.do2[(b * HC + c) * a.HW + s] = acc;
-        }
-        if (!LG_O2_PREF && p + stride < a.total) {
-            const float4* src = reinterpret_cast<const float4*>(a.dy + (p + stride) * E);
-#pragma unroll
-            for (int k = 0; k < E / 4; ++k) nx[k] = src[k];
         }
     }
     const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;

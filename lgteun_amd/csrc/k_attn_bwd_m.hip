@@ -273,7 +273,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
         __builtin_amdgcn_wave_barrier();    // the tiles are this wave's own
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
-#ifndef ABM_SKIP_PASSES
         // (operand fragments are built from the LDS tiles where they are used: an MFMA operand is a tuple of four registers, {lo, hi, hi, 0} and its
         //  B-side permutation are different tuples -- 16 resident fragments were 64 registers)
         const int tok_off = (c >> 3) * a.w + (c & 7);            // pixel offset of token c of a tile (tile t: + 2 t w)
@@ -350,7 +349,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
             }
         }
         // ---------------- orientation B: rows = queries, columns = keys
-#ifndef ABM_SKIP_B
         if constexpr (PH == 1) {
             {   // the statistics of this wave's 64 queries: lane = token, through the wave's LDS region
                 const float4 st = *reinterpret_cast<const float4*>(a.stats + ((porg + (lane >> 3) * a.w + (lane & 7)) * 2 + hd) * 4);
@@ -406,8 +404,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-#endif
-#endif
     }
     if constexpr (PH == 1) return;
     // ---------------- pos_emb gradient of this workgroup: the waves add their accumulators in turn (fixed order), then one slab row

@@ -165,6 +165,16 @@ struct Geo {
     __host__ __device__ static constexpr int v_oc(int nt, int c) { return (HC == 8 && c >= 8) ? -1 : 2 * HC + 16 * nt + c; }
 };
 
+// Multi-stage instances of HC >= this form the lane constants again in every segment, behind a laundered thread index: hoisted out of the segment loop
+// they stay live through the kernel.  k_attn_m<16,2,true>: 9 spilled registers -> 4, its time unchanged.  At HC = 8 nothing was spilled (236 -> 230
+// registers) and the launch got slower, so 8 stays out.  The measured figures are in DESIGN section 4.
+constexpr int MULTI_REFORM_HC = 16;
+// uneven split of a CU's window quads between its two workgroups (attn_m_geometry), in eighths to the first workgroup; 4: even
+constexpr int UNEVEN = 5;
+// the same split in the multi-stage instances (kernels.h: stage_run_chunk), in eighths of a CU's chunk of quads to its first workgroup; 4: even runs
+constexpr int MULTI_UNEVEN = 5;     // HC = 8: k_attn_m<8,2,true> over 3 x 32 pairs (24 quads per CU), us per launch: even 106.2 - 107.8, 5 (15 : 9) 97.9, 6 (18 : 6) 121
+constexpr int MULTI_UNEVEN16 = 4;   // HC = 16 stays EVEN: k_attn_m<16,2,true> with 6 quads per CU at 3 x 32 pairs measured 45.6 - 47.1 us even, 47.5 at 5 (4 : 2), 53.8 at 6 (5 : 1)
+
 }  // namespace am
 
 #ifdef LG_ATTN_STAMPS   // diagnostic build of tools/micro/attn_m_check.hip only: s_memtime ticks per phase, summed over the windows of every wave
@@ -172,12 +182,6 @@ __device__ unsigned long long am_stamps[1024][4][8];
 #define AM_STAMP(i) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t__ = __builtin_amdgcn_s_memtime(); st[i] += t__ - tprev; tprev = t__; __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
 #define AM_STAMP(i) do { } while (0)
-#endif
-// Multi-stage instances of HC >= this form the lane constants again in every segment, behind a laundered thread index: hoisted out of the segment loop
-// they stay live through the kernel.  k_attn_m<16,2,true>: 9 spilled registers -> 4, its time unchanged.  At HC = 8 nothing was spilled (236 -> 230
-// registers) and the launch got slower, so 8 stays out.  The measured figures are in DESIGN section 4.
-#ifndef LG_ATTN_MULTI_REFORM_HC
-#define LG_ATTN_MULTI_REFORM_HC 16
 #endif
 // MULTI: the launch covers the samples of several stages (kernels.h: StageSel); false: the segment loop below is one straight pass
 template <int HC, int NP, bool MULTI = false>
@@ -223,7 +227,7 @@ __global__ __launch_bounds__(256, (HC <= 16 ? 2 : 1)) void k_attn_m(AttnArgs a_,
     const int stg = multi ? __builtin_amdgcn_readfirstlane(seg0 / per_stage) : 0;   // (division runs on the vector pipe: kernels.h, stage_of)
     const int seg1 = multi ? stage_seg_end(stg, run1, per_stage) : run1;
     int tid_ = threadIdx.x;
-    if (MULTI && HC >= LG_ATTN_MULTI_REFORM_HC) asm volatile("" : "+v"(tid_));   // (the lane constants are formed again per segment: see LG_ATTN_MULTI_REFORM_HC)
+    if (MULTI && HC >= MULTI_REFORM_HC) asm volatile("" : "+v"(tid_));   // (the lane constants are formed again per segment: see MULTI_REFORM_HC)
     const int lane = tid_ & 63, wave = tid_ >> 6, g = lane >> 4, c = lane & 15;
     AttnArgs a = a_;
     {
@@ -536,16 +540,6 @@ __global__ __launch_bounds__(256, (HC <= 16 ? 2 : 1)) void k_attn_m(AttnArgs a_,
 #endif
 }
 
-#ifndef LG_ATTN_UNEVEN
-#define LG_ATTN_UNEVEN 5
-#endif
-// the same split in the multi-stage instances (kernels.h: stage_run_chunk), in eighths of a CU's chunk of quads to its first workgroup; 4: even runs
-#ifndef LG_ATTN_MULTI_UNEVEN
-#define LG_ATTN_MULTI_UNEVEN 5     // HC = 8: k_attn_m<8,2,true> over 3 x 32 pairs (24 quads per CU), us per launch: even 106.2 - 107.8, 5 (15 : 9) 97.9, 6 (18 : 6) 121
-#endif
-#ifndef LG_ATTN_MULTI_UNEVEN16
-#define LG_ATTN_MULTI_UNEVEN16 4   // HC = 16 stays EVEN: k_attn_m<16,2,true> with 6 quads per CU at 3 x 32 pairs measured 45.6 - 47.1 us even, 47.5 at 5 (4 : 2), 53.8 at 6 (5 : 1)
-#endif
 // The launch geometry (host only; lg_debug_stage_decision reports it).  n <= 1: one stage.  per_cu: resident workgroups per CU, from the runtime.
 AttnMGeo attn_m_geometry(int HC, int h, int w, int B, int n, int grid_cap, int per_cu) {
     AttnMGeo q;
@@ -561,9 +555,9 @@ AttnMGeo attn_m_geometry(int HC, int h, int w, int B, int n, int grid_cap, int p
         if (q.nquads > cap) q.grid = cap;
         if (grid_cap > 0 && q.grid > grid_cap) { q.grid = grid_cap; capped = true; }
     }
-    int u = (!multi && per_cu == 2 && q.grid == 512 && q.nquads == 4 * q.grid && q.nwin == 4 * q.nquads) ? LG_ATTN_UNEVEN : 0;   // the measured shape only
+    int u = (!multi && per_cu == 2 && q.grid == 512 && q.nquads == 4 * q.grid && q.nwin == 4 * q.nquads) ? am::UNEVEN : 0;   // the measured shape only
     // several stages: two resident workgroups on every CU, no test cap, at least two quads for a CU's pair to share
-    if (multi && per_cu == 2 && q.grid == 2 * ncu && !capped && q.nquads >= 2 * ncu && (HC == 8 || HC == 16)) u = HC == 8 ? LG_ATTN_MULTI_UNEVEN : LG_ATTN_MULTI_UNEVEN16;
+    if (multi && per_cu == 2 && q.grid == 2 * ncu && !capped && q.nquads >= 2 * ncu && (HC == 8 || HC == 16)) u = HC == 8 ? am::MULTI_UNEVEN : am::MULTI_UNEVEN16;
     q.uneven = u == 4 ? 0 : u;
     return q;
 }

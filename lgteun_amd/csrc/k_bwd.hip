@@ -170,12 +170,7 @@ static int ffn_half_bwd(const Blk& k, BwdBufs& bb, const float* dy, float* tmp, 
             if (!f1.w1slab) return -3;
             f1.d_w1 = k.g(B_W1); f1.d_b1 = k.g(B_B1);
         }
-        f1.w2slab = nullptr; f1.d_w2 = nullptr; f1.d_b2 = nullptr;
-        if (!fr.wgrad_w2) {   // dW2 / db2 too
-            f1.w2slab = bb.rq.take((size_t)FFN1_BWD_WGS * ((size_t)n1 * n1 + n1));
-            if (!f1.w2slab) return -3;
-            f1.d_w2 = k.g(B_W2); f1.d_b2 = k.g(B_B2);
-        }
+        f1.w2slab = nullptr; f1.d_w2 = nullptr; f1.d_b2 = nullptr;   // (dW2 / db2: k_wgrad below)
         RC(launch_ffn1_bwd(e, fr.px, f1, s));
     }
     if (fr.wgrad_w2) RC(wgrad(bb.dh2, n1, fb.a1, n1, k.g(B_W2), n1, k.g(B_B2), Pn, n1, n1, n1, n1, hbf, hbf, bb, s, pre));

@@ -50,10 +50,8 @@ int launch_transpose(const float* src, float* dst, int rows, int cols, hipStream
 
 // ------------------------------------------------------------------------------------------------
 #define DW_CG 32   // channels per workgroup (depthwise work is per channel); 16 (3 workgroups per CU) measured no faster
-#define DW_TPW 8   // tiles walked by one workgroup (weight-gradient partials stay in registers across them)
-#ifndef LG_DW_INTERLEAVE
-#define LG_DW_INTERLEAVE 1   // tiles dealt round-robin to the workgroups instead of DW_TPW consecutive ones each (A/B: step 7.463 -> 7.437 ms)
-#endif
+#define DW_TPW 8   // tiles walked by one workgroup (weight-gradient partials stay in registers across them), dealt round-robin (against DW_TPW consecutive
+                   // ones each: step 7.463 -> 7.437 ms)
 // PRE: a.g3 holds the pre-activation h3 (the forward saved h1 / h2 / h3 only): gelu'(h3) is evaluated here, on the halo tile
 template <int E, bool BF, int CG, bool PRE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((E == 16 || (E == 32 && CG == 32)) ? 2 : 1))) void k_ffn_dw_bwd(FfnDwBwdArgs a, int tiles_x, int tiles_y) {
@@ -129,13 +127,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((E == 16 ||
             }
         }
     };
-#if LG_DW_INTERLEAVE
     const int tile_first = blockIdx.x, tile_step = gridDim.x;
     const int tile_end = ntiles;
-#else
-    const int tile_first = blockIdx.x * DW_TPW, tile_step = 1;
-    const int tile_end = min((int)(blockIdx.x + 1) * DW_TPW, ntiles);
-#endif
     if (PF && tile_first < tile_end) issue(tile_first);
     for (int tile = tile_first; tile < tile_end; tile += tile_step) {
     int t = tile;
@@ -323,18 +316,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E == 16 ? 2
             *reinterpret_cast<float4*>(w2l + row * LDH + 4 * k4) = *reinterpret_cast<const float4*>(a.w2t + (size_t)row * N1 + 4 * k4);
         }
     }
-    // FW2 (pre-activation saves, e = 16): gelu(h1) is evaluated here for gelu'(h1) anyway, so dW2 = sum_p dh2 (x) gelu(h1) and db2 are
-    // accumulated in this kernel too: the rows of all four waves (dh2 in bufD, gelu(h1) in bufA) are the operands, wave w owns the
-    // output rows n = 4 i + w (tile t of a float4 at column 4r = channel 4r + t, as in k_wgrad_t's VEC layout)
-    constexpr bool FW2 = PRE && E == 16 && LG_FW2;
-    float* bufA_all = w2l + N1 * LDH;            // [4][MW][LDH] gelu(h1) rows (FW2)
-    float* bufA = bufA_all + wave * (MW * LDH);
-    f32x4 acc2[FW2 ? 4 : 1];
-    float4 bs2 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (FW2) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc2[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
     float4 w1r[PF ? NTE : 1][PF ? N1 / 16 : 1];
     if (PF) load_bfrag<NTE, N1 / 16>(reinterpret_cast<float4(&)[NTE][N1 / 16]>(w1r), a.w1t, N1);
     // LN-gradient partials: PF: this lane's channel quarter (4 gamma + 4 beta); otherwise all 2E of the lane's pixel
@@ -394,10 +375,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E == 16 ? 2
             gelu2_both_f((lg_v2f){g1r[it].x, g1r[it].y}, a01, g01);
             gelu2_both_f((lg_v2f){g1r[it].z, g1r[it].w}, a23, g23);
             g1r[it] = make_float4(g01.x, g01.y, g23.x, g23.y);
-            if (FW2) {
-                *reinterpret_cast<float4*>(bufA + m * LDH + 4 * k4) = make_float4(a01.x, a01.y, a23.x, a23.y);
-                bs2.x += d2.x; bs2.y += d2.y; bs2.z += d2.z; bs2.w += d2.w;   // k4 = lane % (N1/4) is the same for every `it`
-            }
         }
         *reinterpret_cast<float4*>(bufD + m * LDH + 4 * k4) = d2;
     }
@@ -437,24 +414,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E == 16 ? 2
         for (int c = 0; c < E; ++c) bufY[lane * LDY + c] = pv ? (xv[c] - mu) * rstd * lnp[c] + lnp[E + c] : 0.f;
     }
     __syncthreads();
-    if constexpr (FW2) {
-        // ---- dW2[4 i + wave][4 j + t] += sum over the workgroup's 64 pixels: A[i = r][k = g] = dh2[pixel g][4 r + wave],
-        // B[k = g][j = r] = gelu(h1)[pixel g][4 r + t]
-#pragma unroll 1
-        for (int sw = 0; sw < 4; ++sw) {
-            const float* dsrc = smem + sw * (MW * (2 * LDH + LDO));
-            const float* asrc = bufA_all + sw * (MW * LDH);
-#pragma unroll
-            for (int ks = 0; ks < MW / 4; ++ks) {
-                const float yv = dsrc[(4 * ks + g) * LDH + 4 * r + wave];
-                const float4 xv = *reinterpret_cast<const float4*>(asrc + (4 * ks + g) * LDH + 4 * r);
-                acc2[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(yv, xv.x, acc2[0], 0, 0, 0);
-                acc2[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(yv, xv.y, acc2[1], 0, 0, 0);
-                acc2[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(yv, xv.z, acc2[2], 0, 0, 0);
-                acc2[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(yv, xv.w, acc2[3], 0, 0, 0);
-            }
-        }
-    }
     // ---- dh1 = (dh2 W2) * g1
     for (int nc = 0; nc < N1; nc += 64) {
         f32x4 acc[MT][4];
@@ -648,32 +607,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E == 16 ? 2
         float* brow = a.w1slab + (size_t)gridDim.x * (N1 * E) + (size_t)blockIdx.x * N1;
         for (int i = threadIdx.x; i < N1; i += 256) brow[i] = rw[N1 * E + i];
     }
-    if constexpr (FW2) {
-        // dW2: the waves own disjoint output rows -> straight to the slab row of this workgroup; db2 through LDS (4 waves, fixed order)
-        float* wrow = a.w2slab + (size_t)blockIdx.x * (N1 * N1);
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int n = 4 * (4 * g + v) + wave;
-            *reinterpret_cast<float4*>(wrow + n * N1 + 4 * r) = make_float4(acc2[0][v], acc2[1][v], acc2[2][v], acc2[3][v]);
-        }
-        float4 b4 = bs2;
-#pragma unroll
-        for (int off = N1 / 4; off < 64; off <<= 1) {
-            b4.x += __shfl_xor(b4.x, off); b4.y += __shfl_xor(b4.y, off); b4.z += __shfl_xor(b4.z, off); b4.w += __shfl_xor(b4.w, off);
-        }
-        float* rb2 = smem;   // [N1]
-        __syncthreads();
-        for (int w = 0; w < 4; ++w) {
-            if (wave == w && lane < N1 / 4) {
-                float* rb = rb2 + 4 * lane;
-                rb[0] = (w == 0 ? 0.f : rb[0]) + b4.x; rb[1] = (w == 0 ? 0.f : rb[1]) + b4.y;
-                rb[2] = (w == 0 ? 0.f : rb[2]) + b4.z; rb[3] = (w == 0 ? 0.f : rb[3]) + b4.w;
-            }
-            __syncthreads();
-        }
-        float* brow2 = a.w2slab + (size_t)gridDim.x * (N1 * N1) + (size_t)blockIdx.x * N1;
-        for (int i = threadIdx.x; i < N1; i += 256) brow2[i] = rb2[i];
-    }
 }
 
 template <int E, int MT>
@@ -681,7 +614,6 @@ static int launch_ffn1_bwd_t(const Ffn1BwdArgs& a, hipStream_t s) {
     ProfScope prof__(LG_K_FFN1_BWD, s);
     constexpr int N1 = 4 * E, MW = 16 * MT;
     size_t lds = (size_t)(4 * MW * (2 * (N1 + 4) + E + 1) + (E == 16 ? N1 * (N1 + 4) : 0)) * sizeof(float);
-    if (ffn1_bwd_fuses_w2(E, a.pre)) lds += (size_t)4 * MW * (N1 + 4) * sizeof(float);   // gelu(h1) rows
     static DeviceOnce attr_once;
     {
         int rc;
@@ -695,7 +627,6 @@ static int launch_ffn1_bwd_t(const Ffn1BwdArgs& a, hipStream_t s) {
     if (!a.part) { lg_set_error("ffn1_bwd: partial-sum scratch missing"); return -2; }
     if (ffn1_bwd_fuses_w1(E) && (!a.w1slab || !a.d_w1 || !a.d_b1)) { lg_set_error("ffn1_bwd: dW1 slab / destinations missing"); return -2; }
     if (!ffn1_bwd_fuses_w1(E) && (!a.dh1 || !a.y2)) { lg_set_error("ffn1_bwd: dh1 / y2 outputs missing"); return -2; }
-    if (ffn1_bwd_fuses_w2(E, a.pre) && (!a.w2slab || !a.d_w2 || !a.d_b2)) { lg_set_error("ffn1_bwd: dW2 slab / destinations missing"); return -2; }
     if (a.pre && (a.hbf || E != 16)) { lg_set_error("ffn1_bwd: pre-activation saves are fp32, e = 16"); return -2; }
     // (route.hip: the tile kernel is the pixelwise half at e = 32 only behind the fp32 kernels of LG_VAR_FFN_STRIP, and e = 64 keeps fp32 storage)
     if (a.hbf && E != 16) { lg_set_error("ffn1_bwd: bf16 storage runs e = 16 only"); return -2; }
@@ -705,9 +636,7 @@ static int launch_ffn1_bwd_t(const Ffn1BwdArgs& a, hipStream_t s) {
     LG_CHECK_LAUNCH();
     int rc = launch_reduce_slab_pair(a.part, a.part + (size_t)grid * E, grid, E, a.d_ln2g, a.d_ln2b, s);
     if (rc || !ffn1_bwd_fuses_w1(E)) return rc;
-    rc = launch_reduce_slab_wb(a.w1slab, a.w1slab + (size_t)grid * N1 * E, grid, N1, E, a.d_w1, E, a.d_b1, s);
-    if (rc || !ffn1_bwd_fuses_w2(E, a.pre)) return rc;
-    return launch_reduce_slab_wb(a.w2slab, a.w2slab + (size_t)grid * N1 * N1, grid, N1, N1, a.d_w2, N1, a.d_b2, s);
+    return launch_reduce_slab_wb(a.w1slab, a.w1slab + (size_t)grid * N1 * E, grid, N1, E, a.d_w1, E, a.d_b1, s);
 }
 int launch_ffn1_bwd(int e, Ffn1BwdKernel k, const Ffn1BwdArgs& a, hipStream_t s) {
     if (k == FFN1_BWD_X32) {   // (e = 32 only: the split-bf16 kernel needs the forward W1 and the fragment scratch, the f32-MFMA kernel takes neither)

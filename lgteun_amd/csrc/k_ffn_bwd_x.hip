@@ -43,6 +43,7 @@ extern "C" __attribute__((visibility("default"))) int lg_debug_kb_stamps(unsigne
 namespace {
 
 constexpr int NPX = 64;
+constexpr int FFN1B_UNEVEN = 9;   // of the sixteen tile shares of a CU's two workgroups, those of the first (launch_t: the measured shape only); 8: even
 template <int E>
 struct KB {
     static constexpr int N1 = 4 * E, NW = N1 / 16, NT = 64 * NW, LPP = E / 4;
@@ -64,17 +65,6 @@ struct KB {
     static_assert(NT / (N1 / 4) == 16 && NT / LPP == NPX, "loader / LayerNorm thread maps");
 };
 
-#ifndef LG_KB_DACHAINS
-#define LG_KB_DACHAINS 0
-#endif
-#ifndef LG_KB_STAGGER
-#define LG_KB_STAGGER 0
-#endif
-#ifndef LG_KB_FENCE
-#define LG_KB_FENCE 1
-#endif
-#define KB_FENCE() do { if (LG_KB_FENCE) __builtin_amdgcn_sched_barrier(0); } while (0)
-
 __device__ __forceinline__ void mfma6_32(f32x4_t& acc, const bf16x8_t (&a)[3], const bf16x8_t (&b)[3]) {
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[2], acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[0], acc, 0, 0, 0);
@@ -86,9 +76,6 @@ __device__ __forceinline__ void mfma6_32(f32x4_t& acc, const bf16x8_t (&a)[3], c
 // NP = 3: the six piece products (fp32-equivalent); NP = 1 (precision = 'bf16'): one product of round-to-nearest bf16 operands
 // NP = 2 (round 5): f16 pairs (split_bf16.h), three piece products; every operand arrives multiplied by a power of two (see the kernel)
 // K = 16 blocks (mfma_np16): the six products as three 32-deep MFMAs (split_bf16.h: mfma_split16_pair), half the matrix-pipe time of each
-#ifndef LG_KB_PAIR
-#define LG_KB_PAIR 1
-#endif
 template <int NP>
 __device__ __forceinline__ void mfmaN_32(f32x4_t& acc, const bf16x8_t (&a)[3], const bf16x8_t (&b)[3]) {
     if (NP == 3) mfma6_32(acc, a, b);
@@ -247,16 +234,11 @@ __global__ __launch_bounds__(KB<E>::NT) __attribute__((amdgpu_waves_per_eu(2))) 
         STAMP(1);
         __syncthreads();
         STAMP(2);
-#if LG_KB_STAGGER
-        // e = 32: the two waves of a SIMD (w and w + 4) leave the barrier together and would run their matrix bursts and their vector
-        // bursts at the same time; half a block of delay for the second lets one wave's MFMAs run under the other's GELU / splitting
-        if (NW == 8 && wave >= 4) __builtin_amdgcn_s_sleep(LG_KB_STAGGER);
-#endif
 
         // ---- GEMM phase: four blocks of 16 pixels; this wave's 16 hidden channels
 #pragma unroll 1
         for (int pbk = 0; pbk < NPX / 16; ++pbk) {
-            // The phases below are kept apart by scheduling fences (KB_FENCE): on gfx950 a wave that alternates MFMAs and vector
+            // The phases below are kept apart by scheduling fences: on gfx950 a wave that alternates MFMAs and vector
             // instructions runs slower than the sum of the two (tools/micro/mfma_valu_overlap.hip: 482 + 525 us alone, 1178 us interleaved
             // in one wave, 650 us with the two kinds of work in different waves of the SIMD) -- bursts of one kind per wave let the OTHER
             // resident wave's vector work run under this wave's matrix work.  (Measured here: no difference, 101.3 vs 101.5 us; kept.)
@@ -265,40 +247,25 @@ __global__ __launch_bounds__(KB<E>::NT) __attribute__((amdgpu_waves_per_eu(2))) 
             if constexpr (E == 16) {
                 s16x4_t xa[3];
                 ld3_x4<NPE>(XN + (pbk * 16 + r) * E + 4 * g, XN_PIECE, xa);
-                KB_FENCE();
-                mfma_np16<NPE, LG_KB_PAIR>(h1, xa, w1f16.p);
+                __builtin_amdgcn_sched_barrier(0);
+                mfma_np16<NPE, true>(h1, xa, w1f16.p);
             } else {
                 bf16x8_t xa[3];
                 ld3_x8<NPE>(XN + (pbk * 16 + r) * E + 8 * g, XN_PIECE, xa);
-                KB_FENCE();
+                __builtin_amdgcn_sched_barrier(0);
                 mfmaN_32<NPE>(h1, xa, w1f32.p);
             }
             f32x4_t da = (f32x4_t){0.f, 0.f, 0.f, 0.f};
             {
                 const uint16_t* pd = D2 + (pbk * 16 + r) * LDP + 8 * g;
-#if LG_KB_DACHAINS
-                // K = N1 as independent accumulation chains (one per 32-deep block), summed at the end: a chain of 6 KB2 dependent MFMAs
-                // otherwise
-                f32x4_t dak[KB2];
-#pragma unroll
-                for (int kb = 0; kb < KB2; ++kb) {
-                    dak[kb] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-                    bf16x8_t dk[3];
-                    ld3_x8<NP>(pd + 32 * kb, D2_PIECE, dk);
-                    mfmaN_32<NP>(dak[kb], dk, w2f[kb].p);
-                }
-#pragma unroll
-                for (int kb = 0; kb < KB2; ++kb) da += dak[kb];
-#else
 #pragma unroll
                 for (int kb = 0; kb < KB2; ++kb) {
                     bf16x8_t dk[3];
                     ld3_x8<NP>(pd + 32 * kb, D2_PIECE, dk);
                     mfmaN_32<NP>(da, dk, w2f[kb].p);
                 }
-#endif
             }
-            KB_FENCE();
+            __builtin_amdgcn_sched_barrier(0);
             // ---- gelu(h1), gelu'(h1) with one exponential for both; dh1 = da1 * gelu'(h1); pieces
             lg_v2f a01, a23, g01, g23;
             gelu2_both_t<NP == 1>((lg_v2f){h1[0], h1[1]}, a01, g01);
@@ -310,7 +277,7 @@ __global__ __launch_bounds__(KB<E>::NT) __attribute__((amdgpu_waves_per_eu(2))) 
             s16x4_t a1p[3], d1p[3];
             split4<NP>(a1v, a1p);
             split4<NPE>(d1v, d1p);
-            KB_FENCE();
+            __builtin_amdgcn_sched_barrier(0);
             // ---- dW1[16 w + .][.] += dh1^T LN(x) (A = dh1 from the registers, B = LN(x) read by columns);
             //      dW2[.][16 w + .] += dh2^T gelu(h1) (A = dh2 read by columns, B = gelu(h1) from the registers)
             {
@@ -319,17 +286,17 @@ __global__ __launch_bounds__(KB<E>::NT) __attribute__((amdgpu_waves_per_eu(2))) 
                 for (int cb = 0; cb < NE; ++cb) {
                     s16x4_t xt[3];
                     ld3_tr<NPE>(px + 16 * cb, XN_PIECE, xt);
-                    mfma_np16<NPE, LG_KB_PAIR>(acc1[cb], d1p, xt);
+                    mfma_np16<NPE, true>(acc1[cb], d1p, xt);
                 }
                 const uint16_t* pt = D2 + (pbk * 16 + 4 * g + (r >> 2)) * LDP + 4 * (r & 3);
 #pragma unroll
                 for (int nb = 0; nb < NW; ++nb) {
                     s16x4_t dt[3];
                     ld3_tr<NP>(pt + 16 * nb, D2_PIECE, dt);
-                    mfma_np16<NP, LG_KB_PAIR>(acc2[nb], dt, a1p);
+                    mfma_np16<NP, true>(acc2[nb], dt, a1p);
                 }
             }
-            KB_FENCE();
+            __builtin_amdgcn_sched_barrier(0);
             // this wave's K = 16 slice of W1^T dh1: dh1 -> [channel][pixel] in the wave's own LDS region, read back by columns as the B operand
             {
                 uint16_t* dst = D1T + r * 16 + 4 * g;
@@ -345,7 +312,7 @@ __global__ __launch_bounds__(KB<E>::NT) __attribute__((amdgpu_waves_per_eu(2))) 
 #pragma unroll
                 for (int rb = 0; rb < NE; ++rb) {
                     f32x4_t o = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-                    mfma_np16<NPE, LG_KB_PAIR>(o, w1tf[rb].p, dtp);     // o[v] = (W1^T dh1)[out channel 16 rb + 4 g + v][pixel r], hidden channels 16 w .. 16 w + 15 only
+                    mfma_np16<NPE, true>(o, w1tf[rb].p, dtp);     // o[v] = (W1^T dh1)[out channel 16 rb + 4 g + v][pixel r], hidden channels 16 w .. 16 w + 15 only
                     *reinterpret_cast<float4*>(red + ((size_t)wave * NPX + pbk * 16 + r) * E + 16 * rb + 4 * g) = make_float4(o[0], o[1], o[2], o[3]);
                 }
                 __builtin_amdgcn_wave_barrier();      // D1T is rewritten by the next pixel block
@@ -423,10 +390,7 @@ int launch_t(const Ffn1BwdXArgs& a, hipStream_t s) {
     const long ntiles = a.P / NPX;
     const int cap = ffn1_bwd_x_wgs(E);
     const int grid = (int)(ntiles < cap ? ntiles : cap);
-#ifndef LG_FFN1B_UNEVEN
-#define LG_FFN1B_UNEVEN 9
-#endif
-    const int uneven = (E == 16 && grid == 512 && ntiles % (8 * (long)grid) == 0 && LG_FFN1B_UNEVEN != 8) ? LG_FFN1B_UNEVEN : 0;   // the measured shape only (two workgroups per CU)
+    const int uneven = (E == 16 && grid == 512 && ntiles % (8 * (long)grid) == 0 && FFN1B_UNEVEN != 8) ? FFN1B_UNEVEN : 0;   // the measured shape only (two workgroups per CU)
     if (a.hbf) k_ffn1_bwd_xs<E, 1><<<grid, C::NT, C::LDS_BYTES, s>>>(a, ntiles, uneven);      // precision = 'bf16': plain bf16 operands, dh2 stored as bf16
     else if (a.scales) k_ffn1_bwd_xs<E, 2><<<grid, C::NT, C::LDS_BYTES, s>>>(a, ntiles, uneven);   // f16 pairs, scaled operands
     else k_ffn1_bwd_xs<E, 3><<<grid, C::NT, C::LDS_BYTES, s>>>(a, ntiles, uneven);

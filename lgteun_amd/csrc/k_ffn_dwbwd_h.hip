@@ -57,9 +57,6 @@ template <int N>
 struct IC { static constexpr int value = N; };
 
 #define DWH_FENCE() __builtin_amdgcn_sched_barrier(0)
-#ifndef DWH_ROWFENCE
-#define DWH_ROWFENCE 0
-#endif
 
 }  // namespace dwh
 
@@ -205,7 +202,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 #pragma unroll
                     for (int pc = 0; pc < 3; ++pc) wf.p[pc] = __builtin_bit_cast(s16x4_t, sW3[(mt * 3 + pc) * 64 + lane]);
                     const s16x4_t dyq[3] = {__builtin_bit_cast(s16x4_t, q1), __builtin_bit_cast(s16x4_t, q2), __builtin_bit_cast(s16x4_t, q3)};
-                    mfma_np16<3, LG_SPLIT16_PAIR>(acc, wf.p, dyq);
+                    mfma_np16<3, true>(acc, wf.p, dyq);
                     lg_v2f a01, a23, g01, g23;
                     gelu2_both_f(H01[nb][i], a01, g01);
                     gelu2_both_f(H23[nb][i], a23, g23);
@@ -270,16 +267,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 #pragma unroll
             for (int k = 0; k < 5; ++k) hn[k] = h2load(y0 + TY + 2, TY, k);
             dnn[0] = dyload(y0 + TY + 1, 2 * wave); dnn[1] = dyload(y0 + TY + 1, 2 * wave + 1); dnn[2] = dyload(y0 + TY + 1, 8);
-#ifndef DWH_NO_HALO
             halo(IC<2>{}, IC<0>{}, IC<2>{}, y0 + 1, TY * HX, 2 * wave, dn);
             if (role == 1) halo(IC<1>{}, IC<0>{}, IC<1>{}, y0 + 1, TY * HX, 8, dn + 2);
             if (role == 3) halo(IC<1>{}, IC<1>{}, IC<1>{}, y0 + 1, TY * HX, 8, dn + 2);
-#endif
             dn[0] = dnn[0]; dn[1] = dnn[1]; dn[2] = dnn[2];
             HSTAMP(2);
             __syncthreads();     // dh3 rows y0 - 1 .. y0 + 8 complete
             HSTAMP(3);
-#ifndef DWH_NO_P2
             // ---- spatial phase: dh2 of four consecutive pixels of tile row ty, channels 4 q .. + 3: a 3 x 3 window of dh3 vectors slides over them
             {
                 const int sbase = (y0 - Y0) % RING;            // dh3 ring slot of row y0 - 1
@@ -330,7 +324,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
                     DWH_FENCE();
                 }
             }
-#endif
             HSTAMP(4);
         }   // steps of the strip
         __syncthreads();

@@ -61,12 +61,8 @@ struct KA {
 static_assert(KA<16>::R_DB == FFN_DW_BWD_X_DB && KA<16>::R_W3 == FFN_DW_BWD_X_W3 && KA<16>::R_B3 == FFN_DW_BWD_X_B3 && KA<16>::ROW == FFN_DW_BWD_X_ROW, "slab row (bwd_kernels.h)");
 static_assert(KA<32>::ROW == FFN_DW_BWD_X32_ROW, "slab row (bwd_kernels.h)");
 
-#ifndef LG_KA_ITEMFENCE
-#define LG_KA_ITEMFENCE 1   // P2: a scheduling fence behind every LG_KA_ITEMFENCE-th item (0: none)
-#endif
-#ifndef LG_KA_PAIR
-#define LG_KA_PAIR 0   // the K = 16 products as three 32-deep MFMAs (split_bf16.h: mfma_split16_pair).  Measured in THIS kernel (VALU / LDS bound, matrix pipe 10 % busy): the operand concatenation costs 133.7 vs 119.5 us per launch; off
-#endif
+constexpr int ITEMFENCE = 1;   // P2: a scheduling fence behind every ITEMFENCE-th item (0: none)
+// mfma_np16<., false>: tried here, the K = 16 products as three 32-deep MFMAs (split_bf16.h: mfma_split16_pair): 133.7 vs 119.5 us per launch, slower
 
 // NP = 3: fp32 storage of h2 / h3 / dh2, fp32-equivalent split products; NP = 1 (precision = 'bf16'): bf16 storage (hstore.h), plain bf16 products
 template <int E, int NP>
@@ -111,7 +107,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void k_
     float dmx = 0.f;     // max |dh2| of this thread's stores (a.dh2_max: the operand scale of k_ffn1_bwd_xs's f16-pair products)
 #pragma unroll 1
     for (int strip = blockIdx.x; strip < nstrips; strip += gridDim.x) {
-    // dS != 0 (launcher: one strip per workgroup, two workgroups per CU): vertically adjacent strips are SH + dS rows for a workgroup of the first half of the grid and
+    // dS != 0 (the launcher passes 0 today; measured with one strip per workgroup, two workgroups per CU): vertically adjacent strips are SH + dS rows for a workgroup of the first half of the grid and
     // SH - dS for its neighbour's in the second half -- the workgroup a CU received first runs faster (k_ffn_xr.hip strip_geo has the measurement)
     int tx_i, Y0, Yend;
     long b;
@@ -216,7 +212,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void k_
                     s16x4_t xb[3];
                     xb[0] = lds_x4(p);
                     if (NP == 3) { xb[1] = lds_x4(p + DY_PIECE); xb[2] = lds_x4(p + 2 * DY_PIECE); } else { xb[1] = xb[0]; xb[2] = xb[0]; }
-                    mfma_np16<NP, LG_KA_PAIR>(acc, w3f16.p, xb);
+                    mfma_np16<NP, false>(acc, w3f16.p, xb);
                 } else {
                     const uint16_t* p = dyb + (pb * 16 + r) * E + 8 * g;
                     const bf16x8_t x1 = lds_x8(p);
@@ -258,7 +254,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void k_
                         s16x4_t dt[3];
                         dt[0] = lds_tr4(pa);
                         if (NP == 3) { dt[1] = lds_tr4(pa + DY_PIECE); dt[2] = lds_tr4(pa + 2 * DY_PIECE); } else { dt[1] = dt[0]; dt[2] = dt[0]; }
-                        mfma_np16<NP, LG_KA_PAIR>(acc3[mt], dt, at);
+                        mfma_np16<NP, false>(acc3[mt], dt, at);
                     }
                 }
                 __builtin_amdgcn_wave_barrier();   // the image is rewritten by the next block
@@ -368,7 +364,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void k_
                     }
                 HS<BF>::st4(a.dh2, ((b * h + y) * (long)w + x) * N1 + hoff + 4 * q, make_float4(acc01.x, acc01.y, acc23.x, acc23.y));
                 if (NP != 1) dmx = fmaxf(fmaxf(dmx, fmaxf(fabsf(acc01.x), fabsf(acc01.y))), fmaxf(fabsf(acc23.x), fabsf(acc23.y)));
-                if (LG_KA_ITEMFENCE && ((it + 1) % LG_KA_ITEMFENCE) == 0) __builtin_amdgcn_sched_barrier(0);   // one item at a time: interleaved items need more registers than there are
+                if (ITEMFENCE && ((it + 1) % ITEMFENCE) == 0) __builtin_amdgcn_sched_barrier(0);   // one item at a time: interleaved items need more registers than there are
             };
             item(0, h2a); item(1, h2b); item(2, h2c); item(3, h2d);
         };
@@ -439,11 +435,7 @@ static int launch_dw_t(const FfnDwBwdXArgs& a, hipStream_t s) {
     const StripGeo geo = strip_geometry(a.h, a.w, a.B, a.B, wgs, 0);
     const int tiles_x = geo.tiles_x, strips_y = geo.strips_y, nstrips = geo.nstrips, SH = geo.SH, gx = geo.grid;
     const dim3 grid(gx, C::NHALF);
-#ifndef LG_DWB_UNEVEN
-#define LG_DWB_UNEVEN 0   // measured: even strips 110.5 us, 9 : 7 steps 113.2, 10 : 6 110.5 -- this kernel gains nothing from the uneven split (unlike k_ffn_xr, k_attn_m, k_ffn1_bwd_xs)
-#endif
-    int dS = 0;   // uneven strip pairs: the measured shape only (e = 16: one strip per workgroup, exactly two workgroups per CU)
-    if (LG_DWB_UNEVEN && E == 16 && nstrips == wgs && wgs == 512 && (strips_y & 1) == 0 && SH >= 32 && a.h % (2 * SH) == 0) dS = (SH * LG_DWB_UNEVEN / 64 + 7) / 8 * 8;
+    const int dS = 0;   // even strips (tried: uneven strip pairs as in k_ffn_xr: even 110.5 us, 9 : 7 steps 113.2, 10 : 6 110.5, no gain in this kernel)
     if (a.hbf) k_ffn_dw_bwd_xs<E, 1><<<grid, NT, C::LDS_BYTES, s>>>(a, tiles_x, strips_y, nstrips, SH, dS);   // precision = 'bf16'
     else k_ffn_dw_bwd_xs<E, 3><<<grid, NT, C::LDS_BYTES, s>>>(a, tiles_x, strips_y, nstrips, SH, dS);
     LG_CHECK_LAUNCH();

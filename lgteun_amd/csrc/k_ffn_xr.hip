@@ -30,9 +30,6 @@
 
 // In-kernel phase stamps (diagnostic build only, -DLG_STAMPS: tools/mkvariant.sh + tools/xr_stamps.py): branch-free, every wave of every workgroup stores
 // s_memtime at the phase boundaries of every step; no stamp executes in the product build.
-#ifndef LG_XR_GRID
-#define LG_XR_GRID 512   // resident workgroups (two per CU); 256 in the diagnostic one-workgroup-per-CU build
-#endif
 #ifdef LG_STAMPS
 __device__ unsigned long long g_xr_stamps[512 * 4 * 10 * 8];   // [workgroup][wave][step of the strip][stamp]
 #define XSTAMP_AT(si_, i) do { unsigned long long t__; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t__)); \
@@ -47,33 +44,16 @@ extern "C" __attribute__((visibility("default"))) int lg_debug_xr_stamps(unsigne
 #define XSTAMP(i) do { } while (0)
 #endif
 
-// Two workgroups share a CU and the SIMD arbiter issues the OLDER wave first: unthrottled, the workgroup that was dispatched first runs as if it were alone
-// (13.1 k cycles per step) while the other gets what is left (24 k per step), finishes 40 % later and spends the end of the launch alone on a half-empty CU
-// (stamps: profiles/r06_ffn_xr_fairness.txt -- lifetimes of the 512 workgroups exactly bimodal, 105 k / 148 k cycles).  XR_TAKE_TURNS() is placed behind the
-// step's barriers (where lgkmcnt is drained anyway, so that reading the clock stalls nothing): it raises or lowers the wave's user priority by a bit of the
-// clock XOR the parity of the wave's slot on its SIMD -- the two waves of a SIMD take turns of 2^LG_XR_TURN cycles, both workgroups advance at the same mean
-// rate and finish together.
-#ifndef LG_XR_TURN
-#define LG_XR_TURN 0       // A/B build: 14 = turns of 2^14 cycles (measured: lifetimes 125 k / 147 k instead of 105 k / 148 k, step 5.299 -> 5.286 ms; the uneven split below does better)
-#endif
-#ifndef LG_XR_UNEVEN
-#define LG_XR_UNEVEN 16   // rows (per 64-row strip) moved from the second workgroup of a CU to the first; 0: even strips
-#endif
-#ifndef LG_XR_MULTI_UNEVEN
-#define LG_XR_MULTI_UNEVEN 16   // the same in the multi-stage instances, whose workgroups walk runs of strip pairs (kernels.h: stage_run_pairs); 0: even strip runs
-                                // (k_ffn_xr<0,2,true> over 3 x 32 pairs, us per launch on one box: even 212.3, 8 rows 208.7, 16 rows 200.9, 24 rows 203.7)
-#endif
-#define XR_TAKE_TURNS() do { if (LG_XR_TURN) { \
-        const unsigned long long tt__ = __builtin_amdgcn_s_memtime(); \
-        if ((((unsigned)(tt__ >> LG_XR_TURN)) ^ slot_par) & 1u) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0); } } while (0)
-// which of the two waves of its SIMD a wave is: one toggling word per (XCD, SE, SH, CU, SIMD) -- the first wave to arrive reads b, the second 1 - b, whatever the
-// launches before left there (zero-initialised once with the module; no reset, no dependence on how the dispatcher numbers wave slots)
-__device__ unsigned g_xr_turn[8192];
-
 namespace xr {
 
 constexpr int E = 16, N1 = 64, TX = 16, HX = 18, TY = 8, RING = 10, LDR = 68;
 constexpr int NF1 = 8, NF2 = 16, NF3 = 4, NFRAG = NF1 + NF2 + NF3;
+constexpr int GRID = 512;          // resident workgroups (two per CU)
+// Two workgroups share a CU and the SIMD arbiter issues the OLDER wave first: the workgroup dispatched first runs as if it were alone, the other gets what is
+// left (profiles/r06_ffn_xr_fairness.txt; strip_geo below).  Tried: priority turns by the clock (step 5.299 -> 5.286 ms), the uneven split does better, DESIGN 3.7.
+constexpr int UNEVEN = 16;         // rows (per 64-row strip) moved from the second workgroup of a CU to the first; 0: even strips
+constexpr int MULTI_UNEVEN = 16;   // the same in the multi-stage instances, whose workgroups walk runs of strip pairs (kernels.h: stage_run_pairs); 0: even strip runs
+                                   // (k_ffn_xr<0,2,true> over 3 x 32 pairs, us per launch on one box: even 212.3, 8 rows 208.7, 16 rows 200.9, 24 rows 203.7)
 // the tables FIRST: a ds_read's immediate offset has 16 bits, and behind the 48 KB ring every fragment / tap row / bias vector needed a base
 // register of its own (the first build: 28 + 16 + .. hoisted addresses, 206 spilled registers)
 constexpr size_t OFF_W = 0;
@@ -85,15 +65,8 @@ constexpr size_t LDS_BYTES = OFF_RING + (size_t)RING * HX * LDR * 4;
 static_assert(LDS_BYTES <= 80 * 1024, "two workgroups per CU");
 static_assert(OFF_RING % 16 == 0 && OFF_TAPS % 16 == 0 && OFF_PAR % 16 == 0, "16-byte aligned LDS regions");
 
-#ifndef LG_XR_NT
-#define LG_XR_NT 0    // streaming (non-temporal) stores of the saved tensors: bit 0 = h2, bit 1 = h3.  OFF here (k_ffn_xs had them on: its h3 rows left as whole 256-byte lines): the register chain writes a pixel's row as four 64-byte pieces, which only the L2 merges into lines -- WRITE_SIZE 421 MB per saving launch with streaming stores against 310 MB of data; 5.496 -> 5.466 ms per step
-#endif
-#ifndef LG_XR_FENCES
-#define LG_XR_FENCES 1   // scheduling fences between the sections of a block: without them the scheduler interleaves every section of a step and spills (206 registers)
-#endif
-#define XR_ST2(base, idx, v) do { if (LG_XR_NT & 1) HS<BF>::st4_nt(base, idx, v); else HS<BF>::st4(base, idx, v); } while (0)
-#define XR_ST3(base, idx, v) do { if (LG_XR_NT & 2) HS<BF>::st4_nt(base, idx, v); else HS<BF>::st4(base, idx, v); } while (0)
-#define XR_FENCE() do { if (LG_XR_FENCES) __builtin_amdgcn_sched_barrier(0); } while (0)
+// the saved tensors leave by plain stores (tried: streaming stores, whose 64-byte pieces only the L2 merges into lines: WRITE_SIZE 421 MB against 310 MB of data, slower)
+// __builtin_amdgcn_sched_barrier(0) between the sections of a block: without these fences the scheduler interleaves every section of a step and spills (206 registers)
 template <int N>
 struct IC { static constexpr int value = N; };
 
@@ -118,11 +91,8 @@ __device__ __forceinline__ f32x4_t mfma_g1(u32x4_t wa, u32x4_t wb, u32x4_t xb1, 
     }
     return mfma_b(wb, xb2, acc);
 }
-struct GKold { float c1, hr; };
-__device__ __forceinline__ lg_v2f gelu2_k(lg_v2f x, const GKold& k) { return gelu2_scaled(x, k.c1, k.hr); }
-
-template <int NP, class GK>
-__device__ __forceinline__ lg_v2f geluN(lg_v2f x, const GK& k) {
+template <int NP>
+__device__ __forceinline__ lg_v2f geluN(lg_v2f x, const GeluK& k) {
     if constexpr (NP == 2) return gelu2_k(x, k);
     else return gelu2_t<true>(x);
 }
@@ -143,15 +113,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     float* sPar = reinterpret_cast<float*>(smem_raw + OFF_PAR);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, c_ = lane & 15, c = c_;
     const int uwave = __builtin_amdgcn_readfirstlane(wave);   // provably wave-uniform: branches on it are scalar branches
-    unsigned slot_par = 0;
-    if (LG_XR_TURN) {   // requested first thing, used behind the first step's barrier
-        const unsigned hw = __builtin_amdgcn_s_getreg((12 - 1) << 11 | 4 << 6 | 4);    // HW_REG_HW_ID (4) bits [15:4]: simd [1:0], pipe [3:2], cu [7:4], sh [8], se [11:9]
-        const unsigned xcc = __builtin_amdgcn_s_getreg((3 - 1) << 11 | 0 << 6 | 20);   // HW_REG_XCC_ID (20) bits [2:0]
-        const unsigned key = (xcc << 10) | (((hw >> 9) & 7u) << 7) | (((hw >> 8) & 1u) << 6) | (((hw >> 4) & 15u) << 2) | (hw & 3u);
-        unsigned old_ = 0;
-        if (lane == 0) old_ = atomicXor(&g_xr_turn[key & 8191u], 1u);
-        slot_par = (unsigned)__builtin_amdgcn_readfirstlane((int)old_) & 1u;
-    }
     const int h = a2_.h, w = a2_.w;
     // The workgroup's strips.  One stage in the launch: strips blockIdx.x, + gridDim.x, ... and ONE pass of the segment loop below.  Several stages
     // (kernels.h: StageSel; strips ascend with the sample, so a stage is a contiguous range of them): a contiguous run of strips, cut into one segment
@@ -188,11 +149,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     if (NP == 2) { sx = uniform_f(a1.scales[0]); sa1 = uniform_f(a1.scales[1]); sa3 = uniform_f(a1.scales[2]); sw1 = uniform_f(a1.scales[3]); sw2 = uniform_f(a1.scales[4]); sw3 = uniform_f(a1.scales[5]); }
     const float S1 = sx * sw1, S2 = sa1 * sw2, S3 = sa3 * sw3;
     const float inv2 = 1.0f / S2, inv3 = 1.0f / S3;   // (powers of two: exact)
-#ifdef LG_XR_OLDGELU   // A/B build: rounds 2 - 5's GELU sequence (common.h gelu2_scaled)
-    const xr::GKold gk1 = {0.70710678118654752440f / S1, 0.5f * sa1 / S1}, gk3 = {0.70710678118654752440f, 0.5f * sa3};
-#else
     const GeluK gk1 = gelu_k(0.70710678118654752440f / S1, 0.5f * sa1 / S1), gk3 = gelu_k(0.70710678118654752440f, 0.5f * sa3);   // S1 h1 -> s_a1 gelu(h1); h3 -> s_a3 gelu(h3)
-#endif
 
     // strip -> (column strip, sample, rows [Y0, Yend)).  dS != 0 (launcher: exactly two strips per CU, one per workgroup): the rows of two vertically adjacent
     // strips are split UNEVENLY, SH + dS to the strip of a workgroup of the first half of the grid and SH - dS to its neighbour's in the second half.  The
@@ -309,9 +266,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
         int tx_i, Y0, Yend;
         long b;
         strip_geo(strip, tx_i, b, Y0, Yend);
-#ifdef LG_XR_SAMEX   // diagnostic: every workgroup reads (and writes) sample 0 (results wrong)
-        b = 0;
-#endif
         const int x0 = tx_i * TX;
 
         // x vector of the lane's pixel of halo block blk of the row block starting at ya: unconditional, from a clamped (always valid) address
@@ -374,7 +328,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
                 xb1[nb] = (u32x4_t){h01, h23, l01, l23};
                 xb2[nb] = (u32x4_t){h01, h23, 0u, 0u};
             }
-            XR_FENCE();
+            __builtin_amdgcn_sched_barrier(0);
             // ---- GEMM1: every tile's MFMAs are issued before the first GELU reads a result
             f32x4_t a1c[NB][NMT];
 #pragma unroll
@@ -390,7 +344,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 #pragma unroll
             for (int s = 0; s < NS; ++s) { wh[s] = sW[(NF1 + 2 * (S0 + s)) * 64 + lane]; wl[s] = sW[(NF1 + 2 * (S0 + s) + 1) * 64 + lane]; }
             if (PART != 2) b2v = *reinterpret_cast<const float4*>(sPar + P_B2 + 4 * g);
-            XR_FENCE();
+            __builtin_amdgcn_sched_barrier(0);
             // ---- GELU -> f16 pairs of s_a1 gelu(h1): hi / lo [tile][channel pair]
             uint32_t ghi[NB][NMT][2], glo[NB][NMT][2];
 #pragma unroll
@@ -403,7 +357,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
                     pairN<NP>(a23.x, a23.y, ghi[nb][i][1], glo[nb][i][1]);
                     asm volatile("" : "+v"(ghi[nb][i][0]), "+v"(glo[nb][i][0]), "+v"(ghi[nb][i][1]), "+v"(glo[nb][i][1]));
                 }
-                XR_FENCE();
+                __builtin_amdgcn_sched_barrier(0);
             }
             // ---- GEMM2 (K = 64: two 32-deep steps, k-slot j of step s = channel 16 (2 s + (j >> 2)) + 4 g + (j & 3)) -> ring (+ save)
             // h2 = (b2 + k-step 0) mk + (k-step 1) mk, the two k-steps in accumulators of their own and joined by ONE fma: the form in which a
@@ -416,7 +370,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
                     const float mk = geo[nb].mk;
                     float4 hh = make_float4(k0[nb][0] * mk, k0[nb][1] * mk, k0[nb][2] * mk, k0[nb][3] * mk);
                     if (PART == 0) hh = make_float4(__builtin_fmaf(k1[nb][0], mk, hh.x), __builtin_fmaf(k1[nb][1], mk, hh.y), __builtin_fmaf(k1[nb][2], mk, hh.z), __builtin_fmaf(k1[nb][3], mk, hh.w));
-                    if (SAVE && PART == 0 && geo[nb].inner) XR_ST2(a1.h2, geo[nb].prow + 16 * mt2, hh);
+                    if (SAVE && PART == 0 && geo[nb].inner) HS<BF>::st4(a1.h2, geo[nb].prow + 16 * mt2, hh);
                     if (geo[nb].rp >= 0) *reinterpret_cast<float4*>(ring + geo[nb].rp * LDR + 16 * mt2 + 4 * g) = hh;
                 }
             };
@@ -446,7 +400,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
                 if (mt2 > 0) leave(mt2 - 1, accp0, accp1);   // the previous tile's results leave while this tile's MFMAs run
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb) { accp0[nb] = acc0[nb]; accp1[nb] = acc1[nb]; }
-                XR_FENCE();
+                __builtin_amdgcn_sched_barrier(0);
             }
             leave(3, accp0, accp1);
             if (PART == 2) *geo_out = geo[0];
@@ -493,7 +447,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
                 xb1[nb] = (u32x4_t){h01, h23, l01, l23};
                 xb2[nb] = (u32x4_t){h01, h23, 0u, 0u};
             }
-            XR_FENCE();
+            __builtin_amdgcn_sched_barrier(0);
             f32x4_t a1c[2][4];
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb)
@@ -506,7 +460,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 #pragma unroll
             for (int s = 0; s < 2; ++s) { wh[s] = sW[(NF1 + 2 * s) * 64 + lane]; wl[s] = sW[(NF1 + 2 * s + 1) * 64 + lane]; }
             float4 b2v = *reinterpret_cast<const float4*>(sPar + P_B2 + 4 * g);
-            XR_FENCE();
+            __builtin_amdgcn_sched_barrier(0);
             uint32_t ghi[2][4][2], glo[2][4][2];
             auto gelu_tile = [&](int nb, int i) {
                 const lg_v2f a01 = geluN<NP>((lg_v2f){a1c[nb][i][0], a1c[nb][i][1]}, gk1);
@@ -541,11 +495,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
                 const float mk = geo[nb].mk;
                 const float4 hh = make_float4(__builtin_fmaf(acc.k1[0], mk, acc.k0[0] * mk), __builtin_fmaf(acc.k1[1], mk, acc.k0[1] * mk),
                                               __builtin_fmaf(acc.k1[2], mk, acc.k0[2] * mk), __builtin_fmaf(acc.k1[3], mk, acc.k0[3] * mk));
-                if (SAVE && geo[nb].inner) XR_ST2(a1.h2, geo[nb].prow + 16 * mt2, hh);
+                if (SAVE && geo[nb].inner) HS<BF>::st4(a1.h2, geo[nb].prow + 16 * mt2, hh);
                 *reinterpret_cast<float4*>(ring + geo[nb].rp * LDR + 16 * mt2 + 4 * g) = hh;
             };
 #pragma unroll
-            for (int i = 0; i < 4; ++i) { gelu_tile(0, i); XR_FENCE(); }
+            for (int i = 0; i < 4; ++i) { gelu_tile(0, i); __builtin_amdgcn_sched_barrier(0); }
             Acc2 accp;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {        // block A's GEMM2 tile j beside block B's GELU of tile j
@@ -554,7 +508,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
                 gelu_tile(1, j);
                 if (j > 0) leave(0, j - 1, accp);
                 accp = acc;
-                XR_FENCE();
+                __builtin_amdgcn_sched_barrier(0);
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {        // block B's GEMM2; the previous tile's results leave beside it
@@ -562,7 +516,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
                 if (j < 3) next_w2(j + 1);
                 leave(j > 0 ? 1 : 0, j > 0 ? j - 1 : 3, accp);
                 accp = acc;
-                XR_FENCE();
+                __builtin_amdgcn_sched_barrier(0);
             }
             leave(1, 3, accp);
         };
@@ -575,7 +529,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
                 float4 r = *rp4;
                 r = make_float4(__builtin_fmaf(part[mt2][0], ge.mk, r.x), __builtin_fmaf(part[mt2][1], ge.mk, r.y), __builtin_fmaf(part[mt2][2], ge.mk, r.z), __builtin_fmaf(part[mt2][3], ge.mk, r.w));
                 *rp4 = r;
-                if (SAVE && ge.inner) XR_ST2(a1.h2, ge.prow + 16 * mt2, r);
+                if (SAVE && ge.inner) HS<BF>::st4(a1.h2, ge.prow + 16 * mt2, r);
             }
         };
 
@@ -615,7 +569,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
             // next step's halo operands: in flight across the spatial phase (clamped addresses: harmless behind the last step)
             xh[0] = xload(y0 + TY + 1, 2 * wave); xh[1] = xload(y0 + TY + 1, 2 * wave + 1); xh[2] = xload(y0 + TY + 1, 8);
             __syncthreads();     // ring rows y0 - 1 .. y0 + 8 complete (but for the ninth block's second half)
-            XR_TAKE_TURNS();
             XSTAMP(3);
             if (role == 3) ninth_add(part9, geo9);
             // ---- spatial phase: tile rows ty0, ty0 + 1: dw3x3 over the ring -> gelu -> GEMM3 -> + bias + residual -> y (+ planar LN half)
@@ -680,7 +633,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
                     }
 #pragma unroll
                     for (int dx = 0; dx < 3; ++dx) rv[dx] = rvn[dx];
-                    XR_FENCE();
+                    __builtin_amdgcn_sched_barrier(0);
                 }
                 // GEMM3's fragments, bias, the next block's LayerNorm affine: requested in front of the GELUs
                 u32x4_t w3h[2], w3l[2];
@@ -695,9 +648,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
                     uint32_t phi[4][2], plo[4][2];
 #pragma unroll
                     for (int m = 0; m < 4; ++m) {
-#ifndef LG_XR_NOH3   // diagnostic A/B: what not saving h3 would buy the forward (VERDICT r5 lever b)
-                        if (SAVE && ok && a2.a3s) XR_ST3(a2.a3s, ((b * h + y) * (long)w + x) * N1 + 16 * m + 4 * g, make_float4(h3[r2][m][0], h3[r2][m][1], h3[r2][m][2], h3[r2][m][3]));
-#endif
+                        if (SAVE && ok && a2.a3s) HS<BF>::st4(a2.a3s, ((b * h + y) * (long)w + x) * N1 + 16 * m + 4 * g, make_float4(h3[r2][m][0], h3[r2][m][1], h3[r2][m][2], h3[r2][m][3]));
                         const lg_v2f a01 = geluN<NP>((lg_v2f){h3[r2][m][0], h3[r2][m][1]}, gk3);
                         const lg_v2f a23 = geluN<NP>((lg_v2f){h3[r2][m][2], h3[r2][m][3]}, gk3);
                         pairN<NP>(a01.x, a01.y, phi[m][0], plo[m][0]);
@@ -712,22 +663,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
                     }
                     // ---- epilogue in registers: residual, store, LayerNorm statistics of the next block across the four lane groups
                     const float o0 = o[0] * inv3 + xres[r2].x, o1 = o[1] * inv3 + xres[r2].y, o2 = o[2] * inv3 + xres[r2].z, o3 = o[3] * inv3 + xres[r2].w;
-#ifdef LG_XR_NOSTORE   // diagnostic: no output traffic (results wrong)
-                    if (ok && o0 == 12345.678f) *reinterpret_cast<float4*>(a2.y + ((b * h + y) * (long)w + x) * E + 4 * g) = make_float4(o0, o1, o2, o3);
-#else
                     if (ok) *reinterpret_cast<float4*>(a2.y + ((b * h + y) * (long)w + x) * E + 4 * g) = make_float4(o0, o1, o2, o3);
-#endif
                     if (a2.g) {
                         const float s = xg_sum((o0 + o1) + (o2 + o3));
                         const float mu = s * (1.0f / E);
                         const float d0 = o0 - mu, d1 = o1 - mu, d2 = o2 - mu, d3 = o3 - mu;
                         const float vs = xg_sum((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
                         const float rstd = __builtin_amdgcn_rsqf(vs * (1.0f / E) + LG_EPS);
-#ifdef LG_XR_NOSTORE
-                        if (ok && g >= 2 && d0 == 12345.678f) {
-#else
                         if (ok && g >= 2) {      // channels 8..15 = the global-mixer half, planar [B, e/2, h, w]
-#endif
                             const long hw = (long)h * w, sp = (long)y * w + x;
                             float* dst = a2.g + (b * (E / 2) + (4 * g - E / 2)) * hw + sp;
                             dst[0] = d0 * rstd * ng.x + nbv.x;
@@ -736,12 +679,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
                             dst[3 * hw] = d3 * rstd * ng.w + nbv.w;
                         }
                     }
-                    XR_FENCE();
+                    __builtin_amdgcn_sched_barrier(0);
                 }
             }
             XSTAMP(4);
             __syncthreads();     // the ring rows this step read are free for the next step's halo pass
-            XR_TAKE_TURNS();
             XSTAMP(5);
         }   // steps of the strip
     }   // strips of this segment
@@ -753,13 +695,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 XrGeo ffn_xr_geometry(int h, int w, int B, int Bs, int n, int grid_cap) {
     // several stages in the launch: the strip height of ONE stage's launch, so that a workgroup gets whole strips of that size -- three at 3 x 32 pairs
     const bool multi = n > 1;
-    XrGeo q{strip_geometry(h, w, B, multi ? Bs : B, LG_XR_GRID, multi ? grid_cap : 0), 0};
+    XrGeo q{strip_geometry(h, w, B, multi ? Bs : B, xr::GRID, multi ? grid_cap : 0), 0};
     const int SH = q.SH;
     // uneven split of strip pairs (strip_geo in the kernel): only in the shapes it was measured in, exactly two workgroups per CU.  One stage: one strip per
     // workgroup.  Several: the 512 resident workgroups (a capped grid is smaller and keeps the even strip runs), each pair of them on a run of strip pairs.
-    const bool shape_ok = LG_XR_GRID == 512 && (q.strips_y & 1) == 0 && SH >= 32 && h % (2 * SH) == 0;
-    if (!multi && LG_XR_UNEVEN && q.nstrips == LG_XR_GRID && shape_ok) q.dS = (SH * LG_XR_UNEVEN / 64 + 7) / 8 * 8;
-    if (multi && LG_XR_MULTI_UNEVEN && q.grid == LG_XR_GRID && (q.grid & 1) == 0 && shape_ok) q.dS = (SH * LG_XR_MULTI_UNEVEN / 64 + 7) / 8 * 8;
+    const bool shape_ok = xr::GRID == 512 && (q.strips_y & 1) == 0 && SH >= 32 && h % (2 * SH) == 0;
+    if (!multi && xr::UNEVEN && q.nstrips == xr::GRID && shape_ok) q.dS = (SH * xr::UNEVEN / 64 + 7) / 8 * 8;
+    if (multi && xr::MULTI_UNEVEN && q.grid == xr::GRID && (q.grid & 1) == 0 && shape_ok) q.dS = (SH * xr::MULTI_UNEVEN / 64 + 7) / 8 * 8;
     return q;
 }
 

@@ -93,9 +93,7 @@ struct optim_args {
 // `b / c`, sqrt are rounded on their own, `a + s * x` (add with alpha, addcmul, addcdiv, lerp) is one fused multiply-add as the
 // compiler contracts it in torch's kernels -- so that a run fed the same gradients lands on the same bits as `fused=False`.
 // Contraction is switched off for the kernel and every fma is written out.
-#ifndef LG_OPT_FMA
 #define LG_OPT_FMA(a, b, c) __builtin_fmaf(a, b, c)
-#endif
 template <int ALGO, int OPT, int CTL>
 __global__ __launch_bounds__(256) void k_optim(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0,
                                                float* __restrict__ s1, float* __restrict__ s2, const int64_t* __restrict__ ranges,

@@ -185,10 +185,7 @@ __global__ __launch_bounds__(256) void k_embed(EmbedArgs a) {
     ln_stats<E>(e, mu, rstd);
 #pragma unroll
     for (int n = 0; n < E; ++n) e[n] = (e[n] - mu) * rstd * a.lng[n] + a.lnb[n];
-#ifndef LG_EMBED_TR
-#define LG_EMBED_TR 1
-#endif
-    if (LG_EMBED_TR && a.total % 64 == 0) {
+    if (a.total % 64 == 0) {
         // the NHWC rows leave COALESCED: the wave's 64 pixel vectors pass through a wave-private LDS image and every store instruction
         // writes 1 KB of consecutive bytes (lane -> (pixel 16 j + lane / Q4, quad lane % Q4)); as one row per lane a store instruction is
         // 64 separate 16-byte pieces at a 64- / 128-byte stride

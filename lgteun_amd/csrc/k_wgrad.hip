@@ -24,16 +24,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // lanes and 2 loads feed 16 MFMAs.  Output acc[i][j][v] (MFMA row 4g+v, col r) is then dW[n0 + 4(4g+v) + i][k0 + 4r + j].
 // Non-VEC: scalar loads in the natural tile order (tile t = channels 16t .. 16t+15), columns >= n_valid / k_valid read as 0.
 // 4-pixel MFMA steps per batch: narrow blocks have few MFMAs per pixel, so they keep more pixels in flight
-#ifndef LG_WGRAD_VEC_U
-#define LG_WGRAD_VEC_U 4
-#endif
-#ifndef LG_WGRAD_WGS
-#define LG_WGRAD_WGS 512
-#endif
-#ifndef LG_WGRAD_INTERLEAVE
-#define LG_WGRAD_INTERLEAVE 1   // 0: one contiguous pixel range per wave (A/B: the 16-wide blocks run 35 -> 31.5 us interleaved, the 64 x 64 ones the same)
-#endif
-__host__ __device__ constexpr int wgrad_batch(int nt, int kt, bool vec) { return vec ? LG_WGRAD_VEC_U : (nt + kt <= 2 ? 16 : (nt + kt <= 4 ? 8 : 4)); }
+constexpr int WGRAD_VEC_U = 4;     // the VEC blocks' steps per batch
+constexpr int WGRAD_WGS = 512;     // workgroups of a launch (wgrad_splits): two waves per SIMD
+__host__ __device__ constexpr int wgrad_batch(int nt, int kt, bool vec) { return vec ? WGRAD_VEC_U : (nt + kt <= 2 ? 16 : (nt + kt <= 4 ? 8 : 4)); }
 
 // XGELU: the stored X is a pre-activation and the conv input is gelu(X) (feed_forward's second and third 1x1 convs when the forward
 // saved h1 / h3 instead of gelu(h1) / gelu(h3)): evaluated on the operand registers, under the loads of the next batch
@@ -45,18 +38,12 @@ __global__ __launch_bounds__(256) void k_wgrad_t(WgradArgs a, int k_blocks, long
     const int nb = blockIdx.y / k_blocks, kb = blockIdx.y - nb * k_blocks;
     const int n0 = nb * NB, k0 = kb * KB;
     const long slice = (long)blockIdx.x * 4 + wave;
-#if LG_WGRAD_INTERLEAVE
     // batches of 4 U pixels dealt round-robin to the waves of the grid: at any moment the whole grid reads ONE contiguous window of the
-    // operands (all HBM channels), instead of 2 048 streams that all sit at the same offset of their own 64 KiB-aligned chunk
+    // operands (all HBM channels), instead of 2 048 streams that all sit at the same offset of their own 64 KiB-aligned chunk (against one
+    // contiguous range of px_per_wave pixels per wave, an argument no longer read: the 16-wide blocks run 35 -> 31.5 us interleaved, the 64 x 64 ones the same)
     const long p_stride = (long)gridDim.x * 4 * (4 * U);
     const long p_begin = slice * (4 * U);
     const long p_end = a.P;
-#else
-    const long p_stride = 4 * U;
-    const long p_begin = slice * px_per_wave;
-    long p_end = p_begin + px_per_wave;
-    if (p_end > a.P) p_end = a.P;
-#endif
     f32x4 acc[NT][KT];
     float bsum[NT];
 #pragma unroll
@@ -563,9 +550,6 @@ int ReduceQueue::flush() {
     }
     if (total <= 0 || total > 0x3fffffffL) { lg_set_error("reduce queue: %ld workgroups in one launch", total); return -4; }
     im.nheads = nheads; im.njobs = nj; im.total_wgs = (int)total;
-#ifdef LG_RQ_DEBUG
-    fprintf(stderr, "[rq] flush: %d jobs, %d chains, %ld workgroups\n", nj, nheads, total);
-#endif
     const int rc = launch_image(im, stream);
     if (g_rq_stats[3].load() < nj) g_rq_stats[3] = nj;
     if (g_rq_stats[5].load() < nheads) g_rq_stats[5] = nheads;
@@ -659,7 +643,7 @@ static int tiles_per_block(int n16) {   // largest of 4,3,2,1 dividing the tile 
 }
 static long wgrad_splits(int N, int K) {
     const int blocks = (N / 16 / tiles_per_block(N / 16)) * (K / 16 / tiles_per_block(K / 16));
-    long splits = LG_WGRAD_WGS / blocks;   // two waves per SIMD
+    long splits = WGRAD_WGS / blocks;
     return splits < 1 ? 1 : splits;
 }
 size_t wgrad_slab_floats(int N, int K, long P) {

@@ -52,7 +52,7 @@ static void resolve_ffn(const lg_config& cfg, int e, int h, int w, FfnRoute& f) 
     const bool xr_built = split && !(v & LG_VAR_FFN_XS) && (f.hbf || f.scales);   // k_ffn_xr has bf16 and f16-pair instances
     if (e == 16 && f.dw == FFN_DWBWD_XS && (v & LG_VAR_FFN_H3_RECOMPUTE) && xr_built && !f.hbf) f.dw = FFN_DWBWD_H;
     f.bwd_scales = f.px == FFN1_BWD_XS && f.dw != FFN_DWBWD_TILE && f.scales && !(v & LG_VAR_FFN_BWD_BF16X3);
-    f.wgrad_w2 = f.px != FFN1_BWD_XS && !ffn1_bwd_fuses_w2(e, f.pre);
+    f.wgrad_w2 = f.px != FFN1_BWD_XS;
     f.wgrad_w1 = f.px != FFN1_BWD_XS && !ffn1_bwd_fuses_w1(e);
     f.wgrad_w3 = f.dw == FFN_DWBWD_TILE;
 

@@ -124,10 +124,7 @@ __device__ __forceinline__ void mfma_split16(f32x4_t& acc, const s16x4_t (&a)[3]
 // of a lane = one piece pair, 4..7 = another; both operands use the same order, and any order of K is a sum).  v_mfma_f32_16x16x16_bf16
 // costs the matrix pipe what the 32-deep form costs (16 busy cycles each, profiles/r03_sq_counters_*), so this halves the pipe time of a
 // K = 16 product at the price of the concatenations:  a1 b3 + a3 b1 | a2 b2 + a2 b1 | a1 b2 + a1 b1   (small terms first).
-// Whether that pays is measured per kernel: each caller hands mfma_np16 its own switch (LG_SPLIT16_PAIR, LG_KB_PAIR, LG_KA_PAIR).
-#ifndef LG_SPLIT16_PAIR
-#define LG_SPLIT16_PAIR 1   // the forward k_ffn_xs and the W3^T dy product of k_ffn_dw_bwd_h
-#endif
+// Whether that pays is measured per kernel (mfma_np16's PAIR): yes in k_ffn_xs, k_ffn_dw_bwd_h and k_ffn1_bwd_xs, no in k_ffn_dw_bwd_xs.
 __device__ __forceinline__ bf16x8_t sb_cat8(s16x4_t lo, s16x4_t hi) {
     typedef short s16x8_t __attribute__((ext_vector_type(8)));
     return __builtin_bit_cast(bf16x8_t, (s16x8_t)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
@@ -255,7 +252,7 @@ __device__ __forceinline__ void mfma_np32(f32x4_t& acc, const WFrag32& w, bf16x8
         acc = sb_mfma_h(w.p[0], x1, acc);
     } else acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.p[0], x1, acc, 0, 0, 0);
 }
-// PAIR: the NP = 3 products in their paired form (mfma_split16_pair); the caller's own measured switch
+// PAIR: the NP = 3 products in their paired form (mfma_split16_pair); the caller's own measured choice
 template <int NP, bool PAIR>
 __device__ __forceinline__ void mfma_np16(f32x4_t& acc, const s16x4_t (&a)[3], const s16x4_t (&b)[3]) {
     if (NP == 3) { if (PAIR) mfma_split16_pair(acc, a, b); else mfma_split16(acc, a, b); }

@@ -137,7 +137,7 @@ def test_cancelling_sum_gradient_kinds_band_against_band(manifest, name):
            cases, whose FFT mixer runs Bluestein lines: their offset (up to 2.8 x at 208 x 176) is deterministic fp32 arithmetic of another
            algorithm (pocketfft's mixed radix on the reference's side), which nudged inputs do not average out.
     A one-draw comparison cannot tell "inside the band" from "a 3 x wider band"; this can.  What it can and cannot see, checked with
-    k_attn_bwd_f's pos_emb accumulation degraded on purpose (`-DLG_DEGRADE_DPOS` variant builds, LGTEUN_HIP_LIB): a 5 % error in what
+    k_attn_bwd_f's pos_emb accumulation degraded on purpose (a scratch build that is not kept, loaded through LGTEUN_HIP_LIB): a 5 % error in what
     enters the pos_emb gradient turns (ii) red at 208 x 176 (4.65 against its limit 3; 2.76 without) and moves grad_c4_k4_p128 from 0.50
     to 1.9 of its limit 2; rounding every dS to bf16 before it is added changes nothing measurable (0.93 -> 0.94): random 2^-9 errors
     of 16 k terms average out far below the band the reference's own fp32 arithmetic has.  Errors below ~5 % of these kinds are inside

@@ -72,7 +72,7 @@ def _check_geometry(n):
     uneven8, u8, quads8, per8, grid8 = _decision(8, PAN, n)[:5]
     assert (uneven8, quads8, per8, grid8) == (1, 1024 * n, 1024, 512) and u8 != 4
     # k_attn_m<16>: 3 quads per CU.  The default build leaves this instance on even runs (its uneven launch measured slower: csrc/k_attn_m.hip,
-    # LG_ATTN_MULTI_UNEVEN16); a build with that macro at 5 takes 2 : 1 here, and everything below holds for it unchanged
+    # am::MULTI_UNEVEN16); a build with that constant at 5 takes 2 : 1 here, and everything below holds for it unchanged
     uneven16, u16, quads16, per16, grid16 = _decision(16, PAN // 2, n)[:5]
     assert (quads16, per16, grid16) == (256 * n, 256, 512) and uneven16 == (u16 != 4)
     a8_cross, a16_cross = _crossing(1, quads8, per8, grid8, u8), _crossing(1, quads16, per16, grid16, u16)

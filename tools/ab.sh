@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of library builds (boxes differ by several per cent, so only alternating runs inside ONE gpurun call compare):
 #   [AB_ROUNDS=n] [AB_ARGS='--config c3'] bash tools/ab.sh [--prof-kernel K] libA.so libB.so [...]      (paths relative to the repo root; 3 alternating rounds)
-# prints ms/step and the live-timed kernel's average per run.  Build variants with:  make LIB=build_variants/x.so FLAGS+=-DSOMETHING
+# prints ms/step and the live-timed kernel's average per run.  Build variants with tools/mkvariant.sh (a stamp build, or an edited source)
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 PK=ffn
 if [ "$1" = "--prof-kernel" ]; then PK=$2; shift 2; fi

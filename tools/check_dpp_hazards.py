@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """gfx9 DPP hazard check on compiler output (hipcc -S --cuda-device-only): a VALU instruction that writes a VGPR must be followed by 2 wait states before an
 instruction reads that VGPR as its DPP source (src0 of a *_dpp instruction).  The compiler's hazard recogniser inserts them for its own DPP instructions but
-does not look inside inline asm -- k_attn_bwd_f.hip's row_newbcast multiply-adds are inline asm.  Prints every violation; exit code 1 if there is one.
+does not look inside inline asm (written for k_attn_bwd_f.hip's row_newbcast multiply-adds, an experiment no longer in the source).  Prints every violation; exit code 1 if there is one.
 usage: python tools/check_dpp_hazards.py file.s [...]"""
 import re
 import sys
