@@ -290,7 +290,9 @@ const char* lg_kernel_name(int32_t kernel_id);
  * same mask without storing it, and an integrator can reproduce it.  n elements from index `first`; out is a device pointer. */
 int lg_dropout_mask(uint64_t seed, int32_t stage, int32_t blk, int64_t first, int64_t n, float* out, void* stream);
 
-/* ---- per-op entry points (unit-tested against the oracle; same kernels the orchestrators launch) ---- */
+/* ---- per-op entry points (unit-tested against the oracle; same kernels the orchestrators launch) ----
+ * tests/test_gpu_composition.py holds the orchestrators to them: a network composed by hand from lg_op_resample, lg_op_data_step, lg_op_lgt,
+ * lg_op_lgt_bwd and lg_op_data_step_bwd gives the bits of lgteun_forward / lgteun_dead_forward / lgteun_backward, faithful, live and chained. */
 /* bmu.sampling_ bicubic (basic_module_unformer_v2.py:21-23): mode 0: x0.5, 1: x2, 2: x4.  x [planes,hi,wi]. */
 int lg_op_resample(const float* x, float* y, int32_t planes, int32_t hi, int32_t wi, int32_t mode, void* stream);
 /* one data step (unlg_former.py:58-61) for stage `stage`: z_in -> z_out [B,C,H,W]; tmp: 3*B*C*H*W/4 + B*H*W floats (the chain's three

@@ -86,6 +86,14 @@ def assert_workspace_guards(buf, what):
     assert bool(lo.all()) and bool(hi.all()), (what, 'written outside the workspace', int((~lo).sum()), int((~hi).sum()))
 
 
+def assert_bitwise(g0, g1, eng, what):
+    """two flat gradient buffers of `eng`'s layout are equal float by float, the padding between the tensors included; names the tensors that differ"""
+    if torch.equal(g0, g1):
+        return
+    bad = [eng.names[i] for i, (o, p) in enumerate(zip(eng.offsets, eng.params)) if not torch.equal(g0[o:o + p.numel()], g1[o:o + p.numel()])]
+    raise AssertionError((what, 'gradients differ in', bad[:12], len(bad)))
+
+
 class Ops:
     def __init__(self, net, H, W, ws_fill=None):
         """ws_fill=None: the engine's cached torch.empty workspace.  A key of WS_FILLS: every call runs on a guarded workspace of the test's own
@@ -182,11 +190,15 @@ class Ops:
             assert_guards_intact(buf, 'lg_op_block')
         return y
 
-    def _grads(self, owned):
-        """the flat gradient buffer of a per-op backward.  owned=None: plain zeros.  owned=[names]: a guarded view whose owned tensors start at
+    def _grads(self, owned, grads=None):
+        """the flat gradient buffer of a per-op backward.  grads=<tensor>: the caller's own buffer, carried from call to call (the entries ADD into
+        it); it is used as it is, without sentinel.  owned=None: plain zeros.  owned=[names]: a guarded view whose owned tensors start at
         zero and whose every other float (the 16-byte padding between tensors included) starts as a finite sentinel of tiny magnitude,
         2^-100 x (1 + index mod 251): a stray store or a stray `+=` of anything non-zero changes its bits, where NaN would hide the `+=`"""
         flat = self.eng.flat
+        if grads is not None:
+            assert owned is None and grads.shape == flat.shape and grads.dtype == flat.dtype and grads.device == flat.device and grads.is_contiguous()
+            return None, grads
         if owned is None:
             return None, torch.zeros_like(flat)
         buf, grads = guarded_empty((flat.numel(),), flat.device)
@@ -210,11 +222,11 @@ class Ops:
             owners = sorted({self.eng.names[max(j for j, o in enumerate(self.eng.offsets) if o <= i)] for i in at})
             assert False, (what, 'gradient floats that are not its own were written', int(moved.sum()), at, owners)
 
-    def block_bwd(self, stage, blk, which, x, dy, guard=False, owned=None):
+    def block_bwd(self, stage, blk, which, x, dy, guard=False, owned=None, grads=None):
         """returns (dx, flat_param_grads).  which 0: dy/dx planar [B,e/2,h,w]; 1,2: NHWC.  guard / owned: see _out / _grads"""
         B = x.shape[0]
         buf, dx = self._out(dy.shape, dy.device, guard)
-        state, grads = self._grads(owned)
+        state, grads = self._grads(owned, grads)
         ws = self.ws(B, train=True)
         _lib.check(self.lib.lg_op_block_bwd(self.plan, _ptr(self.eng.flat), _ptr(grads), stage, blk, which, _ptr(x), _ptr(dy),
                                             _ptr(dx), _ptr(ws), ws.numel(), B, _stream_ptr()), 'lg_op_block_bwd')
@@ -224,11 +236,11 @@ class Ops:
         self._grads_intact(state, grads, 'lg_op_block_bwd')
         return dx, grads
 
-    def data_step_bwd(self, stage, z, ms, pan, dz_out, guard=False, owned=None):
+    def data_step_bwd(self, stage, z, ms, pan, dz_out, guard=False, owned=None, grads=None):
         """returns (dz_in, flat_param_grads) of one data step"""
         B = z.shape[0]
         buf, dz = self._out(z.shape, z.device, guard)
-        state, grads = self._grads(owned)
+        state, grads = self._grads(owned, grads)
         ws = self.ws(B, train=True)
         _lib.check(self.lib.lg_op_data_step_bwd(self.plan, _ptr(self.eng.flat), _ptr(grads), stage, _ptr(z), _ptr(ms), _ptr(pan),
                                                 _ptr(dz_out), _ptr(dz), _ptr(ws), ws.numel(), B, _stream_ptr()), 'lg_op_data_step_bwd')
@@ -238,11 +250,11 @@ class Ops:
         self._grads_intact(state, grads, 'lg_op_data_step_bwd')
         return dz, grads
 
-    def lgt_bwd(self, stage, z, dout, flags=0, seed=0, guard=False, owned=None):
+    def lgt_bwd(self, stage, z, dout, flags=0, seed=0, guard=False, owned=None, grads=None):
         """returns (dz, flat_param_grads) of one LGT; flags: 0 or LG_FLAG_DROPOUT (with seed)"""
         B = z.shape[0]
         buf, dz = self._out(z.shape, z.device, guard)
-        state, grads = self._grads(owned)
+        state, grads = self._grads(owned, grads)
         ws = self.ws(B, train=True)
         _lib.check(self.lib.lg_op_lgt_bwd(self.plan, _ptr(self.eng.flat), _ptr(grads), stage, _ptr(z), _ptr(dout), _ptr(dz), _ptr(ws),
                                           ws.numel(), B, flags, seed, _stream_ptr()), 'lg_op_lgt_bwd')

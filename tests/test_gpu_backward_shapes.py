@@ -70,6 +70,10 @@ Measured on an MI355X (ratio = element-wise error of dx over the fp32 oracle's; 
   1389 gradient lines in all; 19 of them are above 8 x the fp32 oracle's figure (worst 19 x: the FFN's LayerNorm bias at (9,128,128), 7.7e-06 against
   4.5e-07 -- a sum over 1.5e5 pixels of split-arithmetic products) and pass on G; every other line passes on the fp32 yardstick alone.
   The file: 77 tests in 27 s on the MI355X machine, the slowest case 4.6 s (FFN C=8 blk=0 (9,128,128): fp64 + fp32 autograd over 1.5e5 pixels x 128 channels).
+  The per-op entries at other stage indices (stages 0 and 2 of K = 3, at the smallest LGT and data-step shape of each C; every other stage's slots the
+  sentinel; the fp32 oracle clean on the first draw of all eight, no RESEED entry): one LGT, dz rel-L2 3.7e-07 .. 3.6e-06 (the fp32 oracle's: 3.9e-07 ..
+  1.0e-05), the worst of the 4 x 119 gradient lines at 0.26 of its bar (C=8 stage 2, block 1's point_conv.weight: 2.6e-05, fp32 oracle 9.8e-06, G 1e-4);
+  the data step, dz ratio 1.00 on all four, the worst of the 4 x 13 gradient lines 2.2e-06 (R.bias, C=8 stage 2) against 2e-5.  85 tests with them.
 
 What it sees, checked once with three variant builds loaded through LGTEUN_HIP_LIB (arithmetic-only edits inside the buffers; nothing of them is kept):
   (a) k_ffn_dw_bwd_xs with the ring row below each strip left out of the depthwise transpose.  RED: every FFN case on the strip route whose planes
@@ -378,32 +382,43 @@ def _lgt_family(C):
     return family
 
 
-def _lgt_inputs(C, B, H, W):
-    seed = RESEED.get(('lgt', C, None, B, H, W), 0)
+def _lgt_inputs(C, B, H, W, stage=1, K=2):
+    seed = RESEED.get(('lgt', C, None if (stage, K) == (1, 2) else (stage, K), B, H, W), 0)
     z = lgt_input(C, B, H, W)
     if seed:
         z = T(np.random.default_rng(H + W + 100000 * seed).uniform(0, 1, tuple(z.shape)).astype(np.float32))
     return z, _dy(z.shape, 7, C, H, W, seed)
 
 
-@pytest.mark.parametrize('C,B,H,W', LGT_CASES)
-def test_one_lgt_backward_at_awkward_shapes(C, B, H, W):
-    """stage 1 of K = 2: stage 0's slots and the data-step tensors of the gradient buffer stay the sentinel; every one of the 119 tensors on its own
-    line.  dz: relative L2 and max-norm, no element-wise bar (the FFT mixers are inside)"""
-    tag = f'lgt bwd C={C} ({B},{H},{W})'
-    ops = _ops(C, H, W, K=2)
+def _stage_cases(cases, c_of):
+    """the cases at stage 1 of K = 2 under the ids they have always had, then stages 0 and 2 of K = 3 at the smallest shape of each C: the per-op
+    backward entries at the first stage and at a last stage that is not stage 1, each against its own stage's weights
+    (tests/test_gpu_composition.py strings the entries into networks)"""
+    out = [pytest.param(*c, 1, 2, id='-'.join(str(v) for v in c)) for c in cases]
+    for C in (4, 8):
+        small = min((c for c in cases if c_of(c) == C), key=lambda c: int(np.prod(c)) // C)
+        out += [pytest.param(*small, st, 3, id='-'.join(str(v) for v in small) + f'-stage{st}of3') for st in (0, 2)]
+    return out
+
+
+@pytest.mark.parametrize('C,B,H,W,stage,K', _stage_cases(LGT_CASES, lambda c: c[0]))
+def test_one_lgt_backward_at_awkward_shapes(C, B, H, W, stage, K):
+    """stage 1 of K = 2, and stages 0 and 2 of K = 3: the other stages' slots and the data-step tensors of the gradient buffer stay the sentinel; every
+    one of the 119 tensors on its own line.  dz: relative L2 and max-norm, no element-wise bar (the FFT mixers are inside)"""
+    tag = f'lgt bwd C={C} ({B},{H},{W})' + ('' if (stage, K) == (1, 2) else f' stage {stage} of {K}')
+    ops = _ops(C, H, W, K=K)
     for level, blk in ((0, 0), (1, 2)):
         _assert_route(ops, H, W, level, ffn=_ffn_route(C, blk, H, W), mixer=_mixer_route(C, blk))
-    z, dy = _lgt_inputs(C, B, H, W)
-    pre = 'prior_module.1.'
-    P64, P32 = _params(C, 2, torch.float64), _params(C, 2, torch.float32)
+    z, dy = _lgt_inputs(C, B, H, W, stage, K)
+    pre = f'prior_module.{stage}.'
+    P64, P32 = _params(C, K, torch.float64), _params(C, K, torch.float32)
     names = [n for n in P64 if n.startswith(pre)]
     assert len(names) == 119
     y64, dz64, g64 = _autograd(lambda P, v: orc.lgt(P, pre, v), P64, names, z, dy)
     y32, dz32, g32 = _autograd(lambda P, v: orc.lgt(P, pre, v), P32, names, z, dy)
     pre_fwd = rel_l2(y32, y64)
     _precondition(tag, 'lgt', pre_fwd, dz64, dz32)
-    dz, flat = ops.lgt_bwd(1, z.cuda(), dy.cuda(), guard=True, owned=names)
+    dz, flat = ops.lgt_bwd(stage, z.cuda(), dy.cuda(), guard=True, owned=names)
     den = float(dz64.abs().max())
     _dx_checks(tag, dz.cpu(), dz64, dz32, den, L2['lgt'], pre_fwd, bar=False)
     mx = _max_err(dz.cpu().double(), dz64, den)
@@ -411,15 +426,16 @@ def test_one_lgt_backward_at_awkward_shapes(C, B, H, W):
     _grad_checks(tag, ops, flat, names, g64, g32, _lgt_family(C))
 
 
-# ---- 5. data-step backward: stage 1 of K = 2
+# ---- 5. data-step backward: stage 1 of K = 2; stages 0 and 2 of K = 3
 DSTEP_CASES = FWD_DSTEP_CASES + [(3, 4, 128, 128)]
 
 
-@pytest.mark.parametrize('B,C,H,W', DSTEP_CASES)
-def test_data_step_backward_at_awkward_shapes(B, C, H, W):
-    """the tile kernels on planes that are no multiple of 32 and on a 4 x 4 MS plane; the one-launch form (64 x 64, 128 x 128) at an odd batch"""
-    tag = f'data step bwd C={C} ({B},{H},{W})'
-    ops = _ops(C, H, W, K=2)
+@pytest.mark.parametrize('B,C,H,W,stage,K', _stage_cases(DSTEP_CASES, lambda c: c[1]))
+def test_data_step_backward_at_awkward_shapes(B, C, H, W, stage, K):
+    """the tile kernels on planes that are no multiple of 32 and on a 4 x 4 MS plane; the one-launch form (64 x 64, 128 x 128) at an odd batch; stage 1 of
+    K = 2, and stages 0 and 2 of K = 3 (their own eta, every other stage's eta and every LGT tensor the sentinel)"""
+    tag = f'data step bwd C={C} ({B},{H},{W})' + ('' if (stage, K) == (1, 2) else f' stage {stage} of {K}')
+    ops = _ops(C, H, W, K=K)
     net_line = ops.eng.describe(H, W).splitlines()[0]
     assert ('dstep=fused' if (H, W) in ((64, 64), (128, 128)) else 'dstep=tiles') in net_line.split(': ')[1].split(), net_line
     rng = np.random.default_rng(C * 1000 + H)
@@ -427,14 +443,15 @@ def test_data_step_backward_at_awkward_shapes(B, C, H, W):
     ms = T(rng.uniform(0, 1, (B, C, H // 4, W // 4)).astype(np.float32))
     pan = T(rng.uniform(0, 1, (B, 1, H, W)).astype(np.float32))
     dy = T(rng.standard_normal((B, C, H, W)).astype(np.float32))
-    P64, P32 = _params(C, 2, torch.float64), _params(C, 2, torch.float32)
-    names = [n for n in P64 if n.split('.')[0] in ('D', 'DT', 'R', 'RT')] + ['eta.1']
+    P64, P32 = _params(C, K, torch.float64), _params(C, K, torch.float32)
+    eta = f'eta.{stage}'
+    names = [n for n in P64 if n.split('.')[0] in ('D', 'DT', 'R', 'RT')] + [eta]
     assert len(names) == 13
-    y64, dz64, g64 = _autograd(lambda P, v: orc.data_step(P, v, ms.to(v.dtype), pan.to(v.dtype), P['eta.1']), P64, names, z, dy)
-    y32, dz32, g32 = _autograd(lambda P, v: orc.data_step(P, v, ms.to(v.dtype), pan.to(v.dtype), P['eta.1']), P32, names, z, dy)
+    y64, dz64, g64 = _autograd(lambda P, v: orc.data_step(P, v, ms.to(v.dtype), pan.to(v.dtype), P[eta]), P64, names, z, dy)
+    y32, dz32, g32 = _autograd(lambda P, v: orc.data_step(P, v, ms.to(v.dtype), pan.to(v.dtype), P[eta]), P32, names, z, dy)
     pre_fwd = rel_l2(y32, y64)
     _precondition(tag, 'dstep', pre_fwd, dz64, dz32)
-    dz, flat = ops.data_step_bwd(1, z.cuda(), ms.cuda(), pan.cuda(), dy.cuda(), guard=True, owned=names)
+    dz, flat = ops.data_step_bwd(stage, z.cuda(), ms.cuda(), pan.cuda(), dy.cuda(), guard=True, owned=names)
     _dx_checks(tag, dz.cpu(), dz64, dz32, float(dz64.abs().max()), L2['dstep'], pre_fwd)
     bad = []
     for n in names:

@@ -43,10 +43,8 @@ def _backward(C, K, n, B, flags, variant, seed=977, split=False, kind='smooth'):
 
 
 def _assert_bitwise(g0, g1, eng, what):
-    if torch.equal(g0, g1):
-        return
-    bad = [eng.names[i] for i, (o, p) in enumerate(zip(eng.offsets, eng.params)) if not torch.equal(g0[o:o + p.numel()], g1[o:o + p.numel()])]
-    raise AssertionError((what, 'gradients differ in', bad[:12], len(bad)))
+    from gpu_helpers import assert_bitwise
+    assert_bitwise(g0, g1, eng, what)
 
 
 @pytest.mark.parametrize('drop', [False, True])
