@@ -154,7 +154,7 @@ typedef struct lg_plan lg_plan; /* host-side, immutable after creation */
 
 const char* lg_version(void);
 /* Bumped whenever a struct layout, an argument meaning or a caller-provided buffer size changes (2: lg_config.variant, the data step's
- * tmp of 3*B*C*H*W/4 + B*H*W floats).  Additions keep it: lg_op_lgt_stages, lg_workspace_deadout, LG_FLAG_STAGEWISE, LG_FLAG_LIVE_APART, the lg_debug_stage_* entries and lg_debug_live_slot and the classical baselines (lg_classical_workspace_bytes, lg_interp23_up4, lg_sfim, lg_gsa, then lg_wavelet, lg_wavelet_taps, then lg_mtfglp_workspace_bytes, lg_mtf_glp, then lg_bdsd_workspace_bytes, lg_bdsd) came without a bump (no struct,
+ * tmp of 3*B*C*H*W/4 + B*H*W floats).  Additions keep it: lg_op_lgt_stages, lg_workspace_deadout, LG_FLAG_STAGEWISE, LG_FLAG_LIVE_APART, the lg_debug_stage_* entries and lg_debug_live_slot and the classical baselines (lg_classical_workspace_bytes, lg_interp23_up4, lg_sfim, lg_gsa, then lg_wavelet, lg_wavelet_taps, then lg_mtfglp_workspace_bytes, lg_mtf_glp, then lg_bdsd_workspace_bytes, lg_bdsd, then lg_atrous_workspace_bytes, lg_atrous, lg_atrous_taps with their own new struct lg_atrous_args) came without a bump (no existing struct,
  * argument or caller-sized buffer changed: workspaces are sized by lg_workspace_bytes, which grew for the plans that batch their dead stages).  A binding checks it at load time -- lgteun_amd/_lib.py does -- instead of passing a stale struct. */
 #define LG_ABI_VERSION 2
 int32_t lg_abi_version(void);
@@ -599,6 +599,34 @@ int lg_wavelet_taps(double* out17);
 size_t lg_mtfglp_workspace_bytes(int32_t B, int32_t C, int32_t h, int32_t w, int32_t n_filters, int32_t mode);
 int lg_mtf_glp(const float* ms, const float* pan, float* out, double* stats, const double* taps, int32_t n_filters, int32_t n_taps, int32_t mode, int32_t B,
                int32_t C, int32_t h, int32_t w, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- A trous: ATWT and AWLP, the detail of PAN against its two-level undecimated B3-spline low-pass (lgteun_amd/atrous.py) ----
+ * With u_k = interp23(ms)_k, N = 16 h w and SFIM's statistics (mu = mean pan, s_k = std(u_k) over N - 1): P_L = PAN filtered along rows, then columns, by the 13
+ * taps (1, 4, 10, 20, 31, 40, 44, 40, 31, 20, 10, 4, 1) / 256 at offsets -6 .. 6, indices modulo the sides (the cascade of (1, 4, 6, 4, 1) / 16 at unit step and at
+ * step 2; a scene's rim of 6 pixels wraps, where toolboxes mirror); d = pan - P_L; a_k = s_k / std(pan) (LG_ATROUS_MATCH_PAN) or s_k / s_L with
+ * s_L^2 = sum (P_L - mu)^2 / (N - 1) (LG_ATROUS_MATCH_LOWPASS), 0 where that variance is not > 0.  Then, clipped to [0, 1] with one rounding:
+ *   LG_ATROUS_ATWT  out_k = u_k + a_k d
+ *   LG_ATROUS_AWLP  out_k = u_k + a_k d u_k / (U + 1e-8), U = the mean of u over the bands; the injection is 0 where U + 1e-8 is not > 0 or not finite
+ * PAN enters every sum minus the sample's first pixel: a constant PAN has d = 0 and a = 0 exactly and out = clip(u) bit for bit.  The compute entry takes ONE
+ * pointer to an argument block; struct_bytes must be sizeof(lg_atrous_args), any other value is rejected.  stats: NULL or a device array [B, C + 1] of fp64 that
+ * receives a (C), then the reference deviation, std(pan) or s_L.  Launches: SFIM's moments and finish, for LG_ATROUS_MATCH_LOWPASS the pass that sums
+ * (P_L - mu)^2 and its finish, and the apply pass; neither u nor P_L is stored.  Tensors, limits, alignment, checks (every one before any HIP call: a rejected
+ * call launches and writes nothing, its message starts with "atrous:" and names the argument) and guarantees (same bits on every call, a sample's bits do not
+ * depend on its batch, the workspace needs no initialisation) are those of lg_sfim. */
+#define LG_ATROUS_ATWT 0
+#define LG_ATROUS_AWLP 1
+#define LG_ATROUS_MATCH_PAN 0
+#define LG_ATROUS_MATCH_LOWPASS 1
+typedef struct {
+    uint32_t struct_bytes;            /* sizeof of this struct; any other value is rejected */
+    int32_t rule, match, B, C, h, w;
+    const float *ms, *pan; float* out; double* stats;   /* stats may be NULL */
+    void* workspace; size_t workspace_bytes; void* stream;
+} lg_atrous_args;
+/* bytes of workspace the compute entry needs for `match`; 0 for anything the call rejects */
+size_t lg_atrous_workspace_bytes(int32_t B, int32_t C, int32_t h, int32_t w, int32_t match);
+int lg_atrous(const lg_atrous_args* args);
+/* out13: a HOST array that receives the 13 taps the kernels use, by offset -6 .. 6, from the same constexpr */
+int lg_atrous_taps(double* out13);
 /* ---- BDSD: the band-dependent spatial detail method, global or block-wise (lgteun_amd/bdsd.py) ----
  * With u_k = interp23(ms)_k, A_k(i, j) = sum_a sum_b t_k[a] t_k[b] ms_k(clamp(i + a - r), clamp(j + b - r)) (the band low-passed on its own grid, replicate
  * border, r = n_taps / 2) and D = the raw PAN filtered with taps_pan at (4 i + 2, 4 j + 2) (lg_mtf_glp's rule): per block and band the weights gamma_k in

@@ -9,6 +9,7 @@ from .classical import GSA, SFIM, Wavelet, gsa, interp23, sfim, wavelet  # noqa:
 from .mtf_glp import MTF_GLP, MTF_GLP_CBD, MTF_GLP_HPM  # noqa: F401  (the function is mtf_glp.mtf_glp: its name is the module's)
 from .bdsd import BDSD  # noqa: F401  (the function is bdsd.bdsd: its name is the module's)
 from .cs import GS, IHS, PCA, Brovey  # noqa: F401  (the functions are cs.fuse, cs.ihs, cs.brovey, cs.gs, cs.pca)
+from .atrous import ATWT, AWLP, atwt, awlp  # noqa: F401  (the general function is atrous.atrous: its name is the module's)
 from .device_metrics import no_ref_evaluate_batch, no_ref_evaluate_ext_batch, ref_evaluate_batch, ref_evaluate_ext_batch  # noqa: F401
 from .resident import ResidentLoader, ResidentStore  # noqa: F401
 from .scene import fuse_scene, tile_grid  # noqa: F401

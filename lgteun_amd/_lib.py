@@ -28,6 +28,13 @@ class LgConfig(ctypes.Structure):
     _fields_ = [('C', c_int32), ('K', c_int32), ('H', c_int32), ('W', c_int32), ('precision', c_int32), ('variant', ctypes.c_uint32)]
 
 
+class LgAtrousArgs(ctypes.Structure):
+    """lg_atrous_args: the argument block of lg_atrous; struct_bytes = ctypes.sizeof(LgAtrousArgs)"""
+    _fields_ = [('struct_bytes', ctypes.c_uint32), ('rule', c_int32), ('match', c_int32), ('B', c_int32), ('C', c_int32), ('h', c_int32), ('w', c_int32),
+                ('ms', c_void_p), ('pan', c_void_p), ('out', c_void_p), ('stats', c_void_p), ('workspace', c_void_p), ('workspace_bytes', c_size_t),
+                ('stream', c_void_p)]
+
+
 # lg_config.variant bits (include/lgteun_hip.h): A/B kernels that compute the same function as the product path
 LG_VAR_FFN_STRIP = 1
 LG_VAR_FFN_SAVE3, LG_VAR_FFN_SAVE5 = 1 << 2, 2 << 2
@@ -49,6 +56,8 @@ LG_DT_U8, LG_DT_U16, LG_DT_F32 = 0, 1, 2                                # lg_pyr
 LG_CLASSICAL_SFIM, LG_CLASSICAL_GSA = 0, 1                              # lg_classical_workspace_bytes: method
 LG_MTFGLP_GLP, LG_MTFGLP_HPM, LG_MTFGLP_CBD = 0, 1, 2                   # lg_mtf_glp: mode (the injection rule)
 LG_CS_IHS, LG_CS_BROVEY, LG_CS_GS, LG_CS_PCA = 0, 1, 2, 3                  # lg_cs: mode (the method)
+LG_ATROUS_ATWT, LG_ATROUS_AWLP = 0, 1                                   # lg_atrous_args.rule
+LG_ATROUS_MATCH_PAN, LG_ATROUS_MATCH_LOWPASS = 0, 1                     # lg_atrous_args.match
 LG_ABI_VERSION = 2   # include/lgteun_hip.h: checked against lg_abi_version() when the library is loaded
 
 
@@ -190,6 +199,9 @@ SIGNATURES = {
     'lg_cs_workspace_bytes': (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     'lg_cs': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_double), c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
     'lg_cs_taps': (c_int32, [POINTER(c_double), POINTER(c_double)]),
+    'lg_atrous_workspace_bytes': (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    'lg_atrous': (c_int32, [POINTER(LgAtrousArgs)]),
+    'lg_atrous_taps': (c_int32, [POINTER(c_double)]),
 }
 
 

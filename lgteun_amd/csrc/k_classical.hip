@@ -25,6 +25,7 @@
 //                    block mean of u_k, which is a separable 17-tap circular FIR on ms itself (cl_wavelet_taps).  A lane owns 4 x 4 blocks: 16-byte
 //                    PAN loads, 16-byte stores, M_k from an ms halo tile in LDS (columns, then rows).  No u, no moments, no workspace.
 //   k_mg_*           MTF-GLP with its three injection rules (lg_mtf_glp), on the same tiles: described where they stand, below k_cl_wavelet.
+//   k_at_*           ATWT and AWLP, the a trous pair (lg_atrous; restated in tests/atrous_ref.py): described where they stand, below k_mg_apply.
 //   k_bd_*           BDSD, global and block-wise (lg_bdsd; restated in tests/bdsd_ref.py): described where they stand, below k_mg_*.
 // No atomics; a workgroup sees one sample and the grid of a sample depends on C, h and w only, so a sample has the same bits alone and inside
 // any batch.  All indexing into tensors is 64-bit.
@@ -576,6 +577,195 @@ __global__ __launch_bounds__(CL_NT) void k_mg_apply(const float* __restrict__ ms
     }
 }
 
+// ---- A trous: ATWT and AWLP, the detail of PAN against its two-level undecimated B3-spline low-pass (lg_atrous).  The cascade -- (1, 4, 6, 4, 1) / 16
+// along rows and columns, then the same five taps 2 apart -- is ONE separable 13-tap circular filter (at_taps).  SFIM's moments and finish give mu, m_k and
+// a_k = std(u_k) / std(pan); then
+//   at_rows / at_cols2  the low-pass of a 16 x 32 tile, written once for both kernels: PAN minus the pivot with a circular halo of 6 (28 x 44) into LDS, the 13 row taps
+//                  into a 28 x 32 plane, the 13 column taps straight into the registers of the thread that owns the two pixels.
+//   k_at_lowvar    match = lowpass only, grid (gx2, sample), gx2 = min(tiles, 768); a workgroup walks the tiles gx2 apart and sums (P_L - mu)^2 over each in one order
+//                  (butterfly inside a wave, the four waves pairwise): one partial per workgroup.  k_at_finish: SFIM's partials of u_k and these in ascending
+//                  order (cl_partials_column), then a_k = std(u_k) / s_L over coef's a_k, and s_L into coef's first gain slot, which SFIM leaves unused.
+//   k_at_apply     grid (tile, sample): the detail d = pan - P_L of the thread's two pixels into registers (the staged PAN lies in cl_up_band's scratch, which is free
+//                  until the first band), for AWLP the tile of interp23 of the band mean of ms (interp23 is linear: that is the band mean of u, and the LDS does
+//                  not grow with C), then per band the tile of u, the rule, ONE rounding; the next band's ms samples are in flight under the current band's
+//                  passes.  The workgroup of tile 0 writes stats: a_k, then the reference deviation -- std(pan) from SFIM's partials, or s_L from coef.
+// A PAN side is at least 16 and a ragged tile reaches up to 37 past the origin: an index may wrap more than once, which cl_mod (a true modulo) allows.
+constexpr int AT_REACH = 6, AT_TAPS = 2 * AT_REACH + 1;
+constexpr int AT_PH = CL_TH + 2 * AT_REACH, AT_PW = CL_TW + 2 * AT_REACH;      // the staged PAN: 28 x 44
+constexpr int AT_STAGE = AT_PH * AT_PW + AT_PH * CL_TW;                  // doubles: the staged PAN, then the row-filtered plane [28][32]
+constexpr int AT_RESIDENT = 768;                                         // workgroups per sample of k_at_lowvar, at most: three per CU
+constexpr int AT_FINISH_NT = 64;
+static_assert(AT_STAGE <= CL_SCRATCH, "k_at_apply stages PAN in the scratch of cl_up_band");
+static_assert(AT_FINISH_NT >= 2 * CL_MAX_C + 1, "a thread per column of partials in k_at_finish");
+
+__host__ __device__ inline int at_apply_lds_doubles(int rule) { return CL_SCRATCH + (rule == LG_ATROUS_AWLP ? 2 : 1) * CL_PX; }
+
+// the 13 taps by offset -6 .. 6: tap a of level 1 meets tap c of level 2 at offset a + 2 c.  Every product and every sum is exact: (1, 4, 10, 20, 31, 40, 44, ...) / 256
+struct AtTaps { double t[AT_TAPS]; };
+__host__ __device__ constexpr AtTaps at_taps() {
+    constexpr double B3[5] = {1.0 / 16, 4.0 / 16, 6.0 / 16, 4.0 / 16, 1.0 / 16};
+    AtTaps r = {};
+    for (int a = -2; a <= 2; ++a)
+        for (int c = -2; c <= 2; ++c) r.t[AT_REACH + a + 2 * c] += B3[a + 2] * B3[c + 2];
+    return r;
+}
+
+// PT[28][44]: staged pixel (r, c) = PAN pixel (Y0 - 6 + r, X0 - 6 + c) modulo the sides, minus the pivot; RW[28][32]: RW(r, c) = sum_j t_j PT(r, c + j), the row
+// taps of tile column c.  Ends WITH a barrier.  (src[0] is the sample at offset -6; two chains, as in cl_fir)
+__device__ __forceinline__ void at_rows(const float* __restrict__ pan_b, double pv, int H4, int W4, int Y0, int X0, double* PT, double* RW) {
+    constexpr AtTaps T = at_taps();
+    for (int i = threadIdx.x; i < AT_PH * AT_PW; i += CL_NT) {
+        const int r = i / AT_PW, c = i - r * AT_PW;
+        PT[i] = (double)pan_b[(long)cl_mod(Y0 - AT_REACH + r, H4) * W4 + cl_mod(X0 - AT_REACH + c, W4)] - pv;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < AT_PH * CL_TW; i += CL_NT) {
+        const double* src = PT + (i / CL_TW) * AT_PW + i % CL_TW;
+        double a = 0.0, b = T.t[AT_REACH] * src[AT_REACH];
+#pragma unroll
+        for (int u = 0; u < AT_REACH; ++u) {
+            a = fma(T.t[u], src[u], a);
+            b = fma(T.t[AT_REACH + 1 + u], src[AT_REACH + 1 + u], b);
+        }
+        RW[i] = a + b;
+    }
+    __syncthreads();
+}
+
+// P_L minus the pivot at the tile's pixels (oy, ox) and (oy, ox + 1): the 13 column taps on q = RW + oy * 32 + ox; the two pixels' samples are adjacent doubles
+__device__ __forceinline__ void at_cols2(const double* q, double& l0, double& l1) {
+    constexpr AtTaps T = at_taps();
+    double a0 = 0.0, b0 = T.t[AT_REACH] * q[AT_REACH * CL_TW], a1 = 0.0, b1 = T.t[AT_REACH] * q[AT_REACH * CL_TW + 1];
+#pragma unroll
+    for (int u = 0; u < AT_REACH; ++u) {
+        a0 = fma(T.t[u], q[u * CL_TW], a0);
+        a1 = fma(T.t[u], q[u * CL_TW + 1], a1);
+        b0 = fma(T.t[AT_REACH + 1 + u], q[(AT_REACH + 1 + u) * CL_TW], b0);
+        b1 = fma(T.t[AT_REACH + 1 + u], q[(AT_REACH + 1 + u) * CL_TW + 1], b1);
+    }
+    l0 = a0 + b0;
+    l1 = a1 + b1;
+}
+
+// part2 [B][gx2]: a workgroup's sum of (P_L - mu)^2 over its tiles
+__global__ __launch_bounds__(CL_NT) void k_at_lowvar(const float* __restrict__ pan, const double* __restrict__ coef, double* __restrict__ part2, int C, int h,
+                                                     int w, int tiles_x, int tiles) {
+    __shared__ double S[AT_STAGE], red[CL_NT / 64];
+    const int tid = threadIdx.x, gx = gridDim.x, H4 = 4 * h, W4 = 4 * w;
+    const long b = blockIdx.y;
+    const float* __restrict__ pan_b = pan + b * ((long)H4 * W4);
+    const double pv = (double)pan_b[0], mpc = coef[b * (3 * C + 1)];
+    const int p = 2 * tid, oy = p / CL_TW, ox = p % CL_TW;
+    double acc = 0.0;
+    for (int t = blockIdx.x; t < tiles; t += gx) {
+        const auto [Y0, X0] = cl_tile(t, tiles_x);
+        at_rows(pan_b, pv, H4, W4, Y0, X0, S, S + AT_PH * AT_PW);
+        double l0, l1;
+        at_cols2(S + AT_PH * AT_PW + oy * CL_TW + ox, l0, l1);
+        const double e0 = l0 - mpc, e1 = l1 - mpc;
+        const bool in = Y0 + oy < H4 && X0 + ox < W4;      // W4 is a multiple of 4 and ox is even: both pixels or none
+        acc += block_sum4(in ? fma(e1, e1, e0 * e0) : 0.0, red);
+        // no barrier: the next tile's at_rows writes the plane behind block_sum4's barrier, and red behind its own two
+    }
+    if (tid == 0) part2[b * gx + blockIdx.x] = acc;
+}
+
+// match = lowpass: a_k = std(u_k) / s_L into coef[b][1 + C + k], s_L into coef[b][1 + 2 C]; all of them 0 where s_L^2 is not > 0.  std(u_k) is k_cl_finish's,
+// from the same partials in the same order.
+__global__ __launch_bounds__(AT_FINISH_NT) void k_at_finish(const double* __restrict__ part, const double* __restrict__ part2, double* __restrict__ coef, int C,
+                                                            int gx, int gx2, double N) {
+    __shared__ double sums[2 * CL_MAX_C + 1];
+    const long b = blockIdx.x;
+    const int ns = 2 * C + 2, k = threadIdx.x;
+    if (k < 2 * C) sums[k] = cl_partials_column(part + b * gx * ns + k, gx, ns);
+    if (k == 2 * C) sums[k] = cl_partials_column(part2 + b * gx2, gx2, 1);
+    __syncthreads();
+    if (k >= C) return;
+    double* co = coef + b * (3 * C + 1);
+    const double var_l = sums[2 * C] / (N - 1.0);
+    const double su = sums[2 * k], var_u = (sums[2 * k + 1] - su * su / N) / (N - 1.0);
+    co[1 + C + k] = var_l > 0.0 ? sqrt(fmax(var_u, 0.0) / var_l) : 0.0;
+    if (k == 0) co[1 + 2 * C] = var_l > 0.0 ? sqrt(var_l) : 0.0;
+}
+
+// part: SFIM's partials [B][gx][2 C + 2] (match = pan: the reference deviation is std(pan)) or NULL (match = lowpass: it is in coef).  stats: NULL or [B][C + 1].
+template <int RULE>
+__global__ __launch_bounds__(CL_NT) void k_at_apply(const float* __restrict__ ms, const float* __restrict__ pan, float* __restrict__ out,
+                                                    const double* __restrict__ coef, const double* __restrict__ part, double* __restrict__ stats, int C, int h,
+                                                    int w, int tiles_x, int gx, double N) {
+    extern __shared__ double cl_lds[];
+    __shared__ double pmom[2];
+    double* U = cl_lds + CL_SCRATCH;
+    double* Um = U + CL_PX;                      // AWLP: the tile of the band mean of u
+    const int tid = threadIdx.x, H4 = 4 * h, W4 = 4 * w;
+    const auto [Y0, X0] = cl_tile(blockIdx.x, tiles_x);
+    const long b = blockIdx.y, lp = (long)h * w, plane = (long)H4 * W4;
+    const float* __restrict__ ms_b = ms + b * C * lp;
+    const float* __restrict__ pan_b = pan + b * plane;
+    float* __restrict__ out_b = out + b * C * plane;
+    const double* __restrict__ co = coef + b * (3 * C + 1);
+    const double pv = (double)pan_b[0];
+    if (stats && blockIdx.x == 0) {              // a_k, then the reference deviation
+        if (tid < C) stats[b * (C + 1) + tid] = co[1 + C + tid];
+        if (part) {
+            const int ns = 2 * C + 2;
+            if (tid < 2) pmom[tid] = cl_partials_column(part + b * gx * ns + 2 * C + tid, gx, ns);
+            __syncthreads();
+            const double var_p = (pmom[1] - pmom[0] * pmom[0] / N) / (N - 1.0);      // k_cl_finish's
+            if (tid == 0) stats[b * (C + 1) + C] = var_p > 0.0 ? sqrt(var_p) : 0.0;
+        } else if (tid == 0) {
+            stats[b * (C + 1) + C] = co[1 + 2 * C];
+        }
+    }
+    float v[CL_MLOADS], vn[CL_MLOADS] = {};
+    cl_ms_load(ms_b, h, w, {Y0, X0}, v);         // the first band's, under the passes on PAN
+    double mv[CL_MLOADS] = {};
+    if (RULE == LG_ATROUS_AWLP) {                // the band mean of ms at the samples the tile depends on: four bands in flight, added in ascending order
+        for (int k0 = 0; k0 < C; k0 += 4) {
+            float t[4][CL_MLOADS];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) cl_ms_load(ms_b + (k0 + j < C ? k0 + j : 0) * lp, h, w, {Y0, X0}, t[j]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int u = 0; u < CL_MLOADS; ++u) mv[u] += k0 + j < C ? (double)t[j][u] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < CL_MLOADS; ++u) mv[u] /= (double)C;
+    }
+    const int p = 2 * tid, oy = p / CL_TW, ox = p % CL_TW, y = Y0 + oy, x = X0 + ox;
+    const bool in = y < H4 && x < W4;            // W4 is a multiple of 4 and x is even: both pixels or none
+    const long o = (long)y * W4 + x;
+    double d0, d1;                               // pan - P_L
+    {
+        double* PT = cl_lds;
+        double* RW = PT + AT_PH * AT_PW;
+        at_rows(pan_b, pv, H4, W4, Y0, X0, PT, RW);
+        at_cols2(RW + oy * CL_TW + ox, d0, d1);
+        d0 = PT[(oy + AT_REACH) * AT_PW + ox + AT_REACH] - d0;
+        d1 = PT[(oy + AT_REACH) * AT_PW + ox + AT_REACH + 1] - d1;
+        __syncthreads();                         // the scratch is cl_up_band's from here
+    }
+    if (RULE == LG_ATROUS_AWLP) cl_up_band(mv, cl_lds, Um);      // (the barriers inside the first band's cl_up_band order it before its use)
+    for (int k = 0; k < C; ++k) {
+        if (k + 1 < C) cl_ms_load(ms_b + (k + 1) * lp, h, w, {Y0, X0}, vn);
+        cl_up_band(v, cl_lds, U);
+        __syncthreads();
+        if (in) {
+            const double a = co[1 + C + k], u0 = U[p], u1 = U[p + 1];
+            double g0 = a * d0, g1 = a * d1;
+            if (RULE == LG_ATROUS_AWLP) {
+                const double n0 = Um[p] + 1e-8, n1 = Um[p + 1] + 1e-8;
+                g0 = n0 > 0.0 && n0 - n0 == 0.0 ? g0 * (u0 / n0) : 0.0;
+                g1 = n1 > 0.0 && n1 - n1 == 0.0 ? g1 * (u1 / n1) : 0.0;
+            }
+            *reinterpret_cast<float2*>(out_b + k * plane + o) = make_float2(cl_clip(u0 + g0), cl_clip(u1 + g1));
+        }
+        cl_next(v, vn);
+        // no barrier: the next cl_up_band writes U in its last pass, four barriers from here
+    }
+}
+
 struct ClGeom {
     int tiles_x, tiles, gx, ns;
     size_t off[2], bytes;      // part, coef
@@ -685,6 +875,62 @@ int mg_fuse(const char* who, const float* ms, const float* pan, float* out, doub
     } else {
         k_mg_apply<LG_MTFGLP_GLP><<<dim3(tiles, B), CL_NT, lds, s>>>(ms, pan, dlow, out, coef, stats, C, n_filters, h, w, tiles_x);
     }
+    LG_CHECK_LAUNCH();
+    return 0;
+}
+
+struct AtGeom {
+    ClGeom cl;                 // SFIM's: the tiles and the moments pass
+    int gx2;                   // workgroups per sample of k_at_lowvar
+    size_t off[3], bytes;      // part, coef, part2 (match = lowpass)
+};
+
+bool at_geom(const char* who, int B, int C, int h, int w, int match, AtGeom& g) {
+    if (!cl_geom(who, B, C, h, w, LG_CLASSICAL_SFIM, g.cl)) return false;
+    if (match != LG_ATROUS_MATCH_PAN && match != LG_ATROUS_MATCH_LOWPASS) {
+        lg_set_error("%s: match must be LG_ATROUS_MATCH_PAN or LG_ATROUS_MATCH_LOWPASS (got %d)", who, match);
+        return false;
+    }
+    g.gx2 = g.cl.tiles < AT_RESIDENT ? g.cl.tiles : AT_RESIDENT;
+    const size_t sz[3] = {ws_region(B, (size_t)g.cl.gx * g.cl.ns * sizeof(double)), ws_region(B, (size_t)(3 * C + 1) * sizeof(double)),
+                          match == LG_ATROUS_MATCH_LOWPASS ? ws_region(B, (size_t)g.gx2 * sizeof(double)) : 0};
+    g.bytes = ws_layout(3, sz, g.off);
+    return true;
+}
+
+int at_fuse(const char* who, const lg_atrous_args* a) {
+    if (!a) { lg_set_error("%s: args is NULL", who); return -1; }
+    if (a->struct_bytes != sizeof(lg_atrous_args)) {
+        lg_set_error("%s: struct_bytes must be sizeof(lg_atrous_args) = %zu (got %u)", who, sizeof(lg_atrous_args), a->struct_bytes);
+        return -1;
+    }
+    if (a->rule != LG_ATROUS_ATWT && a->rule != LG_ATROUS_AWLP) { lg_set_error("%s: rule must be LG_ATROUS_ATWT or LG_ATROUS_AWLP (got %d)", who, a->rule); return -1; }
+    const int B = a->B, C = a->C, h = a->h, w = a->w;
+    AtGeom g;
+    if (!at_geom(who, B, C, h, w, a->match, g)) return -1;
+    if (!cl_check_args(who, a->ms, a->pan, a->out, {}, a->stats, a->workspace, a->workspace_bytes, g.bytes, "lg_atrous_workspace_bytes")) return -1;
+    if (int rc = cl_lds_attr(who)) return rc;
+    hipStream_t s = (hipStream_t)a->stream;
+    double *part = cl_ws(a->workspace, g.off[0]), *coef = cl_ws(a->workspace, g.off[1]), *part2 = cl_ws(a->workspace, g.off[2]);
+    const int tiles_x = g.cl.tiles_x, tiles = g.cl.tiles;
+    const double N = 16.0 * h * w;
+    const bool lowpass = a->match == LG_ATROUS_MATCH_LOWPASS;
+    k_cl_moments<<<dim3(g.cl.gx, B), CL_NT, cl_moment_lds_doubles(C) * sizeof(double), s>>>(a->ms, a->pan, part, C, h, w, tiles_x, tiles, 0);
+    LG_CHECK_LAUNCH();
+    k_cl_finish<<<B, CL_NT, 0, s>>>(part, coef, nullptr, C, g.cl.gx, N, (double)h * w, 0);
+    LG_CHECK_LAUNCH();
+    if (lowpass) {
+        k_at_lowvar<<<dim3(g.gx2, B), CL_NT, 0, s>>>(a->pan, coef, part2, C, h, w, tiles_x, tiles);
+        LG_CHECK_LAUNCH();
+        k_at_finish<<<B, AT_FINISH_NT, 0, s>>>(part, part2, coef, C, g.cl.gx, g.gx2, N);
+        LG_CHECK_LAUNCH();
+    }
+    const double* pmom = lowpass ? nullptr : part;
+    const size_t lds = at_apply_lds_doubles(a->rule) * sizeof(double);
+    if (a->rule == LG_ATROUS_AWLP)
+        k_at_apply<LG_ATROUS_AWLP><<<dim3(tiles, B), CL_NT, lds, s>>>(a->ms, a->pan, a->out, coef, pmom, a->stats, C, h, w, tiles_x, g.cl.gx, N);
+    else
+        k_at_apply<LG_ATROUS_ATWT><<<dim3(tiles, B), CL_NT, lds, s>>>(a->ms, a->pan, a->out, coef, pmom, a->stats, C, h, w, tiles_x, g.cl.gx, N);
     LG_CHECK_LAUNCH();
     return 0;
 }
@@ -934,6 +1180,20 @@ extern "C" size_t lg_mtfglp_workspace_bytes(int32_t B, int32_t C, int32_t h, int
 extern "C" int lg_mtf_glp(const float* ms, const float* pan, float* out, double* stats, const double* taps, int32_t n_filters, int32_t n_taps, int32_t mode,
                           int32_t B, int32_t C, int32_t h, int32_t w, void* workspace, size_t workspace_bytes, void* stream) {
     return mg_fuse("mtf_glp", ms, pan, out, stats, taps, n_filters, n_taps, mode, B, C, h, w, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" size_t lg_atrous_workspace_bytes(int32_t B, int32_t C, int32_t h, int32_t w, int32_t match) {
+    AtGeom g;
+    return at_geom("atrous_workspace_bytes", B, C, h, w, match, g) ? g.bytes : 0;
+}
+
+extern "C" int lg_atrous(const lg_atrous_args* args) { return at_fuse("atrous", args); }
+
+extern "C" int lg_atrous_taps(double* out13) {
+    if (!out13) { lg_set_error("atrous_taps: out13 is NULL"); return -1; }
+    constexpr AtTaps T = at_taps();
+    for (int a = 0; a < AT_TAPS; ++a) out13[a] = T.t[a];
+    return 0;
 }
 
 extern "C" size_t lg_classical_workspace_bytes(int32_t B, int32_t C, int32_t h, int32_t w, int32_t method) {

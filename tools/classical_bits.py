@@ -1,5 +1,5 @@
-"""The bits of the classical baselines, for comparing two builds of the library: every public function of lgteun_amd/classical.py, mtf_glp.py, bdsd.py and
-cs.py on tests/classical_ref.make_batch inputs (B make_scene scenes stacked, seeds 7000 + b), at the shapes the GPU tests use, and the SHA-256 of each output and of each stats tensor.
+"""The bits of the classical baselines, for comparing two builds of the library: every public function of lgteun_amd/classical.py, mtf_glp.py, bdsd.py,
+cs.py and atrous.py on tests/classical_ref.make_batch inputs (B make_scene scenes stacked, seeds 7000 + b), at the shapes the GPU tests use, and the SHA-256 of each output and of each stats tensor.
 One more shape for the component-substitution modes only: (C, h, w, B) = (4, 368, 368, 1) has 529 Gram tiles against the 512 workgroups of k_cs_gram, the
 smallest square shape at which one of them walks a second tile ((4, 136, 256, 1), in every list, is that shape for the moments and BDSD Gram passes).
 Prints one JSON line {name: digest}.  Run it once per library and compare the lines:
@@ -14,12 +14,13 @@ sys.path.insert(0, R)
 sys.path.insert(0, os.path.join(R, 'tests'))
 import torch  # noqa: E402
 
+import atrous_ref as ar  # noqa: E402
 import bdsd_ref as br  # noqa: E402
 import classical_ref as cr  # noqa: E402
 import cs_ref as csr  # noqa: E402
 import mtf_glp_ref as mr  # noqa: E402
 import wavelet_ref as wr  # noqa: E402
-from lgteun_amd import bdsd, classical, cs, mtf_glp  # noqa: E402
+from lgteun_amd import atrous, bdsd, classical, cs, mtf_glp  # noqa: E402
 
 CS_SECOND_TILE = (4, 368, 368, 1)
 SEED = 7
@@ -62,6 +63,11 @@ def main():
         ms, pan = batch(*shape)
         for mode in csr.MODES:
             put(f'cs_{mode}', shape, getattr(cs, mode)(ms, pan, return_stats=True))
+    for match in ar.MATCHES:
+        for shape in ar.SHAPES[match] + (ar.STATS_ONLY_SHAPES if match == 'lowpass' else []):
+            ms, pan = batch(*shape)
+            for rule in ar.RULES:
+                put(f'{rule}_{match}', shape, atrous.atrous(ms, pan, rule, match, return_stats=True))
     print(json.dumps({'tool': 'classical_bits', 'lib': os.environ.get('LGTEUN_HIP_LIB', 'in-tree'), 'n': len(res), 'sha256': res}))
 
 

@@ -7,6 +7,7 @@ dataset.read_tiff, fuses them tile by tile on the GPU (lgteun_amd/scene.py) and 
     python tools/fuse_scene.py PREFIX --method mtf_glp|mtf_glp_hpm|mtf_glp_cbd [--mtf-gains g [g ...]] [--bit-depth 11] ...
     python tools/fuse_scene.py PREFIX --method ihs|brovey|gs|pca [--cs-weights w [w ...]] [--bit-depth 11] ...
     python tools/fuse_scene.py PREFIX --method bdsd [--bdsd-block N] [--mtf-gains g [g ...]] [--mtf-gain-pan g] [--bit-depth 11] ...
+    python tools/fuse_scene.py PREFIX --method atwt|awlp [--atrous-match pan|lowpass] [--bit-depth 11] ...
 
 --method gsa / sfim / wavelet (lgteun_amd/classical.py) and mtf_glp / mtf_glp_hpm / mtf_glp_cbd (lgteun_amd/mtf_glp.py) need no checkpoint and no
 tiles: the whole scene is fused in one call, with the same normalisation and the same conversion to digital numbers.  --mtf-gains: the sensor's MTF
@@ -45,8 +46,10 @@ def load_module(path, device='cuda:0'):
 def parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('prefix')
-    ap.add_argument('--method', choices=['network', 'gsa', 'sfim', 'wavelet', 'mtf_glp', 'mtf_glp_hpm', 'mtf_glp_cbd', 'bdsd', 'ihs', 'brovey', 'gs', 'pca'],
-                    default='network')
+    ap.add_argument('--method', choices=['network', 'gsa', 'sfim', 'wavelet', 'mtf_glp', 'mtf_glp_hpm', 'mtf_glp_cbd', 'bdsd', 'ihs', 'brovey', 'gs', 'pca',
+                                         'atwt', 'awlp'], default='network')
+    ap.add_argument('--atrous-match', choices=['pan', 'lowpass'], default='pan',
+                    help="--method atwt / awlp: the deviation the detail is scaled by, std(pan) or std of the low-passed PAN (default: pan)")
     ap.add_argument('--mtf-gains', type=float, nargs='+', default=None, metavar='g',
                     help="--method mtf_glp* / bdsd: the sensor's MTF gain at Nyquist, one for all bands or one per band (default: a placeholder, 0.3)")
     ap.add_argument('--mtf-gain-pan', type=float, default=None, metavar='g', help="--method bdsd: PAN's MTF gain at Nyquist (default: a placeholder, 0.15)")
@@ -88,6 +91,10 @@ def main():
         from lgteun_amd import cs
         fused = cs.fuse_scene(a.method, ms_chw, pan[np.newaxis], weights=a.cs_weights, bit_depth=a.bit_depth, norm_input=a.norm_input,
                               out_dtype='float32' if a.float else 'uint16')
+    elif a.method in ('atwt', 'awlp'):
+        from lgteun_amd import atrous
+        fused = atrous.fuse_scene(atrous.SCENE_METHODS[a.method], ms_chw, pan[np.newaxis], match=a.atrous_match, bit_depth=a.bit_depth,
+                                  norm_input=a.norm_input, out_dtype='float32' if a.float else 'uint16')
     elif a.method.startswith('mtf_glp'):
         from lgteun_amd import mtf_glp
         fused = mtf_glp.fuse_scene(mtf_glp.SCENE_METHODS[a.method], ms_chw, pan[np.newaxis], gains_ms=gains, bit_depth=a.bit_depth, norm_input=a.norm_input,

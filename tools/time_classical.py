@@ -1,11 +1,12 @@
 """What the classical baselines cost on the GPU (lgteun_amd/classical.py, lgteun_amd/mtf_glp.py, lgteun_amd/bdsd.py): ms per call of `sfim`, `gsa`, `wavelet`,
-of `mtf_glp` with each of its three rules (default gains: one filtered plane per sample), of `bdsd`, global and with blocks of 128, and of the four
-component-substitution methods `cs.ihs`, `cs.brovey`, `cs.gs`, `cs.pca` (lgteun_amd/cs.py), in the same run, with the call synchronised, the
+of `mtf_glp` with each of its three rules (default gains: one filtered plane per sample), of `bdsd`, global and with blocks of 128, of the four
+component-substitution methods `cs.ihs`, `cs.brovey`, `cs.gs`, `cs.pca` (lgteun_amd/cs.py) and of `atrous.atwt` and `atrous.awlp` with both matches
+(lgteun_amd/atrous.py), in the same run, with the call synchronised, the
 median of 20 runs after 5 warm-up runs, at C = 4 and C = 8 with PAN 128 x 128 (batch 1 and batch 32) and for one 4096 x 4096 scene of C = 4.
 Beside each: the bytes the passes must move (SFIM and GSA: the moments pass reads ms and pan, the apply pass reads them again and writes the
 output; Wavelet: ms and pan read once, the output written once; MTF-GLP: see the comment below) divided by the time, as a fraction of the HBM bandwidth (--hbm-gbs, default 8000: the MI355X's 8 TB/s), and the ms per image of the float64
 numpy restatement (tests/classical_ref.py, tests/wavelet_ref.py, ...) on the same box (--no-host skips it).  Per case also `alternating`: sfim, mtf_glp_cbd,
-the two forms of bdsd, gsa, gs and pca again, one call of each per round, so that what else the machine does falls on all of them alike.  Prints one JSON line.   python tools/time_classical.py"""
+the two forms of bdsd, gsa, gs, pca and awlp with both matches again, one call of each per round, so that what else the machine does falls on all of them alike.  Prints one JSON line.   python tools/time_classical.py"""
 import argparse
 import json
 import os
@@ -24,7 +25,8 @@ import wavelet_ref as wr  # noqa: E402
 import mtf_glp_ref as mr  # noqa: E402
 import bdsd_ref as br  # noqa: E402
 import cs_ref as csr  # noqa: E402
-from lgteun_amd import bdsd, classical, cs, mtf_glp  # noqa: E402
+import atrous_ref as ar  # noqa: E402
+from lgteun_amd import atrous, bdsd, classical, cs, mtf_glp  # noqa: E402
 
 CASES = [(1, 4, 32, 32), (32, 4, 32, 32), (1, 8, 32, 32), (32, 8, 32, 32), (1, 4, 1024, 1024)]      # B, C, h, w
 
@@ -75,10 +77,13 @@ def main():
                for m in mr.MODES}
         bd = {blk: (lambda ms, pan, blk=blk: bdsd.bdsd(ms, pan, blk), lambda ms, pan, blk=blk: br.bdsd(ms, pan, [br.EQUAL_GAIN] * ms.shape[0], blk))
               for blk in (None, 128)}
+        at = {(r, m): (lambda ms, pan, r=r, m=m: atrous.atrous(ms, pan, r, m), lambda ms, pan, r=r, m=m: ar.atrous(ms, pan, r, m))
+              for r in ar.RULES for m in ar.MATCHES}
         for name, fn, host, reads in (('sfim', classical.sfim, cr.sfim, 2), ('gsa', classical.gsa, cr.gsa, 2), ('wavelet', classical.wavelet, wr.wavelet, 1),
                                       ('mtf_glp', *glp['glp'], 2), ('mtf_glp_hpm', *glp['hpm'], 2), ('mtf_glp_cbd', *glp['cbd'], 3),
                                       ('bdsd', *bd[None], 3), ('bdsd_128', *bd[128], 3),
-                                      *((m, getattr(cs, m), (lambda ms, pan, m=m: csr.fuse(ms, pan, m)), 2) for m in cs.SCENE_METHODS)):
+                                      *((m, getattr(cs, m), (lambda ms, pan, m=m: csr.fuse(ms, pan, m)), 2) for m in cs.SCENE_METHODS),
+                                      *((r if m == 'pan' else f'{r}_lowpass', *at[r, m], 2 if m == 'pan' else 3) for r in ar.RULES for m in ar.MATCHES)):
             moved = 4 * B * (reads * (C * h * w + 16 * h * w) + C * 16 * h * w)
             if name.startswith('mtf_glp'):
                 # equal gains: ms is read by the moments pass, by cbd's second moments pass and by the apply pass; pan by the moments pass, the low-pass and
@@ -92,6 +97,9 @@ def main():
                 # pan is read by the adjoint pass and by the apply pass, ms by the Gram pass and by the apply pass; the fp64 plane q [h, w] is written once and
                 # read by the Gram pass
                 moved = B * (4 * 2 * C * h * w + 4 * 2 * 16 * h * w + 2 * 8 * h * w + 4 * C * 16 * h * w)
+            if name.startswith(('atwt', 'awlp')):
+                # ms and pan are read by the moments pass and by the apply pass, pan once more by the pass that sums (P_L - mu)^2 for match = lowpass
+                moved = 4 * B * (2 * C * h * w + reads * 16 * h * w + C * 16 * h * w)
             ms_call = median_ms(lambda: fn(ms, pan), a.warmup, a.runs)
             row[name] = dict(bytes_moved=moved, ms_per_call=round(ms_call, 4), ms_per_image=round(ms_call / B, 4), gb_per_s=round(moved / ms_call / 1e6, 1),
                              hbm_fraction=round(moved / ms_call / 1e6 / a.hbm_gbs, 4))
@@ -101,7 +109,8 @@ def main():
                 row[name]['numpy_ms_per_image'] = round((time.perf_counter() - t) * 1e3, 2)
         row['alternating'] = alternating_ms({'sfim': lambda: classical.sfim(ms, pan), 'mtf_glp_cbd': lambda: mtf_glp.mtf_glp(ms, pan, 'cbd'),
                                              'bdsd': lambda: bdsd.bdsd(ms, pan), 'bdsd_128': lambda: bdsd.bdsd(ms, pan, 128), 'gsa': lambda: classical.gsa(ms, pan),
-                                             'gs': lambda: cs.gs(ms, pan), 'pca': lambda: cs.pca(ms, pan)}, a.warmup, a.runs)
+                                             'gs': lambda: cs.gs(ms, pan), 'pca': lambda: cs.pca(ms, pan), 'awlp': lambda: atrous.awlp(ms, pan),
+                                             'awlp_lowpass': lambda: atrous.awlp(ms, pan, 'lowpass')}, a.warmup, a.runs)
         res[f'B{B}_C{C}_pan{4 * h}x{4 * w}'] = row
     print(json.dumps({'tool': 'time_classical', 'device': torch.cuda.get_device_name(0), 'runs': a.runs, 'warmup': a.warmup,
                       'hbm_gbs': a.hbm_gbs, 'unit': 'ms per call, synchronised, median', 'cases': res}))
