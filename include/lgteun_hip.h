@@ -154,7 +154,7 @@ typedef struct lg_plan lg_plan; /* host-side, immutable after creation */
 
 const char* lg_version(void);
 /* Bumped whenever a struct layout, an argument meaning or a caller-provided buffer size changes (2: lg_config.variant, the data step's
- * tmp of 3*B*C*H*W/4 + B*H*W floats).  Additions keep it: lg_op_lgt_stages, lg_workspace_deadout, LG_FLAG_STAGEWISE, LG_FLAG_LIVE_APART, the lg_debug_stage_* entries and lg_debug_live_slot and the classical baselines (lg_classical_workspace_bytes, lg_interp23_up4, lg_sfim, lg_gsa, then lg_wavelet, lg_wavelet_taps, then lg_mtfglp_workspace_bytes, lg_mtf_glp, then lg_bdsd_workspace_bytes, lg_bdsd, then lg_atrous_workspace_bytes, lg_atrous, lg_atrous_taps with their own new struct lg_atrous_args) came without a bump (no existing struct,
+ * tmp of 3*B*C*H*W/4 + B*H*W floats).  Additions keep it: lg_op_lgt_stages, lg_workspace_deadout, LG_FLAG_STAGEWISE, LG_FLAG_LIVE_APART, the lg_debug_stage_* entries and lg_debug_live_slot and the classical baselines (lg_classical_workspace_bytes, lg_interp23_up4, lg_sfim, lg_gsa, then lg_wavelet, lg_wavelet_taps, then lg_mtfglp_workspace_bytes, lg_mtf_glp, then lg_bdsd_workspace_bytes, lg_bdsd, then lg_atrous_workspace_bytes, lg_atrous, lg_atrous_taps with their own new struct lg_atrous_args, then lg_mtf_hr_workspace_bytes, lg_mtf_hr with their own new struct lg_mtf_hr_args) came without a bump (no existing struct,
  * argument or caller-sized buffer changed: workspaces are sized by lg_workspace_bytes, which grew for the plans that batch their dead stages).  A binding checks it at load time -- lgteun_amd/_lib.py does -- instead of passing a stale struct. */
 #define LG_ABI_VERSION 2
 int32_t lg_abi_version(void);
@@ -627,6 +627,39 @@ size_t lg_atrous_workspace_bytes(int32_t B, int32_t C, int32_t h, int32_t w, int
 int lg_atrous(const lg_atrous_args* args);
 /* out13: a HOST array that receives the 13 taps the kernels use, by offset -6 .. 6, from the same constexpr */
 int lg_atrous_taps(double* out13);
+/* ---- MTF-HR: the regression-based and haze-corrected members of the MTF-GLP family: FS, HPM-R, HPM-H, BT-H (lgteun_amd/mtf_hr.py) ----
+ * With u_k = interp23(ms)_k, N = 16 h w, m_k = mean u_k, mu = mean pan, D_f = lg_mtf_glp's plane of the RAW pan under the taps of filter f (f = k, or 0 when
+ * n_filters is 1), L_k = interp23(D_k - pan(0, 0)) + pan(0, 0) (no histogram matching; the pivot keeps a constant PAN exact), l_k = mean L_k and H_k = the minimum of ms_k over the sample's h w pixels (the haze):
+ *   LG_MTFHR_FS     out_k = u_k + g_k (pan - L_k), g_k = sum (u_k - m_k)(pan - mu) / sum (L_k - l_k)(pan - mu)
+ *   LG_MTFHR_HPM_R  out_k = u_k r, r = (g_k pan + b_k) / (g_k L_k + b_k), g_k = sum (u_k - m_k)(L_k - l_k) / sum (L_k - l_k)^2, b_k = m_k - g_k l_k
+ *   LG_MTFHR_HPM_H  out_k = (u_k - H_k) r + H_k, r = (pan - H_P,k) / (L_k - H_P,k), H_P,k = mean D_k + sum_j s_j (H_j - mean ms_j) with s the slopes of the
+ *                   least-squares fit [ms_1 .. ms_C, 1] -> D_k over the h w MS pixels (Cholesky solve of the centred normal equations)
+ *   LG_MTFHR_BT_H   out_k = (u_k - H_k) r + H_k, r = (pan - H_I) / sum_j w_j (u_j - H_j), w the slopes and w_0 the intercept of the same fit to the one plane
+ *                   D (taps: PAN's own MTF), H_I = w_0 + sum_j w_j H_j; n_filters must be 1
+ * clipped to [0, 1] with one rounding.  g_k = 0 where its denominator is not > 0 or not finite or the quotient is not finite; r = 1 (no injection at that
+ * pixel) where its denominator is not > 0 or the quotient is not finite; a non-positive Cholesky pivot or a slope that is not finite gives slopes 0 (the
+ * intercept is then mean D).  PAN enters the filter and every sum minus the sample's first pixel: a constant PAN gives g = 0 and, for FS and HPM-R,
+ * out = clip(u) bit for bit.  The compute entry takes ONE pointer to an argument block; struct_bytes must be sizeof(lg_mtf_hr_args).  taps: a DEVICE array
+ * [n_filters, n_taps] of fp64 (wald.mtf_taps), n_filters 1 or C, n_taps odd, in 1 .. 63.  stats: NULL or a device array [B, 2 C + 2] of fp64, unused slots
+ * written as 0: FS g; HPM_R g, b; HPM_H H, H_P; BT_H H, w_1 .. w_C, w_0, H_I.  Launches: FS / HPM_R -- SFIM's moments and finish, the low-pass (D as fp64
+ * [B, n_filters, h, w] in the workspace), a second moments pass and its finish, the apply pass; HPM_H / BT_H -- the low-pass, a Gram pass at the MS scale, the
+ * solve, the apply pass.  Neither u nor L is stored.  Tensors, limits, alignment, checks (every one before any HIP call: a rejected call launches and writes
+ * nothing, its message starts with "mtf_hr:" and names the argument) and guarantees (same bits on every call, a sample's bits do not depend on its batch, one
+ * filtered plane and the same taps C times give the same bits, the workspace needs no initialisation) are those of lg_mtf_glp. */
+#define LG_MTFHR_FS 0
+#define LG_MTFHR_HPM_R 1
+#define LG_MTFHR_HPM_H 2
+#define LG_MTFHR_BT_H 3
+typedef struct {
+    uint32_t struct_bytes;            /* sizeof of this struct; any other value is rejected */
+    int32_t rule, n_filters, n_taps, B, C, h, w;
+    const float *ms, *pan; float* out; double* stats;   /* stats may be NULL */
+    const double* taps;
+    void* workspace; size_t workspace_bytes; void* stream;
+} lg_mtf_hr_args;
+/* bytes of workspace the compute entry needs; 0 for anything the call rejects */
+size_t lg_mtf_hr_workspace_bytes(int32_t B, int32_t C, int32_t h, int32_t w, int32_t n_filters, int32_t rule);
+int lg_mtf_hr(const lg_mtf_hr_args* args);
 /* ---- BDSD: the band-dependent spatial detail method, global or block-wise (lgteun_amd/bdsd.py) ----
  * With u_k = interp23(ms)_k, A_k(i, j) = sum_a sum_b t_k[a] t_k[b] ms_k(clamp(i + a - r), clamp(j + b - r)) (the band low-passed on its own grid, replicate
  * border, r = n_taps / 2) and D = the raw PAN filtered with taps_pan at (4 i + 2, 4 j + 2) (lg_mtf_glp's rule): per block and band the weights gamma_k in

@@ -10,6 +10,8 @@ from .mtf_glp import MTF_GLP, MTF_GLP_CBD, MTF_GLP_HPM  # noqa: F401  (the funct
 from .bdsd import BDSD  # noqa: F401  (the function is bdsd.bdsd: its name is the module's)
 from .cs import GS, IHS, PCA, Brovey  # noqa: F401  (the functions are cs.fuse, cs.ihs, cs.brovey, cs.gs, cs.pca)
 from .atrous import ATWT, AWLP, atwt, awlp  # noqa: F401  (the general function is atrous.atrous: its name is the module's)
+from . import mtf_hr  # noqa: F401  (the functions are mtf_hr.fuse, mtf_hr.fs, mtf_hr.hpm_r, mtf_hr.hpm_h, mtf_hr.bt_h)
+from .mtf_hr import BT_H, MTF_GLP_FS, MTF_GLP_HPM_H, MTF_GLP_HPM_R  # noqa: F401
 from .device_metrics import no_ref_evaluate_batch, no_ref_evaluate_ext_batch, ref_evaluate_batch, ref_evaluate_ext_batch  # noqa: F401
 from .resident import ResidentLoader, ResidentStore  # noqa: F401
 from .scene import fuse_scene, tile_grid  # noqa: F401

@@ -35,6 +35,13 @@ class LgAtrousArgs(ctypes.Structure):
                 ('stream', c_void_p)]
 
 
+class LgMtfHrArgs(ctypes.Structure):
+    """lg_mtf_hr_args: the argument block of lg_mtf_hr; struct_bytes = ctypes.sizeof(LgMtfHrArgs)"""
+    _fields_ = [('struct_bytes', ctypes.c_uint32), ('rule', c_int32), ('n_filters', c_int32), ('n_taps', c_int32), ('B', c_int32), ('C', c_int32),
+                ('h', c_int32), ('w', c_int32), ('ms', c_void_p), ('pan', c_void_p), ('out', c_void_p), ('stats', c_void_p), ('taps', c_void_p),
+                ('workspace', c_void_p), ('workspace_bytes', c_size_t), ('stream', c_void_p)]
+
+
 # lg_config.variant bits (include/lgteun_hip.h): A/B kernels that compute the same function as the product path
 LG_VAR_FFN_STRIP = 1
 LG_VAR_FFN_SAVE3, LG_VAR_FFN_SAVE5 = 1 << 2, 2 << 2
@@ -58,6 +65,7 @@ LG_MTFGLP_GLP, LG_MTFGLP_HPM, LG_MTFGLP_CBD = 0, 1, 2                   # lg_mtf
 LG_CS_IHS, LG_CS_BROVEY, LG_CS_GS, LG_CS_PCA = 0, 1, 2, 3                  # lg_cs: mode (the method)
 LG_ATROUS_ATWT, LG_ATROUS_AWLP = 0, 1                                   # lg_atrous_args.rule
 LG_ATROUS_MATCH_PAN, LG_ATROUS_MATCH_LOWPASS = 0, 1                     # lg_atrous_args.match
+LG_MTFHR_FS, LG_MTFHR_HPM_R, LG_MTFHR_HPM_H, LG_MTFHR_BT_H = 0, 1, 2, 3    # lg_mtf_hr_args.rule
 LG_ABI_VERSION = 2   # include/lgteun_hip.h: checked against lg_abi_version() when the library is loaded
 
 
@@ -202,6 +210,8 @@ SIGNATURES = {
     'lg_atrous_workspace_bytes': (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     'lg_atrous': (c_int32, [POINTER(LgAtrousArgs)]),
     'lg_atrous_taps': (c_int32, [POINTER(c_double)]),
+    'lg_mtf_hr_workspace_bytes': (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    'lg_mtf_hr': (c_int32, [POINTER(LgMtfHrArgs)]),
 }
 
 

@@ -26,6 +26,8 @@
 //                    PAN loads, 16-byte stores, M_k from an ms halo tile in LDS (columns, then rows).  No u, no moments, no workspace.
 //   k_mg_*           MTF-GLP with its three injection rules (lg_mtf_glp), on the same tiles: described where they stand, below k_cl_wavelet.
 //   k_at_*           ATWT and AWLP, the a trous pair (lg_atrous; restated in tests/atrous_ref.py): described where they stand, below k_mg_apply.
+//   k_hr_*           FS, HPM-R, HPM-H and BT-H, the regression-based and haze-corrected rules (lg_mtf_hr; restated in tests/mtf_hr_ref.py): described
+//                    where they stand, below at_fuse.
 //   k_bd_*           BDSD, global and block-wise (lg_bdsd; restated in tests/bdsd_ref.py): described where they stand, below k_mg_*.
 // No atomics; a workgroup sees one sample and the grid of a sample depends on C, h and w only, so a sample has the same bits alone and inside
 // any batch.  All indexing into tensors is 64-bit.
@@ -935,6 +937,436 @@ int at_fuse(const char* who, const lg_atrous_args* a) {
     return 0;
 }
 
+// ---- MTF-HR: the regression-based and haze-corrected members of the MTF-GLP family -- FS, HPM-R, HPM-H, BT-H (lg_mtf_hr; restated in
+// tests/mtf_hr_ref.py).  D_f is k_mg_lowpass's plane (the raw PAN minus the pivot under the MTF taps at the decimated positions); L_k = interp23(D_k) + pivot:
+// there is no histogram matching in this family, and a constant PAN has L = pan exactly.
+//   k_hr_moments   fs / hpm_r, grid (gx2, sample) like k_mg_moments: per band the tiles of u_k (cl_up_band on ms) and of L_k (cl_up_band on D_k), u minus
+//                  m_k, L and PAN minus mu, zero outside the image, as vectors in LDS beside the mask; the seven sums both gains need are sums of products of two
+//                  of them (cl_pair_sums).  k_hr_finish: the partials in ascending order, then thread k: g_k and b_k = m_k - g_k mean L_k.
+//   k_hr_gram      hpm_h / bt_h, at the MS scale, grid (gpb, sample): a workgroup walks the sample's MS pixels in chunks of 256, gpb chunks apart: the mask, the C
+//                  bands minus their first pixel and the F planes D_f as vectors in LDS; every sum of the regression is the sum of a product of two of them
+//                  (cl_pair_sums).  The minimum of every band: a wave's by shuffles, the workgroup's over its four waves -- exact and free of any order.
+//   k_hr_solve     one wave per sample: the partials in ascending order, the minimum of the minima, one thread's Cholesky of the centred Gram matrix of ms, then
+//                  thread f solves for the slopes of D_f; H_P,f (hpm_h) or w_0 and H_I (bt_h) from the means.  A non-positive pivot or a slope that is not finite
+//                  gives slopes 0.
+//   k_hr_apply     grid (tile, sample), two adjacent pixels per thread, the PAN pair loaded ahead of the first band, ONE rounding, 8-byte stores.  fs / hpm_r /
+//                  hpm_h: k_mg_apply's band loop (the tiles of u and L, the next band's samples in flight).  bt_h: the C tiles of u stay in LDS (cl_up_bands, as in
+//                  k_cl_apply and k_bd_apply): sum_k w_k (u_k - H_k) needs every band before the first output, and one interpolation per band is cheaper than
+//                  two sweeps.
+// hc [B][2 C + 2] holds what the apply pass reads, in the layout of stats: fs g; hpm_r g, b; hpm_h H, H_P; bt_h H, w, w_0, H_I; unused slots 0.
+constexpr int HR_SUMS = 7;                                               // per band: sum u, L, p, u p, L p, u L, L L (u, L, p centred)
+constexpr int HR_CHUNK = CL_NT;                                          // MS pixels a Gram workgroup takes at a time: one per thread
+constexpr int HR_GRAM_WGS = 128;                                         // Gram workgroups per sample, at most
+constexpr int HR_SOLVE_NT = 64;
+constexpr int HR_MAX_NS = (CL_MAX_C + 1) * (CL_MAX_C + 2) / 2 + CL_MAX_C * (CL_MAX_C + 1);
+static_assert(HR_SOLVE_NT >= CL_MAX_C, "a thread per filtered plane solves");
+
+__host__ __device__ inline bool hr_haze(int rule) { return rule == LG_MTFHR_HPM_H || rule == LG_MTFHR_BT_H; }
+__host__ __device__ inline int hr_gram_ns(int C, int F) { return (C + 1) * (C + 2) / 2 + F * (C + 1); }
+__host__ __device__ inline int hr_moments_lds_doubles(int C) { return CL_SCRATCH + 4 * CL_PX + HR_SUMS * C; }
+__host__ __device__ inline int hr_gram_lds_doubles(int C, int F) { return (1 + C + F) * HR_CHUNK + hr_gram_ns(C, F) + 4 * C; }
+__host__ __device__ inline int hr_apply_lds_doubles(int C, int rule) { return rule == LG_MTFHR_BT_H ? CL_SCRATCH + C * CL_PX : MG_LDS; }
+
+// the samples of D (the filtered PAN minus the pivot) the tile at o depends on, where cl_ms_load takes those of ms: the tile holds L minus the pivot, which
+// is exactly 0 for a constant PAN
+__device__ __forceinline__ void hr_d_load(const double* __restrict__ dl, int h, int w, ClTile o, double (&v)[CL_MLOADS]) {
+    const int my0 = o.Y0 / 4 - 8, mx0 = o.X0 / 4 - 8;
+#pragma unroll
+    for (int u = 0; u < CL_MLOADS; ++u) {
+        const int i = threadIdx.x + u * CL_NT, r = i / CL_MC, c = i - r * CL_MC;
+        v[u] = 0.0;
+        if (i < CL_MR * CL_MC) v[u] = dl[(long)cl_mod(my0 + r, h) * w + cl_mod(mx0 + c, w)];
+    }
+}
+
+// r = num / den, 1 (no injection) where the denominator is not > 0 or the ratio is not finite
+__device__ __forceinline__ double hr_ratio(double num, double den) {
+    const double r = num / den;
+    return den > 0.0 && r - r == 0.0 ? r : 1.0;
+}
+
+// part [B][gx][7 C]: per band the sums over the sample of uc = u - m_k, lc = L - mu, pc = pan - mu, uc pc, lc pc, uc lc, lc lc
+__global__ __launch_bounds__(CL_NT) void k_hr_moments(const float* __restrict__ ms, const float* __restrict__ pan, const double* __restrict__ dlow,
+                                                      const double* __restrict__ coef, double* __restrict__ part, int C, int F, int h, int w, int tiles_x,
+                                                      int tiles) {
+    extern __shared__ double cl_lds[];
+    __shared__ int pairs[HR_SUMS];
+    double* V = cl_lds + CL_SCRATCH;             // [4][512]: uc, lc, pc, mask
+    double* acc = V + 4 * CL_PX;                 // [7 C]
+    const int tid = threadIdx.x, gx = gridDim.x;
+    const int H4 = 4 * h, W4 = 4 * w;
+    const long b = blockIdx.y, lp = (long)h * w;
+    const float* __restrict__ ms_b = ms + b * C * lp;
+    const float* __restrict__ pan_b = pan + b * ((long)H4 * W4);
+    const double* __restrict__ dl_b = dlow + b * F * lp;
+    const double* __restrict__ co = coef + b * (3 * C + 1);
+    const double pv = (double)pan_b[0], mpc = co[0];
+    if (tid == 0) {
+        pairs[0] = cl_pair(3, 0, 0);
+        pairs[1] = cl_pair(3, 1, 0);
+        pairs[2] = cl_pair(3, 2, 0);
+        pairs[3] = cl_pair(0, 2, 0);
+        pairs[4] = cl_pair(1, 2, 0);
+        pairs[5] = cl_pair(0, 1, 0);
+        pairs[6] = cl_pair(1, 1, 0);
+    }
+    for (int e = tid; e < HR_SUMS * C; e += CL_NT) acc[e] = 0.0;      // (the barriers inside cl_up_band order both before their first use)
+    float v[CL_MLOADS], vn[CL_MLOADS] = {};
+    double q[CL_MLOADS], qn[CL_MLOADS] = {};
+    cl_ms_load(ms_b, h, w, cl_tile(blockIdx.x, tiles_x), v);
+    hr_d_load(dl_b, h, w, cl_tile(blockIdx.x, tiles_x), q);
+    for (int t = blockIdx.x; t < tiles; t += gx) {
+        const auto [Y0, X0] = cl_tile(t, tiles_x);
+        float pn[CL_PX / CL_NT];
+#pragma unroll
+        for (int u = 0; u < CL_PX / CL_NT; ++u) {
+            const int p = tid + u * CL_NT, y = Y0 + p / CL_TW, x = X0 + p % CL_TW;
+            pn[u] = y < H4 && x < W4 ? pan_b[(long)y * W4 + x] : 0.f;
+        }
+        for (int k = 0; k < C; ++k) {
+            const int kn = k + 1 < C ? k + 1 : 0, tn = k + 1 < C ? t : t + gx;
+            if (tn < tiles) {
+                cl_ms_load(ms_b + kn * lp, h, w, cl_tile(tn, tiles_x), vn);
+                hr_d_load(dl_b + (F == 1 ? 0 : kn) * lp, h, w, cl_tile(tn, tiles_x), qn);
+            }
+            cl_up_band(v, cl_lds, V);
+            cl_up_band(q, cl_lds, V + CL_PX);
+            __syncthreads();
+            const double m = co[1 + k];
+#pragma unroll
+            for (int u = 0; u < CL_PX / CL_NT; ++u) {
+                const int p = tid + u * CL_NT;
+                const bool in = Y0 + p / CL_TW < H4 && X0 + p % CL_TW < W4;      // what a ragged tile holds outside the image counts as 0
+                V[p] = in ? V[p] - m : 0.0;
+                V[CL_PX + p] = in ? V[CL_PX + p] - mpc : 0.0;      // (L - pivot) - (mu - pivot)
+                if (k == 0) {      // the tile's own: the last reads of the tile before lie eight barriers back
+                    V[2 * CL_PX + p] = in ? ((double)pn[u] - pv) - mpc : 0.0;
+                    V[3 * CL_PX + p] = in ? 1.0 : 0.0;
+                }
+            }
+            __syncthreads();
+            cl_pair_sums(pairs, HR_SUMS, acc + HR_SUMS * k, [&](int a, int c, int, int lane) { return cl_lane_dot<CL_PX>(V + a * CL_PX, V + c * CL_PX, lane); });
+            cl_next(v, vn);
+            cl_next(q, qn);
+            // no barrier: the next cl_up_band writes the tiles of u and L in its last pass, four barriers from here
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < HR_SUMS * C; e += CL_NT) part[(b * gx + blockIdx.x) * (HR_SUMS * C) + e] = acc[e];
+}
+
+// hc (and stats, unless NULL) [B][2 C + 2]: g_k, then b_k (hpm_r; 0 for fs), then two zeros.  g_k = 0 where the denominator is not > 0 or not finite or the gain
+// is not finite
+__global__ __launch_bounds__(CL_NT) void k_hr_finish(const double* __restrict__ part, const float* __restrict__ pan, const double* __restrict__ coef,
+                                                     double* __restrict__ hc, double* __restrict__ stats, int C, int gx, double N, int rule) {
+    __shared__ double sums[HR_SUMS * CL_MAX_C];
+    const long b = blockIdx.x;
+    const int ns = HR_SUMS * C, k = threadIdx.x;
+    for (int e = threadIdx.x; e < ns; e += CL_NT) sums[e] = cl_partials_column(part + b * gx * ns + e, gx, ns);
+    __syncthreads();
+    if (k >= C + 2) return;
+    double g = 0.0, bk = 0.0;
+    if (k < C) {
+        const double* co = coef + b * (3 * C + 1);
+        const double* s = sums + HR_SUMS * k;
+        const double su = s[0], sl = s[1], sp = s[2];
+        const double num = rule == LG_MTFHR_FS ? s[3] - su * sp / N : s[5] - su * sl / N;
+        const double den = rule == LG_MTFHR_FS ? s[4] - sl * sp / N : s[6] - sl * sl / N;
+        g = num / den;
+        if (!(den > 0.0 && den - den == 0.0 && g - g == 0.0)) g = 0.0;
+        const double mean_l = ((double)pan[b * (long)N] + co[0]) + sl / N;
+        if (rule == LG_MTFHR_HPM_R) bk = co[1 + k] - g * mean_l;
+    }
+    double* o = hc + b * (2 * C + 2);
+    double* st = stats ? stats + b * (2 * C + 2) : nullptr;
+    if (k < C) {
+        o[k] = g;
+        o[C + k] = bk;
+        if (st) st[k] = g, st[C + k] = bk;
+    } else {
+        o[C + k] = 0.0;
+        if (st) st[C + k] = 0.0;
+    }
+}
+
+// part [B][gpb][ns + C], ns = hr_gram_ns(C, F): with the vectors [mask, ms_0 - ms_0(0) .. , D_0 ..] the upper triangle over the first C + 1 in row-major order,
+// then per plane f the C + 1 sums against D_f (the mask first); then the C minima of the raw bands
+__global__ __launch_bounds__(CL_NT) void k_hr_gram(const float* __restrict__ ms, const double* __restrict__ dlow, double* __restrict__ part, int C, int F,
+                                                   int h, int w) {
+    extern __shared__ double cl_lds[];
+    __shared__ int pairs[HR_MAX_NS];
+    const int n = C + 1, nv = n + F, ns = hr_gram_ns(C, F), tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, gpb = gridDim.x;
+    double* V = cl_lds;                          // [nv][256]
+    double* acc = V + nv * HR_CHUNK;             // [ns]
+    double* mins = acc + ns;                     // [C][4]
+    const long b = blockIdx.y, lp = (long)h * w;
+    const float* __restrict__ ms_b = ms + b * C * lp;
+    const double* __restrict__ dl_b = dlow + b * F * lp;
+    if (tid == 0) {
+        int e = 0;
+        for (int a = 0; a < n; ++a)
+            for (int c = a; c < n; ++c) pairs[e++] = cl_pair(a, c, 0);
+        for (int f = 0; f < F; ++f)
+            for (int j = 0; j < n; ++j) pairs[e++] = cl_pair(j, n + f, 0);
+    }
+    for (int e = tid; e < ns; e += CL_NT) acc[e] = 0.0;
+    for (int e = tid; e < 4 * C; e += CL_NT) mins[e] = INFINITY;
+    __syncthreads();
+    for (long c0 = (long)blockIdx.x * HR_CHUNK; c0 < lp; c0 += (long)gpb * HR_CHUNK) {
+        const long o = c0 + tid;
+        const int live = lp - c0 < HR_CHUNK ? (int)(lp - c0) : HR_CHUNK;
+        const bool in = o < lp;
+        V[tid] = in ? 1.0 : 0.0;
+        for (int k = 0; k < C; ++k) {
+            const float x = in ? ms_b[k * lp + o] : INFINITY;
+            V[(1 + k) * HR_CHUNK + tid] = in ? (double)x - (double)ms_b[k * lp] : 0.0;
+            float mn = x;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) mn = fminf(mn, __shfl_xor(mn, off));
+            if (lane == 0) mins[4 * k + wave] = fmin(mins[4 * k + wave], (double)mn);
+        }
+        for (int f = 0; f < F; ++f) V[(n + f) * HR_CHUNK + tid] = in ? dl_b[f * lp + o] : 0.0;
+        __syncthreads();
+        cl_pair_sums(pairs, ns, acc, [&](int a, int c, int, int ln) { return cl_lane_dot(V + a * HR_CHUNK, V + c * HR_CHUNK, ln, live); });
+        __syncthreads();      // the next chunk overwrites the vectors
+    }
+    double* pb = part + (b * gpb + blockIdx.x) * (ns + C);
+    for (int e = tid; e < ns; e += CL_NT) pb[e] = acc[e];
+    for (int k = tid; k < C; k += CL_NT) pb[ns + k] = fmin(fmin(mins[4 * k], mins[4 * k + 1]), fmin(mins[4 * k + 2], mins[4 * k + 3]));
+}
+
+// hc (and stats, unless NULL) [B][2 C + 2].  hpm_h: H_k, then H_P,k (F = 1: one value for every band), two zeros.  bt_h: H_k, the slopes w_k, w_0, H_I.
+__global__ __launch_bounds__(HR_SOLVE_NT) void k_hr_solve(const double* __restrict__ part, const float* __restrict__ ms, const float* __restrict__ pan,
+                                                          double* __restrict__ hc, double* __restrict__ stats, int C, int F, int gpb, long lp, int rule) {
+    __shared__ double sums[HR_MAX_NS];
+    __shared__ double Lm[CL_MAX_C * CL_MAX_C], sl[CL_MAX_C * CL_MAX_C], H[CL_MAX_C], mm[CL_MAX_C], hp[CL_MAX_C], w0[CL_MAX_C];
+    __shared__ int bad_pivot;
+    const int n = C + 1, ng = n * (n + 1) / 2, ns = hr_gram_ns(C, F), stride = ns + C, tid = threadIdx.x;
+    const long b = blockIdx.x;
+    const double nl = (double)lp;
+    const double* pb = part + b * gpb * stride;
+    for (int e = tid; e < ns; e += HR_SOLVE_NT) sums[e] = cl_partials_column(pb + e, gpb, stride);
+    if (tid < C) {
+        double m = INFINITY;
+        for (int j = 0; j < gpb; ++j) m = fmin(m, pb[(long)j * stride + ns + tid]);
+        H[tid] = m;
+    }
+    if (tid == 0) bad_pivot = 0;
+    __syncthreads();
+    auto S = [&](int a, int c) { return sums[a * n - a * (a - 1) / 2 + (c - a)]; };      // a <= c, both among the mask and the bands
+    if (tid < C) mm[tid] = (double)ms[(b * C + tid) * lp] + S(0, 1 + tid) / nl;
+    if (tid == 0) {
+        // the centred Gram matrix of ms, the lower triangle in Lm
+        for (int k = 0; k < C; ++k)
+            for (int l = 0; l <= k; ++l) Lm[k * C + l] = S(1 + l, 1 + k) - S(0, 1 + k) * S(0, 1 + l) / nl;
+        if (!cl_cholesky(Lm, C, C, [&](int i, int j) { return Lm[i * C + j]; }, [](double d, double) { return !(d > 0.0); })) bad_pivot = 1;
+    }
+    __syncthreads();
+    if (tid < F) {
+        const double* r = sums + ng + tid * n;   // sum D_f, then sum (ms_j - pivot_j) D_f
+        double* x = sl + tid * C;
+        bool ok = !bad_pivot;
+        if (ok) {
+            for (int i = 0; i < C; ++i) x[i] = r[1 + i] - S(0, 1 + i) * r[0] / nl;
+            cl_chol_solve(Lm, C, C, x, x, [&](double xi) { ok = ok && xi - xi == 0.0; });
+        }
+        if (!ok)
+            for (int i = 0; i < C; ++i) x[i] = 0.0;
+        const double mean_d = (double)pan[b * 16 * lp] + r[0] / nl;
+        double a = mean_d, c = mean_d;
+        for (int j = 0; j < C; ++j) {
+            a = fma(x[j], H[j] - mm[j], a);
+            c = fma(-x[j], mm[j], c);
+        }
+        hp[tid] = a;
+        w0[tid] = c;
+    }
+    __syncthreads();
+    double* o = hc + b * (2 * C + 2);
+    double* st = stats ? stats + b * (2 * C + 2) : nullptr;
+    for (int i = tid; i < 2 * C + 2; i += HR_SOLVE_NT) {
+        double v;
+        if (i < C) {
+            v = H[i];
+        } else if (rule == LG_MTFHR_HPM_H) {
+            v = i < 2 * C ? hp[F == 1 ? 0 : i - C] : 0.0;
+        } else if (i < 2 * C) {
+            v = sl[i - C];
+        } else if (i == 2 * C) {
+            v = w0[0];
+        } else {
+            v = w0[0];
+            for (int k = 0; k < C; ++k) v = fma(sl[k], H[k], v);
+        }
+        o[i] = v;
+        if (st) st[i] = v;
+    }
+}
+
+template <int RULE>
+__global__ __launch_bounds__(CL_NT) void k_hr_apply(const float* __restrict__ ms, const float* __restrict__ pan, const double* __restrict__ dlow,
+                                                    float* __restrict__ out, const double* __restrict__ hc, int C, int F, int h, int w, int tiles_x) {
+    extern __shared__ double cl_lds[];
+    double* U = cl_lds + CL_SCRATCH;
+    const int tid = threadIdx.x, H4 = 4 * h, W4 = 4 * w;
+    const auto [Y0, X0] = cl_tile(blockIdx.x, tiles_x);
+    const long b = blockIdx.y, lp = (long)h * w, plane = (long)H4 * W4;
+    const float* __restrict__ ms_b = ms + b * C * lp;
+    const float* __restrict__ pan_b = pan + b * plane;
+    float* __restrict__ out_b = out + b * C * plane;
+    const double* __restrict__ co = hc + b * (2 * C + 2);
+    const int p = 2 * tid, y = Y0 + p / CL_TW, x = X0 + p % CL_TW;
+    const bool in = y < H4 && x < W4;            // W4 is a multiple of 4 and x is even: both pixels or none
+    const long o = (long)y * W4 + x;
+    float2 pp = make_float2(0.f, 0.f);
+    if (in) pp = *reinterpret_cast<const float2*>(pan_b + o);
+    const double p0 = (double)pp.x, p1 = (double)pp.y;
+    if constexpr (RULE == LG_MTFHR_BT_H) {
+        cl_up_bands(ms_b, lp, C, h, w, Y0, X0, cl_lds, U);
+        __syncthreads();
+        if (!in) return;
+        double s0 = 0.0, s1 = 0.0;                // I - H_I = sum_k w_k (u_k - H_k)
+        for (int k = 0; k < C; ++k) {
+            const double wk = co[C + k], H = co[k];
+            s0 = fma(wk, U[k * CL_PX + p] - H, s0);
+            s1 = fma(wk, U[k * CL_PX + p + 1] - H, s1);
+        }
+        const double hi = co[2 * C + 1], r0 = hr_ratio(p0 - hi, s0), r1 = hr_ratio(p1 - hi, s1);
+        for (int k = 0; k < C; ++k) {
+            const double H = co[k];
+            *reinterpret_cast<float2*>(out_b + k * plane + o) =
+                make_float2(cl_clip(fma(U[k * CL_PX + p] - H, r0, H)), cl_clip(fma(U[k * CL_PX + p + 1] - H, r1, H)));
+        }
+    } else {
+        double* Lt = U + CL_PX;
+        const double* __restrict__ dl_b = dlow + b * F * lp;
+        const double pv = (double)pan_b[0];
+        float v[CL_MLOADS], vn[CL_MLOADS] = {};
+        double q[CL_MLOADS], qn[CL_MLOADS] = {};
+        cl_ms_load(ms_b, h, w, {Y0, X0}, v);
+        hr_d_load(dl_b, h, w, {Y0, X0}, q);
+        for (int k = 0; k < C; ++k) {
+            if (k + 1 < C) {
+                cl_ms_load(ms_b + (k + 1) * lp, h, w, {Y0, X0}, vn);
+                hr_d_load(dl_b + (F == 1 ? 0 : k + 1) * lp, h, w, {Y0, X0}, qn);
+            }
+            cl_up_band(v, cl_lds, U);
+            cl_up_band(q, cl_lds, Lt);
+            __syncthreads();
+            if (in) {
+                const double c0 = co[k], c1 = co[C + k];      // fs: g; hpm_r: g, b; hpm_h: H, H_P
+                const double u0 = U[p], u1 = U[p + 1], l0 = Lt[p] + pv, l1 = Lt[p + 1] + pv;
+                double o0, o1;
+                if (RULE == LG_MTFHR_FS) {
+                    o0 = fma(c0, p0 - l0, u0);
+                    o1 = fma(c0, p1 - l1, u1);
+                } else if (RULE == LG_MTFHR_HPM_R) {
+                    o0 = u0 * hr_ratio(fma(c0, p0, c1), fma(c0, l0, c1));
+                    o1 = u1 * hr_ratio(fma(c0, p1, c1), fma(c0, l1, c1));
+                } else {
+                    o0 = fma(u0 - c0, hr_ratio(p0 - c1, l0 - c1), c0);
+                    o1 = fma(u1 - c0, hr_ratio(p1 - c1, l1 - c1), c0);
+                }
+                *reinterpret_cast<float2*>(out_b + k * plane + o) = make_float2(cl_clip(o0), cl_clip(o1));
+            }
+            cl_next(v, vn);
+            cl_next(q, qn);
+            // no barrier: the next cl_up_band writes U and Lt in its last pass, four barriers from here
+        }
+    }
+}
+
+struct HrGeom {
+    ClGeom cl;                 // SFIM's: the tiles and the first moments pass (fs, hpm_r)
+    int gx2;                   // workgroups per sample of k_hr_moments (fs, hpm_r) or of k_hr_gram (hpm_h, bt_h)
+    size_t off[5], bytes;      // part, coef (fs, hpm_r), D, part2, hc
+};
+
+bool hr_geom(const char* who, int B, int C, int h, int w, int n_filters, int rule, HrGeom& g) {
+    if (rule != LG_MTFHR_FS && rule != LG_MTFHR_HPM_R && rule != LG_MTFHR_HPM_H && rule != LG_MTFHR_BT_H) {
+        lg_set_error("%s: rule must be LG_MTFHR_FS, LG_MTFHR_HPM_R, LG_MTFHR_HPM_H or LG_MTFHR_BT_H (got %d)", who, rule);
+        return false;
+    }
+    if (!cl_geom(who, B, C, h, w, LG_CLASSICAL_SFIM, g.cl)) return false;
+    if (!mg_filters_ok(who, C, n_filters)) return false;
+    if (rule == LG_MTFHR_BT_H && n_filters != 1) { lg_set_error("%s: n_filters must be 1 for LG_MTFHR_BT_H (got %d)", who, n_filters); return false; }
+    const bool haze = hr_haze(rule);
+    if (haze) {
+        const long chunks = ((long)h * w + HR_CHUNK - 1) / HR_CHUNK;
+        g.gx2 = chunks < HR_GRAM_WGS ? (int)chunks : HR_GRAM_WGS;
+    } else {
+        g.gx2 = g.cl.tiles < MG_RESIDENT ? g.cl.tiles : MG_RESIDENT;
+    }
+    const size_t per2 = haze ? (size_t)g.gx2 * (hr_gram_ns(C, n_filters) + C) : (size_t)g.gx2 * HR_SUMS * C;
+    const size_t sz[5] = {haze ? 0 : ws_region(B, (size_t)g.cl.gx * g.cl.ns * sizeof(double)), haze ? 0 : ws_region(B, (size_t)(3 * C + 1) * sizeof(double)),
+                          ws_region(B, (size_t)n_filters * h * w * sizeof(double)), ws_region(B, per2 * sizeof(double)),
+                          ws_region(B, (size_t)(2 * C + 2) * sizeof(double))};
+    g.bytes = ws_layout(5, sz, g.off);
+    return true;
+}
+
+DeviceOnce hr_attr_once;
+int hr_lds_attr(const char* who) {
+    if (!hr_attr_once.need()) return 0;
+    if (int rc = lds_attr_set(who, hr_moments_lds_doubles(CL_MAX_C) * (int)sizeof(double), k_hr_moments)) return rc;
+    if (int rc = lds_attr_set(who, hr_gram_lds_doubles(CL_MAX_C, CL_MAX_C) * (int)sizeof(double), k_hr_gram)) return rc;
+    if (int rc = lds_attr_set(who, hr_apply_lds_doubles(CL_MAX_C, LG_MTFHR_BT_H) * (int)sizeof(double), k_hr_apply<LG_MTFHR_BT_H>)) return rc;
+    hr_attr_once.done();
+    return 0;
+}
+
+int hr_fuse(const char* who, const lg_mtf_hr_args* a) {
+    if (!a) { lg_set_error("%s: args is NULL", who); return -1; }
+    if (a->struct_bytes != sizeof(lg_mtf_hr_args)) {
+        lg_set_error("%s: struct_bytes must be sizeof(lg_mtf_hr_args) = %zu (got %u)", who, sizeof(lg_mtf_hr_args), a->struct_bytes);
+        return -1;
+    }
+    const int B = a->B, C = a->C, h = a->h, w = a->w, F = a->n_filters, rule = a->rule;
+    HrGeom g;
+    if (!hr_geom(who, B, C, h, w, F, rule, g)) return -1;
+    if (!mg_taps_ok(who, a->n_taps)) return -1;
+    if (!cl_check_args(who, a->ms, a->pan, a->out, {{"taps", a->taps}}, a->stats, a->workspace, a->workspace_bytes, g.bytes, "lg_mtf_hr_workspace_bytes"))
+        return -1;
+    if (int rc = cl_lds_attr(who)) return rc;
+    if (int rc = hr_lds_attr(who)) return rc;
+    hipStream_t s = (hipStream_t)a->stream;
+    double *part = cl_ws(a->workspace, g.off[0]), *coef = cl_ws(a->workspace, g.off[1]), *dlow = cl_ws(a->workspace, g.off[2]);
+    double *part2 = cl_ws(a->workspace, g.off[3]), *hc = cl_ws(a->workspace, g.off[4]);
+    const int tiles_x = g.cl.tiles_x, tiles = g.cl.tiles;
+    const double N = 16.0 * h * w;
+    const int lt_x = (w + MG_TO - 1) / MG_TO, lt = lt_x * ((h + MG_TO - 1) / MG_TO);
+    const size_t lds = hr_apply_lds_doubles(C, rule) * sizeof(double);
+    if (hr_haze(rule)) {
+        k_mg_lowpass<<<dim3(lt, F, B), CL_NT, 0, s>>>(a->pan, a->taps, dlow, h, w, a->n_taps, lt_x);
+        LG_CHECK_LAUNCH();
+        k_hr_gram<<<dim3(g.gx2, B), CL_NT, hr_gram_lds_doubles(C, F) * sizeof(double), s>>>(a->ms, dlow, part2, C, F, h, w);
+        LG_CHECK_LAUNCH();
+        k_hr_solve<<<B, HR_SOLVE_NT, 0, s>>>(part2, a->ms, a->pan, hc, a->stats, C, F, g.gx2, (long)h * w, rule);
+        LG_CHECK_LAUNCH();
+        if (rule == LG_MTFHR_BT_H)
+            k_hr_apply<LG_MTFHR_BT_H><<<dim3(tiles, B), CL_NT, lds, s>>>(a->ms, a->pan, dlow, a->out, hc, C, F, h, w, tiles_x);
+        else
+            k_hr_apply<LG_MTFHR_HPM_H><<<dim3(tiles, B), CL_NT, lds, s>>>(a->ms, a->pan, dlow, a->out, hc, C, F, h, w, tiles_x);
+    } else {
+        k_cl_moments<<<dim3(g.cl.gx, B), CL_NT, cl_moment_lds_doubles(C) * sizeof(double), s>>>(a->ms, a->pan, part, C, h, w, tiles_x, tiles, 0);
+        LG_CHECK_LAUNCH();
+        k_cl_finish<<<B, CL_NT, 0, s>>>(part, coef, nullptr, C, g.cl.gx, N, (double)h * w, 0);
+        LG_CHECK_LAUNCH();
+        k_mg_lowpass<<<dim3(lt, F, B), CL_NT, 0, s>>>(a->pan, a->taps, dlow, h, w, a->n_taps, lt_x);
+        LG_CHECK_LAUNCH();
+        k_hr_moments<<<dim3(g.gx2, B), CL_NT, hr_moments_lds_doubles(C) * sizeof(double), s>>>(a->ms, a->pan, dlow, coef, part2, C, F, h, w, tiles_x, tiles);
+        LG_CHECK_LAUNCH();
+        k_hr_finish<<<B, CL_NT, 0, s>>>(part2, a->pan, coef, hc, a->stats, C, g.gx2, N, rule);
+        LG_CHECK_LAUNCH();
+        if (rule == LG_MTFHR_FS)
+            k_hr_apply<LG_MTFHR_FS><<<dim3(tiles, B), CL_NT, lds, s>>>(a->ms, a->pan, dlow, a->out, hc, C, F, h, w, tiles_x);
+        else
+            k_hr_apply<LG_MTFHR_HPM_R><<<dim3(tiles, B), CL_NT, lds, s>>>(a->ms, a->pan, dlow, a->out, hc, C, F, h, w, tiles_x);
+    }
+    LG_CHECK_LAUNCH();
+    return 0;
+}
+
 // ---- BDSD: the band-dependent spatial detail method, global or per block of block x block PAN pixels.  Per block and band the weights gamma
 // are the least-squares fit of ms_k - A_k on x = [A_1 .. A_C, D] at the MS scale (A_k: the band low-passed on its own grid, D: the raw PAN low-passed at the
 // decimated positions, k_mg_lowpass's plane plus the pivot); out_k = clip(u_k + sum_j gamma_kj u_j + gamma_kC pan).
@@ -1188,6 +1620,13 @@ extern "C" size_t lg_atrous_workspace_bytes(int32_t B, int32_t C, int32_t h, int
 }
 
 extern "C" int lg_atrous(const lg_atrous_args* args) { return at_fuse("atrous", args); }
+
+extern "C" size_t lg_mtf_hr_workspace_bytes(int32_t B, int32_t C, int32_t h, int32_t w, int32_t n_filters, int32_t rule) {
+    HrGeom g;
+    return hr_geom("mtf_hr_workspace_bytes", B, C, h, w, n_filters, rule, g) ? g.bytes : 0;
+}
+
+extern "C" int lg_mtf_hr(const lg_mtf_hr_args* args) { return hr_fuse("mtf_hr", args); }
 
 extern "C" int lg_atrous_taps(double* out13) {
     if (!out13) { lg_set_error("atrous_taps: out13 is NULL"); return -1; }

@@ -1,5 +1,5 @@
 """The bits of the classical baselines, for comparing two builds of the library: every public function of lgteun_amd/classical.py, mtf_glp.py, bdsd.py,
-cs.py and atrous.py on tests/classical_ref.make_batch inputs (B make_scene scenes stacked, seeds 7000 + b), at the shapes the GPU tests use, and the SHA-256 of each output and of each stats tensor.
+cs.py, atrous.py and mtf_hr.py on tests/classical_ref.make_batch inputs (B make_scene scenes stacked, seeds 7000 + b), at the shapes the GPU tests use, and the SHA-256 of each output and of each stats tensor.
 One more shape for the component-substitution modes only: (C, h, w, B) = (4, 368, 368, 1) has 529 Gram tiles against the 512 workgroups of k_cs_gram, the
 smallest square shape at which one of them walks a second tile ((4, 136, 256, 1), in every list, is that shape for the moments and BDSD Gram passes).
 Prints one JSON line {name: digest}.  Run it once per library and compare the lines:
@@ -20,7 +20,8 @@ import classical_ref as cr  # noqa: E402
 import cs_ref as csr  # noqa: E402
 import mtf_glp_ref as mr  # noqa: E402
 import wavelet_ref as wr  # noqa: E402
-from lgteun_amd import atrous, bdsd, classical, cs, mtf_glp  # noqa: E402
+import mtf_hr_ref as hr  # noqa: E402
+from lgteun_amd import atrous, bdsd, classical, cs, mtf_glp, mtf_hr  # noqa: E402
 
 CS_SECOND_TILE = (4, 368, 368, 1)
 SEED = 7
@@ -68,6 +69,13 @@ def main():
             ms, pan = batch(*shape)
             for rule in ar.RULES:
                 put(f'{rule}_{match}', shape, atrous.atrous(ms, pan, rule, match, return_stats=True))
+    for rule in hr.RULES:
+        for shape in hr.SHAPES[rule] + hr.PROPERTY_SHAPES[:1]:
+            ms, pan = batch(*shape)
+            put(f'mtf_hr_{rule}', shape, mtf_hr.fuse(ms, pan, rule, return_stats=True))
+        for shape in hr.PER_BAND_SHAPES[rule]:
+            ms, pan = batch(*shape)
+            put(f'mtf_hr_{rule}_per_band', shape, mtf_hr.fuse(ms, pan, rule, gains_ms=mr.per_band_gains(shape[0]), return_stats=True))
     print(json.dumps({'tool': 'classical_bits', 'lib': os.environ.get('LGTEUN_HIP_LIB', 'in-tree'), 'n': len(res), 'sha256': res}))
 
 

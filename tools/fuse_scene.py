@@ -8,13 +8,15 @@ dataset.read_tiff, fuses them tile by tile on the GPU (lgteun_amd/scene.py) and 
     python tools/fuse_scene.py PREFIX --method ihs|brovey|gs|pca [--cs-weights w [w ...]] [--bit-depth 11] ...
     python tools/fuse_scene.py PREFIX --method bdsd [--bdsd-block N] [--mtf-gains g [g ...]] [--mtf-gain-pan g] [--bit-depth 11] ...
     python tools/fuse_scene.py PREFIX --method atwt|awlp [--atrous-match pan|lowpass] [--bit-depth 11] ...
+    python tools/fuse_scene.py PREFIX --method fs|hpm_r|hpm_h|bt_h [--mtf-gains g [g ...]] [--mtf-gain-pan g] [--bit-depth 11] ...
 
 --method gsa / sfim / wavelet (lgteun_amd/classical.py) and mtf_glp / mtf_glp_hpm / mtf_glp_cbd (lgteun_amd/mtf_glp.py) need no checkpoint and no
 tiles: the whole scene is fused in one call, with the same normalisation and the same conversion to digital numbers.  --mtf-gains: the sensor's MTF
 gains at Nyquist, one for all bands or one per band; without them a placeholder (0.3) applies, which is no sensor's value.  --method bdsd
 (lgteun_amd/bdsd.py) takes them too, with --mtf-gain-pan for PAN (placeholder 0.15), and --bdsd-block N fits its weights per block of N x N PAN pixels (a
 multiple of 32 that divides both sides of PAN; without it one fit serves the whole scene).  --method ihs / brovey / gs / pca (lgteun_amd/cs.py) are the
-component-substitution baselines; --cs-weights gives the intensity weights of the first three, one per band (without them 1 / C each).
+component-substitution baselines; --cs-weights gives the intensity weights of the first three, one per band (without them 1 / C each).  --method fs / hpm_r /
+hpm_h / bt_h (lgteun_amd/mtf_hr.py) are the regression-based and haze-corrected MTF rules: the first three take --mtf-gains, bt_h takes --mtf-gain-pan.
 
 The checkpoint is a plain-tensor file ({'core_module': state_dict}, what Base_model.save writes and tools/convert_checkpoint.py makes of a
 reference-era file); the band count and the stage count are read from it.  The output holds uint16 digital numbers
@@ -47,12 +49,12 @@ def parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('prefix')
     ap.add_argument('--method', choices=['network', 'gsa', 'sfim', 'wavelet', 'mtf_glp', 'mtf_glp_hpm', 'mtf_glp_cbd', 'bdsd', 'ihs', 'brovey', 'gs', 'pca',
-                                         'atwt', 'awlp'], default='network')
+                                         'atwt', 'awlp', 'fs', 'hpm_r', 'hpm_h', 'bt_h'], default='network')
     ap.add_argument('--atrous-match', choices=['pan', 'lowpass'], default='pan',
                     help="--method atwt / awlp: the deviation the detail is scaled by, std(pan) or std of the low-passed PAN (default: pan)")
     ap.add_argument('--mtf-gains', type=float, nargs='+', default=None, metavar='g',
-                    help="--method mtf_glp* / bdsd: the sensor's MTF gain at Nyquist, one for all bands or one per band (default: a placeholder, 0.3)")
-    ap.add_argument('--mtf-gain-pan', type=float, default=None, metavar='g', help="--method bdsd: PAN's MTF gain at Nyquist (default: a placeholder, 0.15)")
+                    help="--method mtf_glp* / bdsd / fs / hpm_r / hpm_h: the sensor's MTF gain at Nyquist, one for all bands or one per band (default: a placeholder, 0.3)")
+    ap.add_argument('--mtf-gain-pan', type=float, default=None, metavar='g', help="--method bdsd / bt_h: PAN's MTF gain at Nyquist (default: a placeholder, 0.15)")
     ap.add_argument('--bdsd-block', type=int, default=None, metavar='N',
                     help='--method bdsd: fit the weights per block of N x N PAN pixels, N a multiple of 32 that divides both sides (default: one global fit)')
     ap.add_argument('--cs-weights', type=float, nargs='+', default=None, metavar='w',
@@ -95,6 +97,10 @@ def main():
         from lgteun_amd import atrous
         fused = atrous.fuse_scene(atrous.SCENE_METHODS[a.method], ms_chw, pan[np.newaxis], match=a.atrous_match, bit_depth=a.bit_depth,
                                   norm_input=a.norm_input, out_dtype='float32' if a.float else 'uint16')
+    elif a.method in ('fs', 'hpm_r', 'hpm_h', 'bt_h'):
+        from lgteun_amd import mtf_hr
+        fused = mtf_hr.fuse_scene(a.method, ms_chw, pan[np.newaxis], gains_ms=gains, gain_pan=a.mtf_gain_pan, bit_depth=a.bit_depth, norm_input=a.norm_input,
+                                  out_dtype='float32' if a.float else 'uint16')
     elif a.method.startswith('mtf_glp'):
         from lgteun_amd import mtf_glp
         fused = mtf_glp.fuse_scene(mtf_glp.SCENE_METHODS[a.method], ms_chw, pan[np.newaxis], gains_ms=gains, bit_depth=a.bit_depth, norm_input=a.norm_input,
