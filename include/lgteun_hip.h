@@ -46,6 +46,9 @@
  *         step to step pays a device drain in every backward.  Results are the same either way.
  *    Everything else -- every forward, loss, optimizer, metric, classical, data-preparation and scene entry, and a backward whose
  *    table is cached -- allocates nothing and synchronises nothing.
+ *  - arguments are validated before any HIP call; a rejected call launches and writes nothing.  The network entries' ranges -- the batch bound, the
+ *    alignment of tensors and workspace, the flag bits each entry takes -- stand at lg_workspace_bytes below (tests/test_net_abi_cpu.py,
+ *    tests/test_gpu_net_limits.py); the entries around the network state theirs in their own blocks (tests/test_abi_limits_cpu.py, test_gpu_abi_limits.py).
  *  - return value: 0 ok; <0 invalid argument / unsupported shape (see lg_last_error());
  *    >0 a hipError_t.  Nothing throws across the boundary.
  *  - parameters live in ONE flat fp32 buffer; `offsets[i]` (in floats) locates the i-th tensor of
@@ -176,11 +179,34 @@ int lg_plan_describe(const lg_plan* plan, char* buf, size_t n);
  * tests/test_gpu_workspace_contract.py:
  *  - what the workspace holds ON ENTRY is arbitrary -- zeros, NaNs, huge values, what an earlier call on other inputs left: every region is
  *    written in a call before that call reads it, and results do not depend on it.  It holds data only (floats, bf16, keep-bit words), never an
- *    index or a pointer.  256-byte alignment is enough; bytes beyond lg_workspace_bytes are not written and change nothing.
+ *    index or a pointer.  It is 256-byte aligned (the entries check it); bytes beyond lg_workspace_bytes are not written and change nothing.
  *  - a call with workspace_bytes below lg_workspace_bytes, or a null workspace, returns an error and launches nothing.
  *  - between a forward with LG_FLAG_SAVE and its backward (same plan, B, flags, seed, pointer) the WHOLE workspace must stay untouched: the
  *    saved activation set(s), the data steps' intermediates and the per-block tables of that forward live there.  Nothing else has to survive
- *    from one call to the next. */
+ *    from one call to the next.
+ *
+ * The network entries' argument contract -- lgteun_forward / _backward / _dead_forward, lg_op_resample, lg_op_data_step, lg_op_lgt, lg_op_lgt_stages,
+ * lg_op_block, lg_op_block_bwd, lg_op_data_step_bwd, lg_op_lgt_bwd, lg_l1_loss, lg_l2_loss, lg_adam_step, lg_optim_step(_ex) and lg_dropout_mask --
+ * held by tests/test_net_abi_cpu.py (every argument one step outside its range, on the host) and tests/test_gpu_net_limits.py (the accepted side at
+ * the bound, on the device).  Arguments are validated before any HIP call, by one shared helper (lgteun_amd/csrc/net_args.h), and lg_last_error
+ * names the entry and the offending argument; a rejected call launches and writes nothing.  -1: null or out of range, -2: unsupported (a defined
+ * flag that does not apply, a shape the plan cannot run), -3: workspace too small.
+ *  - batch: 1 <= B <= B_max(C, K, H, W, train) = min( floor(65535 / C), floor((2^31 - 1) / (S * 16 * C * H * W)) ), with S = K if C = 4, K >= 3,
+ *    H <= 128, W <= 128 and train != 2 (the plans that may run the samples of K stages in one launch), else S = 1.  The first term keeps the B C
+ *    planes of the data step inside a grid's y / z dimension (65535); the second keeps every element index of the largest tensor a launch addresses,
+ *    the FFN's hidden [S B, H, W, 16 C], in a signed 32-bit int.  16 x 16: 16383 (C = 4) / 8191 (C = 8); C = 4, K = 4, 128 x 128: 511; 1024 x 1024:
+ *    31 / 15.  The derivation, site by site, is the comment of lg_net_max_batch in lgteun_amd/csrc/api.hip.  lg_workspace_bytes returns 0 outside the range.
+ *    lg_op_resample: 1 <= planes, hi, wi and hi * wi < 2^27 (the plane count is in no grid dimension; taps are indexed in int inside a plane).
+ *    lg_adam_step / lg_optim_step(_ex): 1 <= n_ranges <= 65535 (a grid's y).  lg_l1_loss / lg_l2_loss / lg_dropout_mask index in 64 bits: any n.
+ *  - alignment: every float tensor (params, grads, inputs, outputs, tmp, the optimizer's state buffers, lg_dropout_mask's out) 16 bytes, `ranges`
+ *    8 bytes, loss_accum / clip_coef / ema 4 bytes.  The network and loss kernels read and write float4 and need it; the optimizer kernels and
+ *    k_dropout_mask index element by element and would take any float -- for them the rule is the uniform contract, not a kernel's need.  The workspace 256 bytes: carve() places every region at a multiple of 256
+ *    bytes from its base and the kernels rely on the regions' alignment, not on the base's.
+ *  - flags: a bit the header does not define (bit 9 and up) is rejected by every entry.  lgteun_forward and lgteun_dead_forward take every defined
+ *    bit but LG_FLAG_BWD_LGT / LG_FLAG_BWD_DATA (dead_forward also needs LG_FLAG_FAITHFUL without LG_FLAG_CHAINED); lgteun_backward takes every
+ *    defined bit, LG_FLAG_BWD_* not together with LG_FLAG_CHAINED; lg_op_lgt takes LG_FLAG_SAVE and LG_FLAG_DROPOUT; lg_op_lgt_stages and lg_op_lgt_bwd
+ *    LG_FLAG_DROPOUT alone.
+ *  - stage in 0 .. K-1 (lg_dropout_mask: 0 .. 15), blk in 0 .. 4, which in 0 .. 2, n in 1 .. K - stage0, grid_cap >= 0. */
 size_t lg_workspace_bytes(const lg_plan* plan, int32_t B, int32_t train);
 
 /* Pansharpening.forward (unlg_former.py:50-67).  seed: dropout counter seed (used with LG_FLAG_DROPOUT). */

@@ -10,6 +10,7 @@
 #include "workspace.h"
 #include "forward.h"
 #include "backward.h"
+#include "net_args.h"
 
 static thread_local char g_err[512] = "";
 
@@ -18,6 +19,61 @@ void lg_set_error(const char* fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the network entries' argument contract (net_args.h; include/lgteun_hip.h states it)
+// ------------------------------------------------------------------------------------------------
+// The largest batch: B_max = min(floor(65535 / C), floor((2^31 - 1) / (S * 16 C * H * W))), S = K for (C = 4, K >= 3, H and W <= 128, train != 2) --
+// a superset of the plans whose dead stages run as one pass (lg_plan_stage_batch), which hand S B samples to one launch -- else 1.  Read off every
+// launcher and kernel a network route reaches; nothing above it was ever launched to find it.  The limiting sites:
+//   planes B C in a grid's y or z, which HIP documents up to 65535 (x: 2^31 - 1):
+//     k_pixel.hip:131       launch_resample_dw: dim3 grid(.., .., a.planes) -- the data step's four forward tile launches (every plan but 64^2 / 128^2)
+//     k_bwd_pixel.hip:101   launch_resample_adj: dim3 grid(.., planes), and the launcher's own refusal of planes > 65535 at :90
+//     k_bwd_pixel.hip:200   resample + depthwise backward: dim3 grid(.., .., a.planes)
+//     k_bwd_pixel.hip:306   the update's backward: dim3 grid(.., .., a.B * a.C)
+//     k_fwd.hip:12, k_bwd.hip:278   const int planes = B * c.C feeds all of them
+//   elements of the largest tensor one launch addresses, the FFN's hidden tensor [S B, H, W, 16 C], in a 32-bit index:
+//     k_ffn_xr.hip:717      launch_ffn_xr refuses a2.B * h * w * N1 >= 2^32 (a2.B = S B in the batched pass): the kernel's 32-bit save index
+//     api.hip               lg_debug_stage_decision refuses Bs * n * h * w >= 2^31: the persistent kernels count pixels and strips in int
+//     k_pixel.hip:621       launch_upfuse: const int grid = a.B * tiles_x * tiles_y;  k_ffn.hip:254 the same;  k_bwd_pixel.hip:766 const int rows = a.B * a.H
+//     k_fft.hip:1220-1288   the FFT mixer: S B 4C planes in grid x, 512 or 1024 threads each -- threads per launch stay below 2^32
+//   Every other product of B in the launchers is taken in long or size_t (k_bwd.hip:30, :122, :198, :347; k_fwd.hip:92, :196, :226; workspace.h).
+// The element bound is signed (2^31) where k_ffn_xr.hip's own is unsigned (2^32): every int index into any tensor of the call stays positive, whichever
+// kernel forms it.  With it 16 x 16 planes give B <= 16383 (C = 4) and 8191 (C = 8) from the grid limit; from 256 x 256 up the element bound is the
+// smaller one (C = 4, K = 4, 128 x 128: 511; 1024 x 1024: 31 / 15).
+int64_t lg_net_max_batch(const lg_config& c, int train) {
+    const int64_t S = (c.C == 4 && c.K >= 3 && c.H <= 128 && c.W <= 128 && train != 2) ? c.K : 1;
+    const int64_t by_grid = 65535 / c.C, by_index = ((1ll << 31) - 1) / (S * 16 * c.C * c.H * c.W);
+    return by_grid < by_index ? by_grid : by_index;
+}
+
+NetArgs& NetArgs::fail(int code, const char* fmt, ...) {
+    char what[400];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(what, sizeof(what), fmt, ap);
+    va_end(ap);
+    lg_set_error("%s: %s", who, what);
+    rc = code;
+    return *this;
+}
+NetArgs& NetArgs::batch(int B, int train) {
+    if (rc) return *this;
+    const long long top = lg_net_max_batch(pl->cfg, train);
+    return (B >= 1 && B <= top) ? *this : fail(-1, "B must be in 1 .. %lld for this plan (got %d)", top, B);
+}
+NetArgs& NetArgs::flags(int fl, int allowed) {
+    if (rc) return *this;
+    if (fl & ~LG_FLAGS_DEFINED) return fail(-1, "flags has bits the header does not define (0x%x)", (unsigned)(fl & ~LG_FLAGS_DEFINED));
+    if (fl & ~allowed) return fail(-2, "flags 0x%x do not apply to this entry (it takes 0x%x)", (unsigned)(fl & ~allowed), (unsigned)allowed);
+    return *this;
+}
+NetArgs& NetArgs::workspace(const void* ws, size_t bytes, int B, int train) {
+    ptr(ws, "workspace").aligned(ws, "workspace", 256);
+    if (rc) return *this;
+    const size_t need = lg_workspace_bytes(pl, B, train);
+    return bytes >= need ? *this : fail(-3, "workspace too small (workspace_bytes %zu < %zu)", bytes, need);
 }
 
 extern "C" const char* lg_version(void) { return "lgteun_hip 0.2 (gfx950)"; }
@@ -82,7 +138,7 @@ extern "C" int lg_plan_describe(const lg_plan* plan, char* buf, size_t n) {
 }
 
 extern "C" size_t lg_workspace_bytes(const lg_plan* plan, int32_t B, int32_t train) {
-    if (!plan || B <= 0 || train < 0 || train > 2) return 0;
+    if (!plan || train < 0 || train > 2 || B <= 0 || B > lg_net_max_batch(plan->cfg, train)) return 0;
     NetBufs nb;
     carve(plan, B, train, nullptr, nb);
     size_t fwd = nb.bytes;
@@ -121,13 +177,13 @@ extern "C" int lg_debug_live_slot(const lg_plan* plan, int32_t B, int32_t train,
 extern "C" int lgteun_backward(const lg_plan* plan, const float* params, float* grads, const float* ms, const float* pan,
                                const float* dout, void* workspace, size_t workspace_bytes, int32_t B, int32_t flags, uint64_t seed,
                                void* stream) {
-    if (!plan || !params || !grads || !ms || !pan || !dout || !workspace || B <= 0) { lg_set_error("backward: null/invalid argument"); return -1; }
-    if ((flags & LG_FLAG_CHAINED) && (flags & (LG_FLAG_BWD_LGT | LG_FLAG_BWD_DATA))) {
-        lg_set_error("backward: LG_FLAG_BWD_LGT / LG_FLAG_BWD_DATA do not apply to LG_FLAG_CHAINED");
-        return -2;
-    }
+    const int train = (flags & LG_FLAG_CHAINED) ? 2 : 1;
+    NetArgs v("backward");
+    v.plan(plan).f32(params, "params").f32(grads, "grads").f32(ms, "ms").f32(pan, "pan").f32(dout, "dout").flags(flags, LG_FLAGS_DEFINED);
+    if (!v.rc && (flags & LG_FLAG_CHAINED) && (flags & (LG_FLAG_BWD_LGT | LG_FLAG_BWD_DATA))) v.fail(-2, "flags: LG_FLAG_BWD_LGT / LG_FLAG_BWD_DATA do not apply to LG_FLAG_CHAINED");
+    if (v.batch(B, train).workspace(workspace, workspace_bytes, B, train).rc) return v.rc;
     NetBufs nb;
-    if (int rc = carve_checked("backward", plan, B, (flags & LG_FLAG_CHAINED) ? 2 : 1, workspace, workspace_bytes, nb)) return rc;
+    carve(plan, B, train, workspace, nb);
     return net_backward(plan, params, grads, ms, pan, dout, nb, (char*)workspace + nb.bytes, B, flags, seed, (hipStream_t)stream);
 }
 
@@ -135,14 +191,21 @@ extern "C" int lgteun_backward(const lg_plan* plan, const float* params, float* 
 // per-op entry points
 // ------------------------------------------------------------------------------------------------
 extern "C" int lg_op_resample(const float* x, float* y, int32_t planes, int32_t hi, int32_t wi, int32_t mode, void* stream) {
-    if (!x || !y || planes <= 0 || hi <= 0 || wi <= 0 || mode < 0 || mode > 2) { lg_set_error("op_resample: invalid argument"); return -1; }
-    if (mode == 0 && ((hi & 1) || (wi & 1))) { lg_set_error("op_resample: x0.5 needs even sizes"); return -2; }
+    // k_pixel.hip:15-38: a one-dimensional grid of at most 4096 workgroups strides over planes * ho * wo outputs in long -- the plane count is in no grid
+    // dimension; inside a plane the taps are indexed in int (common.h: resample_at, yy * wi + x), so a plane holds fewer than 2^31 / 16 inputs
+    NetArgs v("op_resample");
+    v.f32(x, "x").f32(y, "y").range(mode, "mode", 0, 2).range(planes, "planes", 1, 0x7fffffff).range(hi, "hi", 1, 0x7fffffff).range(wi, "wi", 1, 0x7fffffff);
+    if (!v.rc && (long long)hi * wi >= (1ll << 27)) v.fail(-1, "hi * wi must be below 2^27 (got %lld)", (long long)hi * wi);
+    if (!v.rc && mode == 0 && ((hi & 1) || (wi & 1))) v.fail(-2, "hi and wi: x0.5 needs even sizes");
+    if (v.rc) return v.rc;
     return launch_resample(mode, x, y, planes, hi, wi, (hipStream_t)stream);
 }
 
 extern "C" int lg_op_data_step(const lg_plan* plan, const float* params, int32_t stage, const float* z_in, const float* ms,
                                const float* pan, float* z_out, float* tmp, int32_t B, void* stream) {
-    if (!plan || !params || !z_in || !ms || !pan || !z_out || !tmp || stage < 0 || stage >= plan->cfg.K) { lg_set_error("op_data_step: invalid argument"); return -1; }
+    NetArgs v("op_data_step");
+    v.plan(plan).f32(params, "params").stage(stage).f32(z_in, "z_in").f32(ms, "ms").f32(pan, "pan").f32(z_out, "z_out").f32(tmp, "tmp");
+    if (v.batch(B, 0).rc) return v.rc;
     const lg_config& c = plan->cfg;
     size_t q = (size_t)B * c.C * c.H * c.W / 4;
     return data_step_fwd(plan, params, stage, z_in, ms, pan, z_out, tmp, tmp + q, tmp + 2 * q, tmp + 3 * q, B, (hipStream_t)stream);
@@ -150,9 +213,12 @@ extern "C" int lg_op_data_step(const lg_plan* plan, const float* params, int32_t
 
 extern "C" int lg_op_lgt(const lg_plan* plan, const float* params, int32_t stage, const float* z, float* out, void* workspace,
                          size_t workspace_bytes, int32_t B, int32_t flags, uint64_t seed, void* stream) {
-    if (!plan || !params || !z || !out || !workspace || stage < 0 || stage >= plan->cfg.K) { lg_set_error("op_lgt: invalid argument"); return -1; }
+    const int train = (flags & LG_FLAG_SAVE) ? 1 : 0;
+    NetArgs v("op_lgt");
+    v.plan(plan).f32(params, "params").stage(stage).f32(z, "z").f32(out, "out").flags(flags, LG_FLAG_SAVE | LG_FLAG_DROPOUT);
+    if (v.batch(B, train).workspace(workspace, workspace_bytes, B, train).rc) return v.rc;
     NetBufs nb;
-    if (int rc = carve_checked("op_lgt", plan, B, (flags & LG_FLAG_SAVE) ? 1 : 0, workspace, workspace_bytes, nb)) return rc;
+    carve(plan, B, train, workspace, nb);
     nb = live_view(nb);   // a single stage runs where the live stage does: slot K-1 of the transient buffers (workspace.h)
     if (int rc = prep_stages(plan, params, stage, stage + 1, nb, (hipStream_t)stream)) return rc;
     return lgt_fwd(plan, params, stage, z, out, nb, B, flags, seed, (hipStream_t)stream);
@@ -160,11 +226,14 @@ extern "C" int lg_op_lgt(const lg_plan* plan, const float* params, int32_t stage
 
 extern "C" int lg_op_lgt_stages(const lg_plan* plan, const float* params, int32_t stage0, int32_t n, const float* z, float* out, void* workspace,
                                 size_t workspace_bytes, int32_t B, int32_t flags, uint64_t seed, int32_t grid_cap, void* stream) {
-    if (!plan || !params || !z || !out || !workspace || B <= 0 || stage0 < 0 || n < 1 || stage0 + n > plan->cfg.K || grid_cap < 0) { lg_set_error("op_lgt_stages: invalid argument"); return -1; }
-    if (flags & ~LG_FLAG_DROPOUT) { lg_set_error("op_lgt_stages: only LG_FLAG_DROPOUT applies (nothing is saved)"); return -2; }
-    if (n > 1 && (!plan->stage_batch || n > plan->cfg.K - 1)) { lg_set_error("op_lgt_stages: this plan runs one stage per pass (lg_plan_stage_batch), or n > K-1"); return -2; }
+    NetArgs v("op_lgt_stages");
+    v.plan(plan).f32(params, "params");
+    if (!v.rc) v.range(stage0, "stage0", 0, plan->cfg.K - 1).range(n, "n", 1, plan->cfg.K - stage0);
+    v.f32(z, "z").f32(out, "out").range(grid_cap, "grid_cap", 0, 0x7fffffff).flags(flags, LG_FLAG_DROPOUT);
+    if (!v.rc && n > 1 && (!plan->stage_batch || n > plan->cfg.K - 1)) v.fail(-2, "n: this plan runs one stage per pass (lg_plan_stage_batch), or n > K-1");
+    if (v.batch(B, 0).workspace(workspace, workspace_bytes, B, 0).rc) return v.rc;
     NetBufs nb;
-    if (int rc = carve_checked("op_lgt_stages", plan, B, 0, workspace, workspace_bytes, nb)) return rc;
+    carve(plan, B, 0, workspace, nb);
     hipStream_t s = (hipStream_t)stream;
     if (int rc = prep_stages(plan, params, stage0, stage0 + n, nb, s)) return rc;
     return lgt_fwd(plan, params, stage0, z, out, nb, B, flags, seed, s, n, (long)B * plan->cfg.C * plan->cfg.H * plan->cfg.W, grid_cap);
@@ -213,14 +282,13 @@ extern "C" int lg_debug_stage_decision(int32_t kind, int32_t h, int32_t w, int32
 
 extern "C" int lg_op_block(const lg_plan* plan, const float* params, int32_t stage, int32_t blk, int32_t which, const float* x,
                            float* y, void* workspace, size_t workspace_bytes, int32_t B, void* stream) {
-    if (!plan || !params || !x || !y || !workspace || stage < 0 || stage >= plan->cfg.K || blk < 0 || blk > 4 || which < 0 || which > 2) {
-        lg_set_error("op_block: invalid argument");
-        return -1;
-    }
+    NetArgs v("op_block");
+    v.plan(plan).f32(params, "params").stage(stage).range(blk, "blk", 0, LG_NBLK - 1).range(which, "which", 0, 2).f32(x, "x").f32(y, "y");
+    if (v.batch(B, 0).workspace(workspace, workspace_bytes, B, 0).rc) return v.rc;
     hipStream_t s = (hipStream_t)stream;
     NetBufs nb;
     int rc;
-    if ((rc = carve_checked("op_block", plan, B, 0, workspace, workspace_bytes, nb))) return rc;
+    carve(plan, B, 0, workspace, nb);
     nb = live_view(nb);   // a single stage runs where the live stage does: slot K-1 of the transient buffers (workspace.h)
     Blk k = nb.block(plan, params, nullptr, stage, blk);
     BlockBufs& bb = k.b;
@@ -249,15 +317,13 @@ extern "C" int lg_op_block(const lg_plan* plan, const float* params, int32_t sta
 extern "C" int lg_op_block_bwd(const lg_plan* plan, const float* params, float* grads, int32_t stage, int32_t blk, int32_t which,
                                const float* x, const float* dy, float* dx, void* workspace, size_t workspace_bytes, int32_t B,
                                void* stream) {
-    if (!plan || !params || !grads || !x || !dy || !dx || !workspace || stage < 0 || stage >= plan->cfg.K || blk < 0 || blk > 4 ||
-        which < 0 || which > 2) {
-        lg_set_error("op_block_bwd: invalid argument");
-        return -1;
-    }
+    NetArgs v("op_block_bwd");
+    v.plan(plan).f32(params, "params").f32(grads, "grads").stage(stage).range(blk, "blk", 0, LG_NBLK - 1).range(which, "which", 0, 2).f32(x, "x").f32(dy, "dy").f32(dx, "dx");
+    if (v.batch(B, 1).workspace(workspace, workspace_bytes, B, 1).rc) return v.rc;
     hipStream_t s = (hipStream_t)stream;
     NetBufs nb;
     int rc;
-    if ((rc = carve_checked("op_block_bwd", plan, B, 1, workspace, workspace_bytes, nb))) return rc;
+    carve(plan, B, 1, workspace, nb);
     nb = live_view(nb);   // a single stage runs where the live stage does: slot K-1 of the transient buffers (workspace.h)
     Blk k = nb.block(plan, params, grads, stage, blk);
     BlockBufs& bb = k.b;
@@ -278,14 +344,13 @@ extern "C" int lg_op_block_bwd(const lg_plan* plan, const float* params, float* 
 extern "C" int lg_op_data_step_bwd(const lg_plan* plan, const float* params, float* grads, int32_t stage, const float* z_in,
                                    const float* ms, const float* pan, const float* dz_out, float* dz_in, void* workspace,
                                    size_t workspace_bytes, int32_t B, void* stream) {
-    if (!plan || !params || !grads || !z_in || !ms || !pan || !dz_out || !dz_in || !workspace || B <= 0 || stage < 0 || stage >= plan->cfg.K) {
-        lg_set_error("op_data_step_bwd: invalid argument");
-        return -1;
-    }
+    NetArgs v("op_data_step_bwd");
+    v.plan(plan).f32(params, "params").f32(grads, "grads").stage(stage).f32(z_in, "z_in").f32(ms, "ms").f32(pan, "pan").f32(dz_out, "dz_out").f32(dz_in, "dz_in");
+    if (v.batch(B, 1).workspace(workspace, workspace_bytes, B, 1).rc) return v.rc;
     hipStream_t s = (hipStream_t)stream;
     NetBufs nb;
     int rc;
-    if ((rc = carve_checked("op_data_step_bwd", plan, B, 1, workspace, workspace_bytes, nb))) return rc;
+    carve(plan, B, 1, workspace, nb);
     // forward of the step: fills the intermediates its backward reads (t1, r, s1)
     if ((rc = data_step_fwd(plan, params, stage, z_in, ms, pan, nb.Z[stage + 1], nb.t1[stage], nb.r[stage], nb.s1[stage], nb.pr, B, s))) return rc;
     return op_data_step_bwd(plan, params, grads, stage, nb, (char*)workspace + nb.bytes, z_in, pan, dz_out, dz_in, B, s);
@@ -293,15 +358,13 @@ extern "C" int lg_op_data_step_bwd(const lg_plan* plan, const float* params, flo
 
 extern "C" int lg_op_lgt_bwd(const lg_plan* plan, const float* params, float* grads, int32_t stage, const float* z, const float* dout,
                              float* dz, void* workspace, size_t workspace_bytes, int32_t B, int32_t flags, uint64_t seed, void* stream) {
-    if (!plan || !params || !grads || !z || !dout || !dz || !workspace || B <= 0 || stage < 0 || stage >= plan->cfg.K) {
-        lg_set_error("op_lgt_bwd: invalid argument");
-        return -1;
-    }
-    if (flags & ~LG_FLAG_DROPOUT) { lg_set_error("op_lgt_bwd: only LG_FLAG_DROPOUT applies"); return -2; }
+    NetArgs v("op_lgt_bwd");
+    v.plan(plan).f32(params, "params").f32(grads, "grads").stage(stage).f32(z, "z").f32(dout, "dout").f32(dz, "dz").flags(flags, LG_FLAG_DROPOUT);
+    if (v.batch(B, 1).workspace(workspace, workspace_bytes, B, 1).rc) return v.rc;
     hipStream_t s = (hipStream_t)stream;
     NetBufs nb;
     int rc;
-    if ((rc = carve_checked("op_lgt_bwd", plan, B, 1, workspace, workspace_bytes, nb))) return rc;
+    carve(plan, B, 1, workspace, nb);
     nb = live_view(nb);   // a single stage runs where the live stage does: slot K-1 of the transient buffers (workspace.h)
     if ((rc = prep_stages(plan, params, stage, stage + 1, nb, s))) return rc;
     if ((rc = lgt_fwd(plan, params, stage, z, nb.deadout, nb, B, flags | LG_FLAG_SAVE, seed, s))) return rc;

@@ -10,4 +10,3 @@ int block_mixer_fwd(const Blk& k, int B, int flags, uint64_t seed, hipStream_t s
 int block_ffn_fwd(const Blk& k, const Blk* next, int B, int flags, hipStream_t s, const StageSel& sg = StageSel());
 int lgt_fwd(const lg_plan* pl, const float* P, int stage, const float* z, float* out, const NetBufs& nb, int B, int flags, uint64_t seed,
             hipStream_t s, int nst = 1, long zstride = 0, int grid_cap = 0, float* live_out = nullptr);
-int carve_checked(const char* who, const lg_plan* plan, int B, int train, void* workspace, size_t workspace_bytes, NetBufs& nb);

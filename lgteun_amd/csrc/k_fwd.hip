@@ -4,6 +4,7 @@
 
 #include "abi.h"
 #include "forward.h"
+#include "net_args.h"
 
 int data_step_fwd(const lg_plan* pl, const float* P, int stage, const float* z_in, const float* ms, const float* pan,
                   float* z_out, float* t1, float* r, float* s1, float* pr, int B, hipStream_t s) {
@@ -241,22 +242,13 @@ static int dead_stages(const lg_plan* pl, const float* P, const NetBufs& nb, int
     return 0;
 }
 
-// the workspace of entry `who` carved into nb, or -3 if the caller's is too small for (plan, B, train)
-int carve_checked(const char* who, const lg_plan* plan, int B, int train, void* workspace, size_t workspace_bytes, NetBufs& nb) {
-    if (workspace_bytes < lg_workspace_bytes(plan, B, train)) { lg_set_error("%s: workspace too small", who); return -3; }
-    carve(plan, B, train, workspace, nb);
-    return 0;
-}
-
 extern "C" int lgteun_forward(const lg_plan* plan, const float* params, const float* ms, const float* pan, float* out,
                               void* workspace, size_t workspace_bytes, int32_t B, int32_t flags, uint64_t seed, void* stream) {
-    if (!plan || !params || !ms || !pan || !out || !workspace || B <= 0) { lg_set_error("forward: null/invalid argument"); return -1; }
     const bool chained = (flags & LG_FLAG_CHAINED) != 0;
     const int train = (flags & LG_FLAG_SAVE) ? (chained ? 2 : 1) : 0;
-    if (workspace_bytes < lg_workspace_bytes(plan, B, train)) {   // (the one entry that reports both sizes)
-        lg_set_error("forward: workspace too small (%zu < %zu)", workspace_bytes, lg_workspace_bytes(plan, B, train));
-        return -3;
-    }
+    NetArgs v("forward");
+    v.plan(plan).f32(params, "params").f32(ms, "ms").f32(pan, "pan").f32(out, "out").flags(flags, LG_FLAGS_FORWARD);
+    if (v.batch(B, train).workspace(workspace, workspace_bytes, B, train).rc) return v.rc;
     hipStream_t s = (hipStream_t)stream;
     const lg_config& c = plan->cfg;
     NetBufs nb;
@@ -297,10 +289,13 @@ extern "C" int lgteun_forward(const lg_plan* plan, const float* params, const fl
 
 extern "C" int lgteun_dead_forward(const lg_plan* plan, const float* params, void* workspace, size_t workspace_bytes, int32_t B,
                                    int32_t flags, uint64_t seed, void* stream) {
-    if (!plan || !params || !workspace || B <= 0) { lg_set_error("dead_forward: null/invalid argument"); return -1; }
-    if ((flags & LG_FLAG_CHAINED) || !(flags & LG_FLAG_FAITHFUL)) { lg_set_error("dead_forward: only the faithful unfolding has dead stages"); return -2; }
+    const int train = (flags & LG_FLAG_SAVE) ? 1 : 0;
+    NetArgs v("dead_forward");
+    v.plan(plan).f32(params, "params").flags(flags, LG_FLAGS_FORWARD);
+    if (!v.rc && ((flags & LG_FLAG_CHAINED) || !(flags & LG_FLAG_FAITHFUL))) v.fail(-2, "flags: only the faithful unfolding has dead stages");
+    if (v.batch(B, train).workspace(workspace, workspace_bytes, B, train).rc) return v.rc;
     NetBufs nb;
-    if (int rc = carve_checked("dead_forward", plan, B, (flags & LG_FLAG_SAVE) ? 1 : 0, workspace, workspace_bytes, nb)) return rc;
+    carve(plan, B, train, workspace, nb);
     if (int rc = prep_stages(plan, params, 0, plan->cfg.K - 1, nb, (hipStream_t)stream)) return rc;
     return dead_stages(plan, params, nb, B, flags, seed, (hipStream_t)stream);
 }

@@ -4,6 +4,7 @@
 
 #include "abi.h"
 #include "common.h"
+#include "net_args.h"
 
 // ------------------------------------------------------------------------------------------------
 // Adam (torch.optim.Adam single-tensor semantics) over ranges of the flat buffers
@@ -43,6 +44,20 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float
     }
 }
 
+// What every optimizer entry checks first (the network entries' argument contract, include/lgteun_hip.h): the flat buffers are float tensors -- not null
+// where the entry always reads them, 16-byte aligned (the contract's uniform rule for float tensors; these kernels themselves would take any float) --, `ranges` holds int64 pairs, and n_ranges is the grid's y (k_adam / k_optim: dim3 grid(gx, n_ranges)),
+// which HIP documents up to 65535.  Inside a range the kernels index element by element in int64, so a range may begin at any float.
+static int optim_args_ok(const char* who, const float* params, const float* grads, const float* s0, const float* s1, const float* s2, const int64_t* ranges,
+                         int32_t n_ranges, int32_t step) {
+    NetArgs v(who);
+    auto need = [&](const void* p, const char* name) { if (!v.rc && !p) v.fail(-1, "invalid argument: %s is NULL", name); };
+    need(params, "params"); need(grads, "grads"); need(ranges, "ranges");
+    v.aligned(params, "params", 16).aligned(grads, "grads", 16).aligned(s0, "state0", 16).aligned(s1, "state1", 16).aligned(s2, "state2", 16).aligned(ranges, "ranges", 8);
+    if (!v.rc && (n_ranges < 1 || n_ranges > 65535)) v.fail(-1, "invalid argument: n_ranges must be in 1 .. 65535 (got %d)", n_ranges);
+    if (!v.rc && step < 1) v.fail(-1, "invalid argument: step must be at least 1 (got %d)", step);
+    return v.rc;
+}
+
 // lg_adam_step, and the plain-Adam route of lg_optim_step_ex: the same scalars, rounded at the same places
 static int launch_adam(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* ranges, int32_t n_ranges,
                        int64_t max_range, int32_t step, float lr, float beta1, float beta2, float eps, float grad_scale, const ctl_args& c,
@@ -69,7 +84,8 @@ static int launch_adam(float* params, const float* grads, float* exp_avg, float*
 extern "C" int lg_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* ranges,
                             int32_t n_ranges, int64_t max_range, int32_t step, float lr, float beta1, float beta2, float eps,
                             float grad_scale, void* stream) {
-    if (!params || !grads || !exp_avg || !exp_avg_sq || !ranges || n_ranges <= 0 || step < 1) { lg_set_error("adam_step: invalid argument"); return -1; }
+    if (int rc = optim_args_ok("adam_step", params, grads, exp_avg, exp_avg_sq, nullptr, ranges, n_ranges, step)) return rc;
+    if (!exp_avg || !exp_avg_sq) { lg_set_error("adam_step: invalid argument: %s is NULL", !exp_avg ? "exp_avg" : "exp_avg_sq"); return -1; }
     return launch_adam(params, grads, exp_avg, exp_avg_sq, ranges, n_ranges, max_range, step, lr, beta1, beta2, eps, grad_scale,
                        ctl_args{nullptr, nullptr, 0.f}, (hipStream_t)stream);
 }
@@ -173,8 +189,9 @@ static void launch_optim(dim3 grid, hipStream_t st, float* p, const float* g, fl
 static int optim_step(float* params, const float* grads, float* state0, float* state1, float* state2, const int64_t* ranges,
                       int32_t n_ranges, int64_t max_range, int32_t step, int32_t algo, int32_t flags, double lr, double h0, double h1,
                       double eps, double weight_decay, double grad_scale, const ctl_args& c, void* stream) {
-    if (!params || !grads || !ranges || n_ranges <= 0 || step < 1 || algo < LG_OPT_ADAM || algo > LG_OPT_RMSPROP ||
-        (flags & ~(LG_OPT_AMSGRAD | LG_OPT_NESTEROV | LG_OPT_CENTERED))) { lg_set_error("optim_step: invalid argument"); return -1; }
+    if (int rc = optim_args_ok("optim_step", params, grads, state0, state1, state2, ranges, n_ranges, step)) return rc;
+    if (algo < LG_OPT_ADAM || algo > LG_OPT_RMSPROP) { lg_set_error("optim_step: invalid argument: algo must be in 0 .. 3 (got %d)", algo); return -1; }
+    if (flags & ~(LG_OPT_AMSGRAD | LG_OPT_NESTEROV | LG_OPT_CENTERED)) { lg_set_error("optim_step: invalid argument: flags has bits the header does not define (0x%x)", (unsigned)flags); return -1; }
     const bool adam = algo == LG_OPT_ADAM || algo == LG_OPT_ADAMW;
     const int own = adam ? LG_OPT_AMSGRAD : (algo == LG_OPT_SGD ? LG_OPT_NESTEROV : LG_OPT_CENTERED);
     if (flags & ~own) { lg_set_error("optim_step: the flag belongs to another algorithm"); return -1; }
@@ -185,7 +202,10 @@ static int optim_step(float* params, const float* grads, float* state0, float* s
     // the state buffers this option set reads and writes
     const bool need0 = algo != LG_OPT_SGD || (opt & OPT_MOM), need1 = adam || (algo == LG_OPT_RMSPROP && (opt & OPT_MOM));
     const bool need2 = algo != LG_OPT_SGD && (opt & OPT_ALT);
-    if ((need0 && !state0) || (need1 && !state1) || (need2 && !state2)) { lg_set_error("optim_step: a state buffer of this option set is missing"); return -1; }
+    if ((need0 && !state0) || (need1 && !state1) || (need2 && !state2)) {
+        lg_set_error("optim_step: %s is NULL: a state buffer of this option set is missing", (need0 && !state0) ? "state0" : ((need1 && !state1) ? "state1" : "state2"));
+        return -1;
+    }
     // the scalars are torch's Python floats: every derived one is taken in fp64 and rounded to fp32 once, where torch hands it to a tensor op
     optim_args a = {(float)lr, (float)h0, (float)h1, (float)(1.0 - h0), (float)(1.0 - h1), (float)eps, (float)weight_decay, (float)grad_scale,
                     1.f, 1.f};
@@ -240,7 +260,8 @@ extern "C" int lg_optim_step_ex(float* params, const float* grads, float* state0
         lg_set_error("optim_step_ex: plain_adam is algo LG_OPT_ADAM without weight decay and amsgrad");
         return -1;
     }
-    if (!params || !grads || !state0 || !state1 || !ranges || n_ranges <= 0 || step < 1) { lg_set_error("optim_step_ex: invalid argument"); return -1; }
+    if (int rc = optim_args_ok("optim_step_ex", params, grads, state0, state1, nullptr, ranges, n_ranges, step)) return rc;
+    if (!state0 || !state1) { lg_set_error("optim_step_ex: invalid argument: %s is NULL", !state0 ? "state0" : "state1"); return -1; }
     // lg_adam_step takes its scalars as floats: round them first, so that the bias corrections see what that entry point sees
     return launch_adam(params, grads, state0, state1, ranges, n_ranges, max_range, step, (float)lr, (float)h0, (float)h1, (float)eps,
                        (float)grad_scale, c, (hipStream_t)stream);

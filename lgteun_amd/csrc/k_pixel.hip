@@ -7,6 +7,7 @@
 #include "kernels.h"
 #include "resample_tile.h"
 #include "workspace.h"   // LG_MAX_K (lg_dropout_mask)
+#include "net_args.h"
 
 // ------------------------------------------------------------------------------------------------
 // plain bicubic resample of planes (bmu.sampling_, basic_module_unformer_v2.py:21-23)
@@ -721,7 +722,11 @@ __global__ __launch_bounds__(256) void k_dropout_mask(uint64_t seed, long first,
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += gridDim.x * 256L) out[i] = dropout_scale(seed, (uint64_t)(first + i));
 }
 extern "C" int lg_dropout_mask(uint64_t seed, int32_t stage, int32_t blk, int64_t first, int64_t n, float* out, void* stream) {
-    if (!out || n < 0 || first < 0 || stage < 0 || stage >= LG_MAX_K || blk < 0 || blk > 4) { lg_set_error("dropout_mask: invalid argument"); return -1; }
+    // a one-dimensional grid of at most 1024 workgroups, every index in long (k_dropout_mask): first + n only has to stay an int64
+    NetArgs v("dropout_mask");
+    v.f32(out, "out").range(stage, "stage", 0, LG_MAX_K - 1).range(blk, "blk", 0, LG_NBLK - 1).range(first, "first", 0, INT64_MAX);
+    if (!v.rc) v.range(n, "n", 0, INT64_MAX - first);   // (behind the check of `first`: the difference cannot overflow)
+    if (v.rc) return v.rc;
     if (n == 0) return 0;
     const int grid = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
     k_dropout_mask<<<grid, 256, 0, (hipStream_t)stream>>>(mix_seed(seed, stage, blk), first, n, out);

@@ -23,6 +23,7 @@
 #include "abi.h"
 #include "common.h"
 #include "reduce.h"
+#include "net_args.h"
 
 namespace {
 
@@ -312,8 +313,12 @@ __device__ __forceinline__ void rl_stream_diff(const float* __restrict__ out, co
 
 // what lg_l1_loss / lg_l2_loss check; the grid of k_l1 / k_l2, 0 when an argument is not taken
 int rl_flat_grid(const char* who, const float* out, const float* gt, const float* dout, const float* loss_accum, int64_t n_local, int64_t n_global) {
-    if (!out || !gt || !dout || !loss_accum || n_local <= 0 || n_global <= 0) { lg_set_error("%s: invalid argument", who); return 0; }
-    if (((uintptr_t)out | (uintptr_t)gt | (uintptr_t)dout) & 15) { lg_set_error("%s: tensors must be 16-byte aligned", who); return 0; }
+    // at most 256 workgroups, every index in long (k_l1, k_l2): no bound on n_local beyond int64
+    NetArgs v(who);
+    v.f32(out, "out").f32(gt, "gt").f32(dout, "dout").ptr(loss_accum, "loss_accum").aligned(loss_accum, "loss_accum", 4);
+    if (!v.rc && n_local <= 0) v.fail(-1, "n_local must be positive (got %lld)", (long long)n_local);
+    if (!v.rc && n_global <= 0) v.fail(-1, "n_global must be positive (got %lld)", (long long)n_global);
+    if (v.rc) return 0;
     const int64_t grid = (n_local / 4 + 255) / 256;
     return (int)(grid > 256 ? 256 : (grid < 1 ? 1 : grid));
 }

@@ -80,6 +80,13 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _aligned(t):
+    """`t` as the library takes a float tensor: contiguous and 16-byte aligned (the kernels read float4).  A contiguous view that starts inside a
+    storage -- base[1:] of a flat buffer -- is copied to a tensor of its own, like scene.py's inputs; the caller's storage is only read"""
+    t = t.contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
 class TrainControls:
     """What a training run asks for around the optimizer of the fused step; attached with `optimizer.set_controls(...)`, or by the runner
     from `cfg.train_cfg`.  Everything is off by default, and an optimizer without controls steps exactly as it always did.
@@ -335,8 +342,8 @@ class Engine:
     # ------------------------------------------------------------------------------------------
     def forward_raw(self, ms, pan, flags, seed=0, lease=False):
         B, H, W = self._check_inputs(ms, pan)
-        ms = ms.contiguous()
-        pan = pan.contiguous()
+        ms = _aligned(ms)
+        pan = _aligned(pan)
         plan = self.plan(H, W)
         train = (2 if flags & LG_FLAG_CHAINED else 1) if flags & LG_FLAG_SAVE else 0
         if lease:
@@ -352,7 +359,7 @@ class Engine:
 
     def backward_raw(self, saved, dout, gflat, flags, seed=0):
         plan, ws, ms, pan, B = saved[:5]
-        dout = dout.contiguous()
+        dout = _aligned(dout)
         check(self.lib.lgteun_backward(plan, _ptr(self.flat), _ptr(gflat), _ptr(ms), _ptr(pan), _ptr(dout), _ptr(ws),
                                        ws.numel(), B, flags, seed, _stream_ptr()), 'lgteun_backward')
 
@@ -431,7 +438,7 @@ class Engine:
         out, saved = self.forward_raw(ms, pan, flags, seed)
         dout = torch.empty_like(out)
         if gt is not None:
-            gt = gt.contiguous()
+            gt = _aligned(gt)
         if rec:
             n_local = out.numel()
             loss_fn = self.lib.lg_l1_loss if loss_type == 'l1' else self.lib.lg_l2_loss
@@ -506,7 +513,7 @@ class Engine:
         if pan_l.dim() != 4 or tuple(pan_l.shape) != (B, 1, H // 4, W // 4) or pan_l.dtype != torch.float32 or pan_l.device != self.device:
             raise ValueError(f"pan_l (the batch's 'input_pan_l') must be float32 [B,1,h,w] = {(B, 1, H // 4, W // 4)} on {self.device}, got "
                              f'{pan_l.dtype} {tuple(pan_l.shape)} on {pan_l.device}')
-        pan_l = pan_l.contiguous()
+        pan_l = _aligned(pan_l)
         bufs = self._qnr_bufs.get((B, H, W))
         if bufs is None:
             need = int(self.lib.lg_qnr_workspace_bytes(B, C, H, W))

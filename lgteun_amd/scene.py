@@ -106,10 +106,14 @@ def _to_device(a, device, what):
 
 
 def auto_batch(engine, plan, C, th, tw, n_tiles, free_bytes):
-    """the largest B <= min(64, n_tiles) whose inference workspace plus tile tensors fit into half of `free_bytes` (at least 1)"""
+    """the largest B <= min(64, n_tiles) that the plan accepts -- lg_workspace_bytes is 0 for a batch above the plan's bound (include/lgteun_hip.h:
+    31 tiles of 1024 x 1024 at C = 4, 15 at C = 8) -- and whose inference workspace plus tile tensors fit into half of `free_bytes` (at least 1)"""
     per_tile = 4 * (th * tw + C * (th // 4) * (tw // 4) + C * th * tw)
     B = max(1, min(MAX_AUTO_BATCH, int(n_tiles)))
-    while B > 1 and int(engine.lib.lg_workspace_bytes(plan, B, 0)) + B * per_tile > free_bytes // 2:
+    while B > 1:
+        need = int(engine.lib.lg_workspace_bytes(plan, B, 0))
+        if need > 0 and need + B * per_tile <= free_bytes // 2:
+            break
         B -= 1
     return B
 

@@ -55,6 +55,60 @@ def distinct_gains(n, seed=0):
     return g[np.random.default_rng(seed).permutation(n)]
 
 
+# ------------------------------------------------------------------------------------------------------------------------
+# the network entries (tests/test_net_abi_cpu.py, tests/test_gpu_net_limits.py): the header's batch bound restated, plans made on the host
+# ------------------------------------------------------------------------------------------------------------------------
+F_FAITHFUL, F_SAVE, F_DROPOUT, F_BWD_LGT, F_BWD_DATA, F_CHAINED, F_DEFER_DEAD, F_STAGEWISE, F_LIVE_APART = 1, 2, 4, 8, 16, 32, 64, 128, 256
+F_DEFINED = 0x1ff
+F_UNDEFINED_BIT = 1 << 9
+GRID_YZ_MAX, INT_MAX = 65535, TWO31 - 1
+
+
+def net_stage_slots(C, K, H, W, train):
+    """S of include/lgteun_hip.h: the stages whose samples one launch may see"""
+    return K if (C == 4 and K >= 3 and H <= 128 and W <= 128 and train != 2) else 1
+
+
+def net_max_batch(C, K, H, W, train):
+    """include/lgteun_hip.h, "The network entries' argument contract": B_max = min(floor(65535 / C), floor((2^31 - 1) / (S 16 C H W)))"""
+    return min(GRID_YZ_MAX // C, INT_MAX // (net_stage_slots(C, K, H, W, train) * 16 * C * H * W))
+
+
+class NetPlan:
+    """lg_plan_create on the host (no device): precision 0, the product routes, offsets of 4 i floats as tests/test_route_cpu.py uses them"""
+
+    def __init__(self, C, K, H, W):
+        from lgteun_amd import _lib
+        self.lib, self.C, self.K, self.H, self.W = _lib.lib(), C, K, H, W
+        n = 12 + K + 119 * K
+        offs = (ctypes.c_int64 * n)(*[4 * i for i in range(n)])
+        self.handle = ctypes.c_void_p()
+        cfg = _lib.LgConfig(C, K, H, W, 0, 0)
+        rc = self.lib.lg_plan_create(ctypes.byref(cfg), offs, n, ctypes.byref(self.handle))
+        assert rc == 0, (rc, self.lib.lg_last_error())
+
+    def bound(self, train):
+        return net_max_batch(self.C, self.K, self.H, self.W, train)
+
+    def ws(self, B, train):
+        return int(self.lib.lg_workspace_bytes(self.handle, B, train))
+
+    def parts(self, B, train):
+        """(bytes of the forward carving, bytes of the backward's part behind it) from lg_debug_live_slot; their sum is lg_workspace_bytes"""
+        out = (ctypes.c_size_t * 53)()
+        assert self.lib.lg_debug_live_slot(self.handle, B, train, out) == 0, self.lib.lg_last_error()
+        return int(out[0]), int(out[1])
+
+    def describe(self):
+        buf = ctypes.create_string_buffer(2048)
+        assert self.lib.lg_plan_describe(self.handle, buf, len(buf)) == 0, self.lib.lg_last_error()
+        return buf.value.decode()
+
+    def __del__(self):
+        if self.handle:
+            self.lib.lg_plan_destroy(self.handle)
+
+
 def scene_offset(elem, H, W):
     """element offset of a [planes, H, W] array -> (plane, row, column)"""
     plane, r = divmod(elem, H * W)
